@@ -98,8 +98,16 @@ def parse_args(argv=None):
                     help="concurrent m-block groups per GPU (threads x HIP streams); 2 gave +7 %% m-blocks/s in round 2, "
                          "and is slower since the two-stage tridiagonalisation (937 against 1020: the persistent chase kernels of "
                          "the groups compete for the same CUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="configs1: after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float64, at most %d MB in all; see dump_outputs)" % (DUMP_BYTES // 10**6))
     ap.add_argument("--cpu-worker", nargs=2, metavar=("JOBS", "NPROC"), help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "configs1":
+        ap.error("--dump-outputs is only implemented for --workload configs1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -204,7 +212,8 @@ def hot_path_step(tel, bt, kl, ctx, stage_times=None, streams=1, m_range=None, c
     the device.  After the beam-transfer generation the m-blocks are dealt round-robin into `streams` groups,
     each driven by its own thread / libdriftmi context / HIP stream.  With `collect` the spectra of all ranks are
     gathered to rank 0 (beamtransfer.py:931-947, kltransform.py:452-478) and a per-rank band matrix is all-reduced
-    (the pattern of the Fisher assembly, psestimation.py:506-507)."""
+    (the pattern of the Fisher assembly, psestimation.py:506-507).  Returns (m, singular values (host), KL product) for
+    every m-block of the pass; the SVD products of each m stay in `bt._dev[m]`."""
     import numpy as np
     import torch
 
@@ -264,7 +273,56 @@ def hot_path_step(tel, bt, kl, ctx, stage_times=None, streams=1, m_range=None, c
     if stage_times is not None:
         tsvd = max(p[0] for p in parts)
         stage_times.append((t1 - t0, tsvd, (t3 - t1) - tsvd, tcoll))
-    return parts[0][2]
+    return [(mi, p[3][i], p[2][i]) for g, p in zip(groups, parts) for i, mi in enumerate(g)]
+
+
+DUMP_BYTES = 64 * 10**6   # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20     # --dump-outputs: complex elements kept of each large product
+DUMP_SEED = 0
+
+
+def dump_outputs(outdir, bt, products):
+    """Write what one pass of `hot_path_step` computed (`products`, its return value) to `outdir` as float64 .npy files,
+    so that two builds can be compared output for output on the same inputs:
+
+      m                  the m-blocks of the pass (rank 0's at --gpus > 1), ascending
+      singular_values    (nm, nfreq, svd_len) of every m-block
+      kl_ndof            KL degrees of freedom of every m-block
+      kl_evals           the KL eigenvalues of every m-block, concatenated in m order
+      beam_svd, beam_ut  the SVD products, and
+      kl_evecs           the KL eigenvectors (rows below the S/N threshold are zero):
+                         a fixed sample of DUMP_SAMPLE elements, drawn with DUMP_SEED over the flattened blocks of all m
+                         concatenated in m order, ascending; (DUMP_SAMPLE, 2) = (real, imaginary)."""
+    import numpy as np
+    import torch
+
+    products = sorted(products, key=lambda r: r[0])
+    ms = [r[0] for r in products]
+    out = {"m": np.asarray(ms, dtype=np.float64),
+           "singular_values": np.stack([np.asarray(r[1]) for r in products]),
+           "kl_ndof": np.asarray([r[2][0].numel() for r in products], dtype=np.float64),
+           "kl_evals": torch.cat([r[2][0].reshape(-1) for r in products]).cpu().numpy()}
+    large = {"beam_svd": [bt._dev[m]["beam_svd"] for m in ms], "beam_ut": [bt._dev[m]["beam_ut"] for m in ms],
+             "kl_evecs": [r[2][1] for r in products]}
+    for name, blocks in large.items():
+        ends = np.cumsum([b.numel() for b in blocks])
+        total = int(ends[-1])
+        pick = np.arange(total)
+        if total > DUMP_SAMPLE:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_SAMPLE, replace=False))
+        which = np.searchsorted(ends, pick, side="right")
+        vals = []
+        for i in np.unique(which):
+            local = pick[which == i] - (ends[i] - blocks[i].numel())
+            vals.append(blocks[i].reshape(-1)[torch.as_tensor(local, device=blocks[i].device)])
+        out[name] = torch.view_as_real(torch.cat(vals)).cpu().numpy()
+    assert all(a.dtype == np.float64 for a in out.values()), {k: a.dtype for k, a in out.items()}
+    nbytes = sum(a.nbytes for a in out.values())
+    assert nbytes <= DUMP_BYTES, nbytes
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return nbytes
 
 
 def run_job(args):
@@ -428,11 +486,14 @@ def main():
         _BUSY[0] = 0.0
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            hot_path_step(tel, bt, kl, ctx, streams=args.streams, m_range=m_range, collect=collect)
+            last = hot_path_step(tel, bt, kl, ctx, streams=args.streams, m_range=m_range, collect=collect)
         torch.cuda.synchronize()
         t_own = _BUSY[0]                      # this rank's own K steps: BT-gen + SVD + KL, without the waits in the collectives
         parallel.barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:   # before the untimed passes below replace the SVD products in bt._dev
+            dump_outputs(args.dump_outputs, bt, last)
+        del last
         prof = {}
         for c in list(device._all):
             for k, v in c.prof_report().items():

@@ -356,6 +356,36 @@ def gen_pixel_kernels(ref):
     print("pixel_kernels.npz")
 
 
+def gen_pixel_kernels_seeded(ref):
+    """The compiled Cython kernels on the seeds of
+    tests/test_oracle_btgen.py::test_pixel_kernels_live_against_the_compiled_reference_extension,
+    at HEALPix pixel counts that exercise the OpenMP reduction of the solid angles.  The
+    test regenerates the inputs from the seeds; stored are a seeded sample of at most 128
+    pixels per seed: their inputs (to pin the streams) and the kernels' outputs there."""
+    ft = ref["fast_tools"]
+    out = {}
+    for seed, n in ((11, 1), (12, 257), (13, 12 * 32 * 32)):
+        rng = np.random.default_rng(seed)
+        ap = np.stack([np.arccos(rng.uniform(-1, 1, n)), rng.uniform(0, 2 * np.pi, n)], axis=-1)
+        zen = np.array([np.pi / 2.0 - np.radians(rng.uniform(20.0, 60.0)), 0.0])
+        uv = rng.uniform(-40.0, 40.0, 2)
+        st = rng.uniform(-1, 1, n)
+        bx, by = rng.standard_normal((n, 2)), rng.standard_normal((n, 2))
+        pix = np.sort(np.random.default_rng(1000 + seed).choice(n, min(n, 128), replace=False))
+        fr = ft.fringe(ap, zen, uv)
+        p = "s%d_" % seed
+        out.update({p + "pix": pix, p + "zenith": zen, p + "uv": uv, p + "angpos": ap[pix], p + "exptan_in": st[pix],
+                    p + "beam_x": bx[pix], p + "beam_y": by[pix], p + "fringe": fr[pix],
+                    p + "exptan": ft.beam_exptan(st, 0.9)[pix]})
+        hz = ref["visibility"].horizon(ap, zen).astype(np.float64)
+        if hz.sum() == 0:
+            continue
+        out[p + "pol_real"] = ft._construct_pol_real(bx, by, fr, hz)[:, pix]
+        out[p + "pol_complex"] = ft._construct_pol_complex(bx * np.exp(0.3j), by * np.exp(-0.7j), fr, hz)[:, pix]
+    np.savez_compressed(os.path.join(OUT, "pixel_kernels_seeded.npz"), **out)
+    print("pixel_kernels_seeded.npz")
+
+
 def _telescope_cases(ref):
     """(name, constructor) of the reference's other telescope classes (drift/telescope/*.py, examples/disharray)."""
     import importlib
@@ -807,10 +837,14 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "timestream":
         gen_timestream(ref)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "pixel_seeded":
+        gen_pixel_kernels_seeded(ref)
+        return
     gen_matrix_ops(ref)
     gen_eigh_gen(ref)
     gen_geometry(ref)
     gen_pixel_kernels(ref)
+    gen_pixel_kernels_seeded(ref)
     gen_projections(ref)
     # moderately conditioned pencils (cond(N) ~ 1e5): 1e-10 parity is attainable by any
     # backward-stable solver

@@ -16,8 +16,12 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def test_config5_real_block_through_kl():
+def test_config5_real_block_through_kl(monkeypatch):
     import bench
+
+    # measure_configs4_block keeps the products in HBM by setting DRIFTMI_STORAGE=discard for the whole process; the
+    # host tests that sort after this file write product files in the same session
+    monkeypatch.setenv("DRIFTMI_STORAGE", "discard")
 
     def log(*a):
         print(time.strftime("%H:%M:%S"), *a, flush=True)

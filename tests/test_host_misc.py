@@ -264,7 +264,7 @@ def test_exchange_single_process():
     assert parallel.partition_for(range(7), 1, 3) == [3, 4] and parallel.partition_for(range(2), 2, 3) == []
 
 
-def _fisher_worker(rank, world, port, q, nm, resident):
+def _fisher_worker(rank, world, port, q, nm, resident, outdir):
     """One rank of a Fisher assembly with a stand-in per-m estimator (the per-m matrices need the GPU; the partition logic
     and the all-reduce do not)."""
     import os
@@ -286,7 +286,7 @@ def _fisher_worker(rank, world, port, q, nm, resident):
 
     class _KL:
         beamtransfer = _BT()
-        evdir = "/nonexistent"
+        evdir = outdir
 
         class telescope:
             mmax = nm - 1
@@ -312,7 +312,7 @@ def _fisher_worker(rank, world, port, q, nm, resident):
 
 
 @pytest.mark.parametrize("resident", [True, False])
-def test_fisher_assembly_with_more_ranks_than_m_blocks(resident):
+def test_fisher_assembly_with_more_ranks_than_m_blocks(resident, tmp_path):
     """world_size 4 over 3 m-blocks (gloo): `partition_contiguous` leaves a rank without a block; every m must enter the
     all-reduced Fisher matrix exactly once, whether the rank accumulated during the resident pipeline or not."""
     import torch.multiprocessing as mp
@@ -321,7 +321,7 @@ def test_fisher_assembly_with_more_ranks_than_m_blocks(resident):
     q = ctx.Queue()
     port = 31000 + (os.getpid() % 2000) + (7 if resident else 0)
     nm, world = 3, 4
-    ps = [ctx.Process(target=_fisher_worker, args=(r, world, port, q, nm, resident)) for r in range(world)]
+    ps = [ctx.Process(target=_fisher_worker, args=(r, world, port, q, nm, resident, str(tmp_path))) for r in range(world)]
     for p in ps:
         p.start()
     res = sorted(q.get(timeout=180) for _ in ps)

@@ -32,33 +32,49 @@ def test_pixel_kernels_vs_reference(pk):
     assert np.abs(outr - pk["pol_real_xy"]).max() <= 1e-13 * np.abs(pk["pol_real_xy"]).max()
 
 
-def test_pixel_kernels_live_against_the_compiled_reference_extension():
-    """oracle/_ref holds the reference's OWN native extension (drift/util/_fast_tools.pyx compiled by oracle/Makefile; a
-    binary, git-ignored, it travels to the GPU box): the restated pixel kernels against it on seeds the fixture does not
-    hold, at HEALPix pixel counts that exercise the OpenMP reduction."""
+def test_pixel_kernels_live_against_the_compiled_reference_extension(golden_dir):
+    """The restated pixel kernels against the reference's OWN native extension (drift/util/_fast_tools.pyx) on seeds
+    pixel_kernels.npz does not hold, at HEALPix pixel counts that exercise the OpenMP reduction of the solid angles.
+    The extension's outputs at a seeded sample of pixels are stored in tests/golden/pixel_kernels_seeded.npz
+    (oracle/gen_golden.py); where oracle/_ref is built (by oracle/Makefile, from the reference tree) the extension is
+    also run live on every pixel."""
     from oracle import refimport
 
+    g = np.load(os.path.join(golden_dir, "pixel_kernels_seeded.npz"))
     ft = refimport.load_fast_tools()
-    if ft is None:
-        pytest.skip("oracle/_ref not built (make -C oracle ref needs the reference tree)")
     for seed, n in ((11, 1), (12, 257), (13, 12 * 32 * 32)):
         rng = np.random.default_rng(seed)
         ap = np.stack([np.arccos(rng.uniform(-1, 1, n)), rng.uniform(0, 2 * np.pi, n)], axis=-1)
         zen = np.array([np.pi / 2.0 - np.radians(rng.uniform(20.0, 60.0)), 0.0])
         uv = rng.uniform(-40.0, 40.0, 2)
-        fr = ft.fringe(ap, zen, uv)
-        assert np.abs(ob.fringe(ap, zen, uv) - fr).max() < 1e-11
         st = rng.uniform(-1, 1, n)
-        assert np.abs(ob.beam_exptan(st, 0.9) - ft.beam_exptan(st, 0.9)).max() < 1e-15
-        hz = ob.horizon(ap, zen).astype(np.float64)
         bx, by = rng.standard_normal((n, 2)), rng.standard_normal((n, 2))
-        if hz.sum() == 0:
-            continue
-        ref = ft._construct_pol_real(bx, by, fr, hz)
-        assert np.abs(ob.construct_pol_real(bx, by, fr, hz) - ref).max() <= 1e-12 * np.abs(ref).max()
+        p = "s%d_" % seed
+        pix = g[p + "pix"]
+        # the seeded streams still give the inputs the stored outputs were computed from
+        for k, a in (("zenith", zen), ("uv", uv), ("angpos", ap[pix]), ("exptan_in", st[pix]), ("beam_x", bx[pix]),
+                     ("beam_y", by[pix])):
+            assert np.array_equal(a, g[p + k]), k
+        hz = ob.horizon(ap, zen).astype(np.float64)
         bxc, byc = bx * np.exp(0.3j), by * np.exp(-0.7j)
-        refc = ft._construct_pol_complex(bxc, byc, fr, hz)
-        assert np.abs(ob.construct_pol_complex(bxc, byc, fr, hz) - refc).max() <= 1e-12 * np.abs(refc).max()
+        fr = ob.fringe(ap, zen, uv)
+        got = dict(fringe=fr, exptan=ob.beam_exptan(st, 0.9))
+        if hz.sum() > 0:
+            got.update(pol_real=ob.construct_pol_real(bx, by, fr, hz), pol_complex=ob.construct_pol_complex(bxc, byc, fr, hz))
+        refs = [(pix, {k: g[p + k] for k in ("fringe", "exptan", "pol_real", "pol_complex") if p + k in g})]
+        if ft is not None:
+            frl = ft.fringe(ap, zen, uv)
+            refs.append((np.arange(n), dict(fringe=frl, exptan=ft.beam_exptan(st, 0.9))))
+            if hz.sum() > 0:
+                refs[-1][1].update(pol_real=ft._construct_pol_real(bx, by, frl, hz),
+                                   pol_complex=ft._construct_pol_complex(bxc, byc, frl, hz))
+        for sel, ref in refs:
+            assert set(ref) == set(got)
+            assert np.abs(got["fringe"][sel] - ref["fringe"]).max() < 1e-11
+            assert np.abs(got["exptan"][sel] - ref["exptan"]).max() < 1e-15
+            for k in ("pol_real", "pol_complex"):
+                if k in ref:
+                    assert np.abs(got[k][:, sel] - ref[k]).max() <= 1e-12 * np.abs(ref[k]).max(), k
 
 
 def test_cylinder_beams_vs_reference(pk):

@@ -8,7 +8,7 @@ import pytest
 from oracle import kl as okl
 from oracle import svdchain as osvd
 
-from parity_util import assert_same_rowspace, assert_spectrum, relerr
+from parity_util import assert_same_rowspace, assert_spectrum, pencil_tol, relerr
 
 
 @pytest.fixture(scope="module")
@@ -121,7 +121,9 @@ def test_doublekl(svdkl):
         evals, evecs, f_evals, ac = okl.doublekl_transform_m(
             lambda th: _sn(g, pre, use_thermal=th), foreground_threshold=float(g["fg_threshold"])
         )
-        assert_spectrum(f_evals, g[pre + "dk_f_evals"], 1e-10, "f_evals")
+        # stage 1 solves the pencil without thermal noise (cond(N) up to ~1e11 here): its spectrum agrees across LAPACK
+        # builds, CPU kernels and thread counts only to eps * cond(N) (parity_util.pencil_tol)
+        assert_spectrum(f_evals, g[pre + "dk_f_evals"], pencil_tol(_sn(g, pre, use_thermal=False)[1]), "f_evals")
         assert evals.shape == g[pre + "dk_evals"].shape
         assert_spectrum(evals, g[pre + "dk_evals"], 1e-8, "dk evals")
         if evals.size and evals.size < f_evals.size:
@@ -176,8 +178,13 @@ def test_eigh_gen(golden_dir):
     g = np.load(os.path.join(golden_dir, "eigh_gen.npz"))
     for case in ("pd", "npd", "zero"):
         ev, evec, ac = okl.eigh_gen(g[case + "_A"], g[case + "_B"])
-        assert_spectrum(ev, g[case + "_evals"], 1e-10, case)
-        assert np.isclose(ac, float(g[case + "_ac"]), rtol=1e-6, atol=0.0) or ac == float(g[case + "_ac"])
+        B = g[case + "_B"] + ac * np.eye(g[case + "_B"].shape[0])   # the pencil solved: the npd rescue shifts B
+        assert_spectrum(ev, g[case + "_evals"], pencil_tol(B), case)
+        # a rescue shift comes from the smallest eigenvalue of a numerically singular B, known to eps * ||B|| (absolute);
+        # no shift must stay exactly no shift
+        ac_ref = float(g[case + "_ac"])
+        atol = 50.0 * np.finfo(np.float64).eps * np.abs(g[case + "_B"]).sum(axis=1).max() if ac_ref else 0.0
+        assert ac == ac_ref or np.isclose(ac, ac_ref, rtol=1e-6, atol=atol)
     assert float(g["npd_ac"]) > 0.0
 
 
