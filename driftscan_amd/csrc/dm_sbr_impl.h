@@ -12,10 +12,13 @@
 //       The trailing matrix is read 3 times per 32 columns instead of once per column: 5-10 x fewer HBM
 //       bytes than the one-stage reduction (8 n^3 / 3 bytes), which is HBM-bound at 0.5 of the roofline.
 //   S2  band -> real tridiagonal: sweep s annihilates column s below the sub-diagonal and chases the bulge
-//       down the band with reflectors of length <= 32 (sb_chase_kernel).  One WAVE runs one sweep; a 32 x 32
-//       block lives in the registers of the wave as 4 x 4 sub-blocks per lane (row and column reductions are
-//       three butterfly steps each); sweep s + 1 follows sweep s two blocks behind, synchronised through
-//       progress words (LDS within a workgroup, agent-scope flags across workgroups for one large matrix).
+//       down the band with reflectors of length <= 32.  A 32 x 32 block lives in the registers of a wave as
+//       4 x 4 sub-blocks per lane (row and column reductions are three butterfly steps each).  By default the
+//       chase goes BY BAND POSITION (sb_chase_pos_kernel): a pair of waves owns one block position of a matrix
+//       (the E wave the off-diagonal block, the D wave the diagonal one) and every sweep passes through it,
+//       neighbouring positions handing over through LDS or tagged global mailboxes.  A matrix too large for all
+//       of its positions to be resident at once is chased by sweep-owning wave pairs instead (sb_chase2_kernel):
+//       sweep s + 1 follows sweep s two blocks behind, synchronised through progress words.
 //   B2  X = Q2 Z: the n^2 / 64 short reflectors are applied by sb_q2_apply_kernel to column slabs of X that
 //       stay in registers while a group of sweeps passes over them (VALU fp64 — as fast as the fp64 MFMA on
 //       this part — with no T factors and no padding flops); slabs are independent, no inter-workgroup sync.
@@ -56,9 +59,6 @@ struct sb_mat {
   cplx* Yp;     // (n / SQR + 1) x SB: partial dot products v_q^H P[:, c]
   double* Np;   // 2 x (n / SQR + 1): partial norms (double-buffered over q)
   int npstride; // n / SQR + 1
-  cplx* Rb;     // look-ahead only (else NULL): n x SB, row c holds the part of R of column c that lies beyond its diagonal
-                // block, A[c][i0 ..] with i0 = (c / SB + 1) SB — the trailing update of the previous panel is still
-                // writing the rows of A this panel would put it in
 };
 
 // ---- S1: launched panel QR (any size; two launches per column, all matrices in lock-step) ----------------------
@@ -471,10 +471,7 @@ __device__ __forceinline__ void sb_fused_half(const sb_mat& M, cplx (&a)[SFR][SF
         dm_stg(M.Vp, (size_t)qq * n + i, v[r]);
         dm_stg(M.Vp2, (size_t)qq * n + i, v[r]);
         dm_stg(M.Vt, (size_t)(k0 + qq) * n + i, v[r]);
-        if (M.Rb) {
-          if (has ? i <= lead : i - i0 < SB)
-            dm_stg(M.Rb, (size_t)(k0 + qq) * SB + (i - i0), (!has || i < lead) ? cconj(a[r][0]) : make_double2(R.beta, 0.0));
-        } else if (has) {
+        if (has) {
           if (i <= lead) dm_stg(M.A, (size_t)(k0 + qq) * M.lda + i, i < lead ? cconj(a[r][0]) : make_double2(R.beta, 0.0));
         } else {
           dm_stg(M.A, (size_t)(k0 + qq) * M.lda + i, cconj(a[r][0]));
@@ -492,9 +489,7 @@ __device__ __forceinline__ void sb_fused_half(const sb_mat& M, cplx (&a)[SFR][SF
   }
 }
 
-// snap != 0: the panel is read from the snapshot M.Pw (row q = column k0 + q, already updated by the previous panel's
-// reflectors: the look-ahead copy made before that panel's trailing update started) instead of from A.
-__global__ __launch_bounds__(SFT) void sb_panel_fused_kernel(const sb_mat* __restrict__ ms, int k0, int a0, int snap) {
+__global__ __launch_bounds__(SFT) void sb_panel_fused_kernel(const sb_mat* __restrict__ ms, int k0, int a0) {
   const sb_mat M = ms[blockIdx.x];
   const int n = M.n;
   const int m = n - k0 - SB;
@@ -523,8 +518,7 @@ __global__ __launch_bounds__(SFT) void sb_panel_fused_kernel(const sb_mat* __res
       const int i = i0 + tid + SFT * r;
 #pragma unroll
       for (int c = 0; c < SFH; ++c)
-        a[r][c] = (i < n) ? cconj(snap ? dm_ldg(M.Pw, (size_t)(cb + c) * n + i) : dm_ldg(M.A, (size_t)(k0 + cb + c) * M.lda + i))
-                          : make_double2(0.0, 0.0);
+        a[r][c] = (i < n) ? cconj(dm_ldg(M.A, (size_t)(k0 + cb + c) * M.lda + i)) : make_double2(0.0, 0.0);
     }
     // ---- the reflectors of the earlier sub-panels: a_c <- a_c - conj(tau_q) v_q (v_q^H a_c), q = 0 .. cb - 1 in turn
     __syncthreads();  // their vectors are in memory (this workgroup wrote them: L1 holds no older copy)
@@ -665,19 +659,8 @@ __global__ __launch_bounds__(256) void sb_s_kernel(const sb_s_desc* __restrict__
   }
 }
 
-// look-ahead: snapshot of the rows [i0, i0 + SB) of A at the columns >= i0 + SB (the next panel, as the trailing update of
-// the previous panel left it) into Pw; the grouped product that follows applies the current panel's update to the copy
-__global__ __launch_bounds__(256) void sb_strip_copy_kernel(const sb_mat* __restrict__ ms, int i0) {
-  const sb_mat M = ms[blockIdx.z];
-  const int q = blockIdx.y;
-  const int c = i0 + SB + blockIdx.x * 256 + threadIdx.x;
-  if (c >= M.n || i0 + q >= M.n) return;
-  dm_stg(M.Pw, (size_t)q * M.n + c, dm_ldg(M.A, (size_t)(i0 + q) * M.lda + c));
-}
-
 // band extraction: AB[c][i] = A_math[c + i][c] = conj(C[c][c + i]), i <= SB; the bulge rows start at zero
-// (rows c < nrb: the entries beyond the diagonal block of c come from the look-ahead's R buffer, see sb_mat::Rb)
-struct sb_bmat { const cplx* A; int lda; int n; cplx* AB; const cplx* Rb; int nrb; };
+struct sb_bmat { const cplx* A; int lda; int n; cplx* AB; };
 __global__ __launch_bounds__(256) void sb_band_extract_kernel(const sb_bmat* __restrict__ ms) {
   const sb_bmat M = ms[blockIdx.y];
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -685,16 +668,14 @@ __global__ __launch_bounds__(256) void sb_band_extract_kernel(const sb_bmat* __r
   const int c = (int)(idx / SLD), i = (int)(idx % SLD);
   cplx v = make_double2(0.0, 0.0);
   if (i <= SB && c + i < M.n) {
-    const int i0 = (c / SB + 1) * SB;
-    if (M.Rb && c < M.nrb && c + i >= i0) v = cconj(dm_ldg(M.Rb, (size_t)c * SB + (c + i - i0)));
-    else v = cconj(dm_ldg(M.A, (size_t)c * M.lda + c + i));
+    v = cconj(dm_ldg(M.A, (size_t)c * M.lda + c + i));
     if (i == 0) v.y = 0.0;
   }
   dm_stg(M.AB, idx, v);
 }
 
-// The back-transformation reads every diamond block (G, j), j < nb(G) = (n - 2 - G SBG) / SB + 1, whole.  The paired
-// chase writes complete rows, and a sweep of a full group reaches every block j <= nb(G) - 3 with a full-length vector;
+// The back-transformation reads every diamond block (G, j), j < nb(G) = (n - 2 - G SBG) / SB + 1, whole.  Both chase
+// kernels write complete rows, and a sweep of a full group reaches every block j <= nb(G) - 3 with a full-length vector;
 // what it may leave untouched lies in the last two blocks of a group (short or missing vectors at the end of the matrix)
 // and in the last group (missing sweeps): those are cleared here, 64 KB per group instead of the whole n^2 array.
 __global__ __launch_bounds__(256) void sb_vd_tail_zero_kernel(const struct sb_chase_mat* __restrict__ ms);
@@ -741,301 +722,19 @@ constexpr unsigned long long SB_WAIT_TICKS = 30ull * 100000000ull;
 #endif
 
 typedef unsigned int sb_u4 __attribute__((ext_vector_type(4)));
-// sc1 loads: served by the XCD's L2, bypassing the vector L1 of this CU (element index in units of cplx / dwords)
+// sc1 loads: served by the XCD's L2, bypassing the vector L1 of this CU (element index in units of cplx)
 __device__ __forceinline__ cplx sb_ld(__amdgpu_buffer_rsrc_t rs, unsigned idx) {
   const sb_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, idx * 16u, 0, 16);
   cplx w;
   __builtin_memcpy(&w, &v, 16);
   return w;
 }
-__device__ __forceinline__ unsigned sb_ld_u32(__amdgpu_buffer_rsrc_t rs, unsigned idx) {
-  return __builtin_amdgcn_raw_buffer_load_b32(rs, idx * 4u, 0, 16);
-}
-
-// One sweep of the chase by one wave.  A 32 x 32 block lives in the wave as 4 x 4 values per lane with INTERLEAVED
-// ownership: lane (br, bc) = (lane >> 3, lane & 7) holds the rows br + 8 a and the columns bc + 8 b — eight lanes
-// with consecutive br read 128 contiguous bytes of a band column, so every load instruction moves whole lines.
-__device__ __forceinline__ void sb_chase_sweep(const sb_chase_mat& M, __amdgpu_buffer_rsrc_t rsAB, int* err, int s, int lane) {
-  const int n = M.n;
-  const int br = lane >> 3, bc = lane & 7;
-  cplx* AB = M.AB;
-  const int G = s / SBG, gi = s % SBG;
-  unsigned seen = (s == 0) ? SB_DONE : 0u;  // tasks of sweep s - 1 known to be finished
-  cplx vrow[4], vcol[4];  // the current reflector by the rows / the columns of this lane
-  cplx tau = make_double2(0.0, 0.0);
-  for (int j = 0;; ++j) {
-    const int r0 = s + 1 + j * SB;  // first row of R_j
-    if (r0 >= n) break;
-    const int nr = min(SB, n - r0);
-    // ---- wait for sweep s - 1 to have finished task j + 1
-    if (seen < (unsigned)(j + 2)) {
-      // (an atomic load: a plain one would be hoisted out of the loop; agent scope = sc1 = served by L2)
-      int spins = 0;
-      bool bail = false;
-      const unsigned long long t_wait0 = wall_clock64();
-      for (;;) {
-        const unsigned v = __hip_atomic_load(M.prog + (s - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v >= (unsigned)(j + 2)) { seen = v; break; }
-        __builtin_amdgcn_s_sleep(1);
-        // never in a correct run: every wave leaves instead of hanging the GPU (the host reports the failure).  The
-        // limit is WALL time (SB_WAIT_TICKS of the 100 MHz counter), not a poll count: a predecessor that was
-        // descheduled for a while (another process on the card, clock throttling) is not a failure
-        ++spins;
-        if ((spins & 1023) == 0 && wall_clock64() - t_wait0 > SB_WAIT_TICKS) {
-          if (lane == 0) atomicCAS(err, 0, 1 + s + (j << 12) + ((int)(v & 0xff) << 20));  // first failure wins
-          bail = true;
-        }
-        if ((spins & 1023) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) bail = true;
-        if (bail) {
-          if (lane == 0) __hip_atomic_store(M.prog + s, 0x40000000u | ((unsigned)j << 8) | (v & 0xffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          return;
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // keeps the band loads below behind the poll
-    }
-    bool reflect = true;
-    double beta = 0.0;
-    if (j == 0) {
-      // ---- task 0: reflector from column s
-      cplx x[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) x[a] = sb_ld(rsAB, (unsigned)s * SLD + 1u + (unsigned)(br + 8 * a));
-      if (lane == 0) M.d[s] = sb_ld(rsAB, (unsigned)s * SLD).x;
-      double sq = 0.0;
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-        if (br + 8 * a > 0) sq += cabs2(x[a]);
-      cplx t = sb_sum_br(make_double2(sq, 0.0));
-      const double xn2 = __shfl(t.x, 0, 64);
-      const cplx alpha = sb_from_lane(x[0], 0);
-      const trd_refl R = sb_reflector(xn2, alpha);
-      tau = R.tau;
-      beta = R.beta;
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int rr = br + 8 * a;
-        cplx v = cmul(x[a], R.scal);
-        if (rr == 0) v = make_double2(1.0, 0.0);
-        if (rr >= nr) v = make_double2(0.0, 0.0);
-        vrow[a] = v;
-      }
-      if (bc == 0) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const int rr = br + 8 * a;
-          if (rr < nr) dm_stg(AB, (size_t)s * SLD + 1 + rr, rr == 0 ? make_double2(beta, 0.0) : make_double2(0.0, 0.0));
-        }
-      }
-      if (lane == 0) M.e[s] = beta;
-    } else {
-      // ---- E <- E H_{j-1}, new reflector from its first column, E <- H_j^H E
-      const int c0 = r0 - SB;
-      cplx e[4][4];
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb) {
-        const int c = c0 + bc + 8 * bb;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const int r = r0 + br + 8 * a;
-          e[a][bb] = sb_ld(rsAB, (unsigned)c * SLD + (unsigned)(r - c));
-        }
-      }
-      cplx w[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        cplx acc = make_double2(0.0, 0.0);
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) sb_cfma(acc, e[a][bb], vcol[bb]);
-        w[a] = cmul(tau, sb_sum_bc(acc));
-      }
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) sb_cfms_cb(e[a][bb], w[a], vcol[bb]);
-      reflect = nr >= 2;
-      cplx tauj = make_double2(0.0, 0.0);
-      cplx vnew[4];
-      if (reflect) {
-        double sq = 0.0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          if (br + 8 * a > 0 && br + 8 * a < nr) sq += cabs2(e[a][0]);
-        if (bc != 0) sq = 0.0;
-        cplx t = sb_sum_br(make_double2(sq, 0.0));
-        const double xn2 = __shfl(t.x, 0, 64);
-        const cplx alpha = sb_from_lane(e[0][0], 0);
-        const trd_refl R = sb_reflector(xn2, alpha);
-        tauj = R.tau;
-        beta = R.beta;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const int rr = br + 8 * a;
-          cplx x = sb_from_lane(e[a][0], lane & ~7);  // column 0 of the block lives in the lanes bc == 0
-          cplx v = cmul(x, R.scal);
-          if (rr == 0) v = make_double2(1.0, 0.0);
-          if (rr >= nr) v = make_double2(0.0, 0.0);
-          vnew[a] = v;
-        }
-        cplx y[4];
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          cplx acc = make_double2(0.0, 0.0);
-#pragma unroll
-          for (int a = 0; a < 4; ++a) sb_cfma_ca(acc, vnew[a], e[a][bb]);
-          y[bb] = cmul(cconj(tauj), sb_sum_br(acc));
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int bb = 0; bb < 4; ++bb) sb_cfms(e[a][bb], vnew[a], y[bb]);
-        if (bc == 0) {
-#pragma unroll
-          for (int a = 0; a < 4; ++a) e[a][0] = (br + 8 * a == 0) ? make_double2(beta, 0.0) : make_double2(0.0, 0.0);
-        }
-      }
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb) {
-        const int c = c0 + bc + 8 * bb;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const int r = r0 + br + 8 * a;
-          if (r < n) dm_stg(AB, (size_t)c * SLD + (r - c), e[a][bb]);
-        }
-      }
-      tau = tauj;
-#pragma unroll
-      for (int a = 0; a < 4; ++a) vrow[a] = reflect ? vnew[a] : make_double2(0.0, 0.0);
-    }
-    if (reflect) {
-      // the Hermitian diagonal block D_j (loaded once E_j is on its way out: both blocks at once do not fit the registers
-      // of two waves per SIMD)
-      cplx d[4][4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int r = r0 + br + 8 * a;
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          const int c = r0 + bc + 8 * bb;
-          d[a][bb] = (r >= c) ? sb_ld(rsAB, (unsigned)c * SLD + (unsigned)(r - c)) : sb_ld(rsAB, (unsigned)r * SLD + (unsigned)(c - r));
-        }
-      }
-      // ---- store the reflector (lanes bc == 0 hold it by rows)
-      const size_t blk = (size_t)G * M.jb + j;
-      if (bc == 0) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const int rr = br + 8 * a;
-          if (rr < nr) dm_stg(M.Vd, (blk * SBG + gi) * SBW + gi + rr, vrow[a]);
-        }
-      }
-      if (lane == 0) M.tau2[blk * SBG + gi] = tau;
-      // the same vector by columns: lane (br, bc) wants v[bc + 8 b] = vrow[b] of the lanes br' = bc
-#pragma unroll
-      for (int a = 0; a < 4; ++a) vcol[a] = sb_from_lane(vrow[a], bc * 8);
-      // ---- D <- H^H D H on the Hermitian diagonal block (zhetd2's x, w recurrences)
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int r = br + 8 * a;
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          const int c = bc + 8 * bb;
-          if (r < c) d[a][bb] = cconj(d[a][bb]);
-          if (r == c) d[a][bb].y = 0.0;
-        }
-      }
-      cplx x[4];
-      cplx xv = make_double2(0.0, 0.0);
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        cplx acc = make_double2(0.0, 0.0);
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) sb_cfma(acc, d[a][bb], vcol[bb]);
-        x[a] = cmul(tau, sb_sum_bc(acc));
-        // x^H v over the rows of this lane (the same in all lanes that share the rows)
-        sb_cfma_ca(xv, x[a], vrow[a]);
-      }
-      xv = sb_sum_br(xv);
-      const cplx al = cmul(make_double2(-0.5 * tau.x, -0.5 * tau.y), xv);
-      cplx wv[4], wc[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) wv[a] = cadd(x[a], cmul(al, vrow[a]));
-#pragma unroll
-      for (int a = 0; a < 4; ++a) wc[a] = sb_from_lane(wv[a], bc * 8);
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int r = r0 + br + 8 * a;
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          const int c = r0 + bc + 8 * bb;
-          if (r < n && c <= r) {
-            cplx v = d[a][bb];
-            sb_cfms_cb(v, vrow[a], wc[bb]);
-            sb_cfms_cb(v, wv[a], vcol[bb]);
-            if (r == c) v.y = 0.0;
-            dm_stg(AB, (size_t)c * SLD + (r - c), v);
-          }
-        }
-      }
-    }
-    // ---- publish: task j of sweep s is finished (the stores have reached L2)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_store(M.prog + s, (unsigned)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!reflect) break;
-  }
-  // ---- sweep finished
-  if (s == n - 2 && lane == 0) M.d[n - 1] = sb_ld(rsAB, (unsigned)(n - 1) * SLD).x;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_store(M.prog + s, SB_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void sb_chase_kernel(const sb_chase_mat* __restrict__ ms, const sb_chase_ctl ctl) {
-  const int lane = threadIdx.x & 63;
-  const int xcd = __builtin_amdgcn_s_getreg(6164) & 7;  // hwreg(HW_REG_XCC_ID, 0, 4)
-  __shared__ int s_mat;
-  for (int qq = 0; qq < 8; ++qq) {
-    const int q = (xcd + qq) & 7;
-    const int qlen = ctl.qoff[q + 1] - ctl.qoff[q];
-    for (;;) {
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        int m = -1;
-        const int ent = atomicAdd(ctl.qhead + q, 1);
-        if (ent < qlen) {
-          m = ctl.qent[ctl.qoff[q] + ent];
-          const int old = atomicCAS(ms[m].owner, -1, xcd);
-          if (old != -1 && old != xcd) m = -2;  // claimed by another XCD
-        }
-        s_mat = m;
-      }
-      __syncthreads();
-      const int m = s_mat;
-      if (m == -1) break;
-      if (m == -2) continue;
-      const sb_chase_mat M = ms[m];
-      if (M.n == 1) {
-        if (threadIdx.x == 0) M.d[0] = dm_ldg(M.AB, 0).x;
-        continue;
-      }
-      const __amdgpu_buffer_rsrc_t rsAB =
-          __builtin_amdgcn_make_buffer_rsrc((void*)M.AB, 0, (int)min((size_t)M.n * SLD * sizeof(cplx), (size_t)0x7fffffff), 0x00020000);
-      for (;;) {
-        int s = 0;
-        if (lane == 0) s = atomicAdd(M.next, 1);
-        s = __builtin_amdgcn_readfirstlane(s);
-        if (s >= M.n - 1) break;
-        if (__hip_atomic_load(ctl.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-        const unsigned long long t0 = wall_clock64();
-        sb_chase_sweep(M, rsAB, ctl.err, s, lane);
-        if (ctl.dbg && lane == 0) { ctl.dbg[2 * s] = t0; ctl.dbg[2 * s + 1] = wall_clock64(); }
-      }
-    }
-  }
-}
 
 // ---- S2, two waves per sweep -------------------------------------------------------------------------------------------
+//
+// A 32 x 32 block lives in a wave as 4 x 4 values per lane with INTERLEAVED ownership: lane (br, bc) = (lane >> 3, lane & 7)
+// holds the rows br + 8 a and the columns bc + 8 b — eight lanes with consecutive br read 128 contiguous bytes of a band
+// column, so every load instruction moves whole lines.
 //
 // Inside a sweep the reflectors form a chain  E_j -> v_j -> E_{j+1}  that never reads the diagonal blocks; D_j only needs
 // v_j.  So a sweep is run by a PAIR of waves of one workgroup: the E wave walks the chain and posts each reflector in an
@@ -1340,7 +1039,7 @@ __device__ __forceinline__ bool sb_chase_D(const sb_chase_mat& M, __amdgpu_buffe
   return true;
 }
 
-// NP pairs of waves per workgroup (wave 2 p = E, wave 2 p + 1 = D); queues and ownership as in sb_chase_kernel
+// NP pairs of waves per workgroup (wave 2 p = E, wave 2 p + 1 = D); queues and XCD ownership as described at sb_chase_ctl
 template <int NP>
 __global__ __launch_bounds__(128 * NP) void sb_chase2_kernel(const sb_chase_mat* __restrict__ ms, const sb_chase_ctl ctl) {
   const int lane = threadIdx.x & 63;
@@ -2040,15 +1739,14 @@ struct sb_q2_mat {
   int slab0;                           // first slab (of 16 columns) id of this matrix in the launch
 };
 
-// LPC = lanes per column of X: 4 (16 columns per wave, 9 rows of a reflector per lane) or 8 (8 columns per wave, 5 rows per
-// lane: twice the waves for the same X — the choice when the columns alone cannot fill the chip)
-template <int NW, int LPC>
+template <int NW>
 __global__ __launch_bounds__(64 * NW) void sb_q2_apply_kernel(const sb_q2_mat* __restrict__ ms, const int2* __restrict__ wgs) {
   // wgs[blockIdx.x] = (matrix, first slab of this workgroup)
   const int2 wg = wgs[blockIdx.x];
   const sb_q2_mat M = ms[wg.x];
   const int n = M.n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int LPC = 4;                 // lanes per column of X
   constexpr int NCW = 64 / LPC;          // columns per wave
   constexpr int NRL = SB / LPC + 1;      // rows of one reflector a lane can meet
   const int col = (wg.y + wave) * NCW + lane / LPC;
@@ -2129,10 +1827,6 @@ __global__ __launch_bounds__(64 * NW) void sb_q2_apply_kernel(const sb_q2_mat* _
         cplx acc = cadd(cadd(a[0], a[1]), a[2]);
         acc.x = sb_quad_sum(acc.x);
         acc.y = sb_quad_sum(acc.y);
-        if (LPC == 8) {
-          acc.x += dm_dpp_f64<0x141>(acc.x);   // row_half_mirror: the other quad of the eight lanes
-          acc.y += dm_dpp_f64<0x141>(acc.y);
-        }
         const cplx f = cmul(tq, acc);  // H x = x - tau v (v^H x)
 #pragma unroll
         for (int t = 0; t < NRL; ++t) sb_cfms(xw[iq + t], v[t], f);

@@ -1531,56 +1531,32 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
   for (int p = 0; p < np; ++p) scm[p] = dc_scale_mat{dd + offn[p], ee + offn[p], probs[p].n, dscale + p};
   dc_scale_mat* d_scm = dm_ws_upload(ctx, scm);
   if (!d_scm) return DM_ENOMEM;
-  static const bool dc_noscale = getenv("DM_DC_NOSCALE") != nullptr;
-  if (!dc_noscale) DM_PLAUNCH(ctx, DM_PROF_DC, dc_scale_kernel, dim3(np), dim3(256), 0, ctx->stream, d_scm);
+  DM_PLAUNCH(ctx, DM_PROF_DC, dc_scale_kernel, dim3(np), dim3(256), 0, ctx->stream, d_scm);
 
-  // ---- tear at every leaf boundary, then solve the leaves with the QL kernels
+  // ---- tear at every leaf boundary, then solve the leaves (at most DC_LEAF rows) with the in-LDS QL kernel
   {
     std::vector<dc_tear> tears;
     std::vector<ql_mat> qm;
-    std::vector<rot_mat> rm;
-    size_t totsw = 0, totrot = 0;
+    std::vector<int> leafmat;
     int maxleaf = 0;
     for (int p = 0; p < np; ++p) {
       const int n = probs[p].n, D = depth[p];
       if (n == 0) continue;
       for (int i = 0; i < (1 << D); ++i) {
-        const int lo = bound(p, D, i), hi = bound(p, D, i + 1);
-        if (i > 0) tears.push_back(dc_tear{dd + offn[p], ee + offn[p], lo});
-        const int nl = hi - lo;
-        maxleaf = std::max(maxleaf, nl);
-        totsw += 4 * (size_t)nl + 8;
-        totrot += 2 * (size_t)nl * nl + 8;
-      }
-    }
-    int* sw_dir = dm_ws_alloc_t<int>(ctx, std::max<size_t>(totsw, 1));
-    int* sw_lo = dm_ws_alloc_t<int>(ctx, std::max<size_t>(totsw, 1));
-    int* sw_cnt = dm_ws_alloc_t<int>(ctx, std::max<size_t>(totsw, 1));
-    long long* sw_off = dm_ws_alloc_t<long long>(ctx, std::max<size_t>(totsw, 1));
-    double2* rot = dm_ws_alloc_t<double2>(ctx, std::max<size_t>(totrot, 1));
-    size_t so = 0, ro = 0;
-    std::vector<int> leafmat;
-    for (int p = 0; p < np; ++p) {
-      const int n = probs[p].n, D = depth[p];
-      if (n == 0) continue;
-      for (int i = 0; i < (1 << D); ++i) {
         const int lo = bound(p, D, i), hi = bound(p, D, i + 1), nl = hi - lo;
+        if (i > 0) tears.push_back(dc_tear{dd + offn[p], ee + offn[p], lo});
+        maxleaf = std::max(maxleaf, nl);
         leafmat.push_back(p);
-        qm.push_back(ql_mat{dd + offn[p] + lo, ee + offn[p] + lo, nl, sw_dir + so, sw_lo + so, sw_cnt + so, sw_off + so,
-                            rot + ro, 4 * nl + 8, 2LL * nl * nl + 8, nullptr, nullptr, ZA + off[p] + (size_t)lo * n + lo, n});
-        rm.push_back(rot_mat{ZA + off[p] + (size_t)lo * n + lo, nl, n, sw_dir + so, sw_lo + so, sw_cnt + so,
-                             sw_off + so, rot + ro, nullptr});
-        so += 4 * (size_t)nl + 8;
-        ro += 2 * (size_t)nl * nl + 8;
+        qm.push_back(ql_mat{dd + offn[p] + lo, ee + offn[p] + lo, nl, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                            nullptr, nullptr, ZA + off[p] + (size_t)lo * n + lo, n});
       }
     }
     const int nleaf = (int)qm.size();
     int* nsw = dm_ws_alloc_t<int>(ctx, std::max(nleaf, 1));
     int* stat = dm_ws_alloc_t<int>(ctx, std::max(nleaf, 1));
-    if (!sw_dir || !sw_lo || !sw_cnt || !sw_off || !rot || !nsw || !stat) return DM_ENOMEM;
+    if (!nsw || !stat) return DM_ENOMEM;
     for (int i = 0; i < nleaf; ++i) {
       qm[i].nsweeps = nsw + i; qm[i].status = stat + i;
-      rm[i].nsweeps = nsw + i;
     }
     if (!tears.empty()) {
       dc_tear* d_t = dm_ws_upload(ctx, tears);
@@ -1590,25 +1566,10 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
     }
     if (nleaf > 0) {
       ql_mat* d_qm = dm_ws_upload(ctx, qm);
-      rot_mat* d_rm = dm_ws_upload(ctx, rm);
-      if (!d_qm || !d_rm) return DM_ENOMEM;
-      static bool attr = false;
-      if (!attr) {
-        DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(ql_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-        attr = true;
-      }
-      static const bool leaf_apply = !getenv("DM_QL_LEAF_RECORD");
-      if (leaf_apply && maxleaf <= 64) {
-        // rotations applied in LDS as they are generated (d, e and the n x n Z of a leaf: 16 n + 8 n^2 bytes)
-        DM_PLAUNCH(ctx, DM_PROF_DC, (ql_kernel<true, true>), dim3(nleaf), dim3(64), (size_t)maxleaf * 16 + (size_t)maxleaf * maxleaf * 8,
-                           ctx->stream, d_qm);
-      } else {
-        DM_PLAUNCH(ctx, DM_PROF_DC, ql_kernel<true>, dim3(nleaf), dim3(64), (size_t)maxleaf * 16, ctx->stream, d_qm);
-        DM_PLAUNCH(ctx, DM_PROF_DC, zt_identity_kernel, dim3((maxleaf + 255) / 256, maxleaf, nleaf), dim3(256), 0, ctx->stream,
-                           d_rm);
-        DM_PLAUNCH(ctx, DM_PROF_DC, rot_apply_kernel, dim3((maxleaf + 255) / 256, nleaf), dim3(256), 0, ctx->stream, d_rm);
-      }
+      if (!d_qm) return DM_ENOMEM;
+      // rotations applied in LDS as they are generated (d, e and the n x n Z of a leaf: 16 n + 8 n^2 bytes)
+      DM_PLAUNCH(ctx, DM_PROF_DC, (ql_kernel<true, true>), dim3(nleaf), dim3(64), (size_t)maxleaf * 16 + (size_t)maxleaf * maxleaf * 8,
+                         ctx->stream, d_qm);
       DM_HIP(ctx, hipGetLastError());
       std::vector<int> hs(nleaf);
       DM_TRY(dm_download(ctx, hs.data(), stat, sizeof(int) * nleaf));
@@ -1696,36 +1657,18 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
     if (inB && probs[p].n > 0) cp.push_back(dm_cdesc{lamB + offn[p], dd + offn[p], sizeof(double) * probs[p].n});
   }
   DM_TRY(dm_copy_batched(ctx, cp));
-  if (!dc_noscale) DM_PLAUNCH(ctx, DM_PROF_DC, dc_unscale_kernel, dim3(np), dim3(256), 0, ctx->stream, d_scm);
+  DM_PLAUNCH(ctx, DM_PROF_DC, dc_unscale_kernel, dim3(np), dim3(256), 0, ctx->stream, d_scm);
   return DM_OK;
 }
 
 // ===========================================================================
 // driver: C (destroyed) -> evals (unsorted), W rows = eigenvectors^H
 // ===========================================================================
-// The batch is cut into up to four chunks (largest matrices first) that move through
-// T1 -> T2 -> T3/T4 as a software pipeline: the serial QL recurrence of chunk c runs on a
-// side stream while the main stream tridiagonalises chunk c+1 and back-transforms chunk c-1,
-// so the only latency-bound kernel of the solver is hidden behind HBM- and MFMA-bound work.
-namespace {
-struct tri_side {
-  hipStream_t s = nullptr;
-  std::vector<hipEvent_t> ev;
-};
-tri_side g_side;
-hipStream_t g_la_stream = nullptr;   // high-priority stream of the first-stage look-ahead
-hipEvent_t side_event(size_t i) {
-  while (g_side.ev.size() <= i) {
-    hipEvent_t e = nullptr;
-    (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-    g_side.ev.push_back(e);
-  }
-  return g_side.ev[i];
-}
-}  // namespace
-
+// The whole batch, largest matrices first, goes through T1 -> T2 -> T3/T4 on ctx->stream, all matrices in lock-step:
+// T1 is the one-stage reduction or, when `want_two_stage` (dm_trd_policy) and the batch allows it, the two-stage one;
+// T2 is the divide & conquer, or the QL iteration for batches of at most DC_LEAF rows (and under DM_EIG_QL).
 int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, double* evals, int evals_stride,
-                     dm_eig_select* sel) {
+                     dm_eig_select* sel, bool want_two_stage) {
   const int np = (int)probs.size();
   if (np == 0) return DM_OK;
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
@@ -1742,7 +1685,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
   DM_ARG(ctx, maxn <= evals_stride);
   if (maxn == 0) return DM_OK;
 
-  // ---- storage for every problem (all chunks are in flight at once)
+  // ---- storage for every problem
   cplx* Vt = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(tot, 1));
   // panels: per problem 3 TNB rows of n: V, W, V again (see trd_mat)
   cplx* PP = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * 3 * TNB, 1));
@@ -1763,13 +1706,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
   double* dd = dm_ws_alloc_t<double>(ctx, std::max<size_t>(totn, 1));
   double* ee = dm_ws_alloc_t<double>(ctx, std::max<size_t>(totn, 1));
   cplx* tau = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn, 1));
-  // One chunk by default: T1 is a latency-bound chain of ~3 n small launches whose cost hardly
-  // depends on the batch size, so splitting the batch multiplies it (measured: 4 chunks = +40 %).
-  // DM_TRIDIAG_CHUNKS > 1 enables the side-stream pipeline for experiments.
-  int nch = 1;
-  if (const char* e = getenv("DM_TRIDIAG_CHUNKS")) nch = std::max(1, std::min(8, atoi(e)));
-  if (maxn < 256 || np < 2 * nch) nch = 1;
-  const bool use_dc = nch == 1 && maxn > DC_LEAF && !getenv("DM_EIG_QL");
+  const bool use_dc = maxn > DC_LEAF && !getenv("DM_EIG_QL");
   // the recorded rotations (2 n^2 double2) and the QL eigenvector array only exist on the QL path
   size_t totsw = 0, totrot = 0;
   std::vector<size_t> swoff(np), rotoff(np);
@@ -1786,12 +1723,8 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
   int* nsw = dm_ws_alloc_t<int>(ctx, np);
   int* stat = dm_ws_alloc_t<int>(ctx, np);
   double* Zt = dm_ws_alloc_t<double>(ctx, std::max<size_t>(use_dc ? 1 : tot, 1));
-  // back-transformation in compact-WY blocks of NBB reflectors (merged from the TNB-wide panels)
-  int NBB = 128;  // merged from the TNB-wide panels, whatever their width
-  if (const char* e = getenv("DM_WY_BLOCK")) {
-    const int v = atoi(e);
-    if (v == TNB || v == 2 * TNB || v == 4 * TNB) NBB = v;
-  }
+  // back-transformation in compact-WY blocks of NBB reflectors (merged from the TNB-wide panels, whatever their width)
+  constexpr int NBB = 128;
   size_t tottb = 0;
   std::vector<size_t> offtb(np);
   for (int p = 0; p < np; ++p) {
@@ -1817,58 +1750,22 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
   DM_TRY(dm_fill_zero(ctx, tau, sizeof(cplx) * totn));
   DM_TRY(dm_fill_zero(ctx, stat, sizeof(int) * np));
 
-  // ---- chunks: by decreasing size, balanced in n^3
+  // ---- the batch by decreasing size
   std::vector<int> order(np);
   for (int p = 0; p < np; ++p) order[p] = p;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return probs[a].n > probs[b].n; });
-  std::vector<std::vector<int>> chunks(nch);
-  {
-    double total = 0.0;
-    for (int p = 0; p < np; ++p) total += std::pow((double)probs[p].n, 3);
-    double acc = 0.0;
-    int c = 0;
-    for (int idx : order) {
-      chunks[c].push_back(idx);
-      acc += std::pow((double)probs[idx].n, 3);
-      if (c + 1 < nch && acc >= total * (c + 1) / nch) ++c;
-    }
-  }
-  if (nch > 1 && !g_side.s) DM_HIP(ctx, hipStreamCreateWithFlags(&g_side.s, hipStreamNonBlocking));
 
   // ---- two-stage reduction (dm_sbr_impl.h): dense -> band (MFMA) -> tridiagonal (bulge chasing)
 #if DM_TNB == 32
-  bool two_stage = false;
-  {
-    // DM_TRD_TWOSTAGE = 1 / 0 forces / forbids it.  By default it is taken where it was measured faster than the
-    // one-stage reduction with ALL eigenvectors wanted (scratch/twostage_sweep.py; with a selection it gains more): the
-    // bulge chase needs n / 64 sweeps in flight per matrix to be busy, so either many matrices of a few hundred rows or
-    // a few large ones — 111 x <= 1218 (configs[1]) 1.08 x, 512 x 864 1.15 x, 8 x 4000 1.17 x, 8 x 6000 1.19 x, 1 x 16384
-    // 1.03 x; 32 x 1200 0.89 x, 8 x 2000 0.81 x, 1 x 8192 0.75 x stay on the one-stage path.
-    int mode = -1;
-    if (const char* e = getenv("DM_TRD_TWOSTAGE")) mode = atoi(e);
-    if (ctx->trd_mode_override >= 0) mode = ctx->trd_mode_override;
-    // (later sweep, after the launch chains were planned once per panel: 512 x 300 1.05 x, 512 x 432 1.12 x, 256 x 600
-    // 1.14 x, 256 x 700 1.17 x, 512 x 864 1.19 x; 64 x 432 0.94 x, 64 x 700 0.96 x, 32 x 600 0.84 x, 16 x 1000 0.86 x)
-    // (round 5: the levels of the SVD preconditioner of a configs[4] slice are 23 matrices of n = 2500 .. 3552 — below the
-    // n_max >= 3500 rule, on the one-stage path at 0.45 of the HBM roofline for 13 of the 44 s of that stage: n_max >= 2400
-    // with sum n >= 48 000 joins; DM_TRD_TS_MID=0 takes it out)
-    static const bool ts_mid = !getenv("DM_TRD_TS_MID") || atoi(getenv("DM_TRD_TS_MID")) != 0;
-    // (round 6, after the chase by band position: 200 x 128 1.15 x, 300 x 64 1.04, 432 x 64 1.08, 700 x 64 1.05, 700 x 16 1.02,
-    // 1000 x 16 1.02, 1200 x 32 1.06, 2000 x 8 1.04, 16384 x 1 1.26; 300 x 16 0.93, 432 x 16 0.95, 600 x 8 0.90, 1200 x 8 0.96,
-    // 2000 x 2 0.83, 3000 x 4 0.97, 4000 x 2 0.88, 8192 x 1 0.96 — profiles/r06e_twostage_sweep.txt)
-    const bool pays = (maxn >= 700 && np >= 16) || (maxn >= 200 && np >= 64) || (maxn >= 2000 && np >= 8) ||
-                      (maxn >= 300 && totn >= 120000) || (maxn >= 3500 && totn >= 24000) ||
-                      (ts_mid && maxn >= 2400 && totn >= 48000) || maxn >= 14000;
-    two_stage = use_dc && maxn > TSM && maxn > SB + 2 && (mode == 1 || (mode != 0 && pays));
-  }
+  const bool two_stage = want_two_stage && use_dc && maxn > TSM && maxn > SB + 2;
 #else
+  (void)want_two_stage;
   const bool two_stage = false;
 #endif
   const int shift = two_stage ? TNB : 1;  // reflector k has its leading 1 at row k + shift
   auto nrefl_of = [&](int n) { return two_stage ? std::max(0, n - TNB - 1) : std::max(0, n - 1); };
 #if DM_TNB == 32
   cplx* sbPart = nullptr;
-  cplx *sbPP2 = nullptr, *sbRb = nullptr;   // look-ahead of the first stage: second set of panel buffers, R blocks
   cplx *sbPw = nullptr, *sbXt = nullptr, *sbYp = nullptr, *sbAB = nullptr, *sbVd = nullptr, *sbTau2 = nullptr, *sbM1 = nullptr,
        *sbS = nullptr;
   double* sbNp = nullptr;
@@ -1900,12 +1797,6 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
     sbPart = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * SB * 32 + (size_t)np * SB * SB * 32, 1));
     if (!sbPart) return DM_ENOMEM;
     sbNext = dm_ws_alloc_t<int>(ctx, 2 * (size_t)np + 9);  // sweep counters, owners, queue heads, error flag
-    if (maxn - SB <= SFR * SFT && getenv("DM_SB_LOOKAHEAD") && atoi(getenv("DM_SB_LOOKAHEAD")) != 0) {   // (look-ahead experiment)
-      sbPP2 = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * 3 * TNB, 1));
-      sbRb = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * SB, 1));
-      if (!sbPP2 || !sbRb) return DM_ENOMEM;
-      DM_TRY(dm_fill_zero(ctx, sbPP2, sizeof(cplx) * totn * 3 * TNB));
-    }
     if (!sbPw || !sbXt || !sbYp || !sbNp || !sbAB || !sbVd || !sbTau2 || !sbM1 || !sbS || !sbProg || !sbNext) return DM_ENOMEM;
   }
 
@@ -1923,69 +1814,27 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
       cmax = std::max(cmax, probs[p].n);
       cplx* pp = PP + offn[p] * 3 * TNB;
       sm[i] = sb_mat{probs[p].C, probs[p].ldc, probs[p].n, Vt + off[p], pp, pp + n * TNB, pp + 2 * n * TNB,
-                     sbPw + offn[p] * SB, tau + offn[p], sbYp + offyp[p] * SB, sbNp + offyp[p] * 2, (int)(n / SQR + 1), nullptr};
+                     sbPw + offn[p] * SB, tau + offn[p], sbYp + offyp[p] * SB, sbNp + offyp[p] * 2, (int)(n / SQR + 1)};
       dmv[i] = sb_dmat{probs[p].C, probs[p].ldc, probs[p].n};
-      bm[i] = sb_bmat{probs[p].C, probs[p].ldc, probs[p].n, sbAB + offn[p] * SLD, nullptr, 0};
+      bm[i] = sb_bmat{probs[p].C, probs[p].ldc, probs[p].n, sbAB + offn[p] * SLD};
       cm[i] = sb_chase_mat{sbAB + offn[p] * SLD, probs[p].n, sbVd + offvd[p], sbTau2 + offt2[p], dd + offn[p], ee + offn[p],
                            sb_jb[p], sbProg + 2 * offn[p], sbNext + p, sbNext + np + p};
     }
     sb_mat* d_sm = dm_ws_upload(ctx, sm);
     sb_dmat* d_dm = dm_ws_upload(ctx, dmv);
-    sb_bmat* d_bm = nullptr;   // uploaded before the band extraction (the look-ahead decides where R lives)
+    sb_bmat* d_bm = dm_ws_upload(ctx, bm);
     sb_chase_mat* d_cmat = dm_ws_upload(ctx, cm);
-    if (!d_sm || !d_dm || !d_cmat) return DM_ENOMEM;
+    if (!d_sm || !d_dm || !d_bm || !d_cmat) return DM_ENOMEM;
     DM_TRY(dm_fill_zero(ctx, Tbig, sizeof(cplx) * tottb));
-    {
-      // the paired chase writes whole rows of the reflector array: only the slots no sweep reaches are cleared
-      static const bool pairs = !getenv("DM_SB_NOPAIRS") && !getenv("DM_SB_FULLFILL");
-      if (!pairs) DM_TRY(dm_fill_zero(ctx, sbVd, sizeof(cplx) * totvd));
-      else DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_vd_tail_zero_kernel, dim3((cmax + SBG - 1) / SBG, nc), dim3(256), 0, ctx->stream, d_cmat);
-    }
+    // the chase writes whole rows of the reflector array: only the slots no sweep reaches are cleared
+    DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_vd_tail_zero_kernel, dim3((cmax + SBG - 1) / SBG, nc), dim3(256), 0, ctx->stream, d_cmat);
     DM_TRY(dm_fill_zero(ctx, sbTau2, sizeof(cplx) * tott2));
     DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_diag_tiles_kernel, dim3((cmax + 127) / 128, nc), dim3(256), 0, ctx->stream, d_dm);
     // ---- S1: dense -> band, one panel of SB columns at a time, all matrices in lock-step
     //
     // A panel is two chains of launches.  The "side" chain needs nothing but the panel itself: QR, Gram slices, T factor,
     // X^T = T^T V^H.  The "main" chain needs the trailing matrix: Y (slices + sum), M = V^H Y (slices), S, W, and the
-    // rank-64 update.  LOOK-AHEAD (all panels of the chunk small enough for the one-workgroup QR): before the update of
-    // panel k starts, the rows of the NEXT panel are copied and updated on their own (32 rows: a small product), and the
-    // side chain of panel k + 1 runs on a second stream from that snapshot WHILE the main stream updates the trailing
-    // matrix — the latency-bound QR hides behind the HBM-bound update.  What the concurrent chains share is kept apart:
-    // the panel buffers (V, W, V) alternate between two sets, the QR puts its R block into a buffer of its own instead of
-    // into rows of A that the running update still writes (the band extraction collects it from there).
-    static const bool nofuse = getenv("DM_SB_NOFUSE") != nullptr;
-    // MEASURED, OFF BY DEFAULT (DM_SB_LOOKAHEAD=1 turns it on): correct (scratch/twostage_check.py, the GPU suite), but the
-    // QR does not actually overlap — its 512-thread workgroups at 180 VGPRs need two of a CU's three update workgroups to
-    // leave at the same time, and every slot an update tile frees is taken by the next tile first, stream priority or
-    // not: the QR ran 755 us instead of 205, finishing as late as without look-ahead (configs[1]: 135.7-136.3 ms per step
-    // against 133.9-134.2, the snapshot product being extra work).
-    static const bool la_on = getenv("DM_SB_LOOKAHEAD") && atoi(getenv("DM_SB_LOOKAHEAD")) != 0;
-    const bool la = la_on && !nofuse && sbPP2 && sbRb && cmax - SB <= SFR * SFT && cmax - 2 * SB >= 2;
-    sb_mat* d_sm2 = nullptr;   // the descriptors with the second set of panel buffers (odd panels)
-    if (la) {
-      std::vector<sb_mat> sm_a(sm), sm_b(sm);
-      for (int i = 0; i < nc; ++i) {
-        const int p = ch[i];
-        const size_t n = probs[p].n;
-        cplx* pp2 = sbPP2 + offn[p] * 3 * TNB;
-        sm_a[i].Rb = sbRb + offn[p] * SB;
-        sm_b[i].Rb = sm_a[i].Rb;
-        sm_b[i].Vp = pp2; sm_b[i].Wp = pp2 + n * TNB; sm_b[i].Vp2 = pp2 + 2 * n * TNB;
-      }
-      d_sm = dm_ws_upload(ctx, sm_a);
-      d_sm2 = dm_ws_upload(ctx, sm_b);
-      if (!d_sm || !d_sm2) return DM_ENOMEM;
-      // HIGH priority: the one-workgroup-per-matrix QR must get CUs while the update's ten thousand tiles keep arriving —
-      // on an ordinary stream its workgroups were only placed as the update drained (755 us instead of 205)
-      if (!g_la_stream) {
-        int lo = 0, hi = 0;
-        DM_HIP(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        DM_HIP(ctx, hipStreamCreateWithPriority(&g_la_stream, hipStreamNonBlocking, hi));
-      }
-    }
-    auto pp_of = [&](int p, int k0) { return ((la && ((k0 / SB) & 1)) ? sbPP2 : PP) + offn[p] * 3 * TNB; };
-    auto sm_of = [&](int k0) { return (la && ((k0 / SB) & 1)) ? d_sm2 : d_sm; };
-    static const bool nosplit = getenv("DM_SB_NOSPLITK") != nullptr;
+    // rank-64 update.
     cplx* part_y = sbPart;                               // per matrix: SY x (32 x n) at offn * SB * 32
     cplx* part_g = sbPart + totn * SB * 32;              // per matrix: 32 x (32 x 32)
     struct panel_split { int nact, SG, SY; };
@@ -2001,7 +1850,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
       // split-K: the products with K = trailing size have few output tiles (one 32 x 32 tile per matrix for the Gram
       // matrices, one 32 x 128 tile per 128 columns of Y): cut K so that a launch carries ~1000 tiles
       auto slices_for = [&](int tiles) { return std::max(1, std::min(30, std::min((1024 + tiles - 1) / tiles, (kmax + 127) / 128))); };
-      return panel_split{nact, (nosplit || nact == 0) ? 1 : slices_for(nact), (nosplit || nact == 0) ? 1 : slices_for(std::max(ytiles, 1))};
+      return panel_split{nact, nact == 0 ? 1 : slices_for(nact), nact == 0 ? 1 : slices_for(std::max(ytiles, 1))};
     };
     // side chain of panel k0: Gram slices (summed by the T-factor kernel), T, X^T = T^T V^H
     struct side_set { dm_gemm_plan pg, px; std::vector<tf_mat> tf; };
@@ -2014,7 +1863,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
         const int m = n - i0;
         if (m < 2) continue;
         const int kb = std::min(SB, m - 1);
-        cplx* Vp = pp_of(p, k0);
+        cplx* Vp = PP + offn[p] * 3 * TNB;
         cplx* Xt = sbXt + offn[p] * SB;
         const cplx* Vb = Vt + off[p] + (size_t)k0 * n + i0;
         cplx* G = Gs + offg[p] + (size_t)(k0 / TNB) * TNB * TNB;
@@ -2049,7 +1898,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
         if (m < 2) continue;
         const int lda = probs[p].ldc;
         cplx* C = probs[p].C;
-        cplx* pp = pp_of(p, k0);
+        cplx* pp = PP + offn[p] * 3 * TNB;
         cplx* Vp = pp;
         cplx* Wp = pp + (size_t)n * TNB;
         cplx* Xt = sbXt + offn[p] * SB;
@@ -2064,9 +1913,8 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
         // rows of block R) are emitted next to each other: they run on the same XCD at the same time (the tile list is
         // dealt to the XCDs in contiguous runs) and the second one finds the block in L2.  Uniform K = 128 tiles instead of
         // ragged slices; the trailing matrix comes from HBM once per panel for this product instead of twice.
-        static const bool ypair_off = getenv("DM_SB_YPAIR") && atoi(getenv("DM_SB_YPAIR")) == 0;
         const int nblk = (n - a0 + 127) / 128;
-        if (sp.SY > 1 && !ypair_off && nblk <= 30) {
+        if (sp.SY > 1 && nblk <= 30) {
           // column block b covers [lo(b), hi(b)); slots of block b: stored pieces over the blocks c >= b (slot c - b),
           // then mirrored pieces over the blocks r < b (slot (nblk - b) + r)
           auto lo = [&](int b) { return std::max(a0 + b * 128, i0); };
@@ -2141,21 +1989,6 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
       DM_TRY(dm_gemm_plan_build(gh, M_.ph));
       return DM_OK;
     };
-    // look-ahead: the update of panel k0 applied to the snapshot of the rows of panel k0 + SB
-    //   P[q][c] -= sum_j V[i0 + q][j] conj(W[c][j]) + W[i0 + q][j] conj(V[c][j]),   c >= i0 + SB
-    auto build_strip = [&](int k0, dm_gemm_plan& pl) -> int {
-      const int i0 = k0 + SB, i1 = i0 + SB;
-      std::vector<dm_gemm_desc> g;
-      for (int p : ch) {
-        const int n = probs[p].n;
-        if (n - i1 < 2) continue;
-        cplx* pp = pp_of(p, k0);
-        cplx* Pw = sbPw + offn[p] * SB;
-        g.push_back(dm_gemm_make(pp + i0, 1, n, false, pp + (size_t)n * TNB + i1, n, 1, true, Pw + i1, n, SB, n - i1, 2 * TNB, -1.0,
-                                 1.0));
-      }
-      return dm_gemm_plan_build(g, pl);
-    };
     auto qr_flops = [&](int k0) {
       double fl = 0.0;  // Householder QR of an m x SB panel: 2 SB^2 (m - SB / 3) complex multiply-adds
       for (int p : ch) {
@@ -2164,11 +1997,6 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
       }
       return fl;
     };
-    struct stream_swap {   // grouped launches go to ctx->stream: point it at the side stream for a scope
-      dm_ctx* c; hipStream_t keep;
-      stream_swap(dm_ctx* c_, hipStream_t s) : c(c_), keep(c_->stream) { if (s) c->stream = s; }
-      ~stream_swap() { c->stream = keep; }
-    };
     static bool larft_attr = false;
     const size_t larft_lds = 2 * sizeof(cplx) * TNB * (TNB + 1);
     if (!larft_attr) {
@@ -2176,51 +2004,17 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
                                       (int)larft_lds));
       larft_attr = true;
     }
-    // QR (one-workgroup kernel, or the launched one) + side chain of panel k0 on stream `st` (nullptr: the main stream)
-    auto run_side = [&](int k0, const side_set& S_, const char* d_pg, const char* d_px, const tf_mat* d_tf, hipStream_t st,
-                        int snap) -> int {
-      const int i0 = k0 + SB, a0 = i0 & ~127;
-      stream_swap sw(ctx, st);
-      if (cmax - i0 <= SFR * SFT && !nofuse) {
-        // panels that fit the registers of one workgroup per matrix: the whole QR in one launch
-        dm_prof_scope ps(ctx, DM_PROF_SB_PANEL, qr_flops(k0));
-        hipLaunchKernelGGL(sb_panel_fused_kernel, dim3(nc), dim3(SFT), 0, ctx->stream, sm_of(k0), k0, a0, snap);
-      } else {
-        hipLaunchKernelGGL(sb_panel_load_kernel, dim3((cmax - a0 + 255) / 256, nc), dim3(256), 0, ctx->stream, d_sm, k0, a0);
-        const int nchmax = (cmax - i0 + SQR - 1) / SQR;
-        for (int q = 0; q <= SB; ++q) {
-          hipLaunchKernelGGL(sb_qr_update_kernel, dim3(nchmax, nc), dim3(256), 0, ctx->stream, d_sm, k0, q);
-          if (q < SB) hipLaunchKernelGGL(sb_qr_dots_kernel, dim3(nchmax, nc), dim3(256), 0, ctx->stream, d_sm, k0, q);
-        }
-      }
-      if (S_.tf.empty()) return DM_OK;
-      DM_TRY(dm_gemm_plan_run(ctx, S_.pg, d_pg));
-      // T factor of the panel (zlarft from the Gram matrix), straight into the slot the back-transformation reads
-      DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, larft_kernel, dim3((unsigned)S_.tf.size()), dim3(256), larft_lds, ctx->stream, d_tf);
-      DM_TRY(dm_gemm_plan_run(ctx, S_.px, d_px));
-      return DM_OK;
-    };
-    side_set side_next;        // look-ahead: the side chain of the panel after the current one (built one iteration early)
-    bool side_next_ready = false;
     for (int k0 = 0; cmax - k0 - SB >= 2; k0 += SB) {
-      const int i0 = k0 + SB;
+      const int i0 = k0 + SB, a0 = i0 & ~127;
       if (split_of(k0).nact == 0) continue;
-      const bool have_next = la && cmax - (k0 + SB) - SB >= 2 && split_of(k0 + SB).nact > 0;
-      side_set side_cur;
-      const bool run_cur_side = !(la && side_next_ready);   // else it already ran on the side stream
-      if (run_cur_side) DM_TRY(build_side(k0, side_cur));
+      side_set sd;
       main_set mn;
+      DM_TRY(build_side(k0, sd));
       DM_TRY(build_main(k0, mn));
-      side_set side_new;
-      dm_gemm_plan pstrip;
-      if (have_next) {
-        DM_TRY(build_side(k0 + SB, side_new));
-        DM_TRY(build_strip(k0, pstrip));
-      }
       // every descriptor of the iteration travels in ONE staged copy: the grouped products as plans, the lists of slice
       // sums, the S and the T-factor descriptors behind them
       dm_gemm_plan extra;   // not a product: raw arrays carried by the same upload
-      size_t o_sy, o_ss, o_tf, o_tf2;
+      size_t o_sy, o_ss, o_tf;
       {
         auto put = [&](const void* src, size_t bytes) {
           const size_t o = (extra.blob.size() + 15) & ~size_t(15);
@@ -2230,47 +2024,46 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
         };
         o_sy = put(mn.sy.data(), mn.sy.size() * sizeof(sb_sum_desc));
         o_ss = put(mn.ssv.data(), mn.ssv.size() * sizeof(sb_s_desc));
-        o_tf = put(side_cur.tf.data(), side_cur.tf.size() * sizeof(tf_mat));
-        o_tf2 = put(side_new.tf.data(), side_new.tf.size() * sizeof(tf_mat));
+        o_tf = put(sd.tf.data(), sd.tf.size() * sizeof(tf_mat));
         if (extra.blob.empty()) extra.blob.resize(16);
       }
       std::vector<const char*> dv;
-      DM_TRY(dm_gemm_plans_upload(ctx, {&side_cur.pg, &side_cur.px, &mn.py1, &mn.py2, &mn.pm, &mn.pw, &mn.ph, &side_new.pg,
-                                        &side_new.px, &pstrip, &extra}, dv));
-      const char* d_extra = dv[10];
-      auto launch_sums = [&](const std::vector<sb_sum_desc>& v, size_t o) -> int {
-        if (v.empty()) return DM_OK;
-        int mx = 0;
-        for (const auto& d : v) mx = std::max(mx, d.rows * d.cols);
-        DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_sum_partials_kernel, dim3((mx + 255) / 256, (unsigned)v.size()), dim3(256), 0, ctx->stream,
-                           reinterpret_cast<const sb_sum_desc*>(d_extra + o));
-        return DM_OK;
-      };
-      if (run_cur_side) {
-        DM_TRY(run_side(k0, side_cur, dv[0], dv[1], reinterpret_cast<const tf_mat*>(d_extra + o_tf), nullptr, 0));
+      DM_TRY(dm_gemm_plans_upload(ctx, {&sd.pg, &sd.px, &mn.py1, &mn.py2, &mn.pm, &mn.pw, &mn.ph, &extra}, dv));
+      const char* d_extra = dv[7];
+      // side chain: the QR (one workgroup per matrix while the panel fits its registers, else the launched kernels), the
+      // Gram slices, the T factor of the panel (zlarft from the Gram matrix, straight into the slot the back-transformation
+      // reads) and X^T = T^T V^H
+      if (cmax - i0 <= SFR * SFT) {
+        dm_prof_scope ps(ctx, DM_PROF_SB_PANEL, qr_flops(k0));
+        hipLaunchKernelGGL(sb_panel_fused_kernel, dim3(nc), dim3(SFT), 0, ctx->stream, d_sm, k0, a0);
       } else {
-        DM_HIP(ctx, hipStreamWaitEvent(ctx->stream, side_event(18 + ((k0 / SB) & 1)), 0));   // the side chain of this panel
+        hipLaunchKernelGGL(sb_panel_load_kernel, dim3((cmax - a0 + 255) / 256, nc), dim3(256), 0, ctx->stream, d_sm, k0, a0);
+        const int nchmax = (cmax - i0 + SQR - 1) / SQR;
+        for (int q = 0; q <= SB; ++q) {
+          hipLaunchKernelGGL(sb_qr_update_kernel, dim3(nchmax, nc), dim3(256), 0, ctx->stream, d_sm, k0, q);
+          if (q < SB) hipLaunchKernelGGL(sb_qr_dots_kernel, dim3(nchmax, nc), dim3(256), 0, ctx->stream, d_sm, k0, q);
+        }
       }
+      if (!sd.tf.empty()) {
+        DM_TRY(dm_gemm_plan_run(ctx, sd.pg, dv[0]));
+        DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, larft_kernel, dim3((unsigned)sd.tf.size()), dim3(256), larft_lds, ctx->stream,
+                   reinterpret_cast<const tf_mat*>(d_extra + o_tf));
+        DM_TRY(dm_gemm_plan_run(ctx, sd.px, dv[1]));
+      }
+      // main chain
       DM_TRY(dm_gemm_plan_run(ctx, mn.py1, dv[2]));
       DM_TRY(dm_gemm_plan_run(ctx, mn.py2, dv[3]));
-      DM_TRY(launch_sums(mn.sy, o_sy));
+      if (!mn.sy.empty()) {
+        int mx = 0;
+        for (const auto& d : mn.sy) mx = std::max(mx, d.rows * d.cols);
+        DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_sum_partials_kernel, dim3((mx + 255) / 256, (unsigned)mn.sy.size()), dim3(256), 0,
+                   ctx->stream, reinterpret_cast<const sb_sum_desc*>(d_extra + o_sy));
+      }
       DM_TRY(dm_gemm_plan_run(ctx, mn.pm, dv[4]));
       if (!mn.ssv.empty())
         DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_s_kernel, dim3((unsigned)mn.ssv.size()), dim3(256), 0, ctx->stream,
                            reinterpret_cast<const sb_s_desc*>(d_extra + o_ss));
       DM_TRY(dm_gemm_plan_run(ctx, mn.pw, dv[5]));
-      side_next_ready = false;
-      if (have_next) {
-        // snapshot of the next panel's rows + this panel's update of them, then its side chain on the second stream
-        DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_strip_copy_kernel, dim3((cmax - i0 - SB + 255) / 256, SB, nc), dim3(256), 0, ctx->stream, d_sm, i0);
-        DM_TRY(dm_gemm_plan_run(ctx, pstrip, dv[9]));
-        hipEvent_t e_go = side_event(16 + ((k0 / SB) & 1));
-        DM_HIP(ctx, hipEventRecord(e_go, ctx->stream));
-        DM_HIP(ctx, hipStreamWaitEvent(g_la_stream, e_go, 0));
-        DM_TRY(run_side(k0 + SB, side_new, dv[7], dv[8], reinterpret_cast<const tf_mat*>(d_extra + o_tf2), g_la_stream, 1));
-        DM_HIP(ctx, hipEventRecord(side_event(18 + (((k0 + SB) / SB) & 1)), g_la_stream));
-        side_next_ready = true;
-      }
       DM_TRY(dm_gemm_plan_run(ctx, mn.ph, dv[6]));
     }
     // ---- S2: band -> tridiagonal
@@ -2283,21 +2076,14 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
       return DM_OK;
     };
     {
-      size_t maxel = (size_t)cmax * SLD;
-      if (la)
-        for (int i = 0; i < nc; ++i) {
-          const int p = ch[i], n = probs[p].n;
-          bm[i].Rb = sbRb + offn[p] * SB;
-          bm[i].nrb = n - SB - 2 >= 0 ? ((n - SB - 2) / SB) * SB + SB : 0;   // rows of the panels this matrix went through
-        }
-      d_bm = dm_ws_upload(ctx, bm);
-      if (!d_bm) return DM_ENOMEM;
+      const size_t maxel = (size_t)cmax * SLD;
       DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_band_extract_kernel, dim3((unsigned)((maxel + 255) / 256), nc), dim3(256), 0, ctx->stream, d_bm);
       if (dump) DM_TRY(dump_arr(".band", sbAB, sizeof(cplx) * totn * SLD));
       // ---- the chase BY BAND POSITION (sb_chase_pos_kernel; DM_SB_CHASE=pairs keeps the sweep-owning pairs below): one
       // workgroup per (matrix, group of SB_POS_NP positions), largest matrix first, groups left to right; a matrix whose
       // groups could not all be resident at once stays on the sweep-owning kernel (its hand-offs need no co-residency)
-      static const bool by_pos = !(getenv("DM_SB_CHASE") && strcmp(getenv("DM_SB_CHASE"), "pairs") == 0) && !getenv("DM_SB_NOPAIRS");
+      const char* chase = getenv("DM_SB_CHASE");
+      const bool by_pos = !(chase && strcmp(chase, "pairs") == 0);
       int pos_cap = 224;   // workgroups of one matrix that may have to be resident together (one per CU, some CUs left to others)
       if (const char* e = getenv("DM_SB_POS_CAP")) pos_cap = std::max(1, atoi(e));
       bool pos_fits = by_pos;
@@ -2348,27 +2134,24 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
       }
       // One persistent launch: per-XCD queues of matrix ids; a matrix gets as many entries (= workgroups) as its
       // pipeline of sweeps can keep busy (sweep s + 1 trails sweep s by two blocks: n / (2 SB) sweeps in flight).
-      constexpr int NW = 8, NP = 4;
-      static const bool pairs = !getenv("DM_SB_NOPAIRS");  // two waves per sweep (E chain + D updates) or one
-      const int per_wg = pairs ? NP : NW;                  // sweeps a workgroup runs at a time
+      constexpr int NP = 4;   // sweeps a workgroup runs at a time (two waves per sweep: E chain + D updates)
       std::vector<int> order(nc);
       for (int i = 0; i < nc; ++i) order[i] = i;
       std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cm[a].n > cm[b].n; });
-      int wgmax = 32;
-      if (const char* e = getenv("DM_SB_WGPM")) wgmax = std::max(1, atoi(e));
+      constexpr int wgmax = 32;
       std::vector<std::vector<int>> qs(8);
       double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       // workgroups are resident for the whole launch and stay with a matrix until its sweeps are taken: hand out at most
       // as many entries as there are workgroups (one per CU), in proportion to the sweeps each matrix can keep in flight
       double want = 0.0;
       for (int i : order)
-        if (cm[i].n >= 1) want += std::max(1.0, (double)cm[i].n / (2 * SB * per_wg));
+        if (cm[i].n >= 1) want += std::max(1.0, (double)cm[i].n / (2 * SB * NP));
       const double scale = want > 256.0 ? 256.0 / want : 1.0;
       for (int i : order) {
         const int n = cm[i].n;
         if (n < 1) continue;
-        int k = std::max(1, std::min(wgmax, (int)(scale * n / (2 * SB * per_wg) + 0.999)));
-        if (scale < 1.0) k = std::max(1, (int)(scale * n / (2 * SB * per_wg) + 0.5));
+        int k = std::max(1, std::min(wgmax, (int)(scale * n / (2 * SB * NP) + 0.999)));
+        if (scale < 1.0) k = std::max(1, (int)(scale * n / (2 * SB * NP) + 0.5));
         int q = 0;
         for (int t = 1; t < 8; ++t)
           if (load[t] < load[q]) q = t;
@@ -2406,8 +2189,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
           fl += 8.0 * 6.0 * SB * SB * (n * n / (2.0 * SB));
         }
         dm_prof_scope ps(ctx, DM_PROF_SB_CHASE, fl);
-        if (pairs) hipLaunchKernelGGL((sb_chase2_kernel<NP>), dim3(nwg), dim3(128 * NP), 0, ctx->stream, d_cmat, ctl);
-        else hipLaunchKernelGGL((sb_chase_kernel<NW>), dim3(nwg), dim3(64 * NW), 0, ctx->stream, d_cmat, ctl);
+        hipLaunchKernelGGL((sb_chase2_kernel<NP>), dim3(nwg), dim3(128 * NP), 0, ctx->stream, d_cmat, ctl);
       }
       {
         int herr = 0;  // (the eigenvalue selection synchronises right after this stage anyway)
@@ -2440,10 +2222,8 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
     // 16 columns per wave (four lanes per column).  Eight lanes per column (twice the waves, five instead of nine rows
     // of a reflector per lane) were measured slower in both regimes — configs[1] batch 11.3 against 9.2 ms, one matrix of
     // 32 576 rows 8.8 against 7.6 s: the fixed cost per reflector (fetch, fold, scale) weighs more than the extra waves
-    // hide — and stay behind DM_SB_Q2_LPC=8.
-    int lpc = 4;
-    if (const char* e = getenv("DM_SB_Q2_LPC")) lpc = atoi(e) == 8 ? 8 : 4;
-    const int ncw = 64 / lpc;
+    // hide.
+    constexpr int ncw = 16;
     std::vector<sb_q2_mat> qm;
     std::vector<int2> wgs;
     for (int p : order) {
@@ -2457,7 +2237,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
     if (getenv("DM_TRD_SIZES")) {
       fprintf(stderr, "[apply_q2] n:ncol");
       for (const auto& q : qm) fprintf(stderr, " %d:%d", q.n, q.ncol);
-      fprintf(stderr, " -> %zu workgroups, %d lanes per column\n", wgs.size(), lpc);
+      fprintf(stderr, " -> %zu workgroups\n", wgs.size());
     }
     sb_q2_mat* d_qm = dm_ws_upload(ctx, qm);
     int2* d_wgs = dm_ws_upload(ctx, wgs);
@@ -2465,19 +2245,14 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
     const size_t lds = sizeof(cplx) * (2 * SBG * SBW + 2 * SBG);
     static bool attr = false;
     if (!attr) {
-      DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sb_q2_apply_kernel<NW, 4>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sb_q2_apply_kernel<NW, 8>),
+      DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sb_q2_apply_kernel<NW>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       attr = true;
     }
     double fl = 0.0;  // n^2 / (2 SB) reflectors of length SB on ncol columns: 2 SB complex multiply-adds per column each
     for (const auto& q : qm) fl += 8.0 * (double)q.n * q.n * q.ncol;
     dm_prof_scope ps(ctx, DM_PROF_SB_Q2, fl);
-    if (lpc == 8)
-      hipLaunchKernelGGL((sb_q2_apply_kernel<NW, 8>), dim3((unsigned)wgs.size()), dim3(64 * NW), lds, ctx->stream, d_qm, d_wgs);
-    else
-      hipLaunchKernelGGL((sb_q2_apply_kernel<NW, 4>), dim3((unsigned)wgs.size()), dim3(64 * NW), lds, ctx->stream, d_qm, d_wgs);
+    hipLaunchKernelGGL((sb_q2_apply_kernel<NW>), dim3((unsigned)wgs.size()), dim3(64 * NW), lds, ctx->stream, d_qm, d_wgs);
     DM_HIP(ctx, hipGetLastError());
     return DM_OK;
   };
@@ -2485,7 +2260,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
   auto apply_q2 = [&](const std::vector<int>&, const std::vector<int>&) -> int { return DM_OK; };
 #endif
 
-  bool small_path = false;  // set by phase_T1 when the chunk went through trd_small (explicit Q in Ut)
+  bool small_path = false;  // set by phase_T1 when the batch went through trd_small (explicit Q in Ut)
   auto phase_T1 = [&](const std::vector<int>& ch) -> int {
     if (ch.empty()) return DM_OK;
     const int nc = (int)ch.size();
@@ -2502,7 +2277,7 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
     }
     trd_mat* d_tm = dm_ws_upload(ctx, tm);
     if (!d_tm) return DM_ENOMEM;
-    if (cmax <= TSM && !getenv("DM_TRD_NOSMALL")) {
+    if (cmax <= TSM) {
       // small matrices: tridiagonal form and the explicit Q in one launch (Q into Ut, leading dimension n)
       std::vector<trs_mat> sm(nc);
       for (int i = 0; i < nc; ++i) {
@@ -2584,17 +2359,14 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
         // current panel — trd_symv / trd_wx read the vectors q < j at rows > k only (v_q and w_q are written for all
         // rows > k0 + q), the her2k above reads rows >= k1 of all TNB vectors of a FULL panel (a matrix that ends
         // inside the panel has n - k1 <= 0 and takes no part).  (170 MB of memset per panel at configs[1].)
-        static const bool clear_panels = getenv("DM_TRD_CLEAR_PANELS") != nullptr;
-        if (clear_panels) DM_TRY(dm_fill_zero(ctx, PP, sizeof(cplx) * totn * 3 * TNB));
       }
     }
     DM_HIP(ctx, hipGetLastError());
     return DM_OK;
   };
 
-  std::vector<rot_mat*> d_rm_of(nch, nullptr);
-  auto phase_T2 = [&](int c, hipStream_t st) -> int {
-    const std::vector<int>& ch = chunks[c];
+  rot_mat* d_rm = nullptr;  // set by phase_T2 (QL path)
+  auto phase_T2 = [&](const std::vector<int>& ch) -> int {
     if (ch.empty()) return DM_OK;
     const int nc = (int)ch.size();
     int cmax = 0;
@@ -2609,15 +2381,9 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
       rm[i] = rot_mat{Zt + off[p], n, n, sw_dir + swoff[p], sw_lo + swoff[p], sw_cnt + swoff[p], sw_off + swoff[p],
                       rot + rotoff[p], nsw + p};
     }
-    // descriptors are uploaded on the main stream; the caller orders `st` after them with an event
     ql_mat* d_qm = dm_ws_upload(ctx, qm);
-    d_rm_of[c] = dm_ws_upload(ctx, rm);
-    if (!d_qm || !d_rm_of[c]) return DM_ENOMEM;
-    if (st != ctx->stream) {
-      hipEvent_t e = side_event(2 * c);
-      DM_HIP(ctx, hipEventRecord(e, ctx->stream));
-      DM_HIP(ctx, hipStreamWaitEvent(st, e, 0));
-    }
+    d_rm = dm_ws_upload(ctx, rm);
+    if (!d_qm || !d_rm) return DM_ENOMEM;
     if ((size_t)cmax * 16 <= 120u * 1024u) {
       static bool attr = false;
       if (!attr) {
@@ -2625,28 +2391,24 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
         attr = true;
       }
-      DM_PLAUNCH(ctx, DM_PROF_DC, ql_kernel<true>, dim3(nc), dim3(64), (size_t)cmax * 16, st, d_qm);
+      DM_PLAUNCH(ctx, DM_PROF_DC, ql_kernel<true>, dim3(nc), dim3(64), (size_t)cmax * 16, ctx->stream, d_qm);
     } else {
-      DM_PLAUNCH(ctx, DM_PROF_DC, ql_kernel<false>, dim3(nc), dim3(64), 0, st, d_qm);
+      DM_PLAUNCH(ctx, DM_PROF_DC, ql_kernel<false>, dim3(nc), dim3(64), 0, ctx->stream, d_qm);
     }
-    if (st != ctx->stream) DM_HIP(ctx, hipEventRecord(side_event(2 * c + 1), st));
     DM_HIP(ctx, hipGetLastError());
     return DM_OK;
   };
 
   std::vector<double*> zfinal;  // set by the divide & conquer path
-  auto phase_T34 = [&](int c, bool waited_on_side) -> int {
-    const std::vector<int>& ch = chunks[c];
+  auto phase_T34 = [&](const std::vector<int>& ch) -> int {
     if (ch.empty()) return DM_OK;
     const int nc = (int)ch.size();
-    if (waited_on_side) DM_HIP(ctx, hipStreamWaitEvent(ctx->stream, side_event(2 * c + 1), 0));
     int cmax = 0;
     for (int p : ch) cmax = std::max(cmax, probs[p].n);
     // T3 (QL path only: D&C delivers the eigenvectors directly)
     if (zfinal.empty()) {
-      DM_PLAUNCH(ctx, DM_PROF_DC, zt_identity_kernel, dim3((cmax + 255) / 256, cmax, nc), dim3(256), 0, ctx->stream,
-                         d_rm_of[c]);
-      DM_PLAUNCH(ctx, DM_PROF_DC, rot_apply_kernel, dim3((cmax + 255) / 256, nc), dim3(256), 0, ctx->stream, d_rm_of[c]);
+      DM_PLAUNCH(ctx, DM_PROF_DC, zt_identity_kernel, dim3((cmax + 255) / 256, cmax, nc), dim3(256), 0, ctx->stream, d_rm);
+      DM_PLAUNCH(ctx, DM_PROF_DC, rot_apply_kernel, dim3((cmax + 255) / 256, nc), dim3(256), 0, ctx->stream, d_rm);
     }
     {
       std::vector<dm_cdesc> cp;
@@ -2873,32 +2635,22 @@ int herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs,
     return DM_OK;
   };
 
-  if (use_dc) {
 #if DM_TNB == 32
-    if (two_stage) DM_TRY(phase_T1_two(chunks[0]));
-    else
+  if (two_stage) DM_TRY(phase_T1_two(order));
+  else
 #endif
-    DM_TRY(phase_T1(chunks[0]));
+  DM_TRY(phase_T1(order));
+  if (use_dc) {
     // Ut is first written by the back-transformation (unless the LDS-resident small path put Q there)
     DM_TRY(dc_solve(ctx, probs, dd, ee, offn, off, tot, totn, zfinal,
                     maxn > TSM ? reinterpret_cast<double*>(Ut) : nullptr));
-    DM_TRY(phase_T34(0, false));
-  } else if (nch == 1) {
-    DM_TRY(phase_T1(chunks[0]));
-    DM_TRY(phase_T2(0, ctx->stream));
-    DM_TRY(phase_T34(0, false));
   } else {
-    for (int c = 0; c < nch; ++c) {
-      DM_TRY(phase_T1(chunks[c]));
-      DM_TRY(phase_T2(c, g_side.s));
-      if (c > 0) DM_TRY(phase_T34(c - 1, true));
-    }
-    DM_TRY(phase_T34(nch - 1, true));
+    DM_TRY(phase_T2(order));
   }
+  DM_TRY(phase_T34(order));
 
   std::vector<int> hstat(np);
   DM_TRY(dm_download(ctx, hstat.data(), stat, sizeof(int) * np));
-  if (nch > 1) DM_HIP(ctx, hipStreamSynchronize(g_side.s));
   for (int p = 0; p < np; ++p)
     if (hstat[p] != 0) {
       ctx->err = hstat[p] == 1 ? "tridiagonal QL iteration did not converge" : "QL rotation storage exhausted";

@@ -246,13 +246,44 @@ def test_herm_eig_with_exactly_zero_rows(ctx, monkeypatch, twostage):
         assert np.abs(Wh[b] @ Wh[b].conj().T - np.eye(n)).max() < 1e-12
 
 
-def test_herm_eig_mixed_sizes_via_eigh_gen(ctx):
+@pytest.mark.parametrize("n", [97, 129, 161, 452, 1000])
+def test_herm_eig_two_stage_both_chases(ctx, monkeypatch, n):
+    """The two-stage reduction (DM_TRD_TWOSTAGE=1; n = 97 is the smallest size it takes) under both bulge chases: by band
+    position, the default, and by sweep-owning wave pairs (DM_SB_CHASE=pairs), which a matrix too large for the
+    by-position chase takes.  Eigenvalues to rounding and unitary vectors for each, and the two chases agree."""
+    monkeypatch.setenv("DM_TRD_TWOSTAGE", "1")
+    rng = np.random.default_rng(n)
+    nb = 2
+    X = crand(rng, nb, n, n)
+    C = 0.5 * (X + X.conj().transpose(0, 2, 1))
+    ref = np.linalg.eigvalsh(C)
+    scale = np.abs(ref).max()
+    got = {}
+    for chase in ("position", "pairs"):
+        if chase == "pairs":
+            monkeypatch.setenv("DM_SB_CHASE", "pairs")
+        else:
+            monkeypatch.delenv("DM_SB_CHASE", raising=False)
+        ev, W = ctx.herm_eig(ctx.to_device(C.copy()), n, n, strideC=n * n, batch=nb)
+        got[chase] = np.sort(ev.cpu().numpy()[:, :n], axis=1)
+        assert np.abs(got[chase] - ref).max() <= 1e-13 * scale, chase
+        Wh = W.cpu().numpy()
+        for b in range(nb):
+            assert np.abs(Wh[b] @ Wh[b].conj().T - np.eye(n)).max() < 1e-12, chase
+    assert np.abs(got["position"] - got["pairs"]).max() <= 1e-13 * scale
+
+
+@pytest.mark.parametrize("ns,twostage", [
+    pytest.param([70, 3, 129, 1, 40], None, id="policy"),
+    # tiny and single-workgroup matrices in the same two-stage batch as large ones, under both chases
+    pytest.param([2, 34, 35, 66, 97, 129, 161, 452, 1000], "1", id="twostage"),
+])
+def test_herm_eig_mixed_sizes_via_eigh_gen(ctx, monkeypatch, ns, twostage):
     """Different n in one batch (the KL use: ndof varies with m)."""
     from driftscan_amd._lib import block_offsets
     import scipy.linalg as la
 
     rng = np.random.default_rng(5)
-    ns = [70, 3, 129, 1, 40]
     off, tot = block_offsets(ns)
     As, Bs = [], []
     for n in ns:
@@ -261,14 +292,27 @@ def test_herm_eig_mixed_sizes_via_eigh_gen(ctx):
         Bs.append(Y @ Y.conj().T + n * np.eye(n))
     A = np.concatenate([a.ravel() for a in As])
     B = np.concatenate([b.ravel() for b in Bs])
-    evals, evoff, evecs, ac, _ = ctx.eigh_gen(ctx.to_device(A), ctx.to_device(B), ns, off)
-    ev = evals.cpu().numpy()
-    E = evecs.cpu().numpy()
-    for i, n in enumerate(ns):
-        ref = la.eigh(As[i], Bs[i], eigvals_only=True)
-        assert np.abs(ev[evoff[i]: evoff[i] + n] - ref).max() <= 1e-11 * ref.max()
-        Ei = E[off[i]: off[i] + n * n].reshape(n, n)
-        assert np.abs(Ei @ Bs[i] @ Ei.conj().T - np.eye(n)).max() < 1e-10
+    chases = [None]
+    if twostage is not None:
+        monkeypatch.setenv("DM_TRD_TWOSTAGE", twostage)
+        chases.append("pairs")
+    got = []
+    for chase in chases:
+        if chase is None:
+            monkeypatch.delenv("DM_SB_CHASE", raising=False)
+        else:
+            monkeypatch.setenv("DM_SB_CHASE", chase)
+        evals, evoff, evecs, ac, _ = ctx.eigh_gen(ctx.to_device(A), ctx.to_device(B), ns, off)
+        ev = evals.cpu().numpy()
+        E = evecs.cpu().numpy()
+        for i, n in enumerate(ns):
+            ref = la.eigh(As[i], Bs[i], eigvals_only=True)
+            assert np.abs(ev[evoff[i]: evoff[i] + n] - ref).max() <= 1e-11 * ref.max(), chase
+            Ei = E[off[i]: off[i] + n * n].reshape(n, n)
+            assert np.abs(Ei @ Bs[i] @ Ei.conj().T - np.eye(n)).max() < 1e-10, chase
+        got.append(ev)
+    if len(got) == 2:
+        assert np.abs(got[0] - got[1]).max() <= 1e-13 * np.abs(got[0]).max()
 
 
 def test_workspace_reset(ctx):
