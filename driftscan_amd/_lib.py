@@ -81,6 +81,10 @@ SIGNATURES = {
     "dm_fisher": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                 c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_i64), c_vp, c_int]),
+    "dm_qestimate": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
+                c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_i64), c_int, c_vp, c_vp,
+                ctypes.POINTER(c_i64), c_int, c_vp]),
     "dm_bt_beam_cyl": (
         c_int, [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int,
                 ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_dbl, c_vp]),
@@ -414,6 +418,33 @@ def _fisher(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals
 
 
 Context.fisher = _fisher
+
+
+QEST_NOISE, QEST_CROSSPOWER, QEST_ZERO_MEAN = 1, 2, 4   # flags of dm_qestimate (include/driftmi.h)
+
+
+def _qestimate(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off, R, x, x_off, y=None,
+               noise=False, crosspower=False, zero_mean=False):
+    """Band-power q of R data columns per m-block, (nblk, nbands [+1], R) f64 on the device; see dm_qestimate in
+    include/driftmi.h.  x (and y): the (nmodes_b x R) c128 columns of every block at element offsets x_off."""
+    nblk, F, K, P, L = [int(x_) for x_ in beam_svd.shape]
+    nbands = int(cl_bands.shape[0])
+    sv, svp = _iarr(svnum)
+    l0a, l0p = _iarr(l0)
+    eo, eop = _larr(evecs_off)
+    vo, vop = _larr(evals_off)
+    nm, nmp = _iarr(nmodes)
+    xo, xop = _larr(x_off)
+    flags = (QEST_NOISE if noise else 0) | (QEST_CROSSPOWER if crosspower else 0) | (QEST_ZERO_MEAN if zero_mean else 0)
+    out = self.empty((nblk, nbands + (1 if noise else 0), int(R)), np.float64)
+    rc = self.lib.dm_qestimate(self.h, nblk, F, K, P, L, self.ptr(beam_svd), svp, l0p, nbands, self.ptr(cl_bands),
+                               self.ptr(evecs), eop, nmp, self.ptr(evals), vop, int(R), self.ptr(x),
+                               None if y is None else self.ptr(y), xop, flags, self.ptr(out))
+    self.check(rc, "dm_qestimate")
+    return out
+
+
+Context.qestimate = _qestimate
 
 
 def _project_diag(self, beam_ut, svnum, dmat, out, out_off, alpha=1.0, accumulate=False):

@@ -239,12 +239,133 @@ class PSEstimation(config.Reader):
                         f.create_dataset(k, data=getattr(self, k))
         parallel.barrier()
 
+    # ---- q estimator (psestimation.py:582-652) ----------------------------------------------------
+    def _cl_device(self):
+        """The band tables on the device as (nbands, F, F, L) plus the f <-> f' symmetry flag, cached across batches."""
+        import torch
+
+        ctx = get_context()
+        cache = self.__dict__.get("_cl_dev")
+        if cache is None or cache[0] is not self.clarray or cache[1].device.index != ctx.device:
+            dev0 = ctx.to_device(np.ascontiguousarray(np.asarray(self.clarray, dtype=np.float64)))
+            cache = (self.clarray, dev0.permute(0, 2, 3, 1).contiguous(), bool(torch.equal(dev0, dev0.transpose(2, 3))))
+            del dev0
+            self.__dict__["_cl_dev"] = cache
+        return cache
+
+    def q_estimator(self, mi, vec1, vec2=None, noise=False):
+        """q_a of the KL-basis data `vec1` (num_kl,) or (num_kl, R) of one m: (nbands [+1],) or (nbands [+1], R).
+
+        With `vec2` the cross estimate Re y^H C^-1 Q_a C^-1 x of x = vec1, y = vec2.  The reference forms its y-side sky
+        vector from x (psestimation.py:617-620), so its band terms ignore `vec2` while its noise term uses it; here the
+        y side is projected from `vec2`, the evident intent.  `noise=True` appends the projection
+        on the noise, weighted (crosspower ? 0 : 1) + (zero_mean ? lambda : 0)."""
+        return self.q_estimator_batch([mi], [vec1], None if vec2 is None else [vec2], noise=noise)[0]
+
+    def _q_batches(self, ms, idx, R):
+        """Batches (positions into ms) under the device budget: the sky-side columns (nblk, L, F, R), the modes and the
+        per-chunk partial sums of the band terms."""
+        bt = self.kltrans.beamtransfer
+        tel = self.telescope
+        F, L = tel.nfreq, tel.lmax + 1
+        nb = self.clarray.shape[0]
+        budget = self.ps_chunk_gb * (1 << 30)
+        cur, used = [], 0.0
+        for i in idx:
+            n = float(bt.ndof(ms[i]))
+            need = 16.0 * (2 * L * F * R + 2 * n * R + n * n) + 8.0 * nb * (L / 4.0 + 1.0) * R
+            if cur and used + need > budget:
+                yield cur
+                cur, used = [], 0.0
+            cur.append(i)
+            used += need
+        if cur:
+            yield cur
+
+    def q_estimator_batch(self, ms, vecs1, vecs2=None, noise=False):
+        """`q_estimator` for several m: [q of ms[i]] with vecs1[i] (and vecs2[i]) the data of ms[i].  One `dm_qestimate`
+        per batch of m under `ps_chunk_gb`; the modes may be host arrays (KL files) or device rows (mode cache)."""
+        from .beamtransfer import BeamTransferNoSVD
+
+        if isinstance(self.kltrans.beamtransfer, BeamTransferNoSVD):
+            raise NotImplementedError("q_estimator needs the SVD products: BeamTransferNoSVD has none")
+        if self.clarray is None:
+            self.genbands()
+        ms = [int(mi) for mi in ms]
+        if len(vecs1) != len(ms) or (vecs2 is not None and len(vecs2) != len(ms)):
+            raise ValueError("q_estimator_batch: one data set per m")
+        as_arr = lambda v: v if hasattr(v, "device") else np.asarray(v)   # noqa: E731  (device tensors stay put)
+        vecs1 = [as_arr(v) for v in vecs1]
+        vecs2 = None if vecs2 is None else [as_arr(v) for v in vecs2]
+        nq = self.nbands + (1 if noise else 0)
+        out = [None] * len(ms)
+        modes = {}
+        groups = {}   # columns per data set -> positions: one call per batch of equal width
+        for i, mi in enumerate(ms):
+            v1 = vecs1[i]
+            if v1.ndim not in (1, 2) or (vecs2 is not None and tuple(vecs2[i].shape) != tuple(v1.shape)):
+                raise ValueError("q_estimator: vectors of m=%d must be (num_kl,) or (num_kl, R) and agree" % mi)
+            R = 1 if v1.ndim == 1 else int(v1.shape[1])
+            ev, E = self.kltrans.modes_m(mi, device=True)
+            if ev is None or R == 0:
+                out[i] = np.zeros(out_shape(v1, nq))
+                continue
+            if v1.shape[0] != ev.size:
+                raise ValueError("q_estimator: m=%d has %d KL modes, the data %d" % (mi, ev.size, v1.shape[0]))
+            modes[i] = (ev, E)
+            groups.setdefault(R, []).append(i)
+        for R, idx in groups.items():
+            for ii in self._q_batches(ms, idx, R):
+                for i, q in zip(ii, self._q_call([ms[i] for i in ii], ii, modes, vecs1, vecs2, noise, R)):
+                    out[i] = q.reshape(out_shape(vecs1[i], nq))
+        return out
+
+    def _q_call(self, batch, ii, modes, vecs1, vecs2, noise, R):
+        import torch
+
+        ctx = get_context()
+        bt = self.kltrans.beamtransfer
+        cl = self._cl_device()[1]
+        nmodes = np.array([modes[i][0].size for i in ii], dtype=np.int64)
+        bsvd = bt._stacked_products(batch, "beam_svd")
+        svnum = np.stack([bt._svd_num(mi)[0] for mi in batch])
+        ndofs = svnum.sum(axis=1)
+        eoff, _ = _linear_offsets(nmodes * ndofs)
+        voff, vtot = _linear_offsets(nmodes)
+        Vh = np.zeros(max(vtot, 1), dtype=np.float64)
+        parts = []
+        for k, i in enumerate(ii):
+            ev, E = modes[i]
+            if E.shape[1] != ndofs[k]:
+                raise Exception("KL modes of m=%d have length %d, the SVD basis %d" % (batch[k], E.shape[1], ndofs[k]))
+            parts.append(ctx.to_device(np.ascontiguousarray(E).ravel()) if isinstance(E, np.ndarray) else E.reshape(-1))
+            Vh[voff[k] : voff[k] + nmodes[k]] = ev
+        Ed = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
+
+        def columns(vecs):
+            cols = [v.reshape(-1, R) for v in (vecs[i] for i in ii)]
+            if all(isinstance(c, np.ndarray) for c in cols):
+                return ctx.to_device(np.ascontiguousarray(np.concatenate(cols).astype(np.complex128, copy=False)))
+            return torch.cat([c if not isinstance(c, np.ndarray) else ctx.to_device(np.ascontiguousarray(c))
+                              for c in cols]).to(torch.complex128).contiguous()
+
+        x = columns(vecs1)
+        y = None if vecs2 is None else columns(vecs2)
+        q = ctx.qestimate(bsvd, svnum, np.array(batch), cl, Ed, eoff, nmodes, ctx.to_device(Vh), voff, R, x, voff * R,
+                          y=y, noise=noise, crosspower=bool(self.crosspower), zero_mean=bool(self.zero_mean))
+        return list(q.cpu().numpy())
+
     def fisher_file(self):
         return storage.File(self.psdir + "/fisher.hdf5", "r")
 
     def fisher_bias(self):
         with storage.File(self.psdir + "/fisher.hdf5", "r") as f:
             return f["fisher"][:], f["bias"][:]
+
+
+def out_shape(vec, nq):
+    """Shape of the q of one data set: (nq,) for a vector, (nq, R) for R columns."""
+    return (nq,) if len(vec.shape) == 1 else (nq, int(vec.shape[1]))
 
 
 def _linear_offsets(sizes):

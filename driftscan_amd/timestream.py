@@ -236,6 +236,31 @@ class Timestream(object):
         mlist = list(range(1 if self.no_m_zero else 0, self.telescope.mmax + 1))
         self._alm_to_map(make_alm, nside, mapname, mlist=mlist)
 
+    # ---- power spectrum (timestream.py:463-523) -------------------------------------------------------------------
+    @property
+    def _psfile(self):
+        return self.output_directory + ("/ps_%s.hdf5" % self.psname)
+
+    def set_psestimator(self, psname):
+        self.psname = psname
+
+    def powerspectrum(self):
+        """Band powers p = F^-1 (sum_m q_m - bias) of this timestream's KL m-modes, written to `ps_<psname>.hdf5`."""
+        if os.path.exists(self._psfile):
+            return None
+        ps = self.manager.psestimators[self.psname]
+        ps.genbands()
+        mine = parallel.partition(_ps_mlist(self.telescope.mmax, self.no_m_zero))
+        qs = ps.q_estimator_batch(mine, [self.mmode_kl(mi) for mi in mine])
+        qtotal = parallel.allreduce_sum(np.sum(qs, axis=0) if qs else np.zeros(ps.nbands))
+        fisher, bias = ps.fisher_bias()
+        powerspectrum = np.dot(np.linalg.inv(fisher), qtotal - bias)
+        if parallel.rank0():
+            _write_ps(self._psfile, fisher, ps.band_power, powerspectrum)
+        ps.delbands()
+        parallel.barrier()
+        return powerspectrum
+
     # ---- persistence (timestream.py:525-566) -----------------------------------------------------------------
     def __getstate__(self):
         # The reference pickles its ProductManager along with the object; the manager here owns device buffers, so the
@@ -265,6 +290,55 @@ class Timestream(object):
     def load(cls, tsdir):
         with open(cls(tsdir, tsdir)._picklefile, "rb") as f:
             return pickle.load(f)
+
+
+def _ps_mlist(mmax, no_m_zero):
+    return list(range(1 if no_m_zero else 0, mmax + 1))
+
+
+def _write_ps(psfile, fisher, band_power, powerspectrum):
+    cv = np.linalg.inv(fisher)
+    err = cv.diagonal() ** 0.5
+    with storage.File(psfile, "w") as f:
+        f.create_dataset("fisher", data=fisher)
+        f.create_dataset("covariance", data=cv)
+        f.create_dataset("error", data=err)
+        f.create_dataset("correlation", data=cv / np.outer(err, err))
+        f.create_dataset("bandpower", data=band_power)
+        f.create_dataset("powerspectrum", data=powerspectrum)
+
+
+def cross_powerspectrum(timestreams, psname, psfile):
+    """Cross band powers (nstream, nstream, nbands) of every pair of timestreams (timestream.py:570-642): the pairs
+    ti < tj are estimated and mirrored, the diagonal stays zero.  Every pair of an m is a column of one q call."""
+    if os.path.exists(psfile):
+        return None
+    products = timestreams[0].manager
+    ps = products.psestimators[psname]
+    ps.genbands()
+    nstream = len(timestreams)
+    pairs = [(ti, tj) for ti in range(nstream) for tj in range(ti + 1, nstream)]
+    mine = parallel.partition(_ps_mlist(products.telescope.mmax, timestreams[0].no_m_zero))
+    qloc = np.zeros((nstream, nstream, ps.nbands), dtype=np.float64)
+    if pairs and mine:
+        xs, ys = [], []
+        for mi in mine:
+            data = [ts.mmode_kl(mi) for ts in timestreams]
+            xs.append(np.stack([data[ti] for ti, _ in pairs], axis=1))
+            ys.append(np.stack([data[tj] for _, tj in pairs], axis=1))
+        for q in ps.q_estimator_batch(mine, xs, ys):   # (nbands, npairs)
+            for k, (ti, tj) in enumerate(pairs):
+                qloc[ti, tj] += q[:, k]
+                qloc[tj, ti] += q[:, k]
+    qtotal = parallel.allreduce_sum(qloc)
+    fisher, bias = ps.fisher_bias()
+    qtotal = (qtotal - bias).reshape(nstream**2, ps.nbands).T
+    powerspectrum = np.dot(np.linalg.inv(fisher), qtotal).T.reshape(nstream, nstream, ps.nbands)
+    if parallel.rank0():
+        _write_ps(psfile, fisher, ps.band_power, powerspectrum)
+    ps.delbands()
+    parallel.barrier()
+    return powerspectrum
 
 
 def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, **kwargs):

@@ -257,6 +257,29 @@ int dm_fisher(dm_ctx* ctx, int nblk, int F, int K, int P, int L, const void* bea
               const int64_t* evecs_off_host, const int* nmodes_host, const double* evals_dev,
               const int64_t* evals_off_host, void* fisher_dev, int cl_symmetric);
 
+/* Quadratic estimator of the band powers for R data columns per m-block, nblk m-blocks:
+ *   x0 = X / (lam + 1),  x2 = B_T^H E^H x0 (temperature only),  q[a] = Re sum_{l >= l0} y2_l^H C^a_l x2_l
+ * with y2 formed the same way from Y (or y2 = x2 without Y).
+ *   beam_svd_dev, svnum_host, l0_host          as for dm_project_cov
+ *   cl_bands_dev (nbands, F, F, L) f64         band angular power spectra (temperature block), as for dm_fisher
+ *   evecs_dev + evecs_off_host[b]              (nmodes_host[b] x ndof_b) c128, rows = KL modes
+ *   evals_dev + evals_off_host[b]              their eigenvalues (f64)
+ *   x_dev + x_off_host[b]                      (nmodes_host[b] x R) c128 data columns (KL coefficients)
+ *   y_dev + x_off_host[b]                      the second data set of a cross estimate, or NULL
+ *   flags  DM_QEST_NOISE: append the noise term sum_i Re(x0_i conj(y0_i)) w_i, w = (DM_QEST_CROSSPOWER ? 0 : 1)
+ *          + (DM_QEST_ZERO_MEAN ? lam_i : 0)
+ *   q_dev (nblk, nbands [+1], R) f64           out (zero for blocks without modes)
+ * F <= 256.  Fixed-order sums throughout: repeated calls are bit-identical.  Synchronises.
+ * Replaces: PSEstimation.q_estimator, drift/core/psestimation.py:582-652 (with Y projected from Y). */
+#define DM_QEST_NOISE 1
+#define DM_QEST_CROSSPOWER 2
+#define DM_QEST_ZERO_MEAN 4
+int dm_qestimate(dm_ctx* ctx, int nblk, int F, int K, int P, int L, const void* beam_svd_dev, const int* svnum_host,
+                 const int* l0_host, int nbands, const double* cl_bands_dev, const void* evecs_dev,
+                 const int64_t* evecs_off_host, const int* nmodes_host, const double* evals_dev,
+                 const int64_t* evals_off_host, int R, const void* x_dev, const void* y_dev, const int64_t* x_off_host,
+                 int flags, double* q_dev);
+
 /* ---- beam-transfer generation (cylinder telescopes) --------------------------- */
 /* Host geometry shared by the three calls below: ring_cth_host / ring_sth_host hold
  * cos / sin of the colatitude of the 4*nside-1 HEALPix rings; frame_host (9 doubles)
