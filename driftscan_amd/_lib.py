@@ -85,6 +85,14 @@ SIGNATURES = {
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                 c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_i64), c_int, c_vp, c_vp,
                 ctypes.POINTER(c_i64), c_int, c_vp]),
+    "dm_psmc_draw": (
+        c_int, [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_i64), ctypes.c_uint64,
+                c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_i64)]),
+    "dm_psmc_moments": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "dm_psmc_alt": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
+                c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_i64), c_int, c_vp,
+                ctypes.POINTER(c_i64), c_int, c_vp, c_vp]),
     "dm_bt_beam_cyl": (
         c_int, [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int,
                 ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_dbl, c_vp]),
@@ -445,6 +453,64 @@ def _qestimate(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, ev
 
 
 Context.qestimate = _qestimate
+
+
+PSMC_NORMAL, PSMC_RADEMACHER = 0, 1   # kinds of dm_psmc_draw (include/driftmi.h)
+
+
+def _psmc_draw(self, ms, nmodes, R, seed, stream=0, kind=PSMC_NORMAL, power=0, s0=0, evals=None, evals_off=None):
+    """Sample columns of the Monte-Carlo estimators, (sum_b nmodes_b * R,) c128 on the device: block b's
+    (nmodes_b x R) draws back to back; see dm_psmc_draw in include/driftmi.h."""
+    mm, mmp = _iarr(ms)
+    nm, nmp = _iarr(nmodes)
+    off = np.concatenate([[0], np.cumsum(nm.astype(np.int64) * int(R))])
+    xo, xop = _larr(off[:-1])
+    vop = None
+    if evals_off is not None:
+        vo, vop = _larr(evals_off)
+    out = self.empty((max(int(off[-1]), 1),), np.complex128)
+    rc = self.lib.dm_psmc_draw(self.h, len(mm), mmp, nmp, None if evals is None else self.ptr(evals), vop,
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(kind), int(power), int(s0), int(R),
+                               self.ptr(out), xop)
+    self.check(rc, "dm_psmc_draw")
+    return out[: int(off[-1])]
+
+
+def _psmc_moments(self, q):
+    """(mean (nblk, nq), covariance (nblk, nq, nq)) on the device of q (nblk, nq, ns) f64; see dm_psmc_moments."""
+    nblk, nq, ns = [int(x_) for x_ in q.shape]
+    q = q.contiguous()
+    mean = self.empty((nblk, nq), np.float64)
+    cov = self.empty((nblk, nq, nq), np.float64)
+    self.check(self.lib.dm_psmc_moments(self.h, nblk, nq, ns, self.ptr(q), self.ptr(mean), self.ptr(cov)),
+               "dm_psmc_moments")
+    return mean, cov
+
+
+def _psmc_alt(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off, R, x, x_off, nsamples,
+              want_vecs=False):
+    """Stochastic-trace Fisher matrices (nblk, nbands, nbands) c128 on the device of R weighted draws per block (and
+    the band vectors (nbands, sum_b nmodes_b R) c128 with `want_vecs`); see dm_psmc_alt in include/driftmi.h."""
+    nblk, F, K, P, L = [int(x_) for x_ in beam_svd.shape]
+    nbands = int(cl_bands.shape[0])
+    sv, svp = _iarr(svnum)
+    l0a, l0p = _iarr(l0)
+    eo, eop = _larr(evecs_off)
+    vo, vop = _larr(evals_off)
+    nm, nmp = _iarr(nmodes)
+    xo, xop = _larr(x_off)
+    out = self.empty((nblk, nbands, nbands), np.complex128)
+    vecs = self.empty((nbands, max(int(nm.astype(np.int64).sum()) * int(R), 1)), np.complex128) if want_vecs else None
+    rc = self.lib.dm_psmc_alt(self.h, nblk, F, K, P, L, self.ptr(beam_svd), svp, l0p, nbands, self.ptr(cl_bands),
+                              self.ptr(evecs), eop, nmp, self.ptr(evals), vop, int(R), self.ptr(x), xop, int(nsamples),
+                              self.ptr(vecs), self.ptr(out))
+    self.check(rc, "dm_psmc_alt")
+    return (out, vecs) if want_vecs else out
+
+
+Context.psmc_draw = _psmc_draw
+Context.psmc_moments = _psmc_moments
+Context.psmc_alt = _psmc_alt
 
 
 def _project_diag(self, beam_ut, svnum, dmat, out, out_off, alpha=1.0, accumulate=False):

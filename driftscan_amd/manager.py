@@ -5,7 +5,7 @@ import os
 
 import yaml
 
-from . import beamtransfer, cylinder, doublekl, kltransform, parallel, psestimation, storage
+from . import beamtransfer, cylinder, doublekl, kltransform, parallel, psestimation, psmc, storage
 
 logger = logging.getLogger(__name__)
 
@@ -16,8 +16,11 @@ teltype_dict = {
 
 kltype_dict = {"KLTransform": kltransform.KLTransform, "DoubleKL": doublekl.DoubleKL}
 # The reference's Monte-Carlo estimators ("MonteCarlo", "MonteCarloAlt") estimate the same Fisher matrix from
-# random realisations; here they resolve to the exact computation (the expectation they converge to), with a warning.
-pstype_dict = {"Full": psestimation.PSExact, "MonteCarlo": psestimation.PSExact, "MonteCarloAlt": psestimation.PSExact}
+# random realisations.  By default they resolve to the exact computation (the expectation they converge to), with a
+# warning, so that existing configurations keep their results; an entry with `exact: No` gets the sampled estimator.
+pstype_dict = {"Full": psestimation.PSExact, "MonteCarlo": psestimation.PSExact, "MonteCarloAlt": psestimation.PSExact,
+               "Cross": psmc.CrossPower}
+pstype_sampled = {"MonteCarlo": psmc.PSMonteCarlo, "MonteCarloAlt": psmc.PSMonteCarloAlt}
 
 
 
@@ -108,9 +111,12 @@ class ProductManager(object):
             raise Exception("Require a psfisher section if config: psfisher is Yes.")
         for psentry in yconf.get("psfisher", []) or []:
             psclass = _resolve_class(psentry["type"], pstype_dict, "PS estimator")
-            if isinstance(psentry["type"], str) and psentry["type"].startswith("MonteCarlo"):
-                logger.warning("psfisher type %s: computing the exact Fisher matrix instead of a Monte-Carlo estimate"
-                               % psentry["type"])
+            if isinstance(psentry["type"], str) and psentry["type"] in pstype_sampled:
+                if not psentry.get("exact", True):
+                    psclass = pstype_sampled[psentry["type"]]
+                else:
+                    logger.warning("psfisher type %s: computing the exact Fisher matrix instead of a Monte-Carlo estimate "
+                                   "(set `exact: No` in the entry for the sampled estimator)" % psentry["type"])
             klname = psentry["klname"]
             psname = psentry.get("name", "ps")
             if klname not in self.kltransforms:

@@ -280,6 +280,47 @@ int dm_qestimate(dm_ctx* ctx, int nblk, int F, int K, int P, int L, const void* 
                  const int64_t* evals_off_host, int R, const void* x_dev, const void* y_dev, const int64_t* x_off_host,
                  int flags, double* q_dev);
 
+/* ---- Monte-Carlo Fisher estimators ------------------------------------------- */
+/* dm_psmc_draw: sample columns for the Monte-Carlo estimators, drawn on the device.
+ *   x_dev + x_off_host[b]  (nmodes_host[b] x R) c128 out: column r is sample s0 + r of m = m_host[b]
+ * Draw (i, s) of block b is Philox4x32-10 with key = seed (low word first) and counter (i, s, m, stream):
+ *   kind DM_PSMC_NORMAL      complex standard normal, E|z|^2 = 1: Box-Muller with |z| = sqrt(-log u1),
+ *                            arg z = 2 pi u2, u1 / u2 the 53-bit uniforms in (0, 1] of words (0, 1) / (2, 3):
+ *                            u = ((w_a >> 5) 2^26 + (w_b >> 6) + 1) 2^-53
+ *   kind DM_PSMC_RADEMACHER  real -1 if the top bit of word 0 is set, else +1
+ * scaled by (lam_i + 1)^(power / 2), power in {-1, 0, 1} (evals_dev + evals_off_host[b], unused for power 0).
+ * A draw depends on (seed, m, s, i, stream) alone: the first k of n columns equal a k-column draw bit for bit.
+ * Synchronises.
+ * Replaces: PSMonteCarlo.gen_sample, drift/core/psmc.py:26-53 (cora's complex_std_normal), and the Z_2 draws of
+ *           PSMonteCarloAlt.gen_vecs, drift/core/psmc.py:111-128. */
+#define DM_PSMC_NORMAL 0
+#define DM_PSMC_RADEMACHER 1
+int dm_psmc_draw(dm_ctx* ctx, int nblk, const int* m_host, const int* nmodes_host, const double* evals_dev,
+                 const int64_t* evals_off_host, uint64_t seed, int stream, int kind, int power, int s0, int R,
+                 void* x_dev, const int64_t* x_off_host);
+
+/* dm_psmc_moments: the sample moments of q (nblk, nq, ns) f64: mean_dev (nblk, nq) and the unbiased covariance
+ * cov_dev (nblk, nq, nq) (np.cov, ddof = 1), two passes in a fixed order.  ns >= 2.  Synchronises.
+ * Replaces: the np.cov / mean of PSMonteCarlo._work_fisher_bias_m, drift/core/psmc.py:72-89, and of
+ *           CrossPower._work_fisher_bias_m, drift/core/crosspower.py:31-45. */
+int dm_psmc_moments(dm_ctx* ctx, int nblk, int nq, int ns, const double* q_dev, double* mean_dev, double* cov_dev);
+
+/* dm_psmc_alt: the stochastic-trace Fisher estimate of R sample columns per m-block:
+ *   v_a = W E B_T C_a B_T^H E^H X,  W = diag((lam + 1)^-1/2),  F_ab = sum_{i, s} v_a[i, s] conj(v_b[i, s]) / nsamples
+ *   beam_svd_dev ... evals_off_host            as for dm_qestimate
+ *   x_dev + x_off_host[b]                      (nmodes_host[b] x R) c128 draws, already weighted by (lam + 1)^-1/2
+ *   v_dev                                      NULL, or out (nbands, T) c128, T = sum_b nmodes_b R: v_a of block b
+ *                                              is (nmodes_b x R) at a T + sum_{b' < b} nmodes_b' R
+ *   fisher_dev (nblk, nbands, nbands) c128     out (zero for blocks without modes)
+ * Z_a = C_a x2 (band_apply) is formed for every band on the matrix cores and projected back by grouped ZGEMMs; the
+ * Gram sums are partial sums per chunk reduced in a fixed order.  F <= 256, nbands <= 128.  Synchronises.
+ * Replaces: PSMonteCarloAlt.gen_vecs and _work_fisher_bias_m, drift/core/psmc.py:111-199. */
+int dm_psmc_alt(dm_ctx* ctx, int nblk, int F, int K, int P, int L, const void* beam_svd_dev, const int* svnum_host,
+                const int* l0_host, int nbands, const double* cl_bands_dev, const void* evecs_dev,
+                const int64_t* evecs_off_host, const int* nmodes_host, const double* evals_dev,
+                const int64_t* evals_off_host, int R, const void* x_dev, const int64_t* x_off_host, int nsamples,
+                void* v_dev, void* fisher_dev);
+
 /* ---- beam-transfer generation (cylinder telescopes) --------------------------- */
 /* Host geometry shared by the three calls below: ring_cth_host / ring_sth_host hold
  * cos / sin of the colatitude of the 4*nside-1 HEALPix rings; frame_host (9 doubles)
