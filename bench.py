@@ -9,7 +9,7 @@ description resident (beam-transfer generation -> three-stage SVD compression + 
 covariance projection + generalised eigenproblem of the KL transform); products stay in
 HBM, file output is not part of the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--mode weak|sharded]
+    python bench.py --gpus N --steps K --warmup W [--mode weak|sharded] [--full]
 
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset): this process starts N
 rank processes itself — before it makes any GPU call — one per GPU over RCCL ("nccl"), relays
@@ -26,11 +26,17 @@ Modes (m-blocks are independent: no data-path collective in either; weak is the 
            matrix (the Fisher assembly pattern, psestimation.py:506-507) are inside the timed
            region.  value = 129 * steps / time ("scaling": "strong").
 
+A plain run does only what the headline figure needs: set-up, the untimed priming passes, the W warm-up steps, the K
+timed steps, `--dump-outputs` if given, and the line.  `--full` adds, after the timed region, everything else the line can
+carry: `stage_ms` / `stages` and the extended kernel classes (untimed passes of their own), BT-gen alone at both readings of
+the SHT, `roofline`, `cpu_baseline` with `parity`, and `north_star` (`--no-cpu-baseline` / `--no-north-star` leave either out).
+
 Output (rank 0): the full record as `bench_detail {...}` on an EARLIER stdout line and in `bench_detail.json`
-($DRIFT_BENCH_DETAIL), then — LAST — the compact driver line (< 8 KB; `benchlib/line.py`): the contract keys, `config`, `roofline`
-(dominant kernel class: algorithmic flops per launch / its average launch duration by HIP events over the timed region, peak,
-frac, PMC traffic per launch), `cpu_baseline` (the oracle on the host cores, N = 1 only), `parity`, `stage_ms`, per-rank step
-times, `north_star` (live shares of the configs[2] job; at N > 1 the real N-rank job).
+($DRIFT_BENCH_DETAIL), then — LAST — the compact driver line (< 8 KB; `benchlib/line.py`): the contract keys, `config`,
+per-rank step times and, with `--full`, `roofline` (dominant kernel class: algorithmic flops per launch / its average launch
+duration by HIP events over the timed region, peak, frac, PMC traffic per launch), `cpu_baseline` (the oracle on the host
+cores, N = 1 only), `parity`, `stage_ms`, `north_star` (live shares of the configs[2] job; at N > 1 the real N-rank job);
+without it those are null or absent.
 
 The legs live in `benchlib/`: `common` (telescopes, peaks, build id), `cpu` (CPU baseline + parity), `jobs` (shares and jobs
 through `ProductManager.generate()`), `northstar` (the north-star leg of the default line), `line` (the compact line).
@@ -86,10 +92,13 @@ def parse_args(argv=None):
                          "the per-rank step time behind the expected strong-scaling curve (DESIGN.md section 6)")
     ap.add_argument("--no-rebalance", action="store_true",
                     help="--mode sharded: keep the m-ranges of the static cost model instead of rebalancing them on measured times")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="configs1: after the timed steps, also the per-stage and BT-gen passes, the roofline, the CPU baseline "
+                         "with its parity check and the north-star leg (a plain run measures the headline figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
     ap.add_argument("--no-north-star", action="store_true",
-                    help="skip the north-star leg of the default line (one rank's share of the configs[2] job through "
-                         "ProductManager.generate() after the timed configs[1] region; rank 0 at --gpus 1 only)")
+                    help="--full: skip the north-star leg (one rank's share of the configs[2] job through "
+                         "ProductManager.generate() after the timed configs[1] region; at --gpus N > 1 the real N-rank job)")
     ap.add_argument("--north-star-share", default=os.environ.get("DRIFT_BENCH_NS_SHARE", "0/8"),
                     help="which share the north-star leg runs (r/N of the configs[2] job)")
     ap.add_argument("--all-modes", action="store_true",
@@ -360,6 +369,187 @@ def run_configs4(args):
     return 0
 
 
+def full_figures(args, tel, bt, kl, ctx, m_range, collect, rank, world, prof, nblocks):
+    """`--full`: what the headline figure does not need, after the timed region.  Every rank runs the per-stage passes
+    (`collect` keeps their collectives matched); rank 0 adds BT-gen alone at both readings of the SHT, the roofline of the
+    dominant kernel class over the timed region's event records `prof`, the per-stage fractions of the fp64 MFMA peak and
+    (N = 1) the CPU baseline with its parity object.  Returns those entries of the line on rank 0, None on the others."""
+    import numpy as np
+    import torch
+
+    from driftscan_amd import device
+
+    stage = []
+    # The per-stage wall times (`stage_ms`, `stages`) come from a few UNTIMED passes after the timed region: they need
+    # a wait after BT-gen that the pipeline itself does not have (the host prepares the SVD stage while the GPU still
+    # transforms), so their sum is a little above ms_per_step.
+    # ... and they run at profiling level 2: every remaining kernel of the path is bracketed too (the "extended"
+    # classes; their ~200 extra event pairs per step are kept out of the timed region)
+    nstage = min(args.steps, 3)
+    for c in list(device._all):
+        c.prof_reset(2 if os.environ.get("DRIFT_BENCH_NOPROF") != "1" else 0)
+    for _ in range(nstage):
+        hot_path_step(tel, bt, kl, ctx, stage_times=stage, streams=args.streams, m_range=m_range, collect=collect)
+    torch.cuda.synchronize()
+    ext = {}
+    for c in list(device._all):
+        for k, v in c.prof_report().items():
+            if k in EXT_CLASSES:
+                a = ext.setdefault(k, dict(ms=0.0, flops=0.0, launches=0))
+                a["ms"] += v["ms"]; a["flops"] += v["flops"]; a["launches"] += v["launches"]
+    # BT-gen alone at both readings of the reference's SHT: plain quadrature (healpy iter = 0) and healpy's documented
+    # default iter = 3 (the telescope's default, what the timed region ran)
+    bt_ms = {}
+    if rank == 0:
+        from driftscan_amd import btgen as _btgen
+
+        it_keep = tel.sht_iter
+        for it in (0, 3):
+            tel.sht_iter = it
+            ts = []
+            for _ in range(4):
+                ctx.sync(); torch.cuda.synchronize()
+                tb0 = time.perf_counter()
+                _bm = _btgen.beam_m_all(tel, ctx=ctx, m_range=m_range)
+                ctx.sync(); torch.cuda.synchronize()
+                ts.append(time.perf_counter() - tb0)
+                del _bm
+            bt_ms[it] = 1e3 * min(ts[1:])
+        tel.sht_iter = it_keep
+    if rank != 0:
+        return None
+    st = np.array(stage).mean(axis=0)
+    trd_stride = int(ctx.lib.dm_prof_trd_stride())  # the column loop is sampled; the library scales the figures
+    dom = max(prof, key=lambda k: prof[k]["ms"]) if prof else None
+    roofline = None
+    # HBM bytes per launch of the dominant kernel: PMC counters cannot be read from inside this
+    # process, so the figure comes from the committed rocprofv3 --pmc passes of this same
+    # command (profiles/*_pmc_traffic.json, made by scratch/run_profiles.sh + make_traffic_json.py).
+    traffic, traffic_src, mfma_busy, valu_busy = None, None, None, None
+    try:
+        import glob
+
+        bid = build_id()
+        tj = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_traffic.json")))
+        if tj and dom is not None:
+            rec = json.load(open(tj[-1]))
+            if rec.get("_build_id") != bid:
+                # counters of another build of the kernels say nothing about this one
+                traffic_src = "%s is stale (build %s, running %s): traffic not reported" % (
+                    os.path.relpath(tj[-1], ROOT), rec.get("_build_id"), bid)
+                rec = {}
+            key = {"zgemm_grouped": "zgemm_grouped_kernel<false, false>", "trd_symv": "trd_symv_kernel",
+                   "trd_wx": "trd_wx_kernel", "gemm_grouped_realB": "zgemm_grouped_kernel<true, false>",
+                   "dgemm_grouped": "dgemm_grouped_kernel", "jac_inner": "jac_inner_kernel<false>",
+                   "jac_gram": "jac_gram_kernel", "jac_apply": "jac_apply_kernel",
+                   "sb_chase": "sb_chase_pos_kernel", "sb_q2_apply": "sb_q2_apply_kernel<4>",
+                   "sb_panel_qr": "sb_panel_fused_kernel"}.get(dom)
+            if dom == "zgemm_grouped" and key not in rec:
+                key = next((k for k in ("zgemm4_grouped_kernel<false, false, 1, 2>", "zgemm4_grouped_kernel<false, false, 1>")
+                            if k in rec), key)
+            if key is not None and key not in rec:  # kernels compiled inside a namespace (dm_trd32::trd_symv_kernel)
+                key = next((k for k in rec if k.endswith("::" + key)), key)
+            if key in rec:
+                traffic = rec[key]["fetch_bytes_per_launch"] + rec[key]["write_bytes_per_launch"]
+                traffic_src = os.path.relpath(tj[-1], ROOT)
+        mj = sorted(f for f in glob.glob(os.path.join(ROOT, "profiles", "*_pmc_mfma.json")) if "configs2" not in os.path.basename(f))
+        if mj:
+            mrec = json.load(open(mj[-1]))
+            if mrec.get("_build_id") == bid:
+                mfma_busy = dict(mrec, source=os.path.relpath(mj[-1], ROOT))
+            else:
+                mfma_busy = dict(stale="%s was taken at build %s, this is %s" % (os.path.relpath(mj[-1], ROOT),
+                                                                                  mrec.get("_build_id"), bid))
+        vj = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_valu.json")))
+        if vj:   # vector-ALU utilisation by counter: what the latency-bound classes (chase, jac_inner, q2, panel QR) have
+            vrec = json.load(open(vj[-1]))   # instead of a flop rate
+            if vrec.get("_build_id") == bid:
+                valu_busy = dict({k: (round(v["valu_busy"], 4) if isinstance(v, dict) else v) for k, v in vrec.items()},
+                                 source=os.path.relpath(vj[-1], ROOT))
+            else:
+                valu_busy = dict(stale="%s was taken at build %s, this is %s" % (os.path.relpath(vj[-1], ROOT),
+                                                                                  vrec.get("_build_id"), bid))
+    except Exception:
+        traffic, traffic_src = None, None
+    if dom is not None:
+        p = prof[dom]
+        secs = p["ms"] * 1e-3
+        if dom in HBM_CLASSES:  # work counter = algorithmic bytes
+            ach = p["flops"] / secs / 1e9 if secs > 0 else 0.0
+            roofline = dict(bound="hbm", kernel=dom, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s",
+                            frac=ach / HBM_PEAK_GBS, traffic=traffic, traffic_unit="bytes/launch",
+                            traffic_source=traffic_src, launches=p["launches"],
+                            avg_launch_us=1e3 * p["ms"] / max(p["launches"], 1),
+                            bytes_per_launch=p["flops"] / max(p["launches"], 1),
+                            sampling="every %dth launch of the column loop is bracketed by events (position "
+                                     "walking through the panels); time, bytes and `launches` are the samples "
+                                     "scaled by %d" % (trd_stride, trd_stride))
+        else:
+            ach = p["flops"] / secs / 1e12 if secs > 0 else 0.0
+            roofline = dict(bound="mfma", kernel=dom, achieved=ach, peak=FP64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
+                            frac=ach / FP64_MFMA_PEAK_TFLOPS, traffic=traffic, traffic_unit="bytes/launch",
+                            traffic_source=traffic_src, launches=p["launches"],
+                            avg_launch_us=1e3 * p["ms"] / max(p["launches"], 1),
+                            flops_per_launch=p["flops"] / max(p["launches"], 1))
+            if dom in VALU_CLASSES:
+                roofline["pipe"] = ("fp64 VALU (the kernel issues no MFMA; on MI355X the fp64 vector peak equals the "
+                                    "fp64 matrix peak, 78.6 TFLOP/s)")
+        roofline["build_id"] = build_id()
+        # every instrumented class, so that the cross-checks (sum of kernel time <= wall time) can be made; the
+        # extended classes come from the untimed stage passes (profiling level 2)
+        roofline["classes"] = class_table(prof, args.steps)
+        roofline["classes"].update({k: dict(v, source="untimed stage passes (profiling level 2)")
+                                    for k, v in class_table(ext, nstage).items()})
+        roofline["classes_ms_sum"] = sum(v["ms_per_step"] for v in roofline["classes"].values())
+        # the runner-up class of the other kind, for context (MFMA vs HBM side of the step)
+        others = [k for k in prof if (k in HBM_CLASSES) != (dom in HBM_CLASSES)]
+        if others:
+            o = max(others, key=lambda k: prof[k]["ms"])
+            q = prof[o]
+            if o in HBM_CLASSES:
+                oa = q["flops"] / (q["ms"] * 1e-3) / 1e9
+                roofline["also"] = dict(kernel=o, bound="hbm", achieved=oa, unit="GB/s", frac=oa / HBM_PEAK_GBS,
+                                        ms_per_step=q["ms"] / args.steps)
+            else:
+                oa = q["flops"] / (q["ms"] * 1e-3) / 1e12
+                roofline["also"] = dict(kernel=o, bound="mfma", achieved=oa, unit="TFLOP/s",
+                                        frac=oa / FP64_MFMA_PEAK_TFLOPS, ms_per_step=q["ms"] / args.steps)
+        if mfma_busy is not None:
+            roofline["mfma_busy"] = mfma_busy
+            # the counter figure of the dominant class itself (the heaviest kernel of the class by MFMA cycles)
+            pref = {"zgemm_grouped": "zgemm4_grouped_kernel<false, false", "gemm_grouped_realB": "zgemm4_grouped_kernel<true, false",
+                    "dgemm_grouped": "dgemm_grouped_kernel", "jac_gram": "jac_gram_kernel", "jac_apply": "jac_apply_kernel"}.get(dom)
+            cand = [v for k, v in mfma_busy.items() if pref and k.startswith(pref) and isinstance(v, dict) and "util" in v]
+            if cand:
+                roofline["mfma_busy_dominant"] = max(cand, key=lambda v: v.get("mfma_busy_cycles", 0.0))["util"]
+        if valu_busy is not None:
+            roofline["valu_busy"] = valu_busy
+    # per-stage fractions of SURVEY.md §8(d): algorithmic work of the stage / its wall time / fp64 MFMA peak
+    my_ms = list(range(nblocks)) if m_range is None else list(range(m_range[0], m_range[1] + 1))
+    WA, WB, WC = stage_work(tel, bt, my_ms, nkeep=dict(_NKEEP) if _NKEEP else None)
+    stages = {}
+    for name, W, secs in (("btgen", WA, st[0]), ("svd", WB, st[1]), ("kl", WC, st[2])):
+        tf = W / secs / 1e12 if secs > 0 else 0.0
+        stages[name] = dict(work_flop=W, ms=1e3 * secs, tflops=tf, frac_of_fp64_mfma_peak=tf / FP64_MFMA_PEAK_TFLOPS)
+    cpu, parity = None, None
+    if not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N = 1 only
+        keep, spec = {m: None for m in my_ms}, {}
+        hot_path_step(tel, bt, kl, ctx, streams=args.streams, m_range=m_range, keep=keep, spectra=spec)   # untimed: real blocks
+        cpu, parity = cpu_baseline(tel, bt, kl, {m: b for m, b in keep.items() if b is not None}, spec["sv"], spec["ev"])
+        del keep
+    return {
+        "stage_ms": {"btgen": 1e3 * st[0], "svd": 1e3 * st[1], "kl": 1e3 * st[2], "collectives": 1e3 * st[3]},
+        "stages": stages,
+        "btgen": {"btgen_iter0_ms": bt_ms.get(0), "btgen_iter3_ms": bt_ms.get(3),
+                  "ratio": (bt_ms[3] / bt_ms[0]) if bt_ms.get(0) else None,
+                  "note": "BT-gen of the step alone (all blocks of the rank, best of 3 after one warm-up call) with the "
+                          "plain equal-weight quadrature (iter 0) and with healpy's default three refinements (iter 3)"},
+        "roofline": roofline,
+        "cpu_baseline": cpu,
+        "parity": parity,
+    }
+
+
 def main():
     args = parse_args()
     if args.cpu_worker:
@@ -388,7 +578,6 @@ def main():
 
     import tempfile
 
-    import numpy as np
     import torch
 
     from driftscan_amd import device, parallel
@@ -480,7 +669,6 @@ def main():
         gc.freeze()
         for c in list(device._all):  # every context (main thread + stream workers)
             c.prof_reset(os.environ.get("DRIFT_BENCH_NOPROF") != "1")
-        stage = []
         parallel.barrier()
         torch.cuda.synchronize()
         _BUSY[0] = 0.0
@@ -499,42 +687,7 @@ def main():
             for k, v in c.prof_report().items():
                 a = prof.setdefault(k, dict(ms=0.0, flops=0.0, launches=0))
                 a["ms"] += v["ms"]; a["flops"] += v["flops"]; a["launches"] += v["launches"]
-        # The per-stage wall times (`stage_ms`, `stages`) come from a few UNTIMED passes after the timed region: they need
-        # a wait after BT-gen that the pipeline itself does not have (the host prepares the SVD stage while the GPU still
-        # transforms), so their sum is a little above ms_per_step.
-        # ... and they run at profiling level 2: every remaining kernel of the path is bracketed too (the "extended"
-        # classes; their ~200 extra event pairs per step are kept out of the timed region)
-        nstage = min(args.steps, 3)
-        for c in list(device._all):
-            c.prof_reset(2 if os.environ.get("DRIFT_BENCH_NOPROF") != "1" else 0)
-        for _ in range(nstage):
-            hot_path_step(tel, bt, kl, ctx, stage_times=stage, streams=args.streams, m_range=m_range, collect=collect)
-        torch.cuda.synchronize()
-        ext = {}
-        for c in list(device._all):
-            for k, v in c.prof_report().items():
-                if k in EXT_CLASSES:
-                    a = ext.setdefault(k, dict(ms=0.0, flops=0.0, launches=0))
-                    a["ms"] += v["ms"]; a["flops"] += v["flops"]; a["launches"] += v["launches"]
-        # BT-gen alone at both readings of the reference's SHT: plain quadrature (healpy iter = 0) and healpy's documented
-        # default iter = 3 (the telescope's default, what the timed region ran)
-        bt_ms = {}
-        if rank == 0:
-            from driftscan_amd import btgen as _btgen
-
-            it_keep = tel.sht_iter
-            for it in (0, 3):
-                tel.sht_iter = it
-                ts = []
-                for _ in range(4):
-                    ctx.sync(); torch.cuda.synchronize()
-                    tb0 = time.perf_counter()
-                    _bm = _btgen.beam_m_all(tel, ctx=ctx, m_range=m_range)
-                    ctx.sync(); torch.cuda.synchronize()
-                    ts.append(time.perf_counter() - tb0)
-                    del _bm
-                bt_ms[it] = 1e3 * min(ts[1:])
-            tel.sht_iter = it_keep
+        full = full_figures(args, tel, bt, kl, ctx, m_range, collect, rank, world, prof, nblocks) if args.full else None
         parallel.barrier()
         if world > 1 or force_dist:
             import torch.distributed as dist
@@ -556,125 +709,6 @@ def main():
         if args.shard:   # one rank of an emulated N-rank job: its own blocks over its own time
             value = (m_range[1] - m_range[0] + 1) * args.steps / dt
         if rank == 0:
-            st = np.array(stage).mean(axis=0)
-            trd_stride = int(ctx.lib.dm_prof_trd_stride())  # the column loop is sampled; the library scales the figures
-            dom = max(prof, key=lambda k: prof[k]["ms"]) if prof else None
-            roofline = None
-            # HBM bytes per launch of the dominant kernel: PMC counters cannot be read from inside this
-            # process, so the figure comes from the committed rocprofv3 --pmc passes of this same
-            # command (profiles/*_pmc_traffic.json, made by scratch/run_profiles.sh + make_traffic_json.py).
-            traffic, traffic_src, mfma_busy, valu_busy = None, None, None, None
-            try:
-                import glob
-
-                bid = build_id()
-                tj = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_traffic.json")))
-                if tj and dom is not None:
-                    rec = json.load(open(tj[-1]))
-                    if rec.get("_build_id") != bid:
-                        # counters of another build of the kernels say nothing about this one
-                        traffic_src = "%s is stale (build %s, running %s): traffic not reported" % (
-                            os.path.relpath(tj[-1], ROOT), rec.get("_build_id"), bid)
-                        rec = {}
-                    key = {"zgemm_grouped": "zgemm_grouped_kernel<false, false>", "trd_symv": "trd_symv_kernel",
-                           "trd_wx": "trd_wx_kernel", "gemm_grouped_realB": "zgemm_grouped_kernel<true, false>",
-                           "dgemm_grouped": "dgemm_grouped_kernel", "jac_inner": "jac_inner_kernel<false>",
-                           "jac_gram": "jac_gram_kernel", "jac_apply": "jac_apply_kernel",
-                           "sb_chase": "sb_chase_pos_kernel", "sb_q2_apply": "sb_q2_apply_kernel<4>",
-                           "sb_panel_qr": "sb_panel_fused_kernel"}.get(dom)
-                    if dom == "zgemm_grouped" and key not in rec:
-                        key = next((k for k in ("zgemm4_grouped_kernel<false, false, 1, 2>", "zgemm4_grouped_kernel<false, false, 1>")
-                                    if k in rec), key)
-                    if key is not None and key not in rec:  # kernels compiled inside a namespace (dm_trd32::trd_symv_kernel)
-                        key = next((k for k in rec if k.endswith("::" + key)), key)
-                    if key in rec:
-                        traffic = rec[key]["fetch_bytes_per_launch"] + rec[key]["write_bytes_per_launch"]
-                        traffic_src = os.path.relpath(tj[-1], ROOT)
-                mj = sorted(f for f in glob.glob(os.path.join(ROOT, "profiles", "*_pmc_mfma.json")) if "configs2" not in os.path.basename(f))
-                if mj:
-                    mrec = json.load(open(mj[-1]))
-                    if mrec.get("_build_id") == bid:
-                        mfma_busy = dict(mrec, source=os.path.relpath(mj[-1], ROOT))
-                    else:
-                        mfma_busy = dict(stale="%s was taken at build %s, this is %s" % (os.path.relpath(mj[-1], ROOT),
-                                                                                          mrec.get("_build_id"), bid))
-                vj = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_valu.json")))
-                if vj:   # vector-ALU utilisation by counter: what the latency-bound classes (chase, jac_inner, q2, panel QR) have
-                    vrec = json.load(open(vj[-1]))   # instead of a flop rate
-                    if vrec.get("_build_id") == bid:
-                        valu_busy = dict({k: (round(v["valu_busy"], 4) if isinstance(v, dict) else v) for k, v in vrec.items()},
-                                         source=os.path.relpath(vj[-1], ROOT))
-                    else:
-                        valu_busy = dict(stale="%s was taken at build %s, this is %s" % (os.path.relpath(vj[-1], ROOT),
-                                                                                          vrec.get("_build_id"), bid))
-            except Exception:
-                traffic, traffic_src = None, None
-            if dom is not None:
-                p = prof[dom]
-                secs = p["ms"] * 1e-3
-                if dom in HBM_CLASSES:  # work counter = algorithmic bytes
-                    ach = p["flops"] / secs / 1e9 if secs > 0 else 0.0
-                    roofline = dict(bound="hbm", kernel=dom, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s",
-                                    frac=ach / HBM_PEAK_GBS, traffic=traffic, traffic_unit="bytes/launch",
-                                    traffic_source=traffic_src, launches=p["launches"],
-                                    avg_launch_us=1e3 * p["ms"] / max(p["launches"], 1),
-                                    bytes_per_launch=p["flops"] / max(p["launches"], 1),
-                                    sampling="every %dth launch of the column loop is bracketed by events (position "
-                                             "walking through the panels); time, bytes and `launches` are the samples "
-                                             "scaled by %d" % (trd_stride, trd_stride))
-                else:
-                    ach = p["flops"] / secs / 1e12 if secs > 0 else 0.0
-                    roofline = dict(bound="mfma", kernel=dom, achieved=ach, peak=FP64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
-                                    frac=ach / FP64_MFMA_PEAK_TFLOPS, traffic=traffic, traffic_unit="bytes/launch",
-                                    traffic_source=traffic_src, launches=p["launches"],
-                                    avg_launch_us=1e3 * p["ms"] / max(p["launches"], 1),
-                                    flops_per_launch=p["flops"] / max(p["launches"], 1))
-                    if dom in VALU_CLASSES:
-                        roofline["pipe"] = ("fp64 VALU (the kernel issues no MFMA; on MI355X the fp64 vector peak equals the "
-                                            "fp64 matrix peak, 78.6 TFLOP/s)")
-                roofline["build_id"] = build_id()
-                # every instrumented class, so that the cross-checks (sum of kernel time <= wall time) can be made; the
-                # extended classes come from the untimed stage passes (profiling level 2)
-                roofline["classes"] = class_table(prof, args.steps)
-                roofline["classes"].update({k: dict(v, source="untimed stage passes (profiling level 2)")
-                                            for k, v in class_table(ext, nstage).items()})
-                roofline["classes_ms_sum"] = sum(v["ms_per_step"] for v in roofline["classes"].values())
-                # the runner-up class of the other kind, for context (MFMA vs HBM side of the step)
-                others = [k for k in prof if (k in HBM_CLASSES) != (dom in HBM_CLASSES)]
-                if others:
-                    o = max(others, key=lambda k: prof[k]["ms"])
-                    q = prof[o]
-                    if o in HBM_CLASSES:
-                        oa = q["flops"] / (q["ms"] * 1e-3) / 1e9
-                        roofline["also"] = dict(kernel=o, bound="hbm", achieved=oa, unit="GB/s", frac=oa / HBM_PEAK_GBS,
-                                                ms_per_step=q["ms"] / args.steps)
-                    else:
-                        oa = q["flops"] / (q["ms"] * 1e-3) / 1e12
-                        roofline["also"] = dict(kernel=o, bound="mfma", achieved=oa, unit="TFLOP/s",
-                                                frac=oa / FP64_MFMA_PEAK_TFLOPS, ms_per_step=q["ms"] / args.steps)
-                if mfma_busy is not None:
-                    roofline["mfma_busy"] = mfma_busy
-                    # the counter figure of the dominant class itself (the heaviest kernel of the class by MFMA cycles)
-                    pref = {"zgemm_grouped": "zgemm4_grouped_kernel<false, false", "gemm_grouped_realB": "zgemm4_grouped_kernel<true, false",
-                            "dgemm_grouped": "dgemm_grouped_kernel", "jac_gram": "jac_gram_kernel", "jac_apply": "jac_apply_kernel"}.get(dom)
-                    cand = [v for k, v in mfma_busy.items() if pref and k.startswith(pref) and isinstance(v, dict) and "util" in v]
-                    if cand:
-                        roofline["mfma_busy_dominant"] = max(cand, key=lambda v: v.get("mfma_busy_cycles", 0.0))["util"]
-                if valu_busy is not None:
-                    roofline["valu_busy"] = valu_busy
-            # per-stage fractions of SURVEY.md §8(d): algorithmic work of the stage / its wall time / fp64 MFMA peak
-            my_ms = list(range(nblocks)) if m_range is None else list(range(m_range[0], m_range[1] + 1))
-            WA, WB, WC = stage_work(tel, bt, my_ms, nkeep=dict(_NKEEP) if _NKEEP else None)
-            stages = {}
-            for name, W, secs in (("btgen", WA, st[0]), ("svd", WB, st[1]), ("kl", WC, st[2])):
-                tf = W / secs / 1e12 if secs > 0 else 0.0
-                stages[name] = dict(work_flop=W, ms=1e3 * secs, tflops=tf, frac_of_fp64_mfma_peak=tf / FP64_MFMA_PEAK_TFLOPS)
-            cpu, parity = None, None
-            if not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N = 1 only
-                keep, spec = {m: None for m in my_ms}, {}
-                hot_path_step(tel, bt, kl, ctx, streams=args.streams, m_range=m_range, keep=keep, spectra=spec)   # untimed: real blocks
-                cpu, parity = cpu_baseline(tel, bt, kl, {m: b for m, b in keep.items() if b is not None}, spec["sv"], spec["ev"])
-                del keep
             line = {
                 "metric": "m-blocks/sec (BT-gen + SVD + KL)",
                 "value": value,
@@ -712,21 +746,17 @@ def main():
                                   "collectives); `value` uses the MAX over ranks of the whole timed region.  Sharded mode: the step of a rank is a lock-step chain of a few hundred launches whose length "
                                   "follows the LARGEST matrix of its range, not the number of blocks — strong scaling of this small "
                                   "workload is bounded by that chain (DESIGN.md section 6)"},
-                "stage_ms": {"btgen": 1e3 * st[0], "svd": 1e3 * st[1], "kl": 1e3 * st[2], "collectives": 1e3 * st[3]},
-                "stages": stages,
-                "btgen": {"btgen_iter0_ms": bt_ms.get(0), "btgen_iter3_ms": bt_ms.get(3),
-                          "ratio": (bt_ms[3] / bt_ms[0]) if bt_ms.get(0) else None,
-                          "note": "BT-gen of the step alone (all blocks of the rank, best of 3 after one warm-up call) with the "
-                                  "plain equal-weight quadrature (iter 0) and with healpy's default three refinements (iter 3)"},
                 # the two tridiagonalisation classes are timed on every 8th launch: scaled back to all launches
                 "kernels_ms": {k: v["ms"] / args.steps for k, v in prof.items()},
-                "roofline": roofline,
-                "cpu_baseline": cpu,
-                "parity": parity,
+                "roofline": None,
+                "cpu_baseline": None,
+                "parity": None,
             }
+            if full is not None:
+                line.update(full)
         else:
             line = None
-        ns_ok = not args.no_north_star and args.streams == 1 and not args.all_modes and not args.shard
+        ns_ok = args.full and not args.no_north_star and args.streams == 1 and not args.all_modes and not args.shard
         if world == 1 and not force_dist and ns_ok and rank == 0:
             del tel, bt, kl
             line["north_star"] = north_star_leg(args)

@@ -20,5 +20,5 @@ for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1].values())): w.writerow
 PY
 done
 find gpurun_out/pmc_fetch_r02p gpurun_out/pmc_write_r02p gpurun_out/pmc_mfma_r02p gpurun_out/prof_r02p -name "*.csv" -size +5M -delete
-timeout -k 10 600 python bench.py > gpurun_out/r02p_bench_default.json 2> gpurun_out/r02p_bench_default.err
-tail -c 1500 gpurun_out/r02p_bench_default.json
+timeout -k 10 600 python bench.py --full > r02p_bench_default.json 2> r02p_bench_default.err
+tail -c 1500 r02p_bench_default.json

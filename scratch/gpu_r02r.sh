@@ -21,13 +21,13 @@ for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1].values())): w.writerow
 PY
 done
 find gpurun_out/pmc_fetch_r02r gpurun_out/pmc_write_r02r gpurun_out/pmc_mfma_r02r gpurun_out/prof_r02r -name "*.csv" -size +5M -delete
-timeout -k 10 600 python bench.py > gpurun_out/r02r_bench_default.json 2> gpurun_out/r02r_bench_default.err
-tail -c 300 gpurun_out/r02r_bench_default.json
-timeout -k 10 300 python bench.py --gpus 2 --one-gpu --backend gloo --no-cpu-baseline > gpurun_out/r02r_bench2.json 2> gpurun_out/r02r_bench2.err || exit 4
-timeout -k 10 300 python bench.py --gpus 2 --one-gpu --backend gloo --mode sharded --no-cpu-baseline > gpurun_out/r02r_bench2s.json 2> gpurun_out/r02r_bench2s.err || exit 5
+timeout -k 10 600 python bench.py --full > r02r_bench_default.json 2> r02r_bench_default.err
+tail -c 300 r02r_bench_default.json
+timeout -k 10 300 python bench.py --full --gpus 2 --one-gpu --backend gloo --no-cpu-baseline > r02r_bench2.json 2> r02r_bench2.err || exit 4
+timeout -k 10 300 python bench.py --full --gpus 2 --one-gpu --backend gloo --mode sharded --no-cpu-baseline > r02r_bench2s.json 2> r02r_bench2s.err || exit 5
 python - <<'PY'
 import json
 for f in ("r02r_bench_default.json","r02r_bench2.json","r02r_bench2s.json"):
-    d=json.loads(open("gpurun_out/"+f).read().strip().splitlines()[-1])
+    d=json.loads(open(f).read().strip().splitlines()[-1])
     print(f, round(d["value"],1), d["n_gpus"], round(d["ms_per_step"],1), d["scaling"], {k: round(v,1) for k,v in d["stage_ms"].items()}, round(d["roofline"]["frac"],3))
 PY

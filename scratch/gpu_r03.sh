@@ -26,9 +26,9 @@ for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1].values())): w.writerow
 PY
 done
 find gpurun_out/pmc_fetch_$tag gpurun_out/pmc_write_$tag gpurun_out/pmc_mfma_$tag gpurun_out/prof_$tag -name "*.csv" -size +5M -delete
-timeout -k 10 600 python bench.py > gpurun_out/${tag}_bench_default.json 2> gpurun_out/${tag}_bench_default.err || exit 6
-timeout -k 10 300 python bench.py --gpus 2 --one-gpu --backend gloo --no-cpu-baseline > gpurun_out/${tag}_bench2s.json 2> gpurun_out/${tag}_bench2s.err || exit 7
-timeout -k 10 300 python bench.py --gpus 2 --one-gpu --backend gloo --mode weak --no-cpu-baseline > gpurun_out/${tag}_bench2w.json 2> gpurun_out/${tag}_bench2w.err || exit 8
+timeout -k 10 600 python bench.py --full > ${tag}_bench_default.json 2> ${tag}_bench_default.err || exit 6
+timeout -k 10 300 python bench.py --full --gpus 2 --one-gpu --backend gloo --no-cpu-baseline > ${tag}_bench2s.json 2> ${tag}_bench2s.err || exit 7
+timeout -k 10 300 python bench.py --full --gpus 2 --one-gpu --backend gloo --mode weak --no-cpu-baseline > ${tag}_bench2w.json 2> ${tag}_bench2w.err || exit 8
 # BT-gen of a configs[2] rank call (65 blocks) under the kernel trace
 rm -rf gpurun_out/btprof
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/btprof -o bt -- python3 scratch/btgen_bench.py --config 3 --ranges 0:64 --skip-old --out gpurun_out/${tag}_btgen_config3_rank.json > gpurun_out/btprof.log 2>&1 || exit 9
@@ -38,7 +38,7 @@ python - $tag <<'PY'
 import json, sys
 tag = sys.argv[1]
 for f in ("bench_default", "bench2s", "bench2w"):
-    d = json.loads(open("gpurun_out/%s_%s.json" % (tag, f)).read().strip().splitlines()[-1])
+    d = json.loads(open("%s_%s.json" % (tag, f)).read().strip().splitlines()[-1])
     print(f, round(d["value"], 1), d["n_gpus"], round(d["ms_per_step"], 1), d["scaling"], {k: round(v, 1) for k, v in d["stage_ms"].items()},
           d["roofline"]["kernel"], round(d["roofline"]["frac"], 3))
 PY

@@ -30,11 +30,11 @@ PY
 done
 find gpurun_out/pmc_fetch_$tag gpurun_out/pmc_write_$tag gpurun_out/pmc_mfma_$tag gpurun_out/prof_$tag -name "*.csv" -size +5M -delete
 echo "$(date +%T) bench default"
-timeout -k 10 900 python bench.py > gpurun_out/${tag}_bench_default.json 2> gpurun_out/${tag}_bench_default.err || exit 6
+timeout -k 10 900 python bench.py --full > ${tag}_bench_default.json 2> ${tag}_bench_default.err || exit 6
 echo "$(date +%T) rehearsals"
-timeout -k 10 300 python bench.py --gpus 2 --one-gpu --backend gloo --no-cpu-baseline > gpurun_out/${tag}_bench_2ranks_one_gpu_gloo_sharded.json 2> gpurun_out/${tag}_bench2s.err || exit 7
-timeout -k 10 300 python bench.py --gpus 2 --one-gpu --backend gloo --mode weak --no-cpu-baseline > gpurun_out/${tag}_bench_2ranks_one_gpu_gloo_weak.json 2> gpurun_out/${tag}_bench2w.err || exit 8
-DRIFTMI_WORKSPACE_GB=8 timeout -k 10 400 python bench.py --gpus 6 --one-gpu --backend gloo --no-cpu-baseline --steps 3 --prime-passes 2 > gpurun_out/${tag}_bench_6ranks_one_gpu_gloo_sharded.json 2> gpurun_out/${tag}_bench6s.err || exit 9
+timeout -k 10 300 python bench.py --full --gpus 2 --one-gpu --backend gloo --no-cpu-baseline > ${tag}_bench_2ranks_one_gpu_gloo_sharded.json 2> ${tag}_bench2s.err || exit 7
+timeout -k 10 300 python bench.py --full --gpus 2 --one-gpu --backend gloo --mode weak --no-cpu-baseline > ${tag}_bench_2ranks_one_gpu_gloo_weak.json 2> ${tag}_bench2w.err || exit 8
+DRIFTMI_WORKSPACE_GB=8 timeout -k 10 400 python bench.py --full --gpus 6 --one-gpu --backend gloo --no-cpu-baseline --steps 3 --prime-passes 2 > ${tag}_bench_6ranks_one_gpu_gloo_sharded.json 2> ${tag}_bench6s.err || exit 9
 fi
 if [ "$part" = "a" ]; then exit 0; fi
 # a full configs[2] share (0/8) through generate(): kernel stats, then MFMA-busy counters in a pass of their own
@@ -92,9 +92,9 @@ import json, sys
 tag = sys.argv[1]
 import os
 for f in ("bench_default", "bench_2ranks_one_gpu_gloo_sharded", "bench_2ranks_one_gpu_gloo_weak", "bench_6ranks_one_gpu_gloo_sharded"):
-    if not os.path.exists("gpurun_out/%s_%s.json" % (tag, f)):
+    if not os.path.exists("%s_%s.json" % (tag, f)):
         continue
-    d = json.loads(open("gpurun_out/%s_%s.json" % (tag, f)).read().strip().splitlines()[-1])
+    d = json.loads(open("%s_%s.json" % (tag, f)).read().strip().splitlines()[-1])
     print(f, round(d["value"], 1), d["n_gpus"], round(d["ms_per_step"], 1), d["scaling"], {k: round(v, 1) for k, v in d["stage_ms"].items()},
           d["roofline"]["kernel"], round(d["roofline"]["frac"], 3))
     if "north_star" in d:

@@ -26,7 +26,7 @@ cp profiles/${tag}_pmc_traffic.json profiles/${tag}_pmc_mfma.json gpurun_out/ 2>
 f=$(find gpurun_out/prof_$tag -name "*kernel_stats.csv" | head -1); cp "$f" gpurun_out/${tag}_bench_kernel_stats.csv
 find gpurun_out/pmc_fetch_$tag gpurun_out/pmc_write_$tag gpurun_out/pmc_mfma_$tag gpurun_out/pmc_valu_$tag gpurun_out/prof_$tag -name "*.csv" -size +5M -delete
 echo "$(date +%T) bench default"
-DRIFT_BENCH_DETAIL=gpurun_out/${tag}_bench_detail.json timeout -k 10 1000 python bench.py 2> gpurun_out/${tag}_bench_default.err | grep "^{" > gpurun_out/${tag}_bench_default.json || exit 7   # the compact line; the full record is the detail file
+DRIFT_BENCH_DETAIL=${tag}_bench_detail.json timeout -k 10 1000 python bench.py --full 2> ${tag}_bench_default.err | grep "^{" > ${tag}_bench_default.json || exit 7   # the compact line; the full record is the detail file
 fi
 if [ "$part" = "b" ]; then
 echo "$(date +%T) share kernel stats"
@@ -47,7 +47,7 @@ timeout -k 10 1100 python scratch/shares_all.py --n 8 --out gpurun_out/${tag}_co
 fi
 if [ "$part" = "r" ]; then
 echo "$(date +%T) rehearsals"
-timeout -k 10 300 python bench.py --gpus 2 --one-gpu --backend gloo --share-mmax 1 --no-cpu-baseline 2> gpurun_out/${tag}_bench2.err | grep "^{" > gpurun_out/${tag}_bench_2ranks_one_gpu_gloo_sharded_with_job.json || exit 13
+timeout -k 10 300 python bench.py --full --gpus 2 --one-gpu --backend gloo --share-mmax 1 --no-cpu-baseline 2> ${tag}_bench2.err | grep "^{" > ${tag}_bench_2ranks_one_gpu_gloo_sharded_with_job.json || exit 13
 timeout -k 10 300 python bench.py --workload configs2 --job --gpus 4 --one-gpu --backend gloo --share-mmax 1 2> gpurun_out/${tag}_job4.err | grep "^{" > gpurun_out/${tag}_job_configs2_4ranks_one_gpu_gloo_toy.json || exit 14
 timeout -k 10 300 python bench.py --workload configs3 --job --gpus 2 --one-gpu --backend gloo --share-mmax 1 2> gpurun_out/${tag}_job2c3.err | grep "^{" > gpurun_out/${tag}_job_configs3_2ranks_one_gpu_gloo_toy.json || exit 15
 fi

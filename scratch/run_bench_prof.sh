@@ -3,6 +3,6 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-python bench.py --steps 1 --warmup 1 > gpurun_out/bench_r01.json 2> gpurun_out/bench_r01.err
-tail -c 3000 gpurun_out/bench_r01.json
-tail -5 gpurun_out/bench_r01.err
+python bench.py --full --steps 1 --warmup 1 > bench_r01.json 2> bench_r01.err
+tail -c 3000 bench_r01.json
+tail -5 bench_r01.err

@@ -54,3 +54,11 @@ def test_steps_must_be_positive_and_dump_is_for_the_default_workload():
         bench.parse_args(["--steps", "0"])
     with pytest.raises(SystemExit):
         bench.parse_args(["--workload", "configs2", "--dump-outputs", "d"])
+
+
+def test_full_legs_are_off_by_default():
+    """A plain run measures the headline figure only; the per-stage passes, roofline, CPU baseline and north-star leg run
+    behind --full, where --no-cpu-baseline / --no-north-star still leave either out."""
+    assert not bench.parse_args([]).full
+    args = bench.parse_args(["--full", "--no-north-star"])
+    assert args.full and args.no_north_star and not args.no_cpu_baseline
