@@ -128,6 +128,8 @@ SIGNATURES = {
         c_int, [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_int, c_vp, c_int, c_int,
                 ctypes.POINTER(c_dbl), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int,
                 ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_dbl), c_int]),
+    "dm_sht_synth": (
+        c_int, [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "dm_bt_alias_info": (
         c_int, [c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_int, ctypes.POINTER(c_int),
                 ctypes.POINTER(c_int)]),
@@ -737,6 +739,22 @@ def _bt_columns(self, nside, cth, sth, frame, polarised, beams, uv, bi, bj, lsid
     self.check(rc, "dm_bt_columns")
 
 
+def _sht_synth(self, nside, cth, sth, polarised, lmax, M, ncol, alm, maps):
+    """(ncol, P, lmax + 1, M) c128 coefficients -> (ncol, P, 12 nside^2) f64 maps on the device (dm_sht_synth);
+    P = 4 if polarised else 1.  Queued on the context's stream."""
+    P = 4 if polarised else 1
+    if tuple(alm.shape) != (int(ncol), P, int(lmax) + 1, int(M)) or tuple(maps.shape) != (int(ncol), P, 12 * int(nside) ** 2):
+        raise ValueError("sht_synth: alm %s / maps %s do not match ncol %d, P %d, lmax %d, M %d, nside %d"
+                         % (tuple(alm.shape), tuple(maps.shape), ncol, P, lmax, M, nside))
+    if not (alm.is_contiguous() and maps.is_contiguous() and alm.is_complex() and not maps.is_complex()):
+        raise ValueError("sht_synth: need contiguous complex128 alm and float64 maps")
+    c, cp = _darr(cth)
+    s_, sp = _darr(sth)
+    rc = self.lib.dm_sht_synth(self.h, int(nside), cp, sp, int(bool(polarised)), int(lmax), int(M), int(ncol),
+                               self.ptr(alm), self.ptr(maps))
+    self.check(rc, "dm_sht_synth")
+
+
 def bt_alias_info(nside, cth, sth, polarised, lmax_grp):
     """(alias rings per cap, mcut) of the harmonic-space refinement for one nside group (dm_bt_alias_info; host only)."""
     c, cp = _darr(cth)
@@ -753,6 +771,7 @@ Context.bt_beam_cyl = _bt_beam_cyl
 Context.bt_beams_cyl = _bt_beams_cyl
 Context.bt_maps = _bt_maps
 Context.bt_sht = _bt_sht
+Context.sht_synth = _sht_synth
 
 
 PROF_CLASSES = ["zgemm_grouped", "gemm_grouped_realB", "jac_gram", "jac_inner", "jac_apply", "dgemm_grouped",

@@ -26,6 +26,7 @@
 #include "dm_common.h"
 #include <cstring>
 #include "dm_kernels.h"
+#include "dm_sht.h"
 #include "../../include/driftmi.h"
 
 #include <algorithm>
@@ -36,18 +37,6 @@
 #include <tuple>
 
 namespace {
-
-constexpr double kPi = 3.14159265358979323846;
-
-struct ring_geo {
-  const double* cth;   // cos(theta) per ring
-  const double* sth;   // sin(theta) per ring
-  const double* phi0;  // phi of first pixel
-  const int* nphi;     // pixels in ring
-  const int* start;    // first pixel index
-  int nring;
-  int npix;
-};
 
 __device__ __forceinline__ int ring_of_pixel(const ring_geo& g, int pix) {
   // binary search over ring starts
@@ -769,11 +758,11 @@ __global__ __launch_bounds__(TPB) void bt_fused_fft_kernel(ring_geo g, frame3 fr
       const int p = U / (N / 8), u = U - p * (N / 8);
       cplx* x = X + (size_t)p * Np + ph(u * 8);   // eight values never straddle a padding slot (2^sh >= 32)
       cplx e[8];
-#pragma unroll
+  #pragma unroll
       for (int i = 0; i < 8; ++i) e[i] = x[i];
-#pragma unroll
+  #pragma unroll
       for (int i = 0; i < 8; i += 2) { const cplx t = e[i + 1]; e[i + 1] = csub(e[i], t); e[i] = cadd(e[i], t); }
-#pragma unroll
+  #pragma unroll
       for (int i = 0; i < 8; i += 4) {
         cplx t = e[i + 2]; e[i + 2] = csub(e[i], t); e[i] = cadd(e[i], t);
         t = make_double2(-e[i + 3].y, e[i + 3].x);   // times exp(2 pi i / 4) = +i
@@ -789,7 +778,7 @@ __global__ __launch_bounds__(TPB) void bt_fused_fft_kernel(ring_geo g, frame3 fr
         t = make_double2(-h * (e[7].x + e[7].y), h * (e[7].x - e[7].y));       // times exp(3 i pi / 4)
         e[7] = csub(e[3], t); e[3] = cadd(e[3], t);
       }
-#pragma unroll
+  #pragma unroll
       for (int i = 0; i < 8; ++i) x[i] = e[i];
     }
     __syncthreads();
@@ -859,83 +848,6 @@ __global__ __launch_bounds__(256) void bt_fold_kernel(cplx* __restrict__ G, int 
     const cplx a = *gn, b = *gs;
     *gn = cadd(a, b);
     *gs = csub(b, a);
-  }
-}
-
-// tw[pix][mm] laid out per ring as (2*mmax+1) x nphi row-major: tw[off_r + mm*nphi + j] = exp(i (mm - mmax) phi_j)
-__global__ void bt_twiddle_kernel(ring_geo g, int m_lo, int cnt, const size_t* __restrict__ toff, cplx* __restrict__ tw) {
-  // rows [0, cnt): m = +m_lo .. +(m_lo + cnt - 1);  rows [cnt, 2 cnt): the same with a minus sign
-  const int r = blockIdx.y;
-  const int nphi = g.nphi[r];
-  const int nm = 2 * cnt;
-  const size_t tot = (size_t)nm * nphi;
-  for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-    const int mm = (int)(idx / nphi), j = (int)(idx % nphi);
-    const int m = mm < cnt ? m_lo + mm : -(m_lo + mm - cnt);
-    // reduce the argument exactly: m*j mod nphi keeps the phase in [0, 2 pi)
-    const long long mj = ((long long)m * j) % nphi;
-    const double ph = (double)m * g.phi0[r] + 2.0 * kPi * (double)mj / (double)nphi;
-    double s, c;
-    sincos(ph, &s, &c);
-    tw[toff[r] + idx] = make_double2(c, s);
-  }
-}
-
-// Legendre tables: lam[loff[m] + (l-m)*nring + r] = w * lambda_lm(theta_r), same for W and X (polarised)
-__global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, double w, const size_t* __restrict__ loff_,
-                                   double* __restrict__ lam, double* __restrict__ Wt, double* __restrict__ Xt) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  const int m = m_lo + blockIdx.y;
-  const size_t* loff = loff_ - m_lo;  // tables are stored for m_lo .. mmax
-  if (r >= g.nring || m > mmax || m > lmax) return;
-  const double z = g.cth[r], st = g.sth[r];
-  const double s2 = st * st;
-  double logpre = 0.5 * (log(2.0 * m + 1.0) - log(4.0 * kPi));
-  for (int k = 1; k <= m; ++k) logpre += 0.5 * log((2.0 * k - 1.0) / (2.0 * k));
-  double lmm = (m > 0) ? exp(logpre + (double)m * log(st)) : exp(logpre);
-  if (m & 1) lmm = -lmm;
-  double* out = lam + loff[m];
-  const size_t nr = g.nring;
-  double pm2 = 0.0, pm1 = lmm;  // lambda_{l-2}, lambda_{l-1} as l advances
-  out[r] = w * lmm;
-  if (Wt) {
-    double* wo = Wt + loff[m];
-    double* xo = Xt + loff[m];
-    // l = m term (needs lambda_{m-1,m} = 0)
-    if (m >= 2) {
-      const double l = m;
-      const double nl = 2.0 * sqrt(1.0 / ((l - 1.0) * l * (l + 1.0) * (l + 2.0)));
-      wo[r] = -w * nl * (-((l - l * l) / s2 + 0.5 * l * (l - 1.0)) * lmm);
-      xo[r] = w * nl * (l / s2) * ((l - 1.0) * z * lmm);
-    } else {
-      wo[r] = 0.0;
-      xo[r] = 0.0;
-    }
-  }
-  for (int l = m + 1; l <= lmax; ++l) {
-    double cur;
-    if (l == m + 1) {
-      cur = sqrt(2.0 * m + 3.0) * z * pm1;
-    } else {
-      const double a = sqrt((4.0 * l * l - 1.0) / ((double)l * l - (double)m * m));
-      const double b = sqrt(((l - 1.0) * (l - 1.0) - (double)m * m) / (4.0 * (l - 1.0) * (l - 1.0) - 1.0));
-      cur = a * (z * pm1 - b * pm2);
-    }
-    out[(size_t)(l - m) * nr + r] = w * cur;
-    if (Wt) {
-      double wv = 0.0, xv = 0.0;
-      if (l >= 2) {
-        const double dl = l, dm = m;
-        const double nl = 2.0 * sqrt(1.0 / ((dl - 1.0) * dl * (dl + 1.0) * (dl + 2.0)));
-        const double c = sqrt((2.0 * dl + 1.0) / (2.0 * dl - 1.0) * (dl * dl - dm * dm));
-        wv = -nl * (-((dl - dm * dm) / s2 + 0.5 * dl * (dl - 1.0)) * cur + c * z / s2 * pm1);
-        xv = nl * (dm / s2) * ((dl - 1.0) * z * cur - c * pm1);
-      }
-      (Wt + loff[m])[(size_t)(l - m) * nr + r] = w * wv;
-      (Xt + loff[m])[(size_t)(l - m) * nr + r] = w * xv;
-    }
-    pm2 = pm1;
-    pm1 = cur;
   }
 }
 
@@ -1198,52 +1110,6 @@ __global__ void bt_scatter2_kernel(const cplx* __restrict__ src, int src_mlo, in
   cplx v = make_double2(0.0, 0.0);
   if (ms >= 0 && ms < src_nm && l < Ls) v = src[((((size_t)ms * 2 + s) * ncol + col) * P + p) * Lrow + l];
   dst[((((size_t)mo * F + colf[col]) * 2 + s) * B + colb[col]) * P * L + pl] = v;
-}
-
-struct geo_host {
-  ring_geo g;
-  std::vector<double> cth, sth, phi0;
-  std::vector<int> nphi, start;
-};
-
-int upload_geo(dm_ctx* ctx, int nside, const double* cth, const double* sth, geo_host& gh) {
-  const int nring = 4 * nside - 1;
-  gh.cth.assign(cth, cth + nring);
-  gh.sth.assign(sth, sth + nring);
-  gh.phi0.resize(nring);
-  gh.nphi.resize(nring);
-  gh.start.resize(nring);
-  int acc = 0;
-  for (int r = 0; r < nring; ++r) {
-    const int i = r + 1;
-    int np_;
-    double p0;
-    if (i < nside) { np_ = 4 * i; p0 = kPi / (4.0 * i); }
-    else if (i <= 3 * nside) { np_ = 4 * nside; p0 = (((i + nside) & 1) == 0) ? kPi / (4.0 * nside) : 0.0; }
-    else { const int j = 4 * nside - i; np_ = 4 * j; p0 = kPi / (4.0 * j); }
-    gh.nphi[r] = np_;
-    gh.phi0[r] = p0;
-    gh.start[r] = acc;
-    acc += np_;
-  }
-  gh.g.nring = nring;
-  gh.g.npix = acc;
-  // one staged copy for the five arrays (every descriptor upload is a copy kernel of its own in the stream)
-  std::vector<double> blob(4 * (size_t)nring);
-  std::memcpy(blob.data(), gh.cth.data(), sizeof(double) * nring);
-  std::memcpy(blob.data() + nring, gh.sth.data(), sizeof(double) * nring);
-  std::memcpy(blob.data() + 2 * (size_t)nring, gh.phi0.data(), sizeof(double) * nring);
-  int* ib = reinterpret_cast<int*>(blob.data() + 3 * (size_t)nring);
-  std::memcpy(ib, gh.nphi.data(), sizeof(int) * nring);
-  std::memcpy(ib + nring, gh.start.data(), sizeof(int) * nring);
-  double* d = dm_ws_upload(ctx, blob);
-  if (!d) return DM_ENOMEM;
-  gh.g.cth = d;
-  gh.g.sth = d + nring;
-  gh.g.phi0 = d + 2 * (size_t)nring;
-  gh.g.nphi = reinterpret_cast<const int*>(d + 3 * (size_t)nring);
-  gh.g.start = gh.g.nphi + nring;
-  return DM_OK;
 }
 
 frame3 make_frame(const double* xhat, const double* yhat, const double* zhat) {

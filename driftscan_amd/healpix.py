@@ -49,9 +49,9 @@ def ang_positions(nside):
 
 # ---- sky maps <-> spherical harmonics for the consumers of the operators (timestream simulation, map-making) ----
 # cora.util.hputil.sphtrans_sky / sphtrans_inv_sky (drift/pipeline/timestream.py:262, :295, :451, :717) are not
-# available; these restate them on the equal-weight HEALPix quadrature of the rest of the package.  The forward
-# transform runs on the device (dm_bt_sht: ring DFT + Legendre GEMMs); the inverse is a host loop over rings — it is
-# called once per map, off the hot path.
+# available; these restate them on the equal-weight HEALPix quadrature of the rest of the package.  Both directions run
+# on the device: the forward transform through dm_bt_sht (ring DFT + Legendre GEMMs), the inverse through dm_sht_synth
+# (Legendre GEMMs + ring FFT / DFT).  The host loop of the inverse stays as sphtrans_inv_sky_host (the test oracle).
 def ring_layout(nside):
     """(nphi, phi0, start) per ring of the RING scheme."""
     i = np.arange(1, 4 * nside)
@@ -124,8 +124,35 @@ def sphtrans_sky(skymap, lmax):
     return np.ascontiguousarray(h.conj().transpose(1, 2, 3, 0))
 
 
-def sphtrans_inv_sky(alm, nside):
-    """a_lm [freq, pol(T,E,B,V), l, m >= 0] -> real maps [freq, pol(T,Q,U,V), pixel] (cora.util.hputil.sphtrans_inv_sky)."""
+def sphtrans_inv_sky(alm, nside, max_bytes=4 << 30):
+    """a_lm [freq, pol(T,E,B,V), l, m >= 0] -> real maps [freq, pol(T,Q,U,V), pixel] (cora.util.hputil.sphtrans_inv_sky).
+    Runs on the GPU through dm_sht_synth, a chunk of frequencies at a time: ``max_bytes`` bounds the coefficients, maps
+    and harmonic rings of one chunk on the device.  Other numbers of polarisations than 1 or 4 take the host loop."""
+    alm = np.asarray(alm, dtype=np.complex128)
+    nfreq, npol, L, M = alm.shape
+    if npol not in (1, 4):
+        return sphtrans_inv_sky_host(alm, nside)
+    from .device import get_context
+
+    ctx = get_context()
+    cth, sth = ring_trig(nside)
+    npx = npix(nside)
+    nring = 4 * nside - 1
+    per_f = npol * (16 * L * M + 8 * npx + 16 * nring * min(L, M))
+    nf = int(max(1, min(nfreq, max_bytes // per_f)))
+    out = np.empty((nfreq, npol, npx))
+    for f0 in range(0, nfreq, nf):
+        f1 = min(nfreq, f0 + nf)
+        a = ctx.to_device(alm[f0:f1])
+        maps = ctx.empty((f1 - f0, npol, npx), np.float64)
+        ctx.sht_synth(nside, cth, sth, npol == 4, L - 1, M, f1 - f0, a, maps)
+        ctx.torch.from_numpy(out[f0:f1]).copy_(maps)
+        del a, maps
+    return out
+
+
+def sphtrans_inv_sky_host(alm, nside):
+    """sphtrans_inv_sky as a host loop over (m, ring): the oracle of the device synthesis, for any number of polarisations."""
     alm = np.asarray(alm, dtype=np.complex128)
     nfreq, npol, L, M = alm.shape
     lmax = L - 1

@@ -373,6 +373,17 @@ int dm_bt_sht(dm_ctx* ctx, int nside, const double* ring_cth_host, const double*
               int lside, int mmax, int lmax_grp, int F, int B, int ncol, const int* col_f_host,
               const int* col_b_host, const int* col_lmax_host, const void* maps_dev, void* beam_m_dev);
 
+/* dm_sht_synth: spherical-harmonic synthesis of real sky maps, the inverse of the analysis of dm_bt_sht:
+ *   maps[f, p, start_r + j] = sum_m c_m Re(F_m(z_r) exp(i m phi_rj)),  c_0 = 1, c_m = 2 (m < min(M, lmax + 1)),
+ *   F_m = sum_l a_lm lambda_lm for T and V; F_Q = W a_E + i X a_B, F_U = W a_B - i X a_E (the HEALPix spin-2 functions).
+ *   alm_dev   (ncol, P, lmax + 1, M) c128 (a[f, p, l, m], zero for l < m), P = 4 (T, E, B, V) if polarised else 1
+ *   maps_dev  (ncol, P, 12 nside^2) f64 out (T or T, Q, U, V in RING order)
+ * Needs 4 nside <= 8192.  The device workspace holds the Legendre tables of the call and the harmonic rings of a chunk of
+ * columns (at most 1 GiB).  Returns when the work is queued on the context's stream.
+ * Replaces: cora.util.hputil.sphtrans_inv_sky (drift/pipeline/timestream.py:262, :295, :451). */
+int dm_sht_synth(dm_ctx* ctx, int nside, const double* ring_cth_host, const double* ring_sth_host, int polarised, int lmax,
+                 int M, int ncol, const void* alm_dev, void* maps_dev);
+
 /* dm_bt_sht_range: the same for the m-blocks m_lo .. m_hi only; beam_m_dev is then
  * (m_hi - m_lo + 1, F, 2, B, P, L).  A rank that owns a range of m synthesises the maps
  * (replicated, a few per cent of the per-m cost) but transforms and stores only its own blocks —
