@@ -1,6 +1,7 @@
 // dm_sbr_impl.h — two-stage tridiagonalisation (dense -> band on MFMA, band -> tridiagonal by bulge chasing)
-// and the back-transformation of the second stage.  Included by dm_tridiag_impl.h inside the namespace of
-// the 32-wide instantiation (the bandwidth is the panel width TNB = 32).  No include guard on purpose.
+// and the back-transformation of the second stage: the kernels, then the host stages that the panel driver calls
+// (sb_reduce, sb_apply_q2) over its storage trd_ws.  Included by dm_tridiag_impl.h inside the namespace of the 32-wide
+// instantiation (the bandwidth is the panel width TNB = 32).  No include guard on purpose.
 //
 // Replaces the zhetrd inside scipy.linalg.eigh (drift/core/kltransform.py:89, :107) by the LAPACK 3.7
 // two-stage scheme (zhetrd_he2hb + zhetrd_hb2st):
@@ -1863,4 +1864,503 @@ __global__ __launch_bounds__(64 * NW) void sb_q2_apply_kernel(const sb_q2_mat* _
       __syncthreads();
     }
   }
+}
+
+// ==== host side: the stages of the panel route over its storage trd_ws (S1 + S2: sb_reduce; B2: sb_apply_q2) ====
+
+// storage of S1 / S2 / B2, behind the buffers of the one-stage path
+int sb_alloc(dm_ctx* ctx, trd_ws& w) {
+  const auto& probs = w.b.probs;
+  const int np = w.b.np;
+  const size_t totn = w.b.totn;
+  size_t totyp = 0, totvd = 0;
+  for (int p = 0; p < np; ++p) {
+    const size_t n = probs[p].n;
+    w.offyp[p] = totyp; totyp += n / SQR + 1;
+    const size_t ng = n > 1 ? (n - 1 + SBG - 1) / SBG : 0;
+    w.sb_jb[p] = n > 1 ? (int)((n - 2) / SB + 1) : 0;
+    w.offvd[p] = totvd; totvd += ng * w.sb_jb[p] * SBG * SBW;
+    w.offt2[p] = w.tott2; w.tott2 += ng * w.sb_jb[p] * SBG;
+  }
+  w.sbPw = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * SB, 1));
+  w.sbXt = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * SB, 1));
+  w.sbYp = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totyp * SB, 1));
+  w.sbNp = dm_ws_alloc_t<double>(ctx, std::max<size_t>(totyp * 2, 1));
+  w.sbAB = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * SLD, 1));
+  w.sbVd = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totvd, 1));
+  w.sbTau2 = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(w.tott2, 1));
+  w.sbM1 = dm_ws_alloc_t<cplx>(ctx, (size_t)np * SB * SB);
+  w.sbS = dm_ws_alloc_t<cplx>(ctx, (size_t)np * SB * SB);
+  w.sbProg = dm_ws_alloc_t<unsigned>(ctx, std::max<size_t>(2 * totn, 1));  // two progress words per sweep
+  // split-K partials: at most 32 slices of the 32 x n block of Y per matrix (the Gram matrices need far less)
+  w.sbPart = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(totn * SB * 32 + (size_t)np * SB * SB * 32, 1));
+  w.sbNext = dm_ws_alloc_t<int>(ctx, 2 * (size_t)np + 9);  // sweep counters, owners, queue heads, error flag
+  if (!w.sbPw || !w.sbXt || !w.sbYp || !w.sbNp || !w.sbAB || !w.sbVd || !w.sbTau2 || !w.sbM1 || !w.sbS || !w.sbProg ||
+      !w.sbPart || !w.sbNext)
+    return DM_ENOMEM;
+  return DM_OK;
+}
+
+// ---- S1: dense -> band, one panel of SB columns at a time, all matrices in lock-step
+//
+// A panel is two chains of launches.  The "side" chain needs nothing but the panel itself: QR, Gram slices, T factor,
+// X^T = T^T V^H.  The "main" chain needs the trailing matrix: Y (slices + sum), M = V^H Y (slices), S, W, and the
+// rank-64 update.  Split-K partials in sbPart: per matrix SY x (32 x n) (Y), then 32 x (32 x 32) per matrix (Gram, M).
+struct sb_panel_split { int nact, SG, SY; };
+sb_panel_split sb_split_of(const trd_ws& w, int k0) {
+  const int i0 = k0 + SB, a0 = i0 & ~127;
+  int nact = 0, ytiles = 0;
+  for (int p : w.b.order) {
+    if (w.b.probs[p].n - i0 < 2) continue;
+    ++nact;
+    ytiles += (w.b.probs[p].n - a0 + 127) / 128;
+  }
+  const int kmax = w.b.maxn - i0;
+  // split-K: the products with K = trailing size have few output tiles (one 32 x 32 tile per matrix for the Gram
+  // matrices, one 32 x 128 tile per 128 columns of Y): cut K so that a launch carries ~1000 tiles
+  auto slices_for = [&](int tiles) { return std::max(1, std::min(30, std::min((1024 + tiles - 1) / tiles, (kmax + 127) / 128))); };
+  return sb_panel_split{nact, nact == 0 ? 1 : slices_for(nact), nact == 0 ? 1 : slices_for(std::max(ytiles, 1))};
+}
+
+// side chain of panel k0: Gram slices (summed by the T-factor kernel), T, X^T = T^T V^H
+struct sb_side_set { dm_gemm_plan pg, px; std::vector<tf_mat> tf; };
+int sb_build_side(const trd_ws& w, int k0, sb_side_set& S_) {
+  const int i0 = k0 + SB;
+  const sb_panel_split sp = sb_split_of(w, k0);
+  cplx* part_g = w.sbPart + w.b.totn * SB * 32;
+  std::vector<dm_gemm_desc> gg, gx;
+  for (int p : w.b.order) {
+    const int n = w.b.probs[p].n;
+    const int m = n - i0;
+    if (m < 2) continue;
+    const int kb = std::min(SB, m - 1);
+    cplx* Vp = w.PP + w.b.offn[p] * 3 * TNB;
+    cplx* Xt = w.sbXt + w.b.offn[p] * SB;
+    const cplx* Vb = w.Vt + w.b.off[p] + (size_t)k0 * n + i0;
+    cplx* G = w.Gs + w.offg[p] + (size_t)(k0 / TNB) * TNB * TNB;
+    cplx* T = w.Tbig + w.offtb[p] + (size_t)(k0 / NBB) * NBB * NBB + (size_t)(k0 % NBB) * NBB + (k0 % NBB);
+    cplx* pg = part_g + (size_t)p * SB * SB * 32;
+    int gram_slices = 0;
+    if (sp.SG == 1) {
+      gg.push_back(dm_gemm_make(Vb, n, 1, true, Vb, 1, n, false, G, TNB, kb, kb, m));
+    } else {
+      const int kc = (m + sp.SG - 1) / sp.SG;
+      int ns = 0;
+      for (int kk = 0; kk < m; kk += kc, ++ns)
+        gg.push_back(dm_gemm_make(Vb + kk, n, 1, true, Vb + kk, 1, n, false, pg + (size_t)ns * kb * kb, kb, kb, kb, std::min(kc, m - kk)));
+      gram_slices = ns;   // summed by the T-factor kernel
+    }
+    S_.tf.push_back(tf_mat{G, w.tau + w.b.offn[p] + k0, T, kb, NBB, gram_slices ? pg : nullptr, gram_slices});
+    gx.push_back(dm_gemm_make(T, 1, NBB, false, Vp + i0, n, 1, false, Xt + i0, n, SB, m, SB));   // Xt = T^T Vp (SB x m)
+  }
+  DM_TRY(dm_gemm_plan_build(gg, S_.pg));
+  DM_TRY(dm_gemm_plan_build(gx, S_.px));
+  return DM_OK;
+}
+
+// main chain of panel k0
+struct sb_main_set { dm_gemm_plan py1, py2, pm, pw, ph; std::vector<sb_sum_desc> sy; std::vector<sb_s_desc> ssv; };
+int sb_build_main(const trd_ws& w, int k0, sb_main_set& M_) {
+  const int i0 = k0 + SB, a0 = i0 & ~127;
+  const sb_panel_split sp = sb_split_of(w, k0);
+  cplx* part_y = w.sbPart;
+  cplx* part_g = w.sbPart + w.b.totn * SB * 32;
+  std::vector<dm_gemm_desc> gy1, gy2, gm, gw, gh;
+  for (int p : w.b.order) {
+    const int n = w.b.probs[p].n;
+    const int m = n - i0;
+    if (m < 2) continue;
+    const int lda = w.b.probs[p].ldc;
+    cplx* C = w.b.probs[p].C;
+    cplx* pp = w.PP + w.b.offn[p] * 3 * TNB;
+    cplx* Vp = pp;
+    cplx* Wp = pp + (size_t)n * TNB;
+    cplx* Xt = w.sbXt + w.b.offn[p] * SB;
+    cplx* T = w.Tbig + w.offtb[p] + (size_t)(k0 / NBB) * NBB * NBB + (size_t)(k0 % NBB) * NBB + (k0 % NBB);
+    cplx* pg = part_g + (size_t)p * SB * SB * 32;
+    // Yt = Xt A22 by 128-column blocks: stored part (rows >= block start, whole diagonal block) + mirrored part
+    cplx* py = part_y + w.b.offn[p] * SB * 32;
+    size_t pyoff = 0;
+    // BLOCK-PAIR order (split products only, at most 30 blocks per side): K is cut at the 128-boundaries of the matrix,
+    // so every piece reads ONE 128 x 128 block of the stored triangle — and the two pieces that read the same block
+    // (the stored part of column block R over the columns of block C, the mirrored part of column block C over the
+    // rows of block R) are emitted next to each other: they run on the same XCD at the same time (the tile list is
+    // dealt to the XCDs in contiguous runs) and the second one finds the block in L2.  Uniform K = 128 tiles instead of
+    // ragged slices; the trailing matrix comes from HBM once per panel for this product instead of twice.
+    const int nblk = (n - a0 + 127) / 128;
+    if (sp.SY > 1 && nblk <= 30) {
+      // column block b covers [lo(b), hi(b)); slots of block b: stored pieces over the blocks c >= b (slot c - b),
+      // then mirrored pieces over the blocks r < b (slot (nblk - b) + r)
+      auto lo = [&](int b) { return std::max(a0 + b * 128, i0); };
+      auto hi = [&](int b) { return std::min(a0 + (b + 1) * 128, n); };
+      std::vector<size_t> base(nblk);
+      for (int b = 0; b < nblk; ++b) {
+        base[b] = pyoff;
+        pyoff += (size_t)nblk * SB * (hi(b) - lo(b));
+      }
+      for (int r = 0; r < nblk; ++r)
+        for (int c = r; c < nblk; ++c) {
+          const int wr = hi(r) - lo(r), wc = hi(c) - lo(c);
+          // stored: Y[:, block r] += Xt[:, block c] . C[rows of r, columns of c]^T
+          gy1.push_back(dm_gemm_make(Xt + lo(c), n, 1, false, C + (size_t)lo(r) * lda + lo(c), 1, lda, false,
+                                     py + base[r] + (size_t)(c - r) * SB * wr, wr, SB, wr, wc));
+          // mirrored: Y[:, block c] += Xt[:, block r] . conj(C[rows of r, columns of c])
+          if (c > r)
+            gy1.push_back(dm_gemm_make(Xt + lo(r), n, 1, false, C + (size_t)lo(r) * lda + lo(c), lda, 1, true,
+                                       py + base[c] + (size_t)((nblk - c) + r) * SB * wc, wc, SB, wc, wr));
+        }
+      for (int b = 0; b < nblk; ++b)
+        M_.sy.push_back(sb_sum_desc{Wp + lo(b), py + base[b], nblk, SB, hi(b) - lo(b), n, 1.0, 0.0});
+    } else
+    for (int cb = a0; cb < n; cb += 128) {
+      const int c_lo = std::max(cb, i0), c_hi = std::min(cb + 128, n);
+      if (c_hi <= c_lo) continue;
+      const int wN = c_hi - c_lo;
+      if (sp.SY == 1) {
+        gy1.push_back(dm_gemm_make(Xt + c_lo, n, 1, false, C + (size_t)c_lo * lda + c_lo, 1, lda, false, Wp + c_lo, n, SB, wN,
+                                   n - c_lo));
+        if (c_lo > i0)
+          gy2.push_back(dm_gemm_make(Xt + i0, n, 1, false, C + (size_t)i0 * lda + c_lo, lda, 1, true, Wp + c_lo, n, SB, wN,
+                                     c_lo - i0, 1.0, 1.0));
+      } else {
+        const int kc = std::max(128, ((m + sp.SY - 1) / sp.SY + 127) & ~127);
+        cplx* pb = py + pyoff;
+        int ns = 0;
+        for (int kk = c_lo; kk < n; kk += kc, ++ns)   // stored part: rows kk .. of the columns [c_lo, c_hi)
+          gy1.push_back(dm_gemm_make(Xt + kk, n, 1, false, C + (size_t)c_lo * lda + kk, 1, lda, false, pb + (size_t)ns * SB * wN, wN,
+                                     SB, wN, std::min(kc, n - kk)));
+        for (int kk = i0; kk < c_lo; kk += kc, ++ns)  // mirrored part: rows i0 .. c_lo of the transposed block
+          gy1.push_back(dm_gemm_make(Xt + kk, n, 1, false, C + (size_t)kk * lda + c_lo, lda, 1, true, pb + (size_t)ns * SB * wN, wN,
+                                     SB, wN, std::min(kc, c_lo - kk)));
+        M_.sy.push_back(sb_sum_desc{Wp + c_lo, pb, ns, SB, wN, n, 1.0, 0.0});
+        pyoff += (size_t)ns * SB * wN;
+      }
+    }
+    cplx* M1 = w.sbM1 + (size_t)p * SB * SB;
+    cplx* S = w.sbS + (size_t)p * SB * SB;
+    // M1 = V^H Y, S = T^H M1, W = Y - V S / 2  (row-stored: Wp += -1/2 S^T Vp)
+    int m1_slices = 0;
+    if (sp.SG == 1) {
+      gm.push_back(dm_gemm_make(Vp + i0, n, 1, true, Wp + i0, 1, n, false, M1, SB, SB, SB, m));
+    } else {
+      const int kc = (m + sp.SG - 1) / sp.SG;
+      int ns = 0;
+      for (int kk = 0; kk < m; kk += kc, ++ns)
+        gm.push_back(dm_gemm_make(Vp + i0 + kk, n, 1, true, Wp + i0 + kk, 1, n, false, pg + (size_t)ns * SB * SB, SB, SB, SB,
+                                  std::min(kc, m - kk)));
+      m1_slices = ns;
+    }
+    M_.ssv.push_back(sb_s_desc{T, NBB, m1_slices ? pg : M1, m1_slices, S});   // S = T^H (sum of the slices of M1)
+    gw.push_back(dm_gemm_make(S, 1, SB, false, Vp + i0, n, 1, false, Wp + i0, n, SB, m, SB, -0.5, 1.0));
+    // A22 -= V W^H + W V^H on the blocks on or above the diagonal (128-aligned origin a0)
+    gh.push_back(dm_gemm_make(pp + a0, 1, n, false, pp + (size_t)n * TNB + a0, n, 1, true, C + (size_t)a0 * lda + a0, lda,
+                              n - a0, n - a0, 2 * TNB, -1.0, 1.0, nullptr, DM_GEMM_UPPER | DM_GEMM_UPPER128));
+  }
+  DM_TRY(dm_gemm_plan_build(gy1, M_.py1));
+  DM_TRY(dm_gemm_plan_build(gy2, M_.py2));
+  DM_TRY(dm_gemm_plan_build(gm, M_.pm));
+  DM_TRY(dm_gemm_plan_build(gw, M_.pw));
+  DM_TRY(dm_gemm_plan_build(gh, M_.ph));
+  return DM_OK;
+}
+
+// one panel of S1: both chains, their descriptors in one staged copy
+int sb_panel(dm_ctx* ctx, const trd_ws& w, const sb_mat* d_sm, int k0) {
+  const int nc = w.b.np, cmax = w.b.maxn;
+  const int i0 = k0 + SB, a0 = i0 & ~127;
+  sb_side_set sd;
+  sb_main_set mn;
+  DM_TRY(sb_build_side(w, k0, sd));
+  DM_TRY(sb_build_main(w, k0, mn));
+  // every descriptor of the iteration travels in ONE staged copy: the grouped products as plans, the lists of slice
+  // sums, the S and the T-factor descriptors behind them
+  dm_gemm_plan extra;   // not a product: raw arrays carried by the same upload
+  size_t o_sy, o_ss, o_tf;
+  {
+    auto put = [&](const void* src, size_t bytes) {
+      const size_t o = (extra.blob.size() + 15) & ~size_t(15);
+      extra.blob.resize(o + bytes);
+      if (bytes) std::memcpy(extra.blob.data() + o, src, bytes);
+      return o;
+    };
+    o_sy = put(mn.sy.data(), mn.sy.size() * sizeof(sb_sum_desc));
+    o_ss = put(mn.ssv.data(), mn.ssv.size() * sizeof(sb_s_desc));
+    o_tf = put(sd.tf.data(), sd.tf.size() * sizeof(tf_mat));
+    if (extra.blob.empty()) extra.blob.resize(16);
+  }
+  std::vector<const char*> dv;
+  DM_TRY(dm_gemm_plans_upload(ctx, {&sd.pg, &sd.px, &mn.py1, &mn.py2, &mn.pm, &mn.pw, &mn.ph, &extra}, dv));
+  const char* d_extra = dv[7];
+  // side chain: the QR (one workgroup per matrix while the panel fits its registers, else the launched kernels), the
+  // Gram slices, the T factor of the panel (zlarft from the Gram matrix, straight into the slot the back-transformation
+  // reads) and X^T = T^T V^H
+  if (cmax - i0 <= SFR * SFT) {
+    double fl = 0.0;  // Householder QR of an m x SB panel: 2 SB^2 (m - SB / 3) complex multiply-adds
+    for (int p : w.b.order) {
+      const double m = w.b.probs[p].n - k0 - SB;
+      if (m >= 2) fl += 8.0 * 2.0 * SB * SB * std::max(m - SB / 3.0, 1.0);
+    }
+    dm_prof_scope ps(ctx, DM_PROF_SB_PANEL, fl);
+    hipLaunchKernelGGL(sb_panel_fused_kernel, dim3(nc), dim3(SFT), 0, ctx->stream, d_sm, k0, a0);
+  } else {
+    hipLaunchKernelGGL(sb_panel_load_kernel, dim3((cmax - a0 + 255) / 256, nc), dim3(256), 0, ctx->stream, d_sm, k0, a0);
+    const int nchmax = (cmax - i0 + SQR - 1) / SQR;
+    for (int q = 0; q <= SB; ++q) {
+      hipLaunchKernelGGL(sb_qr_update_kernel, dim3(nchmax, nc), dim3(256), 0, ctx->stream, d_sm, k0, q);
+      if (q < SB) hipLaunchKernelGGL(sb_qr_dots_kernel, dim3(nchmax, nc), dim3(256), 0, ctx->stream, d_sm, k0, q);
+    }
+  }
+  if (!sd.tf.empty()) {
+    DM_TRY(dm_gemm_plan_run(ctx, sd.pg, dv[0]));
+    DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, larft_kernel, dim3((unsigned)sd.tf.size()), dim3(256), LARFT_LDS, ctx->stream,
+               reinterpret_cast<const tf_mat*>(d_extra + o_tf));
+    DM_TRY(dm_gemm_plan_run(ctx, sd.px, dv[1]));
+  }
+  // main chain
+  DM_TRY(dm_gemm_plan_run(ctx, mn.py1, dv[2]));
+  DM_TRY(dm_gemm_plan_run(ctx, mn.py2, dv[3]));
+  if (!mn.sy.empty()) {
+    int mx = 0;
+    for (const auto& d : mn.sy) mx = std::max(mx, d.rows * d.cols);
+    DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_sum_partials_kernel, dim3((mx + 255) / 256, (unsigned)mn.sy.size()), dim3(256), 0,
+               ctx->stream, reinterpret_cast<const sb_sum_desc*>(d_extra + o_sy));
+  }
+  DM_TRY(dm_gemm_plan_run(ctx, mn.pm, dv[4]));
+  if (!mn.ssv.empty())
+    DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_s_kernel, dim3((unsigned)mn.ssv.size()), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const sb_s_desc*>(d_extra + o_ss));
+  DM_TRY(dm_gemm_plan_run(ctx, mn.pw, dv[5]));
+  DM_TRY(dm_gemm_plan_run(ctx, mn.ph, dv[6]));
+  return DM_OK;
+}
+
+// debugging aid (DM_SB_DUMP=<prefix>): a device array to the file <prefix><suffix>
+int sb_dump(dm_ctx* ctx, const char* prefix, const char* suffix, const void* src, size_t bytes) {
+  std::vector<char> h(bytes);
+  DM_TRY(dm_download(ctx, h.data(), src, bytes));
+  const std::string fn = std::string(prefix) + suffix;
+  if (FILE* f = fopen(fn.c_str(), "wb")) { fwrite(h.data(), 1, bytes, f); fclose(f); }
+  return DM_OK;
+}
+
+// ---- S2: the bulge chase of the band (sbAB) down to the tridiagonal (dd, ee), and the read-back of its error flag.
+// By default BY BAND POSITION (sb_chase_pos_kernel; DM_SB_CHASE=pairs keeps the sweep-owning pairs below): one
+// workgroup per (matrix, group of SB_POS_NP positions), largest matrix first (the order of cm), groups left to right; a
+// matrix whose groups could not all be resident at once stays on the sweep-owning kernel (no co-residency needed).
+int sb_chase(dm_ctx* ctx, const trd_ws& w, const std::vector<sb_chase_mat>& cm, const sb_chase_mat* d_cmat,
+             const char* dump) {
+  const int np = w.b.np, nc = w.b.np, cmax = w.b.maxn;
+  const size_t totn = w.b.totn;
+  int* sbNext = w.sbNext;
+  const char* chase = getenv("DM_SB_CHASE");
+  const bool by_pos = !(chase && strcmp(chase, "pairs") == 0);
+  int pos_cap = 224;   // workgroups of one matrix that may have to be resident together (one per CU, some CUs left to others)
+  if (const char* e = getenv("DM_SB_POS_CAP")) pos_cap = std::max(1, atoi(e));
+  bool pos_fits = by_pos;
+  for (int i = 0; i < nc && pos_fits; ++i)
+    if (cm[i].n >= 2 && (cm[i].jb + SB_POS_NP - 1) / SB_POS_NP > pos_cap) pos_fits = false;
+  if (pos_fits) {
+    std::vector<int2> ent;
+    double fl = 0.0;
+    for (int i = 0; i < nc; ++i) {
+      const int n = cm[i].n;
+      if (n < 1) continue;
+      const int ng = n >= 2 ? (cm[i].jb + SB_POS_NP - 1) / SB_POS_NP : 1;
+      for (int g = 0; g < ng; ++g) ent.push_back(make_int2(i, g));
+      fl += 8.0 * 6.0 * SB * SB * ((double)n * n / (2.0 * SB));
+    }
+    if (!ent.empty()) {
+      sb_pos_ctl pc;
+      int2* d_ent = dm_ws_upload(ctx, ent);
+      char* mail = dm_ws_alloc_t<char>(ctx, ent.size() * SB_POS_MAIL);
+      if (!d_ent || !mail) return DM_ENOMEM;
+      DM_TRY(dm_fill_zero(ctx, mail, ent.size() * SB_POS_MAIL));            // tags 0: no sweep has posted
+      DM_TRY(dm_fill_zero(ctx, sbNext + 2 * (size_t)np, sizeof(int) * 9));  // ticket counter, error flag
+      pc.ticket = sbNext + 2 * (size_t)np;
+      pc.err = sbNext + 2 * (size_t)np + 8;
+      pc.ent = d_ent;
+      pc.nent = (int)ent.size();
+      pc.mail = mail;
+      {
+        dm_prof_scope ps(ctx, DM_PROF_SB_CHASE, fl);
+        hipLaunchKernelGGL(sb_chase_pos_kernel, dim3((unsigned)ent.size()), dim3(128 * SB_POS_NP), 0, ctx->stream, d_cmat, pc);
+      }
+      int herr = 0;
+      DM_TRY(dm_download(ctx, &herr, pc.err, sizeof(int)));
+      if (herr) {
+        ctx->err = "bulge chase (by position): a wave waited for its neighbour for too long";
+        return 2000 + herr;
+      }
+    }
+    if (dump) {
+      DM_TRY(sb_dump(ctx, dump, ".d", w.dd, sizeof(double) * totn));
+      DM_TRY(sb_dump(ctx, dump, ".e", w.ee, sizeof(double) * totn));
+    }
+    DM_HIP(ctx, hipGetLastError());
+    return DM_OK;
+  }
+  // One persistent launch: per-XCD queues of matrix ids; a matrix gets as many entries (= workgroups) as its
+  // pipeline of sweeps can keep busy (sweep s + 1 trails sweep s by two blocks: n / (2 SB) sweeps in flight).
+  constexpr int NP = 4;   // sweeps a workgroup runs at a time (two waves per sweep: E chain + D updates)
+  constexpr int wgmax = 32;
+  std::vector<std::vector<int>> qs(8);
+  double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // workgroups are resident for the whole launch and stay with a matrix until its sweeps are taken: hand out at most
+  // as many entries as there are workgroups (one per CU), in proportion to the sweeps each matrix can keep in flight
+  double want = 0.0;
+  for (int i = 0; i < nc; ++i)
+    if (cm[i].n >= 1) want += std::max(1.0, (double)cm[i].n / (2 * SB * NP));
+  const double scale = want > 256.0 ? 256.0 / want : 1.0;
+  for (int i = 0; i < nc; ++i) {
+    const int n = cm[i].n;
+    if (n < 1) continue;
+    int k = std::max(1, std::min(wgmax, (int)(scale * n / (2 * SB * NP) + 0.999)));
+    if (scale < 1.0) k = std::max(1, (int)(scale * n / (2 * SB * NP) + 0.5));
+    int q = 0;
+    for (int t = 1; t < 8; ++t)
+      if (load[t] < load[q]) q = t;
+    load[q] += (double)n * n;
+    for (int t = 0; t < k; ++t) qs[q].push_back(i);
+  }
+  sb_chase_ctl ctl;
+  std::vector<int> qent;
+  for (int q = 0; q < 8; ++q) {
+    ctl.qoff[q] = (int)qent.size();
+    qent.insert(qent.end(), qs[q].begin(), qs[q].end());
+  }
+  ctl.qoff[8] = (int)qent.size();
+  int* d_qent = dm_ws_upload(ctx, qent);
+  if (!d_qent) return DM_ENOMEM;
+  ctl.qent = d_qent;
+  ctl.qhead = sbNext + 2 * (size_t)np;
+  DM_TRY(dm_fill_zero(ctx, w.sbProg, sizeof(unsigned) * 2 * totn));
+  DM_TRY(dm_fill_zero(ctx, sbNext, sizeof(int) * np));
+  DM_HIP(ctx, hipMemsetAsync(sbNext + np, 0xff, sizeof(int) * np, ctx->stream));
+  DM_TRY(dm_fill_zero(ctx, sbNext + 2 * (size_t)np, sizeof(int) * 9));
+  ctl.err = sbNext + 2 * (size_t)np + 8;
+  ctl.dbg = nullptr;
+  if (dump) {
+    ctl.dbg = dm_ws_alloc_t<unsigned long long>(ctx, 2 * (size_t)cmax + 2);
+    if (!ctl.dbg) return DM_ENOMEM;
+    DM_TRY(dm_fill_zero(ctx, ctl.dbg, sizeof(unsigned long long) * (2 * (size_t)cmax + 2)));
+  }
+  const int nwg = 256;  // one per CU: a matrix is served by the workgroups of ONE XCD, whichever claims it first
+  {
+    // one task = E <- H^H (E H) and the two-sided update of the Hermitian D: ~6 SB^2 complex multiply-adds
+    double fl = 0.0;
+    for (int i = 0; i < nc; ++i) {
+      const double n = cm[i].n;
+      fl += 8.0 * 6.0 * SB * SB * (n * n / (2.0 * SB));
+    }
+    dm_prof_scope ps(ctx, DM_PROF_SB_CHASE, fl);
+    hipLaunchKernelGGL((sb_chase2_kernel<NP>), dim3(nwg), dim3(128 * NP), 0, ctx->stream, d_cmat, ctl);
+  }
+  {
+    int herr = 0;  // (the eigenvalue selection synchronises right after this stage anyway)
+    DM_TRY(dm_download(ctx, &herr, sbNext + 2 * (size_t)np + 8, sizeof(int)));
+    if (herr) {
+      if (dump) {
+        DM_TRY(sb_dump(ctx, dump, ".dbg", ctl.dbg, sizeof(unsigned long long) * (2 * (size_t)cmax + 2)));
+        DM_TRY(sb_dump(ctx, dump, ".prog", w.sbProg, sizeof(unsigned) * 2 * totn));
+        DM_TRY(sb_dump(ctx, dump, ".next", sbNext, sizeof(int) * (2 * (size_t)np + 9)));
+      }
+      ctx->err = "bulge chase: a sweep waited for its predecessor for too long";
+      return 2000;
+    }
+  }
+  if (dump) {
+    DM_TRY(sb_dump(ctx, dump, ".dbg", ctl.dbg, sizeof(unsigned long long) * (2 * (size_t)cmax + 2)));
+    DM_TRY(sb_dump(ctx, dump, ".d", w.dd, sizeof(double) * totn));
+    DM_TRY(sb_dump(ctx, dump, ".e", w.ee, sizeof(double) * totn));
+  }
+  DM_HIP(ctx, hipGetLastError());
+  return DM_OK;
+}
+
+// ---- T1 by two stages: S1 leaves its reflectors in Vt / tau and the T factors of its panels in Tbig, S2 the tridiagonal
+// in dd / ee and the reflectors of the chase in sbVd / sbTau2
+int sb_reduce(dm_ctx* ctx, trd_ws& w) {
+  DM_TRY(sb_alloc(ctx, w));
+  const auto& probs = w.b.probs;
+  const int np = w.b.np, nc = w.b.np, cmax = w.b.maxn;
+  const std::vector<size_t>&off = w.b.off, &offn = w.b.offn;
+  std::vector<sb_mat> sm(nc);
+  std::vector<sb_dmat> dmv(nc);
+  std::vector<sb_bmat> bm(nc);
+  std::vector<sb_chase_mat> cm(nc);
+  for (int i = 0; i < nc; ++i) {
+    const int p = w.b.order[i];
+    const size_t n = probs[p].n;
+    cplx* pp = w.PP + offn[p] * 3 * TNB;
+    sm[i] = sb_mat{probs[p].C, probs[p].ldc, probs[p].n, w.Vt + off[p], pp, pp + n * TNB, pp + 2 * n * TNB,
+                   w.sbPw + offn[p] * SB, w.tau + offn[p], w.sbYp + w.offyp[p] * SB, w.sbNp + w.offyp[p] * 2, (int)(n / SQR + 1)};
+    dmv[i] = sb_dmat{probs[p].C, probs[p].ldc, probs[p].n};
+    bm[i] = sb_bmat{probs[p].C, probs[p].ldc, probs[p].n, w.sbAB + offn[p] * SLD};
+    cm[i] = sb_chase_mat{w.sbAB + offn[p] * SLD, probs[p].n, w.sbVd + w.offvd[p], w.sbTau2 + w.offt2[p], w.dd + offn[p],
+                         w.ee + offn[p], w.sb_jb[p], w.sbProg + 2 * offn[p], w.sbNext + p, w.sbNext + np + p};
+  }
+  sb_mat* d_sm = dm_ws_upload(ctx, sm);
+  sb_dmat* d_dm = dm_ws_upload(ctx, dmv);
+  sb_bmat* d_bm = dm_ws_upload(ctx, bm);
+  sb_chase_mat* d_cmat = dm_ws_upload(ctx, cm);
+  if (!d_sm || !d_dm || !d_bm || !d_cmat) return DM_ENOMEM;
+  DM_TRY(dm_fill_zero(ctx, w.Tbig, sizeof(cplx) * w.tottb));
+  // the chase writes whole rows of the reflector array: only the slots no sweep reaches are cleared
+  DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_vd_tail_zero_kernel, dim3((cmax + SBG - 1) / SBG, nc), dim3(256), 0, ctx->stream, d_cmat);
+  DM_TRY(dm_fill_zero(ctx, w.sbTau2, sizeof(cplx) * w.tott2));
+  DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_diag_tiles_kernel, dim3((cmax + 127) / 128, nc), dim3(256), 0, ctx->stream, d_dm);
+  // ---- S1
+  DM_TRY(larft_allow_lds(ctx));
+  for (int k0 = 0; cmax - k0 - SB >= 2; k0 += SB) {
+    if (sb_split_of(w, k0).nact == 0) continue;
+    DM_TRY(sb_panel(ctx, w, d_sm, k0));
+  }
+  // ---- S2: band -> tridiagonal
+  const char* dump = getenv("DM_SB_DUMP");  // debugging aid: the band and the tridiagonal of every matrix to files
+  const size_t maxel = (size_t)cmax * SLD;
+  DM_PLAUNCH(ctx, DM_PROF_EIG_OTHER, sb_band_extract_kernel, dim3((unsigned)((maxel + 255) / 256), nc), dim3(256), 0, ctx->stream, d_bm);
+  if (dump) DM_TRY(sb_dump(ctx, dump, ".band", w.sbAB, sizeof(cplx) * w.b.totn * SLD));
+  return sb_chase(ctx, w, cm, d_cmat, dump);
+}
+
+// ---- B2: X <- Q2 X (X = probs[p].C, n x ncolv[p]): workgroups of NW column slabs, large matrices first
+int sb_apply_q2(dm_ctx* ctx, const trd_ws& w, const std::vector<int>& ncolv) {
+  const auto& probs = w.b.probs;
+  constexpr int NW = 4;
+  // 16 columns per wave (four lanes per column).  Eight lanes per column (twice the waves, five instead of nine rows
+  // of a reflector per lane) were measured slower in both regimes — configs[1] batch 11.3 against 9.2 ms, one matrix of
+  // 32 576 rows 8.8 against 7.6 s: the fixed cost per reflector (fetch, fold, scale) weighs more than the extra waves
+  // hide.
+  constexpr int ncw = 16;
+  std::vector<sb_q2_mat> qm;
+  std::vector<int2> wgs;
+  for (int p : w.b.order) {
+    if (probs[p].n < 2 || ncolv[p] <= 0) continue;
+    const int mi = (int)qm.size();
+    qm.push_back(sb_q2_mat{w.sbVd + w.offvd[p], w.sbTau2 + w.offt2[p], w.sb_jb[p], probs[p].C, probs[p].ldc, probs[p].n, ncolv[p], 0});
+    const int nslab = (ncolv[p] + ncw - 1) / ncw;
+    for (int s0 = 0; s0 < nslab; s0 += NW) wgs.push_back(make_int2(mi, s0));
+  }
+  if (wgs.empty()) return DM_OK;
+  if (getenv("DM_TRD_SIZES")) {
+    fprintf(stderr, "[apply_q2] n:ncol");
+    for (const auto& q : qm) fprintf(stderr, " %d:%d", q.n, q.ncol);
+    fprintf(stderr, " -> %zu workgroups\n", wgs.size());
+  }
+  sb_q2_mat* d_qm = dm_ws_upload(ctx, qm);
+  int2* d_wgs = dm_ws_upload(ctx, wgs);
+  if (!d_qm || !d_wgs) return DM_ENOMEM;
+  const size_t lds = sizeof(cplx) * (2 * SBG * SBW + 2 * SBG);
+  static bool attr = false;
+  if (!attr) {
+    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sb_q2_apply_kernel<NW>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  double fl = 0.0;  // n^2 / (2 SB) reflectors of length SB on ncol columns: 2 SB complex multiply-adds per column each
+  for (const auto& q : qm) fl += 8.0 * (double)q.n * q.n * q.ncol;
+  dm_prof_scope ps(ctx, DM_PROF_SB_Q2, fl);
+  hipLaunchKernelGGL((sb_q2_apply_kernel<NW>), dim3((unsigned)wgs.size()), dim3(64 * NW), lds, ctx->stream, d_qm, d_wgs);
+  DM_HIP(ctx, hipGetLastError());
+  return DM_OK;
 }
