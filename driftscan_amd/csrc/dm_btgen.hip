@@ -867,21 +867,6 @@ __global__ void bt_mask_kernel(cplx* __restrict__ beam_m, int F, int B, int P, i
   beam_m[((((size_t)m * F + f) * 2 + s) * B + b) * P * L + (size_t)p * L + l] = make_double2(0.0, 0.0);
 }
 
-// rows of the private coefficient buffer of the refinement path -> the caller's beam_m blocks
-// src (msrc, 1, 2, ncol, P, L), dst (m_hi - m_lo + 1, F, 2, B, P, L); blocks beyond msrc - 1 are zero
-__global__ void bt_scatter_kernel(const cplx* __restrict__ src, int msrc, cplx* __restrict__ dst, int m_lo, int F, int B, int P,
-                                  int L, int ncol, const int* __restrict__ colf, const int* __restrict__ colb) {
-  const int col = blockIdx.y;
-  const int mo = blockIdx.z;  // output block index, m = m_lo + mo
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // over (s, p, l)
-  if (idx >= 2 * P * L) return;
-  const int s = idx / (P * L), pl = idx % (P * L);
-  const int m = m_lo + mo;
-  cplx v = make_double2(0.0, 0.0);
-  if (m < msrc) v = src[(((size_t)m * 2 + s) * ncol + col) * P * L + pl];
-  dst[((((size_t)mo * F + colf[col]) * 2 + s) * B + colb[col]) * P * L + pl] = v;
-}
-
 
 // ---- harmonic-space Jacobi refinement (healpy.map2alm `iter`) ------------------------------------------------------
 // healpy refines the quadrature as  a <- a + A(map - S a)  (A: map2alm with iter = 0, S: alm2map), i.e.
@@ -1063,15 +1048,13 @@ __global__ __launch_bounds__(256) void bt_alias_fold_kernel(const cplx* __restri
 // the alias-ring table value tabA_m[l][ja] (the analysis of the folded rings rides in the K dimension of the product)
 __global__ __launch_bounds__(256) void bt_kext_fill_kernel(const double* __restrict__ tabA, const size_t* __restrict__ loffA,
                                                            double* __restrict__ Kx, const size_t* __restrict__ kxoff, int lmax_grp,
-                                                           int nra, int kfast) {
+                                                           int nra) {
   const int m = blockIdx.y;
   const int Lm = lmax_grp + 1 - m, Kd = Lm + nra;
   const size_t tot = (size_t)Lm * nra;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * 256) {
     const size_t l = idx / nra, ja = idx - l * nra;
-    const double v = tabA[loffA[m] + idx];
-    if (kfast) Kx[kxoff[m] + l * Kd + Lm + ja] = v;
-    else Kx[kxoff[m] + (Lm + ja) * Lm + l] = v;
+    Kx[kxoff[m] + l * Kd + Lm + ja] = tabA[loffA[m] + idx];
   }
 }
 
@@ -1117,6 +1100,68 @@ frame3 make_frame(const double* xhat, const double* yhat, const double* zhat) {
   for (int i = 0; i < 3; ++i) { f.x[i] = xhat[i]; f.y[i] = yhat[i]; f.z[i] = zhat[i]; }
   return f;
 }
+
+// ---- which Stokes term takes which table ----------------------------------------------------------------------------
+// add(input Stokes, table, output Stokes, alpha_re, alpha_im, beta) for the terms of one pass.  Terms whose outputs
+// accumulate (E and B each take two products) go in separate passes = separate launches, so that no two tiles of one
+// launch touch the same C entries.  Analysis: T = lam . I, V = lam . V, E = W . Q - i X . U, B = W . U + i X . Q; the
+// synthesis (Q = W E - i X B, U = W B + i X E) and the Gram products (E' = K_P E - i K_X B, B' = K_P B + i K_X E) apply
+// the same Hermitian block.
+struct bt_tables {
+  double *T = nullptr, *W = nullptr, *X = nullptr;   // the scalar table and the spin-2 pair (polarised only)
+  double* operator[](int i) const { return i == 0 ? T : i == 1 ? W : X; }
+};
+// n doubles per table out of the workspace
+bool bt_tables_alloc(dm_ctx* ctx, bool polarised, size_t n, bt_tables& t) {
+  t.T = dm_ws_alloc_t<double>(ctx, n);
+  if (polarised) { t.W = dm_ws_alloc_t<double>(ctx, n); t.X = dm_ws_alloc_t<double>(ctx, n); }
+  return t.T && (!polarised || (t.W && t.X));
+}
+template <class Add>
+void bt_stokes_terms(bool polarised, int pass, const bt_tables& t, double beta0, Add&& add) {
+  if (pass == 0) {
+    add(0, t.T, 0, 1.0, 0.0, beta0);
+    if (!polarised) return;
+    add(3, t.T, 3, 1.0, 0.0, beta0);
+    add(1, t.W, 1, 1.0, 0.0, beta0);
+    add(2, t.W, 2, 1.0, 0.0, beta0);
+  } else {
+    add(2, t.X, 1, 0.0, -1.0, 1.0);
+    add(1, t.X, 2, 0.0, 1.0, 1.0);
+  }
+}
+
+// ---- kernel choice of the fused ring transform ------------------------------------------------------------------------
+using bt_dft_fn = decltype(&bt_fused_dft_kernel<1, 1, 8>);   // (bt_fused_dft2_kernel has the same signature)
+using bt_fft_fn = decltype(&bt_fused_fft_kernel<1, 1, 256>);
+// fn[1]: complex field patterns
+struct bt_dft_row { int P, nmg_from, cgw, mgw; bt_dft_fn fn[2]; };   // a workgroup takes cgw column groups, mgw groups of four m
+struct bt_fft_row { int P, npt; bt_fft_fn fn[2]; };
+template <int P, int NMG, int NCG>
+bt_dft_row bt_dft_of(int nmg_from) {
+  return {P, nmg_from, 4 * NCG, NMG, {bt_fused_dft_kernel<P, NMG, NCG>, bt_fused_dft_kernel<P, NMG, NCG, true>}};
+}
+template <int P, int NMG, int NCG>
+bt_dft_row bt_dft2_of(int nmg_from) {
+  return {P, nmg_from, NCG, 4 * NMG, {bt_fused_dft2_kernel<P, NMG, NCG>, bt_fused_dft2_kernel<P, NMG, NCG, true>}};
+}
+template <int P, int NPT>
+bt_fft_row bt_fft_of() {
+  return {P, NPT, {bt_fused_fft_kernel<P, NPT, 256>, bt_fused_fft_kernel<P, NPT, 256, true>}};
+}
+// Matrix form: the first row of its P with nmg >= nmg_from, nmg = groups of four m-values of the call.
+// 32 complex accumulators per lane (64 AGPRs) keep two waves per SIMD: the sincos of one wave runs under
+// the MFMAs of the other
+// measured: twice / four times the m-values per pass (<4,4,1>, <4,8,1>, <1,8,2>, <1,16,1>) halve the repeated
+// synthesis but cost a wave per SIMD — no faster on configs[1] or configs[2]
+// shared-synthesis kernel: the four waves of a workgroup take different m-values (16 NMG per pass)
+static const bt_dft_row bt_dft_rows[] = {bt_dft2_of<4, 2, 1>(3), bt_dft_of<4, 2, 2>(2), bt_dft_of<4, 1, 4>(0),
+                                         bt_dft2_of<1, 2, 4>(5), bt_dft_of<1, 4, 4>(2), bt_dft_of<1, 1, 8>(0)};
+// FFT belt: NPT = max(1, N / 256) pixels per thread at 256 threads (measured at nside 512 with four maps: 256 threads
+// 3.6 s per rank call, 1024 threads 6.4 s — the barriers of sixteen waves cost more than their latency hiding brings).
+// N = 512 is <4, 2>, N = 2048 <1, 8>; 4096 x 4 maps does not fit the LDS.
+static const bt_fft_row bt_fft_rows[] = {bt_fft_of<4, 1>(), bt_fft_of<4, 2>(), bt_fft_of<4, 4>(), bt_fft_of<4, 8>(), bt_fft_of<1, 1>(),
+                                         bt_fft_of<1, 2>(), bt_fft_of<1, 4>(), bt_fft_of<1, 8>(), bt_fft_of<1, 16>()};
 
 }  // namespace
 
@@ -1281,600 +1326,570 @@ struct bt_synth_in {
   int complex_beams;   // beams_dev holds complex patterns (interleaved re, im): _construct_pol_complex inside the kernels
 };
 
-static int bt_sht_impl(dm_ctx* ctx, int nside, const double* ring_cth_host, const double* ring_sth_host, int polarised,
-                       int lside, int m_lo, int m_hi, int lmax_grp, int F, int B, int ncol, const int* col_f_host,
-                       const int* col_b_host, const int* col_lmax_host, const void* maps_dev, void* beam_m_dev, int niter,
-                       const double* ring_w_host, const bt_synth_in* syn = nullptr, bool harmonic = false, int row_pad = 0) {
-  if (!ctx) return DM_EARG;
-  DM_ARG(ctx, maps_dev || (syn && (niter == 0 || harmonic)));
-  DM_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && lside >= 0 && m_lo >= 0 && m_hi >= m_lo && lmax_grp >= 0 &&
-                  lmax_grp <= lside && F > 0 && B > 0 && ncol >= 0 && col_f_host && col_b_host && col_lmax_host &&
-                  beam_m_dev && niter >= 0);
-  DM_ARG(ctx, niter == 0 || harmonic || (m_lo == 0 && m_hi >= lmax_grp));  // the residual map needs every m of a column
-  // the harmonic-space refinement runs on a private coefficient buffer laid out (m, 2, col, P, L) (bt_sht_refined)
-  DM_ARG(ctx, !(niter > 0 && harmonic) || (F == 1 && B == ncol && lside == lmax_grp));
-  DM_ARG(ctx, row_pad == 0 || (niter > 0 && harmonic));
-  if (ncol == 0) return DM_OK;
-  dm_ws_scope ws_scope__(ctx);  // releases on every return path
-  const size_t mark = ws_scope__.mark;
+enum bt_sht_mode {
+  BT_ANALYSIS,         // niter == 0: the quadrature alone
+  BT_REFINE_HARMONIC,  // niter > 0 in harmonic space, on a private coefficient buffer laid out (m, 2, col, P, L) whose rows
+                       // carry row_pad alias slots behind the lside + 1 coefficients (bt_sht_private)
+  BT_REFINE_MAPS       // niter > 0 through residual maps (synthesis, inverse ring DFT, re-analysis): DM_SHT_PIXEL_REFINE=1
+};
+
+// what the caller asked for
+struct bt_sht_args {
+  int nside;
+  const double *ring_cth_host, *ring_sth_host;
+  int polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol;
+  const int *col_f_host, *col_b_host, *col_lmax_host;
+  void* beam_m_dev;
+  int niter;
+  const double* ring_w_host;
+  const void* maps_dev = nullptr;     // the Stokes maps, or
+  const bt_synth_in* syn = nullptr;   // what the fused ring transform synthesises them from
+  bt_sht_mode mode = BT_ANALYSIS;
+  int row_pad = 0;
+};
+
+struct bt_run { int c0, n, f, b0; };   // columns c0 .. c0 + n - 1 are baselines b0 .. b0 + n - 1 of frequency f
+
+// what the stages of bt_sht_run share
+struct bt_sht_ws {
   geo_host gh;
-  DM_TRY(upload_geo(ctx, nside, ring_cth_host, ring_sth_host, gh));
-  const int P = polarised ? 4 : 1;
-  const int L = lside + 1 + row_pad;   // row length of the destination (row_pad: alias slots of the private buffers)
-  const int nring = gh.g.nring, npix = gh.g.npix;
-  const int mtop = std::min(m_hi, lmax_grp);  // no (l, m) content above the group's band limit
-  const int cnt = std::max(mtop - m_lo + 1, 0);  // m values with content in this range
-  const int nm = 2 * std::max(cnt, 1);
-  const int ncp = ncol * P;  // map columns
-  const int nmblk = m_hi - m_lo + 1;
-
-  // ---- twiddles and ring DFT: G[mm][ring][colp] — colp = col * P + p from materialised maps, p * ncol + col from the fused kernels
-  const bool fused = maps_dev == nullptr;
-  std::vector<size_t> toff(nring);
-  size_t ttot = 0;
-  for (int r = 0; r < nring; ++r) { toff[r] = ttot; ttot += (size_t)nm * gh.nphi[r]; }
-  size_t* d_toff = dm_ws_upload(ctx, toff);
-  cplx* tw = fused ? nullptr : dm_ws_alloc_t<cplx>(ctx, ttot);
-  cplx* G = dm_ws_alloc_t<cplx>(ctx, (size_t)nm * nring * ncp);
-  if (!d_toff || (!fused && !tw) || !G) return DM_ENOMEM;
-  if (!fused)
-    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_twiddle_kernel, dim3(8, nring), dim3(256), 0, ctx->stream, gh.g, m_lo, std::max(cnt, 1), d_toff,
-                       tw);
-  if (fused && cnt > 0) {
-    // beam solid angles, per-column constants, then synthesis + DFT in one kernel (no Stokes maps in HBM)
-    const bool cbm = syn->complex_beams != 0;
-    const int ncomp = (polarised ? 2 : 1) * (cbm ? 2 : 1);   // doubles per pixel of a beam (complex patterns: re, im)
-    const size_t bstride = (size_t)npix * ncomp;
-    frame3 fr = make_frame(syn->frame_host, syn->frame_host + 3, syn->frame_host + 6);
-    double* omega = dm_ws_alloc_t<double>(ctx, syn->nbeam);
-    double* opart = dm_ws_alloc_t<double>(ctx, (size_t)syn->nbeam * NOMEGA);
-    if (!omega || !opart) return DM_ENOMEM;
-    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_omega_part_kernel, dim3(syn->nbeam, NOMEGA), dim3(256), 0, ctx->stream, gh.g, syn->beams_dev, ncomp,
-                       bstride, opart);
-    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_omega_fin_kernel, dim3((syn->nbeam + 63) / 64), dim3(64), 0, ctx->stream, opart, syn->nbeam,
-                       4.0 * kPi / (double)npix, omega);
-    // (the solid angles stay on the device: the per-column factor 1 / sqrt(Omega_i Omega_j) is filled in by a small
-    // kernel, so the host never waits inside the call)
-    const int ncol16 = (ncol + 15) / 16;
-    std::vector<fdft_col> fc((size_t)ncol16 * 16, fdft_col{0.0, 0.0, 0.0, -1, -1});
-    for (int c = 0; c < ncol; ++c) {
-      const int bi = syn->bi_host[c], bj = syn->bj_host[c];
-      DM_ARG(ctx, bi >= 0 && bi < syn->nbeam && bj >= 0 && bj < syn->nbeam);
-      fc[c] = fdft_col{syn->uv_host[2 * c], syn->uv_host[2 * c + 1], 0.0, bi, bj};
-    }
-    fdft_col* d_fc = dm_ws_upload(ctx, fc);
-    if (d_fc) DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_fdft_pre_kernel, dim3((ncol + 255) / 256), dim3(256), 0, ctx->stream, d_fc, ncol, omega);
-    double* d_rw = nullptr;
-    if (ring_w_host) {
-      std::vector<double> rw(ring_w_host, ring_w_host + nring);
-      d_rw = dm_ws_upload(ctx, rw);
-      if (!d_rw) return DM_ENOMEM;
-    }
-    if (!d_fc) return DM_ENOMEM;
-    const int nmg = (nm + 3) / 4;  // groups of four m-values
-    // The belt (rings nside - 1 .. 3 nside - 1, all with N = 4 nside pixels) goes by FFT when N is a power of two and the
-    // P maps of a column fit the LDS; the matrix-form kernels below then see the rings of the two caps only.  The choice
-    // depends on nside, P and on whether the call is narrow (below) — not on WHICH m it asks for.
-    static const bool fft_off = getenv("DM_BT_FFT") && atoi(getenv("DM_BT_FFT")) == 0;
-    const int N = 4 * nside;
-    int fft_logn = 0;
-    while ((1 << fft_logn) < N) ++fft_logn;
-    const int fft_sh = std::max(5, fft_logn - 6);   // padding of the LDS arrays, as in the kernel
-    const size_t fft_lds = sizeof(cplx) * ((size_t)P * (N + (N >> fft_sh) + 1) + (N / 2 + ((N / 2) >> fft_sh) + 1));
-    // A NARROW call (at most DM_BT_NARROW = 8 m-values: one pass of the shared-synthesis kernel) keeps the matrix form on
-    // the belt too: the FFT computes every m of a ring whether wanted or not — 14 CU-cycles per (pixel, column) at nside
-    // 512 with four maps (150 KB of LDS: one workgroup per CU) against ~1 per group of four m-rows on the matrix pipe.
-    // One m-block of configs[4] (59.6 GB: a rank holds one or two at a time) 24.8 -> 4.6 s of ring transform
-    // (scratch/btgen_narrow_probe.py: 784 -> 146 ms on 8 of the 256 frequencies; 4 m-values 833 -> 229, 8: 1039 -> 555).
-    // The two forms round differently (2e-13 of the largest coefficient): blocks are the same BITS for any partition
-    // of m whose calls are all wide, and equal to rounding when narrow calls are involved.
-    static const int narrow_max = getenv("DM_BT_NARROW") ? atoi(getenv("DM_BT_NARROW")) : 8;
-    const bool narrow = cnt <= narrow_max;
-    const bool use_fft = !fft_off && !narrow && nside >= 2 && (N & (N - 1)) == 0 && N <= 4096 && fft_lds <= 160u * 1024u - 256u;
-    int nring_dft = nring;
-    const int* d_caps = nullptr;
-    if (use_fft) {
-      std::vector<int> caps;
-      for (int r = 0; r < nring; ++r)
-        if (r < nside - 1 || r > 3 * nside - 1) caps.push_back(r);
-      nring_dft = (int)caps.size();
-      if (nring_dft > 0) {
-        d_caps = dm_ws_upload(ctx, caps);
-        if (!d_caps) return DM_ENOMEM;
-      }
-      const int nring_eq = 2 * nside + 1;
-      const int cpw = std::max(4, std::min(32, (int)(((size_t)ncol * nring_eq) / 4096)));
-      const dim3 grid((unsigned)((ncol + cpw - 1) / cpw), (unsigned)nring_eq);
-      static const int wide_env = getenv("DM_BT_FFT_WIDE") ? atoi(getenv("DM_BT_FFT_WIDE")) : -1;
-      // (measured at nside 512 with four maps: 256 threads 3.6 s per rank call, 1024 threads 6.4 s — the barriers of
-      // sixteen waves cost more than their latency hiding brings; the wide variant stays behind DM_BT_FFT_WIDE=1)
-      const bool wide = wide_env > 0 && (polarised ? N >= 1024 : N == 4096);
-      auto fft_launch = [&](auto kern, int tpb) -> int {
-        DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)fft_lds));
-        DM_PLAUNCH(ctx, DM_PROF_BT_RING, kern, grid, dim3(tpb), fft_lds, ctx->stream, gh.g, fr, syn->beams_dev, bstride, d_fc, ncol, m_lo,
-                           cnt, d_rw, G, ncp, nside - 1, cpw);
-        return DM_OK;
-      };
-      if (wide) {
-        const int npt = std::max(1, N / 1024);
-        if (polarised) {
-          if (npt == 1) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<4, 1, 1024, true> : bt_fused_fft_kernel<4, 1, 1024>), 1024));
-          else DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<4, 2, 1024, true> : bt_fused_fft_kernel<4, 2, 1024>), 1024));   // N = 2048 (4096 x 4 maps does not fit)
-        } else {
-          DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<1, 4, 1024, true> : bt_fused_fft_kernel<1, 4, 1024>), 1024));         // N = 4096
-        }
-      } else {
-        const int npt = std::max(1, N / 256);
-        if (polarised) {
-          if (npt == 1) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<4, 1, 256, true> : bt_fused_fft_kernel<4, 1, 256>), 256));
-          else if (npt == 2) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<4, 2, 256, true> : bt_fused_fft_kernel<4, 2, 256>), 256));      // N = 512
-          else if (npt == 4) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<4, 4, 256, true> : bt_fused_fft_kernel<4, 4, 256>), 256));
-          else DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<4, 8, 256, true> : bt_fused_fft_kernel<4, 8, 256>), 256));
-        } else {
-          if (npt == 1) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<1, 1, 256, true> : bt_fused_fft_kernel<1, 1, 256>), 256));
-          else if (npt == 2) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<1, 2, 256, true> : bt_fused_fft_kernel<1, 2, 256>), 256));
-          else if (npt == 4) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<1, 4, 256, true> : bt_fused_fft_kernel<1, 4, 256>), 256));
-          else if (npt == 8) DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<1, 8, 256, true> : bt_fused_fft_kernel<1, 8, 256>), 256));      // N = 2048
-          else DM_TRY(fft_launch((cbm ? bt_fused_fft_kernel<1, 16, 256, true> : bt_fused_fft_kernel<1, 16, 256>), 256));
-        }
-      }
-    }
-    // (m, ring) pairs below rounding: exact zeros, no work (bt_ring_skip_lookup; DM_BT_RING_SKIP=0 computes them all)
-    const bool ring_skip_off = getenv("DM_BT_RING_SKIP") && atoi(getenv("DM_BT_RING_SKIP")) == 0;   // (read per call: the tests flip it)
-    const int* d_mskip = nullptr;
-    if (!ring_skip_off && nring_dft > 0) {
-      d_mskip = dm_ws_upload(ctx, bt_ring_skip_lookup(nside, lmax_grp, polarised != 0, ring_cth_host, ring_sth_host));
-      if (!d_mskip) return DM_ENOMEM;
-    }
-    auto launch = [&](auto kern, int NMG, int NCG) {
-      if (nring_dft == 0) return;
-      const dim3 grid((unsigned)((ncol16 + 4 * NCG - 1) / (4 * NCG)), (unsigned)nring_dft, (unsigned)((nmg + NMG - 1) / NMG));
-      DM_PLAUNCH(ctx, DM_PROF_BT_RING, kern, grid, dim3(256), 0, ctx->stream, gh.g, fr, syn->beams_dev, bstride, d_fc, ncol16, m_lo, cnt, d_rw, G,
-                         ncp, d_caps, d_mskip);
-    };
-    // 32 complex accumulators per lane (64 AGPRs) keep two waves per SIMD: the sincos of one wave runs under
-    // the MFMAs of the other
-    // measured: twice / four times the m-values per pass (<4,4,1>, <4,8,1>, <1,8,2>, <1,16,1>) halve the repeated
-    // synthesis but cost a wave per SIMD — no faster on configs[1] or configs[2]
-    // shared-synthesis kernel: the four waves of a workgroup take different m-values (16 NMG per pass)
-    auto launch2 = [&](auto kern, int NMG, int NCG) {
-      if (nring_dft == 0) return;
-      const dim3 grid((unsigned)((ncol16 + NCG - 1) / NCG), (unsigned)nring_dft, (unsigned)((nmg + 4 * NMG - 1) / (4 * NMG)));
-      DM_PLAUNCH(ctx, DM_PROF_BT_RING, kern, grid, dim3(256), 0, ctx->stream, gh.g, fr, syn->beams_dev, bstride, d_fc, ncol16, m_lo, cnt, d_rw, G,
-                         ncp, d_caps, d_mskip);
-    };
-    static const int shared_env = getenv("DM_FDFT_SHARED") ? atoi(getenv("DM_FDFT_SHARED")) : 1;
-    if (polarised) {
-      if (nmg <= 1) launch((cbm ? bt_fused_dft_kernel<4, 1, 4, true> : bt_fused_dft_kernel<4, 1, 4>), 1, 4);
-      else if (shared_env == 2 && nmg > 8) launch2((cbm ? bt_fused_dft2_kernel<4, 4, 1, true> : bt_fused_dft2_kernel<4, 4, 1>), 4, 1);
-      else if (shared_env >= 1 && nmg > 2) launch2((cbm ? bt_fused_dft2_kernel<4, 2, 1, true> : bt_fused_dft2_kernel<4, 2, 1>), 2, 1);
-      else launch((cbm ? bt_fused_dft_kernel<4, 2, 2, true> : bt_fused_dft_kernel<4, 2, 2>), 2, 2);
-    } else {
-      if (nmg <= 1) launch((cbm ? bt_fused_dft_kernel<1, 1, 8, true> : bt_fused_dft_kernel<1, 1, 8>), 1, 8);
-      else if (shared_env == 2 && nmg > 8) launch2((cbm ? bt_fused_dft2_kernel<1, 4, 4, true> : bt_fused_dft2_kernel<1, 4, 4>), 4, 4);
-      else if (shared_env >= 1 && nmg > 4) launch2((cbm ? bt_fused_dft2_kernel<1, 2, 4, true> : bt_fused_dft2_kernel<1, 2, 4>), 2, 4);
-      else launch((cbm ? bt_fused_dft_kernel<1, 4, 4, true> : bt_fused_dft_kernel<1, 4, 4>), 4, 4);
-    }
-    DM_HIP(ctx, hipGetLastError());
-  }
-  auto ring_dft = [&](const cplx* maps) -> int {
-    std::vector<dm_gemm_desc> g;
-    g.reserve(nring);
-    for (int r = 0; r < nring; ++r) {
-      // C[mm][colp] (ld = nring*ncp, origin at ring r) = w_r * tw_r[mm][j] * maps[colp][start_r + j]
-      g.push_back(dm_gemm_make(tw + toff[r], gh.nphi[r], 1, false, maps + gh.start[r], 1, npix, false,
-                               G + (size_t)r * ncp, nring * ncp, nm, ncp, gh.nphi[r], ring_w_host ? ring_w_host[r] : 1.0));
-    }
-    return dm_gemm_grouped_launch(ctx, g);
-  };
-  if (cnt > 0 && !fused) DM_TRY(ring_dft(reinterpret_cast<const cplx*>(maps_dev)));
-
-  // ---- Legendre tables up to lmax_grp
-  std::vector<size_t> loff(std::max(cnt, 1), 0);  // loff[m - m_lo]
+  int P, L, nring, npix, mtop, cnt, nm, ncp, nmblk;
+  bool fused;            // no maps: the ring transform synthesises them (G rows p * ncol + col instead of col * P + p)
+  bool folded = false;   // G holds north + south / south - north (bt_fold_kernel)
+  std::vector<size_t> toff, loff;   // twiddles per ring; tables per m - m_lo
   size_t ltot = 0;
-  for (int m = m_lo; m <= mtop; ++m) { loff[m - m_lo] = ltot; ltot += (size_t)(lmax_grp + 1 - m) * nring; }
-  size_t* d_loff = dm_ws_upload(ctx, loff);
-  double* lam = dm_ws_alloc_t<double>(ctx, std::max<size_t>(ltot, 1));
-  double* Wt = polarised ? dm_ws_alloc_t<double>(ctx, std::max<size_t>(ltot, 1)) : nullptr;
-  double* Xt = polarised ? dm_ws_alloc_t<double>(ctx, std::max<size_t>(ltot, 1)) : nullptr;
-  if (!d_loff || !lam || (polarised && (!Wt || !Xt))) return DM_ENOMEM;
-  if (cnt > 0)
-    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_legendre_kernel, dim3((nring + 63) / 64, cnt), dim3(64), 0, ctx->stream, gh.g, lmax_grp, m_lo,
-                       mtop, 4.0 * kPi / (double)npix, d_loff, lam, Wt, Xt);
+  std::vector<bt_run> runs;
+  cplx *tw{}, *G{}, *bm{};
+  bt_tables tab;   // lambda_lm, W_lm, X_lm times the quadrature weight
+  int *d_cf{}, *d_cb{}, *d_cl{}, *d_neg{};
+};
+
+// ---- stage: ring-transform buffers.  G[mm][ring][colp] — colp = col * P + p from materialised maps, p * ncol + col from
+// the fused kernels; the twiddle table only where the maps exist
+static int bt_ring_buffers(dm_ctx* ctx, const bt_sht_args& a, bt_sht_ws& w) {
+  w.toff.resize(w.nring);
+  size_t ttot = 0;
+  for (int r = 0; r < w.nring; ++r) { w.toff[r] = ttot; ttot += (size_t)w.nm * w.gh.nphi[r]; }
+  size_t* d_toff = dm_ws_upload(ctx, w.toff);
+  w.tw = w.fused ? nullptr : dm_ws_alloc_t<cplx>(ctx, ttot);
+  w.G = dm_ws_alloc_t<cplx>(ctx, (size_t)w.nm * w.nring * w.ncp);
+  if (!d_toff || (!w.fused && !w.tw) || !w.G) return DM_ENOMEM;
+  if (!w.fused)
+    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_twiddle_kernel, dim3(8, w.nring), dim3(256), 0, ctx->stream, w.gh.g, a.m_lo, std::max(w.cnt, 1),
+                       d_toff, w.tw);
+  return DM_OK;
+}
+
+// ---- stage: ring transform from maps (the caller's, or the residual maps of the map-space refinement): one grouped ZGEMM
+static int bt_ring_from_maps(dm_ctx* ctx, const bt_sht_args& a, const bt_sht_ws& w, const cplx* maps) {
+  std::vector<dm_gemm_desc> g;
+  g.reserve(w.nring);
+  for (int r = 0; r < w.nring; ++r) {
+    // C[mm][colp] (ld = nring*ncp, origin at ring r) = w_r * tw_r[mm][j] * maps[colp][start_r + j]
+    g.push_back(dm_gemm_make(w.tw + w.toff[r], w.gh.nphi[r], 1, false, maps + w.gh.start[r], 1, w.npix, false,
+                             w.G + (size_t)r * w.ncp, w.nring * w.ncp, w.nm, w.ncp, w.gh.nphi[r],
+                             a.ring_w_host ? a.ring_w_host[r] : 1.0));
+  }
+  return dm_gemm_grouped_launch(ctx, g);
+}
+
+// ---- stage: fused ring transform — beam solid angles, per-column constants, then synthesis + DFT in one kernel (no
+// Stokes maps in HBM): the belt by FFT where that pays, the caps (or every ring) in matrix form
+static int bt_ring_fused(dm_ctx* ctx, const bt_sht_args& a, const bt_sht_ws& w) {
+  const bt_synth_in* syn = a.syn;
+  const int nside = a.nside, ncol = a.ncol, nring = w.nring, P = w.P;
+  const int cbm = syn->complex_beams != 0;
+  const int ncomp = (a.polarised ? 2 : 1) * (cbm ? 2 : 1);   // doubles per pixel of a beam (complex patterns: re, im)
+  const size_t bstride = (size_t)w.npix * ncomp;
+  frame3 fr = make_frame(syn->frame_host, syn->frame_host + 3, syn->frame_host + 6);
+  double* omega = dm_ws_alloc_t<double>(ctx, syn->nbeam);
+  double* opart = dm_ws_alloc_t<double>(ctx, (size_t)syn->nbeam * NOMEGA);
+  if (!omega || !opart) return DM_ENOMEM;
+  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_omega_part_kernel, dim3(syn->nbeam, NOMEGA), dim3(256), 0, ctx->stream, w.gh.g, syn->beams_dev, ncomp,
+                     bstride, opart);
+  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_omega_fin_kernel, dim3((syn->nbeam + 63) / 64), dim3(64), 0, ctx->stream, opart, syn->nbeam,
+                     4.0 * kPi / (double)w.npix, omega);
+  // (the solid angles stay on the device: the per-column factor 1 / sqrt(Omega_i Omega_j) is filled in by a small
+  // kernel, so the host never waits inside the call)
+  const int ncol16 = (ncol + 15) / 16;
+  std::vector<fdft_col> fc((size_t)ncol16 * 16, fdft_col{0.0, 0.0, 0.0, -1, -1});
+  for (int c = 0; c < ncol; ++c) {
+    const int bi = syn->bi_host[c], bj = syn->bj_host[c];
+    DM_ARG(ctx, bi >= 0 && bi < syn->nbeam && bj >= 0 && bj < syn->nbeam);
+    fc[c] = fdft_col{syn->uv_host[2 * c], syn->uv_host[2 * c + 1], 0.0, bi, bj};
+  }
+  fdft_col* d_fc = dm_ws_upload(ctx, fc);
+  if (d_fc) DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_fdft_pre_kernel, dim3((ncol + 255) / 256), dim3(256), 0, ctx->stream, d_fc, ncol, omega);
+  double* d_rw = nullptr;
+  if (a.ring_w_host) {
+    std::vector<double> rw(a.ring_w_host, a.ring_w_host + nring);
+    d_rw = dm_ws_upload(ctx, rw);
+    if (!d_rw) return DM_ENOMEM;
+  }
+  if (!d_fc) return DM_ENOMEM;
+  const int nmg = (w.nm + 3) / 4;  // groups of four m-values
+  // The belt (rings nside - 1 .. 3 nside - 1, all with N = 4 nside pixels) goes by FFT when N is a power of two and the
+  // P maps of a column fit the LDS; the matrix-form kernels below then see the rings of the two caps only.  The choice
+  // depends on nside, P and on whether the call is narrow (below) — not on WHICH m it asks for.
+  static const bool fft_off = getenv("DM_BT_FFT") && atoi(getenv("DM_BT_FFT")) == 0;
+  const int N = 4 * nside;
+  int fft_logn = 0;
+  while ((1 << fft_logn) < N) ++fft_logn;
+  const int fft_sh = std::max(5, fft_logn - 6);   // padding of the LDS arrays, as in the kernel
+  const size_t fft_lds = sizeof(cplx) * ((size_t)P * (N + (N >> fft_sh) + 1) + (N / 2 + ((N / 2) >> fft_sh) + 1));
+  // A NARROW call (at most DM_BT_NARROW = 8 m-values: one pass of the shared-synthesis kernel) keeps the matrix form on
+  // the belt too: the FFT computes every m of a ring whether wanted or not — 14 CU-cycles per (pixel, column) at nside
+  // 512 with four maps (150 KB of LDS: one workgroup per CU) against ~1 per group of four m-rows on the matrix pipe.
+  // One m-block of configs[4] (59.6 GB: a rank holds one or two at a time) 24.8 -> 4.6 s of ring transform
+  // (scratch/btgen_narrow_probe.py: 784 -> 146 ms on 8 of the 256 frequencies; 4 m-values 833 -> 229, 8: 1039 -> 555).
+  // The two forms round differently (2e-13 of the largest coefficient): blocks are the same BITS for any partition
+  // of m whose calls are all wide, and equal to rounding when narrow calls are involved.
+  static const int narrow_max = getenv("DM_BT_NARROW") ? atoi(getenv("DM_BT_NARROW")) : 8;
+  const bool narrow = w.cnt <= narrow_max;
+  const bool use_fft = !fft_off && !narrow && nside >= 2 && (N & (N - 1)) == 0 && N <= 4096 && fft_lds <= 160u * 1024u - 256u;
+  int nring_dft = nring;
+  const int* d_caps = nullptr;
+  if (use_fft) {
+    std::vector<int> caps;
+    for (int r = 0; r < nring; ++r)
+      if (r < nside - 1 || r > 3 * nside - 1) caps.push_back(r);
+    nring_dft = (int)caps.size();
+    if (nring_dft > 0) {
+      d_caps = dm_ws_upload(ctx, caps);
+      if (!d_caps) return DM_ENOMEM;
+    }
+    const int nring_eq = 2 * nside + 1;
+    const int cpw = std::max(4, std::min(32, (int)(((size_t)ncol * nring_eq) / 4096)));
+    const dim3 grid((unsigned)((ncol + cpw - 1) / cpw), (unsigned)nring_eq);
+    bt_fft_fn kern = nullptr;
+    for (const bt_fft_row& k : bt_fft_rows)
+      if (k.P == P && k.npt == std::max(1, N / 256)) kern = k.fn[cbm];
+    DM_ARG(ctx, kern != nullptr);
+    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds));
+    DM_PLAUNCH(ctx, DM_PROF_BT_RING, kern, grid, dim3(256), fft_lds, ctx->stream, w.gh.g, fr, syn->beams_dev, bstride, d_fc, ncol, a.m_lo,
+                       w.cnt, d_rw, w.G, w.ncp, nside - 1, cpw);
+  }
+  // (m, ring) pairs below rounding: exact zeros, no work (bt_ring_skip_lookup; DM_BT_RING_SKIP=0 computes them all)
+  const bool ring_skip_off = getenv("DM_BT_RING_SKIP") && atoi(getenv("DM_BT_RING_SKIP")) == 0;   // (read per call: the tests flip it)
+  const int* d_mskip = nullptr;
+  if (!ring_skip_off && nring_dft > 0) {
+    d_mskip = dm_ws_upload(ctx, bt_ring_skip_lookup(nside, a.lmax_grp, a.polarised != 0, a.ring_cth_host, a.ring_sth_host));
+    if (!d_mskip) return DM_ENOMEM;
+  }
+  if (nring_dft > 0) {
+    const bt_dft_row* k = bt_dft_rows;
+    while (k->P != P || nmg < k->nmg_from) ++k;   // (the last row of each P takes any nmg)
+    const dim3 grid((unsigned)((ncol16 + k->cgw - 1) / k->cgw), (unsigned)nring_dft, (unsigned)((nmg + k->mgw - 1) / k->mgw));
+    DM_PLAUNCH(ctx, DM_PROF_BT_RING, k->fn[cbm], grid, dim3(256), 0, ctx->stream, w.gh.g, fr, syn->beams_dev, bstride, d_fc, ncol16, a.m_lo,
+                       w.cnt, d_rw, w.G, w.ncp, d_caps, d_mskip);
+  }
   DM_HIP(ctx, hipGetLastError());
+  return DM_OK;
+}
 
-  // ---- clear the destination rows of this group for every m (then GEMMs fill l in [m, lmax_grp])
-  cplx* bm = reinterpret_cast<cplx*>(beam_m_dev);
-  std::vector<int> cf(col_f_host, col_f_host + ncol), cb(col_b_host, col_b_host + ncol),
-      cl(col_lmax_host, col_lmax_host + ncol);
-  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, cf[c] >= 0 && cf[c] < F && cb[c] >= 0 && cb[c] < B && cl[c] <= lmax_grp);
-  int* d_cf = dm_ws_upload(ctx, cf);
-  int* d_cb = dm_ws_upload(ctx, cb);
-  int* d_cl = dm_ws_upload(ctx, cl);
+// ---- stage: Legendre tables up to lmax_grp
+static int bt_legendre_tables(dm_ctx* ctx, const bt_sht_args& a, bt_sht_ws& w) {
+  w.loff.assign(std::max(w.cnt, 1), 0);  // loff[m - m_lo]
+  for (int m = a.m_lo; m <= w.mtop; ++m) { w.loff[m - a.m_lo] = w.ltot; w.ltot += (size_t)(a.lmax_grp + 1 - m) * w.nring; }
+  size_t* d_loff = dm_ws_upload(ctx, w.loff);
+  if (!bt_tables_alloc(ctx, a.polarised != 0, std::max<size_t>(w.ltot, 1), w.tab) || !d_loff) return DM_ENOMEM;
+  if (w.cnt > 0)
+    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_legendre_kernel, dim3((w.nring + 63) / 64, w.cnt), dim3(64), 0, ctx->stream, w.gh.g, a.lmax_grp, a.m_lo,
+                       w.mtop, 4.0 * kPi / (double)w.npix, d_loff, w.tab.T, w.tab.W, w.tab.X);
+  DM_HIP(ctx, hipGetLastError());
+  return DM_OK;
+}
+
+// ---- stage: the columns of the group — checked, uploaded, merged into runs; their destination rows cleared for every m
+// (the GEMMs then fill l in [m, lmax_grp])
+static int bt_columns_prepare(dm_ctx* ctx, const bt_sht_args& a, bt_sht_ws& w) {
+  const int ncol = a.ncol;
+  std::vector<int> cf(a.col_f_host, a.col_f_host + ncol), cb(a.col_b_host, a.col_b_host + ncol),
+      cl(a.col_lmax_host, a.col_lmax_host + ncol);
+  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, cf[c] >= 0 && cf[c] < a.F && cb[c] >= 0 && cb[c] < a.B && cl[c] <= a.lmax_grp);
+  w.d_cf = dm_ws_upload(ctx, cf);
+  w.d_cb = dm_ws_upload(ctx, cb);
+  w.d_cl = dm_ws_upload(ctx, cl);
   std::vector<int> neg1(ncol, -1);
-  int* d_neg = dm_ws_upload(ctx, neg1);
-  if (!d_cf || !d_cb || !d_cl || !d_neg) return DM_ENOMEM;
-  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_mask_kernel, dim3((2 * P * L + 255) / 256, ncol, nmblk), dim3(256), 0, ctx->stream, bm, F, B,
-                     P, L, m_hi, ncol, d_cf, d_cb, d_neg);
-
-  // ---- Legendre products.  Columns of a group are arbitrary (f, b) pairs, so one GEMM row per
-  // column would be wasteful; instead consecutive columns with the same f and consecutive b are
-  // merged into runs (the usual case: all baselines of a frequency in order).
-  struct run { int c0, n, f, b0; };
-  std::vector<run> runs;
+  w.d_neg = dm_ws_upload(ctx, neg1);
+  if (!w.d_cf || !w.d_cb || !w.d_cl || !w.d_neg) return DM_ENOMEM;
+  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_mask_kernel, dim3((2 * w.P * w.L + 255) / 256, ncol, w.nmblk), dim3(256), 0, ctx->stream, w.bm, a.F, a.B,
+                     w.P, w.L, a.m_hi, ncol, w.d_cf, w.d_cb, w.d_neg);
+  // Columns of a group are arbitrary (f, b) pairs, so one GEMM row per column would be wasteful; instead consecutive
+  // columns with the same f and consecutive b are merged into runs (the usual case: all baselines of a frequency in order).
   for (int c = 0; c < ncol;) {
     int e = c + 1;
     while (e < ncol && cf[e] == cf[c] && cb[e] == cb[e - 1] + 1) ++e;
-    runs.push_back(run{c, e - c, cf[c], cb[c]});
+    w.runs.push_back(bt_run{c, e - c, cf[c], cb[c]});
     c = e;
   }
-  // Terms whose outputs accumulate (E and B each take two products) go in separate launches
-  // so that no two tiles of one launch touch the same C entries.
-  // (the refinement path synthesises from G-shaped buffers and keeps the plain sum; DM_BT_FOLD=0 switches the fold off)
+  return DM_OK;
+}
+
+// ---- stage: north / south fold of G (bt_fold_kernel).  The map-space refinement synthesises from G-shaped buffers and
+// keeps the plain sum; DM_BT_FOLD=0 switches the fold off
+static void bt_fold_rings(dm_ctx* ctx, const bt_sht_args& a, bt_sht_ws& w) {
   static const bool fold_off = getenv("DM_BT_FOLD") && atoi(getenv("DM_BT_FOLD")) == 0;
-  const bool folded = (niter == 0 || harmonic) && !fold_off && cnt > 0 && nring >= 3;
-  if (folded) {
-    const size_t tot = (size_t)nm * (nring / 2) * ncp;
-    const unsigned nb = (unsigned)std::min<size_t>((tot + 255) / 256, 65536);
-    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_fold_kernel, dim3(nb), dim3(256), 0, ctx->stream, G, nm, nring, (size_t)ncp);
-  }
-  auto legendre_analysis = [&](bool accumulate) -> int {
-  for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
+  w.folded = a.mode != BT_REFINE_MAPS && !fold_off && w.cnt > 0 && w.nring >= 3;
+  if (!w.folded) return;
+  const size_t tot = (size_t)w.nm * (w.nring / 2) * w.ncp;
+  const unsigned nb = (unsigned)std::min<size_t>((tot + 255) / 256, 65536);
+  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_fold_kernel, dim3(nb), dim3(256), 0, ctx->stream, w.G, w.nm, w.nring, (size_t)w.ncp);
+}
+
+// ---- stage: Legendre products bm (+)= tables . G, then the per-column band limit
+static int bt_legendre_analysis(dm_ctx* ctx, const bt_sht_args& a, const bt_sht_ws& w, bool accumulate) {
+  const int P = w.P, L = w.L, nring = w.nring, ncp = w.ncp, ncol = a.ncol, m_lo = a.m_lo;
+  const bool fused = w.fused;
+  for (int pass = 0; pass < (a.polarised ? 2 : 1); ++pass) {
     std::vector<dm_gemm_desc> g;
-    for (int m = m_lo; m <= mtop; ++m) {
-      const int Lm = lmax_grp + 1 - m;
+    for (int m = m_lo; m <= w.mtop; ++m) {
+      const int Lm = a.lmax_grp + 1 - m;
       for (int s = 0; s < 2; ++s) {
         if (m == 0 && s == 1) continue;  // the -m slot of m = 0 stays zero (beamtransfer.py:624)
-        const int mm = (s == 0) ? (m - m_lo) : (cnt + m - m_lo);
-        const cplx* Gm = G + (size_t)mm * nring * ncp;
-        for (const run& rn : runs) {
-          cplx* out = bm + ((((size_t)(m - m_lo) * F + rn.f) * 2 + s) * B + rn.b0) * P * L + m;
-          auto add = [&](int pa, const double* tab, int pout, double are, double aim, double beta) {
-            if (!folded) {
-              dm_gemm_desc d = dm_gemm_make(Gm + (fused ? (size_t)pa * ncol + rn.c0 : (size_t)rn.c0 * P + pa), fused ? 1 : P, ncp, s == 1,
-                                            tab + loff[m - m_lo], 1, nring, false,
-                                            out + (size_t)pout * L, P * L, rn.n, Lm, nring, are, beta, nullptr,
-                                            DM_GEMM_B_REAL);
-              d.alpha_im = aim;
-              g.push_back(d);
-              return;
-            }
+        const int mm = (s == 0) ? (m - m_lo) : (w.cnt + m - m_lo);
+        const cplx* Gm = w.G + (size_t)mm * nring * ncp;
+        for (const bt_run& rn : w.runs) {
+          cplx* out = w.bm + ((((size_t)(m - m_lo) * a.F + rn.f) * 2 + s) * a.B + rn.b0) * P * L + m;
+          bt_stokes_terms(a.polarised != 0, pass, w.tab, accumulate ? 1.0 : 0.0,
+                          [&](int pa, const double* tab, int pout, double are, double aim, double beta) {
             // folded rings: the outputs l = m + 2 j (+ 1) are interleaved (column stride 2 of C), each parity sums over one
             // half of the rings — the northern one (with the equator) where the function is even in z, the southern one
-            // where it is odd; lambda and W are even for even l - m, X for odd l - m
-            const int mid = nring / 2;
-            for (int par = 0; par < 2; ++par) {
-              const int nl = (Lm - par + 1) / 2;       // l' = par, par + 2, ... < Lm
-              if (nl <= 0) continue;
-              const bool even_fn = (tab == Xt) ? par == 1 : par == 0;
-              const int r0 = even_fn ? 0 : mid + 1, nr = even_fn ? mid + 1 : mid;
-              if (nr <= 0) continue;
+            // where it is odd; lambda and W are even for even l - m, X for odd l - m.  Unfolded: one product over all rings
+            const int npar = w.folded ? 2 : 1, mid = nring / 2;
+            for (int par = 0; par < npar; ++par) {
+              int nl = Lm, r0 = 0, nr = nring;
+              if (w.folded) {
+                nl = (Lm - par + 1) / 2;       // l' = par, par + 2, ... < Lm
+                const bool even_fn = (tab == w.tab.X) ? par == 1 : par == 0;
+                r0 = even_fn ? 0 : mid + 1;
+                nr = even_fn ? mid + 1 : mid;
+              }
+              if (nl <= 0 || nr <= 0) continue;
               dm_gemm_desc d = dm_gemm_make(Gm + (size_t)r0 * ncp + (fused ? (size_t)pa * ncol + rn.c0 : (size_t)rn.c0 * P + pa),
                                             fused ? 1 : P, ncp, s == 1,
-                                            tab + loff[m - m_lo] + (size_t)par * nring + r0, 1, 2 * nring, false,
+                                            tab + w.loff[m - m_lo] + (size_t)par * nring + r0, 1, npar * nring, false,
                                             out + (size_t)pout * L + par, P * L, rn.n, nl, nr, are, beta, nullptr,
                                             DM_GEMM_B_REAL);
-              d.csc = 2;
+              d.csc = npar;
               d.alpha_im = aim;
               g.push_back(d);
             }
-          };
-          const double b0 = accumulate ? 1.0 : 0.0;
-          if (!polarised) {
-            add(0, lam, 0, 1.0, 0.0, b0);
-          } else if (pass == 0) {
-            add(0, lam, 0, 1.0, 0.0, b0);  // T = lam . G^I
-            add(3, lam, 3, 1.0, 0.0, b0);  // V = lam . G^V
-            add(1, Wt, 1, 1.0, 0.0, b0);   // E  = W . G^Q ...
-            add(2, Wt, 2, 1.0, 0.0, b0);   // B  = W . G^U ...
-          } else {
-            add(2, Xt, 1, 0.0, -1.0, 1.0);  // E -= i X . G^U
-            add(1, Xt, 2, 0.0, 1.0, 1.0);   // B += i X . G^Q
-          }
+          });
         }
       }
     }
     DM_TRY(dm_gemm_grouped_launch(ctx, g));
   }
   // ---- per-column band limit
-  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_mask_kernel, dim3((2 * P * L + 255) / 256, ncol, nmblk), dim3(256), 0, ctx->stream, bm, F, B,
-                     P, L, m_hi, ncol, d_cf, d_cb, d_cl);
+  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_mask_kernel, dim3((2 * P * L + 255) / 256, ncol, w.nmblk), dim3(256), 0, ctx->stream, w.bm, a.F, a.B,
+                     P, L, a.m_hi, ncol, w.d_cf, w.d_cb, w.d_cl);
   DM_HIP(ctx, hipGetLastError());
-  return DM_OK;
-  };
-  {
-    static const bool host_times = getenv("DM_TIME_HOST") != nullptr;  // debugging aid
-    const auto t0 = std::chrono::steady_clock::now();
-    DM_TRY(legendre_analysis(false));
-    if (host_times)
-      fprintf(stderr, "HOSTTIME bt_sht_impl: Legendre descriptors + launch %.3f ms (ncol %d, m %d..%d)\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), ncol, m_lo, m_hi);
-  }
-
-  // ---- Jacobi refinement (healpy map2alm `iter`): coefficients += analysis(map - synthesis(coefficients)).
-  // With c_lm = sum_pix w f Y_lm (the reference's conj(SHT(conj f))) the synthesis is f = sum_lm c_lm conj(Y_lm):
-  //   H[+m][col][ring] = sum_l lambda_lm(ring) b0_lm,   H[-m] = sum_l lambda_lm conj(b1_lm)   (the fold undone)
-  //   f[col][ring, j]  = sum_mm conj(tw[mm][j]) H[mm][col][ring]
-  // and for the spin-2 pair the Hermitian 2x2 block [[W, -iX], [iX, W]] of the analysis applied once more.
-  // The tables carry the quadrature weight w = 4 pi / npix: the synthesis divides it out again.
-  if (niter > 0 && harmonic && cnt > 0) {
-    for (int c = 0; c < ncol; ++c) DM_ARG(ctx, cf[c] == 0 && cb[c] == c);
-    const int Lg = lmax_grp + 1;
-    const double wq = 4.0 * kPi / (double)npix, iw = 1.0 / wq;
-    const bt_alias_info& al = bt_alias_lookup(nside, lmax_grp, polarised != 0, ring_cth_host, ring_sth_host);
-    // alias terms couple the m <= mcut among themselves: a call that touches them must hold all of them (bt_sht_refined)
-    const int Mc = (al.ia > 0 && m_lo == 0) ? std::min(al.mcut, mtop) : -1;
-    DM_ARG(ctx, al.ia == 0 || m_lo == 0 || m_lo > al.mcut);
-    DM_ARG(ctx, Mc < 0 || mtop >= std::min(al.mcut, lmax_grp));
-    const int nra = Mc >= 0 ? 2 * al.ia : 0;
-    DM_ARG(ctx, row_pad == nra);
-    static const bool kfast = !(getenv("DM_SHT_KNFAST") && atoi(getenv("DM_SHT_KNFAST")) == 1);
-    // ---- per-ring factor of A o S and the Gram matrices K_m, extended by the alias-ring tables for m <= Mc:
-    //      block m is a (Lm + xa) x Lm operand, xa = nra alias rows
-    std::vector<double> sc(nring);
-    for (int r = 0; r < nring; ++r) sc[r] = (ring_w_host ? ring_w_host[r] : 1.0) * (double)gh.nphi[r] * iw;
-    double* d_sc = dm_ws_upload(ctx, sc);
-    std::vector<size_t> koff(cnt);
-    size_t ktot = 0;
-    auto xa = [&](int m) { return m <= Mc ? nra : 0; };
-    for (int m = m_lo; m <= mtop; ++m) { koff[m - m_lo] = ktot; const size_t Lm = lmax_grp + 1 - m; ktot += Lm * (Lm + xa(m)); }
-    double* Kl = dm_ws_alloc_t<double>(ctx, ktot);
-    double* Kp = polarised ? dm_ws_alloc_t<double>(ctx, ktot) : nullptr;
-    double* Kx = polarised ? dm_ws_alloc_t<double>(ctx, ktot) : nullptr;
-    if (!d_sc || !Kl || (polarised && (!Kp || !Kx))) return DM_ENOMEM;
-    {
-      dm_ws_scope tmp_scope(ctx);   // scaled tables: released (stream-ordered) once the K products are queued
-      double* lamS = dm_ws_alloc_t<double>(ctx, ltot);
-      double* WS = polarised ? dm_ws_alloc_t<double>(ctx, ltot) : nullptr;
-      double* XS = polarised ? dm_ws_alloc_t<double>(ctx, ltot) : nullptr;
-      if (!lamS || (polarised && (!WS || !XS))) return DM_ENOMEM;
-      const unsigned nb = (unsigned)std::min<size_t>((ltot + 255) / 256, 65536);
-      DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_scale_table_kernel, dim3(nb), dim3(256), 0, ctx->stream, lam, lamS, ltot, nring, d_sc);
-      if (polarised) {
-        DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_scale_table_kernel, dim3(nb), dim3(256), 0, ctx->stream, Wt, WS, ltot, nring, d_sc);
-        DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_scale_table_kernel, dim3(nb), dim3(256), 0, ctx->stream, Xt, XS, ltot, nring, d_sc);
-      }
-      for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
-        std::vector<dm_gemm_desc> g;
-        for (int m = m_lo; m <= mtop; ++m) {
-          const int Lm = lmax_grp + 1 - m;
-          const size_t lo = loff[m - m_lo], ko = koff[m - m_lo];
-          // K is symmetric: row i of the product lands where the chosen layout keeps (k = i, n) resp. (k, n = i)
-          const int ldk = kfast ? Lm + xa(m) : Lm;
-          auto kadd = [&](const double* a, const double* b, double* c, double beta) {
-            g.push_back(dm_gemm_make(reinterpret_cast<const cplx*>(a + lo), nring, 1, false, b + lo, 1, nring, false,
-                                     reinterpret_cast<cplx*>(c + ko), ldk, Lm, Lm, nring, 1.0, beta, nullptr, DM_GEMM_ALL_REAL));
-          };
-          if (pass == 0) {
-            kadd(lam, lamS, Kl, 0.0);
-            if (polarised) { kadd(Wt, WS, Kp, 0.0); kadd(Wt, XS, Kx, 0.0); }
-          } else {
-            kadd(Xt, XS, Kp, 1.0);
-            kadd(Xt, WS, Kx, 1.0);
-          }
-        }
-        DM_TRY(dm_gemm_grouped_launch(ctx, g));
-      }
-    }
-    // ---- alias rings: their own small tables (same recurrences, same bits as the full tables)
-    const int nmmA = 2 * (Mc + 1);
-    double *lamA = nullptr, *WA = nullptr, *XA = nullptr, *d_scA = nullptr;
-    int *d_nphiA = nullptr, *d_mlimA = nullptr;
-    cplx* Ha = nullptr;
-    std::vector<size_t> loffA(std::max(Mc + 1, 1), 0);
-    if (Mc >= 0) {
-      std::vector<double> geoA(2 * (size_t)nra), scA(nra);
-      std::vector<int> nphiA(nra), mlimA(nra);
-      for (int ja = 0; ja < nra; ++ja) {
-        const int r = ja < al.ia ? ja : nring - nra + ja;
-        geoA[ja] = gh.cth[r];
-        geoA[nra + ja] = gh.sth[r];
-        nphiA[ja] = gh.nphi[r];
-        mlimA[ja] = al.mlim[ja < al.ia ? ja : nra - 1 - ja];
-        scA[ja] = (ring_w_host ? ring_w_host[r] : 1.0) * (double)gh.nphi[r];
-      }
-      double* d_geoA = dm_ws_upload(ctx, geoA);
-      d_scA = dm_ws_upload(ctx, scA);
-      d_nphiA = dm_ws_upload(ctx, nphiA);
-      d_mlimA = dm_ws_upload(ctx, mlimA);
-      size_t ltotA = 0;
-      for (int m = 0; m <= Mc; ++m) { loffA[m] = ltotA; ltotA += (size_t)(lmax_grp + 1 - m) * nra; }
-      size_t* d_loffA = dm_ws_upload(ctx, loffA);
-      size_t* d_koff = dm_ws_upload(ctx, koff);
-      lamA = dm_ws_alloc_t<double>(ctx, ltotA);
-      if (polarised) { WA = dm_ws_alloc_t<double>(ctx, ltotA); XA = dm_ws_alloc_t<double>(ctx, ltotA); }
-      Ha = dm_ws_alloc_t<cplx>(ctx, (size_t)nmmA * nra * ncp);
-      if (!d_geoA || !d_scA || !d_nphiA || !d_mlimA || !d_loffA || !d_koff || !lamA || (polarised && (!WA || !XA)) || !Ha)
-        return DM_ENOMEM;
-      ring_geo ga = gh.g;
-      ga.cth = d_geoA;
-      ga.sth = d_geoA + nra;
-      ga.nring = nra;
-      DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_legendre_kernel, dim3((nra + 63) / 64, Mc + 1), dim3(64), 0, ctx->stream, ga, lmax_grp, 0, Mc, wq,
-                         d_loffA, lamA, WA, XA);
-      const dim3 fg(64, Mc + 1);
-      DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_kext_fill_kernel, fg, dim3(256), 0, ctx->stream, lamA, d_loffA, Kl, d_koff, lmax_grp, nra, kfast ? 1 : 0);
-      if (polarised) {
-        DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_kext_fill_kernel, fg, dim3(256), 0, ctx->stream, WA, d_loffA, Kp, d_koff, lmax_grp, nra, kfast ? 1 : 0);
-        DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_kext_fill_kernel, fg, dim3(256), 0, ctx->stream, XA, d_loffA, Kx, d_koff, lmax_grp, nra, kfast ? 1 : 0);
-      }
-    }
-    // ---- iteration on the increments:  d_0 = a_0,  d_{k+1} = d_k - mask((A o S) d_k),  a_n = sum_k d_k
-    const size_t nacc = (size_t)nmblk * 2 * ncol * P * L;
-    cplx* dbuf = dm_ws_alloc_t<cplx>(ctx, nacc);
-    cplx* tbuf = dm_ws_alloc_t<cplx>(ctx, nacc);
-    if (!dbuf || !tbuf) return DM_ENOMEM;
-    DM_HIP(ctx, hipMemcpyAsync(dbuf, bm, sizeof(cplx) * nacc, hipMemcpyDeviceToDevice, ctx->stream));
-    auto blk = [&](cplx* base, int m, int s2) { return base + ((size_t)(m - m_lo) * 2 + s2) * ncol * P * L + m; };
-    for (int it = 0; it < niter; ++it) {
-      if (Mc >= 0) {
-        // synthesis on the alias rings: Ha[mm][col p][ja] = (1 / w) sum_l tabA[l][ja] d[col][p][l]
-        for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
-          std::vector<dm_gemm_desc> g;
-          for (int m = 0; m <= Mc; ++m) {
-            const int Lm = lmax_grp + 1 - m;
-            for (int s2 = 0; s2 < 2; ++s2) {
-              cplx* Hm = Ha + (size_t)(s2 * (Mc + 1) + m) * nra * ncp;
-              if (m == 0 && s2 == 1) continue;   // never read by the fold
-              const cplx* in = blk(dbuf, m, s2);
-              auto add = [&](int pin, const double* tab, int pout, double are, double aim, double beta) {
-                dm_gemm_desc dsc = dm_gemm_make(in + (size_t)pin * L, P * L, 1, false, tab + loffA[m], nra, 1, false,
-                                                Hm + (size_t)pout * nra, P * nra, ncol, nra, Lm, are * iw, beta, nullptr,
-                                                DM_GEMM_B_REAL);
-                dsc.alpha_im = aim * iw;
-                g.push_back(dsc);
-              };
-              if (!polarised) {
-                add(0, lamA, 0, 1.0, 0.0, 0.0);
-              } else if (pass == 0) {
-                add(0, lamA, 0, 1.0, 0.0, 0.0);
-                add(3, lamA, 3, 1.0, 0.0, 0.0);
-                add(1, WA, 1, 1.0, 0.0, 0.0);   // Q = W E - i X B
-                add(2, WA, 2, 1.0, 0.0, 0.0);   // U = W B + i X E
-              } else {
-                add(2, XA, 1, 0.0, -1.0, 1.0);
-                add(1, XA, 2, 0.0, 1.0, 1.0);
-              }
-            }
-          }
-          DM_TRY(dm_gemm_grouped_launch(ctx, g));
-        }
-        DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_alias_fold_kernel, dim3((unsigned)((ncp + 3) / 4), (nra + 63) / 64, nmmA), dim3(64, 4), 0, ctx->stream,
-                           Ha, dbuf, Mc, nra, (size_t)ncp, L, Lg, d_nphiA, d_mlimA, d_scA);
-      }
-      // t = [d | folded rings] [K ; alias tables]: the Gram product and the analysis of the folded rings in one K dimension
-      for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
-        std::vector<dm_gemm_desc> g;
-        for (int m = m_lo; m <= mtop; ++m) {
-          const int Lm = lmax_grp + 1 - m, Kd = Lm + xa(m);
-          const size_t ko = koff[m - m_lo];
-          for (int s2 = 0; s2 < 2; ++s2) {
-            if (m == 0 && s2 == 1) continue;
-            const cplx* in = blk(dbuf, m, s2);
-            cplx* out = blk(tbuf, m, s2);
-            auto add = [&](int pin, const double* Km, int pout, double are, double aim, double beta) {
-              dm_gemm_desc dsc = dm_gemm_make(in + (size_t)pin * L, P * L, 1, false, Km + ko, kfast ? 1 : Lm, kfast ? Kd : 1, false,
-                                              out + (size_t)pout * L, P * L, ncol, Lm, Kd, are, beta, nullptr, DM_GEMM_B_REAL);
-              dsc.alpha_im = aim;
-              g.push_back(dsc);
-            };
-            if (!polarised) {
-              add(0, Kl, 0, 1.0, 0.0, 0.0);
-            } else if (pass == 0) {
-              add(0, Kl, 0, 1.0, 0.0, 0.0);
-              add(3, Kl, 3, 1.0, 0.0, 0.0);
-              add(1, Kp, 1, 1.0, 0.0, 0.0);   // E' = K_P E - i K_X B  (+ W g_Q - i X g_U from the alias slots)
-              add(2, Kp, 2, 1.0, 0.0, 0.0);   // B' = K_P B + i K_X E  (+ W g_U + i X g_Q)
-            } else {
-              add(2, Kx, 1, 0.0, -1.0, 1.0);
-              add(1, Kx, 2, 0.0, 1.0, 1.0);
-            }
-          }
-        }
-        DM_TRY(dm_gemm_grouped_launch(ctx, g));
-      }
-      DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_refine_update_kernel, dim3((P * L + 255) / 256, ncol, 2 * cnt), dim3(256), 0, ctx->stream, bm, dbuf,
-                         tbuf, m_lo, ncol, P, L, Lg, d_cl);
-      DM_HIP(ctx, hipGetLastError());
-    }
-  } else if (niter > 0 && cnt > 0) {
-    const double iw = (double)npix / (4.0 * kPi);
-    cplx* res = dm_ws_alloc_t<cplx>(ctx, (size_t)ncp * npix);
-    if (!res) return DM_ENOMEM;
-    cplx* H = G;  // same size: (nm, ncp, nring) here against (nm, nring, ncp) there
-    for (int it = 0; it < niter; ++it) {
-      DM_HIP(ctx, hipMemcpyAsync(res, maps_dev, sizeof(cplx) * (size_t)ncp * npix, hipMemcpyDeviceToDevice, ctx->stream));
-      for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
-        std::vector<dm_gemm_desc> g;
-        for (int m = m_lo; m <= mtop; ++m) {
-          const int Lm = lmax_grp + 1 - m;
-          for (int s = 0; s < 2; ++s) {
-            const int mm = (s == 0) ? (m - m_lo) : (cnt + m - m_lo);
-            cplx* Hm = H + (size_t)mm * ncp * nring;
-            for (const run& rn : runs) {
-              const cplx* in = bm + ((((size_t)(m - m_lo) * F + rn.f) * 2 + s) * B + rn.b0) * P * L + m;
-              // C[col][ring] (row stride P * nring: the P maps of a column are adjacent rows) = A[col][l] * tab[l][ring]
-              auto add = [&](int pin, const double* tab, int pout, double are, double aim, double beta) {
-                dm_gemm_desc d = dm_gemm_make(in + (size_t)pin * L, P * L, 1, s == 1, tab + loff[m - m_lo], nring, 1, false,
-                                              Hm + ((size_t)rn.c0 * P + pout) * nring, P * nring, rn.n, nring, Lm,
-                                              are * iw, beta, nullptr, DM_GEMM_B_REAL);
-                d.alpha_im = (s == 1 ? -aim : aim) * iw;  // H[-m] = conj(M b1) = conj(M) conj(b1)
-                g.push_back(d);
-              };
-              if (!polarised) {
-                add(0, lam, 0, 1.0, 0.0, 0.0);
-              } else if (pass == 0) {
-                add(0, lam, 0, 1.0, 0.0, 0.0);
-                add(3, lam, 3, 1.0, 0.0, 0.0);
-                add(1, Wt, 1, 1.0, 0.0, 0.0);   // Q  = W . E ...
-                add(2, Wt, 2, 1.0, 0.0, 0.0);   // U  = W . B ...
-              } else {
-                add(2, Xt, 1, 0.0, -1.0, 1.0);  // Q -= i X . B
-                add(1, Xt, 2, 0.0, 1.0, 1.0);   // U += i X . E
-              }
-            }
-          }
-        }
-        DM_TRY(dm_gemm_grouped_launch(ctx, g));
-      }
-      {
-        std::vector<dm_gemm_desc> g;
-        g.reserve(nring);
-        for (int r = 0; r < nring; ++r)  // res[colp][start_r + j] -= sum_mm H[mm][colp][r] conj(tw_r[mm][j])
-          g.push_back(dm_gemm_make(H + r, nring, ncp * nring, false, tw + toff[r], gh.nphi[r], 1, true, res + gh.start[r],
-                                   npix, ncp, gh.nphi[r], nm, -1.0, 1.0));
-        DM_TRY(dm_gemm_grouped_launch(ctx, g));
-      }
-      DM_TRY(ring_dft(res));
-      DM_TRY(legendre_analysis(true));
-    }
-  }
-  // The fused path returns once everything is queued (stream-ordered with the caller's later work on the context's stream,
-  // workspace re-use included: dm_ws_release); the refinement path keeps its wait.
-  if ((niter > 0 && !harmonic) || !fused) DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  dm_ws_release(ctx, mark);
   return DM_OK;
 }
 
-// healpy's `iter` without the maps: the first analysis and the harmonic-space refinement run on a private coefficient
-// buffer that holds the blocks the refinement of [m_lo, m_hi] depends on — the range itself, plus every m <= mcut when the
-// range reaches into the m the polar rings alias (those couple among themselves only) — and the requested blocks are
-// copied out.  The private buffer is (nm, 2, ncol, P, lmax_grp + 1): compact in l, columns adjacent.
-static int bt_sht_refined(dm_ctx* ctx, int nside, const double* ring_cth_host, const double* ring_sth_host, int polarised,
-                          int lside, int m_lo, int m_hi, int lmax_grp, int F, int B, int ncol, const int* col_f_host,
-                          const int* col_b_host, const int* col_lmax_host, const void* maps_dev, void* beam_m_dev, int niter,
-                          const double* ring_w_host, const bt_synth_in* syn) {
+// ---- stage: Jacobi refinement in harmonic space (see bt_alias_info above): the Gram matrices K_m, the alias-ring
+// tables that extend them, then niter times  d <- d - mask((A o S) d),  bm += d
+static int bt_refine_harmonic(dm_ctx* ctx, const bt_sht_args& a, const bt_sht_ws& w) {
+  const int P = w.P, L = w.L, nring = w.nring, ncp = w.ncp, cnt = w.cnt, mtop = w.mtop;
+  const int ncol = a.ncol, m_lo = a.m_lo, lmax_grp = a.lmax_grp;
+  const bool polarised = a.polarised != 0;
+  const double* ring_w_host = a.ring_w_host;
+  const geo_host& gh = w.gh;
+  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, a.col_f_host[c] == 0 && a.col_b_host[c] == c);
+  const int Lg = lmax_grp + 1;
+  const double wq = 4.0 * kPi / (double)w.npix, iw = 1.0 / wq;
+  const bt_alias_info& al = bt_alias_lookup(a.nside, lmax_grp, polarised, a.ring_cth_host, a.ring_sth_host);
+  // alias terms couple the m <= mcut among themselves: a call that touches them must hold all of them (bt_sht_private)
+  const int Mc = (al.ia > 0 && m_lo == 0) ? std::min(al.mcut, mtop) : -1;
+  DM_ARG(ctx, al.ia == 0 || m_lo == 0 || m_lo > al.mcut);
+  DM_ARG(ctx, Mc < 0 || mtop >= std::min(al.mcut, lmax_grp));
+  const int nra = Mc >= 0 ? 2 * al.ia : 0;
+  DM_ARG(ctx, a.row_pad == nra);
+  // ---- per-ring factor of A o S and the Gram matrices K_m, extended by the alias-ring tables for m <= Mc:
+  //      block m is a (Lm + xa) x Lm operand, xa = nra alias rows
+  std::vector<double> sc(nring);
+  for (int r = 0; r < nring; ++r) sc[r] = (ring_w_host ? ring_w_host[r] : 1.0) * (double)gh.nphi[r] * iw;
+  double* d_sc = dm_ws_upload(ctx, sc);
+  std::vector<size_t> koff(cnt);
+  size_t ktot = 0;
+  auto xa = [&](int m) { return m <= Mc ? nra : 0; };
+  for (int m = m_lo; m <= mtop; ++m) { koff[m - m_lo] = ktot; const size_t Lm = lmax_grp + 1 - m; ktot += Lm * (Lm + xa(m)); }
+  bt_tables K;   // T: K_lambda, W: K_P, X: K_X
+  if (!bt_tables_alloc(ctx, polarised, ktot, K) || !d_sc) return DM_ENOMEM;
+  {
+    dm_ws_scope tmp_scope(ctx);   // scaled tables: released (stream-ordered) once the K products are queued
+    bt_tables S;
+    if (!bt_tables_alloc(ctx, polarised, w.ltot, S)) return DM_ENOMEM;
+    const unsigned nb = (unsigned)std::min<size_t>((w.ltot + 255) / 256, 65536);
+    for (int t = 0; t < (polarised ? 3 : 1); ++t)
+      DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_scale_table_kernel, dim3(nb), dim3(256), 0, ctx->stream, w.tab[t], S[t], w.ltot, nring, d_sc);
+    for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
+      std::vector<dm_gemm_desc> g;
+      for (int m = m_lo; m <= mtop; ++m) {
+        const int Lm = lmax_grp + 1 - m;
+        const size_t lo = w.loff[m - m_lo], ko = koff[m - m_lo];
+        // K is symmetric: row i of the product lands where the layout keeps (k = i, n) (n runs fastest, Lm + xa per row)
+        auto kadd = [&](const double* ta, const double* tb, double* c, double beta) {
+          g.push_back(dm_gemm_make(reinterpret_cast<const cplx*>(ta + lo), nring, 1, false, tb + lo, 1, nring, false,
+                                   reinterpret_cast<cplx*>(c + ko), Lm + xa(m), Lm, Lm, nring, 1.0, beta, nullptr, DM_GEMM_ALL_REAL));
+        };
+        if (pass == 0) {
+          kadd(w.tab.T, S.T, K.T, 0.0);
+          if (polarised) { kadd(w.tab.W, S.W, K.W, 0.0); kadd(w.tab.W, S.X, K.X, 0.0); }
+        } else {
+          kadd(w.tab.X, S.X, K.W, 1.0);
+          kadd(w.tab.X, S.W, K.X, 1.0);
+        }
+      }
+      DM_TRY(dm_gemm_grouped_launch(ctx, g));
+    }
+  }
+  // ---- alias rings: their own small tables (same recurrences, same bits as the full tables)
+  const int nmmA = 2 * (Mc + 1);
+  bt_tables A;
+  double* d_scA = nullptr;
+  int *d_nphiA = nullptr, *d_mlimA = nullptr;
+  cplx* Ha = nullptr;
+  std::vector<size_t> loffA(std::max(Mc + 1, 1), 0);
+  if (Mc >= 0) {
+    std::vector<double> geoA(2 * (size_t)nra), scA(nra);
+    std::vector<int> nphiA(nra), mlimA(nra);
+    for (int ja = 0; ja < nra; ++ja) {
+      const int r = ja < al.ia ? ja : nring - nra + ja;
+      geoA[ja] = gh.cth[r];
+      geoA[nra + ja] = gh.sth[r];
+      nphiA[ja] = gh.nphi[r];
+      mlimA[ja] = al.mlim[ja < al.ia ? ja : nra - 1 - ja];
+      scA[ja] = (ring_w_host ? ring_w_host[r] : 1.0) * (double)gh.nphi[r];
+    }
+    double* d_geoA = dm_ws_upload(ctx, geoA);
+    d_scA = dm_ws_upload(ctx, scA);
+    d_nphiA = dm_ws_upload(ctx, nphiA);
+    d_mlimA = dm_ws_upload(ctx, mlimA);
+    size_t ltotA = 0;
+    for (int m = 0; m <= Mc; ++m) { loffA[m] = ltotA; ltotA += (size_t)(lmax_grp + 1 - m) * nra; }
+    size_t* d_loffA = dm_ws_upload(ctx, loffA);
+    size_t* d_koff = dm_ws_upload(ctx, koff);
+    const bool okA = bt_tables_alloc(ctx, polarised, ltotA, A);
+    Ha = dm_ws_alloc_t<cplx>(ctx, (size_t)nmmA * nra * ncp);
+    if (!d_geoA || !d_scA || !d_nphiA || !d_mlimA || !d_loffA || !d_koff || !okA || !Ha) return DM_ENOMEM;
+    ring_geo ga = gh.g;
+    ga.cth = d_geoA;
+    ga.sth = d_geoA + nra;
+    ga.nring = nra;
+    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_legendre_kernel, dim3((nra + 63) / 64, Mc + 1), dim3(64), 0, ctx->stream, ga, lmax_grp, 0, Mc, wq,
+                       d_loffA, A.T, A.W, A.X);
+    for (int t = 0; t < (polarised ? 3 : 1); ++t)
+      DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_kext_fill_kernel, dim3(64, Mc + 1), dim3(256), 0, ctx->stream, A[t], d_loffA, K[t], d_koff,
+                         lmax_grp, nra);
+  }
+  // ---- iteration on the increments:  d_0 = a_0,  d_{k+1} = d_k - mask((A o S) d_k),  a_n = sum_k d_k
+  const size_t nacc = (size_t)w.nmblk * 2 * ncol * P * L;
+  cplx* dbuf = dm_ws_alloc_t<cplx>(ctx, nacc);
+  cplx* tbuf = dm_ws_alloc_t<cplx>(ctx, nacc);
+  if (!dbuf || !tbuf) return DM_ENOMEM;
+  DM_HIP(ctx, hipMemcpyAsync(dbuf, w.bm, sizeof(cplx) * nacc, hipMemcpyDeviceToDevice, ctx->stream));
+  auto blk = [&](cplx* base, int m, int s2) { return base + ((size_t)(m - m_lo) * 2 + s2) * ncol * P * L + m; };
+  for (int it = 0; it < a.niter; ++it) {
+    if (Mc >= 0) {
+      // synthesis on the alias rings: Ha[mm][col p][ja] = (1 / w) sum_l tabA[l][ja] d[col][p][l]
+      for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
+        std::vector<dm_gemm_desc> g;
+        for (int m = 0; m <= Mc; ++m) {
+          const int Lm = lmax_grp + 1 - m;
+          for (int s2 = 0; s2 < 2; ++s2) {
+            cplx* Hm = Ha + (size_t)(s2 * (Mc + 1) + m) * nra * ncp;
+            if (m == 0 && s2 == 1) continue;   // never read by the fold
+            const cplx* in = blk(dbuf, m, s2);
+            bt_stokes_terms(polarised, pass, A, 0.0, [&](int pin, const double* tab, int pout, double are, double aim, double beta) {
+              dm_gemm_desc dsc = dm_gemm_make(in + (size_t)pin * L, P * L, 1, false, tab + loffA[m], nra, 1, false,
+                                              Hm + (size_t)pout * nra, P * nra, ncol, nra, Lm, are * iw, beta, nullptr,
+                                              DM_GEMM_B_REAL);
+              dsc.alpha_im = aim * iw;
+              g.push_back(dsc);
+            });
+          }
+        }
+        DM_TRY(dm_gemm_grouped_launch(ctx, g));
+      }
+      DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_alias_fold_kernel, dim3((unsigned)((ncp + 3) / 4), (nra + 63) / 64, nmmA), dim3(64, 4), 0, ctx->stream,
+                         Ha, dbuf, Mc, nra, (size_t)ncp, L, Lg, d_nphiA, d_mlimA, d_scA);
+    }
+    // t = [d | folded rings] [K ; alias tables]: the Gram product and the analysis of the folded rings in one K dimension
+    // (the alias slots add W g_Q - i X g_U to E' and W g_U + i X g_Q to B')
+    for (int pass = 0; pass < (polarised ? 2 : 1); ++pass) {
+      std::vector<dm_gemm_desc> g;
+      for (int m = m_lo; m <= mtop; ++m) {
+        const int Lm = lmax_grp + 1 - m, Kd = Lm + xa(m);
+        const size_t ko = koff[m - m_lo];
+        for (int s2 = 0; s2 < 2; ++s2) {
+          if (m == 0 && s2 == 1) continue;
+          const cplx* in = blk(dbuf, m, s2);
+          cplx* out = blk(tbuf, m, s2);
+          bt_stokes_terms(polarised, pass, K, 0.0, [&](int pin, const double* Km, int pout, double are, double aim, double beta) {
+            dm_gemm_desc dsc = dm_gemm_make(in + (size_t)pin * L, P * L, 1, false, Km + ko, 1, Kd, false,
+                                            out + (size_t)pout * L, P * L, ncol, Lm, Kd, are, beta, nullptr, DM_GEMM_B_REAL);
+            dsc.alpha_im = aim;
+            g.push_back(dsc);
+          });
+        }
+      }
+      DM_TRY(dm_gemm_grouped_launch(ctx, g));
+    }
+    DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_refine_update_kernel, dim3((P * L + 255) / 256, ncol, 2 * cnt), dim3(256), 0, ctx->stream, w.bm, dbuf,
+                       tbuf, m_lo, ncol, P, L, Lg, w.d_cl);
+    DM_HIP(ctx, hipGetLastError());
+  }
+  return DM_OK;
+}
+
+// ---- stage: Jacobi refinement through residual maps (healpy map2alm `iter`): coefficients += analysis(map - synthesis(coefficients)).
+// With c_lm = sum_pix w f Y_lm (the reference's conj(SHT(conj f))) the synthesis is f = sum_lm c_lm conj(Y_lm):
+//   H[+m][col][ring] = sum_l lambda_lm(ring) b0_lm,   H[-m] = sum_l lambda_lm conj(b1_lm)   (the fold undone)
+//   f[col][ring, j]  = sum_mm conj(tw[mm][j]) H[mm][col][ring]
+// and for the spin-2 pair the Hermitian 2x2 block [[W, -iX], [iX, W]] of the analysis applied once more.
+// The tables carry the quadrature weight w = 4 pi / npix: the synthesis divides it out again.
+static int bt_refine_maps(dm_ctx* ctx, const bt_sht_args& a, const bt_sht_ws& w) {
+  const int P = w.P, L = w.L, nring = w.nring, npix = w.npix, ncp = w.ncp, m_lo = a.m_lo;
+  const double iw = (double)npix / (4.0 * kPi);
+  cplx* res = dm_ws_alloc_t<cplx>(ctx, (size_t)ncp * npix);
+  if (!res) return DM_ENOMEM;
+  cplx* H = w.G;  // same size: (nm, ncp, nring) here against (nm, nring, ncp) there
+  for (int it = 0; it < a.niter; ++it) {
+    DM_HIP(ctx, hipMemcpyAsync(res, a.maps_dev, sizeof(cplx) * (size_t)ncp * npix, hipMemcpyDeviceToDevice, ctx->stream));
+    for (int pass = 0; pass < (a.polarised ? 2 : 1); ++pass) {
+      std::vector<dm_gemm_desc> g;
+      for (int m = m_lo; m <= w.mtop; ++m) {
+        const int Lm = a.lmax_grp + 1 - m;
+        for (int s = 0; s < 2; ++s) {
+          const int mm = (s == 0) ? (m - m_lo) : (w.cnt + m - m_lo);
+          cplx* Hm = H + (size_t)mm * ncp * nring;
+          for (const bt_run& rn : w.runs) {
+            const cplx* in = w.bm + ((((size_t)(m - m_lo) * a.F + rn.f) * 2 + s) * a.B + rn.b0) * P * L + m;
+            // C[col][ring] (row stride P * nring: the P maps of a column are adjacent rows) = A[col][l] * tab[l][ring]
+            bt_stokes_terms(a.polarised != 0, pass, w.tab, 0.0, [&](int pin, const double* tab, int pout, double are, double aim, double beta) {
+              dm_gemm_desc d = dm_gemm_make(in + (size_t)pin * L, P * L, 1, s == 1, tab + w.loff[m - m_lo], nring, 1, false,
+                                            Hm + ((size_t)rn.c0 * P + pout) * nring, P * nring, rn.n, nring, Lm,
+                                            are * iw, beta, nullptr, DM_GEMM_B_REAL);
+              d.alpha_im = (s == 1 ? -aim : aim) * iw;  // H[-m] = conj(M b1) = conj(M) conj(b1)
+              g.push_back(d);
+            });
+          }
+        }
+      }
+      DM_TRY(dm_gemm_grouped_launch(ctx, g));
+    }
+    {
+      std::vector<dm_gemm_desc> g;
+      g.reserve(nring);
+      for (int r = 0; r < nring; ++r)  // res[colp][start_r + j] -= sum_mm H[mm][colp][r] conj(tw_r[mm][j])
+        g.push_back(dm_gemm_make(H + r, nring, ncp * nring, false, w.tw + w.toff[r], w.gh.nphi[r], 1, true, res + w.gh.start[r],
+                                 npix, ncp, w.gh.nphi[r], w.nm, -1.0, 1.0));
+      DM_TRY(dm_gemm_grouped_launch(ctx, g));
+    }
+    DM_TRY(bt_ring_from_maps(ctx, a, w, res));
+    DM_TRY(bt_legendre_analysis(ctx, a, w, true));
+  }
+  return DM_OK;
+}
+
+// The transform of one group of columns: ring transform, Legendre analysis, refinement.
+static int bt_sht_run(dm_ctx* ctx, const bt_sht_args& a) {
   if (!ctx) return DM_EARG;
-  DM_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && lside >= 0 && m_lo >= 0 && m_hi >= m_lo && lmax_grp >= 0 &&
-                  lmax_grp <= lside && F > 0 && B > 0 && ncol >= 0 && col_f_host && col_b_host && col_lmax_host && beam_m_dev &&
-                  niter > 0);
+  const bool harmonic = a.mode == BT_REFINE_HARMONIC;
+  DM_ARG(ctx, a.maps_dev || (a.syn && (a.niter == 0 || harmonic)));
+  DM_ARG(ctx, a.nside > 0 && a.ring_cth_host && a.ring_sth_host && a.lside >= 0 && a.m_lo >= 0 && a.m_hi >= a.m_lo && a.lmax_grp >= 0 &&
+                  a.lmax_grp <= a.lside && a.F > 0 && a.B > 0 && a.ncol >= 0 && a.col_f_host && a.col_b_host && a.col_lmax_host &&
+                  a.beam_m_dev && a.niter >= 0);
+  DM_ARG(ctx, a.niter == 0 || harmonic || (a.m_lo == 0 && a.m_hi >= a.lmax_grp));  // the residual map needs every m of a column
+  // the harmonic-space refinement runs on a private coefficient buffer laid out (m, 2, col, P, L) (bt_sht_private)
+  DM_ARG(ctx, !(a.niter > 0 && harmonic) || (a.F == 1 && a.B == a.ncol && a.lside == a.lmax_grp));
+  DM_ARG(ctx, a.row_pad == 0 || (a.niter > 0 && harmonic));
+  if (a.ncol == 0) return DM_OK;
+  dm_ws_scope ws_scope__(ctx);  // releases on every return path
+  bt_sht_ws w;
+  DM_TRY(upload_geo(ctx, a.nside, a.ring_cth_host, a.ring_sth_host, w.gh));
+  w.P = a.polarised ? 4 : 1;
+  w.L = a.lside + 1 + a.row_pad;   // row length of the destination (row_pad: alias slots of the private buffers)
+  w.nring = w.gh.g.nring;
+  w.npix = w.gh.g.npix;
+  w.mtop = std::min(a.m_hi, a.lmax_grp);  // no (l, m) content above the group's band limit
+  w.cnt = std::max(w.mtop - a.m_lo + 1, 0);  // m values with content in this range
+  w.nm = 2 * std::max(w.cnt, 1);
+  w.ncp = a.ncol * w.P;  // map columns
+  w.nmblk = a.m_hi - a.m_lo + 1;
+  w.fused = a.maps_dev == nullptr;
+  w.bm = reinterpret_cast<cplx*>(a.beam_m_dev);
+
+  DM_TRY(bt_ring_buffers(ctx, a, w));
+  if (w.cnt > 0) DM_TRY(w.fused ? bt_ring_fused(ctx, a, w) : bt_ring_from_maps(ctx, a, w, reinterpret_cast<const cplx*>(a.maps_dev)));
+  DM_TRY(bt_legendre_tables(ctx, a, w));
+  DM_TRY(bt_columns_prepare(ctx, a, w));
+  bt_fold_rings(ctx, a, w);
+  {
+    static const bool host_times = getenv("DM_TIME_HOST") != nullptr;  // debugging aid
+    const auto t0 = std::chrono::steady_clock::now();
+    DM_TRY(bt_legendre_analysis(ctx, a, w, false));
+    if (host_times)
+      fprintf(stderr, "HOSTTIME bt_sht_run: Legendre descriptors + launch %.3f ms (ncol %d, m %d..%d)\n",
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), a.ncol, a.m_lo, a.m_hi);
+  }
+  if (a.niter > 0 && w.cnt > 0) DM_TRY(harmonic ? bt_refine_harmonic(ctx, a, w) : bt_refine_maps(ctx, a, w));
+  // The fused path returns once everything is queued (stream-ordered with the caller's later work on the context's stream,
+  // workspace re-use included: dm_ws_release); the map-based and map-space paths keep their wait.
+  if (a.mode == BT_REFINE_MAPS || !w.fused) DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DM_OK;
+}
+
+// healpy's `iter` on a private coefficient buffer (nm, 2, ncol, P, Lrow), from which the requested blocks are copied out.
+// BT_REFINE_HARMONIC: the buffer holds the blocks the refinement of [m_lo, m_hi] depends on — the range itself, plus every
+// m <= mcut when the range reaches into the m the polar rings alias (those couple among themselves only); its rows are
+// compact in l, with one slot per alias ring behind them (the folded rings ride in the K dimension of the Gram products).
+// BT_REFINE_MAPS: the residual map needs EVERY (l, m) of a column, whatever range of m the caller keeps (and the telescope's
+// mmax may lie below a column's lmax): the buffer holds m = 0 .. lmax_grp with rows as the caller's.
+static int bt_sht_private(dm_ctx* ctx, const bt_sht_args& a) {
+  DM_ARG(ctx, a.nside > 0 && a.ring_cth_host && a.ring_sth_host && a.lside >= 0 && a.m_lo >= 0 && a.m_hi >= a.m_lo && a.lmax_grp >= 0 &&
+                  a.lmax_grp <= a.lside && a.F > 0 && a.B > 0 && a.ncol >= 0 && a.col_f_host && a.col_b_host && a.col_lmax_host &&
+                  a.beam_m_dev && a.niter > 0);
+  const int ncol = a.ncol;
   if (ncol == 0) return DM_OK;
   dm_ws_scope ws_scope__(ctx);
-  const int P = polarised ? 4 : 1, L = lside + 1, Ls = lmax_grp + 1;
-  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, col_f_host[c] >= 0 && col_f_host[c] < F && col_b_host[c] >= 0 && col_b_host[c] < B);
-  const bt_alias_info& al = bt_alias_lookup(nside, lmax_grp, polarised != 0, ring_cth_host, ring_sth_host);
-  int e_lo = m_lo, e_hi = m_hi;
-  if (al.ia > 0 && m_lo <= al.mcut) { e_lo = 0; e_hi = std::max(m_hi, std::min(al.mcut, lmax_grp)); }
-  const int enm = e_hi - e_lo + 1;
-  // rows of the private buffers: Ls coefficients + one slot per alias ring (the folded rings ride in the K dimension of
-  // the Gram products)
-  const int pad = (al.ia > 0 && e_lo == 0 && std::min(e_hi, lmax_grp) >= 0) ? 2 * al.ia : 0;
-  const int Lrow = Ls + pad;
+  const int P = a.polarised ? 4 : 1, L = a.lside + 1;
+  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, a.col_f_host[c] >= 0 && a.col_f_host[c] < a.F && a.col_b_host[c] >= 0 && a.col_b_host[c] < a.B);
+  int e_lo = 0, e_hi = a.lmax_grp, Ls = L, pad = 0;
+  if (a.mode == BT_REFINE_HARMONIC) {
+    const bt_alias_info& al = bt_alias_lookup(a.nside, a.lmax_grp, a.polarised != 0, a.ring_cth_host, a.ring_sth_host);
+    e_lo = a.m_lo;
+    e_hi = a.m_hi;
+    if (al.ia > 0 && a.m_lo <= al.mcut) { e_lo = 0; e_hi = std::max(a.m_hi, std::min(al.mcut, a.lmax_grp)); }
+    Ls = a.lmax_grp + 1;
+    pad = (al.ia > 0 && e_lo == 0 && std::min(e_hi, a.lmax_grp) >= 0) ? 2 * al.ia : 0;
+  }
+  const int enm = e_hi - e_lo + 1, Lrow = Ls + pad;
   cplx* acc = dm_ws_alloc_t<cplx>(ctx, (size_t)enm * 2 * ncol * P * Lrow);
   if (!acc) return DM_ENOMEM;
   std::vector<int> zf(ncol, 0), ib(ncol);
   for (int c = 0; c < ncol; ++c) ib[c] = c;
-  DM_TRY(bt_sht_impl(ctx, nside, ring_cth_host, ring_sth_host, polarised, lmax_grp, e_lo, e_hi, lmax_grp, 1, ncol, ncol,
-                     zf.data(), ib.data(), col_lmax_host, maps_dev, acc, niter, ring_w_host, syn, true, pad));
-  std::vector<int> cfv(col_f_host, col_f_host + ncol), cbv(col_b_host, col_b_host + ncol);
+  DM_TRY(bt_sht_run(ctx, bt_sht_args{a.nside, a.ring_cth_host, a.ring_sth_host, a.polarised, Ls - 1, e_lo, e_hi, a.lmax_grp, 1, ncol, ncol,
+                                     zf.data(), ib.data(), a.col_lmax_host, acc, a.niter, a.ring_w_host, a.maps_dev, a.syn, a.mode, pad}));
+  std::vector<int> cfv(a.col_f_host, a.col_f_host + ncol), cbv(a.col_b_host, a.col_b_host + ncol);
   int* d_cf = dm_ws_upload(ctx, cfv);
   int* d_cb = dm_ws_upload(ctx, cbv);
   if (!d_cf || !d_cb) return DM_ENOMEM;
-  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_scatter2_kernel, dim3((2 * P * L + 255) / 256, ncol, m_hi - m_lo + 1), dim3(256), 0, ctx->stream, acc, e_lo,
-                     enm, Ls, Lrow, reinterpret_cast<cplx*>(beam_m_dev), m_lo, F, B, P, L, ncol, d_cf, d_cb);
+  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_scatter2_kernel, dim3((2 * P * L + 255) / 256, ncol, a.m_hi - a.m_lo + 1), dim3(256), 0, ctx->stream, acc, e_lo,
+                     enm, Ls, Lrow, reinterpret_cast<cplx*>(a.beam_m_dev), a.m_lo, a.F, a.B, P, L, ncol, d_cf, d_cb);
   DM_HIP(ctx, hipGetLastError());
   return DM_OK;
+}
+
+// The fused route of dm_bt_columns, dm_bt_columns_c and dm_bt_columns_iter: the plain analysis, or healpy's `iter` in
+// harmonic space (no Stokes maps, no residual maps).  `a` carries everything but the source of the maps.
+static int bt_columns(dm_ctx* ctx, bt_sht_args a, const bt_synth_in& syn) {
+  a.syn = &syn;
+  if (a.niter == 0) return bt_sht_run(ctx, a);
+  a.mode = BT_REFINE_HARMONIC;
+  return bt_sht_private(ctx, a);
 }
 
 int dm_bt_sht_opts(dm_ctx* ctx, int nside, const double* ring_cth_host, const double* ring_sth_host, int polarised,
@@ -1882,41 +1897,21 @@ int dm_bt_sht_opts(dm_ctx* ctx, int nside, const double* ring_cth_host, const do
                    const int* col_b_host, const int* col_lmax_host, const void* maps_dev, void* beam_m_dev, int niter,
                    const double* ring_w_host) {
   if (!ctx) return DM_EARG;
-  if (niter <= 0)
-    return bt_sht_impl(ctx, nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol,
-                       col_f_host, col_b_host, col_lmax_host, maps_dev, beam_m_dev, 0, ring_w_host);
-  // default: the refinement in harmonic space (no residual maps; bt_sht_refined).  DM_SHT_PIXEL_REFINE=1 keeps the
-  // map-space form (synthesis, inverse ring DFT, residual map, re-analysis) for cross-checks.
+  bt_sht_args a{nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
+                col_b_host, col_lmax_host, beam_m_dev, std::max(niter, 0), ring_w_host, maps_dev};
+  if (niter <= 0) return bt_sht_run(ctx, a);
+  // default: the refinement in harmonic space (no residual maps).  DM_SHT_PIXEL_REFINE=1 keeps the map-space form
+  // (synthesis, inverse ring DFT, residual map, re-analysis) for cross-checks.
   static const bool pixel_refine = getenv("DM_SHT_PIXEL_REFINE") && atoi(getenv("DM_SHT_PIXEL_REFINE")) == 1;
-  if (!pixel_refine) {
+  if (pixel_refine) {
+    DM_ARG(ctx, nside > 0 && lside >= 0 && m_lo >= 0 && m_hi >= m_lo && lmax_grp >= 0 && lmax_grp <= lside && F > 0 && B > 0 &&
+                    ncol >= 0 && col_f_host && col_b_host && col_lmax_host && maps_dev && beam_m_dev);
+    if (ncol == 0) return DM_OK;
+  } else {
     DM_ARG(ctx, maps_dev != nullptr);
-    DM_TRY(bt_sht_refined(ctx, nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol,
-                          col_f_host, col_b_host, col_lmax_host, maps_dev, beam_m_dev, niter, ring_w_host, nullptr));
-    DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DM_OK;
   }
-  // The refinement synthesises the map from EVERY (l, m) of a column, whatever range of m the caller keeps (and the
-  // telescope's mmax may lie below a column's lmax): it runs on a private coefficient buffer holding m = 0 .. lmax_grp
-  // of this group's columns, laid out like beam_m with F = 1, B = ncol; the requested blocks are copied out at the end.
-  DM_ARG(ctx, nside > 0 && lside >= 0 && m_lo >= 0 && m_hi >= m_lo && lmax_grp >= 0 && lmax_grp <= lside && F > 0 && B > 0 &&
-                  ncol >= 0 && col_f_host && col_b_host && col_lmax_host && maps_dev && beam_m_dev);
-  if (ncol == 0) return DM_OK;
-  dm_ws_scope ws_scope__(ctx);
-  const int P = polarised ? 4 : 1, L = lside + 1, msrc = lmax_grp + 1;
-  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, col_f_host[c] >= 0 && col_f_host[c] < F && col_b_host[c] >= 0 && col_b_host[c] < B);
-  cplx* cf = dm_ws_alloc_t<cplx>(ctx, (size_t)msrc * 2 * ncol * P * L);
-  if (!cf) return DM_ENOMEM;
-  std::vector<int> zf(ncol, 0), ib(ncol);
-  for (int c = 0; c < ncol; ++c) ib[c] = c;
-  DM_TRY(bt_sht_impl(ctx, nside, ring_cth_host, ring_sth_host, polarised, lside, 0, lmax_grp, lmax_grp, 1, ncol, ncol,
-                     zf.data(), ib.data(), col_lmax_host, maps_dev, cf, niter, ring_w_host));
-  std::vector<int> cfv(col_f_host, col_f_host + ncol), cbv(col_b_host, col_b_host + ncol);
-  int* d_cf = dm_ws_upload(ctx, cfv);
-  int* d_cb = dm_ws_upload(ctx, cbv);
-  if (!d_cf || !d_cb) return DM_ENOMEM;
-  DM_PLAUNCH(ctx, DM_PROF_BT_OTHER, bt_scatter_kernel, dim3((2 * P * L + 255) / 256, ncol, m_hi - m_lo + 1), dim3(256), 0, ctx->stream, cf, msrc,
-                     reinterpret_cast<cplx*>(beam_m_dev), m_lo, F, B, P, L, ncol, d_cf, d_cb);
-  DM_HIP(ctx, hipGetLastError());
+  a.mode = pixel_refine ? BT_REFINE_MAPS : BT_REFINE_HARMONIC;
+  DM_TRY(bt_sht_private(ctx, a));
   DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return DM_OK;
 }
@@ -1928,9 +1923,9 @@ int dm_bt_columns(dm_ctx* ctx, int nside, const double* ring_cth_host, const dou
                   const int* col_b_host, const int* col_lmax_host, void* beam_m_dev, const double* ring_w_host) {
   if (!ctx) return DM_EARG;
   DM_ARG(ctx, frame_host && nbeam > 0 && beams_dev && uv_host && bi_host && bj_host);
-  bt_synth_in syn{frame_host, nbeam, beams_dev, uv_host, bi_host, bj_host, 0};
-  return bt_sht_impl(ctx, nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
-                     col_b_host, col_lmax_host, nullptr, beam_m_dev, 0, ring_w_host, &syn);
+  return bt_columns(ctx, bt_sht_args{nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
+                                     col_b_host, col_lmax_host, beam_m_dev, 0, ring_w_host},
+                    bt_synth_in{frame_host, nbeam, beams_dev, uv_host, bi_host, bj_host, 0});
 }
 
 // dm_bt_columns for COMPLEX field patterns (beams_dev: nbeam maps of npix * ncomp complex128, zero below the horizon)
@@ -1940,9 +1935,9 @@ int dm_bt_columns_c(dm_ctx* ctx, int nside, const double* ring_cth_host, const d
                     const int* col_b_host, const int* col_lmax_host, void* beam_m_dev, const double* ring_w_host) {
   if (!ctx) return DM_EARG;
   DM_ARG(ctx, frame_host && nbeam > 0 && beams_dev && uv_host && bi_host && bj_host);
-  bt_synth_in syn{frame_host, nbeam, reinterpret_cast<const double*>(beams_dev), uv_host, bi_host, bj_host, 1};
-  return bt_sht_impl(ctx, nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
-                     col_b_host, col_lmax_host, nullptr, beam_m_dev, 0, ring_w_host, &syn);
+  return bt_columns(ctx, bt_sht_args{nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
+                                     col_b_host, col_lmax_host, beam_m_dev, 0, ring_w_host},
+                    bt_synth_in{frame_host, nbeam, reinterpret_cast<const double*>(beams_dev), uv_host, bi_host, bj_host, 1});
 }
 
 // dm_bt_columns / dm_bt_columns_c with healpy's `iter`: niter Jacobi refinements of the quadrature carried out in harmonic
@@ -1954,12 +1949,9 @@ int dm_bt_columns_iter(dm_ctx* ctx, int nside, const double* ring_cth_host, cons
                        const double* ring_w_host, int niter) {
   if (!ctx) return DM_EARG;
   DM_ARG(ctx, frame_host && nbeam > 0 && beams_dev && uv_host && bi_host && bj_host && niter >= 0);
-  bt_synth_in syn{frame_host, nbeam, reinterpret_cast<const double*>(beams_dev), uv_host, bi_host, bj_host, complex_beams ? 1 : 0};
-  if (niter == 0)
-    return bt_sht_impl(ctx, nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
-                       col_b_host, col_lmax_host, nullptr, beam_m_dev, 0, ring_w_host, &syn);
-  return bt_sht_refined(ctx, nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
-                        col_b_host, col_lmax_host, nullptr, beam_m_dev, niter, ring_w_host, &syn);
+  return bt_columns(ctx, bt_sht_args{nside, ring_cth_host, ring_sth_host, polarised, lside, m_lo, m_hi, lmax_grp, F, B, ncol, col_f_host,
+                                     col_b_host, col_lmax_host, beam_m_dev, niter, ring_w_host},
+                    bt_synth_in{frame_host, nbeam, reinterpret_cast<const double*>(beams_dev), uv_host, bi_host, bj_host, complex_beams ? 1 : 0});
 }
 
 // The m the refinement of one nside group couples through the polar rings: n_alias_rings per cap, and mcut — a call for a
