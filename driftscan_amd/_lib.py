@@ -134,6 +134,8 @@ SIGNATURES = {
         c_int, [c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_int, ctypes.POINTER(c_int),
                 ctypes.POINTER(c_int)]),
     "dm_bit_truncate_max_complex": (c_int, [c_vp, c_vp, c_i64, c_int, c_i64, c_dbl, c_dbl]),
+    "dm_blockvec_grouped": (c_int, [c_vp, c_int, ctypes.POINTER(ZgemmProblem)]),
+    "dm_mmode_twiddle": (c_int, [c_vp, c_int, c_int, c_vp]),
 }
 
 _lib = None
@@ -305,6 +307,133 @@ class Context(object):
         self.check(self.lib.dm_jacobi_herm_batched(self.h, n, self.ptr(C), ldc, strideC, self.ptr(W), n, n * n, batch,
                                                    self.ptr(ev), ctypes.byref(sw)), "dm_jacobi_herm_batched")
         return ev, W, sw.value
+
+
+# ---- block-apply of stored product blocks to a few vectors (dm_blockvec_grouped) ---------------------------------------
+# A problem TABLE is a numpy record array, one row per problem y = op(A) x: element offsets of the problem's A, x and y in
+# three buffers shared by the whole call, its shape and strides.  The tables are made by plain numpy code
+# (`blockvec_table` and the builders in beamtransfer.py / kltransform.py) that needs no device, so the packed layouts are
+# testable on the host; `Context.blockvec_grouped` turns the offsets into addresses.
+BLOCKVEC_FIELDS = ("a0", "x0", "y0", "M", "K", "rsA", "csA", "rsB", "csB", "ldc", "conjA", "conjB")
+BLOCKVEC_TABLE = np.dtype([(k, np.int64) for k in BLOCKVEC_FIELDS])
+_ZGEMM_RECORD = np.dtype([("A", np.uint64), ("B", np.uint64), ("C", np.uint64), ("M", np.int32), ("N", np.int32),
+                          ("K", np.int32), ("rsA", np.int32), ("csA", np.int32), ("rsB", np.int32), ("csB", np.int32),
+                          ("ldc", np.int32), ("conjA", np.int32), ("conjB", np.int32), ("alpha", np.float64),
+                          ("beta", np.float64)], align=True)
+assert _ZGEMM_RECORD.itemsize == ctypes.sizeof(ZgemmProblem)
+BLOCKVEC_MAX_R = 8      # right-hand sides the kernel keeps in registers; wider calls go to the grouped ZGEMM
+BLOCKVEC_LEAN_R = 6     # up to here the kernel was at least as fast as the grouped ZGEMM on every measured batch
+BLOCKVEC_LONG_K = 256   # one LDS chunk of x (BV_KC of dm_modes.hip)
+
+
+def blockvec_route(table, R):
+    """Which kernel takes a table at R right-hand sides, from the rates of DESIGN.md section 4.11: the streaming kernel
+    up to 6 right-hand sides; for 7 and 8 only where most of A lies in rows longer than one LDS chunk of x (the KL
+    eigenvector blocks: measured 1.1 to 4.5 times the ZGEMM's rate at R = 8) — on short rows (the `beam_ut` blocks,
+    K = ntel) it is 20 % behind the ZGEMM at R = 8; the grouped ZGEMM above 8."""
+    if R <= BLOCKVEC_LEAN_R:
+        return "blockvec"
+    if R > BLOCKVEC_MAX_R:
+        return "zgemm"
+    work = table["M"] * table["K"]
+    return "blockvec" if 2 * int(work[table["K"] > BLOCKVEC_LONG_K].sum()) >= int(work.sum()) else "zgemm"
+
+
+def blockvec_table(**cols):
+    """Record array of problems from per-problem columns (scalars broadcast); conjA / conjB default to 0."""
+    cols.setdefault("conjA", 0)
+    cols.setdefault("conjB", 0)
+    arrs = np.broadcast_arrays(*[np.asarray(cols[k], dtype=np.int64) for k in BLOCKVEC_FIELDS])
+    tab = np.zeros(arrs[0].shape, dtype=BLOCKVEC_TABLE).reshape(-1)
+    for k, a in zip(BLOCKVEC_FIELDS, arrs):
+        tab[k] = a.reshape(-1)
+    return tab
+
+
+def _blockvec_grouped(self, A, x, y, table, R, route=None):
+    """y_p = op(A_p) x_p for every row of `table` (offsets into the device tensors A, x, y; R right-hand sides) in one
+    launch.  Problems with M = 0 or K = 0 are left out: nothing is written for them.  route: None (`blockvec_route`),
+    "blockvec" or "zgemm"."""
+    R = int(R)
+    if R < 1:
+        raise ValueError("blockvec_grouped: R must be positive")
+    if route == "blockvec" and R > BLOCKVEC_MAX_R:
+        raise ValueError("blockvec_grouped: the kernel takes at most %d right-hand sides" % BLOCKVEC_MAX_R)
+    table = np.asarray(table)
+    table = table[(table["M"] > 0) & (table["K"] > 0)]
+    n = int(table.shape[0])
+    if n == 0:
+        return
+    if route is None:
+        route = blockvec_route(table, R)
+    for t in (A, x, y):
+        if not (t.is_complex() and t.element_size() == 16 and t.is_contiguous()):
+            raise ValueError("blockvec_grouped: contiguous complex128 device tensors expected")
+    # every problem must lie inside its buffers (a wrong offset would be an out-of-bounds access on the device)
+    M1, K1 = table["M"] - 1, table["K"] - 1
+    for lo, hi, t, what in (
+            (table["a0"] + np.minimum(0, M1 * table["rsA"]) + np.minimum(0, K1 * table["csA"]),
+             table["a0"] + np.maximum(0, M1 * table["rsA"]) + np.maximum(0, K1 * table["csA"]), A, "A"),
+            (table["x0"] + np.minimum(0, K1 * table["rsB"]) + np.minimum(0, (R - 1) * table["csB"]),
+             table["x0"] + np.maximum(0, K1 * table["rsB"]) + np.maximum(0, (R - 1) * table["csB"]), x, "x"),
+            (table["y0"], table["y0"] + M1 * table["ldc"] + (R - 1), y, "y")):
+        if int(lo.min()) < 0 or int(hi.max()) >= int(t.numel()):
+            raise ValueError("blockvec_grouped: a problem reaches outside its %s buffer" % what)
+    if int(table["ldc"].min()) < R:
+        raise ValueError("blockvec_grouped: ldc < R")
+    rec = np.zeros(n, dtype=_ZGEMM_RECORD)
+    rec["A"] = A.data_ptr() + 16 * table["a0"]
+    rec["B"] = x.data_ptr() + 16 * table["x0"]
+    rec["C"] = y.data_ptr() + 16 * table["y0"]
+    rec["N"] = R
+    for k in ("M", "K", "rsA", "csA", "rsB", "csB", "ldc", "conjA", "conjB"):
+        rec[k] = table[k]
+    rec["alpha"] = 1.0
+    arr = rec.ctypes.data_as(ctypes.POINTER(ZgemmProblem))
+    if route == "blockvec":
+        self.check(self.lib.dm_blockvec_grouped(self.h, n, arr), "dm_blockvec_grouped")
+    elif route == "zgemm":
+        self.check(self.lib.dm_zgemm_grouped(self.h, n, arr), "dm_zgemm_grouped")
+    else:
+        raise ValueError("blockvec_grouped: unknown route %r" % (route,))
+
+
+def _mmode_twiddle(self, ntime, mmax):
+    """(ntime, mmax + 1) c128 table W[t, m] = exp(-2 pi i m t / ntime) / ntime on the device (dm_mmode_twiddle)."""
+    W = self.empty((int(ntime), int(mmax) + 1), np.complex128)
+    self.check(self.lib.dm_mmode_twiddle(self.h, int(ntime), int(mmax), self.ptr(W)), "dm_mmode_twiddle")
+    return W
+
+
+def _mmode_transform(self, X, mmax, out=None):
+    """Pruned time -> m transform of timestreams X (nf, npairs, ntime) on the device: out[m, f, 0] = the +m bin of
+    fft(X) / ntime, out[m, f, 1] = the conjugate of the -m bin (zero for m = 0) — the [m][f][2][npairs] layout of the
+    mode.hdf5 files.  Two strided-batched ZGEMMs with the twiddle table: the same table against conj(X) gives slot 1,
+    conj(Xhat[ntime - m]) = sum_t conj(x_t) exp(-2 pi i m t / ntime)."""
+    nf, npairs, ntime = (int(v) for v in X.shape)
+    mmax = int(mmax)
+    if ntime < 2 * mmax + 1:
+        raise ValueError("mmode_transform: %d time samples cannot hold m up to %d" % (ntime, mmax))
+    if not X.is_contiguous():
+        X = X.contiguous()
+    if out is None:
+        out = self.empty((mmax + 1, nf, 2, npairs), np.complex128)
+    if tuple(out.shape) != (mmax + 1, nf, 2, npairs) or not out.is_contiguous():
+        raise ValueError("mmode_transform: out must be a contiguous (mmax + 1, nf, 2, npairs) tensor")
+    if nf == 0 or npairs == 0:
+        return out
+    W = self.mmode_twiddle(ntime, mmax)
+    flat = out.view(-1)
+    for slot in (0, 1):
+        self.zgemm(W, X, flat[slot * npairs:], mmax + 1, npairs, ntime, rsA=1, csA=mmax + 1, rsB=1, csB=ntime,
+                   ldc=nf * 2 * npairs, conjB=bool(slot), batch=nf, strideA=0, strideB=npairs * ntime, strideC=2 * npairs)
+    out[0, :, 1].zero_()
+    return out
+
+
+Context.blockvec_grouped = _blockvec_grouped
+Context.mmode_twiddle = _mmode_twiddle
+Context.mmode_transform = _mmode_transform
 
 
 def _iarr(a):
@@ -780,7 +909,8 @@ PROF_CLASSES = ["zgemm_grouped", "gemm_grouped_realB", "jac_gram", "jac_inner", 
                 "zgemm_cov",                                  # gathered-B ZGEMM: the covariance projections
                 # extended classes (profiling level 2, time only)
                 "bt_ring", "bt_other", "trd_small", "dc", "chol_solve", "util", "eig_other", "svd_other",
-                "unused20", "unused21", "unused22", "unused23"]
+                "blockvec",   # reports algorithmic BYTES of A in the "flops" field
+                "unused21", "unused22", "unused23"]
 PROF_NCLASS = len(PROF_CLASSES)
 
 

@@ -14,7 +14,7 @@ import time
 import numpy as np
 
 from . import btgen, config, parallel, storage, util
-from ._lib import block_offsets
+from ._lib import block_offsets, blockvec_table
 from .device import get_context
 
 logger = logging.getLogger(__name__)
@@ -855,6 +855,53 @@ class BeamTransfer(config.Reader):
         return vecf
 
 
+    # ---- vector projections of a BATCH of m on the device (dm_blockvec_grouped) ---------------------------------
+    def _svnum_batch(self, ms):
+        """(len(ms), nfreq) modes kept per frequency for the m of a batch."""
+        return np.stack([np.asarray(self._svd_num(mi)[0]) for mi in ms]).astype(np.int64).reshape(len(ms), self.nfreq)
+
+    def _dev_stack(self, ms, key):
+        """The product `key` ("beam_ut", "invbeam_svd") of the m of a batch as ONE device tensor (len(ms), ...): a view of
+        the resident copies where `_dev` holds them all (during product generation), one upload from the files otherwise —
+        of this product only, and nothing is left in `_dev`: the caller's reference is the only one."""
+        if ms and all(mi in self._dev and self._dev[mi].get(key) is not None for mi in ms):
+            return self._stacked_products(ms, key)
+        return get_context().to_device(np.stack([getattr(self, key)(mi) for mi in ms]))
+
+    def project_vectors_telescope_to_svd_device(self, ms, vecs, products=None):
+        """Batch form of `project_vector_telescope_to_svd`: vecs (len(ms), nfreq, ntel, R) on the device -> (out, off) with
+        out (sum of ndof, R) packed as the per-m vectors are (`svbounds` inside an m, m after m) and off the first row of
+        every m (len(ms) + 1).  One launch for all (m, frequency) blocks; `products` is the `_dev_stack(ms, "beam_ut")` of
+        the batch if the caller holds it already."""
+        ctx = get_context()
+        nb, F, T, R = (int(v) for v in vecs.shape)
+        if (nb, F, T) != (len(ms), self.nfreq, self.ntel):
+            raise ValueError("vectors of shape (len(ms), nfreq, ntel, R) expected")
+        tab, off = svd_forward_table(self._svnum_batch(ms), self.svd_len, T, R)
+        out = ctx.zeros((max(int(off[-1]), 1), R), np.complex128)[: int(off[-1])]
+        if len(tab):
+            but = self._dev_stack(ms, "beam_ut") if products is None else products
+            ctx.blockvec_grouped(but, vecs.contiguous(), out, tab, R)
+        return out, off
+
+    def project_vectors_svd_to_sky_device(self, ms, vecs, off=None, products=None):
+        """Batch form of `project_vector_svd_to_sky` (through `invbeam_svd`): vecs (rows, R) packed SVD vectors on the
+        device, m number i starting at row off[i] (default: back to back) -> (len(ms), nfreq, npol, lmax + 1, R)."""
+        ctx = get_context()
+        tel = self.telescope
+        P, L = int(tel.num_pol_sky), int(tel.lmax) + 1
+        R = int(vecs.shape[1])
+        svnum = self._svnum_batch(ms)
+        if off is None:
+            off = np.concatenate([[0], np.cumsum(svnum.sum(axis=1))])
+        tab = svd_to_sky_table(svnum, off, self.svd_len, P, L, R)
+        out = ctx.zeros((len(ms), self.nfreq, P, L, R), np.complex128)
+        if len(tab):
+            inv = self._dev_stack(ms, "invbeam_svd") if products is None else products
+            ctx.blockvec_grouped(inv, vecs.contiguous(), out, tab, R)
+        return out
+
+
 class BeamTransferFullSVD(BeamTransfer):
     """One SVD of the full (all sky polarisations) noise-weighted beam per (m, frequency) instead of
     the three-stage chain (beamtransfer.py:1595-1733): the same device chain run on the blocks with
@@ -968,6 +1015,13 @@ class BeamTransferNoSVD(BeamTransfer):
     def project_vector_telescope_to_svd(self, mi, vec, *args, **kwargs):
         return np.asarray(vec).flatten()
 
+    def project_vectors_telescope_to_svd_device(self, ms, vecs, products=None):
+        nb, F, T, R = (int(v) for v in vecs.shape)
+        return vecs.reshape(nb * F * T, R), np.arange(nb + 1, dtype=np.int64) * (F * T)
+
+    def project_vectors_svd_to_sky_device(self, ms, vecs, off=None, products=None):
+        raise NotImplementedError("no batch form of the no-SVD map-making operator (it is the pseudo-inverse per m)")
+
     def project_vector_svd_to_sky(self, mi, vec, temponly=False, conj=False):
         if temponly:
             raise NotImplementedError("temponly not implemented for no-SVD project_vector_svd_to_sky!")
@@ -1021,3 +1075,39 @@ def _device_bgemv(mats, vecs):
     ctx.zgemm(dA, dB, dC, M, 1, K, rsA=K, csA=1, rsB=1, csB=1, ldc=1, batch=nb, strideA=M * K, strideB=K, strideC=M)
     ctx.sync()
     return dC.cpu().numpy().reshape(nb, M)
+
+
+# ---- problem tables of the batched vector projections ------------------------------------------------------------------
+# Plain numpy on the (batch, nfreq) table of kept modes: where every (m, frequency[, polarisation]) block of a batch
+# lies in the stacked products and in the packed vectors.  Blocks of a frequency without modes (and with them every m
+# without modes) have no row.  Offsets are in complex128 elements (`_lib.blockvec_table`).
+def _svbounds(svnum):
+    svnum = np.asarray(svnum, dtype=np.int64)
+    bounds = np.zeros((svnum.shape[0], svnum.shape[1] + 1), dtype=np.int64)
+    np.cumsum(svnum, axis=1, out=bounds[:, 1:])
+    return svnum, bounds
+
+
+def svd_forward_table(svnum, svd_len, ntel, R):
+    """beam_ut (nb, F, svd_len, ntel) applied to vectors (nb, F, ntel, R) into the packed (sum ndof, R) layout.
+    Returns (table, off): off[i] = first packed row of m number i."""
+    svnum, bounds = _svbounds(svnum)
+    F = svnum.shape[1]
+    off = np.concatenate([[0], np.cumsum(bounds[:, -1])]).astype(np.int64)
+    i, f = np.nonzero(svnum > 0)
+    blk = i * F + f
+    tab = blockvec_table(a0=blk * svd_len * ntel, x0=blk * ntel * R, y0=(off[i] + bounds[i, f]) * R, M=svnum[i, f], K=ntel,
+                         rsA=ntel, csA=1, rsB=R, csB=1, ldc=R)
+    return tab, off
+
+
+def svd_to_sky_table(svnum, off, svd_len, npol, nl, R):
+    """invbeam_svd (nb, F, npol, nl, svd_len) applied to packed SVD vectors (rows, R), m number i at row off[i], into
+    (nb, F, npol, nl, R)."""
+    svnum, bounds = _svbounds(svnum)
+    F = svnum.shape[1]
+    off = np.asarray(off, dtype=np.int64)
+    i, f, p = np.nonzero(np.repeat((svnum > 0)[:, :, None], npol, axis=2))
+    blk = (i * F + f) * npol + p
+    return blockvec_table(a0=blk * nl * svd_len, x0=(off[i] + bounds[i, f]) * R, y0=blk * nl * R, M=nl, K=svnum[i, f],
+                          rsA=svd_len, csA=1, rsB=R, csB=1, ldc=R)

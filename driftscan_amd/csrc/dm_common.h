@@ -71,6 +71,7 @@ enum { DM_PROF_GEMM = 0, DM_PROF_GEMM_REAL = 1, DM_PROF_JAC_GRAM = 2, DM_PROF_JA
        DM_PROF_UTIL = 17,        // transposes, copies, identities, regularisation / all-zero scans, Fisher helpers
        DM_PROF_EIG_OTHER = 18,   // T factors, slice sums, band extraction, eigenvector gathers
        DM_PROF_SVD_OTHER = 19,   // Jacobi engine helpers (norms, ranks, gathers, cleaning) and SVD chain assembly
+       DM_PROF_BLOCKVEC = 20,    // block-apply of product blocks to a few vectors (HBM-bound: algorithmic BYTES of A)
        DM_PROF_NCLASS = 24 };
 
 hipEvent_t dm_prof_event(dm_ctx* ctx);

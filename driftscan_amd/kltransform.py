@@ -14,7 +14,7 @@ import time
 import numpy as np
 
 from . import config, parallel, skymodel, storage, util
-from ._lib import block_offsets
+from ._lib import block_offsets, blockvec_table
 from .device import get_context
 
 logger = logging.getLogger(__name__)
@@ -457,6 +457,73 @@ class KLTransform(config.Reader):
 
         return _device_gemm(self.invmodes_m(mi, threshold), vec)
 
+    # ---- projections of a BATCH of m on the device (dm_blockvec_grouped) ------------------------------------------
+    def _read_modes(self, mi, threshold=None, inverse=False):
+        """(evals, matrix) of one m above `threshold` straight from its file, or (None, None) without modes: the
+        eigenvectors (nmodes, ndof), or with `inverse` the rows of `evinv` of those modes (nmodes, ndof) — its transpose is
+        what `invmodes_m` returns (from the pseudo-inverse of the modes if the file has no `evinv`)."""
+        if not os.path.exists(self._evfile % mi):
+            self.transform_save(mi)
+        with storage.File(self._evfile % mi, "r") as f:
+            if f["evals"].shape[0] == 0:
+                return None, None
+            evals = f["evals"][:]
+            startind = int(np.searchsorted(evals, threshold)) if threshold is not None else 0
+            if startind == evals.size:
+                return None, None
+            if inverse and "evinv" in f:
+                return evals[startind:], f["evinv"][startind:]
+            evecs = f["evecs"][startind:]
+        if self.olddatafile:
+            evecs = evecs.conj()
+        return evals[startind:], (np.ascontiguousarray(np.linalg.pinv(evecs).T) if inverse else evecs)
+
+    def project_vectors_svd_to_kl_device(self, ms, vecs, off=None, threshold=None, modes=None):
+        """Batch form of `project_vector_svd_to_kl`: vecs (rows, R) packed SVD vectors on the device, m number i at row
+        off[i] (default: back to back) -> (out, kloff): out (sum of modes, R), the modes of m number i from row kloff[i]
+        (none for an m without modes above the threshold).  The eigenvectors of the batch (`modes`: the matrices of
+        `_read_modes` per m, if the caller has read them already) are uploaded once."""
+        ctx = get_context()
+        R = int(vecs.shape[1])
+        ndofs = np.array([int(self.beamtransfer.ndof(mi)) for mi in ms], dtype=np.int64)
+        if off is None:
+            off = np.concatenate([[0], np.cumsum(ndofs)])
+        mats = [self._read_modes(mi, threshold)[1] for mi in ms] if modes is None else list(modes)
+        for n, e in zip(ndofs, mats):
+            if e is not None and e.shape[1] != n:
+                raise Exception("Vectors are incompatible.")
+        nmodes = np.array([0 if e is None else e.shape[0] for e in mats], dtype=np.int64)
+        tab, kloff = kl_forward_table(nmodes, ndofs, off, R)
+        out = ctx.zeros((max(int(kloff[-1]), 1), R), np.complex128)[: int(kloff[-1])]
+        if len(tab):
+            E = ctx.to_device(np.concatenate([np.asarray(e, dtype=np.complex128).reshape(-1) for e in mats if e is not None]))
+            ctx.blockvec_grouped(E, vecs.contiguous(), out, tab, R)
+        return out, kloff
+
+    def project_vectors_kl_to_svd_device(self, ms, vecs, kloff=None, threshold=None):
+        """Batch form of `project_vector_kl_to_svd`: vecs (rows, R) packed KL vectors on the device, m number i at row
+        kloff[i] (kloff has len(ms) + 1 entries; default: back to back) -> (out, off): out (sum of ndof, R) packed SVD
+        vectors, zero for an m without modes."""
+        ctx = get_context()
+        R = int(vecs.shape[1])
+        ndofs = np.array([int(self.beamtransfer.ndof(mi)) for mi in ms], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(ndofs)]).astype(np.int64)
+        mats = [self._read_modes(mi, threshold, inverse=True)[1] for mi in ms]
+        nmodes = np.array([0 if e is None else e.shape[0] for e in mats], dtype=np.int64)
+        if kloff is None:
+            kloff = np.concatenate([[0], np.cumsum(nmodes)])
+        given = np.diff(np.asarray(kloff, dtype=np.int64))
+        if np.any((given != 0) & (nmodes != 0) & (given != nmodes)):
+            raise Exception("Vectors are incompatible.")
+        nmodes = np.where(given == 0, 0, nmodes)   # an m given no mode contributes nothing, whatever the transform keeps
+        mats = [e if n else None for e, n in zip(mats, nmodes)]
+        tab = kl_backward_table(nmodes, ndofs, kloff, off, R)
+        out = ctx.zeros((max(int(off[-1]), 1), R), np.complex128)[: int(off[-1])]
+        if len(tab):
+            E = ctx.to_device(np.concatenate([np.asarray(e, dtype=np.complex128).reshape(-1) for e in mats if e is not None]))
+            ctx.blockvec_grouped(E, vecs.contiguous(), out, tab, R)
+        return out, off
+
     def skymodes_m(self, mi, threshold=None):
         """KL modes rotated onto the sky, [nmodes, nfreq, nsky] (kltransform.py:663-708; like the
         reference this assumes un-compressed modes of length nfreq * ntel)."""
@@ -486,3 +553,27 @@ class KLTransform(config.Reader):
 
     def project_matrix_sky_to_kl(self, mi, mat, threshold=None):
         return self.project_matrix_svd_to_kl(mi, self.beamtransfer.project_matrix_sky_to_svd(mi, mat), threshold)
+
+
+# ---- problem tables of the batched KL projections (plain numpy, see beamtransfer.svd_forward_table) ------------------------
+def kl_forward_table(nmodes, ndofs, off, R):
+    """Eigenvector blocks (nmodes[i], ndofs[i]) stored back to back, applied to packed SVD vectors (m number i at row
+    off[i]) into packed KL vectors.  Returns (table, kloff); an m without modes has no row."""
+    nmodes, ndofs, off = (np.asarray(a, dtype=np.int64) for a in (nmodes, ndofs, off))
+    eoff = np.concatenate([[0], np.cumsum(nmodes * ndofs)])
+    kloff = np.concatenate([[0], np.cumsum(nmodes)]).astype(np.int64)
+    i = np.nonzero((nmodes > 0) & (ndofs > 0))[0]
+    tab = blockvec_table(a0=eoff[i], x0=off[i] * R, y0=kloff[i] * R, M=nmodes[i], K=ndofs[i], rsA=ndofs[i], csA=1, rsB=R,
+                         csB=1, ldc=R)
+    return tab, kloff
+
+
+def kl_backward_table(nmodes, ndofs, kloff, off, R):
+    """Inverse-mode blocks stored back to back as the files hold them — (nmodes[i], ndofs[i]), the TRANSPOSE of the
+    operator, so memory runs along the OUTPUT dimension — applied to packed KL vectors (m number i at row kloff[i]) into
+    packed SVD vectors (at row off[i])."""
+    nmodes, ndofs, kloff, off = (np.asarray(a, dtype=np.int64) for a in (nmodes, ndofs, kloff, off))
+    eoff = np.concatenate([[0], np.cumsum(nmodes * ndofs)])
+    i = np.nonzero((nmodes > 0) & (ndofs > 0))[0]
+    return blockvec_table(a0=eoff[i], x0=kloff[i] * R, y0=off[i] * R, M=ndofs[i], K=nmodes[i],
+                          rsA=1, csA=ndofs[i], rsB=R, csB=1, ldc=R)

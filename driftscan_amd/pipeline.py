@@ -1,0 +1,188 @@
+"""PipelineManager: one YAML file that takes telescope timestreams to KL modes, power spectra and maps.
+
+The counterpart of ``drift.pipeline.pipeline.PipelineManager`` (drift/pipeline/pipeline.py:20-198), by behaviour: the same
+sections — ``config`` (the properties below), ``timestreams`` (entries with ``name``, ``directory``, optionally
+``output_directory`` and a ``simulate`` block of arguments for ``timestream.simulate`` plus its ``product_directory``)
+and optionally ``crosspower`` (entries with ``psname``, ``klname``, ``timestreams``, ``psfile``) — the same defaults,
+exceptions and methods.  Two deliberate differences:
+
+* ``timestreams`` and ``simulations`` belong to the instance.  The reference keeps them as class attributes, so every
+  PipelineManager of a process shares (and keeps adding to) one dictionary.
+* the cross-power block selects the power-spectrum estimator ``psname`` on its timestreams.  The reference passes
+  ``klname`` to ``set_psestimator`` there, which only works when the two names coincide.
+
+One knob of this package: ``batched`` (default True) runs the m-mode chain and the a_lm stage of the SVD / KL map-makers
+in device batches (``Timestream.generate_modes_batched``, ``mapmake_svd_batched``, ``mapmake_kl_batched``); False runs the
+per-m methods.  Both write the same files.
+
+    python -m driftscan_amd.pipeline params.yaml
+"""
+import argparse
+import logging
+import os
+
+import yaml
+
+from . import config, manager, timestream
+
+logger = logging.getLogger(__name__)
+
+
+def fixpath(path):
+    """`~`, environment variables and redundant separators resolved."""
+    return os.path.normpath(os.path.expandvars(os.path.expanduser(path)))
+
+
+class PipelineManager(config.Reader):
+    product_directory = config.Property(proptype=str, default="")
+
+    generate_modes = config.Property(proptype=bool, default=True)
+    generate_klmodes = config.Property(proptype=bool, default=True)
+    generate_powerspectra = config.Property(proptype=bool, default=True)
+    generate_maps = config.Property(proptype=bool, default=True)
+
+    no_m_zero = config.Property(proptype=bool, default=True)
+
+    klmodes = config.Property(proptype=list, default=[])
+    powerspectra = config.Property(proptype=list, default=[])
+    klmaps = config.Property(proptype=list, default=[])
+
+    nside = config.Property(proptype=int, default=128)
+    wiener = config.Property(proptype=bool, default=False)
+
+    collect_klmodes = config.Property(proptype=bool, default=True)
+
+    # device route of the m-mode chain and the map-makers (not in the reference)
+    batched = config.Property(proptype=bool, default=True)
+    chunk_gb = config.Property(proptype=float, default=4.0)
+
+    manager = None
+
+    def __init__(self):
+        self.timestreams = {}
+        self.simulations = {}
+        self.crosspower = []
+
+    @classmethod
+    def from_configfile(cls, configfile):
+        c = cls()
+        c.load_configfile(configfile)
+        return c
+
+    def load_configfile(self, configfile):
+        with open(configfile, "r") as f:
+            yconf = yaml.safe_load(f)
+        if not yconf or "config" not in yconf:
+            raise Exception("Configuration file must have an 'config' section.")
+        self.read_config(yconf["config"])
+        self.product_directory = fixpath(self.product_directory) if self.product_directory else self.product_directory
+        if "timestreams" not in yconf:
+            raise Exception("Configuration file must have an 'timestream' section.")
+        for tsconf in yconf["timestreams"]:
+            ts = timestream.Timestream(fixpath(tsconf["directory"]), self._products(self.product_directory))
+            if "output_directory" in tsconf:
+                ts.output_directory = fixpath(tsconf["output_directory"])
+            ts.no_m_zero = self.no_m_zero
+            self.timestreams[tsconf["name"]] = ts
+            if "simulate" in tsconf:
+                self.simulations[tsconf["name"]] = tsconf["simulate"]
+        if "crosspower" in yconf:
+            self.crosspower = list(yconf["crosspower"] or [])
+
+    def _products(self, directory):
+        """The ProductManager of a product directory (opened once per directory: its objects hold caches and device
+        buffers that the timestreams of one run can share)."""
+        cache = self.__dict__.setdefault("_product_cache", {})
+        key = fixpath(directory)
+        if key not in cache:
+            cache[key] = manager.ProductManager.from_config(key)
+        self.manager = cache[key] if self.manager is None else self.manager
+        return cache[key]
+
+    def simulate(self):
+        """Make the timestreams that carry a `simulate` block and do not exist yet."""
+        for tsname, simconf in self.simulations.items():
+            ts = self.timestreams[tsname]
+            if os.path.exists(ts._ffile(0)):
+                logger.info("Timestream %s exists already, not simulated again.", tsname)
+                continue
+            simconf = dict(simconf)
+            products = self._products(simconf.pop("product_directory", self.product_directory))
+            if "maps" in simconf:
+                simconf["maps"] = [fixpath(m) for m in simconf["maps"]]
+            timestream.simulate(products, ts.directory, **simconf)
+
+    def generate(self):
+        """Run the stages that are switched on, for every timestream, in the reference's order: m-modes and SVD modes, KL
+        modes (collected into one file per filter if `collect_klmodes`), power spectra and cross-power spectra, maps."""
+        for tsobj in self.timestreams.values():
+            os.makedirs(tsobj.output_directory, exist_ok=True)
+        if self.generate_modes:
+            for tsname, tsobj in self.timestreams.items():
+                logger.info("Generating modes (%s)", tsname)
+                if self.batched:
+                    # the KL filters ride along while the SVD vectors of a batch are on the device
+                    tsobj.generate_modes_batched(self.klmodes if self.generate_klmodes else (), chunk_gb=self.chunk_gb)
+                else:
+                    tsobj.generate_mmodes()
+                    tsobj.generate_mmodes_svd()
+        if self.generate_klmodes:
+            for tsname, tsobj in self.timestreams.items():
+                for klname in self.klmodes:
+                    logger.info("Generating KL filter (%s:%s)", tsname, klname)
+                    tsobj.set_kltransform(klname)
+                    if self.batched:
+                        tsobj.generate_modes_batched([(klname, tsobj.klthreshold)], chunk_gb=self.chunk_gb)
+                    else:
+                        tsobj.generate_mmodes_kl()
+                    if self.collect_klmodes:
+                        tsobj.collect_mmodes_kl()
+        if self.generate_powerspectra:
+            for tsname, tsobj in self.timestreams.items():
+                for ps in self.powerspectra:
+                    logger.info("Estimating powerspectra (%s:%s)", tsname, ps["psname"])
+                    tsobj.set_kltransform(ps["klname"])
+                    tsobj.set_psestimator(ps["psname"])
+                    tsobj.powerspectrum()
+            for xp in self.crosspower:
+                tslist = []
+                for tsname in xp["timestreams"]:
+                    tsobj = self.timestreams[tsname]
+                    tsobj.set_kltransform(xp["klname"])
+                    tsobj.set_psestimator(xp["psname"])
+                    tslist.append(tsobj)
+                timestream.cross_powerspectrum(tslist, xp["psname"], os.path.abspath(fixpath(xp["psfile"])))
+        if self.generate_maps:
+            for tsname, tsobj in self.timestreams.items():
+                for klname in self.klmaps:
+                    logger.info("Generating KL map (%s:%s)", tsname, klname)
+                    tsobj.set_kltransform(klname)
+                    if self.batched:
+                        tsobj.mapmake_kl_batched(self.nside, "map_%s.hdf5" % klname, wiener=self.wiener, chunk_gb=self.chunk_gb)
+                    else:
+                        tsobj.mapmake_kl(self.nside, "map_%s.hdf5" % klname, wiener=self.wiener)
+                logger.info("Generating SVD map (%s)", tsname)
+                if self.batched:
+                    tsobj.mapmake_svd_batched(self.nside, "map_svd.hdf5", chunk_gb=self.chunk_gb)
+                else:
+                    tsobj.mapmake_svd(self.nside, "map_svd.hdf5")
+                logger.info("Generating full map (%s)", tsname)
+                tsobj.mapmake_full(self.nside, "map_full.hdf5")
+
+    run = generate
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(prog="python -m driftscan_amd.pipeline",
+                                     description="Simulate the timestreams that ask for it, then run the pipeline.")
+    parser.add_argument("configfile", help="YAML file with `config` and `timestreams` sections")
+    args = parser.parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    pl = PipelineManager.from_configfile(args.configfile)
+    pl.simulate()
+    pl.generate()
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -11,10 +11,12 @@ MPI transposes: timestream files are per frequency and m-mode files per m, so a 
 """
 import os
 import pickle
+import time
 
 import numpy as np
 
 from . import healpix, parallel, storage, util
+from .device import get_context
 
 
 class Timestream(object):
@@ -126,6 +128,167 @@ class Timestream(object):
                 f.attrs["m"] = mi
         parallel.barrier()
 
+    # ---- the batched device route: the same files, one launch per stage and batch of m ----------------------------
+    def _generate_mmodes_device(self, chunk_gb):
+        """`generate_mmodes` with the time -> m transform on the device (`Context.mmode_transform`: a pruned DFT as two
+        strided-batched ZGEMMs against a twiddle table, written in the layout of the mode files); the regrouping across
+        ranks and the files are the per-m route's."""
+        marker = self.output_directory + "/mmodes/COMPLETED_M"
+        if os.path.exists(marker):
+            return {}
+        ctx = get_context()
+        tel = self.telescope
+        mmax, nfreq, ntime, npairs = tel.mmax, tel.nfreq, self.ntime, tel.npairs
+        nranks = parallel.size() if parallel._dist() else 1
+        all_m = list(range(mmax + 1))
+        m_of = [parallel.partition_for(all_m, r, nranks) for r in range(nranks)]
+        f_of = [parallel.partition_for(list(range(nfreq)), r, nranks) for r in range(nranks)]
+        me = parallel.rank() if parallel._dist() else 0
+        local_f = f_of[me]
+        pairs = np.zeros((mmax + 1, len(local_f), 2, npairs), dtype=np.complex128)
+        per_f = 16 * npairs * (ntime + 2 * (mmax + 1))
+        step = max(1, int(chunk_gb * (1 << 30) // max(per_f, 1)))
+        for c0 in range(0, len(local_f), step):
+            fs = local_f[c0 : c0 + step]
+            with self._timed("read"):
+                host = np.stack([np.asarray(self.timestream_f(fi), dtype=np.complex128) for fi in fs])
+            with self._timed("upload"):
+                X = ctx.to_device(host)
+            with self._timed("device"):
+                out = ctx.mmode_transform(X, mmax)
+            with self._timed("download"):
+                pairs[:, c0 : c0 + len(fs)] = ctx.to_host(out)
+            del X, out
+        got = parallel.exchange([np.ascontiguousarray(pairs[m_of[r]]) for r in range(nranks)])
+        mine = m_of[me]
+        if mine:
+            full = np.zeros((len(mine), nfreq, 2, npairs), dtype=np.complex128)
+            for src, part in enumerate(got):
+                if len(f_of[src]):
+                    full[:, f_of[src]] = part
+            with self._timed("write"):
+                for k, mi in enumerate(mine):
+                    os.makedirs(self._mdir(mi), exist_ok=True)
+                    with storage.File(self._mfile(mi), "w") as f:
+                        f.create_dataset("mmode", data=np.ascontiguousarray(full[k]))
+                        f.attrs["m"] = mi
+        parallel.barrier()
+        if parallel.rank0():
+            open(marker, "a").close()
+        parallel.barrier()
+        # what the files of this rank hold, for the SVD stage of the same call (same partition of m)
+        return {mi: full[k] for k, mi in enumerate(mine)} if mine else {}
+
+    # Opt-in log of the batched route: a dict set here collects wall seconds per kind of step ("read" product and data
+    # files, "upload", "device", "upload+device" for the KL stage, whose eigenvectors go up inside the call, "download",
+    # "write"), waiting for the device at every boundary.  None: no waits added.
+    mode_log = None
+
+    def _timed(self, what):
+        return _StepTimer(self.mode_log, what)
+
+    def _klfile_of(self, mi, klname, threshold):
+        return self._mdir(mi) + ("/klmode_%s_%f.hdf5" % (klname, threshold))
+
+    def _kl_entries(self, klnames):
+        """[(name, threshold)] of `klnames`: names (threshold of the transform) or (name, threshold) pairs."""
+        out = []
+        for entry in klnames:
+            name, thr = entry if isinstance(entry, (tuple, list)) else (entry, None)
+            out.append((name, self.manager.kltransforms[name].threshold if thr is None else thr))
+        return out
+
+    def _m_batches(self, ms, per_m_bytes, chunk_gb):
+        """`ms` cut into runs whose summed `per_m_bytes(mi)` stays within chunk_gb (at least one m per batch)."""
+        budget = chunk_gb * (1 << 30)
+        out, cur, used = [], [], 0.0
+        for mi in ms:
+            need = float(per_m_bytes(mi))
+            if cur and used + need > budget:
+                out.append(cur)
+                cur, used = [], 0.0
+            cur.append(mi)
+            used += need
+        if cur:
+            out.append(cur)
+        return out
+
+    @staticmethod
+    def _write_vector(fname, dset, vec, mi):
+        with storage.File(fname, "w") as f:
+            f.create_dataset(dset, data=vec)
+            f.attrs["m"] = mi
+
+    def generate_modes_batched(self, klnames=(), chunk_gb=4.0):
+        """`generate_mmodes`, `generate_mmodes_svd` and, for every entry of `klnames` (a name, or (name, threshold)),
+        `generate_mmodes_kl` in one pass: the same files with the same datasets, written where they do not exist yet.
+
+        The per-m methods take every (m, frequency) block through an upload, a launch and a wait of its own.  Here the
+        m of this rank go through the device in batches of at most `chunk_gb` of products: `beam_ut` of a batch is
+        uploaded once and applied to all its m-modes in ONE launch (`dm_blockvec_grouped`) into the packed `svbounds`
+        layout; per KL name the thresholded eigenvectors of the batch are uploaded and applied in one more launch to the
+        SVD vectors, which stay on the device in between.  Nothing stays resident after a batch."""
+        fresh = self._generate_mmodes_device(chunk_gb)
+        ctx = get_context()
+        bt, tel = self.beamtransfer, self.telescope
+        kls = self._kl_entries(klnames)
+        todo = [mi for mi in parallel.partition(list(range(tel.mmax + 1)))
+                if not os.path.exists(self._svdfile(mi))
+                or any(not os.path.exists(self._klfile_of(mi, n, t)) for n, t in kls)]
+
+        def per_m(mi):
+            nd = float(bt.ndof(mi))
+            return 16.0 * (tel.nfreq * bt.svd_len * bt.ntel + (nd * nd if kls else 0.0))
+
+        for batch in self._m_batches(todo, per_m, chunk_gb):
+            need = [mi for mi in batch if not os.path.exists(self._svdfile(mi))]
+            made = {}
+            if need:
+                with self._timed("read"):
+                    tm = np.stack([(fresh[mi] if mi in fresh else self.mmode(mi)).reshape(tel.nfreq, bt.ntel) for mi in need])
+                    but = bt._dev_stack(need, "beam_ut") if any(int(bt.ndof(mi)) for mi in need) else None
+                with self._timed("upload"):
+                    dtm = ctx.to_device(tm[..., None])
+                with self._timed("device"):
+                    out, off = bt.project_vectors_telescope_to_svd_device(need, dtm, products=but)
+                with self._timed("download"):
+                    host = ctx.to_host(out)[:, 0] if out.numel() else np.zeros((0,), dtype=np.complex128)
+                del out, but, dtm
+                with self._timed("write"):
+                    for i, mi in enumerate(need):
+                        made[mi] = host[off[i] : off[i + 1]].copy()
+                        self._write_vector(self._svdfile(mi), "mmode_svd", made[mi], mi)
+            svec = None
+            for name, thr in kls:
+                want = [mi for mi in batch if not os.path.exists(self._klfile_of(mi, name, thr))]
+                if not want:
+                    continue
+                if svec is None:   # the SVD vectors of the batch, packed, for every KL name
+                    with self._timed("read"):
+                        vecs = [made[mi] if mi in made else self.mmode_svd(mi) for mi in batch]
+                    voff = np.concatenate([[0], np.cumsum([v.shape[0] for v in vecs])]).astype(np.int64)
+                    with self._timed("upload"):
+                        svec = ctx.to_device(np.concatenate(vecs + [np.zeros((1,), dtype=np.complex128)])[:, None])
+                idx = [batch.index(mi) for mi in want]
+                ndofs = [int(bt.ndof(mi)) for mi in want]
+                for i, n in zip(idx, ndofs):
+                    if n != voff[i + 1] - voff[i]:
+                        raise Exception("Vectors are incompatible.")
+                kl = self.manager.kltransforms[name]
+                with self._timed("read"):
+                    modes = [kl._read_modes(mi, thr)[1] for mi in want]
+                with self._timed("upload+device"):   # (the eigenvectors go up inside the call)
+                    out, kloff = kl.project_vectors_svd_to_kl_device(want, svec, off=voff[idx], threshold=thr, modes=modes)
+                del modes
+                with self._timed("download"):
+                    host = ctx.to_host(out)[:, 0] if out.numel() else np.zeros((0,), dtype=np.complex128)
+                del out
+                with self._timed("write"):
+                    for i, mi in enumerate(want):
+                        self._write_vector(self._klfile_of(mi, name, thr), "mmode_kl", host[kloff[i] : kloff[i + 1]].copy(), mi)
+            del svec
+        parallel.barrier()
+
     # ---- map-making (timestream.py:237-300, :400-457) -----------------------------------------------------
     def _alm_to_map(self, make_alm, nside, mapname, mlist=None):
         tel = self.telescope
@@ -148,6 +311,91 @@ class Timestream(object):
     def mapmake_svd(self, nside, mapname):
         self.generate_mmodes_svd()
         self._alm_to_map(lambda mi: self.beamtransfer.project_vector_svd_to_sky(mi, self.mmode_svd(mi)), nside, mapname)
+
+    # ---- batched map-making: the a_lm stage of mapmake_svd / mapmake_kl in device batches ----------------------------
+    def _alm_batches(self, mlist, vectors, chunk_gb, extra_bytes=None):
+        """[(m, a_lm (nfreq, npol, lmax + 1))] for the m of this rank: `vectors(batch)` gives the packed SVD vectors of a
+        batch on the device (rows, 1) and their row offsets; `invbeam_svd` of the batch is uploaded once and applied in
+        one launch."""
+        ctx = get_context()
+        bt, tel = self.beamtransfer, self.telescope
+
+        def per_m(mi):
+            return 16.0 * tel.nfreq * tel.num_pol_sky * (tel.lmax + 1) * bt.svd_len + (extra_bytes(mi) if extra_bytes else 0.0)
+
+        out = []
+        for batch in self._m_batches(parallel.partition(mlist), per_m, chunk_gb):
+            svec, off = vectors(batch)
+            alm = ctx.to_host(bt.project_vectors_svd_to_sky_device(batch, svec, off=off))[..., 0]
+            out.extend((mi, np.ascontiguousarray(alm[i])) for i, mi in enumerate(batch))
+        return out
+
+    def _packed_device(self, vecs):
+        """Vectors of a batch back to back on the device as one column, and the row offsets of every m."""
+        off = np.concatenate([[0], np.cumsum([v.shape[0] for v in vecs])]).astype(np.int64)
+        packed = np.concatenate(list(vecs) + [np.zeros((1,), dtype=np.complex128)])   # (never empty)
+        return get_context().to_device(packed[:, None]), off
+
+    def alm_svd_batched(self, mlist=None, chunk_gb=4.0):
+        """The a_lm stage of `mapmake_svd` for this rank's share of `mlist`: [(m, (nfreq, npol, lmax + 1))]."""
+        mlist = list(range(self.telescope.mmax + 1)) if mlist is None else list(mlist)
+        return self._alm_batches(mlist, lambda batch: self._packed_device([self.mmode_svd(mi) for mi in batch]), chunk_gb)
+
+    def alm_kl_batched(self, mlist=None, wiener=False, chunk_gb=4.0):
+        """The a_lm stage of `mapmake_kl` for this rank's share of `mlist` (default: all m but m = 0 under `no_m_zero`):
+        KL modes, optionally Wiener weighted by lambda / (1 + lambda), through the stored inverse modes back to the SVD
+        basis and through `invbeam_svd` to the sky, without leaving the device in between."""
+        kl = self.manager.kltransforms[self.klname]
+        thr = self.klthreshold
+        bt = self.beamtransfer
+        if mlist is None:
+            mlist = list(range(1 if self.no_m_zero else 0, self.telescope.mmax + 1))
+
+        def vectors(batch):
+            modes = []
+            for mi in batch:
+                klmode = self.mmode_kl(mi)
+                if wiener and klmode.size:
+                    evals = kl.evals_m(mi, thr)
+                    if evals is not None:
+                        klmode = klmode * (evals / (1.0 + evals))
+                modes.append(klmode)
+            dev, kloff = self._packed_device(modes)
+            return kl.project_vectors_kl_to_svd_device(batch, dev, kloff=kloff, threshold=thr)
+
+        def extra(mi):
+            return 16.0 * float(bt.ndof(mi)) ** 2
+
+        return self._alm_batches(mlist, vectors, chunk_gb, extra_bytes=extra)
+
+    def _write_map(self, parts, nside, mapname):
+        tel = self.telescope
+        parts = parallel.gather_objects(parts)
+        if parallel.rank0():
+            alm = np.zeros((tel.nfreq, tel.num_pol_sky, tel.lmax + 1, tel.lmax + 1), dtype=np.complex128)
+            for part in parts:
+                for mi, a in part:
+                    alm[..., mi] = a
+            skymap = healpix.sphtrans_inv_sky(alm, nside)
+            with storage.File(self.output_directory + "/" + mapname, "w") as f:
+                f.create_dataset("map", data=skymap)
+        parallel.barrier()
+
+    def mapmake_svd_batched(self, nside, mapname, chunk_gb=4.0):
+        """`mapmake_svd` with its a_lm stage in device batches; returns at once if the map file exists."""
+        if os.path.exists(self.output_directory + "/" + mapname):
+            return
+        self.generate_modes_batched(chunk_gb=chunk_gb)
+        self._write_map(self.alm_svd_batched(chunk_gb=chunk_gb), nside, mapname)
+
+    def mapmake_kl_batched(self, nside, mapname, wiener=False, chunk_gb=4.0):
+        """`mapmake_kl` with its a_lm stage in device batches: leaves out m = 0 under `no_m_zero`, needs a KL transform
+        with `inverse`, returns at once if the map file exists."""
+        if os.path.exists(self.output_directory + "/" + mapname):
+            return
+        if not self.manager.kltransforms[self.klname].inverse:
+            raise Exception("Need the inverse to make a meaningful map.")
+        self._write_map(self.alm_kl_batched(wiener=wiener, chunk_gb=chunk_gb), nside, mapname)
 
     # ---- KL m-modes (timestream.py:306-396) ---------------------------------------------------------------
     def set_kltransform(self, klname, threshold=None):
@@ -290,6 +538,24 @@ class Timestream(object):
     def load(cls, tsdir):
         with open(cls(tsdir, tsdir)._picklefile, "rb") as f:
             return pickle.load(f)
+
+
+class _StepTimer(object):
+    """`with` block whose wall time (device idle at both ends) is added to log[what]; a no-op without a log."""
+
+    def __init__(self, log, what):
+        self.log, self.what = log, what
+
+    def __enter__(self):
+        if self.log is not None:
+            get_context().sync()
+            self.t0 = time.perf_counter()
+
+    def __exit__(self, *exc):
+        if self.log is not None:
+            get_context().sync()
+            self.log[self.what] = self.log.get(self.what, 0.0) + time.perf_counter() - self.t0
+        return False
 
 
 def _ps_mlist(mmax, no_m_zero):

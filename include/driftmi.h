@@ -64,7 +64,7 @@ int dm_prof_trd_stride(void);
  *   extended: 12 fused ring transform of BT-gen, 13 other BT-gen kernels, 14 LDS-resident small tridiagonalisation,
  *   15 divide & conquer (without its real GEMMs), 16 Cholesky panels + triangular diagonal solves, 17 transposes /
  *   copies / scans, 18 T factors / slice sums / gathers of the eigensolver, 19 Jacobi-engine and SVD-chain helpers,
- *   20-23 unused. */
+ *   20 block-apply of stored product blocks to vectors [algorithmic BYTES of A], 21-23 unused. */
 int dm_prof_reset(dm_ctx* ctx, int enable);
 int dm_prof_report(dm_ctx* ctx, double* ms, double* flops, long long* launches);
 
@@ -457,6 +457,23 @@ int dm_bt_alias_info(int nside, const double* ring_cth_host, const double* ring_
  * vendored with the reference; restated from its documented contract, see oracle/truncate.py). */
 int dm_bit_truncate_max_complex(dm_ctx* ctx, void* data_dev, int64_t nrows, int ncols, int64_t ld, double prec,
                                 double prec_max_row);
+
+/* ---- the data side: m-mode chain of a timestream ----------------------------------------------------- */
+/* dm_blockvec_grouped: y_p = alpha_p op(A_p) x_p for a ragged list of independent problems with FEW right-hand sides, one
+ * launch.  Problems are dm_zgemm_problem descriptors read as: A (M x K) through (rsA, csA) with optional conjA, B = x
+ * (K x N) through (rsB, csB) with optional conjB, C = y (M x N) row-major with leading dimension ldc; N = R is the same
+ * for all problems of a call, 1 <= R <= 8, and beta must be 0.  A problem with M = 0 or K = 0 is skipped: nothing is
+ * written.  Bound by the read of A (each element once, 16-byte loads along whichever of the two dimensions is
+ * contiguous); every output element is summed by one wave in an order fixed by (K, strides), so the result of a problem
+ * does not depend on the rest of the batch.  Returns when the work is queued on the context's stream.
+ * Replaces: the np.dot per (m, frequency[, polarisation]) of drift/core/beamtransfer.py:1233-1271, :1366-1421 and
+ * drift/core/kltransform.py:710-769 as drift/pipeline/timestream.py:191-231, :306-457 call them. */
+int dm_blockvec_grouped(dm_ctx* ctx, int nprob, const dm_zgemm_problem* probs_host);
+
+/* dm_mmode_twiddle: W[t, m] = exp(-2 pi i ((m t) mod ntime) / ntime) / ntime, t < ntime, m <= mmax, row-major
+ * (ntime, mmax + 1) c128 — the table of the pruned time -> m transform (a product with dm_zgemm_strided_batched).
+ * Replaces: np.fft.fft(timestream) / ntime at drift/pipeline/timestream.py:141-148. */
+int dm_mmode_twiddle(dm_ctx* ctx, int ntime, int mmax, void* W_dev);
 
 #ifdef __cplusplus
 }
