@@ -41,9 +41,6 @@ struct dm_ctx {
   std::vector<prof_rec> prof;
   std::vector<hipEvent_t> ev_pool;
   unsigned long long* prof_dev = nullptr;  // device flop counters, one per class
-  // eigensolver policy override of the caller in flight (-1: the library's policy; 0: one-stage tridiagonalisation only):
-  // set and restored around dm_herm_eig_tridiag by a caller that knows its batch (dm_jacobi_rows, `one_stage_eig`)
-  int trd_mode_override = -1;
 };
 
 // Event records are not free on a chain of thousands of short launches (each is a marker packet that breaks the
@@ -126,6 +123,13 @@ struct dm_prof_scope {
       (ctx)->err = std::string("bad argument: ") + #cond;         \
       return DM_EARG;                                             \
     }                                                             \
+  } while (0)
+
+// a 256-thread kernel of the SVD chain on the context's stream (time class "other"), its launch checked
+#define DM_SVD_LAUNCH(ctx_, kernel_, grid_, ...)                                                     \
+  do {                                                                                               \
+    DM_PLAUNCH(ctx_, DM_PROF_SVD_OTHER, kernel_, grid_, dim3(256), 0, (ctx_)->stream, __VA_ARGS__);  \
+    DM_HIP(ctx_, hipGetLastError());                                                                 \
   } while (0)
 
 #define DM_TRY(expr)            \

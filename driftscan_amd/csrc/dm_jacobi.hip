@@ -793,450 +793,471 @@ void plan_rounds(const std::vector<int>& nrows, F make_item, round_plan& plan) {
   }
 }
 
-}  // namespace
+// max off-diagonal |cos| per problem of the pass just queued: the kernels keep it as the bit pattern of a double
+int jac_read_off(dm_ctx* ctx, const unsigned long long* d_off, std::vector<double>& off) {
+  static_assert(sizeof(double) == sizeof(unsigned long long), "bit pattern of a double");
+  return dm_download(ctx, off.data(), d_off, sizeof(double) * off.size());
+}
 
-// ===========================================================================
-// one-sided driver
-// ===========================================================================
-int dm_jacobi_rows(dm_ctx* ctx, const std::vector<dm_jac_problem>& probs, double* sigma, int sigma_stride,
-                   int* sweeps_out, const dm_jac_rows_opts* opts) {
-  dm_jac_rows_opts O = opts ? *opts : dm_jac_rows_opts();
-  if (getenv("DM_JAC_MEASURE")) O.unconverged = false;   // debugging switches
-  if (getenv("DM_JAC_NO_DROP")) O.drop_below = 0.0;
-  const bool full_gram = getenv("DM_JAC_FULL_GRAM") != nullptr;
-  // DM_DEBUG: wall-clock of the phases of this call (synchronises at every mark)
-  const bool dbg_t = getenv("DM_DEBUG") != nullptr;
-  const bool dbg_sync = getenv("DM_DEBUG_NOSYNC") == nullptr;
-  auto dbg_now = [&]() { if (dbg_sync) (void)hipStreamSynchronize(ctx->stream); return std::chrono::steady_clock::now(); };
-  auto dbg_t0 = dbg_t ? dbg_now() : std::chrono::steady_clock::time_point();
-  auto dbg_mark = [&](const char* what) {
-    if (!dbg_t) return;
-    auto t1 = dbg_now();
-    fprintf(stderr, "[jacobi_rows]   %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - dbg_t0).count());
-    dbg_t0 = t1;
-  };
-  const int np = (int)probs.size();
-  if (sweeps_out) *sweeps_out = 0;
-  if (np == 0) return DM_OK;
-  DM_TRY(set_attrs(ctx));
-  dm_ws_scope ws_scope__(ctx);  // releases on every return path
-  const size_t mark = ws_scope__.mark;
+// the rows of a batch permuted by `key`: rank -> gather into tmp (and the keys into key_sorted) -> scatter back
+int jac_sort_rows(dm_ctx* ctx, int np, int maxrows, int maxcols, const jac_pdesc* pd, const int* nrows, const size_t* toff, int* rank,
+                   cplx* tmp, const double* key, int stride, double* key_sorted, bool descending) {
+  DM_SVD_LAUNCH(ctx, jac_rank_kernel, dim3((maxrows + 255) / 256, np), key, stride, nrows, rank, descending ? 1 : 0);
+  const int gx = std::max(1, std::min(8, (maxcols + 255) / 256));
+  DM_SVD_LAUNCH(ctx, jac_gather_rows_kernel, dim3(gx, maxrows, np), pd, rank, stride, tmp, toff, key, key_sorted);
+  DM_SVD_LAUNCH(ctx, jac_scatter_back_kernel, dim3(gx, maxrows, np), pd, tmp, toff);
+  return DM_OK;
+}
 
-  std::vector<int> nrows(np);
+// DM_DEBUG: wall-clock of the phases of a call (synchronises at every mark unless DM_DEBUG_NOSYNC is set)
+struct jac_stopwatch {
+  dm_ctx* ctx;
+  const bool on = getenv("DM_DEBUG") != nullptr, sync = getenv("DM_DEBUG_NOSYNC") == nullptr;
+  std::chrono::steady_clock::time_point t0;
+  explicit jac_stopwatch(dm_ctx* c) : ctx(c) { mark(nullptr); }
+  void mark(const char* what) {   // nullptr: start the clock only
+    if (!on) return;
+    if (sync) (void)hipStreamSynchronize(ctx->stream);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (what) fprintf(stderr, "[jacobi_rows]   %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+    t0 = t1;
+  }
+};
+
+constexpr double JAC_TOL_INNER = 1e-15;
+constexpr double JAC_E4 = 4.0 * 2.220446049250313e-16;   // 4 eps
+constexpr int JAC_MAX_SWEEPS = 40;
+constexpr int JAC_LEVELS = 4;               // levels of the preconditioner
+constexpr int JAC_LEVEL_MIN_ROWS = 2 * JP;  // a level of its own only for more rows than one pair of blocks
+enum { JAC_GRAM_FULL = 0, JAC_GRAM_CROSS = 1 };   // jac_gram_kernel: pair Gram in full | only the cross block of blocks known orthogonal
+
+// what the stages of dm_jacobi_rows share
+struct jac_rows_ws {
+  const std::vector<dm_jac_problem>& probs;
+  const dm_jac_rows_opts O;
+  const int stride, np;   // of the caller's sigma; problems
+  jac_stopwatch dbg;
   int maxrows = 0, maxcols = 0;
-  for (int p = 0; p < np; ++p) {
-    nrows[p] = probs[p].nrows;
-    maxrows = std::max(maxrows, nrows[p]);
-    maxcols = std::max(maxcols, probs[p].ncols);
-  }
-  DM_ARG(ctx, maxrows <= sigma_stride);
-  if (maxrows == 0) {  // nothing to orthogonalise anywhere (e.g. every row of every block was cut by the caller)
-    dm_ws_release(ctx, mark);
-    return DM_OK;
-  }
-
+  std::vector<int> nrows, nrows_eff;  // nrows_eff: rows that take part in the sweeps (all of them unless drop_below cuts the tail)
+  std::vector<int> flag0;             // one "rows mutually orthogonal" flag per 32-row block of every problem (jac_gram's CROSS mode)
   round_plan plan;
-  std::vector<int> nrows_eff(nrows);  // rows that take part in the sweeps (all of them unless drop_below cuts the tail)
-  // one "rows mutually orthogonal" flag per 32-row block of every problem (jac_gram's CROSS mode)
-  std::vector<int> flag0(np + 1, 0);
-  for (int p = 0; p < np; ++p) flag0[p + 1] = flag0[p] + (nrows[p] + JB - 1) / JB;
-  auto build_plan = [&]() {
-    plan_rounds(nrows_eff, [&](int p, int ba, int bb, int slot) {
-      const dm_jac_problem& P = probs[p];
-      jac_item it;
-      it.Z = P.Z; it.ld = P.ld;
-      it.ra = P.row0 + ba * JB; it.na = std::min(JB, nrows_eff[p] - ba * JB);
-      if (bb >= 0) { it.rb = P.row0 + bb * JB; it.nb = std::min(JB, nrows_eff[p] - bb * JB); }
-      else { it.rb = 0; it.nb = 0; }
-      it.c0 = 0; it.c1 = P.ncols; it.g0 = P.gc0; it.g1 = P.gc1;
-      it.prob = p; it.q = slot;
-      it.fa = flag0[p] + ba; it.fb = bb >= 0 ? flag0[p] + bb : it.fa;
-      return it;
-    }, plan);
-  };
-  build_plan();
+  std::vector<jac_pdesc> pd; std::vector<size_t> toff;
+  jac_item* d_items{}; jac_pdesc* d_pd{}; int* d_nrows{}; size_t* d_toff{}; int* d_active{}; unsigned long long* d_off{};
+  cplx *d_G{}, *d_Q{}, *d_tmp{}; int *d_skip{}, *d_rank{}, *d_ok{}; double *d_key{}, *d_floor{};
+  size_t nflags = 0;
+  std::vector<int> active;
+  std::vector<double> off;     // read-back of d_off
+  std::vector<char> placed;    // subspace mode: a level of the preconditioner placed the cut of this problem
+  double tol_outer = 0.0;
+  int nrounds = 0;
+  // the preconditioner's level loop
+  std::vector<size_t> goff;        // the Gram matrix / eigenvector block of each problem in Gm / Wm
+  cplx *Gm{}, *Wm{}; double* evp{};
+  std::vector<int> sub0, lev_on;   // first row of the current level's sub-block, per problem; problems with a level to do
+  std::vector<double> ev0;         // largest Gram eigenvalue of level 0 (sigma_1^2)
+  std::vector<dm_jac_herm_problem> hp;   // the eigenproblems of the level in flight, and whose they are
+  std::vector<int> who;
+  jac_rows_ws(dm_ctx* ctx, const std::vector<dm_jac_problem>& pr, const dm_jac_rows_opts* o, int stride_)
+      : probs(pr), O(o ? *o : dm_jac_rows_opts()), stride(stride_), np((int)pr.size()), dbg(ctx) {}
+};
 
-  std::vector<jac_pdesc> pd(np);
-  std::vector<size_t> toff(np);
+// ---- stage: the tournament of the rows that take part (w.nrows_eff)
+void jac_rows_plan(jac_rows_ws& w) {
+  plan_rounds(w.nrows_eff, [&w](int p, int ba, int bb, int slot) {
+    const dm_jac_problem& P = w.probs[p];
+    jac_item it;
+    it.Z = P.Z; it.ld = P.ld;
+    it.ra = P.row0 + ba * JB; it.na = std::min(JB, w.nrows_eff[p] - ba * JB);
+    if (bb >= 0) { it.rb = P.row0 + bb * JB; it.nb = std::min(JB, w.nrows_eff[p] - bb * JB); }
+    else { it.rb = 0; it.nb = 0; }
+    it.c0 = 0; it.c1 = P.ncols; it.g0 = P.gc0; it.g1 = P.gc1;
+    it.prob = p; it.q = slot;
+    it.fa = w.flag0[p] + ba; it.fb = bb >= 0 ? w.flag0[p] + bb : it.fa;
+    return it;
+  }, w.plan);
+  w.nrounds = (int)w.plan.round_begin.size() - 1;
+}
+
+// ---- stage: descriptors, buffers, row norms and the noise floor
+int jac_rows_setup(dm_ctx* ctx, jac_rows_ws& w) {
+  const auto& probs = w.probs;
+  w.nrows_eff = w.nrows;
+  w.flag0.assign(w.np + 1, 0);
+  for (int p = 0; p < w.np; ++p) w.flag0[p + 1] = w.flag0[p] + (w.nrows[p] + JB - 1) / JB;
+  jac_rows_plan(w);
+  w.pd.resize(w.np);
+  w.toff.resize(w.np);
   size_t ttot = 0;
-  for (int p = 0; p < np; ++p) {
-    pd[p] = jac_pdesc{probs[p].Z, probs[p].ld, probs[p].row0, probs[p].nrows, 0, probs[p].ncols, probs[p].gc0,
-                      probs[p].gc1};
-    toff[p] = ttot;
+  for (int p = 0; p < w.np; ++p) {
+    w.pd[p] = jac_pdesc{probs[p].Z, probs[p].ld, probs[p].row0, probs[p].nrows, 0, probs[p].ncols, probs[p].gc0, probs[p].gc1};
+    w.toff[p] = ttot;
     ttot += (size_t)probs[p].nrows * probs[p].ncols;
   }
 
-  jac_item* d_items = dm_ws_upload(ctx, plan.items);
-  jac_pdesc* d_pd = dm_ws_upload(ctx, pd);
-  int* d_nrows = dm_ws_upload(ctx, nrows);
-  size_t* d_toff = dm_ws_upload(ctx, toff);
-  std::vector<int> active(np, 1);
-  int* d_active = dm_ws_upload(ctx, active);
-  unsigned long long* d_off = dm_ws_alloc_t<unsigned long long>(ctx, np);
-  const size_t nslots = (size_t)std::max(plan.max_items_per_round, 1);
-  cplx* d_G = dm_ws_alloc_t<cplx>(ctx, nslots * JP * JP);
-  cplx* d_Q = dm_ws_alloc_t<cplx>(ctx, nslots * JP * JP);
-  int* d_skip = dm_ws_alloc_t<int>(ctx, nslots);
-  int* d_rank = dm_ws_alloc_t<int>(ctx, (size_t)np * sigma_stride);
-  double* d_key = dm_ws_alloc_t<double>(ctx, (size_t)np * sigma_stride);
-  cplx* d_tmp = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(ttot, 1));
-  double* d_floor = dm_ws_alloc_t<double>(ctx, np);
-  const size_t nflags = (size_t)std::max(flag0[np], 1);
-  int* d_ok = dm_ws_alloc_t<int>(ctx, nflags);
-  if (!d_items || !d_pd || !d_nrows || !d_toff || !d_active || !d_off || !d_G || !d_Q || !d_skip || !d_rank ||
-      !d_key || !d_tmp || !d_floor || !d_ok)
-    return DM_ENOMEM;
-  // DM_JAC_CROSS=0: every pair Gram in full (upper tiles), as before round 5
-  static const int allow_cross = getenv("DM_JAC_CROSS") ? atoi(getenv("DM_JAC_CROSS")) : 1;
-  DM_HIP(ctx, hipMemsetAsync(d_ok, 0, sizeof(int) * nflags, ctx->stream));
+  w.d_items = dm_ws_upload(ctx, w.plan.items);
+  w.d_pd = dm_ws_upload(ctx, w.pd);
+  w.d_nrows = dm_ws_upload(ctx, w.nrows);
+  w.d_toff = dm_ws_upload(ctx, w.toff);
+  w.active.assign(w.np, 1);
+  w.d_active = dm_ws_upload(ctx, w.active);
+  w.d_off = dm_ws_alloc_t<unsigned long long>(ctx, w.np);
+  const size_t nslots = (size_t)std::max(w.plan.max_items_per_round, 1);
+  w.d_G = dm_ws_alloc_t<cplx>(ctx, nslots * JP * JP);
+  w.d_Q = dm_ws_alloc_t<cplx>(ctx, nslots * JP * JP);
+  w.d_skip = dm_ws_alloc_t<int>(ctx, nslots);
+  w.d_rank = dm_ws_alloc_t<int>(ctx, (size_t)w.np * w.stride);
+  w.d_key = dm_ws_alloc_t<double>(ctx, (size_t)w.np * w.stride);
+  w.d_tmp = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(ttot, 1));
+  w.d_floor = dm_ws_alloc_t<double>(ctx, w.np);
+  w.nflags = (size_t)std::max(w.flag0[w.np], 1);
+  w.d_ok = dm_ws_alloc_t<int>(ctx, w.nflags);
+  if (!w.d_items || !w.d_pd || !w.d_nrows || !w.d_toff || !w.d_active || !w.d_off || !w.d_G || !w.d_Q || !w.d_skip || !w.d_rank ||
+      !w.d_key || !w.d_tmp || !w.d_floor || !w.d_ok) return DM_ENOMEM;
+  DM_HIP(ctx, hipMemsetAsync(w.d_ok, 0, sizeof(int) * w.nflags, ctx->stream));
 
   // noise floor for Gram entries: (4 eps)^2 * (largest row norm)^2.  Rows that are pure
   // rounding residue (rank-deficient inputs) can never be made mutually orthogonal to
   // relative accuracy — there are more of them than dimensions left — so pairs of such
   // rows are left alone, exactly the level at which LAPACK's backward error sits.
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_rownorm_kernel, dim3((maxrows + 3) / 4, np), dim3(256), 0, ctx->stream, d_pd, d_key,
-                     sigma_stride, maxrows);
-  {
-    const double e4 = 4.0 * 2.220446049250313e-16;
-    DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_floor_kernel, dim3(np), dim3(256), 0, ctx->stream, d_key, sigma_stride, d_nrows,
-                       d_floor, e4 * e4);
-  }
+  DM_SVD_LAUNCH(ctx, jac_rownorm_kernel, dim3((w.maxrows + 3) / 4, w.np), w.d_pd, w.d_key, w.stride, w.maxrows);
+  DM_SVD_LAUNCH(ctx, jac_floor_kernel, dim3(w.np), w.d_key, w.stride, w.d_nrows, w.d_floor, JAC_E4 * JAC_E4);
   // Rows count as orthogonal at |cos| <= K u, K the length of the inner products and u the unit roundoff —
   // the computed Gram entry of two exactly orthogonal rows is no smaller than that (LAPACK's zgesvj stops
   // at the same level, TOL = CTOL * EPS with CTOL = M) — but never looser than 1e-13 (K <= 900).
   int maxk = 0;
-  for (int p = 0; p < np; ++p) maxk = std::max(maxk, probs[p].gc1 - probs[p].gc0);
-  const double tol_outer = std::max(1e-13, maxk * 1.1102230246251565e-16), tol_inner = 1e-15;
-  int nrounds = (int)plan.round_begin.size() - 1;
-  std::vector<unsigned long long> h_off(np);
-  // Measuring pass (no rotations): problems whose rows are already orthogonal to tolerance — the
-  // pseudo-inverse pass of an unpolarised telescope sees exactly the rows the previous pass
-  // produced — skip the preconditioner and the sweeps.  (Re-diagonalising their Gram matrix would
-  // even hurt: it is only accurate to eps sigma_1^2 and disturbs the small rows.)
-  if (O.unconverged) {
-    for (int p = 0; p < np; ++p) active[p] = nrows[p] > 1 ? 1 : 0;
-    DM_TRY(dm_upload(ctx, d_active, active.data(), sizeof(int) * np));
-  } else {
-    DM_HIP(ctx, hipMemsetAsync(d_off, 0, sizeof(unsigned long long) * np, ctx->stream));
-    for (int r = 0; r < nrounds; ++r) {
-      const int nb = plan.round_begin[r], ni = plan.round_begin[r + 1] - nb;
-      if (ni == 0) continue;
-      hipLaunchKernelGGL(jac_gram_kernel, dim3(ni), dim3(256), 0, ctx->stream, d_items + nb, d_active, d_G,
-                         (const int*)d_ok, 0, (unsigned long long*)nullptr);
-      hipLaunchKernelGGL(jac_inner_kernel<false>, dim3(ni), dim3(JNT), INNER_LDS, ctx->stream, d_items + nb, d_active,
-                         (const double*)d_floor, d_G, d_Q, d_off, d_skip, tol_outer, tol_inner, 1, (int*)nullptr);
-    }
-    DM_HIP(ctx, hipGetLastError());
-    DM_TRY(dm_download(ctx, h_off.data(), d_off, sizeof(unsigned long long) * np));
-    for (int p = 0; p < np; ++p) {
-      double mo;
-      std::memcpy(&mo, &h_off[p], sizeof(double));
-      active[p] = (nrows[p] > 1 && mo > tol_outer) ? 1 : 0;
-    }
-    DM_TRY(dm_upload(ctx, d_active, active.data(), sizeof(int) * np));
-  }
-  dbg_mark("setup + measuring pass");
-  // Preconditioner: one Hermitian eigendecomposition of the full Gram matrix G = X X^H of every
-  // (still active) problem (batched tridiagonal solver) followed by Z <- W Z.  On its own this would only be
-  // accurate to eps ||X||^2 (the Gram squares the condition number), but it brings every pair of
-  // rows to |cos| <~ eps sigma_1^2 / (sigma_i sigma_j), from where the Jacobi sweeps below — which recompute
-  // the Gram blocks from the rows themselves and therefore keep full relative accuracy — converge
-  // in two or three sweeps instead of a dozen on the graded spectra of beam matrices.
-  // That bound says nothing about pairs with sigma_i sigma_j <~ eps sigma_1^2: the directions below
-  // ~1e-8 sigma_1 come out of the first level as an arbitrary mixture (a polarised beam block has several
-  // hundred of them, spread over 8 more decades: 30 sweeps).  So the preconditioner is applied again to
-  // just those rows — their own Gram matrix resolves another 8 decades relative to THEIR largest norm —
-  // and once more below that; each level costs a fraction of one sweep.
-  std::vector<char> placed(np, 0);   // subspace mode: a level of the preconditioner placed the cut of this problem
-  {
-    std::vector<size_t> goff(np);
-    size_t gtot = 0;
-    for (int p = 0; p < np; ++p) { goff[p] = gtot; gtot += (size_t)nrows[p] * nrows[p]; }
-    cplx* Gm = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(gtot, 1));
-    cplx* Wm = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(gtot, 1));
-    double* evp = dm_ws_alloc_t<double>(ctx, (size_t)np * sigma_stride);
-    if (!Gm || !Wm || !evp) return DM_ENOMEM;
-    std::vector<int> sub0(np, 0), lvl_on(active);  // first row of the current level's sub-block, per problem
-    std::vector<double> ev0(np, 0.0);              // largest Gram eigenvalue of level 0 (sigma_1^2)
-    std::vector<double> hev;
-    int max_levels = 4;
-    if (const char* e = getenv("DM_JAC_PRECOND_LEVELS")) max_levels = std::max(0, std::min(6, atoi(e)));
-    const bool clean = !getenv("DM_JAC_NO_CLEAN");
-    int level_min_rows = 2 * JP;
-    if (const char* e = getenv("DM_JAC_LEVEL_MIN_ROWS")) level_min_rows = std::max(1, atoi(e));
-    for (int level = 0; level < max_levels; ++level) {
-      if (level > 0 && clean) {
-        // The rows of this level still carry components along the rows above them (A) of absolute size
-        // ~eps sigma_1^2 / sigma_i — as large as the rows themselves.  Remove them BEFORE looking at the
-        // level's own Gram matrix, with the block rotation W = [[I - T^H T / 2, -T^H], [T, I - T T^H / 2]],
-        // T = -(B A^H) diag(||a_i||^-2): the rows of A are mutually orthogonal already, |T_ji| <= eps
-        // sigma_1^2 / sigma_i^2 <= 2e-7 by the choice of the level boundary, so W is unitary to ||T||^4.
-        std::vector<jac_clean_desc> cd;
-        std::vector<jac_pdesc> pa;
-        std::vector<dm_gemm_desc> gC, gP1, gP2, gA, gB;
-        int maxra = 0, maxrb = 0;
-        for (int p = 0; p < np; ++p) {
-          const dm_jac_problem& P = probs[p];
-          const int ra = sub0[p], rb = P.nrows - sub0[p];
-          if (!lvl_on[p] || ra < 1 || rb < 1) continue;
-          cplx* Arow = P.Z + (size_t)P.row0 * P.ld;
-          cplx* Brow = P.Z + (size_t)(P.row0 + ra) * P.ld;
-          cplx* th = Gm + goff[p];                         // rb x ra  (<= nrows^2 / 4)
-          cplx* t2 = d_tmp + toff[p];                      // P2: ra x ncols
-          cplx* t1 = t2 + (size_t)ra * P.ncols;            // P1: rb x ncols
-          cd.push_back(jac_clean_desc{P.Z, P.ld, P.row0, ra, rb, P.ncols, th, nullptr, t2});  // anorm set below
-          jac_pdesc d = pd[p];
-          d.nrows = ra;
-          pa.push_back(d);
-          gC.push_back(dm_gemm_make(Brow + P.gc0, P.ld, 1, false, Arow + P.gc0, 1, P.ld, true, th, ra, rb, ra,
-                                    P.gc1 - P.gc0));
-          gP1.push_back(dm_gemm_make(th, ra, 1, false, Arow, P.ld, 1, false, t1, P.ncols, rb, P.ncols, ra));
-          gP2.push_back(dm_gemm_make(th, 1, ra, true, Brow, P.ld, 1, false, t2, P.ncols, ra, P.ncols, rb));
-          gA.push_back(dm_gemm_make(th, 1, ra, true, t1, P.ncols, 1, false, Arow, P.ld, ra, P.ncols, rb, -1.0, 1.0));
-          gB.push_back(dm_gemm_make(th, ra, 1, false, t2, P.ncols, 1, false, Brow, P.ld, rb, P.ncols, ra, 1.0, 1.0));
-          maxra = std::max(maxra, ra);
-          maxrb = std::max(maxrb, rb);
-        }
-        if (!cd.empty()) {
-          // row norms of A: one output row per (compacted) descriptor
-          double* an = dm_ws_alloc_t<double>(ctx, cd.size() * (size_t)sigma_stride);
-          if (!an) return DM_ENOMEM;
-          for (size_t k = 0; k < cd.size(); ++k) cd[k].anorm = an + k * (size_t)sigma_stride;
-          jac_pdesc* d_pa = dm_ws_upload(ctx, pa);
-          jac_clean_desc* d_cd = dm_ws_upload(ctx, cd);
-          if (!d_pa || !d_cd) return DM_ENOMEM;
-          DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_rownorm_kernel, dim3((maxra + 3) / 4, (unsigned)pa.size()), dim3(256), 0, ctx->stream, d_pa,
-                             an, sigma_stride, maxra);
-          DM_TRY(dm_gemm_grouped_launch(ctx, gC));
-          DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_theta_kernel, dim3((maxra + 255) / 256, maxrb, (unsigned)cd.size()), dim3(256), 0,
-                             ctx->stream, d_cd);
-          DM_TRY(dm_gemm_grouped_launch(ctx, gP1));
-          DM_TRY(dm_gemm_grouped_launch(ctx, gP2));
-          const int gxm = std::max(1, std::min(8, (maxcols + 255) / 256));
-          DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_clean_mix_kernel, dim3(gxm, maxra + maxrb, (unsigned)cd.size()), dim3(256), 0, ctx->stream,
-                             d_cd);
-          DM_TRY(dm_gemm_grouped_launch(ctx, gA));
-          DM_TRY(dm_gemm_grouped_launch(ctx, gB));
-          DM_HIP(ctx, hipGetLastError());
-        }
-      }
-      std::vector<dm_gemm_desc> g;
-      std::vector<dm_jac_herm_problem> hp;
-      std::vector<int> who;
-      for (int p = 0; p < np; ++p) {
-        const dm_jac_problem& P = probs[p];
-        const int ns = P.nrows - sub0[p];
-        if (!lvl_on[p] || ns < 1) continue;
-        const cplx* X = P.Z + (size_t)(P.row0 + sub0[p]) * P.ld + P.gc0;
-        // the eigensolver reads the upper triangle only (LAPACK's uplo = 'U'): half of the Gram product
-        g.push_back(dm_gemm_make(X, P.ld, 1, false, X, 1, P.ld, true, Gm + goff[p], ns, ns, ns, P.gc1 - P.gc0, 1.0, 0.0,
-                                 nullptr, full_gram ? 0 : DM_GEMM_UPPER));
-        hp.push_back(dm_jac_herm_problem{Gm + goff[p], ns, Wm + goff[p], ns, ns});
-        who.push_back(p);
-      }
-      if (hp.empty()) break;
-      DM_TRY(dm_gemm_grouped_launch(ctx, g));
-      // evals land at consecutive strides of the *compacted* problem list
-      dbg_mark("level: cleaning + Gram");
-      {
-        const int keep_mode = ctx->trd_mode_override;
-        if (O.one_stage_eig) ctx->trd_mode_override = 0;
-        const int rc_eig = dm_herm_eig_tridiag(ctx, hp, evp, sigma_stride);
-        ctx->trd_mode_override = keep_mode;
-        DM_TRY(rc_eig);
-      }
-      dbg_mark("level: eigensolver");
-      std::vector<dm_jac_problem> sp;
-      for (auto& h : hp) sp.push_back(dm_jac_problem{h.W, h.ldw, 0, h.n, h.n, 0, 0});
-      DM_TRY(dm_sort_rows_by_key(ctx, sp, evp, sigma_stride, true));  // largest eigenvalue first
-      // Z <- W Z through the temporary, then back
-      std::vector<dm_gemm_desc> ga;
-      std::vector<jac_pdesc> pda;   // the scatter only touches the rows that were transformed
-      std::vector<size_t> toffa;
-      int subrows = 0;
-      for (size_t k = 0; k < who.size(); ++k) {
-        const int p = who[k];
-        const dm_jac_problem& P = probs[p];
-        const int ns = hp[k].n;
-        ga.push_back(dm_gemm_make(hp[k].W, ns, 1, false, P.Z + (size_t)(P.row0 + sub0[p]) * P.ld, P.ld, 1, false,
-                                  d_tmp + toff[p], P.ncols, ns, P.ncols, ns));
-        jac_pdesc d = pd[p];
-        d.row0 = P.row0 + sub0[p];
-        d.nrows = ns;
-        pda.push_back(d);
-        toffa.push_back(toff[p]);
-        subrows = std::max(subrows, ns);
-      }
-      DM_TRY(dm_gemm_grouped_launch(ctx, ga));
-      jac_pdesc* d_pda = dm_ws_upload(ctx, pda);
-      size_t* d_toffa = dm_ws_upload(ctx, toffa);
-      if (!d_pda || !d_toffa) return DM_ENOMEM;
-      const int gx0 = std::max(1, std::min(8, (maxcols + 255) / 256));
-      DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_scatter_back_kernel, dim3(gx0, subrows, (unsigned)pda.size()), dim3(256), 0, ctx->stream,
-                         d_pda, d_tmp, d_toffa);
-      DM_HIP(ctx, hipGetLastError());
-      dbg_mark("level: sort + W Z");
-      if (level + 1 == max_levels) break;
-      // next level: the rows whose Gram eigenvalue fell below 1e-9 of this level's largest (sigma below
-      // 3e-5 of it: a margin of three decades above what this level resolves, and the bound on the block
-      // rotation above), unless they already sit at the rounding floor of the whole matrix
-      hev.resize(who.size() * (size_t)sigma_stride);
-      DM_TRY(dm_download(ctx, hev.data(), evp, sizeof(double) * hev.size()));
-      bool more = false;
-      for (size_t k = 0; k < who.size(); ++k) {
-        const int p = who[k];
-        const double* ev = &hev[k * (size_t)sigma_stride];
-        const int ns = hp[k].n;
-        if (level == 0) ev0[p] = ev[0];
-        lvl_on[p] = 0;
-        if (!(ev[0] > 0.0)) continue;
-        int i = 0;
-        // (subspace mode: the level below begins at margin x cut of the largest row norm if that is higher than the
-        // regular boundary — the rows next to the cut then get a level of their own)
-        const double sm2 = O.subspace_cut > 0.0 ? O.subspace_margin * O.subspace_margin * O.subspace_cut * O.subspace_cut : 0.0;
-        const double bound = std::max(1e-9 * ev[0], level == 0 ? sm2 * ev[0] : 0.0);
-        while (i < ns && ev[i] >= bound) ++i;
-        const double e4 = 4.0 * 2.220446049250313e-16;
-        // worth a level only when the rows below span several row blocks: a sweep costs ~(row blocks)^2, and up
-        // to one pair of blocks the inner Jacobi solver sorts them out in LDS anyway (config 2: T = 92 rows)
-        // subspace mode: this level begins within margin x cut of the largest row norm — the cut is placed
-        if (O.subspace_cut > 0.0 && ev[0] <= sm2 * ev0[p] * (1.0 + 1e-9)) { placed[p] = 1; continue; }
-        if (ns - i <= level_min_rows || i == 0) continue;   // (subspace mode: not placed — the sweeps below do it)
-        if (bound <= e4 * e4 * ev0[p]) continue;  // what is left is rounding residue of the largest rows
-        if (O.drop_below > 0.0 && ev[i] <= O.drop_below * O.drop_below * ev0[p] * 1e-2) continue;  // nobody wants them
-        sub0[p] += i;
-        lvl_on[p] = 1;
-        more = true;
-      }
-      if (getenv("DM_DEBUG")) {
-        int cnt = 0, lo = 1 << 30, hi = 0;
-        for (int p = 0; p < np; ++p)
-          if (lvl_on[p]) { ++cnt; lo = std::min(lo, probs[p].nrows - sub0[p]); hi = std::max(hi, probs[p].nrows - sub0[p]); }
-        fprintf(stderr, "[jacobi_rows] preconditioner level %d done; %d problems go one level down (%d..%d rows)\n", level,
-                cnt, cnt ? lo : 0, hi);
-      }
-      if (!more) break;
-    }
-  }
-
-  dbg_mark("level: W Z + rest");
-  if (O.subspace_cut > 0.0) {
-    // the problems whose cut is placed are done: their rows are unitary mixtures of the input rows, split at the cut to
-    // the accuracy a converged SVD would give; the others (too few rows for a level of their own, level cap) are swept
-    bool ch = false;
-    for (int p = 0; p < np; ++p)
-      if (placed[p] && active[p]) { active[p] = 0; ch = true; }
-    if (ch) DM_TRY(dm_upload(ctx, d_active, active.data(), sizeof(int) * np));
-  }
-  if (O.drop_below > 0.0) {
-    // rows below the caller's level of interest leave the tournament (they sit at the end: the levels are
-    // ordered by scale and sorted inside)
-    DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_rownorm_kernel, dim3((maxrows + 3) / 4, np), dim3(256), 0, ctx->stream, d_pd, d_key,
-                       sigma_stride, maxrows);
-    std::vector<double> hk((size_t)np * sigma_stride);
-    DM_TRY(dm_download(ctx, hk.data(), d_key, sizeof(double) * hk.size()));
-    bool changed = false;
-    for (int p = 0; p < np; ++p) {
-      const double* kp = &hk[(size_t)p * sigma_stride];
-      double mx = 0.0;
-      for (int i = 0; i < nrows[p]; ++i) mx = std::max(mx, kp[i]);
-      int last = -1;
-      for (int i = 0; i < nrows[p]; ++i)
-        if (kp[i] >= O.drop_below * mx) last = i;
-      const int ne = std::max(std::min(nrows[p], 1), last + 1);
-      if (ne != nrows_eff[p]) { nrows_eff[p] = ne; changed = true; }
-    }
-    if (changed) {
-      build_plan();  // never more items per round than the plan the buffers were sized for
-      nrounds = (int)plan.round_begin.size() - 1;
-      d_items = dm_ws_upload(ctx, plan.items);
-      if (!d_items) return DM_ENOMEM;
-    }
-  }
-  const int chunks = (maxcols + APPLY_CHUNK - 1) / APPLY_CHUNK;
-  int sweep = 0;
-  const int max_sweeps = 40;
-  bool any_pairs = false;
-  for (int p = 0; p < np; ++p) any_pairs |= active[p] != 0;
-  for (; any_pairs && sweep < max_sweeps; ++sweep) {
-    DM_HIP(ctx, hipMemsetAsync(d_off, 0, sizeof(unsigned long long) * np, ctx->stream));
-    // every block's own Gram is measured from its rows the first time the block is met in a sweep
-    DM_HIP(ctx, hipMemsetAsync(d_ok, 0, sizeof(int) * nflags, ctx->stream));
-    for (int r = 0; r < nrounds; ++r) {
-      const int nb = plan.round_begin[r], ne = plan.round_begin[r + 1];
-      const int ni = ne - nb;
-      if (ni == 0) continue;
-      unsigned long long* fc = ctx->prof_on ? ctx->prof_dev : nullptr;
-      {
-        dm_prof_scope ps(ctx, DM_PROF_JAC_GRAM, 0.0);
-        hipLaunchKernelGGL(jac_gram_kernel, dim3(ni), dim3(256), 0, ctx->stream, d_items + nb, d_active, d_G,
-                           (const int*)d_ok, allow_cross, fc ? fc + DM_PROF_JAC_GRAM : nullptr);
-      }
-      {
-        dm_prof_scope ps(ctx, DM_PROF_JAC_INNER, 0.0);
-        hipLaunchKernelGGL(jac_inner_kernel<false>, dim3(ni), dim3(JNT), INNER_LDS, ctx->stream, d_items + nb,
-                           d_active, (const double*)d_floor, d_G, d_Q, d_off, d_skip, tol_outer, tol_inner, 0, d_ok);
-      }
-      {
-        dm_prof_scope ps(ctx, DM_PROF_JAC_APPLY, 0.0);
-        hipLaunchKernelGGL(jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, d_items + nb,
-                           d_active, d_skip, d_Q, fc ? fc + DM_PROF_JAC_APPLY : nullptr);
-      }
-    }
-    DM_HIP(ctx, hipGetLastError());
-    DM_TRY(dm_download(ctx, h_off.data(), d_off, sizeof(unsigned long long) * np));
-    bool any = false;
-    double dbg_max = 0.0;
-    for (int p = 0; p < np; ++p) {
-      double mo;
-      std::memcpy(&mo, &h_off[p], sizeof(double));
-      dbg_max = std::max(dbg_max, mo);
-      // A sweep that met nothing above 1e-9 leaves nothing above ~n 1e-18 behind (the rotations of a sweep
-      // disturb each other only to second order): the problem is done without a sweep that merely confirms it.
-      active[p] = (active[p] && mo > std::max(tol_outer, 1e-9)) ? 1 : 0;
-      any |= active[p] != 0;
-    }
-    if (getenv("DM_DEBUG")) {
-      int nact = 0, first = -1;
-      for (int p = 0; p < np; ++p) if (active[p]) { ++nact; if (first < 0) first = p; }
-      fprintf(stderr, "[jacobi_rows] sweep %d offmax %.3e active %d/%d first %d (rows %d gram %d-%d)\n", sweep, dbg_max,
-              nact, np, first, first >= 0 ? probs[first].nrows : 0, first >= 0 ? probs[first].gc0 : 0,
-              first >= 0 ? probs[first].gc1 : 0);
-    }
-    if (!any) { ++sweep; break; }
-    DM_TRY(dm_upload(ctx, d_active, active.data(), sizeof(int) * np));
-  }
-  if (sweeps_out) *sweeps_out = sweep;
-
-  dbg_mark("sweeps");
-  // sort rows by descending norm over the Gram columns
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_rownorm_kernel, dim3((maxrows + 3) / 4, np), dim3(256), 0, ctx->stream, d_pd, d_key,
-                     sigma_stride, maxrows);
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_rank_kernel, dim3((maxrows + 255) / 256, np), dim3(256), 0, ctx->stream, d_key,
-                     sigma_stride, d_nrows, d_rank, 1);
-  const int gx = std::max(1, std::min(8, (maxcols + 255) / 256));
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_gather_rows_kernel, dim3(gx, maxrows, np), dim3(256), 0, ctx->stream, d_pd, d_rank,
-                     sigma_stride, d_tmp, d_toff, d_key, sigma);
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_scatter_back_kernel, dim3(gx, maxrows, np), dim3(256), 0, ctx->stream, d_pd, d_tmp,
-                     d_toff);
-  DM_HIP(ctx, hipGetLastError());
-  DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  dbg_mark("final sort");
-  dm_ws_release(ctx, mark);
+  for (int p = 0; p < w.np; ++p) maxk = std::max(maxk, probs[p].gc1 - probs[p].gc0);
+  w.tol_outer = std::max(1e-13, maxk * 1.1102230246251565e-16);
+  w.off.resize(w.np);
   return DM_OK;
 }
 
-// ===========================================================================
+// ---- stage: measuring pass (no rotations): problems whose rows are already orthogonal to tolerance — the
+// pseudo-inverse pass of an unpolarised telescope sees exactly the rows the previous pass
+// produced — skip the preconditioner and the sweeps.  (Re-diagonalising their Gram matrix would
+// even hurt: it is only accurate to eps sigma_1^2 and disturbs the small rows.)
+int jac_rows_measure(dm_ctx* ctx, jac_rows_ws& w) {
+  if (!w.O.unconverged) {
+    DM_HIP(ctx, hipMemsetAsync(w.d_off, 0, sizeof(unsigned long long) * w.np, ctx->stream));
+    for (int r = 0; r < w.nrounds; ++r) {
+      const int nb = w.plan.round_begin[r], ni = w.plan.round_begin[r + 1] - nb;
+      if (ni == 0) continue;
+      hipLaunchKernelGGL(jac_gram_kernel, dim3(ni), dim3(256), 0, ctx->stream, w.d_items + nb, w.d_active, w.d_G,
+                         (const int*)w.d_ok, JAC_GRAM_FULL, (unsigned long long*)nullptr);
+      hipLaunchKernelGGL(jac_inner_kernel<false>, dim3(ni), dim3(JNT), INNER_LDS, ctx->stream, w.d_items + nb, w.d_active,
+                         (const double*)w.d_floor, w.d_G, w.d_Q, w.d_off, w.d_skip, w.tol_outer, JAC_TOL_INNER, 1, (int*)nullptr);
+    }
+    DM_HIP(ctx, hipGetLastError());
+    DM_TRY(jac_read_off(ctx, w.d_off, w.off));
+  }
+  for (int p = 0; p < w.np; ++p) w.active[p] = (w.nrows[p] > 1 && (w.O.unconverged || w.off[p] > w.tol_outer)) ? 1 : 0;
+  return dm_upload(ctx, w.d_active, w.active.data(), sizeof(int) * w.np);
+}
+
+// ---- level, part 1: cleaning against the rows above
+int jac_level_clean(dm_ctx* ctx, jac_rows_ws& w) {
+  // The rows of this level still carry components along the rows above them (A) of absolute size
+  // ~eps sigma_1^2 / sigma_i — as large as the rows themselves.  Remove them BEFORE looking at the
+  // level's own Gram matrix, with the block rotation W = [[I - T^H T / 2, -T^H], [T, I - T T^H / 2]],
+  // T = -(B A^H) diag(||a_i||^-2): the rows of A are mutually orthogonal already, |T_ji| <= eps
+  // sigma_1^2 / sigma_i^2 <= 2e-7 by the choice of the level boundary, so W is unitary to ||T||^4.
+  std::vector<jac_clean_desc> cd;
+  std::vector<jac_pdesc> pa;
+  std::vector<dm_gemm_desc> gC, gP1, gP2, gA, gB;
+  int maxra = 0, maxrb = 0;
+  for (int p = 0; p < w.np; ++p) {
+    const dm_jac_problem& P = w.probs[p];
+    const int ra = w.sub0[p], rb = P.nrows - w.sub0[p];
+    if (!w.lev_on[p] || ra < 1 || rb < 1) continue;
+    cplx* Arow = P.Z + (size_t)P.row0 * P.ld;
+    cplx* Brow = P.Z + (size_t)(P.row0 + ra) * P.ld;
+    cplx* th = w.Gm + w.goff[p];                   // rb x ra  (<= nrows^2 / 4)
+    cplx* t2 = w.d_tmp + w.toff[p];                  // P2: ra x ncols
+    cplx* t1 = t2 + (size_t)ra * P.ncols;            // P1: rb x ncols
+    cd.push_back(jac_clean_desc{P.Z, P.ld, P.row0, ra, rb, P.ncols, th, nullptr, t2});  // anorm set below
+    jac_pdesc d = w.pd[p];
+    d.nrows = ra;
+    pa.push_back(d);
+    gC.push_back(dm_gemm_make(Brow + P.gc0, P.ld, 1, false, Arow + P.gc0, 1, P.ld, true, th, ra, rb, ra, P.gc1 - P.gc0));
+    gP1.push_back(dm_gemm_make(th, ra, 1, false, Arow, P.ld, 1, false, t1, P.ncols, rb, P.ncols, ra));
+    gP2.push_back(dm_gemm_make(th, 1, ra, true, Brow, P.ld, 1, false, t2, P.ncols, ra, P.ncols, rb));
+    gA.push_back(dm_gemm_make(th, 1, ra, true, t1, P.ncols, 1, false, Arow, P.ld, ra, P.ncols, rb, -1.0, 1.0));
+    gB.push_back(dm_gemm_make(th, ra, 1, false, t2, P.ncols, 1, false, Brow, P.ld, rb, P.ncols, ra, 1.0, 1.0));
+    maxra = std::max(maxra, ra);
+    maxrb = std::max(maxrb, rb);
+  }
+  if (cd.empty()) return DM_OK;
+  // row norms of A: one output row per (compacted) descriptor
+  double* an = dm_ws_alloc_t<double>(ctx, cd.size() * (size_t)w.stride);
+  if (!an) return DM_ENOMEM;
+  for (size_t k = 0; k < cd.size(); ++k) cd[k].anorm = an + k * (size_t)w.stride;
+  jac_pdesc* d_pa = dm_ws_upload(ctx, pa);
+  jac_clean_desc* d_cd = dm_ws_upload(ctx, cd);
+  if (!d_pa || !d_cd) return DM_ENOMEM;
+  DM_SVD_LAUNCH(ctx, jac_rownorm_kernel, dim3((maxra + 3) / 4, (unsigned)pa.size()), d_pa, an, w.stride, maxra);
+  DM_TRY(dm_gemm_grouped_launch(ctx, gC));
+  DM_SVD_LAUNCH(ctx, jac_theta_kernel, dim3((maxra + 255) / 256, maxrb, (unsigned)cd.size()), d_cd);
+  DM_TRY(dm_gemm_grouped_launch(ctx, gP1));
+  DM_TRY(dm_gemm_grouped_launch(ctx, gP2));
+  const int gxm = std::max(1, std::min(8, (w.maxcols + 255) / 256));
+  DM_SVD_LAUNCH(ctx, jac_clean_mix_kernel, dim3(gxm, maxra + maxrb, (unsigned)cd.size()), d_cd);
+  DM_TRY(dm_gemm_grouped_launch(ctx, gA));
+  DM_TRY(dm_gemm_grouped_launch(ctx, gB));
+  DM_HIP(ctx, hipGetLastError());
+  return DM_OK;
+}
+
+// ---- level, part 2: Gram matrix of the level's rows, its eigenvectors W sorted by descending eigenvalue, Z <- W Z.
+// Leaves w.hp empty when no problem has a level to do.
+int jac_level_rotate(dm_ctx* ctx, jac_rows_ws& w) {
+  std::vector<dm_gemm_desc> g;
+  w.hp.clear();
+  w.who.clear();
+  for (int p = 0; p < w.np; ++p) {
+    const dm_jac_problem& P = w.probs[p];
+    const int ns = P.nrows - w.sub0[p];
+    if (!w.lev_on[p] || ns < 1) continue;
+    const cplx* X = P.Z + (size_t)(P.row0 + w.sub0[p]) * P.ld + P.gc0;
+    // the eigensolver reads the upper triangle only (LAPACK's uplo = 'U'): half of the Gram product
+    g.push_back(dm_gemm_make(X, P.ld, 1, false, X, 1, P.ld, true, w.Gm + w.goff[p], ns, ns, ns, P.gc1 - P.gc0, 1.0, 0.0,
+                             nullptr, DM_GEMM_UPPER));
+    w.hp.push_back(dm_jac_herm_problem{w.Gm + w.goff[p], ns, w.Wm + w.goff[p], ns, ns});
+    w.who.push_back(p);
+  }
+  if (w.hp.empty()) return DM_OK;
+  DM_TRY(dm_gemm_grouped_launch(ctx, g));
+  // evals land at consecutive strides of the *compacted* problem list
+  w.dbg.mark("level: cleaning + Gram");
+  DM_TRY(dm_herm_eig_tridiag(ctx, w.hp, w.evp, w.stride, nullptr, w.O.one_stage_eig ? 0 : -1));
+  w.dbg.mark("level: eigensolver");
+  std::vector<dm_jac_problem> sp;
+  for (auto& h : w.hp) sp.push_back(dm_jac_problem{h.W, h.ldw, 0, h.n, h.n, 0, 0});
+  DM_TRY(dm_sort_rows_by_key(ctx, sp, w.evp, w.stride, true));  // largest eigenvalue first
+  // Z <- W Z through the temporary, then back
+  std::vector<dm_gemm_desc> ga;
+  std::vector<jac_pdesc> pda;   // the scatter only touches the rows that were transformed
+  std::vector<size_t> toffa;
+  int subrows = 0;
+  for (size_t k = 0; k < w.who.size(); ++k) {
+    const int p = w.who[k];
+    const dm_jac_problem& P = w.probs[p];
+    const int ns = w.hp[k].n;
+    ga.push_back(dm_gemm_make(w.hp[k].W, ns, 1, false, P.Z + (size_t)(P.row0 + w.sub0[p]) * P.ld, P.ld, 1, false,
+                              w.d_tmp + w.toff[p], P.ncols, ns, P.ncols, ns));
+    jac_pdesc d = w.pd[p];
+    d.row0 = P.row0 + w.sub0[p];
+    d.nrows = ns;
+    pda.push_back(d);
+    toffa.push_back(w.toff[p]);
+    subrows = std::max(subrows, ns);
+  }
+  DM_TRY(dm_gemm_grouped_launch(ctx, ga));
+  jac_pdesc* d_pda = dm_ws_upload(ctx, pda);
+  size_t* d_toffa = dm_ws_upload(ctx, toffa);
+  if (!d_pda || !d_toffa) return DM_ENOMEM;
+  const int gx0 = std::max(1, std::min(8, (w.maxcols + 255) / 256));
+  DM_SVD_LAUNCH(ctx, jac_scatter_back_kernel, dim3(gx0, subrows, (unsigned)pda.size()), d_pda, w.d_tmp, d_toffa);
+  w.dbg.mark("level: sort + W Z");
+  return DM_OK;
+}
+
+// ---- level, part 3: the rows of the next level.  `more`: some problem goes one level down
+int jac_level_next(dm_ctx* ctx, jac_rows_ws& w, int level, bool& more) {
+  const dm_jac_rows_opts& O = w.O;
+  // next level: the rows whose Gram eigenvalue fell below 1e-9 of this level's largest (sigma below
+  // 3e-5 of it: a margin of three decades above what this level resolves, and the bound on the block
+  // rotation above), unless they already sit at the rounding floor of the whole matrix
+  std::vector<double> hev(w.who.size() * (size_t)w.stride);
+  DM_TRY(dm_download(ctx, hev.data(), w.evp, sizeof(double) * hev.size()));
+  more = false;
+  for (size_t k = 0; k < w.who.size(); ++k) {
+    const int p = w.who[k];
+    const double* ev = &hev[k * (size_t)w.stride];
+    const int ns = w.hp[k].n;
+    if (level == 0) w.ev0[p] = ev[0];
+    w.lev_on[p] = 0;
+    if (!(ev[0] > 0.0)) continue;
+    int i = 0;
+    // (subspace mode: the level below begins at margin x cut of the largest row norm if that is higher than the
+    // regular boundary — the rows next to the cut then get a level of their own)
+    const double sm2 = O.subspace_cut > 0.0 ? O.subspace_margin * O.subspace_margin * O.subspace_cut * O.subspace_cut : 0.0;
+    const double bound = std::max(1e-9 * ev[0], level == 0 ? sm2 * ev[0] : 0.0);
+    while (i < ns && ev[i] >= bound) ++i;
+    // worth a level only when the rows below span several row blocks: a sweep costs ~(row blocks)^2, and up
+    // to one pair of blocks the inner Jacobi solver sorts them out in LDS anyway (config 2: T = 92 rows)
+    // subspace mode: this level begins within margin x cut of the largest row norm — the cut is placed
+    if (O.subspace_cut > 0.0 && ev[0] <= sm2 * w.ev0[p] * (1.0 + 1e-9)) { w.placed[p] = 1; continue; }
+    if (ns - i <= JAC_LEVEL_MIN_ROWS || i == 0) continue;   // (subspace mode: not placed — the sweeps below do it)
+    if (bound <= JAC_E4 * JAC_E4 * w.ev0[p]) continue;  // what is left is rounding residue of the largest rows
+    if (O.drop_below > 0.0 && ev[i] <= O.drop_below * O.drop_below * w.ev0[p] * 1e-2) continue;  // nobody wants them
+    w.sub0[p] += i;
+    w.lev_on[p] = 1;
+    more = true;
+  }
+  if (w.dbg.on) {
+    int cnt = 0, lo = 1 << 30, hi = 0;
+    for (int p = 0; p < w.np; ++p)
+      if (w.lev_on[p]) { ++cnt; lo = std::min(lo, w.probs[p].nrows - w.sub0[p]); hi = std::max(hi, w.probs[p].nrows - w.sub0[p]); }
+    fprintf(stderr, "[jacobi_rows] preconditioner level %d done; %d problems go one level down (%d..%d rows)\n", level,
+            cnt, cnt ? lo : 0, hi);
+  }
+  return DM_OK;
+}
+
+// ---- stage: preconditioner.  One Hermitian eigendecomposition of the full Gram matrix G = X X^H of every
+// (still active) problem (batched tridiagonal solver) followed by Z <- W Z.  On its own this would only be
+// accurate to eps ||X||^2 (the Gram squares the condition number), but it brings every pair of
+// rows to |cos| <~ eps sigma_1^2 / (sigma_i sigma_j), from where the Jacobi sweeps below — which recompute
+// the Gram blocks from the rows themselves and therefore keep full relative accuracy — converge
+// in two or three sweeps instead of a dozen on the graded spectra of beam matrices.
+// That bound says nothing about pairs with sigma_i sigma_j <~ eps sigma_1^2: the directions below
+// ~1e-8 sigma_1 come out of the first level as an arbitrary mixture (a polarised beam block has several
+// hundred of them, spread over 8 more decades: 30 sweeps).  So the preconditioner is applied again to
+// just those rows — their own Gram matrix resolves another 8 decades relative to THEIR largest norm —
+// and once more below that; each level costs a fraction of one sweep.
+int jac_precondition(dm_ctx* ctx, jac_rows_ws& w) {
+  w.goff.resize(w.np);
+  size_t gtot = 0;
+  for (int p = 0; p < w.np; ++p) { w.goff[p] = gtot; gtot += (size_t)w.nrows[p] * w.nrows[p]; }
+  w.Gm = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(gtot, 1));
+  w.Wm = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(gtot, 1));
+  w.evp = dm_ws_alloc_t<double>(ctx, (size_t)w.np * w.stride);
+  if (!w.Gm || !w.Wm || !w.evp) return DM_ENOMEM;
+  w.sub0.assign(w.np, 0);
+  w.lev_on = w.active;
+  w.ev0.assign(w.np, 0.0);
+  for (int level = 0; level < JAC_LEVELS; ++level) {
+    if (level > 0) DM_TRY(jac_level_clean(ctx, w));
+    DM_TRY(jac_level_rotate(ctx, w));
+    if (w.hp.empty() || level + 1 == JAC_LEVELS) break;
+    bool more = false;
+    DM_TRY(jac_level_next(ctx, w, level, more));
+    if (!more) break;
+  }
+  return DM_OK;
+}
+
+// ---- stage: who stays out of the sweeps
+int jac_rows_retire(dm_ctx* ctx, jac_rows_ws& w) {
+  if (w.O.subspace_cut > 0.0) {
+    // the problems whose cut is placed are done: their rows are unitary mixtures of the input rows, split at the cut to
+    // the accuracy a converged SVD would give; the others (too few rows for a level of their own, level cap) are swept
+    bool ch = false;
+    for (int p = 0; p < w.np; ++p) if (w.placed[p] && w.active[p]) { w.active[p] = 0; ch = true; }
+    if (ch) DM_TRY(dm_upload(ctx, w.d_active, w.active.data(), sizeof(int) * w.np));
+  }
+  if (w.O.drop_below > 0.0) {
+    // rows below the caller's level of interest leave the tournament (they sit at the end: the levels are
+    // ordered by scale and sorted inside)
+    DM_SVD_LAUNCH(ctx, jac_rownorm_kernel, dim3((w.maxrows + 3) / 4, w.np), w.d_pd, w.d_key, w.stride, w.maxrows);
+    std::vector<double> hk((size_t)w.np * w.stride);
+    DM_TRY(dm_download(ctx, hk.data(), w.d_key, sizeof(double) * hk.size()));
+    bool changed = false;
+    for (int p = 0; p < w.np; ++p) {
+      const double* kp = &hk[(size_t)p * w.stride];
+      double mx = 0.0;
+      for (int i = 0; i < w.nrows[p]; ++i) mx = std::max(mx, kp[i]);
+      int last = -1;
+      for (int i = 0; i < w.nrows[p]; ++i) if (kp[i] >= w.O.drop_below * mx) last = i;
+      const int ne = std::max(std::min(w.nrows[p], 1), last + 1);
+      if (ne != w.nrows_eff[p]) { w.nrows_eff[p] = ne; changed = true; }
+    }
+    if (changed) {
+      jac_rows_plan(w);  // never more items per round than the plan the buffers were sized for
+      w.d_items = dm_ws_upload(ctx, w.plan.items);
+      if (!w.d_items) return DM_ENOMEM;
+    }
+  }
+  return DM_OK;
+}
+
+// ---- stage: the sweeps
+int jac_rows_sweep(dm_ctx* ctx, jac_rows_ws& w, int* sweeps_out) {
+  const auto& probs = w.probs;
+  const int chunks = (w.maxcols + APPLY_CHUNK - 1) / APPLY_CHUNK;
+  int sweep = 0;
+  bool any_pairs = false;
+  for (int p = 0; p < w.np; ++p) any_pairs |= w.active[p] != 0;
+  for (; any_pairs && sweep < JAC_MAX_SWEEPS; ++sweep) {
+    DM_HIP(ctx, hipMemsetAsync(w.d_off, 0, sizeof(unsigned long long) * w.np, ctx->stream));
+    // every block's own Gram is measured from its rows the first time the block is met in a sweep
+    DM_HIP(ctx, hipMemsetAsync(w.d_ok, 0, sizeof(int) * w.nflags, ctx->stream));
+    for (int r = 0; r < w.nrounds; ++r) {
+      const int nb = w.plan.round_begin[r], ni = w.plan.round_begin[r + 1] - nb;
+      if (ni == 0) continue;
+      unsigned long long* fc = ctx->prof_on ? ctx->prof_dev : nullptr;
+      DM_PLAUNCH(ctx, DM_PROF_JAC_GRAM, jac_gram_kernel, dim3(ni), dim3(256), 0, ctx->stream, w.d_items + nb, w.d_active, w.d_G,
+                 (const int*)w.d_ok, JAC_GRAM_CROSS, fc ? fc + DM_PROF_JAC_GRAM : nullptr);
+      DM_PLAUNCH(ctx, DM_PROF_JAC_INNER, jac_inner_kernel<false>, dim3(ni), dim3(JNT), INNER_LDS, ctx->stream, w.d_items + nb, w.d_active,
+                 (const double*)w.d_floor, w.d_G, w.d_Q, w.d_off, w.d_skip, w.tol_outer, JAC_TOL_INNER, 0, w.d_ok);
+      DM_PLAUNCH(ctx, DM_PROF_JAC_APPLY, jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, w.d_items + nb,
+                 w.d_active, w.d_skip, w.d_Q, fc ? fc + DM_PROF_JAC_APPLY : nullptr);
+    }
+    DM_HIP(ctx, hipGetLastError());
+    DM_TRY(jac_read_off(ctx, w.d_off, w.off));
+    bool any = false;
+    double dbg_max = 0.0;
+    for (int p = 0; p < w.np; ++p) {
+      dbg_max = std::max(dbg_max, w.off[p]);
+      // A sweep that met nothing above 1e-9 leaves nothing above ~n 1e-18 behind (the rotations of a sweep
+      // disturb each other only to second order): the problem is done without a sweep that merely confirms it.
+      w.active[p] = (w.active[p] && w.off[p] > std::max(w.tol_outer, 1e-9)) ? 1 : 0;
+      any |= w.active[p] != 0;
+    }
+    if (w.dbg.on) {
+      int nact = 0, first = -1;
+      for (int p = 0; p < w.np; ++p) if (w.active[p]) { ++nact; if (first < 0) first = p; }
+      fprintf(stderr, "[jacobi_rows] sweep %d offmax %.3e active %d/%d first %d (rows %d gram %d-%d)\n", sweep, dbg_max,
+              nact, w.np, first, first >= 0 ? probs[first].nrows : 0, first >= 0 ? probs[first].gc0 : 0, first >= 0 ? probs[first].gc1 : 0);
+    }
+    if (!any) { ++sweep; break; }
+    DM_TRY(dm_upload(ctx, w.d_active, w.active.data(), sizeof(int) * w.np));
+  }
+  if (sweeps_out) *sweeps_out = sweep;
+  return DM_OK;
+}
+
+}  // namespace
+
+// one-sided driver
+int dm_jacobi_rows(dm_ctx* ctx, const std::vector<dm_jac_problem>& probs, double* sigma, int sigma_stride,
+                   int* sweeps_out, const dm_jac_rows_opts* opts) {
+  jac_rows_ws w(ctx, probs, opts, sigma_stride);
+  if (sweeps_out) *sweeps_out = 0;
+  if (w.np == 0) return DM_OK;
+  DM_TRY(set_attrs(ctx));
+  dm_ws_scope ws_scope__(ctx);  // releases on every return path
+  w.nrows.resize(w.np);
+  for (int p = 0; p < w.np; ++p) {
+    w.nrows[p] = probs[p].nrows;
+    w.maxrows = std::max(w.maxrows, w.nrows[p]);
+    w.maxcols = std::max(w.maxcols, probs[p].ncols);
+  }
+  DM_ARG(ctx, w.maxrows <= w.stride);
+  if (w.maxrows == 0) return DM_OK;  // nothing to orthogonalise anywhere (e.g. every row of every block was cut by the caller)
+  w.placed.assign(w.np, 0);
+  DM_TRY(jac_rows_setup(ctx, w));
+  DM_TRY(jac_rows_measure(ctx, w));
+  w.dbg.mark("setup + measuring pass");
+  DM_TRY(jac_precondition(ctx, w));
+  w.dbg.mark("level: W Z + rest");
+  DM_TRY(jac_rows_retire(ctx, w));
+  DM_TRY(jac_rows_sweep(ctx, w, sweeps_out));
+  w.dbg.mark("sweeps");
+  // sort rows by descending norm over the Gram columns
+  DM_SVD_LAUNCH(ctx, jac_rownorm_kernel, dim3((w.maxrows + 3) / 4, w.np), w.d_pd, w.d_key, w.stride, w.maxrows);
+  DM_TRY(jac_sort_rows(ctx, w.np, w.maxrows, w.maxcols, w.d_pd, w.d_nrows, w.d_toff, w.d_rank, w.d_tmp, w.d_key, w.stride, sigma, true));
+  DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  w.dbg.mark("final sort");
+  return DM_OK;
+}
+
 // two-sided (Hermitian) driver
-// ===========================================================================
-int dm_jacobi_herm(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, double* evals, int evals_stride,
-                   int* sweeps_out) {
+int dm_jacobi_herm(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, double* evals, int evals_stride, int* sweeps_out) {
   const int np = (int)probs.size();
   if (sweeps_out) *sweeps_out = 0;
   if (np == 0) return DM_OK;
   DM_TRY(set_attrs(ctx));
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
-  const size_t mark = ws_scope__.mark;
 
   std::vector<int> nrows(np);
   int maxn = 0;
@@ -1295,25 +1316,23 @@ int dm_jacobi_herm(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, d
   const size_t nslots = (size_t)std::max(planC.max_items_per_round, 1);
   cplx* d_Q = dm_ws_alloc_t<cplx>(ctx, nslots * JP * JP);
   int* d_skip = dm_ws_alloc_t<int>(ctx, nslots);
-  if (!d_iC || !d_iT || !d_iW || !d_tdC || !d_tdT || !d_active || !d_off || !d_floor || !d_Q || !d_skip)
-    return DM_ENOMEM;
+  if (!d_iC || !d_iT || !d_iW || !d_tdC || !d_tdT || !d_active || !d_off || !d_floor || !d_Q || !d_skip) return DM_ENOMEM;
 
   // absolute rotation floor: 32 eps * max|C_ij| (a backward-stable solver cannot
   // resolve off-diagonals below this; kltransform's LAPACK path is no different)
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_absmax_kernel, dim3(np), dim3(256), 0, ctx->stream, d_tdC, d_floor,
-                     32.0 * 2.220446049250313e-16);
+  DM_SVD_LAUNCH(ctx, jac_absmax_kernel, dim3(np), d_tdC, d_floor, 32.0 * 2.220446049250313e-16);
 
   const double tol_outer = 1e-13, tol_inner = 1e-15;
+  const bool debug = getenv("DM_DEBUG") != nullptr;
   const int nrounds = (int)planC.round_begin.size() - 1;
   const int chunks = (maxn + APPLY_CHUNK - 1) / APPLY_CHUNK;
   const int tb = (maxn + 31) / 32;
-  std::vector<unsigned long long> h_off(np);
+  std::vector<double> off(np);
   int sweep = 0;
-  const int max_sweeps = 40;
   int cur = 0;  // 0: matrix lives in C, 1: in T
   bool any_pairs = false;
   for (int p = 0; p < np; ++p) any_pairs |= nrows[p] > 1;
-  for (; any_pairs && sweep < max_sweeps; ++sweep) {
+  for (; any_pairs && sweep < JAC_MAX_SWEEPS; ++sweep) {
     DM_HIP(ctx, hipMemsetAsync(d_off, 0, sizeof(unsigned long long) * np, ctx->stream));
     for (int r = 0; r < nrounds; ++r) {
       const int nb = planC.round_begin[r], ne = planC.round_begin[r + 1];
@@ -1322,45 +1341,31 @@ int dm_jacobi_herm(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, d
       jac_item* icur = (cur == 0 ? d_iC : d_iT) + nb;
       jac_item* ioth = (cur == 0 ? d_iT : d_iC) + nb;
       unsigned long long* fc = ctx->prof_on ? ctx->prof_dev + DM_PROF_JAC_APPLY : nullptr;
-      {
-        dm_prof_scope ps(ctx, DM_PROF_JAC_INNER, 0.0);
-        hipLaunchKernelGGL(jac_inner_kernel<true>, dim3(ni), dim3(JNT), INNER_LDS, ctx->stream, icur, d_active,
-                           d_floor, (const cplx*)nullptr, d_Q, d_off, d_skip, tol_outer, tol_inner, 0, (int*)nullptr);
-      }
-      {
-        dm_prof_scope ps(ctx, DM_PROF_JAC_APPLY, 0.0);
-        hipLaunchKernelGGL(jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, icur, d_active,
-                           d_skip, d_Q, fc);
-      }
-      {
-        dm_prof_scope ps(ctx, DM_PROF_JAC_APPLY, 0.0);
-        hipLaunchKernelGGL(jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, d_iW + nb,
-                           d_active, d_skip, d_Q, fc);
-      }
-      DM_PLAUNCH(ctx, DM_PROF_UTIL, jac_ctrans_kernel, dim3(tb, tb, np), dim3(256), 0, ctx->stream,
-                         cur == 0 ? d_tdC : d_tdT, d_active);
-      {
-        dm_prof_scope ps(ctx, DM_PROF_JAC_APPLY, 0.0);
-        hipLaunchKernelGGL(jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, ioth, d_active,
-                           d_skip, d_Q, fc);
-      }
+      DM_PLAUNCH(ctx, DM_PROF_JAC_INNER, jac_inner_kernel<true>, dim3(ni), dim3(JNT), INNER_LDS, ctx->stream, icur, d_active, d_floor,
+                 (const cplx*)nullptr, d_Q, d_off, d_skip, tol_outer, tol_inner, 0, (int*)nullptr);
+      DM_PLAUNCH(ctx, DM_PROF_JAC_APPLY, jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, icur, d_active, d_skip,
+                 d_Q, fc);
+      DM_PLAUNCH(ctx, DM_PROF_JAC_APPLY, jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, d_iW + nb, d_active,
+                 d_skip, d_Q, fc);
+      DM_PLAUNCH(ctx, DM_PROF_UTIL, jac_ctrans_kernel, dim3(tb, tb, np), dim3(256), 0, ctx->stream, cur == 0 ? d_tdC : d_tdT, d_active);
+      DM_PLAUNCH(ctx, DM_PROF_JAC_APPLY, jac_apply_kernel, dim3(ni, chunks), dim3(APPLY_NT), APPLY_LDS, ctx->stream, ioth, d_active, d_skip,
+                 d_Q, fc);
       cur ^= 1;
     }
     DM_HIP(ctx, hipGetLastError());
-    DM_TRY(dm_download(ctx, h_off.data(), d_off, sizeof(unsigned long long) * np));
+    DM_TRY(jac_read_off(ctx, d_off, off));
     bool any = false;
     std::vector<int> newly_done;
     double dbg_max = 0.0;
     for (int p = 0; p < np; ++p) {
-      double mo;
-      std::memcpy(&mo, &h_off[p], sizeof(double));
+      const double mo = off[p];
       dbg_max = std::max(dbg_max, mo);
       int was = active[p];
       active[p] = (was && mo > tol_outer) ? 1 : 0;
       any |= active[p] != 0;
       if (was && !active[p] && cur == 1) newly_done.push_back(p);
     }
-    if (getenv("DM_DEBUG")) fprintf(stderr, "[jacobi_herm] sweep %d offmax %.3e\n", sweep, dbg_max);
+    if (debug) fprintf(stderr, "[jacobi_herm] sweep %d offmax %.3e\n", sweep, dbg_max);
     // a problem that converged while its matrix lives in T: bring it home to C
     // (the transpose of a Hermitian matrix's conjugate is itself)
     if (!newly_done.empty()) {
@@ -1384,23 +1389,16 @@ int dm_jacobi_herm(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, d
     }
   }
   if (sweeps_out) *sweeps_out = sweep;
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_diag_kernel, dim3((maxn + 255) / 256, np), dim3(256), 0, ctx->stream, d_tdC, evals,
-                     evals_stride);
-  DM_HIP(ctx, hipGetLastError());
+  DM_SVD_LAUNCH(ctx, jac_diag_kernel, dim3((maxn + 255) / 256, np), d_tdC, evals, evals_stride);
   DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  dm_ws_release(ctx, mark);
   return DM_OK;
 }
 
-// ===========================================================================
 // sort the rows of a batch of matrices by a per-row key (device), stable
-// ===========================================================================
-int dm_sort_rows_by_key(dm_ctx* ctx, const std::vector<dm_jac_problem>& probs, double* key, int key_stride,
-                        bool descending) {
+int dm_sort_rows_by_key(dm_ctx* ctx, const std::vector<dm_jac_problem>& probs, double* key, int key_stride, bool descending) {
   const int np = (int)probs.size();
   if (np == 0) return DM_OK;
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
-  const size_t mark = ws_scope__.mark;
   std::vector<jac_pdesc> pd(np);
   std::vector<size_t> toff(np);
   std::vector<int> nrows(np);
@@ -1422,21 +1420,11 @@ int dm_sort_rows_by_key(dm_ctx* ctx, const std::vector<dm_jac_problem>& probs, d
   double* d_ks = dm_ws_alloc_t<double>(ctx, (size_t)np * key_stride);
   cplx* d_tmp = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(ttot, 1));
   if (!d_pd || !d_toff || !d_nrows || !d_rank || !d_ks || !d_tmp) return DM_ENOMEM;
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_rank_kernel, dim3((maxrows + 255) / 256, np), dim3(256), 0, ctx->stream, key, key_stride,
-                     d_nrows, d_rank, descending ? 1 : 0);
-  const int gx = std::max(1, std::min(8, (maxcols + 255) / 256));
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_gather_rows_kernel, dim3(gx, maxrows, np), dim3(256), 0, ctx->stream, d_pd, d_rank,
-                     key_stride, d_tmp, d_toff, key, d_ks);
-  DM_PLAUNCH(ctx, DM_PROF_SVD_OTHER, jac_scatter_back_kernel, dim3(gx, maxrows, np), dim3(256), 0, ctx->stream, d_pd, d_tmp, d_toff);
-  // sorted keys back into `key` (only the first nrows entries of each problem)
-  {
-    std::vector<dm_cdesc> cp;
-    for (int p = 0; p < np; ++p)
-      if (nrows[p] > 0)
-        cp.push_back(dm_cdesc{d_ks + (size_t)p * key_stride, key + (size_t)p * key_stride, sizeof(double) * nrows[p]});
-    DM_TRY(dm_copy_batched(ctx, cp));
-  }
+  DM_TRY(jac_sort_rows(ctx, np, maxrows, maxcols, d_pd, d_nrows, d_toff, d_rank, d_tmp, key, key_stride, d_ks, descending));
+  std::vector<dm_cdesc> cp;   // sorted keys back into `key` (only the first nrows entries of each problem)
+  for (int p = 0; p < np; ++p)
+    if (nrows[p] > 0) cp.push_back(dm_cdesc{d_ks + (size_t)p * key_stride, key + (size_t)p * key_stride, sizeof(double) * nrows[p]});
+  DM_TRY(dm_copy_batched(ctx, cp));
   DM_HIP(ctx, hipGetLastError());
-  dm_ws_release(ctx, mark);
   return DM_OK;
 }

@@ -178,12 +178,13 @@ int dm_jacobi_herm(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, d
 // (rows [0, nsel[p])); the back-transformation and everything downstream then cost nsel/n of the
 // full amount.  `evals` still receives ALL eigenvalues in natural order.  `pick` is called from several host threads
 // at once, each call with a different p: it may only touch state that belongs to problem p.
+// `two_stage`: 1 forces the two-stage tridiagonalisation, 0 forbids it, otherwise DM_TRD_TWOSTAGE, then the size policy.
 struct dm_eig_select {
   std::function<void(int p, const double* ev, int n, std::vector<int>& cols)> pick;
   std::vector<int> nsel;  // out
 };
 int dm_herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, double* evals, int evals_stride,
-                        dm_eig_select* sel = nullptr);
+                        dm_eig_select* sel = nullptr, int two_stage = -1);
 
 // Permute the rows [row0, row0+nrows) x [0, ncols) of each problem so that the
 // device keys (key_stride doubles per problem) end up sorted; keys are sorted too.

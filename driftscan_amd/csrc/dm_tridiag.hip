@@ -1446,7 +1446,7 @@ struct trd_policy {
                    // allows it)
 };
 
-// `mode` is DM_TRD_TWOSTAGE or ctx->trd_mode_override: 1 forces the two-stage reduction, 0 forbids it, anything else
+// `mode` is the caller's `two_stage` argument or, without one, DM_TRD_TWOSTAGE: 1 forces the two-stage reduction, 0 forbids it, anything else
 // leaves the choice to the measurements below.
 //
 // One stage: narrow panels up to n_max = 2048, wide ones above (see the panel width above).
@@ -1479,7 +1479,7 @@ trd_policy trd_policy_of(int maxn, int np, size_t totn, int mode) {
 }  // namespace
 
 int dm_herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, double* evals, int evals_stride,
-                        dm_eig_select* sel) {
+                        dm_eig_select* sel, int two_stage) {
   const trd_batch b(probs);
   if (getenv("DM_TRD_SIZES")) {  // debugging aid: the batch composition
     fprintf(stderr, "[dm_herm_eig_tridiag] %zu problems, n =", probs.size());
@@ -1492,7 +1492,7 @@ int dm_herm_eig_tridiag(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& pro
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
   if (b.maxn <= TSM) return herm_eig_small(ctx, b, evals, evals_stride, sel);
   const char* e = getenv("DM_TRD_TWOSTAGE");
-  const int mode = ctx->trd_mode_override >= 0 ? ctx->trd_mode_override : (e ? atoi(e) : -1);
+  const int mode = two_stage >= 0 ? two_stage : (e ? atoi(e) : -1);
   const trd_policy pol = trd_policy_of(b.maxn, b.np, b.totn, mode);
   return pol.width == 32 ? dm_trd32::herm_eig_tridiag(ctx, b, evals, evals_stride, sel, pol.two_stage)
                          : dm_trd64::herm_eig_tridiag(ctx, b, evals, evals_stride, sel, false);
