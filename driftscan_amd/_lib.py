@@ -93,6 +93,9 @@ SIGNATURES = {
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                 c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_i64), c_int, c_vp,
                 ctypes.POINTER(c_i64), c_int, c_vp, c_vp]),
+    "dm_sky_draw": (
+        c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_i64, ctypes.POINTER(c_int), ctypes.POINTER(c_i64), c_int, c_int,
+                c_int, ctypes.c_uint64, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64]),
     "dm_bt_beam_cyl": (
         c_int, [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int,
                 ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_dbl, c_vp]),
@@ -607,6 +610,30 @@ def _psmc_draw(self, ms, nmodes, R, seed, stream=0, kind=PSMC_NORMAL, power=0, s
     return out[: int(off[-1])]
 
 
+def _sky_draw(self, T, jglobal, rowoff, nfreq, row0, nrows, M, seed, stream, first, nreal, out, strides):
+    """Correlated a_lm draws of one group into `out` (c128 on the device, any shape): T (L, n, n) f64 roots on the
+    device, `rowoff` (n) the offset of every component in `out` and `strides` those of (realisation, l, m), all in complex
+    elements; see dm_sky_draw in include/driftmi.h.  Every element the call addresses must lie inside `out`."""
+    L, n = int(T.shape[0]), int(T.shape[1])
+    if tuple(T.shape) != (L, n, n) or T.is_complex() or not T.is_contiguous():
+        raise ValueError("sky_draw: need contiguous float64 roots (L, n, n), got %s" % (tuple(T.shape),))
+    if not (out.is_contiguous() and out.is_complex()):
+        raise ValueError("sky_draw: need a contiguous complex128 output")
+    jg, jgp = _iarr(jglobal)
+    ro, rop = _larr(rowoff)
+    sr, sl, sm = [int(x_) for x_ in strides]
+    if jg.shape != (n,) or ro.shape != (n,) or not 0 <= int(row0) <= int(row0) + int(nrows) <= n or not 1 <= int(M) <= L:
+        raise ValueError("sky_draw: tables, row range or M do not match the roots")
+    if nrows > 0 and nreal > 0:
+        rows = ro[int(row0) : int(row0) + int(nrows)]
+        last = int(rows.max()) + (int(nreal) - 1) * sr + (L - 1) * sl + (int(M) - 1) * sm
+        if int(rows.min()) < 0 or min(sr, sl, sm) < 0 or last >= out.numel():
+            raise ValueError("sky_draw: the call would write outside its output")
+    rc = self.lib.dm_sky_draw(self.h, n, L, int(M), self.ptr(T), n, n * n, jgp, rop, int(nfreq), int(row0), int(nrows),
+                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(first), int(nreal), self.ptr(out), sr, sl, sm)
+    self.check(rc, "dm_sky_draw")
+
+
 def _psmc_moments(self, q):
     """(mean (nblk, nq), covariance (nblk, nq, nq)) on the device of q (nblk, nq, ns) f64; see dm_psmc_moments."""
     nblk, nq, ns = [int(x_) for x_ in q.shape]
@@ -642,6 +669,7 @@ def _psmc_alt(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, eva
 Context.psmc_draw = _psmc_draw
 Context.psmc_moments = _psmc_moments
 Context.psmc_alt = _psmc_alt
+Context.sky_draw = _sky_draw
 
 
 def _project_diag(self, beam_ut, svnum, dmat, out, out_off, alpha=1.0, accumulate=False):

@@ -9,6 +9,7 @@
 // ranks.  Every reduction is a fixed-order sum (no atomics): two calls give bit-identical results.
 #include "dm_common.h"
 #include "dm_kernels.h"
+#include "dm_philox.h"
 #include "../../include/driftmi.h"
 
 #include <algorithm>
@@ -21,29 +22,6 @@ constexpr int BA_NJ = 4;          // 16-column MFMA sub-tiles per wave
 constexpr int BA_COLS = 4 * 16 * BA_NJ;   // real columns per workgroup: 256
 constexpr int BA_TILE = 4096;     // doubles of the staged table tile (32 KB of LDS)
 constexpr int BG_CHUNK = 2048;    // complex elements of (mode, sample) per band_gram partial sum
-
-// ---- Philox4x32-10 (Salmon et al., SC'11) ----------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-  }
-}
-
-// 53-bit uniform in (0, 1] from two words: ((a >> 5) 2^26 + (b >> 6) + 1) 2^-53, exact in double
-__device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
-  const uint64_t k = ((uint64_t)(a >> 5) << 26) | (uint64_t)(b >> 6);
-  return (double)(k + 1) * 0x1p-53;
-}
 
 struct draw_desc { const double* lam; cplx* x; int n; int m; };
 
@@ -66,12 +44,7 @@ __global__ __launch_bounds__(256) void psmc_draw_kernel(const draw_desc* __restr
       z.x = (c[0] >> 31) ? -sc : sc;
       z.y = 0.0;
     } else {
-      const double u1 = u53(c[0], c[1]), u2 = u53(c[2], c[3]);
-      const double rad = sqrt(-log(u1)) * sc;
-      double sn, cs;
-      sincos(6.283185307179586 * u2, &sn, &cs);
-      z.x = rad * cs;
-      z.y = rad * sn;
+      z = philox_normal(c, sc);
     }
     d.x[e] = z;
   }

@@ -124,26 +124,36 @@ def sphtrans_sky(skymap, lmax):
     return np.ascontiguousarray(h.conj().transpose(1, 2, 3, 0))
 
 
+def synth_chunk(nfreq, npol, L, M, nside, max_bytes):
+    """Frequencies per pass of `sphtrans_inv_sky`: ``max_bytes`` bounds the coefficients, maps and harmonic rings of one
+    pass on the device."""
+    per_f = npol * (16 * L * M + 8 * npix(nside) + 16 * (4 * nside - 1) * min(L, M))
+    return int(max(1, min(nfreq, max_bytes // per_f)))
+
+
 def sphtrans_inv_sky(alm, nside, max_bytes=4 << 30):
     """a_lm [freq, pol(T,E,B,V), l, m >= 0] -> real maps [freq, pol(T,Q,U,V), pixel] (cora.util.hputil.sphtrans_inv_sky).
     Runs on the GPU through dm_sht_synth, a chunk of frequencies at a time: ``max_bytes`` bounds the coefficients, maps
-    and harmonic rings of one chunk on the device.  Other numbers of polarisations than 1 or 4 take the host loop."""
-    alm = np.asarray(alm, dtype=np.complex128)
-    nfreq, npol, L, M = alm.shape
+    and harmonic rings of one chunk on the device.  Other numbers of polarisations than 1 or 4 take the host loop.
+    ``alm`` may be a complex128 tensor already on the device (`skysim.draw_alm(..., to_host=False)`)."""
+    on_device = bool(getattr(alm, "is_cuda", False))
+    if on_device and not (alm.is_complex() and alm.element_size() == 16):
+        raise ValueError("sphtrans_inv_sky: a device tensor must be complex128, got %s" % (alm.dtype,))
+    if not on_device:   # numpy, or a host tensor
+        alm = np.asarray(alm, dtype=np.complex128)
+    nfreq, npol, L, M = [int(x) for x in alm.shape]
     if npol not in (1, 4):
-        return sphtrans_inv_sky_host(alm, nside)
+        return sphtrans_inv_sky_host(alm.cpu().numpy() if on_device else alm, nside)
     from .device import get_context
 
     ctx = get_context()
     cth, sth = ring_trig(nside)
     npx = npix(nside)
-    nring = 4 * nside - 1
-    per_f = npol * (16 * L * M + 8 * npx + 16 * nring * min(L, M))
-    nf = int(max(1, min(nfreq, max_bytes // per_f)))
+    nf = synth_chunk(nfreq, npol, L, M, nside, max_bytes)
     out = np.empty((nfreq, npol, npx))
     for f0 in range(0, nfreq, nf):
         f1 = min(nfreq, f0 + nf)
-        a = ctx.to_device(alm[f0:f1])
+        a = alm[f0:f1].contiguous() if on_device else ctx.to_device(alm[f0:f1])
         maps = ctx.empty((f1 - f0, npol, npx), np.float64)
         ctx.sht_synth(nside, cth, sth, npol == 4, L - 1, M, f1 - f0, a, maps)
         ctx.torch.from_numpy(out[f0:f1]).copy_(maps)

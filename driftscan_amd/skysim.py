@@ -1,0 +1,212 @@
+"""Gaussian skies with the statistics of the model covariances C_l(nu, nu').
+
+The reference makes its simulated skies with ``cora.core.skysim.mkfullsky``; cora is not available, so this module draws
+them from the arrays every other stage works from: ``[pol, pol, l, freq, freq]`` as ``skymodel`` or
+``KLTransform.signal()`` / ``foreground()`` give them.  The definition:
+
+* the components i = (pol, freq) form one group per polarisation when every cross-polarisation block is zero, one joint
+  group otherwise; a polarisation whose block is zero has no group and zero coefficients;
+* per group and l, ``T_l`` is the symmetric positive semi-definite square root of ``C_l`` (eigenvalues clipped at 0);
+* ``a[r, f, p, l, m] = sum_j T_l[i, j] z_j`` with one Philox4x32-10 block per (component j, l, m, realisation r):
+  key = seed, counter ``(p F + f, (l << 16) | m, r, stream)``, complex with E|z|^2 = 1 for m > 0 and real with
+  E z^2 = 1 for m = 0; E and B are zero for l < 2 and everything is zero for m > l.
+
+``draw_alm`` does this on the device (``dm_sky_draw``: the draws are made inside the kernel and multiplied on the matrix
+cores); ``groups``, ``covariance_roots(device=False)``, ``draws_host`` and ``correlate_host`` restate it in numpy and need
+no GPU.
+"""
+import numpy as np
+
+STREAM_SKY_SIGNAL = 16       # clear of psmc.STREAM_X, STREAM_X2, STREAM_ALT = 0, 1, 2
+STREAM_SKY_FOREGROUND = 17
+LMAX_LIMIT = 65536           # m and l share one 32-bit counter word
+
+
+def _check_cv(cv):
+    cv = np.asarray(cv, dtype=np.float64)
+    if cv.ndim != 5 or cv.shape[0] != cv.shape[1] or cv.shape[3] != cv.shape[4]:
+        raise ValueError("need a covariance [pol, pol, l, freq, freq], got shape %s" % (cv.shape,))
+    if cv.shape[2] - 1 >= LMAX_LIMIT:
+        raise ValueError("lmax = %d is beyond the %d the draw counters can address" % (cv.shape[2] - 1, LMAX_LIMIT - 1))
+    return cv
+
+
+def groups(cv):
+    """The groups of jointly drawn components: a list of int arrays of ``j_global = pol * nfreq + freq``."""
+    cv = _check_cv(cv)
+    npol, nfreq = cv.shape[0], cv.shape[3]
+    cross = any(cv[p, q].any() for p in range(npol) for q in range(npol) if p != q)
+    if cross:
+        return [np.arange(npol * nfreq, dtype=np.int64)]
+    return [p * nfreq + np.arange(nfreq, dtype=np.int64) for p in range(npol) if cv[p, p].any()]
+
+
+def group_covariance(cv, jglobal):
+    """(L, n, n) covariance of one group: C[l, (p, f), (q, f')] = cv[p, q, l, f, f']."""
+    cv = _check_cv(cv)
+    nfreq = cv.shape[3]
+    p, f = np.asarray(jglobal) // nfreq, np.asarray(jglobal) % nfreq
+    return np.ascontiguousarray(cv[p[:, None], p[None, :], :, f[:, None], f[None, :]].transpose(2, 0, 1))
+
+
+def covariance_roots(cv, device=True):
+    """Per group of ``groups(cv)``, the symmetric roots T (L, n, n) with T_l T_l = C_l.
+
+    device=True: float64 tensors on the GPU, from one batched Hermitian eigendecomposition per group
+    (``Context.herm_eig``) and V sqrt(max(lambda, 0)) V^H by the batched ZGEMM.  device=False: numpy arrays from
+    ``numpy.linalg.eigh``, the oracle of the tests."""
+    cv = _check_cv(cv)
+    out = []
+    if not device:
+        for jg in groups(cv):
+            ev, V = np.linalg.eigh(group_covariance(cv, jg))
+            T = np.einsum("lik,lk,ljk->lij", V, np.sqrt(np.maximum(ev, 0.0)), V)
+            out.append(0.5 * (T + T.transpose(0, 2, 1)))
+        return out
+    from .device import get_context
+
+    ctx = get_context()
+    for jg in groups(cv):
+        C = group_covariance(cv, jg)
+        L, n = C.shape[0], C.shape[1]
+        Cd = ctx.to_device(C.astype(np.complex128))
+        ev, W = ctx.herm_eig(Cd, n, n, strideC=n * n, batch=L)      # C = W^H diag(ev) W
+        s = ctx.torch.sqrt(ctx.torch.clamp(ev, min=0.0)).contiguous()
+        T = ctx.empty((L, n, n), np.complex128)
+        ctx.zgemm(W, W, T, n, n, n, 1, n, n, 1, n, conjA=True, kscale=s, batch=L, strideA=n * n, strideB=n * n,
+                  strideC=n * n, stride_kscale=n)
+        out.append(T.real.contiguous())
+        del Cd, W, T
+    return out
+
+
+# ---- numpy restatement of the draws and of the product ----------------------------------------------------------------
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _philox4x32_10(ctr, key):
+    c = [np.asarray(x, dtype=np.uint64) & _M32 for x in ctr]
+    k0, k1 = np.uint64(key[0]), np.uint64(key[1])
+    for r in range(10):
+        if r:
+            k0 = (k0 + np.uint64(0x9E3779B9)) & _M32
+            k1 = (k1 + np.uint64(0xBB67AE85)) & _M32
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & _M32]
+    return c
+
+
+def _u53(a, b):
+    k = ((a >> np.uint64(5)) << np.uint64(26)) | (b >> np.uint64(6))
+    return (k + np.uint64(1)).astype(np.float64) * 2.0**-53
+
+
+def draws_host(jglobal, L, M=None, nreal=1, seed=0, stream=STREAM_SKY_SIGNAL, first=0):
+    """The unit draws z [nreal, n, L, M] of the components ``jglobal`` in numpy (zero for m > l)."""
+    M = L if M is None else int(M)
+    if L - 1 >= LMAX_LIMIT:
+        raise ValueError("lmax beyond the draw counters")
+    jg = np.asarray(jglobal, dtype=np.uint64)
+    r, j, l, m = np.meshgrid(np.arange(first, first + nreal, dtype=np.uint64), jg, np.arange(L, dtype=np.uint64),
+                             np.arange(M, dtype=np.uint64), indexing="ij")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = _philox4x32_10([j, (l << np.uint64(16)) | m, r, np.full_like(j, stream)], (seed & 0xFFFFFFFF, seed >> 32))
+    rad = np.sqrt(-np.log(_u53(w[0], w[1])))
+    th = 6.283185307179586 * _u53(w[2], w[3])
+    z = rad * np.cos(th) + 1j * (rad * np.sin(th))
+    z = np.where(m == 0, 1.4142135623730951 * z.real, z)
+    return np.where(m <= l, z, 0.0)
+
+
+def correlate_host(T, z):
+    """a[..., i, l, m] = sum_j T[l, i, j] z[..., j, l, m] summed in numpy.longdouble (returned as clongdouble):
+    T (L, n, n), z [..., n, L, M]."""
+    T = np.asarray(T, dtype=np.longdouble)
+    z = np.asarray(z)
+    re = np.einsum("lij,...jlm->...ilm", T, z.real.astype(np.longdouble))
+    im = np.einsum("lij,...jlm->...ilm", T, z.imag.astype(np.longdouble))
+    return re + 1j * im
+
+
+# ---- the device path ---------------------------------------------------------------------------------------------------
+def _runs(idx):
+    """Sorted integers as [(start, count)] of consecutive runs."""
+    out = []
+    for i in idx:
+        if out and out[-1][0] + out[-1][1] == i:
+            out[-1][1] += 1
+        else:
+            out.append([int(i), 1])
+    return out
+
+
+def draw_alm(cv, nreal=1, seed=0, stream=STREAM_SKY_SIGNAL, first=0, mmax=None, freqs=None, to_host=True, roots=None):
+    """Realisations ``first .. first + nreal - 1`` of the sky of covariance ``cv``: a_lm [nreal, nfreq_sel, npol, L, M]
+    complex128, M = min(mmax, lmax) + 1 (all m by default).
+
+    ``freqs`` (sorted frequency indices) computes only those rows, from the same draws as the full call: a rank of a
+    distributed simulation gets its share without communication.  ``roots`` takes ``covariance_roots(cv)`` made
+    earlier.  ``to_host=False`` returns the device tensor."""
+    cv = _check_cv(cv)
+    from .device import get_context
+
+    ctx = get_context()
+    npol, L, nfreq = cv.shape[0], cv.shape[2], cv.shape[3]
+    M = L if mmax is None else min(int(mmax) + 1, L)
+    sel = list(range(nfreq)) if freqs is None else [int(f) for f in freqs]
+    if sorted(set(sel)) != sel or (sel and not 0 <= sel[0] <= sel[-1] < nfreq):
+        raise ValueError("freqs must be sorted, distinct frequency indices")
+    pos = {f: k for k, f in enumerate(sel)}
+    nsel = len(sel)
+    grp = groups(cv)
+    roots = covariance_roots(cv) if roots is None else roots
+    out = ctx.empty((int(nreal), nsel, npol, L, M), np.complex128)
+    if out.numel() == 0:
+        return np.zeros(tuple(out.shape), dtype=np.complex128) if to_host else out
+    drawn = set()
+    for jg, T in zip(grp, roots):
+        p, f = jg // nfreq, jg % nfreq
+        drawn.update(int(x) for x in p)
+        rowoff = np.array([(pos.get(int(fi), 0) * npol + int(pi)) * L * M for pi, fi in zip(p, f)], dtype=np.int64)
+        for row0, nrows in _runs([i for i in range(len(jg)) if int(f[i]) in pos]):
+            ctx.sky_draw(T, jg, rowoff, nfreq, row0, nrows, M, seed, stream, first, nreal, out,
+                         (nsel * npol * L * M, M, 1))
+    for pi in range(npol):   # polarisations without power
+        if pi not in drawn:
+            out[:, :, pi].zero_()
+    return ctx.to_host(out) if to_host else out
+
+
+def gaussian_sky(cv, nside, nreal=1, seed=0, stream=STREAM_SKY_SIGNAL, first=0, mmax=None, freqs=None,
+                 max_bytes=4 << 30):
+    """``draw_alm`` followed by ``healpix.sphtrans_inv_sky``: real maps [nreal, freq, pol, pixel].  The coefficients stay
+    on the device; a pass is one realisation of as many frequencies as ``max_bytes`` allows the synthesis."""
+    from . import healpix
+
+    cv = _check_cv(cv)
+    npol, L, nfreq = cv.shape[0], cv.shape[2], cv.shape[3]
+    if npol not in (1, 4):
+        raise ValueError("gaussian_sky: 1 or 4 polarisations")
+    sel = list(range(nfreq)) if freqs is None else [int(f) for f in freqs]
+    M = L if mmax is None else min(int(mmax) + 1, L)
+    nf = healpix.synth_chunk(len(sel), npol, L, M, nside, max_bytes)
+    roots = covariance_roots(cv)
+    out = np.empty((int(nreal), len(sel), npol, healpix.npix(nside)))
+    for r in range(int(nreal)):
+        for f0 in range(0, len(sel), nf):
+            a = draw_alm(cv, 1, seed, stream, first + r, mmax, sel[f0 : f0 + nf], to_host=False, roots=roots)
+            out[r, f0 : f0 + nf] = healpix.sphtrans_inv_sky(a[0], nside, max_bytes)
+            del a
+    return out
+
+
+def write_sky(fname, maps):
+    """Write one sky [freq, pol, pixel] as the ``map`` dataset that ``timestream.simulate(maps=[...])`` reads."""
+    from . import storage
+
+    maps = np.asarray(maps, dtype=np.float64)
+    if maps.ndim != 3:
+        raise ValueError("write_sky: one sky [freq, pol, pixel]")
+    with storage.File(fname, "w") as f:
+        f.create_dataset("map", data=maps)

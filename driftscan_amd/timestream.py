@@ -607,11 +607,32 @@ def cross_powerspectrum(timestreams, psname, psfile):
     return powerspectrum
 
 
-def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, **kwargs):
+def _sky_covariance(m, model, klname):
+    """[pol, pol, l, freq, freq] of `model` ("signal" / "foreground"): that of KL transform `klname` of the products
+    (the first one by default), or the committed model for the telescope when the products hold no KL transform."""
+    from . import skymodel
+
+    if model not in ("signal", "foreground"):
+        raise ValueError("skymodels: 'signal' or 'foreground', not %r" % (model,))
+    kls = getattr(m, "kltransforms", None) or {}
+    if klname is not None and klname not in kls:
+        raise ValueError("klname %r is not a KL transform of these products" % (klname,))
+    if kls:
+        kl = kls[klname] if klname is not None else next(iter(kls.values()))
+        return kl.signal() if model == "signal" else kl.foreground()
+    tel = m.beamtransfer.telescope
+    make = skymodel.im21cm_model if model == "signal" else skymodel.foreground_model
+    return make(tel.lmax, tel.frequencies, tel.num_pol_sky)
+
+
+def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=(), klname=None, sky_seed=0,
+             sky_realisation=0, **kwargs):
     """Simulated timestream of the telescope of ProductManager `m` (timestream.py:645-829).
 
     maps: list of files holding a dataset `map` [freq, pol, pixel] whose sum is the sky; ndays = 0: no noise;
-    resolution = 0: 2 mmax + 1 time samples.  Returns the Timestream."""
+    resolution = 0: 2 mmax + 1 time samples.  skymodels: any of "signal", "foreground" — a Gaussian realisation
+    (`sky_seed`, `sky_realisation`) of that covariance of KL transform `klname` is drawn on the device (`skysim.draw_alm`,
+    every rank the rows of its own frequencies) and its a_lm are added to those of the maps.  Returns the Timestream."""
     bt = m.beamtransfer
     tel = bt.telescope
     lmax, mmax, nfreq, npol = tel.lmax, tel.mmax, tel.nfreq, tel.num_pol_sky
@@ -624,7 +645,8 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, **kwargs):
     lfreq = len(local_freq)
     col_vis = np.zeros((tel.npairs, lfreq, ntime), dtype=np.complex128)
 
-    if len(maps) > 0:
+    skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
+    if len(maps) > 0 or len(skymodels) > 0:
         # The reference's two MPI transposes (timestream.py:700-760): every rank transforms the maps of ITS frequencies,
         # the a_lm are regrouped by m, every rank projects ITS m through the beam (all frequencies of an m in one grouped
         # product on the device), and the visibilities come back regrouped by frequency.
@@ -635,8 +657,15 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, **kwargs):
             with storage.File(mapfile, "r") as f:
                 part = f["map"][local_freq[0] : local_freq[-1] + 1] if lfreq else None
             skymap = part if skymap is None else skymap + part
-        alm_loc = (healpix.sphtrans_sky(skymap, lmax) if lfreq else
-                   np.zeros((0, npol, lmax + 1, lmax + 1), dtype=np.complex128))       # (lfreq, npol, L, L): [l, m]
+        alm_loc = (healpix.sphtrans_sky(skymap, lmax) if lfreq and len(maps) > 0 else
+                   np.zeros((lfreq, npol, lmax + 1, lmax + 1), dtype=np.complex128))   # (lfreq, npol, L, L): [l, m]
+        for model in skymodels:
+            from . import skysim
+
+            stream = skysim.STREAM_SKY_SIGNAL if model == "signal" else skysim.STREAM_SKY_FOREGROUND
+            cv = _sky_covariance(m, model, klname)
+            if lfreq:   # straight to a_lm (no map in between), only the m the telescope measures
+                alm_loc[..., : mmax + 1] += skysim.draw_alm(cv, 1, sky_seed, stream, sky_realisation, mmax, local_freq)[0]
         got = parallel.exchange([np.ascontiguousarray(alm_loc[..., m_of[r]]) for r in range(nranks)])
         my_m = m_of[me]
         alm_m = np.zeros((nfreq, npol, lmax + 1, len(my_m)), dtype=np.complex128)

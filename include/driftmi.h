@@ -321,6 +321,26 @@ int dm_psmc_alt(dm_ctx* ctx, int nblk, int F, int K, int P, int L, const void* b
                 const int64_t* evals_off_host, int R, const void* x_dev, const int64_t* x_off_host, int nsamples,
                 void* v_dev, void* fisher_dev);
 
+/* ---- Gaussian skies from the covariance models --------------------------------- */
+/* dm_sky_draw: correlated draws of spherical-harmonic coefficients for one group of n components (pol, freq):
+ *   a[r, i, l, m] = sum_j T_l[i, j] z[r, j, l, m],  rows i in [row0, row0 + nrows), l < L, m < M <= L, r < nreal
+ *   T_dev         (L, n, n) f64: the symmetric square root of C_l of the group; row stride ldT, strideT between l
+ *   jglobal_host  (n) pol * nfreq + freq of every component: counter word 0 of its draws, and its polarisation
+ *   rowoff_host   (n) offset of component i in out_dev, in complex elements (read for the rows of the call)
+ *   out_dev       c128: a[r, i, l, m] at rowoff[i] + r stride_real + l stride_l + m stride_m
+ * z[r, j, l, m] is one Philox4x32-10 block with key = seed (low word first) and counter
+ * (jglobal[j], (l << 16) | m, first + r, stream), mapped as DM_PSMC_NORMAL of dm_psmc_draw: complex with E|z|^2 = 1
+ * for m > 0; for m = 0 real with E z^2 = 1 (sqrt(2) Re of that draw, imaginary part exactly 0).  Every element of the
+ * range is written: 0 for m > l, and for l < 2 on the components of polarisation 1 and 2 (E, B).  The draws are made in
+ * the kernel and multiplied on the matrix cores; the sum over j runs in an order set by n alone, so a coefficient has
+ * the same bits whatever rows, M, first / nreal or grouping of calls produced it.  n <= 1024 and L <= 65536; beyond,
+ * the call returns an error and launches nothing.  Synchronises.
+ * Replaces: cora.core.skysim.mkfullsky (the Gaussian skies the reference's simulations are made from). */
+int dm_sky_draw(dm_ctx* ctx, int n, int L, int M, const double* T_dev, int ldT, int64_t strideT,
+                const int* jglobal_host, const int64_t* rowoff_host, int nfreq, int row0, int nrows, uint64_t seed,
+                int stream, int first, int nreal, void* out_dev, int64_t stride_real, int64_t stride_l,
+                int64_t stride_m);
+
 /* ---- beam-transfer generation (cylinder telescopes) --------------------------- */
 /* Host geometry shared by the three calls below: ring_cth_host / ring_sth_host hold
  * cos / sin of the colatitude of the 4*nside-1 HEALPix rings; frame_host (9 doubles)
