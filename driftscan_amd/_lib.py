@@ -139,6 +139,7 @@ SIGNATURES = {
     "dm_bit_truncate_max_complex": (c_int, [c_vp, c_vp, c_i64, c_int, c_i64, c_dbl, c_dbl]),
     "dm_blockvec_grouped": (c_int, [c_vp, c_int, ctypes.POINTER(ZgemmProblem)]),
     "dm_mmode_twiddle": (c_int, [c_vp, c_int, c_int, c_vp]),
+    "dm_ts_noise": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.c_uint64, c_int, c_vp]),
 }
 
 _lib = None
@@ -434,9 +435,80 @@ def _mmode_transform(self, X, mmax, out=None):
     return out
 
 
+def _mmode_synthesis(self, V, ntime, out=None, accumulate=False):
+    """The inverse of `mmode_transform`: m-modes V (mmax + 1, nf, 2, npairs) on the device, the layout of the mode files,
+    to timestreams out (nf, npairs, ntime),
+
+        out[f, p, t] = sum_{m=0..mmax} V[m, f, 0, p] e^{+2 pi i m t / ntime}
+                     + sum_{m=1..mmax} conj(V[m, f, 1, p]) e^{-2 pi i m t / ntime}
+
+    (slot 1 of m = 0 is not read) — what `timestream.simulate` computes as ifft(col_vis) ntime.  Two strided-batched
+    ZGEMMs over the frequencies against ntime times the table of `mmode_twiddle`: its conjugate for slot 0, the table
+    itself against conj(V) for slot 1.  accumulate=True adds to what `out` holds (the noise `ts_noise` has just drawn
+    there)."""
+    if V.dim() != 4 or int(V.shape[2]) != 2 or not (V.is_complex() and V.element_size() == 16):
+        raise ValueError("mmode_synthesis: m-modes (mmax + 1, nf, 2, npairs) complex128 expected, got %s" % (tuple(V.shape),))
+    nm, nf, _, npairs = (int(v) for v in V.shape)
+    mmax, ntime = nm - 1, int(ntime)
+    if nm < 1 or ntime < 2 * mmax + 1:
+        raise ValueError("mmode_synthesis: %d time samples cannot hold m up to %d" % (ntime, mmax))
+    # V may be one column of a contiguous (mmax + 1, nf, 2, npairs, R) array (the batched projection's output): the
+    # products read it through its element stride, without a copy
+    s = int(V.stride(3))
+    if s < 1 or tuple(V.stride()) != (nf * 2 * npairs * s, 2 * npairs * s, npairs * s, s):
+        V, s = V.contiguous(), 1
+    if out is None:
+        if accumulate:
+            raise ValueError("mmode_synthesis: accumulate needs the buffer to add to")
+        out = self.empty((nf, npairs, ntime), np.complex128)
+    if tuple(out.shape) != (nf, npairs, ntime) or not out.is_contiguous() or not (out.is_complex() and out.element_size() == 16):
+        raise ValueError("mmode_synthesis: out must be a contiguous (nf, npairs, ntime) complex128 tensor")
+    if nf == 0 or npairs == 0:
+        return out
+    W = self.mmode_twiddle(ntime, mmax)
+    row = nf * 2 * npairs * s
+    self.zgemm(V, W, out, npairs, ntime, mmax + 1, rsA=s, csA=row, rsB=1, csB=mmax + 1, ldc=ntime, conjB=True,
+               alpha=float(ntime), beta=1.0 if accumulate else 0.0, batch=nf, strideA=2 * npairs * s, strideB=0,
+               strideC=npairs * ntime)
+    if mmax > 0:   # slot 1 from m = 1: A starts at V[1, 0, 1], the table at its column 1
+        self.zgemm(V[1, 0, 1], W[0, 1:], out, npairs, ntime, mmax, rsA=s, csA=row, rsB=1, csB=mmax + 1, ldc=ntime,
+                   conjA=True, alpha=float(ntime), beta=1.0, batch=nf, strideA=2 * npairs * s, strideB=0,
+                   strideC=npairs * ntime)
+    return out
+
+
+def _ts_noise(self, sigma, fglobal, ntime, nreal, seed, first=0, out=None):
+    """Receiver noise out[r, i, p, t] = sigma[i, p] z on the device (dm_ts_noise): sigma (nf, npairs) f64 (numpy or
+    device), `fglobal` the global frequency index of every row of sigma, z the unit complex normal of (seed, pair, global
+    frequency, t, realisation first + r) — `skysim.noise_host` restates it.  Every element of `out`
+    (nreal, nf, npairs, ntime) is written."""
+    if isinstance(sigma, np.ndarray) or not hasattr(sigma, "data_ptr"):
+        sigma = self.to_device(np.asarray(sigma, dtype=np.float64))
+    if sigma.dim() != 2 or sigma.dtype != self.torch.float64:
+        raise ValueError("ts_noise: sigma (nf, npairs) float64 expected")
+    sigma = sigma.contiguous()
+    nf, npairs = (int(v) for v in sigma.shape)
+    fg, fgp = _iarr(fglobal)
+    ntime, nreal, first = int(ntime), int(nreal), int(first)
+    if fg.shape != (nf,) or (nf and int(fg.min()) < 0):
+        raise ValueError("ts_noise: one non-negative global frequency index per row of sigma expected")
+    if ntime < 0 or nreal < 0 or first < 0:
+        raise ValueError("ts_noise: ntime, nreal and first must not be negative")
+    if out is None:
+        out = self.empty((nreal, nf, npairs, ntime), np.complex128)
+    if tuple(out.shape) != (nreal, nf, npairs, ntime) or not out.is_contiguous() or not (out.is_complex() and out.element_size() == 16):
+        raise ValueError("ts_noise: out must be a contiguous (nreal, nf, npairs, ntime) complex128 tensor")
+    rc = self.lib.dm_ts_noise(self.h, nreal, nf, npairs, ntime, self.ptr(sigma), fgp, int(seed) & 0xFFFFFFFFFFFFFFFF, first,
+                              self.ptr(out))
+    self.check(rc, "dm_ts_noise")
+    return out
+
+
 Context.blockvec_grouped = _blockvec_grouped
 Context.mmode_twiddle = _mmode_twiddle
 Context.mmode_transform = _mmode_transform
+Context.mmode_synthesis = _mmode_synthesis
+Context.ts_noise = _ts_noise
 
 
 def _iarr(a):

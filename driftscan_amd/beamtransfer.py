@@ -901,6 +901,43 @@ class BeamTransfer(config.Reader):
             ctx.blockvec_grouped(inv, vecs.contiguous(), out, tab, R)
         return out
 
+    def _device_beam_blocks_of(self, ms, freqs=None):
+        """`_device_beam_blocks(ms)` restricted to the frequencies `freqs` (all by default) as a contiguous
+        (len(ms), len(freqs), 2, B, P, L) device tensor; from the files only those frequency slices are read."""
+        if freqs is None or list(freqs) == list(range(self.nfreq)):
+            return self._device_beam_blocks(ms).contiguous()
+        ctx = get_context()
+        freqs = [int(f) for f in freqs]
+        ba = getattr(self, "_beam_all", None)
+        m0 = getattr(self, "_beam_all_m0", 0)
+        if ba is not None and all(m0 <= mi < m0 + int(ba.shape[0]) for mi in ms):
+            import torch
+
+            return self._device_beam_blocks(ms)[:, torch.as_tensor(freqs, device=ba.device)].contiguous()
+        return ctx.to_device(np.stack([np.stack([self.beam_m(mi, fi) for fi in freqs]) for mi in ms]))
+
+    def project_vectors_sky_to_telescope_device(self, ms, alm, freqs=None, products=None):
+        """Batch form of `project_vector_sky_to_telescope`: alm (len(ms), nf, npol, lmax + 1, R) on the device, the a_lm of
+        every m of the batch for R skies -> (len(ms), nf, ntel, R).  One launch for all (m, frequency) blocks, each
+        M = ntel rows of K = nsky contiguous elements.  `freqs` (default: all) are the frequencies the nf rows stand for;
+        `products` is the `_device_beam_blocks_of(ms, freqs)` of the batch if the caller holds it already."""
+        ctx = get_context()
+        tel = self.telescope
+        ms = list(ms)
+        nf = self.nfreq if freqs is None else len(freqs)
+        P, L = int(tel.num_pol_sky), int(tel.lmax) + 1
+        if alm.dim() != 5 or tuple(int(v) for v in alm.shape[:4]) != (len(ms), nf, P, L):
+            raise ValueError("a_lm of shape (len(ms), nf, npol, lmax + 1, R) expected")
+        R = int(alm.shape[4])
+        out = ctx.empty((len(ms), nf, self.ntel, R), np.complex128)
+        tab = sky_to_telescope_table(len(ms), nf, self.ntel, self.nsky, R)
+        if len(tab) and out.numel():
+            beam = self._device_beam_blocks_of(ms, freqs) if products is None else products
+            if int(beam.numel()) != len(ms) * nf * self.ntel * self.nsky or not beam.is_contiguous():
+                raise ValueError("beam blocks (len(ms), nf, 2, npairs, npol, lmax + 1) of the batch expected")
+            ctx.blockvec_grouped(beam, alm.contiguous(), out, tab, R)
+        return out
+
 
 class BeamTransferFullSVD(BeamTransfer):
     """One SVD of the full (all sky polarisations) noise-weighted beam per (m, frequency) instead of
@@ -1099,6 +1136,14 @@ def svd_forward_table(svnum, svd_len, ntel, R):
     tab = blockvec_table(a0=blk * svd_len * ntel, x0=blk * ntel * R, y0=(off[i] + bounds[i, f]) * R, M=svnum[i, f], K=ntel,
                          rsA=ntel, csA=1, rsB=R, csB=1, ldc=R)
     return tab, off
+
+
+def sky_to_telescope_table(nb, nf, ntel, nsky, R):
+    """beam_m blocks (nb, nf, ntel, nsky) applied to a_lm (nb, nf, nsky, R) into (nb, nf, ntel, R): one problem per
+    (m, frequency) block, rows of nsky contiguous elements."""
+    blk = np.arange(int(nb) * int(nf), dtype=np.int64)
+    return blockvec_table(a0=blk * ntel * nsky, x0=blk * nsky * R, y0=blk * ntel * R, M=ntel, K=nsky, rsA=nsky, csA=1,
+                          rsB=R, csB=1, ldc=R)
 
 
 def svd_to_sky_table(svnum, off, svd_len, npol, nl, R):

@@ -19,6 +19,8 @@ import numpy as np
 
 STREAM_SKY_SIGNAL = 16       # clear of psmc.STREAM_X, STREAM_X2, STREAM_ALT = 0, 1, 2
 STREAM_SKY_FOREGROUND = 17
+STREAM_TS_NOISE = 24         # receiver noise (dm_ts_noise): the low byte of counter word 3, the realisation above it
+TS_NOISE_MAX_REAL = 1 << 24
 LMAX_LIMIT = 65536           # m and l share one 32-bit counter word
 
 
@@ -117,6 +119,25 @@ def draws_host(jglobal, L, M=None, nreal=1, seed=0, stream=STREAM_SKY_SIGNAL, fi
     z = rad * np.cos(th) + 1j * (rad * np.sin(th))
     z = np.where(m == 0, 1.4142135623730951 * z.real, z)
     return np.where(m <= l, z, 0.0)
+
+
+def noise_host(sigma, fglobal, ntime, nreal, seed, first=0, stream=STREAM_TS_NOISE):
+    """The receiver noise of ``Context.ts_noise`` in numpy: [nreal, nf, npairs, ntime] with ``sigma`` (nf, npairs) (or a
+    scalar) times the unit draw of counter ``(pair, fglobal[i], t, ((first + r) << 8) | stream)``."""
+    fg = np.asarray(fglobal, dtype=np.uint64).reshape(-1)
+    sigma = np.asarray(sigma, dtype=np.float64)
+    if sigma.ndim == 0:
+        raise ValueError("noise_host: sigma (nf, npairs) expected")
+    sigma = np.broadcast_to(sigma, (fg.shape[0], sigma.shape[-1]))
+    if first < 0 or first + nreal > TS_NOISE_MAX_REAL:
+        raise ValueError("noise_host: realisations beyond the %d the counter word holds" % TS_NOISE_MAX_REAL)
+    r, f, p, t = np.meshgrid(np.arange(first, first + nreal, dtype=np.uint64), fg,
+                             np.arange(sigma.shape[1], dtype=np.uint64), np.arange(ntime, dtype=np.uint64), indexing="ij")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = _philox4x32_10([p, f, t, (r << np.uint64(8)) | np.uint64(stream)], (seed & 0xFFFFFFFF, seed >> 32))
+    rad = np.sqrt(-np.log(_u53(w[0], w[1]))) * sigma[None, :, :, None]
+    th = 6.283185307179586 * _u53(w[2], w[3])
+    return rad * np.cos(th) + 1j * (rad * np.sin(th))
 
 
 def correlate_host(T, z):

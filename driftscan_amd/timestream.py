@@ -200,18 +200,7 @@ class Timestream(object):
 
     def _m_batches(self, ms, per_m_bytes, chunk_gb):
         """`ms` cut into runs whose summed `per_m_bytes(mi)` stays within chunk_gb (at least one m per batch)."""
-        budget = chunk_gb * (1 << 30)
-        out, cur, used = [], [], 0.0
-        for mi in ms:
-            need = float(per_m_bytes(mi))
-            if cur and used + need > budget:
-                out.append(cur)
-                cur, used = [], 0.0
-            cur.append(mi)
-            used += need
-        if cur:
-            out.append(cur)
-        return out
+        return m_batches(ms, per_m_bytes, chunk_gb)
 
     @staticmethod
     def _write_vector(fname, dset, vec, mi):
@@ -558,6 +547,22 @@ class _StepTimer(object):
         return False
 
 
+def m_batches(ms, per_m_bytes, chunk_gb):
+    """`ms` cut into runs whose summed `per_m_bytes(mi)` stays within chunk_gb (at least one m per batch)."""
+    budget = chunk_gb * (1 << 30)
+    out, cur, used = [], [], 0.0
+    for mi in ms:
+        need = float(per_m_bytes(mi))
+        if cur and used + need > budget:
+            out.append(cur)
+            cur, used = [], 0.0
+        cur.append(mi)
+        used += need
+    if cur:
+        out.append(cur)
+    return out
+
+
 def _ps_mlist(mmax, no_m_zero):
     return list(range(1 if no_m_zero else 0, mmax + 1))
 
@@ -715,3 +720,197 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
     tstream.save()
     parallel.barrier()
     return tstream
+
+
+# ---- ensembles of simulated timestreams on the device -------------------------------------------
+# Opt-in log of `simulate_visibilities` / `simulate_ensemble`: a dict set here collects wall seconds per kind of step
+# ("sky": map transforms, covariance roots and a_lm draws; "beam": reading and uploading beam blocks; "project"; "noise";
+# "synthesis"; "download"; "write"), waiting for the device at every boundary.  None: no waits added.
+sim_log = None
+
+
+def _sim_freqs(tel, freqs):
+    if freqs is None:
+        nranks = parallel.size() if parallel._dist() else 1
+        me = parallel.rank() if parallel._dist() else 0
+        return parallel.partition_for(list(range(tel.nfreq)), me, nranks)
+    freqs = [int(f) for f in freqs]
+    if sorted(set(freqs)) != freqs or (freqs and not 0 <= freqs[0] <= freqs[-1] < tel.nfreq):
+        raise ValueError("freqs must be sorted, distinct frequency indices")
+    return freqs
+
+
+def _sim_ntime(tel, resolution):
+    return 2 * tel.mmax + 1 if resolution == 0 else int(np.round(24 * 3600.0 / resolution))
+
+
+def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
+                       out=None):
+    """The passes of `simulate_visibilities`: yields (r0, device tensor (R, nf, npairs, ntime)) for the realisations
+    first + r0 .. first + r0 + R - 1, R <= BLOCKVEC_MAX_R.  With `out` (nreal, nf, npairs, ntime) the groups are views of
+    it; without, ONE buffer is used for every group (the caller is done with a group when it asks for the next)."""
+    from . import skysim
+    from ._lib import BLOCKVEC_MAX_R
+
+    ctx = get_context()
+    bt = m.beamtransfer
+    tel = bt.telescope
+    lmax, mmax, npol, npairs = int(tel.lmax), int(tel.mmax), int(tel.num_pol_sky), int(tel.npairs)
+    if ndays is None:
+        ndays = tel.ndays
+    ntime = _sim_ntime(tel, resolution)
+    if ntime < 2 * mmax + 1:
+        raise ValueError("%d time samples cannot hold m up to %d" % (ntime, mmax))
+    nreal, first = int(nreal), int(first)
+    nf = len(freqs)
+    skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
+    have_sky = len(maps) > 0 or len(skymodels) > 0
+    if nf == 0 or nreal <= 0:
+        return
+    log = sim_log
+
+    sigma = None
+    if ndays > 0:
+        noise_ps = np.asarray(tel.noisepower(np.arange(npairs)[np.newaxis, :], np.array(freqs)[:, np.newaxis],
+                                             ndays=ndays), dtype=np.float64).reshape(nf, npairs)
+        sigma = ctx.to_device(np.sqrt(ntime * noise_ps))
+
+    fixed, models = None, []
+    if have_sky:
+        with _StepTimer(log, "sky"):
+            if len(maps) > 0:
+                skymap = None
+                for mapfile in maps:
+                    with storage.File(mapfile, "r") as f:
+                        part = f["map"][freqs[0] : freqs[-1] + 1][[fi - freqs[0] for fi in freqs]]
+                    skymap = part if skymap is None else skymap + part
+                alm = healpix.sphtrans_sky(skymap, lmax)                       # (nf, npol, L, L): [l, m]
+                fixed = ctx.to_device(np.ascontiguousarray(alm[..., : mmax + 1]))
+            for model in skymodels:
+                stream = skysim.STREAM_SKY_SIGNAL if model == "signal" else skysim.STREAM_SKY_FOREGROUND
+                cv = _sky_covariance(m, model, klname)
+                models.append((cv, stream, skysim.covariance_roots(cv)))
+        batches = m_batches(list(range(mmax + 1)), lambda mi: 16.0 * nf * bt.ntel * bt.nsky, chunk_gb)
+
+    buf = None
+    for r0 in range(0, nreal, BLOCKVEC_MAX_R):
+        R = min(BLOCKVEC_MAX_R, nreal - r0)
+        if out is not None:
+            grp = out[r0 : r0 + R]
+        else:
+            if buf is None:
+                buf = ctx.empty((min(BLOCKVEC_MAX_R, nreal), nf, npairs, ntime), np.complex128)
+            grp = buf[:R]
+        if sigma is not None:
+            with _StepTimer(log, "noise"):
+                ctx.ts_noise(sigma, freqs, ntime, R, seed, first + r0, out=grp)
+        elif not have_sky:
+            grp.zero_()
+        if have_sky:
+            with _StepTimer(log, "sky"):
+                alm = ctx.zeros((R, nf, npol, lmax + 1, mmax + 1), np.complex128) if not models else None
+                for cv, stream, roots in models:
+                    a = skysim.draw_alm(cv, R, sky_seed, stream, first + r0, mmax, freqs, to_host=False, roots=roots)
+                    alm = a if alm is None else alm.add_(a)
+                if fixed is not None:
+                    alm.add_(fixed[None])
+                alm_m = alm.permute(4, 1, 2, 3, 0).contiguous()                # (m, nf, npol, L, R)
+                del alm
+            vis = ctx.empty((mmax + 1, nf, bt.ntel, R), np.complex128)
+            for batch in batches:
+                with _StepTimer(log, "beam"):
+                    beam = bt._device_beam_blocks_of(batch, freqs)
+                with _StepTimer(log, "project"):
+                    vis[batch[0] : batch[-1] + 1] = bt.project_vectors_sky_to_telescope_device(
+                        batch, alm_m[batch[0] : batch[-1] + 1], freqs=freqs, products=beam)
+                del beam
+            del alm_m
+            with _StepTimer(log, "synthesis"):
+                cols = vis.view(mmax + 1, nf, 2, npairs, R)
+                for r in range(R):
+                    ctx.mmode_synthesis(cols[..., r], ntime, out=grp[r], accumulate=sigma is not None)
+            del vis, cols
+        yield r0, grp
+
+
+def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None, sky_seed=0,
+                          first=0, freqs=None, chunk_gb=4.0):
+    """`nreal` simulated timestreams of the telescope of ProductManager `m` as ONE device tensor
+    (nreal, len(freqs), npairs, ntime): what `simulate` writes per frequency, for many statistically independent data
+    sets, without leaving the device between the draws and the result.
+
+    Realisation first + i uses `sky_realisation = first + i` of every model of `skymodels` ("signal", "foreground": the
+    a_lm of `skysim.draw_alm` with `sky_seed`) and noise realisation first + i of `seed`; `maps` are fixed skies shared
+    by all.  `freqs` (sorted; default: this rank's share of the frequencies) are the rows computed: every draw is
+    counter based, so a rank draws, projects and synthesises its own frequencies and the union of the ranks' results is
+    the single-process result — there are no collectives.
+
+    Realisations go in groups of up to 8: per group the beam blocks of every m are read once (from the resident
+    products or the files, batches of at most `chunk_gb`) and applied to the a_lm of the whole group in one launch per
+    batch (`BeamTransfer.project_vectors_sky_to_telescope_device`); the noise is drawn into the result
+    (`Context.ts_noise`) and the m -> time transform adds to it (`Context.mmode_synthesis`).
+
+    Noise: `simulate` adds complex noise of variance `noisepower` to each of the ntime Fourier bins before
+    ifft * ntime; in the time domain that is white noise of variance ntime * noisepower, exactly, and that is what is
+    drawn here, sigma[f, p] = sqrt(ntime * noisepower(p, f, ndays)).  It is the same DISTRIBUTION as `simulate`'s, not
+    the same numbers.  ndays = 0: no noise."""
+    ctx = get_context()
+    tel = m.beamtransfer.telescope
+    freqs = _sim_freqs(tel, freqs)
+    out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.npairs), _sim_ntime(tel, resolution)), np.complex128)
+    for _ in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
+                                chunk_gb, out=out):
+        pass
+    return out
+
+
+def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None,
+                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0):
+    """`simulate_visibilities` written out: realisation first + i as the Timestream directory
+    `outdir/real_%04d` % (first + i), each with the per-frequency files, datasets and attributes of `simulate` and the
+    saved object.  Every rank writes its own frequencies (one device-to-host copy per group of up to 8 realisations),
+    rank 0 saves the objects.  Returns the list of `Timestream`.
+
+    End to end (does the estimator recover the injected spectrum through the real chain?):
+
+        tss = timestream.simulate_ensemble(pm, "ens", 64, skymodels=("signal",), ndays=733)
+        for ts in tss:
+            ts.generate_modes_batched(klnames=["kl"])
+            ts.set_kltransform("kl")
+            ts.set_psestimator("ps")
+            p = ts.powerspectrum()      # mean over the ensemble -> the injected band powers, scatter -> Fisher errors
+    """
+    ctx = get_context()
+    bt = m.beamtransfer
+    tel = bt.telescope
+    freqs = _sim_freqs(tel, freqs)
+    ntime = _sim_ntime(tel, resolution)
+    nreal, first = int(nreal), int(first)
+    tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
+    tss = [Timestream(os.path.join(outdir, "real_%04d" % (first + i)), m) for i in range(max(nreal, 0))]
+    for r0, grp in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
+                                      chunk_gb):
+        with _StepTimer(sim_log, "download"):
+            host = ctx.to_host(grp)
+        with _StepTimer(sim_log, "write"):
+            for r in range(host.shape[0]):
+                tstream = tss[r0 + r]
+                for lfi, fi in enumerate(freqs):
+                    os.makedirs(tstream._fdir(fi), exist_ok=True)
+                    with storage.File(tstream._ffile(fi), "w") as f:
+                        f.create_dataset("timestream", data=np.ascontiguousarray(host[r, lfi]))
+                        f.create_dataset("phi", data=tphi)
+                        f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
+                        f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
+                        f.create_dataset("feedmask", data=np.asarray(tel.feedmask))
+                        f.create_dataset("uniquepairs", data=np.asarray(tel.uniquepairs))
+                        f.create_dataset("baselines", data=np.asarray(tel.baselines))
+                        f.attrs["beamtransfer_path"] = os.path.abspath(bt.directory)
+                        f.attrs["ntime"] = ntime
+    parallel.barrier()
+    if parallel.rank0():
+        for tstream in tss:
+            os.makedirs(tstream.directory, exist_ok=True)
+            tstream.save()
+    parallel.barrier()
+    return tss

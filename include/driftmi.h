@@ -495,6 +495,22 @@ int dm_blockvec_grouped(dm_ctx* ctx, int nprob, const dm_zgemm_problem* probs_ho
  * Replaces: np.fft.fft(timestream) / ntime at drift/pipeline/timestream.py:141-148. */
 int dm_mmode_twiddle(dm_ctx* ctx, int ntime, int mmax, void* W_dev);
 
+/* dm_ts_noise: receiver noise of simulated timestreams, drawn in the time domain:
+ *   out[r, i, p, t] = sigma[i, p] z,  r < nreal, i < nf, p < npairs, t < ntime
+ *   sigma_dev     (nf, npairs) f64 on the device
+ *   fglobal_host  (nf) global frequency index of every row i (>= 0)
+ *   out_dev       contiguous (nreal, nf, npairs, ntime) c128; every element is written (no memset needed)
+ * z is the complex standard normal (E|z|^2 = 1) that dm_psmc_draw and dm_sky_draw map one Philox4x32-10 block to, with
+ * key = seed (low word first) and counter (p, fglobal[i], t, ((first + r) << 8) | 24).  The low byte 24 keeps word 3 apart
+ * from the Monte-Carlo streams 0, 1, 2 and the sky streams 16, 17 for every realisation.  A draw depends on (seed, pair,
+ * global frequency, time sample, realisation) alone: not on the frequencies a call holds, its realisation range or how a
+ * caller chunks the work.  first + nreal > 2^24 is refused (dm_last_error) and nothing is launched.  One draw and one
+ * 16-byte store per lane, 64-bit element index.  Returns when the work is queued on the context's stream.
+ * Replaces: the np.random.standard_normal noise of drift/pipeline/timestream.py:779-798 (same distribution in the time
+ * domain at sigma^2 = ntime noisepower, not the same numbers). */
+int dm_ts_noise(dm_ctx* ctx, int nreal, int nf, int npairs, int ntime, const double* sigma_dev, const int* fglobal_host,
+                uint64_t seed, int first, void* out_dev);
+
 #ifdef __cplusplus
 }
 #endif
