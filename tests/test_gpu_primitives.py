@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+import eig_cases as ec
+
 pytestmark = pytest.mark.gpu
 
 
@@ -242,8 +244,11 @@ def test_herm_eig_with_exactly_zero_rows(ctx, monkeypatch, twostage):
     assert np.isfinite(got).all()
     assert np.abs(got - ref).max() <= 1e-13 * np.abs(ref).max()
     Wh = W.cpu().numpy()
+    evh = ev.cpu().numpy()[:, :n]
     for b in range(nb):
         assert np.abs(Wh[b] @ Wh[b].conj().T - np.eye(n)).max() < 1e-12
+        # ... and they are the eigenvectors of G[b]: a back-transformation that is wrong but unitary passes the line above
+        ec.assert_eigvecs(G[b], Wh[b].conj().T, evh[b], np.abs(ref[b]).max(), "twostage=%s [%d]" % (twostage, b))
 
 
 @pytest.mark.parametrize("n", [97, 129, 161, 452, 1000])
@@ -268,8 +273,10 @@ def test_herm_eig_two_stage_both_chases(ctx, monkeypatch, n):
         got[chase] = np.sort(ev.cpu().numpy()[:, :n], axis=1)
         assert np.abs(got[chase] - ref).max() <= 1e-13 * scale, chase
         Wh = W.cpu().numpy()
+        evh = ev.cpu().numpy()[:, :n]
         for b in range(nb):
             assert np.abs(Wh[b] @ Wh[b].conj().T - np.eye(n)).max() < 1e-12, chase
+            ec.assert_eigvecs(C[b], Wh[b].conj().T, evh[b], np.abs(ref[b]).max(), "%s n=%d [%d]" % (chase, n, b))
     assert np.abs(got["position"] - got["pairs"]).max() <= 1e-13 * scale
 
 
@@ -310,6 +317,10 @@ def test_herm_eig_mixed_sizes_via_eigh_gen(ctx, monkeypatch, ns, twostage):
             assert np.abs(ev[evoff[i]: evoff[i] + n] - ref).max() <= 1e-11 * ref.max(), chase
             Ei = E[off[i]: off[i] + n * n].reshape(n, n)
             assert np.abs(Ei @ Bs[i] @ Ei.conj().T - np.eye(n)).max() < 1e-10, chase
+            # A E^H = B E^H diag(ev), as the residual of the standard problem the pencil reduces to
+            res = ec.res_ratio_pencil(As[i], Bs[i], Ei.conj().T, ev[evoff[i]: evoff[i] + n])
+            print("%s n=%d: pencil res %.3g, cond(B) %.3g" % (chase, n, res, np.linalg.cond(Bs[i])))
+            assert res <= ec.bounds(n)[0] * np.linalg.cond(Bs[i]), (chase, n, res)
         got.append(ev)
     if len(got) == 2:
         assert np.abs(got[0] - got[1]).max() <= 1e-13 * np.abs(got[0]).max()
