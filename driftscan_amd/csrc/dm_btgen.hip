@@ -896,12 +896,15 @@ static double bt_table_peak(int lmax, int m, double z, double st, bool pol) {
   double logpre = 0.5 * (std::log(2.0 * m + 1.0) - std::log(4.0 * kPi));
   for (int k = 1; k <= m; ++k) logpre += 0.5 * std::log((2.0 * k - 1.0) / (2.0 * k));
   double lmm = (m > 0) ? std::exp(logpre + (double)m * std::log(st)) : std::exp(logpre);
-  double peak = std::fabs(lmm);
+  int ex = 0;   // an underflowing seed is carried as (value / 2^ex), as in the kernel
+  if (m > 0 && lmm < kDblMin) lmm = legendre_scaled_seed(m, s2, &ex);
+  double peak = std::fabs(std::ldexp(lmm, ex));
   if (pol && m >= 2) {
     const double l = m;
     const double nl = 2.0 * std::sqrt(1.0 / ((l - 1.0) * l * (l + 1.0) * (l + 2.0)));
-    peak = std::max(peak, std::fabs(nl * (-((l - l * l) / s2 + 0.5 * l * (l - 1.0)) * lmm)));
-    peak = std::max(peak, std::fabs(nl * (l / s2) * ((l - 1.0) * z * lmm)));
+    const double lm0 = std::ldexp(lmm, ex);
+    peak = std::max(peak, std::fabs(nl * (-((l - l * l) / s2 + 0.5 * l * (l - 1.0)) * lm0)));
+    peak = std::max(peak, std::fabs(nl * (l / s2) * ((l - 1.0) * z * lm0)));
   }
   double pm2 = 0.0, pm1 = lmm;
   for (int l = m + 1; l <= lmax; ++l) {
@@ -913,13 +916,14 @@ static double bt_table_peak(int lmax, int m, double z, double st, bool pol) {
       const double b = std::sqrt(((l - 1.0) * (l - 1.0) - (double)m * m) / (4.0 * (l - 1.0) * (l - 1.0) - 1.0));
       cur = a * (z * pm1 - b * pm2);
     }
-    peak = std::max(peak, std::fabs(cur));
+    if (ex < 0 && std::fabs(cur) > kTwoP512) { cur *= kTwoM512; pm1 *= kTwoM512; ex += 512; }
+    peak = std::max(peak, std::fabs(std::ldexp(cur, ex)));
     if (pol && l >= 2) {
       const double dl = l, dm = m;
       const double nl = 2.0 * std::sqrt(1.0 / ((dl - 1.0) * dl * (dl + 1.0) * (dl + 2.0)));
       const double c = std::sqrt((2.0 * dl + 1.0) / (2.0 * dl - 1.0) * (dl * dl - dm * dm));
-      peak = std::max(peak, std::fabs(nl * (-((dl - dm * dm) / s2 + 0.5 * dl * (dl - 1.0)) * cur + c * z / s2 * pm1)));
-      peak = std::max(peak, std::fabs(nl * (dm / s2) * ((dl - 1.0) * z * cur - c * pm1)));
+      peak = std::max(peak, std::fabs(std::ldexp(nl * (-((dl - dm * dm) / s2 + 0.5 * dl * (dl - 1.0)) * cur + c * z / s2 * pm1), ex)));
+      peak = std::max(peak, std::fabs(std::ldexp(nl * (dm / s2) * ((dl - 1.0) * z * cur - c * pm1), ex)));
     }
     pm2 = pm1;
     pm1 = cur;

@@ -112,6 +112,29 @@ __global__ void bt_twiddle_kernel(ring_geo g, int m_lo, int cnt, const size_t* _
   }
 }
 
+// Seeds of the Legendre recurrence that underflow (m ln(1 / sin theta) > 708).  Returns |lambda_mm| / 2^ex in
+// (2^-512, 1] with ex a multiple of 512, at most -1024: the square root of
+//   lambda_mm^2 = (2m + 1) / (4 pi) prod_{k <= m} sin^2 theta (2k - 1) / (2k),
+// a product carried with its own exponent.  Its relative error grows like sqrt(m) ulp; exp(m ln sin theta) would lose
+// |m ln sin theta| ulp here.  sin theta = 0 gives 0.  Shared by bt_legendre_kernel and bt_table_peak (dm_btgen.hip).
+constexpr double kDblMin = 2.2250738585072014e-308;
+constexpr double kTwoP512 = 1.3407807929942597e154;    // 2^512
+constexpr double kTwoM512 = 7.458340731200207e-155;    // 2^-512
+constexpr double kTwoM256 = 8.636168555094445e-78;     // 2^-256
+__host__ __device__ inline double legendre_scaled_seed(int m, double s2, int* ex) {
+  double p = (2.0 * m + 1.0) / (4.0 * kPi);
+  int e2 = 0;
+  for (int k = 1; k <= m; ++k) {
+    p *= s2 * ((2.0 * k - 1.0) / (2.0 * k));
+    if (p < kTwoM512) { p *= kTwoP512; e2 -= 512; }
+  }
+  double v = sqrt(p);
+  int e = e2 / 2;   // a multiple of 256
+  if (e % 512) { v *= kTwoM256; e += 256; }
+  *ex = e;
+  return v;
+}
+
 // Legendre tables: lam[loff[m] + (l-m)*nring + r] = w * lambda_lm(theta_r), same for W and X (polarised)
 __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, double w, const size_t* __restrict__ loff_,
                                    double* __restrict__ lam, double* __restrict__ Wt, double* __restrict__ Xt) {
@@ -124,11 +147,16 @@ __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, dou
   double logpre = 0.5 * (log(2.0 * m + 1.0) - log(4.0 * kPi));
   for (int k = 1; k <= m; ++k) logpre += 0.5 * log((2.0 * k - 1.0) / (2.0 * k));
   double lmm = (m > 0) ? exp(logpre + (double)m * log(st)) : exp(logpre);
+  // A seed below the smallest normal double (m ln(1 / sin theta) > 708) while the functions come back to order one at
+  // higher l: the pair is carried as (value / 2^ex), ex a multiple of 512 stepped up until it is 0.  ex = 0 from the
+  // start for every normal seed: the arithmetic and the bits of those columns are the plain recurrence's.
+  int ex = 0;
+  if (m > 0 && lmm < kDblMin) lmm = legendre_scaled_seed(m, s2, &ex);
   if (m & 1) lmm = -lmm;
   double* out = lam + loff[m];
   const size_t nr = g.nring;
   double pm2 = 0.0, pm1 = lmm;  // lambda_{l-2}, lambda_{l-1} as l advances
-  out[r] = w * lmm;
+  out[r] = w * ldexp(lmm, ex);
   if (Wt) {
     double* wo = Wt + loff[m];
     double* xo = Xt + loff[m];
@@ -136,8 +164,9 @@ __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, dou
     if (m >= 2) {
       const double l = m;
       const double nl = 2.0 * sqrt(1.0 / ((l - 1.0) * l * (l + 1.0) * (l + 2.0)));
-      wo[r] = -w * nl * (-((l - l * l) / s2 + 0.5 * l * (l - 1.0)) * lmm);
-      xo[r] = w * nl * (l / s2) * ((l - 1.0) * z * lmm);
+      const double lm0 = ldexp(lmm, ex);
+      wo[r] = -w * nl * (-((l - l * l) / s2 + 0.5 * l * (l - 1.0)) * lm0);
+      xo[r] = w * nl * (l / s2) * ((l - 1.0) * z * lm0);
     } else {
       wo[r] = 0.0;
       xo[r] = 0.0;
@@ -152,7 +181,8 @@ __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, dou
       const double b = sqrt(((l - 1.0) * (l - 1.0) - (double)m * m) / (4.0 * (l - 1.0) * (l - 1.0) - 1.0));
       cur = a * (z * pm1 - b * pm2);
     }
-    out[(size_t)(l - m) * nr + r] = w * cur;
+    if (ex < 0 && fabs(cur) > kTwoP512) { cur *= kTwoM512; pm1 *= kTwoM512; ex += 512; }
+    out[(size_t)(l - m) * nr + r] = w * ldexp(cur, ex);
     if (Wt) {
       double wv = 0.0, xv = 0.0;
       if (l >= 2) {
@@ -162,8 +192,8 @@ __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, dou
         wv = -nl * (-((dl - dm * dm) / s2 + 0.5 * dl * (dl - 1.0)) * cur + c * z / s2 * pm1);
         xv = nl * (dm / s2) * ((dl - 1.0) * z * cur - c * pm1);
       }
-      (Wt + loff[m])[(size_t)(l - m) * nr + r] = w * wv;
-      (Xt + loff[m])[(size_t)(l - m) * nr + r] = w * xv;
+      (Wt + loff[m])[(size_t)(l - m) * nr + r] = w * ldexp(wv, ex);
+      (Xt + loff[m])[(size_t)(l - m) * nr + r] = w * ldexp(xv, ex);
     }
     pm2 = pm1;
     pm1 = cur;

@@ -83,6 +83,52 @@ def lambda_lm(lmax, m, z):
         a = np.sqrt((4.0 * l * l - 1.0) / (l * l - m * m))
         b = np.sqrt(((l - 1.0) ** 2 - m * m) / (4.0 * (l - 1.0) ** 2 - 1.0))
         out[l - m] = a * (z * out[l - m - 1] - b * out[l - m - 2])
+    if m > 0:
+        # seeds below the smallest normal double (m ln(1 / sin theta) > 708): the rows above are zeros or digits lost to
+        # gradual underflow, though the functions come back to order one at higher l.  Those columns are redone with the
+        # running pair carried next to a power-of-two exponent; every other column keeps the bits of the plain recurrence.
+        sc = np.nonzero((np.abs(lmm) < np.finfo(np.float64).tiny) & (st > 0.0))[0]
+        if sc.size:
+            out[:, sc] = _lambda_scaled(lmax, m, z[sc])
+    return out
+
+
+def _lambda_scaled(lmax, m, z):
+    """`lambda_lm` for columns whose seed underflows: the recurrence on (value / 2^ex) with ex a multiple of 512 per
+    column, stepped up by 512 whenever the scaled value passes 2^512 until ex = 0, from where on the arithmetic is the
+    plain recurrence.  Values below the smallest normal double come out denormal or zero (ldexp).  The seed is the
+    square root of lambda_mm^2 = (2m + 1) / (4 pi) prod_k sin^2 (2k - 1) / (2k), a product carried with its own
+    exponent: its relative error grows like sqrt(m) ulp, where exp(m ln sin theta) loses |m ln sin theta| ulp."""
+    s2 = (1.0 - z) * (1.0 + z)
+    p = np.full(z.size, (2.0 * m + 1.0) / (4.0 * np.pi))
+    e2 = np.zeros(z.size, dtype=np.intc)
+    for k in range(1, m + 1):
+        p *= s2 * ((2.0 * k - 1.0) / (2.0 * k))
+        low = p < 2.0 ** -512
+        p[low] *= 2.0 ** 512
+        e2[low] -= 512
+    p1 = ((-1.0) ** m) * np.sqrt(p)
+    ex = e2 // 2                                           # a multiple of 256, at most -1024 for an underflowed seed
+    odd = ex % 512 != 0
+    p1[odd] *= 2.0 ** -256
+    ex[odd] += 256
+    p2 = np.zeros_like(p1)
+    out = np.empty((lmax + 1 - m, z.size))
+    out[0] = np.ldexp(p1, ex)
+    for l in range(m + 1, lmax + 1):
+        if l == m + 1:
+            cur = np.sqrt(2.0 * m + 3.0) * z * p1
+        else:
+            a = np.sqrt((4.0 * l * l - 1.0) / (l * l - m * m))
+            b = np.sqrt(((l - 1.0) ** 2 - m * m) / (4.0 * (l - 1.0) ** 2 - 1.0))
+            cur = a * (z * p1 - b * p2)
+        big = (ex < 0) & (np.abs(cur) > 2.0 ** 512)
+        if big.any():
+            cur[big] *= 2.0 ** -512
+            p1[big] *= 2.0 ** -512
+            ex[big] += 512
+        out[l - m] = np.ldexp(cur, ex)
+        p2, p1 = p1, cur
     return out
 
 
