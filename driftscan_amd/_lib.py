@@ -27,6 +27,18 @@ class ZgemmProblem(ctypes.Structure):
                 ("conjA", c_int), ("conjB", c_int), ("alpha", c_dbl), ("beta", c_dbl)]
 
 
+class JacobiProblemDesc(ctypes.Structure):
+    """dm_jacobi_problem_desc of include/driftmi.h."""
+    _fields_ = [("Z", c_vp), ("ld", c_int), ("row0", c_int), ("nrows", c_int), ("ncols", c_int), ("gc0", c_int),
+                ("gc1", c_int)]
+
+
+class JacobiOptions(ctypes.Structure):
+    """dm_jacobi_options of include/driftmi.h."""
+    _fields_ = [("unconverged", c_int), ("drop_below", c_dbl), ("one_stage_eig", c_int), ("subspace_cut", c_dbl),
+                ("subspace_margin", c_dbl)]
+
+
 # name -> (restype, argtypes); mirrors include/driftmi.h one to one
 SIGNATURES = {
     "dm_ctx_create": (c_int, [c_int, c_sz, c_vp, ctypes.POINTER(c_vp)]),
@@ -50,6 +62,9 @@ SIGNATURES = {
         c_int, [c_vp, c_int, c_int, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int]),
     "dm_jacobi_rows_batched": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_i64, c_int, c_vp, ctypes.POINTER(c_int)]),
+    "dm_jacobi_rows_problems": (
+        c_int, [c_vp, c_int, ctypes.POINTER(JacobiProblemDesc), c_vp, c_int, ctypes.POINTER(JacobiOptions),
+                ctypes.POINTER(c_int)]),
     "dm_jacobi_herm_batched": (
         c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_vp, ctypes.POINTER(c_int)]),
     "dm_herm_eig_batched": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_vp]),
@@ -302,6 +317,44 @@ class Context(object):
         sw = c_int(0)
         self.check(self.lib.dm_jacobi_rows_batched(self.h, rows, cols, gc0, gc1, self.ptr(Z), ld, stride, batch,
                                                    self.ptr(sigma), ctypes.byref(sw)), "dm_jacobi_rows_batched")
+        return sigma, sw.value
+
+    def jacobi_rows_problems(self, Z, problems, sigma=None, sigma_stride=None, **opts):
+        """The ragged form of `jacobi_rows` (dm_jacobi_rows_problems).  Z: one complex128 device tensor that holds every
+        matrix; each problem is a dict with `off` (element offset of its matrix in Z), ld, row0, nrows, ncols, gc0, gc1.
+        Options by keyword: unconverged, drop_below, one_stage_eig, subspace_cut, subspace_margin (none given: the
+        library gets no option block).  Every problem must lie inside Z (a wrong offset would be an out-of-bounds access
+        on the device).  Returns (sigma (nprob, sigma_stride) f64 on the device, sweeps)."""
+        n = len(problems)
+        unknown = set(opts) - {f[0] for f in JacobiOptions._fields_}
+        if unknown:
+            raise ValueError("jacobi_rows_problems: unknown option(s) %s" % sorted(unknown))
+        if n and not (Z.is_complex() and Z.element_size() == 16 and Z.is_contiguous()):
+            raise ValueError("jacobi_rows_problems: a contiguous complex128 device tensor expected")
+        arr = (JacobiProblemDesc * max(n, 1))()
+        for q, p in zip(arr, problems):
+            off, ld, row0, nrows, ncols = (int(p[k]) for k in ("off", "ld", "row0", "nrows", "ncols"))
+            if min(off, ld, row0, nrows, ncols) < 0 or ncols > ld:
+                raise ValueError("jacobi_rows_problems: negative size or ncols > ld")
+            if nrows > 0 and ncols > 0 and off + (row0 + nrows - 1) * ld + ncols > int(Z.numel()):
+                raise ValueError("jacobi_rows_problems: a problem reaches outside its buffer")
+            q.Z = Z.data_ptr() + 16 * off if nrows > 0 else None
+            q.ld, q.row0, q.nrows, q.ncols, q.gc0, q.gc1 = ld, row0, nrows, ncols, int(p["gc0"]), int(p["gc1"])
+        if sigma_stride is None:
+            sigma_stride = max([int(p["nrows"]) for p in problems] + [1])
+        if sigma is None:
+            sigma = self.zeros((max(n, 1), sigma_stride), np.float64)
+        elif n and (sigma.dtype != self.torch.float64 or not sigma.is_contiguous() or sigma.numel() < n * sigma_stride):
+            raise ValueError("jacobi_rows_problems: sigma must be a contiguous float64 tensor of nprob * sigma_stride")
+        o = None
+        if opts:
+            o = JacobiOptions(int(bool(opts.get("unconverged", False))), float(opts.get("drop_below", 0.0)),
+                              int(bool(opts.get("one_stage_eig", False))), float(opts.get("subspace_cut", 0.0)),
+                              float(opts.get("subspace_margin", 0.0)))
+        sw = c_int(0)
+        self.check(self.lib.dm_jacobi_rows_problems(self.h, n, arr, self.ptr(sigma), int(sigma_stride),
+                                                    ctypes.byref(o) if o is not None else None, ctypes.byref(sw)),
+                   "dm_jacobi_rows_problems")
         return sigma, sw.value
 
     def jacobi_herm(self, C, n, ldc, strideC=0, batch=1):

@@ -83,6 +83,29 @@ int dm_jacobi_rows_batched(dm_ctx* ctx, int rows, int cols, int gc0, int gc1, vo
   return dm_jacobi_rows(ctx, ps, sigma_dev, rows > 0 ? rows : 1, sweeps_host);
 }
 
+int dm_jacobi_rows_problems(dm_ctx* ctx, int nprob, const dm_jacobi_problem_desc* probs, double* sigma_dev,
+                            int sigma_stride, const dm_jacobi_options* opts, int* sweeps_host) {
+  if (!ctx) return DM_EARG;
+  DM_ARG(ctx, nprob >= 0 && (nprob == 0 || (probs && sigma_dev)) && sigma_stride >= 0);
+  std::vector<dm_jac_problem> ps(nprob);
+  for (int i = 0; i < nprob; ++i) {
+    const dm_jacobi_problem_desc& p = probs[i];
+    DM_ARG(ctx, 0 <= p.gc0 && p.gc0 <= p.gc1 && p.gc1 <= p.ncols && p.ncols <= p.ld);
+    DM_ARG(ctx, p.row0 >= 0 && p.nrows >= 0 && p.nrows <= sigma_stride && (p.nrows == 0 || p.Z));
+    ps[i] = dm_jac_problem{reinterpret_cast<cplx*>(p.Z), p.ld, p.row0, p.nrows, p.ncols, p.gc0, p.gc1};
+  }
+  dm_jac_rows_opts o;
+  if (opts) {
+    DM_ARG(ctx, opts->drop_below >= 0.0 && opts->subspace_cut >= 0.0 && opts->subspace_margin >= 0.0);
+    o.unconverged = opts->unconverged != 0;
+    o.drop_below = opts->drop_below;
+    o.one_stage_eig = opts->one_stage_eig != 0;
+    o.subspace_cut = opts->subspace_cut;
+    if (opts->subspace_margin > 0.0) o.subspace_margin = opts->subspace_margin;
+  }
+  return dm_jacobi_rows(ctx, ps, sigma_dev, sigma_stride, sweeps_host, &o);
+}
+
 int dm_jacobi_herm_batched(dm_ctx* ctx, int n, void* C, int ldc, int64_t strideC, void* W, int ldw,
                            int64_t strideW, int batch, double* evals_dev, int* sweeps_host) {
   if (!ctx) return DM_EARG;

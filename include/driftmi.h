@@ -117,6 +117,39 @@ int dm_ztrsm_left_lower_batched(dm_ctx* ctx, int n, int nrhs, const void* L_dev,
 int dm_jacobi_rows_batched(dm_ctx* ctx, int rows, int cols, int gc0, int gc1, void* Z_dev, int ld, int64_t stride,
                            int batch, double* sigma_dev, int* sweeps_host);
 
+/* The same engine for a ragged list of problems with its options (what the SVD chain hands it; exposed for the
+ * parity tests).  Problem i mixes the rows [row0, row0 + nrows) of the row-major matrix at Z (device c128, leading
+ * dimension ld) over its columns [0, ncols) until they are orthogonal with respect to the columns [gc0, gc1), and
+ * sorts them by descending norm over those columns; nothing outside that row and column range is read or written.
+ * Needs 0 <= gc0 <= gc1 <= ncols <= ld, row0 >= 0 and 0 <= nrows <= sigma_stride; Z may be NULL where nrows = 0.
+ * sigma_dev gets the nrows row norms of problem i at i * sigma_stride (the rest of its stride is left alone).
+ * Options (opts NULL: all defaults):
+ *   unconverged      non-zero: the rows are known not to be orthogonal yet, the measuring pass is skipped
+ *   drop_below       > 0: rows that end below drop_below * (largest row norm) are kept out of the sweeps
+ *   one_stage_eig    non-zero: the Gram eigenproblems of the preconditioner on the one-stage tridiagonalisation
+ *   subspace_cut     > 0: only split the rows at subspace_cut * (largest row norm), no order inside the two sides
+ *   subspace_margin  how far above the cut the last preconditioner level may begin, in units of the cut
+ *                    (0: the engine's default, 3.2e5)
+ * The orthogonality reached is RELATIVE, |<y_i, y_j>| <= tol |y_i| |y_j|.  Synchronises.
+ * sweeps_host (optional) receives the sweep count.
+ * Exposed for the parity tests: this is the engine behind dm_svd_chain and dm_jacobi_rows_batched, as the chain calls
+ * it.  On its own it is not a drop-in for a reference call site (matrix_image / matrix_nullspace of
+ * drift/core/beamtransfer.py:68-143 also cut at rtol and take the null space from full_matrices: dm_svd_chain does
+ * that around this engine). */
+typedef struct dm_jacobi_problem_desc {
+  void* Z;
+  int ld, row0, nrows, ncols, gc0, gc1;
+} dm_jacobi_problem_desc;
+typedef struct dm_jacobi_options {
+  int unconverged;
+  double drop_below;
+  int one_stage_eig;
+  double subspace_cut;
+  double subspace_margin;
+} dm_jacobi_options;
+int dm_jacobi_rows_problems(dm_ctx* ctx, int nprob, const dm_jacobi_problem_desc* probs_host, double* sigma_dev,
+                            int sigma_stride, const dm_jacobi_options* opts /* may be NULL */, int* sweeps_host);
+
 /* Two-sided block-Jacobi eigendecomposition of `batch` Hermitian n x n matrices:
  * on return C is diagonal (to working accuracy), W_dev (n x n per matrix, rows
  * are eigenvectors^H) holds the accumulated unitary, evals_dev the unsorted

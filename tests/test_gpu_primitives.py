@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import eig_cases as ec
+import jacobi_cases as jc
 
 pytestmark = pytest.mark.gpu
 
@@ -115,6 +116,10 @@ def test_jacobi_rows(ctx, rows, cols):
         assert np.abs(G - np.diag(np.diag(G))).max() <= 1e-11 * ref[0] ** 2
         # same row space / Gram: Z^H Z == A^H A
         assert np.abs(Z[b].conj().T @ Z[b] - A[b].conj().T @ A[b]).max() <= 1e-11 * ref[0] ** 2
+        # and the engine's contract (tests/jacobi_cases.py; no identity columns here: c, d, e) — orthogonality relative to the
+        # two rows of every pair, not to sigma_0
+        prob = dict(off=b * rows * cols, ld=cols, row0=0, nrows=rows, ncols=cols, gc0=0, gc1=cols, acols=cols)
+        jc.check_rows_result(A[b], A.reshape(-1), Z.reshape(-1), s[b], prob, sweeps, parts="cde")
     assert sweeps < 30
 
 
