@@ -111,6 +111,7 @@ SIGNATURES = {
     "dm_sky_draw": (
         c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_i64, ctypes.POINTER(c_int), ctypes.POINTER(c_i64), c_int, c_int,
                 c_int, ctypes.c_uint64, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64]),
+    "dm_source_alm": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_sz]),
     "dm_bt_beam_cyl": (
         c_int, [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int,
                 ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_dbl, c_vp]),
@@ -759,6 +760,36 @@ def _sky_draw(self, T, jglobal, rowoff, nfreq, row0, nrows, M, seed, stream, fir
     self.check(rc, "dm_sky_draw")
 
 
+def _source_alm(self, z, sth, phi, flux, lmax, m_lo, m_hi, out=None, max_bytes=2 << 30):
+    """a_lm (nf, npol, lmax + 1, m_hi - m_lo + 1) c128 on the device of point sources at (z, sth, phi) (nsrc each) with
+    fluxes (nf, npol, nsrc), npol 1 or 4; numpy or float64 device tensors (dm_source_alm in include/driftmi.h)."""
+    def dev(a):
+        if not hasattr(a, "data_ptr"):
+            a = self.to_device(np.asarray(a, dtype=np.float64))
+        if a.dtype != self.torch.float64:
+            raise ValueError("source_alm: float64 expected")
+        return a.contiguous()
+
+    z, sth, phi, flux = dev(z), dev(sth), dev(phi), dev(flux)
+    if flux.dim() != 3:
+        raise ValueError("source_alm: flux (nf, npol, nsrc) expected")
+    nf, npol, nsrc = (int(v) for v in flux.shape)
+    if not (tuple(z.shape) == tuple(sth.shape) == tuple(phi.shape) == (nsrc,)):
+        raise ValueError("source_alm: z, sth and phi need one entry per source")
+    lmax, m_lo, m_hi = int(lmax), int(m_lo), int(m_hi)
+    if lmax < 0 or not 0 <= m_lo <= m_hi:
+        raise ValueError("source_alm: lmax >= 0 and 0 <= m_lo <= m_hi expected")
+    shape = (nf, npol, lmax + 1, m_hi - m_lo + 1)
+    if out is None:
+        out = self.empty(shape, np.complex128)
+    if tuple(out.shape) != shape or not out.is_contiguous() or not (out.is_complex() and out.element_size() == 16):
+        raise ValueError("source_alm: out must be a contiguous %s complex128 tensor" % (shape,))
+    rc = self.lib.dm_source_alm(self.h, nsrc, self.ptr(z), self.ptr(sth), self.ptr(phi), nf, npol, self.ptr(flux), lmax, m_lo,
+                                m_hi, self.ptr(out), int(max_bytes))
+    self.check(rc, "dm_source_alm")
+    return out
+
+
 def _psmc_moments(self, q):
     """(mean (nblk, nq), covariance (nblk, nq, nq)) on the device of q (nblk, nq, ns) f64; see dm_psmc_moments."""
     nblk, nq, ns = [int(x_) for x_ in q.shape]
@@ -795,6 +826,7 @@ Context.psmc_draw = _psmc_draw
 Context.psmc_moments = _psmc_moments
 Context.psmc_alt = _psmc_alt
 Context.sky_draw = _sky_draw
+Context.source_alm = _source_alm
 
 
 def _project_diag(self, beam_ut, svnum, dmat, out, out_off, alpha=1.0, accumulate=False):

@@ -1105,36 +1105,6 @@ frame3 make_frame(const double* xhat, const double* yhat, const double* zhat) {
   return f;
 }
 
-// ---- which Stokes term takes which table ----------------------------------------------------------------------------
-// add(input Stokes, table, output Stokes, alpha_re, alpha_im, beta) for the terms of one pass.  Terms whose outputs
-// accumulate (E and B each take two products) go in separate passes = separate launches, so that no two tiles of one
-// launch touch the same C entries.  Analysis: T = lam . I, V = lam . V, E = W . Q - i X . U, B = W . U + i X . Q; the
-// synthesis (Q = W E - i X B, U = W B + i X E) and the Gram products (E' = K_P E - i K_X B, B' = K_P B + i K_X E) apply
-// the same Hermitian block.
-struct bt_tables {
-  double *T = nullptr, *W = nullptr, *X = nullptr;   // the scalar table and the spin-2 pair (polarised only)
-  double* operator[](int i) const { return i == 0 ? T : i == 1 ? W : X; }
-};
-// n doubles per table out of the workspace
-bool bt_tables_alloc(dm_ctx* ctx, bool polarised, size_t n, bt_tables& t) {
-  t.T = dm_ws_alloc_t<double>(ctx, n);
-  if (polarised) { t.W = dm_ws_alloc_t<double>(ctx, n); t.X = dm_ws_alloc_t<double>(ctx, n); }
-  return t.T && (!polarised || (t.W && t.X));
-}
-template <class Add>
-void bt_stokes_terms(bool polarised, int pass, const bt_tables& t, double beta0, Add&& add) {
-  if (pass == 0) {
-    add(0, t.T, 0, 1.0, 0.0, beta0);
-    if (!polarised) return;
-    add(3, t.T, 3, 1.0, 0.0, beta0);
-    add(1, t.W, 1, 1.0, 0.0, beta0);
-    add(2, t.W, 2, 1.0, 0.0, beta0);
-  } else {
-    add(2, t.X, 1, 0.0, -1.0, 1.0);
-    add(1, t.X, 2, 0.0, 1.0, 1.0);
-  }
-}
-
 // ---- kernel choice of the fused ring transform ------------------------------------------------------------------------
 using bt_dft_fn = decltype(&bt_fused_dft_kernel<1, 1, 8>);   // (bt_fused_dft2_kernel has the same signature)
 using bt_fft_fn = decltype(&bt_fused_fft_kernel<1, 1, 256>);

@@ -135,14 +135,11 @@ __host__ __device__ inline double legendre_scaled_seed(int m, double s2, int* ex
   return v;
 }
 
-// Legendre tables: lam[loff[m] + (l-m)*nring + r] = w * lambda_lm(theta_r), same for W and X (polarised)
-__global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, double w, const size_t* __restrict__ loff_,
-                                   double* __restrict__ lam, double* __restrict__ Wt, double* __restrict__ Xt) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  const int m = m_lo + blockIdx.y;
-  const size_t* loff = loff_ - m_lo;  // tables are stored for m_lo .. mmax
-  if (r >= g.nring || m > mmax || m > lmax) return;
-  const double z = g.cth[r], st = g.sth[r];
+// One column of the Legendre tables: out[(l - m) * stride] = w * lambda_lm(z), l = m .. lmax, and the same for W and X at
+// wo, xo (nullptr: scalar table only); st = sin(theta) > 0 wherever W and X are asked for.  The arithmetic of every
+// table of the package: the ring tables (bt_legendre_kernel) and the tables at source positions (dm_sources.hip).
+__device__ __forceinline__ void legendre_column(double z, double st, int lmax, int m, double w, size_t stride,
+                                                double* __restrict__ out, double* __restrict__ wo, double* __restrict__ xo) {
   const double s2 = st * st;
   double logpre = 0.5 * (log(2.0 * m + 1.0) - log(4.0 * kPi));
   for (int k = 1; k <= m; ++k) logpre += 0.5 * log((2.0 * k - 1.0) / (2.0 * k));
@@ -153,23 +150,19 @@ __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, dou
   int ex = 0;
   if (m > 0 && lmm < kDblMin) lmm = legendre_scaled_seed(m, s2, &ex);
   if (m & 1) lmm = -lmm;
-  double* out = lam + loff[m];
-  const size_t nr = g.nring;
   double pm2 = 0.0, pm1 = lmm;  // lambda_{l-2}, lambda_{l-1} as l advances
-  out[r] = w * ldexp(lmm, ex);
-  if (Wt) {
-    double* wo = Wt + loff[m];
-    double* xo = Xt + loff[m];
+  out[0] = w * ldexp(lmm, ex);
+  if (wo) {
     // l = m term (needs lambda_{m-1,m} = 0)
     if (m >= 2) {
       const double l = m;
       const double nl = 2.0 * sqrt(1.0 / ((l - 1.0) * l * (l + 1.0) * (l + 2.0)));
       const double lm0 = ldexp(lmm, ex);
-      wo[r] = -w * nl * (-((l - l * l) / s2 + 0.5 * l * (l - 1.0)) * lm0);
-      xo[r] = w * nl * (l / s2) * ((l - 1.0) * z * lm0);
+      wo[0] = -w * nl * (-((l - l * l) / s2 + 0.5 * l * (l - 1.0)) * lm0);
+      xo[0] = w * nl * (l / s2) * ((l - 1.0) * z * lm0);
     } else {
-      wo[r] = 0.0;
-      xo[r] = 0.0;
+      wo[0] = 0.0;
+      xo[0] = 0.0;
     }
   }
   for (int l = m + 1; l <= lmax; ++l) {
@@ -182,8 +175,8 @@ __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, dou
       cur = a * (z * pm1 - b * pm2);
     }
     if (ex < 0 && fabs(cur) > kTwoP512) { cur *= kTwoM512; pm1 *= kTwoM512; ex += 512; }
-    out[(size_t)(l - m) * nr + r] = w * ldexp(cur, ex);
-    if (Wt) {
+    out[(size_t)(l - m) * stride] = w * ldexp(cur, ex);
+    if (wo) {
       double wv = 0.0, xv = 0.0;
       if (l >= 2) {
         const double dl = l, dm = m;
@@ -192,12 +185,23 @@ __global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, dou
         wv = -nl * (-((dl - dm * dm) / s2 + 0.5 * dl * (dl - 1.0)) * cur + c * z / s2 * pm1);
         xv = nl * (dm / s2) * ((dl - 1.0) * z * cur - c * pm1);
       }
-      (Wt + loff[m])[(size_t)(l - m) * nr + r] = w * ldexp(wv, ex);
-      (Xt + loff[m])[(size_t)(l - m) * nr + r] = w * ldexp(xv, ex);
+      wo[(size_t)(l - m) * stride] = w * ldexp(wv, ex);
+      xo[(size_t)(l - m) * stride] = w * ldexp(xv, ex);
     }
     pm2 = pm1;
     pm1 = cur;
   }
+}
+
+// Legendre tables: lam[loff[m] + (l-m)*nring + r] = w * lambda_lm(theta_r), same for W and X (polarised)
+__global__ void bt_legendre_kernel(ring_geo g, int lmax, int m_lo, int mmax, double w, const size_t* __restrict__ loff_,
+                                   double* __restrict__ lam, double* __restrict__ Wt, double* __restrict__ Xt) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  const int m = m_lo + blockIdx.y;
+  const size_t* loff = loff_ - m_lo;  // tables are stored for m_lo .. mmax
+  if (r >= g.nring || m > mmax || m > lmax) return;
+  legendre_column(g.cth[r], g.sth[r], lmax, m, w, (size_t)g.nring, lam + loff[m] + r, Wt ? Wt + loff[m] + r : nullptr,
+                  Wt ? Xt + loff[m] + r : nullptr);
 }
 
 struct geo_host {
@@ -244,6 +248,36 @@ int upload_geo(dm_ctx* ctx, int nside, const double* cth, const double* sth, geo
   gh.g.nphi = reinterpret_cast<const int*>(d + 3 * (size_t)nring);
   gh.g.start = gh.g.nphi + nring;
   return DM_OK;
+}
+
+// ---- which Stokes term takes which table ----------------------------------------------------------------------------
+// add(input Stokes, table, output Stokes, alpha_re, alpha_im, beta) for the terms of one pass.  Terms whose outputs
+// accumulate (E and B each take two products) go in separate passes = separate launches, so that no two tiles of one
+// launch touch the same C entries.  Analysis: T = lam . I, V = lam . V, E = W . Q - i X . U, B = W . U + i X . Q; the
+// synthesis (Q = W E - i X B, U = W B + i X E) and the Gram products (E' = K_P E - i K_X B, B' = K_P B + i K_X E) apply
+// the same Hermitian block.
+struct bt_tables {
+  double *T = nullptr, *W = nullptr, *X = nullptr;   // the scalar table and the spin-2 pair (polarised only)
+  double* operator[](int i) const { return i == 0 ? T : i == 1 ? W : X; }
+};
+// n doubles per table out of the workspace
+bool bt_tables_alloc(dm_ctx* ctx, bool polarised, size_t n, bt_tables& t) {
+  t.T = dm_ws_alloc_t<double>(ctx, n);
+  if (polarised) { t.W = dm_ws_alloc_t<double>(ctx, n); t.X = dm_ws_alloc_t<double>(ctx, n); }
+  return t.T && (!polarised || (t.W && t.X));
+}
+template <class Add>
+void bt_stokes_terms(bool polarised, int pass, const bt_tables& t, double beta0, Add&& add) {
+  if (pass == 0) {
+    add(0, t.T, 0, 1.0, 0.0, beta0);
+    if (!polarised) return;
+    add(3, t.T, 3, 1.0, 0.0, beta0);
+    add(1, t.W, 1, 1.0, 0.0, beta0);
+    add(2, t.W, 2, 1.0, 0.0, beta0);
+  } else {
+    add(2, t.X, 1, 0.0, -1.0, 1.0);
+    add(1, t.X, 2, 0.0, 1.0, 1.0);
+  }
 }
 
 }  // namespace

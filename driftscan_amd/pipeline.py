@@ -2,7 +2,8 @@
 
 The counterpart of ``drift.pipeline.pipeline.PipelineManager`` (drift/pipeline/pipeline.py:20-198), by behaviour: the same
 sections — ``config`` (the properties below), ``timestreams`` (entries with ``name``, ``directory``, optionally
-``output_directory`` and a ``simulate`` block of arguments for ``timestream.simulate`` plus its ``product_directory``)
+``output_directory`` and a ``simulate`` block of arguments for ``timestream.simulate`` plus its ``product_directory``;
+the files of its ``maps`` and ``sources`` lists go through ``fixpath``)
 and optionally ``crosspower`` (entries with ``psname``, ``klname``, ``timestreams``, ``psfile``) — the same defaults,
 exceptions and methods.  Two deliberate differences:
 
@@ -110,6 +111,8 @@ class PipelineManager(config.Reader):
             products = self._products(simconf.pop("product_directory", self.product_directory))
             if "maps" in simconf:
                 simconf["maps"] = [fixpath(m) for m in simconf["maps"]]
+            if "sources" in simconf:
+                simconf["sources"] = [fixpath(c) for c in simconf["sources"]]
             timestream.simulate(products, ts.directory, **simconf)
 
     def generate(self):

@@ -11,6 +11,9 @@ them from the arrays every other stage works from: ``[pol, pol, l, freq, freq]``
   key = seed, counter ``(p F + f, (l << 16) | m, r, stream)``, complex with E|z|^2 = 1 for m > 0 and real with
   E z^2 = 1 for m = 0; E and B are zero for l < 2 and everything is zero for m > l.
 
+Point sources are the non-Gaussian skies: ``source_alm`` gives the exact band-limited a_lm of a
+catalogue on the device (``dm_source_alm``), ``source_alm_host`` is its numpy statement and oracle.
+
 ``draw_alm`` does this on the device (``dm_sky_draw``: the draws are made inside the kernel and multiplied on the matrix
 cores); ``groups``, ``covariance_roots(device=False)``, ``draws_host`` and ``correlate_host`` restate it in numpy and need
 no GPU.
@@ -231,3 +234,186 @@ def write_sky(fname, maps):
         raise ValueError("write_sky: one sky [freq, pol, pixel]")
     with storage.File(fname, "w") as f:
         f.create_dataset("map", data=maps)
+
+
+# ---- point sources ----------------------------------------------------------------------------
+SOURCE_CHUNK = 1024          # sources per product of dm_source_alm (SRC_CHUNK of dm_sources.hip): fixes the summation order
+_C_LIGHT = 299792458.0       # m / s
+_K_BOLTZMANN = 1.380649e-23  # J / K
+_CAT_KEYS = ("theta", "phi", "flux", "nu0", "index", "curvature")
+
+
+def read_catalogue(cat):
+    """A catalogue as a dict of float64 arrays: ``theta``, ``phi`` (nsrc, rad), ``flux`` (nsrc, 1 or 4) in Jy at ``nu0``
+    (MHz, a scalar or one per source), ``index`` and ``curvature`` (nsrc; the latter 0 when absent).  ``cat``: such a dict,
+    or the name of a file written by `write_catalogue` (`.npz` or HDF5 through `storage.File`)."""
+    if isinstance(cat, (str, bytes)) or hasattr(cat, "__fspath__"):
+        from . import storage
+
+        with storage.File(cat, "r") as f:
+            cat = {k: np.asarray(f[k][:]) for k in _CAT_KEYS if k in f}
+    missing = [k for k in ("theta", "phi", "flux", "nu0", "index") if k not in cat]
+    if missing:
+        raise ValueError("source catalogue without %s" % ", ".join(missing))
+    theta = np.asarray(cat["theta"], dtype=np.float64).reshape(-1)
+    n = theta.size
+    flux = np.asarray(cat["flux"], dtype=np.float64)
+    flux = flux.reshape(n, 1) if flux.ndim == 1 else flux
+    if flux.shape not in ((n, 1), (n, 4)):
+        raise ValueError("source catalogue: flux (nsrc, 1 or 4) expected, got %s" % (flux.shape,))
+    out = dict(theta=theta, flux=flux)
+    for k in ("phi", "nu0", "index", "curvature"):
+        v = np.asarray(cat.get(k, 0.0), dtype=np.float64).reshape(-1)
+        if v.size not in (1, n):
+            raise ValueError("source catalogue: %s needs one value, or one per source" % k)
+        out[k] = np.broadcast_to(v, (n,)).copy()
+    if n and not (np.all(theta >= 0.0) and np.all(theta <= np.pi)):
+        raise ValueError("source catalogue: theta outside [0, pi]")
+    if n and not np.all(out["nu0"] > 0.0):
+        raise ValueError("source catalogue: nu0 must be positive")
+    return out
+
+
+def write_catalogue(fname, cat):
+    """Write a catalogue (see `read_catalogue`) as the file `timestream.simulate(sources=[...])` reads."""
+    from . import storage
+
+    cat = read_catalogue(cat)
+    with storage.File(fname, "w") as f:
+        for k in _CAT_KEYS:
+            f.create_dataset(k, data=cat[k])
+
+
+def source_spectra(cat, frequencies):
+    """Temperature x solid angle (nf, npol, nsrc) in K sr of the sources at ``frequencies`` (MHz):
+    S(nu) = S0 (nu / nu0)^(index + curvature ln(nu / nu0)) in Jy and T Omega = S 1e-26 c^2 / (2 k_B nu^2); every Stokes
+    parameter of a source follows the same spectrum."""
+    cat = read_catalogue(cat)
+    nu = np.asarray(frequencies, dtype=np.float64).reshape(-1)
+    x = np.log(nu[:, None] / cat["nu0"][None, :])                                       # (nf, nsrc)
+    s = np.exp((cat["index"][None, :] + cat["curvature"][None, :] * x) * x)
+    conv = 1e-26 * _C_LIGHT ** 2 / (2.0 * _K_BOLTZMANN * (nu * 1e6) ** 2)               # Jy -> K sr
+    return np.ascontiguousarray((conv[:, None] * s)[:, None, :] * cat["flux"].T[None, :, :])
+
+
+def random_catalogue(n, seed, flux_min=0.1, flux_max=100.0, gamma=2.5, index_mean=-0.7, index_sigma=0.2, pol_frac=0.0,
+                     nu0=600.0):
+    """A stand-in population of ``n`` sources (like the other sky models here: the shape of a radio-source population, not a
+    fitted one): isotropic positions, fluxes in [flux_min, flux_max] Jy at ``nu0`` MHz with dN/dS ~ S^-gamma by inverse
+    transform, Gaussian spectral indices.  pol_frac > 0 gives (I, Q, U, V) with linear polarisation pol_frac I at a
+    uniform angle and V = 0; pol_frac = 0 gives I alone.  Host numpy, reproducible by ``seed``."""
+    n = int(n)
+    if not 0.0 < flux_min <= flux_max:
+        raise ValueError("random_catalogue: 0 < flux_min <= flux_max expected")
+    rng = np.random.default_rng(seed)
+    z = rng.uniform(-1.0, 1.0, n)
+    phi = rng.uniform(0.0, 2.0 * np.pi, n)
+    u = rng.uniform(0.0, 1.0, n)
+    if gamma == 1.0:
+        s = flux_min * (flux_max / flux_min) ** u
+    else:
+        a = 1.0 - gamma
+        s = (flux_min ** a + u * (flux_max ** a - flux_min ** a)) ** (1.0 / a)
+    s = np.clip(s, flux_min, flux_max)
+    index = index_mean + index_sigma * rng.standard_normal(n)
+    if pol_frac:
+        chi = rng.uniform(0.0, np.pi, n)
+        flux = np.stack([s, pol_frac * s * np.cos(2.0 * chi), pol_frac * s * np.sin(2.0 * chi), np.zeros(n)], axis=1)
+    else:
+        flux = s[:, None]
+    return dict(theta=np.arccos(z), phi=phi, flux=flux, nu0=np.full(n, float(nu0)), index=index, curvature=np.zeros(n))
+
+
+def _source_arrays(theta, phi, flux):
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    phi = np.mod(np.asarray(phi, dtype=np.float64).reshape(-1), 2.0 * np.pi)            # [0, 2 pi) on entry
+    phi = np.where(phi >= 2.0 * np.pi, 0.0, phi)
+    flux = np.asarray(flux, dtype=np.float64)
+    if flux.ndim != 3 or flux.shape[1] not in (1, 4):
+        raise ValueError("point sources: flux (nf, 1 or 4, nsrc) expected, got %s" % (flux.shape,))
+    if not (theta.shape == phi.shape == (flux.shape[2],)):
+        raise ValueError("point sources: theta, phi and flux need one entry per source")
+    z, sth = np.cos(theta), np.sin(theta)
+    if flux.shape[1] == 4:
+        bad = np.nonzero((sth == 0.0) & (flux[:, 1:3] != 0.0).any(axis=(0, 1)))[0]
+        if bad.size:
+            raise ValueError("point sources: source %d lies at a pole (sin theta = 0) and is polarised: Q and U are "
+                             "undefined there" % bad[0])
+    return z, sth, phi, np.ascontiguousarray(flux)
+
+
+def _m_range(lmax, mmax, m_range):
+    if m_range is not None and mmax is not None:
+        raise ValueError("point sources: mmax or m_range, not both")
+    m_lo, m_hi = (0, lmax if mmax is None else min(int(mmax), lmax)) if m_range is None else (int(m_range[0]), int(m_range[1]))
+    if not 0 <= m_lo <= m_hi <= lmax:
+        raise ValueError("point sources: 0 <= m_lo <= m_hi <= lmax expected, got (%d, %d) with lmax %d" % (m_lo, m_hi, lmax))
+    return m_lo, m_hi
+
+
+def source_alm_host(theta, phi, flux, lmax, mmax=None, m_range=None):
+    """The a_lm (nf, npol, lmax + 1, nm) of point sources at (theta, phi) with temperature x solid angle ``flux``
+    (nf, npol, nsrc), npol = 1 (I -> T) or 4 (I, Q, U, V -> T, E, B, V), m = 0 .. mmax (or m_range, inclusive):
+
+        a^T_lm = sum_s I_s lambda_lm(cos theta_s) e^{-i m phi_s}                      (a^V alike)
+        a^E_lm = sum_s e^{-i m phi_s} (W_lm Q_s + i X_lm U_s),   a^B_lm = sum_s e^{-i m phi_s} (W_lm U_s - i X_lm Q_s)
+
+    with `healpix.lambda_lm` / `wx_lm`: the coefficients whose synthesis `healpix.sphtrans_inv_sky_host`, summed against
+    the fluxes at the sources, gives sum_pol sum_l [Re(a_l0 b*_l0) + 2 sum_{m > 0} Re(a_lm b*_lm)].  Plain numpy: the oracle
+    of `source_alm`, for any input."""
+    from . import healpix
+
+    z, sth, phi, flux = _source_arrays(theta, phi, flux)
+    lmax = int(lmax)
+    m_lo, m_hi = _m_range(lmax, mmax, m_range)
+    nf, npol, nsrc = flux.shape
+    out = np.zeros((nf, npol, lmax + 1, m_hi - m_lo + 1), dtype=np.complex128)
+    if nsrc == 0:
+        return out
+    off = sth > 0.0                                                  # W and X exist off the poles only
+    for m in range(m_lo, m_hi + 1):
+        ph = np.cos(m * phi) - 1j * np.sin(m * phi)
+        lam = healpix.lambda_lm(lmax, m, z)                          # (L - m, nsrc)
+        fp = flux * ph[None, None, :]
+        o = out[:, :, m:, m - m_lo]
+        o[:, 0] = fp[:, 0] @ lam.T
+        if npol == 4:
+            o[:, 3] = fp[:, 3] @ lam.T
+            W, X = healpix.wx_lm(lmax, m, z[off])
+            q, u = fp[:, 1][:, off], fp[:, 2][:, off]
+            o[:, 1] = q @ W.T + 1j * (u @ X.T)
+            o[:, 2] = u @ W.T - 1j * (q @ X.T)
+    return out
+
+
+def source_alm(cat_or_arrays, lmax, frequencies=None, mmax=None, m_range=None, freqs=None, to_host=True,
+               max_bytes=2 << 30):
+    """The exact band-limited a_lm of point sources on the device (`dm_source_alm`): (nf, npol, lmax + 1, nm) complex128,
+    polarisations T or T, E, B, V, m = 0 .. min(mmax, lmax) or ``m_range = (m_lo, m_hi)`` inclusive — the layout
+    `draw_alm` gives per realisation.  No map, no nside: a source sits where the catalogue puts it.
+
+    ``cat_or_arrays``: a catalogue (`read_catalogue`: a dict or a file name) evaluated at ``frequencies`` (MHz) through
+    `source_spectra`, or arrays ``(theta, phi, flux)`` with flux (nf, npol, nsrc) in K sr.  ``freqs`` (sorted indices)
+    computes those frequency rows only.  ``to_host=False`` returns the device tensor.  ``max_bytes`` bounds the tables
+    alive on the device at once and has no influence on the bits of the result."""
+    if isinstance(cat_or_arrays, (tuple, list)):
+        theta, phi, flux = cat_or_arrays
+    else:
+        if frequencies is None:
+            raise ValueError("source_alm: a catalogue needs the frequencies (MHz) to evaluate its spectra at")
+        cat = read_catalogue(cat_or_arrays)
+        theta, phi, flux = cat["theta"], cat["phi"], source_spectra(cat, frequencies)
+    flux = np.asarray(flux, dtype=np.float64)
+    if freqs is not None:
+        sel = [int(f) for f in freqs]
+        if flux.ndim != 3 or sorted(set(sel)) != sel or (sel and not 0 <= sel[0] <= sel[-1] < flux.shape[0]):
+            raise ValueError("freqs must be sorted, distinct frequency indices")
+        flux = flux[sel]
+    z, sth, phi, flux = _source_arrays(theta, phi, flux)
+    lmax = int(lmax)
+    m_lo, m_hi = _m_range(lmax, mmax, m_range)
+    from .device import get_context
+
+    ctx = get_context()
+    out = ctx.source_alm(z, sth, phi, flux, lmax, m_lo, m_hi, max_bytes=max_bytes)
+    return ctx.to_host(out) if to_host else out

@@ -630,14 +630,42 @@ def _sky_covariance(m, model, klname):
     return make(tel.lmax, tel.frequencies, tel.num_pol_sky)
 
 
+def _as_sources(sources):
+    return (sources,) if isinstance(sources, (str, bytes, dict)) else tuple(sources)
+
+
+def _sources_alm(sources, tel, freqs, to_host):
+    """Sum of the exact a_lm (len(freqs), num_pol_sky, lmax + 1, mmax + 1) of the point-source catalogues `sources`
+    (`skysim.source_alm`) at the telescope's frequencies `freqs`; a device tensor with to_host=False.  An unpolarised
+    telescope takes I alone, an unpolarised catalogue has zero Q, U, V."""
+    from . import skysim
+
+    npol = int(tel.num_pol_sky)
+    total = None
+    for cat in sources:
+        cat = skysim.read_catalogue(cat)
+        flux = skysim.source_spectra(cat, np.asarray(tel.frequencies, dtype=np.float64)[list(freqs)])
+        if npol == 1:
+            flux = flux[:, :1]
+        elif flux.shape[1] == 1:
+            flux = np.concatenate([flux, np.zeros((flux.shape[0], 3, flux.shape[2]))], axis=1)
+        a = skysim.source_alm((cat["theta"], cat["phi"], flux), int(tel.lmax), mmax=int(tel.mmax), to_host=to_host)
+        if a.shape[1] != npol:
+            a = a[:, :npol] if to_host else a[:, :npol].contiguous()
+        total = a if total is None else total + a
+    return total
+
+
 def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=(), klname=None, sky_seed=0,
-             sky_realisation=0, **kwargs):
+             sky_realisation=0, sources=(), **kwargs):
     """Simulated timestream of the telescope of ProductManager `m` (timestream.py:645-829).
 
     maps: list of files holding a dataset `map` [freq, pol, pixel] whose sum is the sky; ndays = 0: no noise;
     resolution = 0: 2 mmax + 1 time samples.  skymodels: any of "signal", "foreground" — a Gaussian realisation
     (`sky_seed`, `sky_realisation`) of that covariance of KL transform `klname` is drawn on the device (`skysim.draw_alm`,
-    every rank the rows of its own frequencies) and its a_lm are added to those of the maps.  Returns the Timestream."""
+    every rank the rows of its own frequencies) and its a_lm are added to those of the maps.  sources: point-source
+    catalogues (dicts or files, `skysim.read_catalogue`) whose exact a_lm (`skysim.source_alm`) are added too.  Returns
+    the Timestream."""
     bt = m.beamtransfer
     tel = bt.telescope
     lmax, mmax, nfreq, npol = tel.lmax, tel.mmax, tel.nfreq, tel.num_pol_sky
@@ -651,7 +679,8 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
     col_vis = np.zeros((tel.npairs, lfreq, ntime), dtype=np.complex128)
 
     skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
-    if len(maps) > 0 or len(skymodels) > 0:
+    sources = _as_sources(sources)
+    if len(maps) > 0 or len(skymodels) > 0 or len(sources) > 0:
         # The reference's two MPI transposes (timestream.py:700-760): every rank transforms the maps of ITS frequencies,
         # the a_lm are regrouped by m, every rank projects ITS m through the beam (all frequencies of an m in one grouped
         # product on the device), and the visibilities come back regrouped by frequency.
@@ -671,6 +700,8 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
             cv = _sky_covariance(m, model, klname)
             if lfreq:   # straight to a_lm (no map in between), only the m the telescope measures
                 alm_loc[..., : mmax + 1] += skysim.draw_alm(cv, 1, sky_seed, stream, sky_realisation, mmax, local_freq)[0]
+        if lfreq and len(sources) > 0:
+            alm_loc[..., : mmax + 1] += _sources_alm(sources, tel, local_freq, True)
         got = parallel.exchange([np.ascontiguousarray(alm_loc[..., m_of[r]]) for r in range(nranks)])
         my_m = m_of[me]
         alm_m = np.zeros((nfreq, npol, lmax + 1, len(my_m)), dtype=np.complex128)
@@ -745,7 +776,7 @@ def _sim_ntime(tel, resolution):
 
 
 def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
-                       out=None):
+                       out=None, sources=()):
     """The passes of `simulate_visibilities`: yields (r0, device tensor (R, nf, npairs, ntime)) for the realisations
     first + r0 .. first + r0 + R - 1, R <= BLOCKVEC_MAX_R.  With `out` (nreal, nf, npairs, ntime) the groups are views of
     it; without, ONE buffer is used for every group (the caller is done with a group when it asks for the next)."""
@@ -764,7 +795,8 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
     nreal, first = int(nreal), int(first)
     nf = len(freqs)
     skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
-    have_sky = len(maps) > 0 or len(skymodels) > 0
+    sources = _as_sources(sources)
+    have_sky = len(maps) > 0 or len(skymodels) > 0 or len(sources) > 0
     if nf == 0 or nreal <= 0:
         return
     log = sim_log
@@ -786,6 +818,9 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
                     skymap = part if skymap is None else skymap + part
                 alm = healpix.sphtrans_sky(skymap, lmax)                       # (nf, npol, L, L): [l, m]
                 fixed = ctx.to_device(np.ascontiguousarray(alm[..., : mmax + 1]))
+            if len(sources) > 0:   # fixed like the maps, and never on the host
+                a = _sources_alm(sources, tel, freqs, False)
+                fixed = a if fixed is None else fixed.add_(a)
             for model in skymodels:
                 stream = skysim.STREAM_SKY_SIGNAL if model == "signal" else skysim.STREAM_SKY_FOREGROUND
                 cv = _sky_covariance(m, model, klname)
@@ -834,14 +869,14 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
 
 
 def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None, sky_seed=0,
-                          first=0, freqs=None, chunk_gb=4.0):
+                          first=0, freqs=None, chunk_gb=4.0, sources=()):
     """`nreal` simulated timestreams of the telescope of ProductManager `m` as ONE device tensor
     (nreal, len(freqs), npairs, ntime): what `simulate` writes per frequency, for many statistically independent data
     sets, without leaving the device between the draws and the result.
 
     Realisation first + i uses `sky_realisation = first + i` of every model of `skymodels` ("signal", "foreground": the
-    a_lm of `skysim.draw_alm` with `sky_seed`) and noise realisation first + i of `seed`; `maps` are fixed skies shared
-    by all.  `freqs` (sorted; default: this rank's share of the frequencies) are the rows computed: every draw is
+    a_lm of `skysim.draw_alm` with `sky_seed`) and noise realisation first + i of `seed`; `maps` and `sources`
+    (point-source catalogues, `skysim.source_alm`) are fixed skies shared by all.  `freqs` (sorted; default: this rank's share of the frequencies) are the rows computed: every draw is
     counter based, so a rank draws, projects and synthesises its own frequencies and the union of the ranks' results is
     the single-process result — there are no collectives.
 
@@ -859,13 +894,13 @@ def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, s
     freqs = _sim_freqs(tel, freqs)
     out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.npairs), _sim_ntime(tel, resolution)), np.complex128)
     for _ in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                chunk_gb, out=out):
+                                chunk_gb, out=out, sources=sources):
         pass
     return out
 
 
 def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None,
-                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0):
+                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=()):
     """`simulate_visibilities` written out: realisation first + i as the Timestream directory
     `outdir/real_%04d` % (first + i), each with the per-frequency files, datasets and attributes of `simulate` and the
     saved object.  Every rank writes its own frequencies (one device-to-host copy per group of up to 8 realisations),
@@ -889,7 +924,7 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     tss = [Timestream(os.path.join(outdir, "real_%04d" % (first + i)), m) for i in range(max(nreal, 0))]
     for r0, grp in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                      chunk_gb):
+                                      chunk_gb, sources=sources):
         with _StepTimer(sim_log, "download"):
             host = ctx.to_host(grp)
         with _StepTimer(sim_log, "write"):

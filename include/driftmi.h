@@ -374,6 +374,23 @@ int dm_sky_draw(dm_ctx* ctx, int n, int L, int M, const double* T_dev, int ldT, 
                 int stream, int first, int nreal, void* out_dev, int64_t stride_real, int64_t stride_l,
                 int64_t stride_m);
 
+/* dm_source_alm: the exact spherical-harmonic coefficients of nsrc point sources, band-limited at lmax:
+ *   a^T_lm(f) = sum_s I_s(f) lambda_lm(z_s) e^{-i m phi_s}   (a^V alike with V_s)
+ *   a^E_lm(f) = sum_s e^{-i m phi_s} (W_lm(s) Q_s(f) + i X_lm(s) U_s(f))
+ *   a^B_lm(f) = sum_s e^{-i m phi_s} (W_lm(s) U_s(f) - i X_lm(s) Q_s(f))
+ *   z_dev, sth_dev, phi_dev  (nsrc) f64: cos and sin of the colatitude, and the longitude reduced to [0, 2 pi)
+ *   flux_dev                 (nf, npol, nsrc) f64: temperature x solid angle of (I) or (I, Q, U, V)
+ *   alm_dev                  (nf, npol, lmax + 1, m_hi - m_lo + 1) c128, polarisations (T) or (T, E, B, V); every element is
+ *                            written, 0 for l < m and for E, B at l < 2
+ * lambda, W, X come from the recurrence of the ring tables (a column whose seed is a normal double has their bits), the
+ * phases from sincos of the double product m * phi.  The sums over sources run as complex x real products on the matrix
+ * cores, sources in chunks of 1024 in catalogue order and m in blocks of 8 aligned to multiples of 8; max_bytes bounds the
+ * tables and phased fluxes alive at once (one m-block of one chunk at least) and has no influence on the bits.
+ * Errors, with nothing launched: npol other than 1 or 4; m_hi > lmax; npol = 4 and a source with sin theta = 0 whose Q
+ * or U is not zero at some frequency (an unpolarised source at a pole is fine).  Synchronises. */
+int dm_source_alm(dm_ctx* ctx, int nsrc, const double* z_dev, const double* sth_dev, const double* phi_dev, int nf,
+                  int npol, const double* flux_dev, int lmax, int m_lo, int m_hi, void* alm_dev, size_t max_bytes);
+
 /* ---- beam-transfer generation (cylinder telescopes) --------------------------- */
 /* Host geometry shared by the three calls below: ring_cth_host / ring_sth_host hold
  * cos / sin of the colatitude of the 4*nside-1 HEALPix rings; frame_host (9 doubles)
