@@ -32,6 +32,10 @@ struct dm_ctx {
   size_t hpin_cap = 0;
   size_t hpin_used = 0;  // ring offset (per context: contexts may be driven from different threads)
   char* hpin_dl = nullptr;  // page-locked landing buffer of dm_download (allocated on first use)
+  bool dl_open = false;     // between the first dm_download_queue and its dm_download_wait
+  size_t dl_used = 0;       // bytes of it that queued copies (dm_download_queue) have claimed
+  hipEvent_t dl_ev = nullptr;  // recorded behind the last queued copy
+  std::vector<std::vector<char>> dl_spill;  // queued copies that did not fit the landing buffer (taken at once)
   std::string err;
   // optional per-kernel-class timing (HIP events on ctx->stream) and flop accounting
   bool prof_on = false;
@@ -145,6 +149,12 @@ size_t dm_ws_mark(dm_ctx* ctx);
 void dm_ws_release(dm_ctx* ctx, size_t mark);
 int dm_upload(dm_ctx* ctx, void* dst, const void* src, size_t bytes);    // async H2D via pinned staging
 int dm_download(dm_ctx* ctx, void* dst, const void* src, size_t bytes);  // D2H + stream sync
+// The same without the wait in between: queue the copy behind the work already on the stream, go on launching, and
+// read *host only after dm_download_wait (which waits for the copies, not for what was launched after them).  No
+// dm_download between a queue and its wait: both land in the same buffer.
+int dm_download_queue(dm_ctx* ctx, const void* src, size_t bytes, const void** host);
+int dm_download_wait(dm_ctx* ctx);
+void dm_download_abandon(dm_ctx* ctx);  // an error return between a queue and its wait: drain the copies, free the buffer
 
 // RAII guard for the bump arena: every extern "C" entry point (and every internal driver that
 // allocates) opens one, so an early `return` after a failed launch or allocation cannot leave

@@ -124,6 +124,48 @@ int dm_download(dm_ctx* ctx, void* dst, const void* src, size_t bytes) {
   return DM_OK;
 }
 
+int dm_download_queue(dm_ctx* ctx, const void* src, size_t bytes, const void** host) {
+  constexpr size_t kLand = 8u << 20;
+  *host = nullptr;
+  if (!ctx->dl_open) ctx->dl_spill.clear();  // the first copy after a wait: what the last round spilled has been read
+  ctx->dl_open = true;
+  if (bytes == 0) return DM_OK;
+  if (!ctx->hpin_dl) {
+    void* hp = nullptr;
+    if (hipHostMalloc(&hp, kLand, hipHostMallocDefault) == hipSuccess) ctx->hpin_dl = reinterpret_cast<char*>(hp);
+    else (void)hipGetLastError();
+  }
+  const size_t need = align_up(bytes);
+  if (!ctx->hpin_dl || ctx->dl_used + need > kLand) {  // no room: take it now, through pageable memory
+    ctx->dl_spill.emplace_back(bytes);
+    DM_HIP(ctx, hipMemcpyAsync(ctx->dl_spill.back().data(), src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    DM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *host = ctx->dl_spill.back().data();
+    return DM_OK;
+  }
+  if (!ctx->dl_ev) DM_HIP(ctx, hipEventCreateWithFlags(&ctx->dl_ev, hipEventDisableTiming));
+  char* land = ctx->hpin_dl + ctx->dl_used;
+  ctx->dl_used += need;
+  DM_HIP(ctx, hipMemcpyAsync(land, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  DM_HIP(ctx, hipEventRecord(ctx->dl_ev, ctx->stream));
+  *host = land;
+  return DM_OK;
+}
+
+int dm_download_wait(dm_ctx* ctx) {
+  if (ctx->dl_used > 0) DM_HIP(ctx, hipEventSynchronize(ctx->dl_ev));
+  ctx->dl_open = false;
+  ctx->dl_used = 0;  // (the caller reads what landed before it queues or downloads again)
+  return DM_OK;
+}
+
+void dm_download_abandon(dm_ctx* ctx) {
+  if (!ctx->dl_open) return;
+  (void)hipStreamSynchronize(ctx->stream);  // the copies may still be landing
+  ctx->dl_open = false;
+  ctx->dl_used = 0;
+}
+
 hipEvent_t dm_prof_event(dm_ctx* ctx) {
   if (!ctx->ev_pool.empty()) {
     hipEvent_t e = ctx->ev_pool.back();
@@ -223,6 +265,7 @@ int dm_ctx_destroy(dm_ctx* ctx) {
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->hpin) (void)hipHostFree(ctx->hpin);
   if (ctx->hpin_dl) (void)hipHostFree(ctx->hpin_dl);
+  if (ctx->dl_ev) (void)hipEventDestroy(ctx->dl_ev);
   if (ctx->prof_dev) (void)hipFree(ctx->prof_dev);
   for (auto& r : ctx->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);

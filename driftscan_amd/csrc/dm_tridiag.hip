@@ -607,9 +607,10 @@ __global__ void zt_to_x_kernel(const cvt_mat* __restrict__ cs) {
 // <= DC_LEAF rows, the leaves are solved by the QL kernels above, and the tree is merged level
 // by level with every node of a level (all matrices) in the same launches:
 //   dc_setup    z vector, sort, deflation (tiny z / close poles via Givens)      1 WG / node
-//   dc_permute  rotate + gather the non-deflated eigenvectors, copy the deflated ones
-//   dc_secular  one thread per root: safeguarded rational iteration, root kept as (origin, mu)
-//   dc_zhat     Loewner formula for z-hat (numerical orthogonality)
+//   dc_permute  the Givens rotations of the deflation on the eigenvectors
+//   dc_gather   gather the non-deflated eigenvectors, copy the deflated ones
+//   dc_secular  G lanes per root: safeguarded rational iteration, root kept as (origin, mu)
+//   dc_zhat     Loewner formula for z-hat (numerical orthogonality), G lanes per component
 //   dc_unorm / dc_ubuild   eigenvectors of the rank-one modified diagonal
 //   grouped DGEMM         Z_parent = U^T Z_children                                (MFMA)
 // Parallel depth O(log n) instead of the ~1.1 n^2 serial rotations of QL.
@@ -629,6 +630,7 @@ struct dc_mat {
   int* org; double* mu; double* zhat; double* inv;
   double* U;                    // n x n scratch: node block at U + lo * n, leading dimension n
   double* gs; int* gi;          // 4 n doubles + n ints: setup scratch of nodes too large for LDS (node at 4 lo / lo)
+  int* fail;                    // 0, or why this matrix is not merged: 1 a leaf did not converge, 2 non-finite input
 };
 
 struct dc_node {
@@ -638,6 +640,24 @@ struct dc_node {
 };
 
 struct dc_nodeout { int k, ndefl, nrot; double rho; };
+
+// exclusive prefix sum of one int per thread over the 256 threads of the workgroup (sw: 4 ints of LDS); total = the sum
+__device__ __forceinline__ int dc_block_scan(int v, int* sw, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  __syncthreads();  // sw may still be read from the scan before
+  if (lane == 63) sw[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  for (int w = 0; w < wave; ++w) base += sw[w];
+  total = sw[0] + sw[1] + sw[2] + sw[3];
+  return base + inc - v;
+}
 
 // BIG = false: the node's work arrays live in LDS (nn <= DC_MAXNODE); BIG = true: in the global scratch
 // M.gs / M.gi (any nn), the counting sort then broadcasts 64 keys at a time through lane reads.
@@ -660,12 +680,26 @@ __global__ __launch_bounds__(256) void dc_setup_kernel(const dc_mat* __restrict_
   const double* Z = nd.flip ? M.ZB : M.ZA;
   const double beta = *nd.pbeta;
   const double sgn = beta >= 0.0 ? 1.0 : -1.0;
+  // A matrix that has failed is not merged: its node reports k = ndefl = nrot = 0, and every later kernel of the level
+  // leaves or copies nothing for it.  Non-finite poles or weights fail it here: the ranks below are a permutation only
+  // for ordered keys, and the columns the other kernels address come out of them.
   double part = 0.0;
+  int nonfinite = isfinite(beta) ? 0 : 1;
+  if (tid == 0 && *M.fail != 0) nonfinite = 1;  // (one reader: another node of the matrix may set the flag meanwhile)
   for (int i = tid; i < nn; i += 256) {
-    ud[i] = lam[lo + i];
+    const double li = lam[lo + i];
+    ud[i] = li;
     const double zi = (i < nd.n1) ? Z[(size_t)(lo + i) * n + (lo + nd.n1 - 1)] : sgn * Z[(size_t)(lo + i) * n + (lo + nd.n1)];
     uz[i] = zi;
     part += zi * zi;
+    nonfinite |= (isfinite(li) && isfinite(zi)) ? 0 : 1;
+  }
+  if (__syncthreads_or(nonfinite)) {
+    if (tid == 0) {
+      if (*M.fail == 0) *M.fail = 2;
+      outs[blockIdx.x] = dc_nodeout{0, 0, 0, 0.0};
+    }
+    return;
   }
   part = dm_wave_sum(part);
   if ((tid & 63) == 0) red[tid >> 6] = part;
@@ -717,60 +751,182 @@ __global__ __launch_bounds__(256) void dc_setup_kernel(const dc_mat* __restrict_
   __syncthreads();
   if (tid == 0) s_dmax = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
   __syncthreads();
-  if (tid != 0) return;
-  // ---- serial deflation scan (dlaed2)
   const double eps = 1.1102230246251565e-16;
   const double tol = 8.0 * eps * fmax(s_dmax, s_zmax);
-  int k = 0, ndefl = 0, nrot = 0;
-  int* keeppos = reinterpret_cast<int*>(ud);  // reuse: positions (in sorted order) of kept entries
-  if (rho * s_zmax <= tol) {
-    for (int i = 0; i < nn; ++i) { M.deflcol[lo + ndefl] = sidx[i]; M.defld[lo + ndefl] = sd[i]; ++ndefl; }
-  } else {
-    int prev = -1;
-    for (int i = 0; i < nn; ++i) {
-      if (rho * fabs(sz[i]) <= tol) {
-        M.deflcol[lo + ndefl] = sidx[i]; M.defld[lo + ndefl] = sd[i]; ++ndefl;
-        continue;
-      }
-      if (prev >= 0) {
-        double s = sz[prev], c = sz[i];
-        const double tau = hypot(c, s);
-        const double t = sd[i] - sd[prev];
-        c /= tau;
-        s = -s / tau;
-        if (fabs(t * c * s) <= tol) {
-          sz[i] = tau;
-          sz[prev] = 0.0;
-          M.rots[lo + nrot] = make_double4((double)sidx[prev], (double)sidx[i], c, s);
-          ++nrot;
-          const double dp = sd[prev], di = sd[i];
-          sd[prev] = dp * c * c + di * s * s;
-          sd[i] = dp * s * s + di * c * c;
-          M.deflcol[lo + ndefl] = sidx[prev]; M.defld[lo + ndefl] = sd[prev]; ++ndefl;
-          keeppos[k - 1] = i;
-          prev = i;
+  if constexpr (BIG) {
+    if (tid != 0) return;
+    int k = 0, ndefl = 0, nrot = 0;
+    // ---- serial deflation scan (dlaed2)
+    int* keeppos = reinterpret_cast<int*>(ud);  // reuse: positions (in sorted order) of kept entries
+    if (rho * s_zmax <= tol) {
+      for (int i = 0; i < nn; ++i) { M.deflcol[lo + ndefl] = sidx[i]; M.defld[lo + ndefl] = sd[i]; ++ndefl; }
+    } else {
+      int prev = -1;
+      for (int i = 0; i < nn; ++i) {
+        if (rho * fabs(sz[i]) <= tol) {
+          M.deflcol[lo + ndefl] = sidx[i]; M.defld[lo + ndefl] = sd[i]; ++ndefl;
           continue;
         }
+        if (prev >= 0) {
+          double s = sz[prev], c = sz[i];
+          const double tau = hypot(c, s);
+          const double t = sd[i] - sd[prev];
+          c /= tau;
+          s = -s / tau;
+          if (fabs(t * c * s) <= tol) {
+            sz[i] = tau;
+            sz[prev] = 0.0;
+            M.rots[lo + nrot] = make_double4((double)sidx[prev], (double)sidx[i], c, s);
+            ++nrot;
+            const double dp = sd[prev], di = sd[i];
+            sd[prev] = dp * c * c + di * s * s;
+            sd[i] = dp * s * s + di * c * c;
+            M.deflcol[lo + ndefl] = sidx[prev]; M.defld[lo + ndefl] = sd[prev]; ++ndefl;
+            keeppos[k - 1] = i;
+            prev = i;
+            continue;
+          }
+        }
+        keeppos[k++] = i;
+        prev = i;
       }
-      keeppos[k++] = i;
-      prev = i;
+      // poles must increase: the rotations can perturb the order by a few ulp -> insertion sort
+      for (int a = 1; a < k; ++a) {
+        const int pa = keeppos[a];
+        const double da = sd[pa];
+        int b = a - 1;
+        while (b >= 0 && sd[keeppos[b]] > da) { keeppos[b + 1] = keeppos[b]; --b; }
+        keeppos[b + 1] = pa;
+      }
+      for (int j = 0; j < k; ++j) {
+        const int pos = keeppos[j];
+        M.dk[lo + j] = sd[pos];
+        M.zk[lo + j] = sz[pos];
+        M.keepcol[lo + j] = sidx[pos];
+      }
     }
-    // poles must increase: the rotations can perturb the order by a few ulp -> insertion sort
-    for (int a = 1; a < k; ++a) {
-      const int pa = keeppos[a];
-      const double da = sd[pa];
-      int b = a - 1;
-      while (b >= 0 && sd[keeppos[b]] > da) { keeppos[b + 1] = keeppos[b]; --b; }
-      keeppos[b + 1] = pa;
+    outs[blockIdx.x] = dc_nodeout{k, ndefl, nrot, rho};
+  } else {
+    // ---- the deflation scan of dlaed2 with the decisions of the serial scan (the BIG branch above), in four steps:
+    //   1  tiny weights are marked and the others ("survivors") compacted, in parallel
+    //   2  one wave tests 64 consecutive survivor pairs (prev, i) at a time with the weights as they stand; a pair
+    //      before the first that passes the close-pole test is kept as the serial scan keeps it (nothing it read has
+    //      been modified), the first that passes is rotated by its lane, and the scan resumes behind it
+    //   3  the deflated entries (in the order the serial scan emits them: by the position it is at) and the kept ones
+    //      are compacted in parallel
+    //   4  the kept poles are put in increasing order (stable, as the insertion sort: ranks by counting, and only if
+    //      a rotation has disturbed the order) and written out in parallel
+    __shared__ int s_sw[4];
+    __shared__ int s_nrot, s_unsorted;
+    int* surv = reinterpret_cast<int*>(ud);          // step 2: survivors by sorted position; from step 3: kept ones
+    int* ecol = surv + nn;                           // local column deflated when the scan is at position i, or -1
+    double* ed = reinterpret_cast<double*>(ecol + nn);   // ... and its pole
+    unsigned char* st = reinterpret_cast<unsigned char*>(sidx + nn);  // 0 tiny, 1 survivor, 2 rotated away
+    const int lane = tid & 63;
+    if (rho * s_zmax <= tol) {
+      for (int i = tid; i < nn; i += 256) { M.deflcol[lo + i] = sidx[i]; M.defld[lo + i] = sd[i]; }
+      if (tid == 0) outs[blockIdx.x] = dc_nodeout{0, nn, 0, rho};
+      return;
     }
-    for (int j = 0; j < k; ++j) {
-      const int pos = keeppos[j];
-      M.dk[lo + j] = sd[pos];
-      M.zk[lo + j] = sz[pos];
-      M.keepcol[lo + j] = sidx[pos];
+    const int chunk = (nn + 255) / 256;
+    const int c0 = min(tid * chunk, nn), c1 = min(c0 + chunk, nn);
+    int cnt = 0;
+    for (int i = c0; i < c1; ++i) {
+      const bool tiny = rho * fabs(sz[i]) <= tol;
+      st[i] = tiny ? 0 : 1;
+      ecol[i] = tiny ? sidx[i] : -1;
+      ed[i] = sd[i];
+      cnt += tiny ? 0 : 1;
     }
+    int m;
+    int pos = dc_block_scan(cnt, s_sw, m);
+    for (int i = c0; i < c1; ++i)
+      if (st[i]) surv[pos++] = i;
+    __syncthreads();
+    if (tid < 64) {
+      int nrot = 0;
+      for (int t0 = 1; t0 < m;) {
+        const int t = t0 + lane;
+        bool pass = false;
+        int pv = 0, ii = 0;
+        double c = 0.0, s = 0.0, tau = 0.0;
+        if (t < m) {
+          pv = surv[t - 1];
+          ii = surv[t];
+          s = sz[pv];
+          c = sz[ii];
+          tau = hypot(c, s);
+          const double dt = sd[ii] - sd[pv];
+          c /= tau;
+          s = -s / tau;
+          pass = fabs(dt * c * s) <= tol;
+        }
+        const unsigned long long hit = __ballot(pass);
+        if (hit == 0ull) { t0 += 64; continue; }
+        const int f = __ffsll((long long)hit) - 1;
+        if (lane == f) {
+          sz[ii] = tau;
+          sz[pv] = 0.0;
+          M.rots[lo + nrot] = make_double4((double)sidx[pv], (double)sidx[ii], c, s);
+          const double dp = sd[pv], di = sd[ii];
+          sd[pv] = dp * c * c + di * s * s;
+          sd[ii] = dp * s * s + di * c * c;
+          ecol[ii] = sidx[pv];
+          ed[ii] = sd[pv];
+          st[pv] = 2;
+        }
+        ++nrot;
+        t0 += f + 1;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the lanes of the next round read what lane f wrote
+        __builtin_amdgcn_wave_barrier();
+      }
+      if (tid == 0) s_nrot = nrot;
+    }
+    if (tid == 0) s_unsorted = 0;
+    __syncthreads();
+    int ne = 0, nk = 0;
+    for (int i = c0; i < c1; ++i) {
+      ne += ecol[i] >= 0 ? 1 : 0;
+      nk += st[i] == 1 ? 1 : 0;
+    }
+    int ndefl, k;
+    int pe = dc_block_scan(ne, s_sw, ndefl);
+    int pk = dc_block_scan(nk, s_sw, k);
+    for (int i = c0; i < c1; ++i) {
+      if (ecol[i] >= 0) { M.deflcol[lo + pe] = ecol[i]; M.defld[lo + pe] = ed[i]; ++pe; }
+      if (st[i] == 1) surv[pk++] = i;
+    }
+    __syncthreads();
+    // poles must increase: the rotations can perturb the order by a few ulp
+    int* kp = surv;
+    if (s_nrot > 0) {
+      for (int a = tid + 1; a < k; a += 256)
+        if (sd[kp[a - 1]] > sd[kp[a]]) s_unsorted = 1;
+      __syncthreads();
+      if (s_unsorted) {
+        int* kp2 = ecol;
+        for (int a = tid; a < k; a += 256) {
+          const int pa = kp[a];
+          const double da = sd[pa];
+          int r = 0;
+          for (int b = 0; b < k; ++b) {
+            const double db = sd[kp[b]];
+            r += (db < da || (db == da && b < a)) ? 1 : 0;
+          }
+          kp2[r] = pa;
+        }
+        __syncthreads();
+        kp = kp2;
+      }
+    }
+    for (int j = tid; j < k; j += 256) {
+      const int p = kp[j];
+      M.dk[lo + j] = sd[p];
+      M.zk[lo + j] = sz[p];
+      M.keepcol[lo + j] = sidx[p];
+    }
+    if (tid == 0) outs[blockIdx.x] = dc_nodeout{k, ndefl, s_nrot, rho};
   }
-  outs[blockIdx.x] = dc_nodeout{k, ndefl, nrot, rho};
 }
 
 __global__ __launch_bounds__(256) void dc_permute_kernel(const dc_mat* __restrict__ ms, const dc_node* __restrict__ nodes,
@@ -828,17 +984,33 @@ __global__ __launch_bounds__(256) void dc_gather_kernel(const dc_mat* __restrict
   }
 }
 
-// grid = (root tiles of 256, nodes); dynamic LDS: 2 * kmax doubles (BIG: poles and weights are read
-// from global memory instead -- every lane of a wave reads the same element, one request per load)
-template <bool BIG>
+// Orders the LDS traffic of one wave: what its lanes wrote before is what they read after (the groups of lanes below
+// hand their terms to each other through LDS inside a wave; no other wave touches those slots)
+__device__ __forceinline__ void dc_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Secular equation: a group of G lanes of one wave per root, 256 / G roots per workgroup.  The lanes of a group form
+// the terms of G consecutive i at once -- the divisions, nearly all of the work -- hand them to each other through LDS,
+// and every lane adds them up in the order i = 0 .. k - 1 (one LDS read and the dependent add or fma per term), so a
+// root gets the bits one thread walking the k terms gets, whatever G is, and every lane of a group takes the same
+// step.  The iteration loop is uniform over the wave (a group that has converged idles until the last one of its wave
+// has).  Root kept as (origin, mu), safeguarded bracket, rational step of the interior and of the last root.
+// grid = (root tiles of 256 / G over the largest node, nodes): k comes from `outs`, and a workgroup whose tile lies
+// beyond it leaves before the barrier.  Dynamic LDS: 2 * maxnn doubles (BIG: poles and weights from global memory).
+template <bool BIG, int G>
 __global__ __launch_bounds__(256) void dc_secular_kernel(const dc_mat* __restrict__ ms, const dc_node* __restrict__ nodes,
                                                          const dc_nodeout* __restrict__ outs) {
   extern __shared__ __align__(16) unsigned char dc_smem[];
+  constexpr int R = 256 / G;
+  __shared__ double2 s_stage[256];  // (t, rho z^2) of the G terms a group has just formed
+  double2* stg = s_stage + (threadIdx.x & ~(G - 1));
   const dc_node nd = nodes[blockIdx.y];
   const dc_mat M = ms[nd.mat];
   const dc_nodeout o = outs[blockIdx.y];
   const int k = o.k, lo = nd.lo;
-  if ((int)(blockIdx.x * 256) >= k) return;
+  if ((int)(blockIdx.x * R) >= k) return;
   const double* d = BIG ? M.dk + lo : reinterpret_cast<double*>(dc_smem);
   const double* zsrc = BIG ? M.zk + lo : d + k;
   auto Z2 = [&](int i) -> double {
@@ -855,105 +1027,184 @@ __global__ __launch_bounds__(256) void dc_secular_kernel(const dc_mat* __restric
     }
     __syncthreads();
   }
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= k) return;
+  const int g = threadIdx.x & (G - 1);
+  const int jr = blockIdx.x * R + threadIdx.x / G;
+  const bool act = jr < k;        // a group past the last root solves that root again and stores nothing
+  const int j = act ? jr : k - 1;
   const double rho = o.rho;
   const double eps = 2.220446049250313e-16;
   double* lamn = nd.flip ? M.lamA : M.lamB;
   if (k == 1) {
-    M.org[lo] = 0;
-    M.mu[lo] = rho * Z2(0);
-    lamn[lo] = d[0] + rho * Z2(0);
+    if (threadIdx.x == 0) {
+      M.org[lo] = 0;
+      M.mu[lo] = rho * Z2(0);
+      lamn[lo] = d[0] + rho * Z2(0);
+    }
     return;
   }
   const bool last = (j == k - 1);
   int og;
   double lo_b, hi_b;
-  if (!last) {
-    const double mid = 0.5 * (d[j + 1] - d[j]);
-    double f = 1.0;
-    for (int i = 0; i < k; ++i) f += rho * Z2(i) / ((d[i] - d[j]) - mid);
-    if (f > 0.0) { og = j; lo_b = 0.0; hi_b = mid; } else { og = j + 1; lo_b = -mid; hi_b = 0.0; }
-  } else {
-    og = j;
-    double sz = 0.0;
-    for (int i = 0; i < k; ++i) sz += Z2(i);
-    lo_b = 0.0;
-    hi_b = rho * sz;
+  {
+    // interior root: the sign of f at the midpoint picks the origin; last root: the bracket [0, rho sum z^2]
+    const double dj = d[j], mid = last ? 0.0 : 0.5 * (d[j + 1] - dj);
+    double acc = last ? 0.0 : 1.0;
+    for (int i0 = 0; i0 < k; i0 += G) {
+      const int i = i0 + g;
+      double v = 0.0;
+      if (i < k) {
+        const double z2 = Z2(i);
+        v = last ? z2 : rho * z2 / ((d[i] - dj) - mid);
+      }
+      stg[g].x = v;
+      dc_wave_sync();
+      const int cnt = min(G, k - i0);
+      if (cnt == G) {
+#pragma unroll
+        for (int s = 0; s < G; ++s) acc += stg[s].x;
+      } else {
+        for (int s = 0; s < cnt; ++s) acc += stg[s].x;
+      }
+      dc_wave_sync();
+    }
+    if (last) { og = j; lo_b = 0.0; hi_b = rho * acc; }
+    else if (acc > 0.0) { og = j; lo_b = 0.0; hi_b = mid; }
+    else { og = j + 1; lo_b = -mid; hi_b = 0.0; }
   }
   const double dorg = d[og];
   double mu = 0.5 * (lo_b + hi_b);
+  bool done = false;
   for (int it = 0; it < 100; ++it) {
     double psi = 0.0, phi = 0.0, dpsi = 0.0, dphi = 0.0;
-    for (int i = 0; i <= j; ++i) {
-      const double t = 1.0 / ((d[i] - dorg) - mu);
-      const double term = rho * Z2(i) * t;
-      psi += term;
-      dpsi += term * t;
-    }
-    for (int i = j + 1; i < k; ++i) {
-      const double t = 1.0 / ((d[i] - dorg) - mu);
-      const double term = rho * Z2(i) * t;
-      phi += term;
-      dphi += term * t;
-    }
-    const double fv = 1.0 + psi + phi;
-    const double erretm = 8.0 * (fabs(psi) + fabs(phi)) + 1.0 + fabs(mu) * (dpsi + dphi);
-    if (fabs(fv) <= eps * erretm) break;
-    if (fv > 0.0) hi_b = mu; else lo_b = mu;
-    double eta;
-    if (!last) {
-      const double dj = (d[j] - dorg) - mu, dj1 = (d[j + 1] - dorg) - mu;
-      const double a = (dj + dj1) * fv - dj * dj1 * (dpsi + dphi);
-      const double b = dj * dj1 * fv;
-      const double c = fv - dj * dpsi - dj1 * dphi;
-      if (c == 0.0) {
-        eta = a != 0.0 ? b / a : 0.0;
-      } else {
-        const double disc = sqrt(fmax(a * a - 4.0 * b * c, 0.0));
-        eta = (a <= 0.0) ? (a - disc) / (2.0 * c) : 2.0 * b / (a + disc);
+    for (int i0 = 0; i0 < k; i0 += G) {
+      const int i = i0 + g;
+      double t = 0.0, rz = 0.0;
+      if (i < k) {
+        t = 1.0 / ((d[i] - dorg) - mu);
+        rz = rho * Z2(i);
       }
-    } else {
-      const double tq = (d[j] - dorg) - mu, tp = (d[j - 1] - dorg) - mu;
-      const double dphil = rho * Z2(j) / (tq * tq);
-      const double dpsil = dpsi + dphi - dphil;
-      double c = fv - tp * dpsil - tq * dphil;
-      const double a = (tp + tq) * fv - tp * tq * (dpsil + dphil);
-      const double b = tp * tq * fv;
-      if (c < 0.0) c = -c;
-      if (c == 0.0) eta = hi_b - mu;
-      else if (a >= 0.0) eta = (a + sqrt(fabs(a * a - 4.0 * b * c))) / (2.0 * c);
-      else eta = 2.0 * b / (a - sqrt(fabs(a * a - 4.0 * b * c)));
-      if (fv * eta > 0.0) eta = -fv / (dpsi + dphi);
+      stg[g] = make_double2(t, rz);
+      dc_wave_sync();
+      const int cnt = min(G, k - i0);
+      // the roots of a wave are neighbours: all but one or two chunks lie on one side of j for every group of it
+      auto add = [&](double& a, double& da, int s) {
+        const double2 v = stg[s];
+        const double term = v.y * v.x;
+        a = __builtin_fma(v.y, v.x, a);
+        da = __builtin_fma(v.x, term, da);
+      };
+      if (i0 + cnt - 1 <= j) {
+        if (cnt == G) {
+#pragma unroll
+          for (int s = 0; s < G; ++s) add(psi, dpsi, s);
+        } else {
+          for (int s = 0; s < cnt; ++s) add(psi, dpsi, s);
+        }
+      } else if (i0 > j) {
+        if (cnt == G) {
+#pragma unroll
+          for (int s = 0; s < G; ++s) add(phi, dphi, s);
+        } else {
+          for (int s = 0; s < cnt; ++s) add(phi, dphi, s);
+        }
+      } else {
+        for (int s = 0; s < cnt; ++s) {
+          if (i0 + s <= j) add(psi, dpsi, s);
+          else add(phi, dphi, s);
+        }
+      }
+      dc_wave_sync();
     }
-    double nw = mu + eta;
-    if (!(nw > lo_b && nw < hi_b) || !isfinite(nw)) nw = 0.5 * (lo_b + hi_b);
-    if (nw == mu || (hi_b - lo_b) <= 2.0 * eps * fabs(nw)) { mu = nw; break; }
-    mu = nw;
+    if (!done) {
+      const double fv = 1.0 + psi + phi;
+      const double erretm = 8.0 * (fabs(psi) + fabs(phi)) + 1.0 + fabs(mu) * (dpsi + dphi);
+      if (fabs(fv) <= eps * erretm) {
+        done = true;
+      } else {
+        if (fv > 0.0) hi_b = mu; else lo_b = mu;
+        double eta;
+        if (!last) {
+          const double dj = (d[j] - dorg) - mu, dj1 = (d[j + 1] - dorg) - mu;
+          const double a = (dj + dj1) * fv - dj * dj1 * (dpsi + dphi);
+          const double b = dj * dj1 * fv;
+          const double c = fv - dj * dpsi - dj1 * dphi;
+          if (c == 0.0) {
+            eta = a != 0.0 ? b / a : 0.0;
+          } else {
+            const double disc = sqrt(fmax(a * a - 4.0 * b * c, 0.0));
+            eta = (a <= 0.0) ? (a - disc) / (2.0 * c) : 2.0 * b / (a + disc);
+          }
+        } else {
+          const double tq = (d[j] - dorg) - mu, tp = (d[j - 1] - dorg) - mu;
+          const double dphil = rho * Z2(j) / (tq * tq);
+          const double dpsil = dpsi + dphi - dphil;
+          double c = fv - tp * dpsil - tq * dphil;
+          const double a = (tp + tq) * fv - tp * tq * (dpsil + dphil);
+          const double b = tp * tq * fv;
+          if (c < 0.0) c = -c;
+          if (c == 0.0) eta = hi_b - mu;
+          else if (a >= 0.0) eta = (a + sqrt(fabs(a * a - 4.0 * b * c))) / (2.0 * c);
+          else eta = 2.0 * b / (a - sqrt(fabs(a * a - 4.0 * b * c)));
+          if (fv * eta > 0.0) eta = -fv / (dpsi + dphi);
+        }
+        double nw = mu + eta;
+        if (!(nw > lo_b && nw < hi_b) || !isfinite(nw)) nw = 0.5 * (lo_b + hi_b);
+        if (nw == mu || (hi_b - lo_b) <= 2.0 * eps * fabs(nw)) done = true;
+        mu = nw;
+      }
+    }
+    if (__all(done)) break;
   }
-  M.org[lo + j] = og;
-  M.mu[lo + j] = mu;
-  lamn[lo + j] = dorg + mu;
+  if (act && g == 0) {
+    M.org[lo + j] = og;
+    M.mu[lo + j] = mu;
+    lamn[lo + j] = dorg + mu;
+  }
 }
 
-// zhat_i = sign(z_i) sqrt( prod_j (lam_j - d_i) / (rho prod_{j != i} (d_j - d_i)) )
+// zhat_i = sign(z_i) sqrt( prod_j (lam_j - d_i) / (rho prod_{j != i} (d_j - d_i)) ): a group of G lanes per i forms
+// G factors at once, hands them over through LDS, and every lane multiplies them up in the order j = 0 .. k - 1 (the
+// bits of one thread per i).
+// grid = (tiles of 256 / G over the largest node, nodes)
+template <int G>
 __global__ __launch_bounds__(256) void dc_zhat_kernel(const dc_mat* __restrict__ ms, const dc_node* __restrict__ nodes,
                                                       const dc_nodeout* __restrict__ outs) {
+  constexpr int R = 256 / G;
+  __shared__ double s_stage[256];
+  double* stg = s_stage + (threadIdx.x & ~(G - 1));
   const dc_node nd = nodes[blockIdx.y];
   const dc_mat M = ms[nd.mat];
   const dc_nodeout o = outs[blockIdx.y];
   const int k = o.k, lo = nd.lo;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= k) return;
+  if ((int)(blockIdx.x * R) >= k) return;
+  const int g = threadIdx.x & (G - 1);
+  const int ir = blockIdx.x * R + threadIdx.x / G;
+  const bool act = ir < k;
+  const int i = act ? ir : k - 1;
   const double di = M.dk[lo + i];
   double prod = 1.0;
-  for (int j = 0; j < k; ++j) {
-    const double num = M.mu[lo + j] - (di - M.dk[lo + M.org[lo + j]]);  // lam_j - d_i
-    if (j == i) prod *= num;
-    else prod *= num / (M.dk[lo + j] - di);
+  for (int j0 = 0; j0 < k; j0 += G) {
+    const int j = j0 + g;
+    double r = 1.0;
+    if (j < k) {
+      const double num = M.mu[lo + j] - (di - M.dk[lo + M.org[lo + j]]);  // lam_j - d_i
+      r = (j == i) ? num : num / (M.dk[lo + j] - di);
+    }
+    stg[g] = r;
+    dc_wave_sync();
+    const int cnt = min(G, k - j0);
+    if (cnt == G) {
+#pragma unroll
+      for (int s = 0; s < G; ++s) prod *= stg[s];
+    } else {
+      for (int s = 0; s < cnt; ++s) prod *= stg[s];
+    }
+    dc_wave_sync();
   }
-  const double zh = sqrt(fabs(prod) / o.rho);
-  M.zhat[lo + i] = M.zk[lo + i] >= 0.0 ? zh : -zh;
+  if (act && g == 0) {
+    const double zh = sqrt(fabs(prod) / o.rho);
+    M.zhat[lo + i] = M.zk[lo + i] >= 0.0 ? zh : -zh;
+  }
 }
 
 // inv[j] = 1 / || zhat_i / (d_i - lam_j) ||_i
@@ -974,17 +1225,22 @@ __global__ __launch_bounds__(256) void dc_unorm_kernel(const dc_mat* __restrict_
   M.inv[lo + j] = 1.0 / sqrt(s);
 }
 
-// Ut[j][i] = zhat_i / (d_i - lam_j) * inv_j   (row j = eigenvector j of the rank-one problem)
+// Ut[j][i] = zhat_i / (d_i - lam_j) * inv_j   (row j = eigenvector j of the rank-one problem); a workgroup forms
+// DC_UROWS rows of 256 columns: the grid is sized from the largest node, and most of it leaves at once
+constexpr int DC_UROWS = 8;
 __global__ __launch_bounds__(256) void dc_ubuild_kernel(const dc_mat* __restrict__ ms, const dc_node* __restrict__ nodes,
                                                         const dc_nodeout* __restrict__ outs) {
   const dc_node nd = nodes[blockIdx.z];
   const dc_mat M = ms[nd.mat];
   const dc_nodeout o = outs[blockIdx.z];
   const int k = o.k, lo = nd.lo;
-  const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
-  if (i >= k || j >= k) return;
-  const double dor = M.dk[lo + M.org[lo + j]], mu = M.mu[lo + j];
-  M.U[(size_t)lo * M.n + (size_t)j * M.n + i] = M.zhat[lo + i] / ((M.dk[lo + i] - dor) - mu) * M.inv[lo + j];
+  const int i = blockIdx.x * 256 + threadIdx.x, j0 = blockIdx.y * DC_UROWS;
+  if (i >= k || j0 >= k) return;
+  const int j1 = min(j0 + DC_UROWS, k);
+  for (int j = j0; j < j1; ++j) {
+    const double dor = M.dk[lo + M.org[lo + j]], mu = M.mu[lo + j];
+    M.U[(size_t)lo * M.n + (size_t)j * M.n + i] = M.zhat[lo + i] / ((M.dk[lo + i] - dor) - mu) * M.inv[lo + j];
+  }
 }
 
 // LAPACK's dstedc scales the tridiagonal to unit max-norm before the divide & conquer (DLASCL with ORGNRM) and scales
@@ -1020,6 +1276,12 @@ __global__ __launch_bounds__(256) void dc_unscale_kernel(const dc_scale_mat* __r
   for (int i = threadIdx.x; i < M.n; i += 256) M.d[i] *= sc;
 }
 
+// a leaf that did not converge fails its matrix (the flag dc_setup reads)
+__global__ void dc_leaf_fail_kernel(const int* __restrict__ stat, const int* __restrict__ leafmat, int nleaf, int* __restrict__ fail) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nleaf && stat[i] != 0) fail[leafmat[i]] = 1;
+}
+
 struct dc_tear { double* d; const double* e; int b; };
 __global__ void dc_tear_kernel(const dc_tear* __restrict__ ts, int nt) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1032,6 +1294,34 @@ __global__ void dc_tear_kernel(const dc_tear* __restrict__ ts, int nt) {
 
 }  // namespace
 
+
+// Lanes per root of dc_secular / per component of dc_zhat.  Every lane of a group walks all k terms for the ordered
+// sum, so the work of a root grows with G (about 36 + 4 G instructions per G terms) while its dependent chain shrinks.
+// Measured on the configs[1] step (secular + z-hat per step): one thread per root 3.76 ms, G = 4 2.93, G = 8 2.46.
+// Not measured: G = 16, and batches that fill the device with roots (sum nn beyond ~10^5), where the narrower group's
+// smaller work may win; one width is compiled until a workload says otherwise.
+constexpr int DC_G = 8;
+
+template <int G>
+static int dc_secular_attr(dm_ctx* ctx) {
+  DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dc_secular_kernel<false, G>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 16 * DC_MAXNODE + 64));
+  return DM_OK;
+}
+
+// secular equation and z-hat of one level with G lanes per root
+template <int G>
+static void dc_roots_launch(dm_ctx* ctx, bool big, int maxnn, int nn_nodes, const dc_mat* d_dm, const dc_node* d_nodes,
+                            const dc_nodeout* d_out) {
+  constexpr int R = 256 / G;
+  const dim3 grid((maxnn + R - 1) / R, nn_nodes);
+  if (big)
+    DM_PLAUNCH(ctx, DM_PROF_DC, (dc_secular_kernel<true, G>), grid, dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
+  else
+    DM_PLAUNCH(ctx, DM_PROF_DC, (dc_secular_kernel<false, G>), grid, dim3(256), (size_t)16 * maxnn + 64, ctx->stream, d_dm,
+               d_nodes, d_out);
+  DM_PLAUNCH(ctx, DM_PROF_DC, dc_zhat_kernel<G>, grid, dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
+}
 
 // ---- D&C driver: on entry dd/ee hold the tridiagonals (offsets offn); on return dd holds the
 // eigenvalues (unsorted) and zfinal[p] points at the eigenvector-major n x n eigenvector array.
@@ -1052,13 +1342,15 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
   double* muv = dm_ws_alloc_t<double>(ctx, std::max<size_t>(totn, 1));
   double* zhat = dm_ws_alloc_t<double>(ctx, std::max<size_t>(totn, 1));
   double* inv = dm_ws_alloc_t<double>(ctx, std::max<size_t>(totn, 1));
+  int* fail = dm_ws_alloc_t<int>(ctx, std::max(np, 1));  // per matrix: dc_mat::fail
   int* keepcol = dm_ws_alloc_t<int>(ctx, std::max<size_t>(totn, 1));
   int* deflcol = dm_ws_alloc_t<int>(ctx, std::max<size_t>(totn, 1));
   int* org = dm_ws_alloc_t<int>(ctx, std::max<size_t>(totn, 1));
   double4* rots = dm_ws_alloc_t<double4>(ctx, std::max<size_t>(totn, 1));
   double* gsc = dm_ws_alloc_t<double>(ctx, std::max<size_t>(4 * totn, 1));
   int* gic = dm_ws_alloc_t<int>(ctx, std::max<size_t>(totn, 1));
-  if (!gsc || !gic) return DM_ENOMEM;
+  if (!gsc || !gic || !fail) return DM_ENOMEM;
+  DM_TRY(dm_fill_zero(ctx, fail, sizeof(int) * std::max(np, 1)));
   if (!ZA || !ZB || !Zp || !Uw || !lamB || !dk || !zk || !defld || !muv || !zhat || !inv || !keepcol || !deflcol ||
       !org || !rots)
     return DM_ENOMEM;
@@ -1076,7 +1368,7 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
     dmax = std::max(dmax, D);
     dm[p] = dc_mat{n, dd + offn[p], lamB + offn[p], ZA + off[p], ZB + off[p], Zp + off[p], dk + offn[p], zk + offn[p],
                    keepcol + offn[p], deflcol + offn[p], defld + offn[p], rots + offn[p], org + offn[p],
-                   muv + offn[p], zhat + offn[p], inv + offn[p], Uw + off[p], gsc + 4 * offn[p], gic + offn[p]};
+                   muv + offn[p], zhat + offn[p], inv + offn[p], Uw + off[p], gsc + 4 * offn[p], gic + offn[p], fail + p};
   }
   dc_mat* d_dm = dm_ws_upload(ctx, dm);
   if (!d_dm) return DM_ENOMEM;
@@ -1092,10 +1384,10 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
   DM_PLAUNCH(ctx, DM_PROF_DC, dc_scale_kernel, dim3(np), dim3(256), 0, ctx->stream, d_scm);
 
   // ---- tear at every leaf boundary, then solve the leaves (at most DC_LEAF rows) with the in-LDS QL kernel
+  std::vector<int> leafmat;
   {
     std::vector<dc_tear> tears;
     std::vector<ql_mat> qm;
-    std::vector<int> leafmat;
     int maxleaf = 0;
     for (int p = 0; p < np; ++p) {
       const int n = probs[p].n, D = depth[p];
@@ -1128,26 +1420,44 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
       // rotations applied in LDS as they are generated (d, e and the n x n Z of a leaf: 16 n + 8 n^2 bytes)
       DM_PLAUNCH(ctx, DM_PROF_DC, ql_kernel<true>, dim3(nleaf), dim3(64), (size_t)maxleaf * 16 + (size_t)maxleaf * maxleaf * 8,
                          ctx->stream, d_qm);
+      // the status of the leaves stays on the device: a leaf that did not converge fails its matrix, dc_setup then
+      // merges nothing of it, and the host reads the flags with the first level's copy (fail_check)
+      int* d_leafmat = dm_ws_upload(ctx, leafmat);
+      if (!d_leafmat) return DM_ENOMEM;
+      DM_PLAUNCH(ctx, DM_PROF_DC, dc_leaf_fail_kernel, dim3((nleaf + 255) / 256), dim3(256), 0, ctx->stream, stat, d_leafmat,
+                 nleaf, fail);
       DM_HIP(ctx, hipGetLastError());
-      std::vector<int> hs(nleaf);
-      DM_TRY(dm_download(ctx, hs.data(), stat, sizeof(int) * nleaf));
-      for (int i = 0; i < nleaf; ++i)
-        if (hs[i] != 0) {
-          ctx->err = "tridiagonal QL iteration (D&C leaf) did not converge";
-          return 1000 + leafmat[i];
-        }
     }
   }
+  // a queued copy that an error return leaves behind is given up, so that the landing buffer is free for the caller
+  struct dl_guard {
+    dm_ctx* c;
+    ~dl_guard() { dm_download_abandon(c); }
+  } dl_guard_{ctx};
+  // after the dm_download_wait of a copy of `fail`: 0, or the return code of the first matrix that failed
+  auto fail_check = [&](const int* hf) -> int {
+    for (int p = 0; hf && p < np; ++p)
+      if (hf[p] != 0) {
+        ctx->err = hf[p] == 1 ? "tridiagonal QL iteration (D&C leaf) did not converge"
+                              : "non-finite tridiagonal in the divide & conquer";
+        return 1000 + p;
+      }
+    return DM_OK;
+  };
 
-  // ---- merge level by level
+  // ---- merge level by level.  The host needs the k of every node for one thing only, the shapes of the merge
+  // products: the copy of `outs` is queued behind dc_setup, every other kernel of the level is launched with grids and
+  // LDS sized from the node sizes (the kernels read k on the device), and only then does the host wait for the copy
+  // and build the product plan, while those kernels run.
   static bool attr2 = false;
   if (!attr2) {
     DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dc_setup_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 36 * DC_MAXNODE + 64));
-    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dc_secular_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 16 * DC_MAXNODE + 64));
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 37 * DC_MAXNODE + 64));
+    DM_TRY(dc_secular_attr<DC_G>(ctx));
     attr2 = true;
   }
+  const bool dc_stats = getenv("DM_DC_STATS") != nullptr;
+  bool merged = false;
   for (int l = dmax - 1; l >= 0; --l) {
     std::vector<dc_node> nodes;
     int maxnn = 0;
@@ -1170,27 +1480,29 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
     if (big)
       DM_PLAUNCH(ctx, DM_PROF_DC, dc_setup_kernel<true>, dim3(nn_nodes), dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
     else
-      DM_PLAUNCH(ctx, DM_PROF_DC, dc_setup_kernel<false>, dim3(nn_nodes), dim3(256), (size_t)36 * maxnn + 64, ctx->stream, d_dm,
+      DM_PLAUNCH(ctx, DM_PROF_DC, dc_setup_kernel<false>, dim3(nn_nodes), dim3(256), (size_t)37 * maxnn + 64, ctx->stream, d_dm,
                          d_nodes, d_out);
+    const dc_nodeout* ho = nullptr;
+    DM_TRY(dm_download_queue(ctx, d_out, sizeof(dc_nodeout) * nn_nodes, reinterpret_cast<const void**>(&ho)));
+    const int* hf = nullptr;
+    DM_TRY(dm_download_queue(ctx, fail, sizeof(int) * np, reinterpret_cast<const void**>(&hf)));
     DM_PLAUNCH(ctx, DM_PROF_DC, dc_permute_kernel, dim3(nn_nodes), dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
     DM_PLAUNCH(ctx, DM_PROF_DC, dc_gather_kernel, dim3((maxnn + DCG - 1) / DCG, nn_nodes), dim3(256), 0, ctx->stream, d_dm,
                        d_nodes, d_out);
-    DM_HIP(ctx, hipGetLastError());
-    std::vector<dc_nodeout> ho(nn_nodes);
-    DM_TRY(dm_download(ctx, ho.data(), d_out, sizeof(dc_nodeout) * nn_nodes));
-    int kmax = 0;
-    for (auto& o : ho) kmax = std::max(kmax, o.k);
-    if (kmax == 0) continue;
-    const int kt = (kmax + 255) / 256;
-    if (big)
-      DM_PLAUNCH(ctx, DM_PROF_DC, dc_secular_kernel<true>, dim3(kt, nn_nodes), dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
-    else
-      DM_PLAUNCH(ctx, DM_PROF_DC, dc_secular_kernel<false>, dim3(kt, nn_nodes), dim3(256), (size_t)16 * kmax + 64, ctx->stream,
-                         d_dm, d_nodes, d_out);
-    DM_PLAUNCH(ctx, DM_PROF_DC, dc_zhat_kernel, dim3(kt, nn_nodes), dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
+    dc_roots_launch<DC_G>(ctx, big, maxnn, nn_nodes, d_dm, d_nodes, d_out);
+    const int kt = (maxnn + 255) / 256;
     DM_PLAUNCH(ctx, DM_PROF_DC, dc_unorm_kernel, dim3(kt, nn_nodes), dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
-    DM_PLAUNCH(ctx, DM_PROF_DC, dc_ubuild_kernel, dim3(kt, kmax, nn_nodes), dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
+    DM_PLAUNCH(ctx, DM_PROF_DC, dc_ubuild_kernel, dim3(kt, (maxnn + DC_UROWS - 1) / DC_UROWS, nn_nodes), dim3(256), 0, ctx->stream, d_dm, d_nodes, d_out);
     DM_HIP(ctx, hipGetLastError());
+    DM_TRY(dm_download_wait(ctx));
+    DM_TRY(fail_check(hf));
+    merged = true;
+    if (dc_stats) {  // debugging aid: what the deflation decided at this level
+      long long sk = 0, sd = 0, sr = 0;
+      for (int i = 0; i < nn_nodes; ++i) { sk += ho[i].k; sd += ho[i].ndefl; sr += ho[i].nrot; }
+      fprintf(stderr, "dc_solve: level %d nodes %d maxnn %d sum_k %lld sum_ndefl %lld sum_nrot %lld\n", l, nn_nodes, maxnn,
+              sk, sd, sr);
+    }
     std::vector<dm_gemm_desc> g;
     for (int i = 0; i < nn_nodes; ++i) {
       const dc_node& nd = nodes[i];
@@ -1205,6 +1517,12 @@ static int dc_solve(dm_ctx* ctx, const std::vector<dm_jac_herm_problem>& probs, 
       g.push_back(d);
     }
     DM_TRY(dm_gemm_grouped_launch(ctx, g));
+  }
+  if (!merged) {  // no merge level took the flags along
+    const int* hf = nullptr;
+    DM_TRY(dm_download_queue(ctx, fail, sizeof(int) * np, reinterpret_cast<const void**>(&hf)));
+    DM_TRY(dm_download_wait(ctx));
+    DM_TRY(fail_check(hf));
   }
   // ---- results: eigenvalues back into dd, eigenvector buffer per matrix
   zfinal.assign(np, nullptr);
