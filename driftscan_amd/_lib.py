@@ -669,8 +669,9 @@ def _project_cov(self, beam_svd, svnum, cl_pfl, out, out_off, npol=None, polmask
     self.check(rc, "dm_project_cov")
 
 
-def _fisher(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off, cl_symmetric=False):
-    """Per-m Fisher matrices (nblk, nbands, nbands) complex; see dm_fisher in include/driftmi.h."""
+def _band_args(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off):
+    """What dm_fisher, dm_qestimate and dm_psmc_alt take alike: (their arguments from nblk to evals_off_host in the
+    order of include/driftmi.h, nblk, nbands, nmodes as an int32 array).  The pointers keep their host arrays alive."""
     nblk, F, K, P, L = [int(x) for x in beam_svd.shape]
     nbands = int(cl_bands.shape[0])
     sv, svp = _iarr(svnum)
@@ -678,9 +679,16 @@ def _fisher(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals
     eo, eop = _larr(evecs_off)
     vo, vop = _larr(evals_off)
     nm, nmp = _iarr(nmodes)
+    args = (nblk, F, K, P, L, self.ptr(beam_svd), svp, l0p, nbands, self.ptr(cl_bands), self.ptr(evecs), eop, nmp,
+            self.ptr(evals), vop)
+    return args, nblk, nbands, nm
+
+
+def _fisher(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off, cl_symmetric=False):
+    """Per-m Fisher matrices (nblk, nbands, nbands) complex; see dm_fisher in include/driftmi.h."""
+    args, nblk, nbands, nm = _band_args(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off)
     out = self.empty((nblk, nbands, nbands), np.complex128)
-    rc = self.lib.dm_fisher(self.h, nblk, F, K, P, L, self.ptr(beam_svd), svp, l0p, nbands, self.ptr(cl_bands),
-                            self.ptr(evecs), eop, nmp, self.ptr(evals), vop, self.ptr(out), int(bool(cl_symmetric)))
+    rc = self.lib.dm_fisher(self.h, *args, self.ptr(out), int(bool(cl_symmetric)))
     self.check(rc, "dm_fisher")
     return out
 
@@ -695,19 +703,12 @@ def _qestimate(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, ev
                noise=False, crosspower=False, zero_mean=False):
     """Band-power q of R data columns per m-block, (nblk, nbands [+1], R) f64 on the device; see dm_qestimate in
     include/driftmi.h.  x (and y): the (nmodes_b x R) c128 columns of every block at element offsets x_off."""
-    nblk, F, K, P, L = [int(x_) for x_ in beam_svd.shape]
-    nbands = int(cl_bands.shape[0])
-    sv, svp = _iarr(svnum)
-    l0a, l0p = _iarr(l0)
-    eo, eop = _larr(evecs_off)
-    vo, vop = _larr(evals_off)
-    nm, nmp = _iarr(nmodes)
+    args, nblk, nbands, nm = _band_args(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off)
     xo, xop = _larr(x_off)
     flags = (QEST_NOISE if noise else 0) | (QEST_CROSSPOWER if crosspower else 0) | (QEST_ZERO_MEAN if zero_mean else 0)
     out = self.empty((nblk, nbands + (1 if noise else 0), int(R)), np.float64)
-    rc = self.lib.dm_qestimate(self.h, nblk, F, K, P, L, self.ptr(beam_svd), svp, l0p, nbands, self.ptr(cl_bands),
-                               self.ptr(evecs), eop, nmp, self.ptr(evals), vop, int(R), self.ptr(x),
-                               None if y is None else self.ptr(y), xop, flags, self.ptr(out))
+    rc = self.lib.dm_qestimate(self.h, *args, int(R), self.ptr(x), None if y is None else self.ptr(y), xop, flags,
+                               self.ptr(out))
     self.check(rc, "dm_qestimate")
     return out
 
@@ -805,19 +806,11 @@ def _psmc_alt(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, eva
               want_vecs=False):
     """Stochastic-trace Fisher matrices (nblk, nbands, nbands) c128 on the device of R weighted draws per block (and
     the band vectors (nbands, sum_b nmodes_b R) c128 with `want_vecs`); see dm_psmc_alt in include/driftmi.h."""
-    nblk, F, K, P, L = [int(x_) for x_ in beam_svd.shape]
-    nbands = int(cl_bands.shape[0])
-    sv, svp = _iarr(svnum)
-    l0a, l0p = _iarr(l0)
-    eo, eop = _larr(evecs_off)
-    vo, vop = _larr(evals_off)
-    nm, nmp = _iarr(nmodes)
+    args, nblk, nbands, nm = _band_args(self, beam_svd, svnum, l0, cl_bands, evecs, evecs_off, nmodes, evals, evals_off)
     xo, xop = _larr(x_off)
     out = self.empty((nblk, nbands, nbands), np.complex128)
     vecs = self.empty((nbands, max(int(nm.astype(np.int64).sum()) * int(R), 1)), np.complex128) if want_vecs else None
-    rc = self.lib.dm_psmc_alt(self.h, nblk, F, K, P, L, self.ptr(beam_svd), svp, l0p, nbands, self.ptr(cl_bands),
-                              self.ptr(evecs), eop, nmp, self.ptr(evals), vop, int(R), self.ptr(x), xop, int(nsamples),
-                              self.ptr(vecs), self.ptr(out))
+    rc = self.lib.dm_psmc_alt(self.h, *args, int(R), self.ptr(x), xop, int(nsamples), self.ptr(vecs), self.ptr(out))
     self.check(rc, "dm_psmc_alt")
     return (out, vecs) if want_vecs else out
 

@@ -304,4 +304,16 @@ __device__ __forceinline__ double dm_wave_max(double v) {
   return v;
 }
 
+// Sum of one value per thread over a 256-thread workgroup through red[256] in LDS (double, or double2 by component):
+// a fixed tree, so the same inputs give the same bits.  On return red[0] holds the sum, readable by every thread.
+template <typename T>
+__device__ __forceinline__ void dm_block_sum256(T* red, T v) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+}
+
 #endif  // __HIPCC__

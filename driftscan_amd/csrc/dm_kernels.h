@@ -219,6 +219,42 @@ int dm_trsm_plan_build(dm_ctx* ctx, const std::vector<dm_trsm_problem>& probs, b
 int dm_trsm_plan_run(dm_ctx* ctx, dm_trsm_plan& plan);
 
 // ---------------------------------------------------------------------------
+// band products of the power-spectrum estimators (dm_band.hip), shared by dm_qest.hip and dm_psmc.hip
+// ---------------------------------------------------------------------------
+constexpr int DM_BAND_LC = 4;   // multipoles per band-product workgroup: dm_band_qform's partial sums are per chunk of it
+
+// The projection of KL-basis columns (nmodes_b x R per m-block) onto the sky, temperature only:
+//   x1 = E^H [diag(w)] X,   x2[b][l][f][:] = B_f[:, 0, l]^H x1[f-range] for l >= l0eff[b]   (x2 laid out (nblk, L, F, R))
+// init() checks the arguments the estimators share and forms the per-block tables; the two stages are one grouped ZGEMM
+// each over 1 or 2 data sets, whose descriptors alternate per block (and per frequency) within the launch.
+struct dm_band_proj {
+  int nblk = 0, F = 0, K = 0, P = 0, L = 0, R = 0;
+  const int* svnum = nullptr;
+  const int* nmodes = nullptr;
+  const int64_t* evals_off = nullptr;
+  std::vector<int> ndof, active, l0eff;   // per block: sum of svnum, has work, first multipole (L for inactive blocks)
+  std::vector<int64_t> off1;              // per block: element offset of its (ndof x R) rows in x1
+  size_t tot1 = 0, totw = 0;              // elements of x1; length of the eigenvalue array the blocks address
+  int init(dm_ctx* ctx, int nblk_, int F_, int K_, int P_, int L_, const int* svnum_host, const int* l0_host,
+           const int* nmodes_host, const int64_t* evals_off_host, int R_);
+  // x1[s] + off1[b] = E_b^H diag(w_b) (xin[s] + x_off[b]); w (at evals_off, over the modes) may be nullptr
+  int to_svd(dm_ctx* ctx, const cplx* evecs, const int64_t* evecs_off, const double* w, const int64_t* x_off, int nset,
+             const cplx* const* xin, cplx* const* x1) const;
+  // x2[s] from x1[s]; blocks that have frequencies without modes are zeroed first
+  int to_sky(dm_ctx* ctx, const cplx* beam, int nset, const cplx* const* x1, cplx* const* x2) const;
+};
+
+// (nbands, F, F, L) -> tab (nbands, L, F, F): every (band, l) tile contiguous for the staging of the band products
+void dm_band_tables(dm_ctx* ctx, const double* cl_bands, double* tab, int nbands, int F, int L);
+// part[(a * nlc + lc) * N + n] = Re sum_{l in chunk lc, l >= l0[b]} y2[l, :, n]^H C_a[l] x2[l, :, n], n = b R + r < N = nblk R,
+// nlc = ceil(L / DM_BAND_LC); x2 / y2 (nblk, L, F, R) c128
+void dm_band_qform(dm_ctx* ctx, const cplx* x2, const cplx* y2, const double* tab, const int* l0_dev, double* part, int F,
+                   int L, int R, int N, int nbands);
+// z[b][a][l][f][:] = sum_f' C_a[l][f][f'] x2[b][l][f'][:] for l >= l0[b], 0 below; z (nblk, nbands, L, F, R) c128
+void dm_band_apply(dm_ctx* ctx, const cplx* x2, const double* tab, const int* l0_dev, cplx* z, int F, int L, int R, int N,
+                   int nbands);
+
+// ---------------------------------------------------------------------------
 // small utility kernels (dm_util.hip)
 // ---------------------------------------------------------------------------
 int dm_conj_transpose(dm_ctx* ctx, const cplx* src, int lds, cplx* dst, int ldd, int rows, int cols);

@@ -17,10 +17,6 @@
 
 namespace {
 
-constexpr int BA_LC = 4;          // multipoles per band_apply workgroup
-constexpr int BA_NJ = 4;          // 16-column MFMA sub-tiles per wave
-constexpr int BA_COLS = 4 * 16 * BA_NJ;   // real columns per workgroup: 256
-constexpr int BA_TILE = 4096;     // doubles of the staged table tile (32 KB of LDS)
 constexpr int BG_CHUNK = 2048;    // complex elements of (mode, sample) per band_gram partial sum
 
 struct draw_desc { const double* lam; cplx* x; int n; int m; };
@@ -58,12 +54,7 @@ __global__ __launch_bounds__(256) void psmc_mean_kernel(const double* __restrict
   const double* qa = q + row * ns;
   double s = 0.0;
   for (int i = threadIdx.x; i < ns; i += 256) s += qa[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-    __syncthreads();
-  }
+  dm_block_sum256(red, s);
   if (threadIdx.x == 0) mean[row] = red[0] / ns;
 }
 
@@ -78,105 +69,11 @@ __global__ __launch_bounds__(256) void psmc_cov_kernel(const double* __restrict_
   const double ma = mean[(size_t)b * nq + a], mc = mean[(size_t)b * nq + c];
   double s = 0.0;
   for (int i = threadIdx.x; i < ns; i += 256) s += (qa[i] - ma) * (qc[i] - mc);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-    __syncthreads();
-  }
+  dm_block_sum256(red, s);
   if (threadIdx.x == 0) {
     const double v = red[0] / (ns - 1);
     cov[((size_t)b * nq + a) * nq + c] = v;
     cov[((size_t)b * nq + c) * nq + a] = v;
-  }
-}
-
-// (nbands, F*F, L) -> (nbands, L, F*F): every (band, l) tile contiguous for band_apply's staging
-__global__ __launch_bounds__(256) void psmc_table_transpose_kernel(const double* __restrict__ in, double* __restrict__ out,
-                                                                   int FF, int L) {
-  __shared__ double t[32][33];
-  const size_t band = blockIdx.z;
-  const double* src = in + band * (size_t)FF * L;
-  double* dst = out + band * (size_t)FF * L;
-  const int l0 = blockIdx.x * 32, p0 = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-  for (int r = ty; r < 32; r += 8) {
-    const int p = p0 + r, l = l0 + tx;
-    t[r][tx] = (p < FF && l < L) ? src[(size_t)p * L + l] : 0.0;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int l = l0 + r, p = p0 + tx;
-    if (l < L && p < FF) dst[(size_t)l * FF + p] = t[tx][r];
-  }
-}
-
-// band_apply: Z[b][a][l][f][n] = sum_f' C_a[l][f][f'] X[b][l][f'][n] for l >= l0_b, 0 below, for every band a and the
-// R complex columns n of each block (X laid out (nblk, L, F, R) c128, Z (nblk, nbands, L, F, R) c128: each band's
-// slice is laid out as X, so the back-projection reads it without a transpose).  The tiling is band_qform's
-// (dm_qest.hip): the (a, l) tile is staged into LDS in row chunks of at most BA_TILE doubles, Z = C_a[l] X is an F x F
-// by F x 2N real product on v_mfma_f64_16x16x4_f64 (A = 16 tile rows from LDS, B = 16 real columns of X,
-// D = Z[i0 + (lane >> 4) + 4 r][col]) and each lane stores its D values instead of folding them.
-__global__ __launch_bounds__(256) void band_apply_kernel(const double* __restrict__ X, const double* __restrict__ tab,
-                                                        const int* __restrict__ l0b, double* __restrict__ Z, int F, int L,
-                                                        int R, int N, int nbands) {
-  __shared__ double tile[BA_TILE];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lbeg = blockIdx.y * BA_LC, lend = min(L, lbeg + BA_LC);
-  const int Fk = (F + 3) & ~3;
-  const int FR = max(16, min((F + 15) & ~15, (BA_TILE / Fk) & ~15));
-  const int kq = lane >> 4, cj = lane & 15;
-  const size_t fstride = 2 * (size_t)R;           // doubles between (l, f) and (l, f + 1)
-  const size_t lstride = (size_t)F * fstride;     // doubles between l and l + 1
-  const size_t bandstride = (size_t)L * lstride;  // doubles between the bands of one block in Z
-  size_t xbase[BA_NJ], zbase[BA_NJ];
-  int lfirst[BA_NJ];
-  bool valid[BA_NJ];
-#pragma unroll
-  for (int j = 0; j < BA_NJ; ++j) {
-    const int c = blockIdx.x * BA_COLS + wave * 16 * BA_NJ + j * 16 + cj;   // real column
-    valid[j] = c < 2 * N;
-    const int n = valid[j] ? c >> 1 : 0, b = n / R, r = n - b * R;
-    const size_t col = 2 * (size_t)r + (c & 1);
-    xbase[j] = (size_t)b * bandstride + col;
-    zbase[j] = (size_t)b * nbands * bandstride + col;
-    lfirst[j] = valid[j] ? l0b[b] : L;
-  }
-  for (int a = 0; a < nbands; ++a) {
-    for (int l = lbeg; l < lend; ++l) {
-      const double* T = tab + ((size_t)a * L + l) * F * F;
-      for (int r0 = 0; r0 < F; r0 += FR) {
-        const int nr = min(FR, F - r0);
-        __syncthreads();
-        for (int e = threadIdx.x; e < FR * Fk; e += 256) {
-          const int i = e / Fk, k = e - i * Fk;
-          tile[e] = (i < nr && k < F) ? T[(size_t)(r0 + i) * F + k] : 0.0;
-        }
-        __syncthreads();
-        for (int i0 = 0; i0 < nr; i0 += 16) {
-#pragma unroll
-          for (int j = 0; j < BA_NJ; ++j) {
-            const bool on = l >= lfirst[j];
-            const double* xc = X + xbase[j] + (size_t)l * lstride;
-            dm_f64x4 z = {0.0, 0.0, 0.0, 0.0};
-            for (int k0 = 0; k0 < Fk; k0 += 4) {
-              const int k = k0 + kq;
-              const double av = tile[(i0 + cj) * Fk + k];
-              const double bv = (on && k < F) ? xc[(size_t)k * fstride] : 0.0;
-              z = dm_mfma(av, bv, z);
-            }
-            if (valid[j]) {
-              double* zc = Z + zbase[j] + (size_t)a * bandstride + (size_t)l * lstride;
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const int f = r0 + i0 + kq + 4 * q;
-                if (f < r0 + nr) zc[(size_t)f * fstride] = on ? z[q] : 0.0;
-              }
-            }
-          }
-        }
-      }
-    }
   }
 }
 
@@ -220,15 +117,7 @@ __global__ __launch_bounds__(256) void band_gram_kernel(const gram_desc* __restr
     sr += x.x * y.x + x.y * y.y;
     si += x.y * y.x - x.x * y.y;
   }
-  red[threadIdx.x] = make_double2(sr, si);
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      red[threadIdx.x].x += red[threadIdx.x + h].x;
-      red[threadIdx.x].y += red[threadIdx.x + h].y;
-    }
-    __syncthreads();
-  }
+  dm_block_sum256(red, make_double2(sr, si));
   if (threadIdx.x == 0) part[(((size_t)blockIdx.z * nbands + a) * nbands + c) * nchunk + blockIdx.x] = red[0];
 }
 
@@ -305,31 +194,30 @@ extern "C" int dm_psmc_alt(dm_ctx* ctx, int nblk, int F, int K, int P, int L, co
                            const double* evals_dev, const int64_t* evals_off_host, int R, const void* x_dev,
                            const int64_t* x_off_host, int nsamples, void* v_dev, void* fisher_dev) {
   if (!ctx) return DM_EARG;
-  DM_ARG(ctx, nblk >= 0 && F > 0 && K > 0 && P > 0 && L > 0 && nbands > 0 && R > 0 && nsamples > 0 && beam_svd_dev &&
-                  svnum_host && l0_host && cl_bands_dev && evecs_dev && evecs_off_host && nmodes_host && evals_dev &&
-                  evals_off_host && x_dev && x_off_host && fisher_dev);
-  DM_ARG(ctx, F <= 256 && (int64_t)nblk * R < (1LL << 29) && nblk <= 65535 && nbands <= 128);
+  DM_ARG(ctx, nbands > 0 && nsamples > 0 && beam_svd_dev && cl_bands_dev && evecs_dev && evecs_off_host && evals_dev &&
+                  x_dev && x_off_host && fisher_dev);
+  DM_ARG(ctx, nblk <= 65535 && nbands <= 128);
+  dm_band_proj pj;
+  DM_TRY(pj.init(ctx, nblk, F, K, P, L, svnum_host, l0_host, nmodes_host, evals_off_host, R));
   if (nblk == 0) return DM_OK;
   dm_ws_scope ws_scope__(ctx);
   const int N = nblk * R, PL = P * L;
+  const std::vector<int>& ndof = pj.ndof;
+  const std::vector<int>& active = pj.active;
+  const std::vector<int>& l0eff = pj.l0eff;
+  const std::vector<int64_t>& off1 = pj.off1;
+  const size_t tot1 = pj.tot1, totw = pj.totw;
   const cplx* evecs = reinterpret_cast<const cplx*>(evecs_dev);
   const cplx* beam = reinterpret_cast<const cplx*>(beam_svd_dev);
   const cplx* xin = reinterpret_cast<const cplx*>(x_dev);
   cplx* fisher = reinterpret_cast<cplx*>(fisher_dev);
 
-  std::vector<int> ndof(nblk, 0), active(nblk, 0), l0eff(nblk, L);
-  std::vector<int64_t> off1(nblk, 0), offv(nblk, 0);
-  size_t tot1 = 0, totv = 0, totw = 0;
+  std::vector<int64_t> offv(nblk, 0);
+  size_t totv = 0;
   for (int b = 0; b < nblk; ++b) {
-    for (int f = 0; f < F; ++f) ndof[b] += svnum_host[b * F + f];
-    DM_ARG(ctx, svnum_host[b * F] >= 0 && ndof[b] >= 0 && nmodes_host[b] >= 0);
-    active[b] = nmodes_host[b] > 0 && ndof[b] > 0 && l0_host[b] < L;
-    if (active[b]) l0eff[b] = std::max(l0_host[b], 0);
-    off1[b] = (int64_t)tot1;
-    tot1 += (size_t)ndof[b] * R;
+    DM_ARG(ctx, nmodes_host[b] >= 0);
     offv[b] = (int64_t)totv;
     totv += (size_t)nmodes_host[b] * R;
-    totw = std::max<size_t>(totw, (size_t)evals_off_host[b] + nmodes_host[b]);
   }
   const size_t x2n = (size_t)nblk * L * F * R;
   cplx* x1 = dm_ws_alloc_t<cplx>(ctx, std::max<size_t>(tot1, 1));
@@ -343,48 +231,11 @@ extern "C" int dm_psmc_alt(dm_ctx* ctx, int nblk, int F, int K, int P, int L, co
   if (!x1 || !x2 || !z || !y1 || !v || !w || !tab || !d_l0) return DM_ENOMEM;
   if (v_dev) DM_TRY(dm_fill_zero(ctx, v, sizeof(cplx) * std::max<size_t>(totv, 1) * nbands));
 
-  {
-    const int FF = F * F;
-    DM_PLAUNCH(ctx, DM_PROF_UTIL, psmc_table_transpose_kernel, dim3((L + 31) / 32, (FF + 31) / 32, nbands), dim3(256), 0,
-               ctx->stream, cl_bands_dev, tab, FF, L);
-  }
-  // x1 = E^H X (the draws carry their C^-1/2 weight already)
-  {
-    std::vector<dm_gemm_desc> g;
-    for (int b = 0; b < nblk; ++b) {
-      if (!active[b]) continue;
-      const int n = ndof[b], nm = nmodes_host[b];
-      g.push_back(dm_gemm_make(evecs + evecs_off_host[b], 1, n, true, xin + x_off_host[b], R, 1, false, x1 + off1[b], R,
-                               n, R, nm));
-    }
-    DM_TRY(dm_gemm_grouped_launch(ctx, g));
-  }
-  // x2[b][l][f][:] = B_f[:, 0, l]^H x1[f-range] for l >= l0; frequencies without modes are zero
-  {
-    std::vector<dm_gemm_desc> g;
-    for (int b = 0; b < nblk; ++b) {
-      if (!active[b]) continue;
-      const int l0 = l0eff[b];
-      bool gaps = false;
-      for (int f = 0; f < F; ++f) gaps |= svnum_host[b * F + f] == 0;
-      if (gaps) DM_TRY(dm_fill_zero(ctx, x2 + (size_t)b * L * F * R, sizeof(cplx) * (size_t)L * F * R));
-      int row = 0;
-      for (int f = 0; f < F; ++f) {
-        const int ns = svnum_host[b * F + f];
-        if (ns > 0) {
-          const cplx* Bf = beam + (((size_t)b * F + f) * K) * PL + l0;   // pol 0
-          g.push_back(dm_gemm_make(Bf, 1, PL, true, x1 + off1[b] + (size_t)row * R, R, 1, false,
-                                   x2 + (size_t)b * L * F * R + ((size_t)l0 * F + f) * R, F * R, L - l0, R, ns));
-        }
-        row += ns;
-      }
-    }
-    DM_TRY(dm_gemm_grouped_launch(ctx, g));
-  }
-  // Z_a = C_a x2 for every band
-  DM_PLAUNCH(ctx, DM_PROF_UTIL, band_apply_kernel, dim3((unsigned)((2 * (size_t)N + BA_COLS - 1) / BA_COLS),
-             (unsigned)((L + BA_LC - 1) / BA_LC)), dim3(256), 0, ctx->stream, reinterpret_cast<const double*>(x2), tab,
-             d_l0, reinterpret_cast<double*>(z), F, L, R, N, nbands);
+  dm_band_tables(ctx, cl_bands_dev, tab, nbands, F, L);
+  // x1 = E^H X (the draws carry their C^-1/2 weight already), x2 = B^H x1, Z_a = C_a x2 for every band
+  DM_TRY(pj.to_svd(ctx, evecs, evecs_off_host, nullptr, x_off_host, 1, &xin, &x1));
+  DM_TRY(pj.to_sky(ctx, beam, 1, &x1, &x2));
+  dm_band_apply(ctx, x2, tab, d_l0, z, F, L, R, N, nbands);
   // y1_a[f-range] = B_f[:, 0, l >= l0] Z_a[l >= l0][f], then v_a = E y1_a
   {
     std::vector<dm_gemm_desc> g;
