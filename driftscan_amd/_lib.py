@@ -156,6 +156,14 @@ SIGNATURES = {
     "dm_blockvec_grouped": (c_int, [c_vp, c_int, ctypes.POINTER(ZgemmProblem)]),
     "dm_mmode_twiddle": (c_int, [c_vp, c_int, c_int, c_vp]),
     "dm_ts_noise": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.c_uint64, c_int, c_vp]),
+    "dm_ts_gain_coeff": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_dbl), c_dbl,
+                ctypes.c_uint64, c_int, c_int, c_vp]),
+    "dm_ts_gain_compose": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "dm_ts_gain_tile": (c_int, [c_int]),
+    "dm_ts_gain_apply": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp,
+                c_vp, c_i64, c_int]),
 }
 
 _lib = None
@@ -573,6 +581,111 @@ def _iarr(a):
 def _larr(a):
     a = np.ascontiguousarray(a, dtype=np.int64)
     return a, a.ctypes.data_as(ctypes.POINTER(c_i64))
+
+
+def _is_c128(t, shape=None):
+    return (hasattr(t, "data_ptr") and t.is_complex() and t.element_size() == 16 and t.is_contiguous()
+            and (shape is None or tuple(t.shape) == tuple(shape)))
+
+
+def _rstride(t):
+    """Element stride between the realisations of a (nreal, nf, npairs, ntime) c128 tensor that is contiguous apart from
+    it (a frequency slice of a contiguous array), or None."""
+    if not (hasattr(t, "data_ptr") and t.is_complex() and t.element_size() == 16 and t.dim() == 4):
+        return None
+    nreal, nf, npairs, ntime = (int(v) for v in t.shape)
+    if t.numel() and tuple(t.stride())[1:] != (npairs * ntime, ntime, 1) and not t[0].is_contiguous():
+        return None
+    rs = int(t.stride(0)) if nreal > 1 else nf * npairs * ntime
+    return rs if rs >= nf * npairs * ntime else None
+
+
+def _rows_overlap(a, b):
+    """Whether two tensors that `_rstride` accepts, of one shape and (beyond one realisation) one stride, share an
+    element: some row of `b` begins less than a row's length from some row of `a`."""
+    nreal, row = int(a.shape[0]), 16 * int(a[0].numel())
+    if row == 0 or nreal == 0:
+        return False
+    rs, d = 16 * _rstride(a), b.data_ptr() - a.data_ptr()
+    near = -d // rs                                         # d + k rs is smallest in size at k = near or near + 1
+    return any(abs(d + min(max(k, 1 - nreal), nreal - 1) * rs) < row for k in (near, near + 1))
+
+
+def _ts_gain_coeff(self, nreal, fglobal, nfeed, ck, sigma, seed, first=0, stream=25, broadband=False, out=None):
+    """Fourier coefficients out[r, i, a, k] = sigma ck[k] (A_k - i B_k) of one component of the feed gains on the device
+    (dm_ts_gain_coeff; `skysim.gain_coeff_host` restates it): `fglobal` the global frequency index of every row i, `ck`
+    the (K + 1) weights, stream 25 (amplitude) or 26 (phase), broadband=True one draw for all frequencies.  Every element
+    of `out` (nreal, nf, nfeed, K + 1) is written."""
+    fg, fgp = _iarr(fglobal)
+    ck = np.ascontiguousarray(ck, dtype=np.float64)
+    nreal, nfeed, first, nf, nk = int(nreal), int(nfeed), int(first), int(fg.shape[0]), int(ck.shape[0])
+    if fg.ndim != 1 or ck.ndim != 1 or (nf and int(fg.min()) < 0):
+        raise ValueError("ts_gain_coeff: non-negative global frequency indices (nf) and weights (K + 1) expected")
+    if nreal < 0 or nfeed < 0 or first < 0:
+        raise ValueError("ts_gain_coeff: nreal, nfeed and first must not be negative")
+    if out is None:
+        out = self.empty((nreal, nf, nfeed, nk), np.complex128)
+    if not _is_c128(out, (nreal, nf, nfeed, nk)):
+        raise ValueError("ts_gain_coeff: out must be a contiguous (nreal, nf, nfeed, K + 1) complex128 tensor")
+    rc = self.lib.dm_ts_gain_coeff(self.h, nreal, nf, nfeed, nk, fgp, int(bool(broadband)),
+                                   ck.ctypes.data_as(ctypes.POINTER(c_dbl)), float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   first, int(stream), self.ptr(out))
+    self.check(rc, "dm_ts_gain_coeff")
+    return out
+
+
+def _ts_gain_compose(self, xamp, xphase, out=None):
+    """g = (1 + Re xamp) exp(i Re xphase) elementwise on the device (dm_ts_gain_compose): complex128 tensors of one shape
+    (the series as the ZGEMM leaves them)."""
+    if not (_is_c128(xamp) and _is_c128(xphase, xamp.shape)):
+        raise ValueError("ts_gain_compose: two contiguous complex128 tensors of one shape expected")
+    if out is None:
+        out = self.empty(tuple(xamp.shape), np.complex128)
+    if not _is_c128(out, xamp.shape):
+        raise ValueError("ts_gain_compose: out must be a contiguous complex128 tensor of the inputs' shape")
+    self.check(self.lib.dm_ts_gain_compose(self.h, int(xamp.numel()), self.ptr(xamp), self.ptr(xphase), self.ptr(out)),
+               "dm_ts_gain_compose")
+    return out
+
+
+def _ts_gain_apply(self, g, class_off, members, sky, out=None, accumulate=False):
+    """Per-feed gains on stacked visibilities (dm_ts_gain_apply): out[r, f, c, t] (+)= G[r, f, c, t] sky[r, f, c, t] with
+    G = (1 / n_c) sum_{(i, j) in class c} g_i conj(g_j) over the pair table (`class_off`, `members`) of
+    `TransitTelescope.redundant_pairs` — `skysim.baseline_gains_host` restates G.  g is contiguous
+    (g_nreal, nf, nfeed, ntime) with g_nreal 1 (one array for all realisations) or nreal; sky and out are
+    (nreal, nf, npairs, ntime), contiguous or frequency slices [:, f0:f1] of contiguous arrays with one stride between
+    realisations; out (a new tensor by default) must share no element with sky.  accumulate=True adds to what out holds:
+    the noise `ts_noise` drew there, so the gains multiply the sky part only and the noise keeps its level — the convention
+    of this package.  An empty class, a feed index outside g or more feeds than one time sample of LDS holds are refused before
+    anything is launched."""
+    if not (_is_c128(g) and g.dim() == 4) or _rstride(sky) is None:
+        raise ValueError("ts_gain_apply: complex128 tensors g (g_nreal, nf, nfeed, ntime) and sky "
+                         "(nreal, nf, npairs, ntime) expected")
+    g_nreal, nf, nfeed, ntime = (int(v) for v in g.shape)
+    nreal, _, npairs, _ = (int(v) for v in sky.shape)
+    off, offp = _iarr(class_off)
+    mem, memp = _iarr(np.asarray(members, dtype=np.int32).reshape(-1, 2))
+    if tuple(sky.shape) != (nreal, nf, npairs, ntime) or g_nreal not in (1, nreal):
+        raise ValueError("ts_gain_apply: g %s does not fit sky %s" % (tuple(g.shape), tuple(sky.shape)))
+    if off.shape != (npairs + 1,) or mem.shape[0] != int(off[-1]):
+        raise ValueError("ts_gain_apply: class_off (npairs + 1) and members (class_off[-1], 2) expected")
+    if out is None:
+        if accumulate:
+            raise ValueError("ts_gain_apply: accumulate needs the buffer to add to")
+        out = self.empty((nreal, nf, npairs, ntime), np.complex128)
+    if (_rstride(out) is None or tuple(out.shape) != tuple(sky.shape) or (nreal > 1 and _rstride(out) != _rstride(sky))
+            or _rows_overlap(sky, out)):
+        raise ValueError("ts_gain_apply: out must be a complex128 tensor of sky's shape and strides that shares no "
+                         "element with sky")
+    rc = self.lib.dm_ts_gain_apply(self.h, nreal, g_nreal, nf, nfeed, npairs, ntime, offp, memp, self.ptr(g), self.ptr(sky),
+                                   self.ptr(out), _rstride(sky), int(bool(accumulate)))
+    self.check(rc, "dm_ts_gain_apply")
+    return out
+
+
+Context.ts_gain_coeff = _ts_gain_coeff
+Context.ts_gain_compose = _ts_gain_compose
+Context.ts_gain_apply = _ts_gain_apply
 
 
 def _svd_chain(self, beam_m, noisew, polsvcut, skip_svd_inv=False, max_bytes=None, lmin=None):

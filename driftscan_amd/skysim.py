@@ -11,6 +11,9 @@ them from the arrays every other stage works from: ``[pol, pol, l, freq, freq]``
   key = seed, counter ``(p F + f, (l << 16) | m, r, stream)``, complex with E|z|^2 = 1 for m > 0 and real with
   E z^2 = 1 for m = 0; E and B are zero for l < 2 and everything is zero for m > l.
 
+Per-feed gain errors: ``GainModel`` and its numpy statement ``gain_coeff_host``, ``gains_host``
+and ``baseline_gains_host``, the oracle of ``gains_device`` / ``Context.ts_gain_apply``.
+
 Point sources are the non-Gaussian skies: ``source_alm`` gives the exact band-limited a_lm of a
 catalogue on the device (``dm_source_alm``), ``source_alm_host`` is its numpy statement and oracle.
 
@@ -20,10 +23,15 @@ no GPU.
 """
 import numpy as np
 
+from .telescope import T_SIDEREAL
+
 STREAM_SKY_SIGNAL = 16       # clear of psmc.STREAM_X, STREAM_X2, STREAM_ALT = 0, 1, 2
 STREAM_SKY_FOREGROUND = 17
 STREAM_TS_NOISE = 24         # receiver noise (dm_ts_noise): the low byte of counter word 3, the realisation above it
 TS_NOISE_MAX_REAL = 1 << 24
+STREAM_TS_GAIN_AMP = 25      # per-feed gain errors (dm_ts_gain_coeff): amplitude and phase components, laid out as the noise
+STREAM_TS_GAIN_PHASE = 26
+GAIN_BROADBAND = 0xFFFFFFFF  # the frequency word of a gain shared by all channels (freq_corr = "full")
 LMAX_LIMIT = 65536           # m and l share one 32-bit counter word
 
 
@@ -151,6 +159,185 @@ def correlate_host(T, z):
     re = np.einsum("lij,...jlm->...ilm", T, z.real.astype(np.longdouble))
     im = np.einsum("lij,...jlm->...ilm", T, z.imag.astype(np.longdouble))
     return re + 1j * im
+
+
+
+# ---- per-feed gain errors ------------------------------------------------------------------------
+class GainModel:
+    """Complex gain errors of the feeds, g = (1 + x_amp(t)) exp(i x_phase(t)) per (feed, frequency, realisation).
+
+    Each x_q is a stationary Gaussian process, periodic over the sidereal day, of standard deviation ``sigma_amp`` /
+    ``sigma_phase`` (radians) and a Gaussian spectrum of correlation time ``corr_time`` seconds (0: equal weights, white
+    for an odd number of samples).  ``freq_corr``: "none" — independent channels; "full" — one broadband gain per feed.
+    The gains multiply the sky part of a simulated visibility only: receiver noise is added after them at its usual
+    level."""
+
+    def __init__(self, sigma_amp=0.0, sigma_phase=0.0, corr_time=0.0, freq_corr="none", seed=0):
+        self.sigma_amp, self.sigma_phase, self.corr_time = float(sigma_amp), float(sigma_phase), float(corr_time)
+        self.freq_corr, self.seed = str(freq_corr), int(seed)
+        if self.sigma_amp < 0 or self.sigma_phase < 0 or self.corr_time < 0:
+            raise ValueError("GainModel: sigma_amp, sigma_phase and corr_time must not be negative")
+        if self.freq_corr not in ("none", "full"):
+            raise ValueError("GainModel: freq_corr is 'none' or 'full', not %r" % (freq_corr,))
+
+    @classmethod
+    def from_config(cls, conf):
+        conf = dict(conf)
+        unknown = set(conf) - {"sigma_amp", "sigma_phase", "corr_time", "freq_corr", "seed"}
+        if unknown:
+            raise ValueError("GainModel: unknown keys %s" % sorted(unknown))
+        return cls(**conf)
+
+    def __repr__(self):
+        return "GainModel(sigma_amp=%r, sigma_phase=%r, corr_time=%r, freq_corr=%r, seed=%r)" % (
+            self.sigma_amp, self.sigma_phase, self.corr_time, self.freq_corr, self.seed)
+
+    def kmax(self, ntime):
+        """K: (ntime - 1) // 2, capped where s_k = exp(-(2 pi k corr_time / T_SIDEREAL)^2 / 2) drops below 2^-53, i.e. at
+        floor(sqrt(106 ln 2) T_SIDEREAL / (2 pi corr_time))."""
+        K = (int(ntime) - 1) // 2
+        if self.corr_time > 0.0:
+            K = min(K, int(np.floor(np.sqrt(106.0 * np.log(2.0)) * T_SIDEREAL / (2.0 * np.pi * self.corr_time))))
+        return max(K, 0)
+
+    def weights(self, ntime):
+        """c_k, k = 0 .. K: c_k^2 = s_k / sum_j s_j (sum of squares 1, so Var x_q = sigma_q^2)."""
+        k = np.arange(self.kmax(ntime) + 1, dtype=np.float64)
+        s = np.exp(-0.5 * (2.0 * np.pi * k * self.corr_time / T_SIDEREAL) ** 2)
+        return np.sqrt(s / s.sum())
+
+    def correlation(self, ntime, lag):
+        """E x(t) x(t + lag) / sigma^2 = sum_k c_k^2 cos(2 pi k lag / ntime), exactly."""
+        c = self.weights(ntime)
+        return float(np.sum(c**2 * np.cos(2.0 * np.pi * np.arange(c.shape[0]) * lag / ntime)))
+
+
+def as_gains(gains):
+    """None, a GainModel, a dict (-> GainModel.from_config) or an explicit array / device tensor, checked."""
+    if gains is None or isinstance(gains, GainModel):
+        return gains
+    if isinstance(gains, dict):
+        return GainModel.from_config(gains)
+    if hasattr(gains, "data_ptr"):
+        if gains.dim() not in (3, 4) or not (gains.is_complex() and gains.element_size() == 16):
+            raise ValueError("gains: a complex128 tensor (nf, nfeed, ntime) or (nreal, nf, nfeed, ntime) expected")
+        return gains
+    gains = np.asarray(gains)
+    if gains.ndim not in (3, 4) or gains.dtype != np.complex128:
+        raise ValueError("gains: a complex128 array (nf, nfeed, ntime) or (nreal, nf, nfeed, ntime) expected")
+    return gains
+
+
+def _gain_fword(model, fglobal):
+    fg = np.asarray(fglobal, dtype=np.int64).reshape(-1)
+    if fg.size and fg.min() < 0:
+        raise ValueError("gains: negative global frequency index")
+    return np.full(fg.shape, GAIN_BROADBAND, dtype=np.uint64) if model.freq_corr == "full" else fg.astype(np.uint64)
+
+
+def gain_coeff_host(model, nfeed, fglobal, ntime, nreal, first=0, stream=STREAM_TS_GAIN_AMP):
+    """The coefficients of ``Context.ts_gain_coeff`` in numpy: [nreal, nf, nfeed, K + 1],
+    sigma_q c_k (A_k - i B_k) = sigma_q c_k sqrt(2) conj(z_k) with z_k the unit draw of counter
+    (feed, fglobal[i] or 0xFFFFFFFF, k, ((first + r) << 8) | stream), key = the model's seed."""
+    if stream not in (STREAM_TS_GAIN_AMP, STREAM_TS_GAIN_PHASE):
+        raise ValueError("gain_coeff_host: stream is STREAM_TS_GAIN_AMP or STREAM_TS_GAIN_PHASE")
+    if first < 0 or first + nreal > TS_NOISE_MAX_REAL:
+        raise ValueError("gain_coeff_host: realisations beyond the %d the counter word holds" % TS_NOISE_MAX_REAL)
+    sigma = model.sigma_amp if stream == STREAM_TS_GAIN_AMP else model.sigma_phase
+    ck = model.weights(ntime)
+    r, f, a, k = np.meshgrid(np.arange(first, first + nreal, dtype=np.uint64), _gain_fword(model, fglobal),
+                             np.arange(nfeed, dtype=np.uint64), np.arange(ck.shape[0], dtype=np.uint64), indexing="ij")
+    seed = int(model.seed) & 0xFFFFFFFFFFFFFFFF
+    w = _philox4x32_10([a, f, k, (r << np.uint64(8)) | np.uint64(stream)], (seed & 0xFFFFFFFF, seed >> 32))
+    rad = np.sqrt(-np.log(_u53(w[0], w[1]))) * (sigma * ck * 1.4142135623730951)
+    th = 6.283185307179586 * _u53(w[2], w[3])
+    return rad * np.cos(th) - 1j * (rad * np.sin(th))
+
+
+def gain_series_host(coeff, ntime):
+    """x(t) = Re sum_k coeff[..., k] e^{2 pi i k t / ntime}: [..., ntime] float64."""
+    k = np.arange(coeff.shape[-1])
+    ph = np.exp(2j * np.pi * (np.outer(k, np.arange(ntime)) % ntime) / ntime)
+    return (coeff @ ph).real
+
+
+def gains_host(model, nfeed, fglobal, ntime, nreal, first=0):
+    """The gains of ``gains_device`` in numpy: [nreal, nf, nfeed, ntime] complex128."""
+    xa = gain_series_host(gain_coeff_host(model, nfeed, fglobal, ntime, nreal, first, STREAM_TS_GAIN_AMP), ntime)
+    xp = gain_series_host(gain_coeff_host(model, nfeed, fglobal, ntime, nreal, first, STREAM_TS_GAIN_PHASE), ntime)
+    return (1.0 + xa) * np.cos(xp) + 1j * ((1.0 + xa) * np.sin(xp))
+
+
+def baseline_gains_host(g, class_off, members):
+    """G[..., c, t] = (1 / n_c) sum_{(i, j) in class c} g[..., i, t] conj(g[..., j, t]) for g [..., nfeed, ntime] and the
+    pair table of ``TransitTelescope.redundant_pairs``: what per-feed gains do to a stack of redundant baselines.  The
+    members of a class are added one after the other in the table's order."""
+    g = np.asarray(g)
+    class_off = np.asarray(class_off, dtype=np.int64)
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    n = np.diff(class_off)
+    if class_off[0] != 0 or np.any(n <= 0) or class_off[-1] != members.shape[0]:
+        raise ValueError("baseline_gains_host: class offsets must start at 0, ascend strictly and end at len(members)")
+    if members.size and (members.min() < 0 or members.max() >= g.shape[-2]):
+        raise ValueError("baseline_gains_host: a member names a feed the gains do not have")
+    G = np.zeros(g.shape[:-2] + (n.shape[0], g.shape[-1]), dtype=g.dtype)
+    for c in range(n.shape[0]):
+        for i, j in members[class_off[c] : class_off[c + 1]]:
+            G[..., c, :] += g[..., i, :] * g[..., j, :].conj()
+    return G / n[:, None]
+
+
+def check_explicit_gains(gains, nreal, nf, nfeed, ntime):
+    """Refuse an explicit gain array that is not (nf, nfeed, ntime) or (1 or nreal, nf, nfeed, ntime); only shapes are
+    looked at."""
+    shape = tuple(int(v) for v in gains.shape)
+    if shape[-3:] != (nf, nfeed, ntime) or shape[:-3] not in ((), (1,), (nreal,)):
+        raise ValueError("gains: shape %s does not fit (nreal = %d, nf = %d, nfeed = %d, ntime = %d)"
+                         % (shape, nreal, nf, nfeed, ntime))
+
+
+def explicit_gains(gains, nreal, nf, r0, R, sel, nfeed, ntime):
+    """The rows of an explicit gain array for realisations r0 .. r0 + R - 1 of a call of `nreal` realisations and `nf`
+    frequencies, at the positions `sel` of its frequencies: (1 or R, len(sel), nfeed, ntime), numpy or device as given."""
+    check_explicit_gains(gains, nreal, nf, nfeed, ntime)
+    g = gains if len(gains.shape) == 4 else gains[None]
+    g = g if g.shape[0] == 1 else g[r0 : r0 + R]
+    if isinstance(sel, range) and sel.step == 1:
+        return g[:, sel.start : sel.stop]             # a view: nothing is copied
+    return g[:, list(sel)]
+
+
+def gain_series_device(model, nfeed, fglobal, ntime, nreal, first=0, stream=STREAM_TS_GAIN_AMP):
+    """(coeff, x) on the device: the coefficients (nreal, nf, nfeed, K + 1) of one component (``Context.ts_gain_coeff``)
+    and its series (nreal, nf, nfeed, ntime) as the complex numbers sum_k coeff_k e^{2 pi i k t / ntime}, whose real part
+    is x(t): one strided-batched ZGEMM against ntime times the conjugate of the table of ``Context.mmode_twiddle``."""
+    from .device import get_context
+
+    ctx = get_context()
+    fg = np.asarray(fglobal, dtype=np.int64).reshape(-1)
+    nf, ntime, nreal, nfeed = int(fg.shape[0]), int(ntime), int(nreal), int(nfeed)
+    ck = model.weights(ntime)
+    K = ck.shape[0] - 1
+    sigma = model.sigma_amp if stream == STREAM_TS_GAIN_AMP else model.sigma_phase
+    coeff = ctx.ts_gain_coeff(nreal, fg, nfeed, ck, sigma, model.seed, first, stream, broadband=model.freq_corr == "full")
+    x = ctx.empty((nreal, nf, nfeed, ntime), np.complex128)
+    rows = nreal * nf * nfeed
+    if rows and ntime:
+        W = ctx.mmode_twiddle(ntime, K)
+        ctx.zgemm(coeff, W, x, rows, ntime, K + 1, rsA=K + 1, csA=1, rsB=1, csB=K + 1, ldc=ntime, conjB=True,
+                  alpha=float(ntime))
+    return coeff, x
+
+
+def gains_device(model, nfeed, fglobal, ntime, nreal, first=0, out=None):
+    """The gains of `model` on the device: (nreal, nf, nfeed, ntime) c128 — ``gains_host`` restates it.  The series of
+    both components come from ``gain_series_device`` and ``Context.ts_gain_compose`` makes g from them.  Working memory:
+    two more buffers of g's size."""
+    from .device import get_context
+
+    xa = gain_series_device(model, nfeed, fglobal, ntime, nreal, first, STREAM_TS_GAIN_AMP)[1]
+    xp = gain_series_device(model, nfeed, fglobal, ntime, nreal, first, STREAM_TS_GAIN_PHASE)[1]
+    return get_context().ts_gain_compose(xa, xp, out=out)
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------

@@ -266,6 +266,24 @@ class TransitTelescope(config.Reader):
     feedmask = property(lambda self: self._pair("feedmask"))
     feedconj = property(lambda self: self._pair("feedconj"))
 
+    def redundant_pairs(self):
+        """(class_off (npairs + 1) int32, members (n, 2) int32): the feed pairs stacked into every unique pair.  The
+        members of unique pair c are the pairs (i, j) with feedmask & ~feedconj and feedmap == c in row-major (i, j)
+        order, so there are redundancy[c] of them and uniquepairs[c] is the first.  A pair marked conjugate is the
+        transpose of a listed one and does not appear itself."""
+        if self._pairs is None:
+            self.calculate_feedpairs()
+        if "redundant_pairs" not in self._pairs:
+            sel = self._pairs["feedmask"] & ~self._pairs["feedconj"]
+            i, j = np.nonzero(sel)                                    # row-major
+            lab = self._pairs["feedmap"][i, j]
+            order = np.argsort(lab, kind="stable")
+            members = np.stack([i[order], j[order]], axis=1).astype(np.int32).reshape(-1, 2)
+            count = np.bincount(lab, minlength=self.npairs)
+            class_off = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+            self._pairs["redundant_pairs"] = (class_off, members)
+        return self._pairs["redundant_pairs"]
+
     @property
     def npairs(self):
         return self.uniquepairs.shape[0]

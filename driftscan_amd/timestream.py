@@ -657,15 +657,21 @@ def _sources_alm(sources, tel, freqs, to_host):
 
 
 def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=(), klname=None, sky_seed=0,
-             sky_realisation=0, sources=(), **kwargs):
+             sky_realisation=0, sources=(), gains=None, **kwargs):
     """Simulated timestream of the telescope of ProductManager `m` (timestream.py:645-829).
 
     maps: list of files holding a dataset `map` [freq, pol, pixel] whose sum is the sky; ndays = 0: no noise;
     resolution = 0: 2 mmax + 1 time samples.  skymodels: any of "signal", "foreground" — a Gaussian realisation
     (`sky_seed`, `sky_realisation`) of that covariance of KL transform `klname` is drawn on the device (`skysim.draw_alm`,
     every rank the rows of its own frequencies) and its a_lm are added to those of the maps.  sources: point-source
-    catalogues (dicts or files, `skysim.read_catalogue`) whose exact a_lm (`skysim.source_alm`) are added too.  Returns
-    the Timestream."""
+    catalogues (dicts or files, `skysim.read_catalogue`) whose exact a_lm (`skysim.source_alm`) are added too.
+
+    gains: per-feed gain errors — a `skysim.GainModel`, a dict of its arguments (the YAML
+    `gains:` mapping) or an explicit complex128 array (nf, nfeed, ntime) / (1, nf, nfeed, ntime) over the
+    telescope's frequencies (every rank takes the rows of its own).  A model is evaluated for realisation `sky_realisation` (`skysim.gains_host`).  The time stream of the
+    sky is multiplied by the stacked baseline gain G (`skysim.baseline_gains_host` on `redundant_pairs()`), all in numpy;
+    the noise is transformed by itself and added after: gains multiply the sky part only and the noise level is
+    unchanged.  With gains=None nothing of this runs.  Returns the Timestream."""
     bt = m.beamtransfer
     tel = bt.telescope
     lmax, mmax, nfreq, npol = tel.lmax, tel.mmax, tel.nfreq, tel.num_pol_sky
@@ -730,9 +736,27 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
         noise_vis *= (noise_ps / 2.0) ** 0.5
         if seed is not None:
             np.random.seed()
-        col_vis += noise_vis
+        if gains is None:
+            col_vis += noise_vis
+    else:
+        noise_vis = None
 
     vis_stream = np.fft.ifft(col_vis, axis=-1) * ntime
+    gain_f = None
+    if gains is not None:
+        from . import skysim
+
+        gains = skysim.as_gains(gains)
+        if isinstance(gains, skysim.GainModel):
+            gain_f = skysim.gains_host(gains, tel.nfeed, local_freq, ntime, 1, first=int(sky_realisation))[0]
+        else:
+            if hasattr(gains, "data_ptr"):
+                gains = gains.cpu().numpy()
+            gain_f = skysim.explicit_gains(gains, 1, nfreq, 0, 1, list(local_freq), tel.nfeed, ntime)[0]
+        if lfreq:
+            vis_stream = vis_stream * skysim.baseline_gains_host(gain_f, *tel.redundant_pairs()).transpose(1, 0, 2)
+        if noise_vis is not None:
+            vis_stream = vis_stream + np.fft.ifft(noise_vis, axis=-1) * ntime
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     tstream = Timestream(outdir, m)
     for lfi, fi in enumerate(local_freq):
@@ -740,6 +764,8 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
         with storage.File(tstream._ffile(fi), "w") as f:
             f.create_dataset("timestream", data=np.ascontiguousarray(vis_stream[:, lfi]))
             f.create_dataset("phi", data=tphi)
+            if gain_f is not None:
+                f.create_dataset("gain", data=np.ascontiguousarray(gain_f[lfi]))
             f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
             f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
             f.create_dataset("feedmask", data=np.asarray(tel.feedmask))
@@ -756,7 +782,8 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
 # ---- ensembles of simulated timestreams on the device -------------------------------------------
 # Opt-in log of `simulate_visibilities` / `simulate_ensemble`: a dict set here collects wall seconds per kind of step
 # ("sky": map transforms, covariance roots and a_lm draws; "beam": reading and uploading beam blocks; "project"; "noise";
-# "synthesis"; "download"; "write"), waiting for the device at every boundary.  None: no waits added.
+# "synthesis"; "gains": drawing the feed gains and applying them; "download"; "write"), waiting for the device at every
+# boundary.  None: no waits added.
 sim_log = None
 
 
@@ -776,10 +803,16 @@ def _sim_ntime(tel, resolution):
 
 
 def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
-                       out=None, sources=()):
+                       out=None, sources=(), gains=None, gain_sink=None):
     """The passes of `simulate_visibilities`: yields (r0, device tensor (R, nf, npairs, ntime)) for the realisations
     first + r0 .. first + r0 + R - 1, R <= BLOCKVEC_MAX_R.  With `out` (nreal, nf, npairs, ntime) the groups are views of
-    it; without, ONE buffer is used for every group (the caller is done with a group when it asks for the next)."""
+    it; without, ONE buffer is used for every group (the caller is done with a group when it asks for the next).
+
+    With `gains` the sky of a group is synthesised into a scratch buffer of the group's size and reaches the result
+    through `Context.ts_gain_apply` (adding to the noise when there is any).  The gains g (1 or R, nfc, nfeed, ntime) are
+    made for chunks of nfc frequencies at a time (`skysim.gains_device`, which needs three buffers of that size) so that
+    they fit in `chunk_gb` together with the scratch buffer — one frequency at the least; `gain_sink(r0, f0, g)` is
+    called with every chunk."""
     from . import skysim
     from ._lib import BLOCKVEC_MAX_R
 
@@ -800,6 +833,16 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
     if nf == 0 or nreal <= 0:
         return
     log = sim_log
+    gains = skysim.as_gains(gains)
+    if gains is not None:
+        nfeed = int(tel.nfeed)
+        class_off, members = tel.redundant_pairs()
+        if not isinstance(gains, skysim.GainModel):
+            skysim.check_explicit_gains(gains, nreal, nf, nfeed, ntime)   # before any work
+        scratch_bytes = 16.0 * min(BLOCKVEC_MAX_R, nreal) * nf * npairs * ntime
+        per_freq = 3 * 16.0 * min(BLOCKVEC_MAX_R, nreal) * nfeed * ntime
+        nfc = int(min(nf, max(1, (chunk_gb * 2.0**30 - scratch_bytes) // per_freq)))
+    skybuf = None
 
     sigma = None
     if ndays > 0:
@@ -860,16 +903,36 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
                         batch, alm_m[batch[0] : batch[-1] + 1], freqs=freqs, products=beam)
                 del beam
             del alm_m
+            if gains is not None and skybuf is None:
+                skybuf = ctx.empty((min(BLOCKVEC_MAX_R, nreal), nf, npairs, ntime), np.complex128)
             with _StepTimer(log, "synthesis"):
                 cols = vis.view(mmax + 1, nf, 2, npairs, R)
                 for r in range(R):
-                    ctx.mmode_synthesis(cols[..., r], ntime, out=grp[r], accumulate=sigma is not None)
+                    if gains is None:
+                        ctx.mmode_synthesis(cols[..., r], ntime, out=grp[r], accumulate=sigma is not None)
+                    else:
+                        ctx.mmode_synthesis(cols[..., r], ntime, out=skybuf[r])
             del vis, cols
+        if gains is not None and (have_sky or gain_sink is not None):
+            with _StepTimer(log, "gains"):
+                for f0 in range(0, nf, nfc):
+                    f1 = min(nf, f0 + nfc)
+                    if isinstance(gains, skysim.GainModel):
+                        g = skysim.gains_device(gains, nfeed, freqs[f0:f1], ntime, R, first + r0)
+                    else:
+                        g = skysim.explicit_gains(gains, nreal, nf, r0, R, range(f0, f1), nfeed, ntime)
+                        g = g.contiguous() if hasattr(g, "data_ptr") else ctx.to_device(np.ascontiguousarray(g))
+                    if have_sky:
+                        ctx.ts_gain_apply(g, class_off, members, skybuf[:R, f0:f1], out=grp[:, f0:f1],
+                                          accumulate=sigma is not None)
+                    if gain_sink is not None:
+                        gain_sink(r0, f0, g)
+                    del g
         yield r0, grp
 
 
 def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None, sky_seed=0,
-                          first=0, freqs=None, chunk_gb=4.0, sources=()):
+                          first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None):
     """`nreal` simulated timestreams of the telescope of ProductManager `m` as ONE device tensor
     (nreal, len(freqs), npairs, ntime): what `simulate` writes per frequency, for many statistically independent data
     sets, without leaving the device between the draws and the result.
@@ -888,23 +951,33 @@ def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, s
     Noise: `simulate` adds complex noise of variance `noisepower` to each of the ntime Fourier bins before
     ifft * ntime; in the time domain that is white noise of variance ntime * noisepower, exactly, and that is what is
     drawn here, sigma[f, p] = sqrt(ntime * noisepower(p, f, ndays)).  It is the same DISTRIBUTION as `simulate`'s, not
-    the same numbers.  ndays = 0: no noise."""
+    the same numbers.  ndays = 0: no noise.
+
+    gains: per-feed gain errors — a `skysim.GainModel` (or the dict of its arguments), whose
+    realisation first + i belongs to data set i, or an explicit complex128 array / device tensor (len(freqs), nfeed,
+    ntime) for all or (nreal, len(freqs), nfeed, ntime).  Per-feed gains break the redundancy of a stacked baseline: the
+    sky part of unique pair c is multiplied by G_c = mean over the feed pairs (i, j) of the class of g_i conj(g_j)
+    (`Context.ts_gain_apply`).  The gains multiply the sky part only: receiver noise is added after them and its level
+    is unchanged.  They are counter based like the rest, so a frequency subset or a realisation range reproduces the rows
+    of the full call.  gains=None: none of this runs and the result is what it was."""
     ctx = get_context()
     tel = m.beamtransfer.telescope
     freqs = _sim_freqs(tel, freqs)
     out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.npairs), _sim_ntime(tel, resolution)), np.complex128)
     for _ in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                chunk_gb, out=out, sources=sources):
+                                chunk_gb, out=out, sources=sources, gains=gains):
         pass
     return out
 
 
 def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None,
-                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=()):
+                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None):
     """`simulate_visibilities` written out: realisation first + i as the Timestream directory
     `outdir/real_%04d` % (first + i), each with the per-frequency files, datasets and attributes of `simulate` and the
     saved object.  Every rank writes its own frequencies (one device-to-host copy per group of up to 8 realisations),
-    rank 0 saves the objects.  Returns the list of `Timestream`.
+    rank 0 saves the objects.  Returns the list of `Timestream`.  With `gains` (see `simulate_visibilities`: they multiply
+    the sky part only, the noise is added after at its usual level) every per-frequency file also holds the dataset
+    `gain` (nfeed, ntime), the feed gains that were applied to that realisation and frequency.
 
     End to end (does the estimator recover the injected spectrum through the real chain?):
 
@@ -923,10 +996,21 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
     nreal, first = int(nreal), int(first)
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     tss = [Timestream(os.path.join(outdir, "real_%04d" % (first + i)), m) for i in range(max(nreal, 0))]
+    gain_host = {}
+
+    def gain_sink(r0, f0, g):
+        gain_host[f0] = ctx.to_host(g)
+
     for r0, grp in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                      chunk_gb, sources=sources):
+                                      chunk_gb, sources=sources, gains=gains,
+                                      gain_sink=gain_sink if gains is not None else None):
         with _StepTimer(sim_log, "download"):
             host = ctx.to_host(grp)
+        gain_at = {}
+        for f0, gh in gain_host.items():
+            for k in range(gh.shape[1]):
+                gain_at[f0 + k] = gh[:, k]                      # (1 or R, nfeed, ntime)
+        gain_host.clear()
         with _StepTimer(sim_log, "write"):
             for r in range(host.shape[0]):
                 tstream = tss[r0 + r]
@@ -935,6 +1019,8 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
                     with storage.File(tstream._ffile(fi), "w") as f:
                         f.create_dataset("timestream", data=np.ascontiguousarray(host[r, lfi]))
                         f.create_dataset("phi", data=tphi)
+                        if lfi in gain_at:
+                            f.create_dataset("gain", data=np.ascontiguousarray(gain_at[lfi][r if gain_at[lfi].shape[0] > 1 else 0]))
                         f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
                         f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
                         f.create_dataset("feedmask", data=np.asarray(tel.feedmask))

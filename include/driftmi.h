@@ -561,6 +561,43 @@ int dm_mmode_twiddle(dm_ctx* ctx, int ntime, int mmax, void* W_dev);
 int dm_ts_noise(dm_ctx* ctx, int nreal, int nf, int npairs, int ntime, const double* sigma_dev, const int* fglobal_host,
                 uint64_t seed, int first, void* out_dev);
 
+/* ---- per-feed gain errors of simulated timestreams ---------------------------- */
+/* dm_ts_gain_coeff: Fourier coefficients of one Gaussian component (amplitude or phase) of the feed gains,
+ *   out[r, i, a, k] = sigma ck[k] sqrt(2) conj(z),  r < nreal, i < nf, a < nfeed, k < nk
+ *   fglobal_host  (nf) global frequency index of every row i (>= 0); not read when broadband != 0
+ *   ck_host       (nk) f64 weights c_k of the spectrum (sum of squares 1)
+ *   out_dev       contiguous (nreal, nf, nfeed, nk) c128; every element is written
+ * z is the complex normal of dm_ts_noise with key = seed and counter (a, fglobal[i], k, ((first + r) << 8) | stream);
+ * broadband != 0 puts 0xFFFFFFFF in the frequency word: one gain per feed for all frequencies (every row i the same).
+ * stream is 25 (amplitude) or 26 (phase), apart from 0, 1, 2, 16, 17 and 24.  Re sum_k out[.., k] e^{2 pi i k t / ntime}
+ * is the series x(t) = sigma sum_k c_k (A_k cos + B_k sin), A + i B = sqrt(2) z: a product of dm_zgemm_strided_batched
+ * with the table of dm_mmode_twiddle.  first + nreal > 2^24 is refused and nothing is launched.  One draw per lane,
+ * 64-bit element index.  Returns when the work is queued on the context's stream.  No counterpart in the reference. */
+int dm_ts_gain_coeff(dm_ctx* ctx, int nreal, int nf, int nfeed, int nk, const int* fglobal_host, int broadband,
+                     const double* ck_host, double sigma, uint64_t seed, int first, int stream, void* out_dev);
+
+/* dm_ts_gain_compose: g[e] = (1 + Re xamp[e]) exp(i Re xphase[e]) for e < n; three contiguous c128 device buffers. */
+int dm_ts_gain_compose(dm_ctx* ctx, int64_t n, const void* xamp_dev, const void* xphase_dev, void* g_dev);
+
+/* dm_ts_gain_tile: time samples per workgroup tile of dm_ts_gain_apply for nfeed feeds (host only): the largest power
+ * of two <= 16 whose tile nfeed x tile x 16 B fits in 64 KiB, 1 up to the 160 KiB of a CU, 0 when not even one fits. */
+int dm_ts_gain_tile(int nfeed);
+
+/* dm_ts_gain_apply: per-feed gains on stacked (unique-baseline) visibilities,
+ *   out[r, f, c, t] (+)= G sky[r, f, c, t],  G = (1 / n_c) sum_{(i, j) in class c} g[r, f, i, t] conj(g[r, f, j, t])
+ *   class_off_host (npairs + 1), members_host (class_off[npairs], 2): the feed pairs of every class
+ *   g_dev    contiguous (g_nreal, nf, nfeed, ntime) c128, g_nreal = 1 (one array for all realisations) or nreal
+ *   sky_dev, out_dev (nreal, nf, npairs, ntime) c128, t fastest, distinct buffers; rstride elements lie between the
+ *            realisations of both (0: contiguous, nf npairs ntime; larger for a frequency slice of a wider array)
+ * accumulate != 0 adds to out (the noise dm_ts_noise drew there: gains multiply the sky part only, the noise level is
+ * unchanged — the convention of this library).  The sum of a class runs in an order fixed by (n_c, nfeed) alone, so the
+ * same (g, table) gives the same bits in any batch.  Refused before any launch (dm_last_error): an empty class, a feed
+ * index outside [0, nfeed), nfeed whose single-sample tile does not fit in LDS.  Returns when the work is queued on the
+ * context's stream.  No counterpart in the reference, which simulates a perfectly calibrated telescope. */
+int dm_ts_gain_apply(dm_ctx* ctx, int nreal, int g_nreal, int nf, int nfeed, int npairs, int ntime,
+                     const int* class_off_host, const int* members_host, const void* g_dev, const void* sky_dev,
+                     void* out_dev, int64_t rstride, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif
