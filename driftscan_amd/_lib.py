@@ -164,6 +164,8 @@ SIGNATURES = {
     "dm_ts_gain_apply": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp,
                 c_vp, c_i64, c_int]),
+    "dm_toeplitz_solve": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "dm_toeplitz_max_rhs": (c_int, [c_int]),
 }
 
 _lib = None
@@ -686,6 +688,146 @@ def _ts_gain_apply(self, g, class_off, members, sky, out=None, accumulate=False)
 Context.ts_gain_coeff = _ts_gain_coeff
 Context.ts_gain_compose = _ts_gain_compose
 Context.ts_gain_apply = _ts_gain_apply
+
+
+def _toeplitz_max_rhs(self, n):
+    """The most right-hand sides one `dm_toeplitz_solve` call takes for order n (0: the order does not fit in LDS)."""
+    return int(self.lib.dm_toeplitz_max_rhs(int(n)))
+
+
+def _toeplitz_solve(self, col, b, ridge=0.0):
+    """`batch` Hermitian positive-definite Toeplitz systems on the device (dm_toeplitz_solve, the Levinson recursion of
+    DESIGN.md section 4.16; `timestream.toeplitz_levinson_host` restates it): col (batch, n) complex128 first columns
+    (numpy or device; Im c_0 is ignored), b (batch, nrhs, n) right-hand sides.  `ridge` adds ridge * c_0 to c_0 on a copy.
+    Returns (x, info): new device tensors (batch, nrhs, n) complex128 and (batch,) int32 — 0 solved, k < n: not positive
+    definite at step k, n: c_0 <= 0; such a system's solutions are zeros.  More right-hand sides than
+    `toeplitz_max_rhs(n)` go through several calls (the bits of a solution do not depend on its companions)."""
+    torch = self.torch
+    col = self.to_device(np.asarray(col, dtype=np.complex128)) if not hasattr(col, "data_ptr") else col
+    b = self.to_device(np.asarray(b, dtype=np.complex128)) if not hasattr(b, "data_ptr") else b
+    if col.dim() != 2 or b.dim() != 3 or not (col.is_complex() and col.element_size() == 16) or not (
+            b.is_complex() and b.element_size() == 16):
+        raise ValueError("toeplitz_solve: complex128 col (batch, n) and b (batch, nrhs, n) expected")
+    batch, n = (int(v) for v in col.shape)
+    nrhs = int(b.shape[1])
+    if tuple(b.shape) != (batch, nrhs, n) or n < 1 or nrhs < 1:
+        raise ValueError("toeplitz_solve: b %s does not fit col %s" % (tuple(b.shape), tuple(col.shape)))
+    ridge = float(ridge)
+    if not (ridge >= 0.0 and np.isfinite(ridge)):
+        raise ValueError("toeplitz_solve: ridge must be finite and not negative")
+    most = self.toeplitz_max_rhs(n)
+    if most < 1:
+        raise ValueError("toeplitz_solve: a system of order %d does not fit in the LDS of a CU" % n)
+    col = col.contiguous()
+    if ridge > 0.0:
+        col = col.clone()
+        col[:, 0] += ridge * col[:, 0].real
+    x = b.clone(memory_format=torch.contiguous_format)
+    info = self.empty((batch,), np.int32)
+    if nrhs <= most:
+        self.check(self.lib.dm_toeplitz_solve(self.h, n, nrhs, batch, self.ptr(col), self.ptr(x), self.ptr(info)),
+                   "dm_toeplitz_solve")
+        return x, info
+    for r0 in range(0, nrhs, most):   # info depends on col alone: every call writes the same values
+        part = x[:, r0 : r0 + most].contiguous()
+        self.check(self.lib.dm_toeplitz_solve(self.h, n, int(part.shape[1]), batch, self.ptr(col), self.ptr(part),
+                                              self.ptr(info)), "dm_toeplitz_solve")
+        x[:, r0 : r0 + most] = part
+    return x, info
+
+
+def _mmode_weights(self, weight, nf, npairs, ntime):
+    """The weights of `mmode_transform_weighted` as a device tensor (S, ntime) float64 with S = nf * npairs, nf or 1, and
+    the shape of the systems along (frequency, pair); a shape that does not broadcast, a negative or a non-finite weight
+    raise ValueError."""
+    torch = self.torch
+    if hasattr(weight, "data_ptr"):
+        w = weight
+        if w.dtype != torch.float64:
+            raise ValueError("mmode_transform_weighted: float64 weights expected")
+        bad = bool((~(torch.isfinite(w) & (w >= 0))).any()) if w.numel() else False
+    else:
+        w = np.asarray(weight, dtype=np.float64)
+        bad = bool(w.size) and not bool(np.all(np.isfinite(w) & (w >= 0)))
+    if tuple(w.shape) not in ((nf, npairs, ntime), (nf, ntime), (ntime,)):
+        raise ValueError("mmode_transform_weighted: weights %s are not (nf, npairs, ntime), (nf, ntime) or (ntime,) of X "
+                         "(%d, %d, %d)" % (tuple(w.shape), nf, npairs, ntime))
+    if bad:
+        raise ValueError("mmode_transform_weighted: weights must be finite and not negative")
+    if not hasattr(w, "data_ptr"):
+        w = self.to_device(w)
+    lead = {3: (nf, npairs), 2: (nf, 1), 1: (1, 1)}[w.dim()]                  # the systems along (frequency, pair)
+    return w.reshape(-1, ntime).contiguous(), lead
+
+
+def _mmode_transform_weighted(self, X, weight, mmax, ridge=0.0, out=None):
+    """Weighted least-squares m-modes of flagged timestreams on the device: the a_k, |k| <= mmax,
+    that minimise sum_t w_t |x_t - sum_k a_k e^{2 pi i k t / ntime}|^2 (+ ridge * mean(w) * |a|^2), in the layout of
+    `mmode_transform`, (mmax + 1, nf, 2, npairs): slot 1 is the conjugate of the -m mode, zero for m = 0.
+
+    X (nf, npairs, ntime) complex128 on the device; `weight` float64 >= 0, numpy or device, of shape (nf, npairs, ntime),
+    (nf, ntime) or (ntime,).  Returns (out, info) with info (nf, npairs) int32: 0 solved, -1 not solved (fewer than
+    2 mmax + 1 samples of weight > 0 and ridge = 0, or none at all: the modes are zeros), > 0 the code of `toeplitz_solve`.
+
+    The right-hand sides are `mmode_transform` of w x; the first columns c_d = mean_t w_t e^{-2 pi i d t / ntime},
+    d <= 2 mmax, one ZGEMM of the weights against the twiddle table; per (frequency, baseline) one Toeplitz system of
+    order 2 mmax + 1 (`toeplitz_solve`).  Without a pair axis the baselines of a frequency (of all frequencies for
+    (ntime,)) are right-hand sides of one system.  A row of constant weight w_0 has A = w_0 I exactly and gets that
+    column, so data without flags gives the bits of `mmode_transform`.  Host statement:
+    `timestream.mmodes_weighted_host`.  (Device weights are checked with a torch reduction and a read-back.)"""
+    torch = self.torch
+    if X.dim() != 3 or not (X.is_complex() and X.element_size() == 16):
+        raise ValueError("mmode_transform_weighted: X (nf, npairs, ntime) complex128 expected")
+    nf, npairs, ntime = (int(v) for v in X.shape)
+    mmax, ridge = int(mmax), float(ridge)
+    N = 2 * mmax + 1
+    if mmax < 0 or ntime < N:
+        raise ValueError("mmode_transform_weighted: %d time samples cannot hold m up to %d" % (ntime, mmax))
+    if not (ridge >= 0.0 and np.isfinite(ridge)):
+        raise ValueError("mmode_transform_weighted: ridge must be finite and not negative")
+    w, lead = _mmode_weights(self, weight, nf, npairs, ntime)
+    if out is None:
+        out = self.empty((mmax + 1, nf, 2, npairs), np.complex128)
+    if tuple(out.shape) != (mmax + 1, nf, 2, npairs) or not out.is_contiguous():
+        raise ValueError("mmode_transform_weighted: out must be a contiguous (mmax + 1, nf, 2, npairs) tensor")
+    S = int(w.shape[0])
+    if nf == 0 or npairs == 0:
+        return out, self.zeros((nf, npairs), np.int32)
+    if self.toeplitz_max_rhs(N) < 1:
+        raise ValueError("mmode_transform_weighted: systems of order %d do not fit in the LDS of a CU" % N)
+    bm = self.mmode_transform(X * w.view(lead + (ntime,)), mmax)                                   # (mmax + 1, nf, 2, npairs)
+    # c[s, d] = (1 / ntime) sum_t w[s, t] e^{-2 pi i d t / ntime}
+    W2 = self.mmode_twiddle(ntime, 2 * mmax)
+    col = self.empty((S, N), np.complex128)
+    self.zgemm(w.to(torch.complex128), W2, col, S, N, ntime, rsA=ntime, csA=1, rsB=N, csB=1, ldc=N)
+    wmin, wmax = w.amin(dim=1), w.amax(dim=1)
+    flat = (wmin == wmax) & (wmin > 0)
+    e0 = torch.zeros((S, N), dtype=torch.complex128, device=col.device)
+    e0[:, 0] = wmin
+    col = torch.where(flat[:, None], e0, col)
+    short = (w > 0).sum(dim=1) < (N if ridge == 0.0 else 1)     # (the ridge is relative to mean(w): 0 for an empty row)
+    e0[:, 0] = 1.0
+    col = torch.where(short[:, None], e0, col)
+    # right-hand sides in k = -mmax .. mmax order: (nf, npairs, N), the pair axis the right-hand sides of a system
+    B = self.empty((nf, npairs, N), np.complex128)
+    B[:, :, mmax:] = bm[:, :, 0].permute(1, 2, 0)
+    if mmax > 0:
+        B[:, :, :mmax] = bm[1:, :, 1].conj().permute(1, 2, 0).flip(-1)
+    B = B.view(S, (nf * npairs) // S, N)
+    B = torch.where(short[:, None, None], torch.zeros_like(B), B)
+    x, info = self.toeplitz_solve(col, B, ridge=ridge)
+    x = x.view(nf, npairs, N)
+    out[:, :, 0] = x[:, :, mmax:].permute(2, 0, 1)
+    out[0, :, 1].zero_()
+    if mmax > 0:
+        out[1:, :, 1] = x[:, :, :mmax].flip(-1).conj().permute(2, 0, 1)
+    info = torch.where(short, torch.full_like(info, -1), info)
+    return out, info.view(lead).expand(nf, npairs).contiguous()
+
+
+Context.toeplitz_max_rhs = _toeplitz_max_rhs
+Context.toeplitz_solve = _toeplitz_solve
+Context.mmode_transform_weighted = _mmode_transform_weighted
 
 
 def _svd_chain(self, beam_m, noisew, polsvcut, skip_svd_inv=False, max_bytes=None, lmin=None):

@@ -2,7 +2,8 @@
 
 The counterpart of ``drift.pipeline.pipeline.PipelineManager`` (drift/pipeline/pipeline.py:20-198), by behaviour: the same
 sections — ``config`` (the properties below), ``timestreams`` (entries with ``name``, ``directory``, optionally
-``output_directory`` and a ``simulate`` block of arguments for ``timestream.simulate`` plus its ``product_directory``;
+``output_directory``, ``mmode_ridge`` (this package: the ridge of the weighted m-modes of flagged data) and a ``simulate``
+block of arguments for ``timestream.simulate`` plus its ``product_directory``;
 the files of its ``maps`` and ``sources`` lists go through ``fixpath``)
 and optionally ``crosspower`` (entries with ``psname``, ``klname``, ``timestreams``, ``psfile``) — the same defaults,
 exceptions and methods.  Two deliberate differences:
@@ -84,6 +85,8 @@ class PipelineManager(config.Reader):
             if "output_directory" in tsconf:
                 ts.output_directory = fixpath(tsconf["output_directory"])
             ts.no_m_zero = self.no_m_zero
+            if "mmode_ridge" in tsconf:   # Tikhonov term of the weighted m-modes of flagged data
+                ts.mmode_ridge = float(tsconf["mmode_ridge"])
             self.timestreams[tsconf["name"]] = ts
             if "simulate" in tsconf:
                 self.simulations[tsconf["name"]] = tsconf["simulate"]

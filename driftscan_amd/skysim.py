@@ -212,6 +212,81 @@ class GainModel:
         return float(np.sum(c**2 * np.cos(2.0 * np.pi * np.arange(c.shape[0]) * lag / ntime)))
 
 
+# ---- flags of simulated timestreams ---------------------------------------------------------------
+STREAM_TS_FLAG = 27          # flag bursts: apart from 0, 1, 2, 16, 17 and 24-26
+
+
+class FlagModel:
+    """Flags of a simulated timestream, weights 0 (flagged) / 1 per (frequency, time sample), the same for every baseline.
+
+    Bursts: a run of ``burst`` samples, cyclic over the day, starts at sample s of global frequency f when
+    u(seed, f, s) < p with 1 - (1 - p)^burst = ``fraction``, the probability that a sample is flagged; u is the uniform
+    of Philox4x32-10 with key ``seed`` and counter (s, f, 0, 27).  ``windows``: (start, end) in sidereal hours (end <
+    start wraps midnight), flagged at all frequencies — the daytime cut.  Host only; the mask of a frequency depends on
+    (seed, global frequency) alone, so frequency subsets reproduce the rows of the full call."""
+
+    def __init__(self, fraction=0.0, burst=1, windows=(), seed=0):
+        self.fraction, self.burst, self.seed = float(fraction), int(burst), int(seed)
+        self.windows = tuple((float(a), float(b)) for a, b in windows)
+        if not 0.0 <= self.fraction < 1.0:
+            raise ValueError("FlagModel: fraction must lie in [0, 1)")
+        if self.burst < 1:
+            raise ValueError("FlagModel: burst must be at least 1")
+        if any(not (0.0 <= a <= 24.0 and 0.0 <= b <= 24.0) for a, b in self.windows):
+            raise ValueError("FlagModel: windows are (start, end) in hours between 0 and 24")
+
+    @classmethod
+    def from_config(cls, conf):
+        conf = dict(conf)
+        unknown = set(conf) - {"fraction", "burst", "windows", "seed"}
+        if unknown:
+            raise ValueError("FlagModel: unknown keys %s" % sorted(unknown))
+        return cls(**conf)
+
+    def __repr__(self):
+        return "FlagModel(fraction=%r, burst=%r, windows=%r, seed=%r)" % (self.fraction, self.burst, self.windows, self.seed)
+
+    def start_probability(self):
+        """p with 1 - (1 - p)^burst = fraction."""
+        return 1.0 - (1.0 - self.fraction) ** (1.0 / self.burst)
+
+    def mask(self, ntime, fglobal):
+        """(nf, ntime) float64 of 0 (flagged) / 1 for the global frequency indices ``fglobal``."""
+        ntime = int(ntime)
+        fg = np.asarray(fglobal, dtype=np.uint64).reshape(-1)
+        flagged = np.zeros((fg.shape[0], ntime), dtype=bool)
+        if self.fraction > 0.0 and ntime > 0 and fg.shape[0] > 0:
+            f, s = np.meshgrid(fg, np.arange(ntime, dtype=np.uint64), indexing="ij")
+            seed = self.seed & 0xFFFFFFFFFFFFFFFF
+            w = _philox4x32_10([s, f, np.zeros_like(s), np.full_like(s, STREAM_TS_FLAG)], (seed & 0xFFFFFFFF, seed >> 32))
+            start = _u53(w[0], w[1]) < self.start_probability()
+            for d in range(min(self.burst, ntime)):
+                flagged |= np.roll(start, d, axis=1)
+        t_hours = 24.0 * np.arange(ntime) / max(ntime, 1)
+        for a, b in self.windows:
+            cut = (t_hours >= a) & (t_hours < b) if a <= b else (t_hours >= a) | (t_hours < b)
+            flagged |= cut[None, :]
+        return np.where(flagged, 0.0, 1.0)
+
+
+def as_weights(weights, nf, npairs, ntime, fglobal):
+    """The `weights` argument of the simulators as a float64 array broadcastable to (nf, npairs, ntime) — (nf, npairs,
+    ntime), (nf, 1, ntime) from a FlagModel, a dict of its arguments or an (nf, ntime) array, or (ntime,) — checked."""
+    if isinstance(weights, dict):
+        weights = FlagModel.from_config(weights)
+    if isinstance(weights, FlagModel):
+        return weights.mask(ntime, fglobal)[:, None, :]
+    if hasattr(weights, "data_ptr"):
+        weights = weights.cpu().numpy()
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape not in ((nf, npairs, ntime), (nf, ntime), (ntime,)):
+        raise ValueError("weights %s are not (nfreq, npairs, ntime), (nfreq, ntime) or (ntime,) = (%d, %d, %d)"
+                         % (w.shape, nf, npairs, ntime))
+    if w.size and not np.all(np.isfinite(w) & (w >= 0)):
+        raise ValueError("weights must be finite and not negative")
+    return w[:, None, :] if w.ndim == 2 else w
+
+
 def as_gains(gains):
     """None, a GainModel, a dict (-> GainModel.from_config) or an explicit array / device tensor, checked."""
     if gains is None or isinstance(gains, GainModel):

@@ -24,6 +24,7 @@ class Timestream(object):
     output_directory = None
     beamtransfer_dir = None
     no_m_zero = True
+    mmode_ridge = 0.0   # Tikhonov term of the weighted m-mode estimate, relative to the mean weight
 
     def __init__(self, tsdir, prodmanager):
         self.directory = os.path.abspath(tsdir)
@@ -56,6 +57,38 @@ class Timestream(object):
         with storage.File(self._ffile(fi), "r") as f:
             return f["timestream"][:]
 
+    def weight_f(self, fi):
+        """[npairs, ntime] float64 weights of one frequency (flags: 0), or None when the file holds no `weight`."""
+        with storage.File(self._ffile(fi), "r") as f:
+            return np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f else None
+
+    def _weights_of(self, fs, ntime):
+        """(len(fs), npairs, ntime) weights of the frequencies `fs` (ones for a file without the dataset) when the data
+        is flagged — the file of frequency 0 holds `weight`, a choice every rank makes alike — else None."""
+        if self.weight_f(0) is None:
+            return None
+        ones = np.ones((self.telescope.npairs, ntime), dtype=np.float64)
+        return np.stack([ones if w is None else w for w in (self.weight_f(fi) for fi in fs)]) if len(fs) else \
+            np.zeros((0, self.telescope.npairs, ntime), dtype=np.float64)
+
+    def _write_weight_summary(self, local_f, kept, info):
+        """Kept-sample counts and solver info (nfreq, npairs) of a weighted m-mode estimate, gathered from the ranks'
+        frequencies and written once to mmodes/weights.hdf5."""
+        tel = self.telescope
+        parts = parallel.gather_objects((list(local_f), kept, info))
+        if parallel.rank0():
+            nkept = np.zeros((tel.nfreq, tel.npairs), dtype=np.int64)
+            infos = np.zeros((tel.nfreq, tel.npairs), dtype=np.int32)
+            for fs, k, i in parts:
+                if len(fs):
+                    nkept[fs], infos[fs] = k, i
+            os.makedirs(self.output_directory + "/mmodes", exist_ok=True)
+            with storage.File(self.output_directory + "/mmodes/weights.hdf5", "w") as f:
+                f.create_dataset("nkept", data=nkept)
+                f.create_dataset("info", data=infos)
+                f.attrs["ridge"] = float(self.mmode_ridge)
+                f.attrs["ntime"] = int(self.ntime)
+
     # ---- m-modes (timestream.py:103-185) ------------------------------------------------------------------
     def _mdir(self, mi):
         return (self.output_directory + "/mmodes/" + util.natpattern(self.telescope.mmax)) % abs(mi)
@@ -69,7 +102,9 @@ class Timestream(object):
             return f["mmode"][:]
 
     def generate_mmodes(self):
-        """FFT the timestreams along time and regroup by m: +m in slot 0, the conjugate of -m in slot 1."""
+        """FFT the timestreams along time and regroup by m: +m in slot 0, the conjugate of -m in slot 1.  When the files
+        hold a dataset `weight` (flags) the modes are the weighted least-squares estimate instead (`mmodes_weighted_host`
+        with `mmode_ridge`; counts and solver info go to mmodes/weights.hdf5)."""
         marker = self.output_directory + "/mmodes/COMPLETED_M"
         if os.path.exists(marker):
             return
@@ -84,11 +119,18 @@ class Timestream(object):
         me = parallel.rank() if parallel._dist() else 0
         local_f = f_of[me]
         pairs = np.zeros((len(local_f), 2, tel.npairs, mmax + 1), dtype=np.complex128)
-        for k, fi in enumerate(local_f):
-            row = np.fft.fft(self.timestream_f(fi), axis=-1) / ntime        # (npairs, ntime)
-            pairs[k, 0, :, 0] = row[:, 0]
-            pairs[k, 0, :, 1:] = row[:, 1 : mmax + 1]
-            pairs[k, 1, :, 1:] = row[:, : -mmax - 1 : -1].conj()
+        weights = self._weights_of(local_f, ntime)
+        if weights is not None:
+            x = np.stack([self.timestream_f(fi) for fi in local_f]) if local_f else np.zeros((0, tel.npairs, ntime), complex)
+            modes, info = mmodes_weighted_host(x, weights, mmax, ridge=self.mmode_ridge)
+            pairs[:] = modes.transpose(1, 2, 3, 0)
+            self._write_weight_summary(local_f, np.count_nonzero(weights > 0, axis=-1), info)
+        else:
+            for k, fi in enumerate(local_f):
+                row = np.fft.fft(self.timestream_f(fi), axis=-1) / ntime        # (npairs, ntime)
+                pairs[k, 0, :, 0] = row[:, 0]
+                pairs[k, 0, :, 1:] = row[:, 1 : mmax + 1]
+                pairs[k, 1, :, 1:] = row[:, : -mmax - 1 : -1].conj()
         got = parallel.exchange([np.ascontiguousarray(pairs[..., m_of[r]]) for r in range(nranks)])
         mine = m_of[me]
         if mine:
@@ -132,7 +174,8 @@ class Timestream(object):
     def _generate_mmodes_device(self, chunk_gb):
         """`generate_mmodes` with the time -> m transform on the device (`Context.mmode_transform`: a pruned DFT as two
         strided-batched ZGEMMs against a twiddle table, written in the layout of the mode files); the regrouping across
-        ranks and the files are the per-m route's."""
+        ranks and the files are the per-m route's.  Files with a dataset `weight` go through
+        `Context.mmode_transform_weighted` and leave mmodes/weights.hdf5."""
         marker = self.output_directory + "/mmodes/COMPLETED_M"
         if os.path.exists(marker):
             return {}
@@ -148,17 +191,30 @@ class Timestream(object):
         pairs = np.zeros((mmax + 1, len(local_f), 2, npairs), dtype=np.complex128)
         per_f = 16 * npairs * (ntime + 2 * (mmax + 1))
         step = max(1, int(chunk_gb * (1 << 30) // max(per_f, 1)))
+        weighted = self.weight_f(0) is not None
+        kept, infos = [], []
+        if weighted:   # the weights, their product with the data and the right-hand sides share the chunk
+            step = max(1, int(chunk_gb * (1 << 30) // max(per_f + 16 * npairs * (2 * ntime + 4 * mmax + 2), 1)))
         for c0 in range(0, len(local_f), step):
             fs = local_f[c0 : c0 + step]
             with self._timed("read"):
                 host = np.stack([np.asarray(self.timestream_f(fi), dtype=np.complex128) for fi in fs])
+                wts = self._weights_of(fs, ntime) if weighted else None
             with self._timed("upload"):
                 X = ctx.to_device(host)
             with self._timed("device"):
-                out = ctx.mmode_transform(X, mmax)
+                if weighted:
+                    out, info = ctx.mmode_transform_weighted(X, wts, mmax, ridge=self.mmode_ridge)
+                    kept.append(np.count_nonzero(wts > 0, axis=-1))
+                    infos.append(info.cpu().numpy())
+                else:
+                    out = ctx.mmode_transform(X, mmax)
             with self._timed("download"):
                 pairs[:, c0 : c0 + len(fs)] = ctx.to_host(out)
             del X, out
+        if weighted:
+            self._write_weight_summary(local_f, np.concatenate(kept) if kept else np.zeros((0, npairs), np.int64),
+                                       np.concatenate(infos) if infos else np.zeros((0, npairs), np.int32))
         got = parallel.exchange([np.ascontiguousarray(pairs[m_of[r]]) for r in range(nranks)])
         mine = m_of[me]
         if mine:
@@ -547,6 +603,86 @@ class _StepTimer(object):
         return False
 
 
+# ---- m-modes of flagged timestreams: the host statement -------------------------------------
+def mmodes_weighted_host(x, w, mmax, ridge=0.0):
+    """Weighted least-squares m-modes in numpy, the oracle of `Context.mmode_transform_weighted`: x (nf, npairs, ntime)
+    complex, w >= 0 broadcastable to it from (nf, npairs, ntime), (nf, ntime) or (ntime,).  Per (frequency, pair) the normal
+    equations A a = b are built from the explicit Fourier matrix F[t, k] = e^{2 pi i k t / ntime}, k = -mmax .. mmax,
+    A = F^H diag(w) F / ntime + ridge mean(w) I, b = F^H (w x) / ntime, and solved with a dense solver (LAPACK's LU: not
+    the device's algorithm).  Returns (modes (mmax + 1, nf, 2, npairs) in the layout of the mode files, info (nf, npairs)
+    int32: 0 solved, -1 fewer than 2 mmax + 1 samples of weight > 0 with ridge = 0, or none at all — not solved, zeros)."""
+    x = np.asarray(x, dtype=np.complex128)
+    if x.ndim != 3:
+        raise ValueError("mmodes_weighted_host: x (nf, npairs, ntime) expected")
+    nf, npairs, ntime = x.shape
+    mmax, ridge = int(mmax), float(ridge)
+    N = 2 * mmax + 1
+    w = np.asarray(w, dtype=np.float64)
+    if w.shape not in ((nf, npairs, ntime), (nf, ntime), (ntime,)):
+        raise ValueError("mmodes_weighted_host: weights %s do not fit x %s" % (w.shape, x.shape))
+    if w.size and not np.all(np.isfinite(w) & (w >= 0)):
+        raise ValueError("mmodes_weighted_host: weights must be finite and not negative")
+    if mmax < 0 or ntime < N or not (ridge >= 0.0 and np.isfinite(ridge)):
+        raise ValueError("mmodes_weighted_host: %d time samples cannot hold m up to %d, or a bad ridge" % (ntime, mmax))
+    w = np.broadcast_to(w[:, None, :] if w.ndim == 2 else w, x.shape)
+    k = np.arange(-mmax, mmax + 1)
+    F = np.exp(2j * np.pi * ((np.arange(ntime)[:, None] * k[None, :]) % ntime) / ntime)       # (ntime, N)
+    modes = np.zeros((mmax + 1, nf, 2, npairs), dtype=np.complex128)
+    info = np.zeros((nf, npairs), dtype=np.int32)
+    for fi in range(nf):
+        for p in range(npairs):
+            wr = w[fi, p]
+            if np.count_nonzero(wr > 0) < (N if ridge == 0.0 else 1):     # (the ridge is relative to mean(w): 0 of 0)
+                info[fi, p] = -1
+                continue
+            A = (F.conj().T * wr[None, :]) @ F / ntime + ridge * wr.mean() * np.eye(N)
+            a = np.linalg.solve(A, F.conj().T @ (wr * x[fi, p]) / ntime)
+            modes[:, fi, 0, p] = a[mmax:]
+            modes[1:, fi, 1, p] = a[:mmax][::-1].conj()
+    return modes, info
+
+
+def toeplitz_levinson_host(col, b):
+    """The recursion of `dm_toeplitz_solve` restated in numpy (not its summation order): col (n,) or (batch, n) first
+    columns of Hermitian Toeplitz systems, b (n,), (nrhs, n) or (batch, nrhs, n) right-hand sides.  Returns (x of b's
+    shape, info int32 per system): 0 solved, k the step at which beta <= 0 or not finite, n for c_0 <= 0; the solutions of a
+    failed system are zeros."""
+    col = np.asarray(col, dtype=np.complex128)
+    b = np.asarray(b, dtype=np.complex128)
+    single = col.ndim == 1
+    cols = col[None] if single else col
+    batch, n = cols.shape
+    bs = b.reshape(batch, -1, n)
+    xs = np.zeros_like(bs)
+    info = np.zeros(batch, dtype=np.int32)
+    for s in range(batch):
+        c0 = cols[s, 0].real
+        if not (c0 > 0 and np.isfinite(c0)):
+            info[s] = n
+            continue
+        r = cols[s] / c0
+        r[0] = 1.0
+        bp = bs[s] / c0
+        f = np.zeros(n, dtype=np.complex128)
+        f[0] = 1.0
+        x = np.zeros_like(bp)
+        x[:, 0] = bp[:, 0]
+        beta = 1.0
+        for k in range(1, n):
+            rev = r[k:0:-1]                                  # r_{k-i}, i = 0 .. k - 1
+            gamma = -np.dot(rev, f[:k]) / beta
+            f[: k + 1] = f[: k + 1] + gamma * f[k::-1].conj()        # (f_k is 0 before the step)
+            beta *= 1.0 - abs(gamma) ** 2
+            if not (beta > 0 and np.isfinite(beta)):
+                info[s] = k
+                x[:] = 0
+                break
+            coef = (bp[:, k] - x[:, :k] @ rev) / beta
+            x[:, : k + 1] += coef[:, None] * f[k::-1].conj()[None, :]   # conj(f_{k-i}), i = 0 .. k
+        xs[s] = x
+    return xs.reshape(b.shape), (info[0] if single else info)
+
+
 def m_batches(ms, per_m_bytes, chunk_gb):
     """`ms` cut into runs whose summed `per_m_bytes(mi)` stays within chunk_gb (at least one m per batch)."""
     budget = chunk_gb * (1 << 30)
@@ -657,7 +793,7 @@ def _sources_alm(sources, tel, freqs, to_host):
 
 
 def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=(), klname=None, sky_seed=0,
-             sky_realisation=0, sources=(), gains=None, **kwargs):
+             sky_realisation=0, sources=(), gains=None, weights=None, **kwargs):
     """Simulated timestream of the telescope of ProductManager `m` (timestream.py:645-829).
 
     maps: list of files holding a dataset `map` [freq, pol, pixel] whose sum is the sky; ndays = 0: no noise;
@@ -671,7 +807,13 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
     telescope's frequencies (every rank takes the rows of its own).  A model is evaluated for realisation `sky_realisation` (`skysim.gains_host`).  The time stream of the
     sky is multiplied by the stacked baseline gain G (`skysim.baseline_gains_host` on `redundant_pairs()`), all in numpy;
     the noise is transformed by itself and added after: gains multiply the sky part only and the noise level is
-    unchanged.  With gains=None nothing of this runs.  Returns the Timestream."""
+    unchanged.  With gains=None nothing of this runs.
+
+    weights: flags — a `skysim.FlagModel`, a dict of its arguments (the YAML `weights:` mapping)
+    or a float64 array >= 0 of shape (nfreq, npairs, ntime), (nfreq, ntime) or (ntime,) over the telescope's frequencies.
+    Samples of weight 0 are set to exactly 0 after sky, gains and noise, and every frequency file gets the dataset
+    `weight` (npairs, ntime), from which `generate_mmodes` / `generate_modes_batched` take the weighted estimate of the
+    m-modes.  With weights=None nothing of this runs.  Returns the Timestream."""
     bt = m.beamtransfer
     tel = bt.telescope
     lmax, mmax, nfreq, npol = tel.lmax, tel.mmax, tel.nfreq, tel.num_pol_sky
@@ -757,6 +899,13 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
             vis_stream = vis_stream * skysim.baseline_gains_host(gain_f, *tel.redundant_pairs()).transpose(1, 0, 2)
         if noise_vis is not None:
             vis_stream = vis_stream + np.fft.ifft(noise_vis, axis=-1) * ntime
+    weight_f = None
+    if weights is not None:
+        from . import skysim
+
+        w = skysim.as_weights(weights, nfreq, tel.npairs, ntime, range(nfreq))
+        weight_f = np.broadcast_to(w[local_freq] if w.ndim == 3 else w, (lfreq, tel.npairs, ntime))
+        vis_stream = np.where(weight_f.transpose(1, 0, 2) == 0, 0.0, vis_stream)
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     tstream = Timestream(outdir, m)
     for lfi, fi in enumerate(local_freq):
@@ -766,6 +915,8 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
             f.create_dataset("phi", data=tphi)
             if gain_f is not None:
                 f.create_dataset("gain", data=np.ascontiguousarray(gain_f[lfi]))
+            if weight_f is not None:
+                f.create_dataset("weight", data=np.ascontiguousarray(weight_f[lfi]))
             f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
             f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
             f.create_dataset("feedmask", data=np.asarray(tel.feedmask))
@@ -802,8 +953,18 @@ def _sim_ntime(tel, resolution):
     return 2 * tel.mmax + 1 if resolution == 0 else int(np.round(24 * 3600.0 / resolution))
 
 
+def _sim_weights(tel, weights, freqs, ntime):
+    """`weights` of `simulate_visibilities` / `simulate_ensemble` as a host array broadcastable to (nf, npairs, ntime) over
+    the rows `freqs`: a FlagModel is evaluated for their global frequency indices, an array has one row per entry."""
+    if weights is None:
+        return None
+    from . import skysim
+
+    return skysim.as_weights(weights, len(freqs), int(tel.npairs), ntime, freqs)
+
+
 def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
-                       out=None, sources=(), gains=None, gain_sink=None):
+                       out=None, sources=(), gains=None, gain_sink=None, weights=None):
     """The passes of `simulate_visibilities`: yields (r0, device tensor (R, nf, npairs, ntime)) for the realisations
     first + r0 .. first + r0 + R - 1, R <= BLOCKVEC_MAX_R.  With `out` (nreal, nf, npairs, ntime) the groups are views of
     it; without, ONE buffer is used for every group (the caller is done with a group when it asks for the next).
@@ -812,7 +973,8 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
     through `Context.ts_gain_apply` (adding to the noise when there is any).  The gains g (1 or R, nfc, nfeed, ntime) are
     made for chunks of nfc frequencies at a time (`skysim.gains_device`, which needs three buffers of that size) so that
     they fit in `chunk_gb` together with the scratch buffer — one frequency at the least; `gain_sink(r0, f0, g)` is
-    called with every chunk."""
+    called with every chunk.  `weights`: a host array broadcastable to (nf, npairs, ntime) (`_sim_weights`); the samples
+    of weight 0 of every group are set to exactly 0, last of all."""
     from . import skysim
     from ._lib import BLOCKVEC_MAX_R
 
@@ -843,6 +1005,7 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
         per_freq = 3 * 16.0 * min(BLOCKVEC_MAX_R, nreal) * nfeed * ntime
         nfc = int(min(nf, max(1, (chunk_gb * 2.0**30 - scratch_bytes) // per_freq)))
     skybuf = None
+    flagged = None if weights is None else ctx.to_device(np.ascontiguousarray(weights == 0))
 
     sigma = None
     if ndays > 0:
@@ -928,11 +1091,13 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
                     if gain_sink is not None:
                         gain_sink(r0, f0, g)
                     del g
+        if flagged is not None:
+            grp.masked_fill_(flagged, 0.0)
         yield r0, grp
 
 
 def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None, sky_seed=0,
-                          first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None):
+                          first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None):
     """`nreal` simulated timestreams of the telescope of ProductManager `m` as ONE device tensor
     (nreal, len(freqs), npairs, ntime): what `simulate` writes per frequency, for many statistically independent data
     sets, without leaving the device between the draws and the result.
@@ -959,25 +1124,32 @@ def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, s
     sky part of unique pair c is multiplied by G_c = mean over the feed pairs (i, j) of the class of g_i conj(g_j)
     (`Context.ts_gain_apply`).  The gains multiply the sky part only: receiver noise is added after them and its level
     is unchanged.  They are counter based like the rest, so a frequency subset or a realisation range reproduces the rows
-    of the full call.  gains=None: none of this runs and the result is what it was."""
+    of the full call.  gains=None: none of this runs and the result is what it was.
+
+    weights: flags — a `skysim.FlagModel` (or the dict of its arguments) or a float64 array >= 0
+    of shape (len(freqs), npairs, ntime), (len(freqs), ntime) or (ntime,), the same for every realisation: samples of
+    weight 0 are set to exactly 0 after sky, gains and noise.  weights=None: none of this runs."""
     ctx = get_context()
     tel = m.beamtransfer.telescope
     freqs = _sim_freqs(tel, freqs)
+    weights = _sim_weights(tel, weights, freqs, _sim_ntime(tel, resolution))
     out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.npairs), _sim_ntime(tel, resolution)), np.complex128)
     for _ in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                chunk_gb, out=out, sources=sources, gains=gains):
+                                chunk_gb, out=out, sources=sources, gains=gains, weights=weights):
         pass
     return out
 
 
 def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None,
-                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None):
+                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None):
     """`simulate_visibilities` written out: realisation first + i as the Timestream directory
     `outdir/real_%04d` % (first + i), each with the per-frequency files, datasets and attributes of `simulate` and the
     saved object.  Every rank writes its own frequencies (one device-to-host copy per group of up to 8 realisations),
     rank 0 saves the objects.  Returns the list of `Timestream`.  With `gains` (see `simulate_visibilities`: they multiply
     the sky part only, the noise is added after at its usual level) every per-frequency file also holds the dataset
-    `gain` (nfeed, ntime), the feed gains that were applied to that realisation and frequency.
+    `gain` (nfeed, ntime), the feed gains that were applied to that realisation and frequency.  With `weights` (see
+    `simulate_visibilities`) every per-frequency file holds the dataset `weight` (npairs, ntime) and exact zeros where it
+    is 0; `generate_modes_batched` then estimates the m-modes from the samples that are there.
 
     End to end (does the estimator recover the injected spectrum through the real chain?):
 
@@ -994,6 +1166,8 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
     freqs = _sim_freqs(tel, freqs)
     ntime = _sim_ntime(tel, resolution)
     nreal, first = int(nreal), int(first)
+    weights = _sim_weights(tel, weights, freqs, ntime)
+    weight_f = None if weights is None else np.broadcast_to(weights, (len(freqs), int(tel.npairs), ntime))
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     tss = [Timestream(os.path.join(outdir, "real_%04d" % (first + i)), m) for i in range(max(nreal, 0))]
     gain_host = {}
@@ -1003,7 +1177,7 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
 
     for r0, grp in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
                                       chunk_gb, sources=sources, gains=gains,
-                                      gain_sink=gain_sink if gains is not None else None):
+                                      gain_sink=gain_sink if gains is not None else None, weights=weights):
         with _StepTimer(sim_log, "download"):
             host = ctx.to_host(grp)
         gain_at = {}
@@ -1021,6 +1195,8 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
                         f.create_dataset("phi", data=tphi)
                         if lfi in gain_at:
                             f.create_dataset("gain", data=np.ascontiguousarray(gain_at[lfi][r if gain_at[lfi].shape[0] > 1 else 0]))
+                        if weight_f is not None:
+                            f.create_dataset("weight", data=np.ascontiguousarray(weight_f[lfi]))
                         f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
                         f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
                         f.create_dataset("feedmask", data=np.asarray(tel.feedmask))

@@ -598,6 +598,27 @@ int dm_ts_gain_apply(dm_ctx* ctx, int nreal, int g_nreal, int nf, int nfeed, int
                      const int* class_off_host, const int* members_host, const void* g_dev, const void* sky_dev,
                      void* out_dev, int64_t rstride, int accumulate);
 
+/* ---- m-modes of flagged timestreams: batched Toeplitz systems --------------------- */
+/* dm_toeplitz_solve: `batch` independent Hermitian positive-definite Toeplitz systems T_s x = b of order n, each given
+ * by its first column, solved by the normalised Levinson recursion (2 n^2 complex multiply-adds per right-hand side,
+ * n values of storage per system instead of n^2):
+ *   col_dev   (batch, n) c128: c_0 .. c_{n-1}, T[k, k'] = c_{k-k'} for k >= k' and conj(c_{k'-k}) otherwise; Im c_0 ignored
+ *   b_dev     (batch, nrhs, n) c128: the right-hand sides on entry, the solutions on return
+ *   info_dev  (batch) int32 on the device: 0 solved; k in 1 .. n - 1: the system is not positive definite, found at step k
+ *             of the recursion (beta <= 0 or not finite); n: c_0 <= 0 or not finite.  A system with info != 0 has every
+ *             solution written as zeros; no other system is affected.
+ * One system per workgroup (one wave for n <= 384, 256 threads beyond), all of it in LDS: (2 + nrhs) n 16 bytes plus
+ * 80 (1 + nrhs) bytes of reduction scratch, at most the 160 KiB of a CU — dm_toeplitz_max_rhs(n) is the largest nrhs
+ * that fits.  The order of every sum is a function of n alone: a system has the same bits alone, in any batch and at any
+ * position.  batch may exceed 65535 (64-bit element offsets); batch = 0 is a no-op.  Refused before any launch
+ * (dm_last_error): n < 1, nrhs < 1, nrhs > dm_toeplitz_max_rhs(n), batch < 0, a null pointer with batch > 0.  Returns
+ * when the work is queued on the context's stream.  No counterpart in the reference, which transforms complete days. */
+int dm_toeplitz_solve(dm_ctx* ctx, int n, int nrhs, int batch, const void* col_dev, void* b_dev, int* info_dev);
+
+/* dm_toeplitz_max_rhs: the largest nrhs of dm_toeplitz_solve whose LDS need fits one CU for order n (host only), 0 if
+ * not even one right-hand side fits (n > 3410) or n < 1.  No counterpart in the reference. */
+int dm_toeplitz_max_rhs(int n);
+
 #ifdef __cplusplus
 }
 #endif
