@@ -27,6 +27,26 @@ class ZgemmProblem(ctypes.Structure):
                 ("conjA", c_int), ("conjB", c_int), ("alpha", c_dbl), ("beta", c_dbl)]
 
 
+class ZgemmProblemEx(ctypes.Structure):
+    """dm_zgemm_problem_ex of include/driftmi.h."""
+    _fields_ = [("A", c_vp), ("B", c_vp), ("C", c_vp), ("kscale", c_vp), ("bgather", c_vp),
+                ("M", c_int), ("N", c_int), ("K", c_int),
+                ("rsA", c_int), ("csA", c_int), ("rsB", c_int), ("csB", c_int), ("ldc", c_int), ("csc", c_int),
+                ("flags", c_int), ("alpha", c_dbl), ("alpha_im", c_dbl), ("beta", c_dbl), ("launch", c_int)]
+
+
+class ZgemmLaunchInfo(ctypes.Structure):
+    """dm_zgemm_launch_info of include/driftmi.h."""
+    _fields_ = [("launch", c_int), ("use4", c_int), ("deep", c_int), ("wide_r", c_int), ("tiles", c_int * 4),
+                ("flat", c_int * 4), ("cells", c_int * 8 * 4)]   # [class][4 flat + 2 ragged + rmw]
+
+
+# DM_ZGEMM_* of include/driftmi.h
+ZGEMM_CONJ_A, ZGEMM_CONJ_B, ZGEMM_B_REAL, ZGEMM_LOWER = 1, 2, 4, 8
+ZGEMM_ALL_REAL, ZGEMM_UPPER, ZGEMM_B_GATHER, ZGEMM_UPPER128 = 16, 32, 64, 128
+ZGEMM_CLASSES = ("complex", "real_b", "all_real", "gathered")   # class index of dm_zgemm_launch_info
+
+
 class JacobiProblemDesc(ctypes.Structure):
     """dm_jacobi_problem_desc of include/driftmi.h."""
     _fields_ = [("Z", c_vp), ("ld", c_int), ("row0", c_int), ("nrows", c_int), ("ncols", c_int), ("gc0", c_int),
@@ -57,6 +77,9 @@ SIGNATURES = {
          c_dbl, c_vp, c_int, c_i64, c_vp, c_i64, c_int],
     ),
     "dm_zgemm_grouped": (c_int, [c_vp, c_int, ctypes.POINTER(ZgemmProblem)]),
+    "dm_zgemm_grouped_ex": (c_int, [c_vp, c_int, ctypes.POINTER(ZgemmProblemEx)]),
+    "dm_zgemm_plan_info": (c_int, [c_int, ctypes.POINTER(ZgemmProblemEx), c_int, ctypes.POINTER(ZgemmLaunchInfo),
+                                   ctypes.POINTER(c_int)]),
     "dm_zpotrf_batched": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, ctypes.POINTER(c_int)]),
     "dm_ztrsm_left_lower_batched": (
         c_int, [c_vp, c_int, c_int, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int]),
@@ -194,8 +217,87 @@ def load():
     return lib
 
 
+# ---- the grouped product with its whole descriptor (dm_zgemm_grouped_ex / dm_zgemm_plan_info) --------------------------
+# A problem is a dict: M, N, K, rsA, csA, rsB, csB, ldc and optionally csc (1), flags (0), alpha (1), alpha_im (0),
+# beta (0), launch (0), a_off, b_off, c_off, ks_off (element offsets of the views in their tensors, 0) and bgather
+# (a host integer array (N, 2)); `Context.zgemm_grouped_ex` also wants the tensors A, B, C and, where used, kscale.
+def _zgemm_ex_has_kscale(p):
+    return p.get("kscale") is not None or bool(p.get("has_kscale", False))
+
+
+def zgemm_ex_check_views(p, nA, nB, nC, nks=0):
+    """Host arithmetic only: raise ValueError unless every element that the problem's kernel may touch lies inside a
+    buffer of nA / nB / nC / nks elements (counted in the element type of that operand)."""
+    M, N, K = int(p["M"]), int(p["N"]), int(p["K"])
+    flags = int(p.get("flags", 0))
+    strides = [int(p[k]) for k in ("rsA", "csA", "rsB", "csB", "ldc")] + [int(p.get("csc", 1))]
+    offs = [int(p.get(k, 0)) for k in ("a_off", "b_off", "c_off", "ks_off")]
+    if min(M, N, K) < 0 or min(strides) < 0 or min(offs) < 0:
+        raise ValueError("zgemm_grouped_ex: negative size, stride or offset")
+    if M == 0 or N == 0:
+        return
+    a_off, b_off, c_off, ks_off = offs
+    rsA, csA, rsB, csB, ldc, csc = strides
+    if c_off + (M - 1) * ldc + (N - 1) * csc >= nC:
+        raise ValueError("zgemm_grouped_ex: the view of C reaches outside its tensor")
+    g = p.get("bgather")
+    if flags & ZGEMM_B_GATHER:
+        if g is None or not _zgemm_ex_has_kscale(p):
+            return  # the library refuses it before anything is launched
+        g = np.asarray(g, dtype=np.int64)
+        if g.shape != (N, 2) or g.min() < 0 or g.max() >= 2 ** 31:
+            raise ValueError("zgemm_grouped_ex: bgather must be N pairs of non-negative 32-bit offsets")
+    if K == 0:
+        return
+    if a_off + (M - 1) * rsA + (K - 1) * csA >= nA:
+        raise ValueError("zgemm_grouped_ex: the view of A reaches outside its tensor")
+    if flags & ZGEMM_B_GATHER:
+        if b_off + int(g[:, 0].max()) + (K - 1) * rsB >= nB:
+            raise ValueError("zgemm_grouped_ex: a gathered column of B reaches outside its tensor")
+        if ks_off + int(g[:, 1].max()) + K - 1 >= nks:
+            raise ValueError("zgemm_grouped_ex: a weight run of a gathered column reaches outside kscale")
+        return
+    if b_off + (K - 1) * rsB + (N - 1) * csB >= nB:
+        raise ValueError("zgemm_grouped_ex: the view of B reaches outside its tensor")
+    if _zgemm_ex_has_kscale(p) and ks_off + K - 1 >= nks:
+        raise ValueError("zgemm_grouped_ex: kscale reaches outside its tensor")
+
+
+def _zgemm_ex_record(q, p, ptrs):
+    """Fill one ZgemmProblemEx from a problem dict; ptrs = addresses of (A, B, C, kscale, bgather), 0 for none."""
+    q.A, q.B, q.C, q.kscale, q.bgather = [int(x) or None for x in ptrs]
+    q.M, q.N, q.K = int(p["M"]), int(p["N"]), int(p["K"])
+    q.rsA, q.csA, q.rsB, q.csB, q.ldc = (int(p[k]) for k in ("rsA", "csA", "rsB", "csB", "ldc"))
+    q.csc, q.flags, q.launch = int(p.get("csc", 1)), int(p.get("flags", 0)), int(p.get("launch", 0))
+    q.alpha, q.alpha_im, q.beta = float(p.get("alpha", 1.0)), float(p.get("alpha_im", 0.0)), float(p.get("beta", 0.0))
+
+
+def zgemm_plan_info(problems):
+    """What the planner of the grouped product decides for a list of problem dicts (dm_zgemm_plan_info; needs no GPU
+    and looks at no memory: kscale counts as present with a `kscale` tensor or `has_kscale` true, bgather with a `bgather` array).  Returns
+    one dict per launch, in ascending `launch` order: launch, use4, deep, wide_r, tiles and flat (per class, in the
+    order of ZGEMM_CLASSES) and cells, an int array [class, flat, ragged, rmw] of tile counts.  Raises DriftMIError
+    where the planner refuses a flag combination."""
+    lib = load()
+    n = len(problems)
+    arr = (ZgemmProblemEx * max(n, 1))()
+    for q, p in zip(arr, problems):
+        full = int(p["M"]) > 0 and int(p["N"]) > 0
+        _zgemm_ex_record(q, p, (full, full, full, _zgemm_ex_has_kscale(p), p.get("bgather") is not None))
+    nl = len({int(p.get("launch", 0)) for p in problems})
+    out = (ZgemmLaunchInfo * max(nl, 1))()
+    got = c_int(0)
+    rc = lib.dm_zgemm_plan_info(n, arr, nl, out, ctypes.byref(got))
+    if rc != 0:
+        raise DriftMIError("dm_zgemm_plan_info failed (%d)" % rc)
+    assert got.value == nl
+    return [dict(launch=o.launch, use4=bool(o.use4), deep=bool(o.deep), wide_r=bool(o.wide_r), tiles=list(o.tiles),
+                 flat=list(o.flat), cells=np.array([list(c) for c in o.cells], dtype=np.int64).reshape(4, 2, 2, 2))
+            for o in out[:nl]]
+
+
 class Context(object):
-    """One per GPU / process.  Binds to torch's current stream on that device so
+    """One per GPU / process. Binds to torch's current stream on that device so
     that torch.cuda events bracket the work."""
 
     def __init__(self, device=0, workspace_bytes=1 << 30):
@@ -305,6 +407,40 @@ class Context(object):
             q.conjA, q.conjB = int(bool(p.get("conjA", False))), int(bool(p.get("conjB", False)))
             q.alpha, q.beta = float(p.get("alpha", 1.0)), float(p.get("beta", 0.0))
         self.check(self.lib.dm_zgemm_grouped(self.h, n, arr), "dm_zgemm_grouped")
+
+    def zgemm_grouped_ex(self, problems):
+        """The grouped product with every field of its descriptor (dm_zgemm_grouped_ex, exposed for the parity tests).
+        Each problem is a dict as described above `zgemm_ex_check_views`, with contiguous device tensors A, B, C
+        (complex128; float64 for B with ZGEMM_B_REAL and for all three with ZGEMM_ALL_REAL) and optionally kscale
+        (float64).  Problems with the same `launch` share one grouped launch; the launches run in ascending order.
+        Every view is checked against its tensor on the host first (ValueError): a wrong stride or offset would be an
+        out-of-bounds access on the device."""
+        n = len(problems)
+        if n == 0:
+            return
+        torch = self.torch
+        arr = (ZgemmProblemEx * n)()
+        keep = []
+        for q, p in zip(arr, problems):
+            flags = int(p.get("flags", 0))
+            A, B, C, ks = p["A"], p["B"], p["C"], p.get("kscale")
+            want = [torch.float64 if flags & ZGEMM_ALL_REAL else torch.complex128,
+                    torch.float64 if flags & (ZGEMM_ALL_REAL | ZGEMM_B_REAL) else torch.complex128,
+                    torch.float64 if flags & ZGEMM_ALL_REAL else torch.complex128, torch.float64]
+            for t, dt in zip((A, B, C, ks), want):
+                if t is not None and not (t.dtype == dt and t.is_contiguous() and t.is_cuda):
+                    raise ValueError("zgemm_grouped_ex: contiguous device tensors of the class's element types expected")
+            zgemm_ex_check_views(p, A.numel(), B.numel(), C.numel(), ks.numel() if ks is not None else 0)
+            a_off, b_off, c_off, ks_off = (int(p.get(k, 0)) for k in ("a_off", "b_off", "c_off", "ks_off"))
+            g = None
+            if p.get("bgather") is not None:
+                g = self.to_device(np.asarray(p["bgather"], dtype=np.int32))
+                keep.append(g)
+            _zgemm_ex_record(q, p, (A.data_ptr() + A.element_size() * a_off, B.data_ptr() + B.element_size() * b_off,
+                                    C.data_ptr() + C.element_size() * c_off,
+                                    ks.data_ptr() + 8 * ks_off if ks is not None else 0,
+                                    g.data_ptr() if g is not None else 0))
+        self.check(self.lib.dm_zgemm_grouped_ex(self.h, n, arr), "dm_zgemm_grouped_ex")
 
     def bit_truncate_max_complex(self, t, prec, prec_max_row):
         """In place on a contiguous complex device tensor whose LAST axis is the row (drift/core/beamtransfer.py:641-646)."""

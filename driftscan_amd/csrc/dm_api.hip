@@ -3,6 +3,8 @@
 #include "dm_kernels.h"
 #include "../../include/driftmi.h"
 
+#include <algorithm>
+
 extern "C" {
 
 int dm_zgemm_strided_batched(dm_ctx* ctx, int M, int N, int K, double alpha, const void* A, int rsA, int csA,
@@ -41,6 +43,114 @@ int dm_zgemm_grouped(dm_ctx* ctx, int nprob, const dm_zgemm_problem* probs) {
                              p.conjB != 0, reinterpret_cast<cplx*>(p.C), p.ldc, p.M, p.N, p.K, p.alpha, p.beta));
   }
   return dm_gemm_grouped_launch(ctx, g);
+}
+
+// ---- the grouped product with its whole descriptor (exposed for the parity tests) ----
+static_assert(DM_ZGEMM_CONJ_A == DM_GEMM_CONJ_A && DM_ZGEMM_CONJ_B == DM_GEMM_CONJ_B && DM_ZGEMM_B_REAL == DM_GEMM_B_REAL &&
+                  DM_ZGEMM_LOWER == DM_GEMM_LOWER && DM_ZGEMM_ALL_REAL == DM_GEMM_ALL_REAL &&
+                  DM_ZGEMM_UPPER == DM_GEMM_UPPER && DM_ZGEMM_B_GATHER == DM_GEMM_B_GATHER &&
+                  DM_ZGEMM_UPPER128 == DM_GEMM_UPPER128,
+              "the public DM_ZGEMM_* flags are the planner's DM_GEMM_* flags");
+static_assert(sizeof(int2) == 2 * sizeof(int), "bgather travels as pairs of int");
+
+}  // extern "C"
+
+namespace {
+
+constexpr int kZgemmFlags = DM_GEMM_CONJ_A | DM_GEMM_CONJ_B | DM_GEMM_B_REAL | DM_GEMM_LOWER | DM_GEMM_ALL_REAL |
+                            DM_GEMM_UPPER | DM_GEMM_B_GATHER | DM_GEMM_UPPER128;
+
+// The problems sorted into launches (ascending `launch`, the order of the list kept inside one).  Looks at no memory
+// behind the pointers.  false: a negative size, unknown flag bits, or a missing operand.
+bool zgemm_ex_launches(int nprob, const dm_zgemm_problem_ex* probs, std::vector<int>& ids,
+                       std::vector<std::vector<dm_gemm_desc>>& launches) {
+  ids.clear();
+  launches.clear();
+  for (int i = 0; i < nprob; ++i) ids.push_back(probs[i].launch);
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  launches.resize(ids.size());
+  for (int i = 0; i < nprob; ++i) {
+    const dm_zgemm_problem_ex& p = probs[i];
+    if (p.M < 0 || p.N < 0 || p.K < 0 || (p.flags & ~kZgemmFlags)) return false;
+    if (p.M > 0 && p.N > 0 && (!p.C || (p.K > 0 && (!p.A || !p.B)))) return false;
+    dm_gemm_desc d;
+    d.A = p.A; d.B = p.B; d.C = p.C; d.kscale = p.kscale;
+    d.bgather = reinterpret_cast<const int2*>(p.bgather);
+    d.M = p.M; d.N = p.N; d.K = p.K;
+    d.rsA = p.rsA; d.csA = p.csA; d.rsB = p.rsB; d.csB = p.csB; d.ldc = p.ldc; d.csc = p.csc;
+    d.flags = p.flags;
+    d.alpha = p.alpha; d.beta = p.beta; d.alpha_im = p.alpha_im;
+    launches[std::lower_bound(ids.begin(), ids.end(), p.launch) - ids.begin()].push_back(d);
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dm_zgemm_grouped_ex(dm_ctx* ctx, int nprob, const dm_zgemm_problem_ex* probs) {
+  if (!ctx) return DM_EARG;
+  DM_ARG(ctx, nprob >= 0 && (nprob == 0 || probs));
+  std::vector<int> ids;
+  std::vector<std::vector<dm_gemm_desc>> launches;
+  DM_ARG(ctx, zgemm_ex_launches(nprob, probs, ids, launches));
+  dm_ws_scope ws_scope__(ctx);
+  if (launches.size() == 1) {
+    const int rc = dm_gemm_grouped_launch(ctx, launches[0]);
+    if (rc == DM_EARG) ctx->err = "bad argument: a flag combination the grouped product does not take";
+    return rc;
+  }
+  // a chain: every plan first, one copy of all their host images, then the launches in turn
+  std::vector<dm_gemm_plan> plans(launches.size());
+  for (size_t l = 0; l < launches.size(); ++l) {
+    const int rc = dm_gemm_plan_build(launches[l], plans[l]);
+    if (rc == DM_EARG) ctx->err = "bad argument: a flag combination the grouped product does not take";
+    if (rc != DM_OK) return rc;
+  }
+  std::vector<const dm_gemm_plan*> pp;
+  for (const auto& pl : plans) pp.push_back(&pl);
+  std::vector<const char*> dev;
+  DM_TRY(dm_gemm_plans_upload(ctx, pp, dev));
+  for (size_t l = 0; l < plans.size(); ++l) DM_TRY(dm_gemm_plan_run(ctx, plans[l], dev[l]));
+  return DM_OK;
+}
+
+int dm_zgemm_plan_info(int nprob, const dm_zgemm_problem_ex* probs, int max_launch, dm_zgemm_launch_info* out,
+                       int* nlaunch) {
+  if (nprob < 0 || (nprob > 0 && !probs) || max_launch < 0 || (max_launch > 0 && !out) || !nlaunch) return DM_EARG;
+  std::vector<int> ids;
+  std::vector<std::vector<dm_gemm_desc>> launches;
+  if (!zgemm_ex_launches(nprob, probs, ids, launches)) return DM_EARG;
+  *nlaunch = (int)launches.size();
+  for (size_t l = 0; l < launches.size(); ++l) {
+    dm_gemm_plan plan;
+    DM_TRY(dm_gemm_plan_build(launches[l], plan));
+    if ((int)l >= max_launch) continue;  // still planned: a refused combination is reported wherever it sits
+    dm_zgemm_launch_info& o = out[l];
+    std::memset(&o, 0, sizeof(o));
+    o.launch = ids[l];
+    o.use4 = plan.use4;
+    o.deep = plan.deep;
+    o.wide_r = plan.wide_r;
+    if (plan.blob.empty()) continue;
+    const dm_gemm_tile* t = reinterpret_cast<const dm_gemm_tile*>(plan.blob.data() + plan.desc_bytes);
+    const size_t cnt[4] = {plan.n0, plan.n1, plan.n2, plan.n3};
+    for (int c = 0; c < 4; ++c)
+      for (size_t i = 0; i < cnt[c]; ++i, ++t) {
+        const dm_gemm_desc& d = launches[l][t->desc];
+        // the extent of the tile as the kernel of its class cuts it
+        const bool flat = t->tm < 0, wide = c == 1 && plan.wide_r;
+        const int rows = flat ? 32 : 64, cols = (flat ? 128 : 64) * (wide ? 2 : 1);
+        const int m0 = flat ? (-t->tm - 1) * 32 : t->tm * 64, n0 = t->tn * cols;
+        const bool ragged = m0 + rows > d.M || n0 + cols > d.N || d.kscale != nullptr || c == 3;
+        o.tiles[c] += 1;
+        o.flat[c] += flat;
+        o.cells[c][flat][ragged][d.beta != 0.0] += 1;
+      }
+  }
+  return DM_OK;
 }
 
 int dm_zpotrf_batched(dm_ctx* ctx, int n, void* A, int ld, int64_t stride, int batch, int* info_host) {

@@ -656,6 +656,13 @@ int dm_gemm_plan_build(const std::vector<dm_gemm_desc>& descs, dm_gemm_plan& pla
     const dm_gemm_desc& d = descs[i];
     if (d.M <= 0 || d.N <= 0) continue;
     if ((d.flags & DM_GEMM_B_REAL) && (d.flags & (DM_GEMM_LOWER | DM_GEMM_UPPER))) return DM_EARG;  // no triangular real-B products
+    // fields that the kernel of the problem's class would not read are refused, not ignored
+    if ((d.flags & DM_GEMM_ALL_REAL) &&
+        (d.kscale || d.csc != 1 || d.alpha_im != 0.0 ||
+         (d.flags & (DM_GEMM_CONJ_A | DM_GEMM_CONJ_B | DM_GEMM_B_REAL | DM_GEMM_B_GATHER))))
+      return DM_EARG;
+    if ((d.flags & DM_GEMM_B_REAL) && (d.flags & DM_GEMM_B_GATHER)) return DM_EARG;
+    if ((d.flags & DM_GEMM_B_GATHER) && (!d.bgather || !d.kscale)) return DM_EARG;
     const bool wide = wide_r && (d.flags & DM_GEMM_B_REAL) && !(d.flags & DM_GEMM_ALL_REAL);
     const int BNd = wide ? 2 * BN : BN, FNd = wide ? 256 : 128;
     int tm = (d.M + BM - 1) / BM, tn = (d.N + BNd - 1) / BNd;

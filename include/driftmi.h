@@ -95,6 +95,67 @@ typedef struct dm_zgemm_problem {
 } dm_zgemm_problem;
 int dm_zgemm_grouped(dm_ctx* ctx, int nprob, const dm_zgemm_problem* probs_host);
 
+/* The grouped product with every field of its internal descriptor.  Exposed for the parity tests: the drivers of the
+ * library (Cholesky and triangular solves, the tridiagonalisations, BT-gen, sky synthesis, the covariance
+ * projections) fill these fields themselves; the two entries below let a test reach each kernel class and flag
+ * directly.  C(m, n) lives at C[m ldc + n csc]:
+ *   C = (alpha + i alpha_im) op(A) diag(kscale) op(B) + beta C
+ * flags (DM_ZGEMM_*):
+ *   CONJ_A, CONJ_B  conjugate the elements as they are read
+ *   B_REAL          B holds doubles (strides in doubles)
+ *   ALL_REAL        A, B and C hold doubles; takes no kscale, csc != 1, alpha_im, conj flag, B_REAL or B_GATHER
+ *   B_GATHER        B(k, n) = B[bgather[2n] + k rsB] * kscale[bgather[2n + 1] + k]; needs bgather and kscale, csB is
+ *                   not read; not together with B_REAL
+ *   LOWER / UPPER   only the 64 x 64 tiles on or below / above the block diagonal are computed, the rest of C is
+ *                   left alone; UPPER | UPPER128 also computes the tile left of an odd diagonal tile.  Complex B only.
+ * A combination listed as not taken is refused with DM_EARG before anything is launched. */
+enum {
+  DM_ZGEMM_CONJ_A = 1,
+  DM_ZGEMM_CONJ_B = 2,
+  DM_ZGEMM_B_REAL = 4,
+  DM_ZGEMM_LOWER = 8,
+  DM_ZGEMM_ALL_REAL = 16,
+  DM_ZGEMM_UPPER = 32,
+  DM_ZGEMM_B_GATHER = 64,
+  DM_ZGEMM_UPPER128 = 128
+};
+typedef struct dm_zgemm_problem_ex {
+  const void* A;
+  const void* B;
+  void* C;
+  const double* kscale; /* K weights (applied to A), the weight runs of a gathered B, or NULL */
+  const int* bgather;   /* B_GATHER: N pairs (element offset of the column's K-run in B, offset of its weights) */
+  int M, N, K;
+  int rsA, csA, rsB, csB, ldc, csc;
+  int flags;
+  double alpha, alpha_im, beta;
+  int launch; /* problems with the same value share one grouped launch */
+} dm_zgemm_problem_ex;
+/* The problems of each `launch` value form one plan; all plans are built first, their host images travel to the
+ * device in ONE copy, and the launches run in ascending `launch` order on the context's stream (the route of the
+ * Cholesky, solve and tridiagonalisation chains), so a later launch may read what an earlier one wrote.  M, N, K >= 0;
+ * a problem with M = 0 or N = 0 writes nothing, K = 0 gives C = beta C.  Returns when the work is queued. */
+int dm_zgemm_grouped_ex(dm_ctx* ctx, int nprob, const dm_zgemm_problem_ex* probs_host);
+
+/* What the planner decides for the same list, per launch in ascending `launch` order (exposed for the parity tests,
+ * which assert their coverage of the kernels from it).  Host only: no context, no device, and no pointer of a problem
+ * is followed (only NULL or not).  Classes are 0 complex, 1 real B, 2 all real, 3 gathered B.
+ * cells[class][flat][ragged][rmw] counts the tiles: flat = a 32-row tile of the register-only kernel, ragged = the
+ * tile reaches past M or N or its operands are scaled (kscale, gathered B) — the masked path of the kernels —, rmw =
+ * beta != 0.  *nlaunch gets the number of launches; at most max_launch entries of out are written.  DM_EARG for a
+ * flag combination the planner refuses. */
+typedef struct dm_zgemm_launch_info {
+  int launch;
+  int use4;   /* register-only kernels (0: the LDS-staged ones) */
+  int deep;   /* complex class on the deep-prefetch kernel */
+  int wide_r; /* real-B class on 64 x 128 tiles */
+  int tiles[4];
+  int flat[4];
+  int cells[4][2][2][2];
+} dm_zgemm_launch_info;
+int dm_zgemm_plan_info(int nprob, const dm_zgemm_problem_ex* probs_host, int max_launch, dm_zgemm_launch_info* out,
+                       int* nlaunch);
+
 /* Batched lower Cholesky A = L L^H in place (n x n, row-major, ld), `batch`
  * matrices `stride` elements apart.  info_host[i] = 0 or the order of the first
  * non-positive-definite leading minor.  Synchronises.
