@@ -189,6 +189,7 @@ SIGNATURES = {
                 c_vp, c_i64, c_int]),
     "dm_toeplitz_solve": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "dm_toeplitz_max_rhs": (c_int, [c_int]),
+    "dm_toeplitz_solve_diag": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None
@@ -831,13 +832,17 @@ def _toeplitz_max_rhs(self, n):
     return int(self.lib.dm_toeplitz_max_rhs(int(n)))
 
 
-def _toeplitz_solve(self, col, b, ridge=0.0):
+def _toeplitz_solve(self, col, b, ridge=0.0, diag=False):
     """`batch` Hermitian positive-definite Toeplitz systems on the device (dm_toeplitz_solve, the Levinson recursion of
     DESIGN.md section 4.16; `timestream.toeplitz_levinson_host` restates it): col (batch, n) complex128 first columns
     (numpy or device; Im c_0 is ignored), b (batch, nrhs, n) right-hand sides.  `ridge` adds ridge * c_0 to c_0 on a copy.
     Returns (x, info): new device tensors (batch, nrhs, n) complex128 and (batch,) int32 — 0 solved, k < n: not positive
     definite at step k, n: c_0 <= 0; such a system's solutions are zeros.  More right-hand sides than
-    `toeplitz_max_rhs(n)` go through several calls (the bits of a solution do not depend on its companions)."""
+    `toeplitz_max_rhs(n)` go through several calls (the bits of a solution do not depend on its companions).
+
+    diag=True: returns (x, info, d) with d (batch, n) float64 the diagonal of the inverse of the system as solved, that
+    is of (A + ridge c_0 I)^-1 (dm_toeplitz_solve_diag; zeros for info != 0; taken from the first call when the right-hand
+    sides are split).  x and info have the bits of diag=False."""
     torch = self.torch
     col = self.to_device(np.asarray(col, dtype=np.complex128)) if not hasattr(col, "data_ptr") else col
     b = self.to_device(np.asarray(b, dtype=np.complex128)) if not hasattr(b, "data_ptr") else b
@@ -860,16 +865,47 @@ def _toeplitz_solve(self, col, b, ridge=0.0):
         col[:, 0] += ridge * col[:, 0].real
     x = b.clone(memory_format=torch.contiguous_format)
     info = self.empty((batch,), np.int32)
+    d = self.empty((batch, n), np.float64) if diag else None
+
+    def call(part, first):
+        if diag and first:
+            self.check(self.lib.dm_toeplitz_solve_diag(self.h, n, int(part.shape[1]), batch, self.ptr(col), self.ptr(part),
+                                                       self.ptr(d), self.ptr(info)), "dm_toeplitz_solve_diag")
+        else:
+            self.check(self.lib.dm_toeplitz_solve(self.h, n, int(part.shape[1]), batch, self.ptr(col), self.ptr(part),
+                                                  self.ptr(info)), "dm_toeplitz_solve")
+
     if nrhs <= most:
-        self.check(self.lib.dm_toeplitz_solve(self.h, n, nrhs, batch, self.ptr(col), self.ptr(x), self.ptr(info)),
-                   "dm_toeplitz_solve")
-        return x, info
+        call(x, True)
+        return (x, info, d) if diag else (x, info)
     for r0 in range(0, nrhs, most):   # info depends on col alone: every call writes the same values
         part = x[:, r0 : r0 + most].contiguous()
-        self.check(self.lib.dm_toeplitz_solve(self.h, n, int(part.shape[1]), batch, self.ptr(col), self.ptr(part),
-                                              self.ptr(info)), "dm_toeplitz_solve")
+        call(part, r0 == 0)
         x[:, r0 : r0 + most] = part
-    return x, info
+    return (x, info, d) if diag else (x, info)
+
+
+def _toeplitz_inverse_diag(self, col, ridge=0.0):
+    """The diagonals of the inverses of `batch` Hermitian positive-definite Toeplitz matrices given by their first
+    columns col (batch, n) complex128 (numpy or device), with ridge * c_0 added to c_0: (d (batch, n) float64, info
+    (batch,) int32) on the device, by dm_toeplitz_solve_diag without right-hand sides.  info as `toeplitz_solve`; a
+    failed system has d = 0.  Host statement: `timestream.toeplitz_inverse_diag_host`."""
+    col = self.to_device(np.asarray(col, dtype=np.complex128)) if not hasattr(col, "data_ptr") else col
+    if col.dim() != 2 or not (col.is_complex() and col.element_size() == 16) or int(col.shape[1]) < 1:
+        raise ValueError("toeplitz_inverse_diag: complex128 col (batch, n) expected")
+    batch, n = (int(v) for v in col.shape)
+    ridge = float(ridge)
+    if not (ridge >= 0.0 and np.isfinite(ridge)):
+        raise ValueError("toeplitz_inverse_diag: ridge must be finite and not negative")
+    col = col.contiguous()
+    if ridge > 0.0:
+        col = col.clone()
+        col[:, 0] += ridge * col[:, 0].real
+    d = self.empty((batch, n), np.float64)
+    info = self.empty((batch,), np.int32)
+    self.check(self.lib.dm_toeplitz_solve_diag(self.h, n, 0, batch, self.ptr(col), self.ptr(None), self.ptr(d),
+                                               self.ptr(info)), "dm_toeplitz_solve_diag")
+    return d, info
 
 
 def _mmode_weights(self, weight, nf, npairs, ntime):
@@ -896,7 +932,7 @@ def _mmode_weights(self, weight, nf, npairs, ntime):
     return w.reshape(-1, ntime).contiguous(), lead
 
 
-def _mmode_transform_weighted(self, X, weight, mmax, ridge=0.0, out=None):
+def _mmode_transform_weighted(self, X, weight, mmax, ridge=0.0, out=None, inflation=False):
     """Weighted least-squares m-modes of flagged timestreams on the device: the a_k, |k| <= mmax,
     that minimise sum_t w_t |x_t - sum_k a_k e^{2 pi i k t / ntime}|^2 (+ ridge * mean(w) * |a|^2), in the layout of
     `mmode_transform`, (mmax + 1, nf, 2, npairs): slot 1 is the conjugate of the -m mode, zero for m = 0.
@@ -910,7 +946,17 @@ def _mmode_transform_weighted(self, X, weight, mmax, ridge=0.0, out=None):
     order 2 mmax + 1 (`toeplitz_solve`).  Without a pair axis the baselines of a frequency (of all frequencies for
     (ntime,)) are right-hand sides of one system.  A row of constant weight w_0 has A = w_0 I exactly and gets that
     column, so data without flags gives the bits of `mmode_transform`.  Host statement:
-    `timestream.mmodes_weighted_host`.  (Device weights are checked with a torch reduction and a read-back.)"""
+    `timestream.mmodes_weighted_host`.  (Device weights are checked with a torch reduction and a read-back.)
+
+    inflation=True: a third return value, float64 (mmax + 1, nf, 2, npairs) in the layout of the modes, the noise
+    variance of every mode relative to that of complete data: with circular white noise of per-sample variance
+    ntime * noisepower on the data, Cov(a) = noisepower A^-1 and the pseudo-covariance vanishes, so the noise of an
+    m-block stays diagonal with variance noisepower * d, d = diag(A^-1) at k = +m (slot 0) and k = -m (slot 1) — from
+    the same launch as the modes (`toeplitz_solve(diag=True)`).  Exactly 1.0 at (m = 0, slot 1), where the data holds a
+    zero and the nominal model unit noise; exactly 1 / w_0 on a row of constant weight w_0 (1.0 for complete data) when
+    ridge = 0; 0.0 on rows with info != 0, whose modes are zeros and carry no noise; without a pair axis the diagonal of
+    the one system for all its baselines.  For ridge = 0 this is the exact variance ratio; for ridge > 0 it is the
+    diagonal of A_rho^-1, an upper bound of the variance, A_rho^-1 A A_rho^-1 <= A_rho^-1."""
     torch = self.torch
     if X.dim() != 3 or not (X.is_complex() and X.element_size() == 16):
         raise ValueError("mmode_transform_weighted: X (nf, npairs, ntime) complex128 expected")
@@ -928,7 +974,8 @@ def _mmode_transform_weighted(self, X, weight, mmax, ridge=0.0, out=None):
         raise ValueError("mmode_transform_weighted: out must be a contiguous (mmax + 1, nf, 2, npairs) tensor")
     S = int(w.shape[0])
     if nf == 0 or npairs == 0:
-        return out, self.zeros((nf, npairs), np.int32)
+        info = self.zeros((nf, npairs), np.int32)
+        return (out, info, self.zeros((mmax + 1, nf, 2, npairs), np.float64)) if inflation else (out, info)
     if self.toeplitz_max_rhs(N) < 1:
         raise ValueError("mmode_transform_weighted: systems of order %d do not fit in the LDS of a CU" % N)
     bm = self.mmode_transform(X * w.view(lead + (ntime,)), mmax)                                   # (mmax + 1, nf, 2, npairs)
@@ -951,18 +998,31 @@ def _mmode_transform_weighted(self, X, weight, mmax, ridge=0.0, out=None):
         B[:, :, :mmax] = bm[1:, :, 1].conj().permute(1, 2, 0).flip(-1)
     B = B.view(S, (nf * npairs) // S, N)
     B = torch.where(short[:, None, None], torch.zeros_like(B), B)
-    x, info = self.toeplitz_solve(col, B, ridge=ridge)
+    if inflation:
+        x, info, d = self.toeplitz_solve(col, B, ridge=ridge, diag=True)
+    else:
+        x, info = self.toeplitz_solve(col, B, ridge=ridge)
     x = x.view(nf, npairs, N)
     out[:, :, 0] = x[:, :, mmax:].permute(2, 0, 1)
     out[0, :, 1].zero_()
     if mmax > 0:
         out[1:, :, 1] = x[:, :, :mmax].flip(-1).conj().permute(2, 0, 1)
     info = torch.where(short, torch.full_like(info, -1), info)
+    if inflation:
+        d = torch.where(short[:, None], torch.zeros_like(d), d)                  # not solved: zeros, no noise
+        d = d.view(lead + (N,)).expand(nf, npairs, N)
+        infl = self.empty((mmax + 1, nf, 2, npairs), np.float64)
+        infl[:, :, 0] = d[:, :, mmax:].permute(2, 0, 1)
+        infl[0, :, 1] = 1.0
+        if mmax > 0:
+            infl[1:, :, 1] = d[:, :, :mmax].flip(-1).permute(2, 0, 1)
+        return out, info.view(lead).expand(nf, npairs).contiguous(), infl
     return out, info.view(lead).expand(nf, npairs).contiguous()
 
 
 Context.toeplitz_max_rhs = _toeplitz_max_rhs
 Context.toeplitz_solve = _toeplitz_solve
+Context.toeplitz_inverse_diag = _toeplitz_inverse_diag
 Context.mmode_transform_weighted = _mmode_transform_weighted
 
 

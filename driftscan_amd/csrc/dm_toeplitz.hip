@@ -49,9 +49,26 @@ __device__ __forceinline__ double tz_wave_sum(double v) {
 // thread adds the partials wave 0, 1, .. and so holds the same gamma, beta and coefficients; the thread of i updates
 // the elements i and k - i of f and of every x_j in place.  Barrier.  The order of every sum is a function of (n, k)
 // alone, so a system has the same bits alone, in any batch and at any position.
-template <int NT>
+//
+// DIAG (dm_toeplitz_solve_diag): after the last step f solves T' f = beta e_0, so f / (beta c_0) is the first column of
+// the inverse and the Gohberg-Semencul formula gives its diagonal as one prefix sum, d_i = (sum_{j<=i} g_j) / (beta c_0)
+// with g_j = |f_j|^2 - |f_{n-j}|^2 and f_n := 0.  |f_i|^2 goes into the space of r (dead by then); the thread of
+// tid owns the elements tid C .. tid C + C - 1, C = ceil(n / NT): it adds its g in index order, the wave scans the
+// threads' sums (tz_wave_scan), every thread adds the totals of the waves before its own in wave order and then walks
+// its elements again.  The order is a function of n alone.  A failed system gets zeros.  nrhs = 0 is allowed here.
+__device__ __forceinline__ double tz_wave_scan(double v, uint32_t lane) {   // inclusive, over the lanes 0 .. lane
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const double t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+template <int NT, bool DIAG>
 __global__ __launch_bounds__(NT) void toeplitz_levinson_kernel(const cplx* __restrict__ col, cplx* __restrict__ b,
-                                                               int* __restrict__ info, uint32_t n, uint32_t nrhs) {
+                                                               int* __restrict__ info, uint32_t n, uint32_t nrhs,
+                                                               double* __restrict__ diag) {
   extern __shared__ __attribute__((aligned(16))) cplx tz_lds[];
   constexpr uint32_t NW = NT / 64;
   const uint32_t nvec = 1 + nrhs;
@@ -137,6 +154,37 @@ __global__ __launch_bounds__(NT) void toeplitz_levinson_kernel(const cplx* __res
       }
       __syncthreads();
     }
+    if constexpr (DIAG) {
+      if (!fail) {                                                // the same value in every thread
+        double* const p = reinterpret_cast<double*>(r);           // |f_i|^2, i < n: r is dead
+        double* const tot = reinterpret_cast<double*>(red);       // the waves' totals: red is dead too
+        double* const ds = diag + sys * n;
+        for (uint32_t i = tid; i < n; i += NT) p[i] = cabs2(vec[i]);
+        __syncthreads();
+        const uint32_t per = (n + NT - 1) / NT;
+        const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
+        double own = 0.0;
+        for (uint32_t i = lo; i < hi; ++i) own += p[i] - (i == 0 ? 0.0 : p[n - i]);
+        const double incl = tz_wave_scan(own, lane);
+        const double before = __shfl_up(incl, 1, 64);
+        if (NW > 1) {
+          if (lane == 63) tot[wave] = incl;
+          __syncthreads();
+        }
+        double run = 0.0;
+        for (uint32_t w = 0; w < wave; ++w) run += tot[w];
+        if (lane > 0) run += before;
+        const double scale = beta * c0;
+        for (uint32_t i = lo; i < hi; ++i) {
+          run += p[i] - (i == 0 ? 0.0 : p[n - i]);
+          dm_stg(ds, i, run / scale);
+        }
+      }
+    }
+  }
+  if constexpr (DIAG) {
+    if (fail)
+      for (uint32_t i = tid; i < n; i += NT) dm_stg(diag + sys * n, i, 0.0);
   }
   if (fail) {
     for (uint32_t e = tid; e < nb; e += NT) dm_stg(bs, e, zero);
@@ -146,14 +194,14 @@ __global__ __launch_bounds__(NT) void toeplitz_levinson_kernel(const cplx* __res
   if (tid == 0) info[sys] = fail;
 }
 
-template <int NT>
-int toeplitz_launch(dm_ctx* ctx, int n, int nrhs, int batch, const cplx* col, cplx* b, int* info) {
+template <int NT, bool DIAG>
+int toeplitz_launch(dm_ctx* ctx, int n, int nrhs, int batch, const cplx* col, cplx* b, int* info, double* diag) {
   const size_t lds = (size_t)dm_toeplitz_lds(n, nrhs);
   if (lds > (size_t)DM_TOEPLITZ_LDS_PLAIN)
-    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&toeplitz_levinson_kernel<NT>),
+    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&toeplitz_levinson_kernel<NT, DIAG>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  DM_PLAUNCH(ctx, DM_PROF_UTIL, toeplitz_levinson_kernel<NT>, dim3((unsigned)batch), dim3(NT), lds, ctx->stream, col, b,
-             info, (uint32_t)n, (uint32_t)nrhs);
+  DM_PLAUNCH(ctx, DM_PROF_UTIL, (toeplitz_levinson_kernel<NT, DIAG>), dim3((unsigned)batch), dim3(NT), lds, ctx->stream,
+             col, b, info, (uint32_t)n, (uint32_t)nrhs, diag);
   DM_HIP(ctx, hipGetLastError());
   return DM_OK;
 }
@@ -174,6 +222,22 @@ extern "C" int dm_toeplitz_solve(dm_ctx* ctx, int n, int nrhs, int batch, const 
   DM_HIP(ctx, hipSetDevice(ctx->device));
   const cplx* col = static_cast<const cplx*>(col_dev);
   cplx* b = static_cast<cplx*>(b_dev);
-  if (n <= DM_TOEPLITZ_WAVE_N) return toeplitz_launch<64>(ctx, n, nrhs, batch, col, b, info_dev);
-  return toeplitz_launch<256>(ctx, n, nrhs, batch, col, b, info_dev);
+  if (n <= DM_TOEPLITZ_WAVE_N) return toeplitz_launch<64, false>(ctx, n, nrhs, batch, col, b, info_dev, nullptr);
+  return toeplitz_launch<256, false>(ctx, n, nrhs, batch, col, b, info_dev, nullptr);
+}
+
+extern "C" int dm_toeplitz_solve_diag(dm_ctx* ctx, int n, int nrhs, int batch, const void* col_dev, void* b_dev,
+                                      double* diag_dev, int* info_dev) {
+  if (!ctx) return DM_EARG;
+  const std::string bad = dm_toeplitz_check_diag(n, nrhs, batch, col_dev, b_dev, diag_dev, info_dev);
+  if (!bad.empty()) {
+    ctx->err = "dm_toeplitz_solve_diag: " + bad;
+    return DM_EARG;
+  }
+  if (batch == 0) return DM_OK;
+  DM_HIP(ctx, hipSetDevice(ctx->device));
+  const cplx* col = static_cast<const cplx*>(col_dev);
+  cplx* b = nrhs > 0 ? static_cast<cplx*>(b_dev) : nullptr;     // without right-hand sides b is never touched
+  if (n <= DM_TOEPLITZ_WAVE_N) return toeplitz_launch<64, true>(ctx, n, nrhs, batch, col, b, info_dev, diag_dev);
+  return toeplitz_launch<256, true>(ctx, n, nrhs, batch, col, b, info_dev, diag_dev);
 }

@@ -1,4 +1,4 @@
-// dm_toeplitz_args.h — host-side sizing and argument checks of dm_toeplitz_solve.  Plain C++
+// dm_toeplitz_args.h — host-side sizing and argument checks of dm_toeplitz_solve[_diag].  Plain C++
 // with no HIP in it, so a stand-alone program can compile and call it (scratch/toeplitz_args_check.cpp does, under the
 // address and undefined-behaviour sanitizers); dm_toeplitz.hip includes the same text.
 #pragma once
@@ -41,5 +41,23 @@ inline std::string dm_toeplitz_check(int n, int nrhs, int batch, const void* col
            " (dm_toeplitz_max_rhs: " + std::to_string(most) + ")";
   if (batch < 0) return "batch = " + std::to_string(batch) + " < 0";
   if (batch > 0 && (!col || !b || !info)) return "null pointer with batch > 0";
+  return "";
+}
+
+// The same for dm_toeplitz_solve_diag: nrhs = 0 is allowed (the diagonal alone: b is then not looked at, null or not)
+// and `diag` must be there.  Order n without right-hand sides needs the LDS of r, f and the reduction rows.
+inline std::string dm_toeplitz_check_diag(int n, int nrhs, int batch, const void* col, const void* b, const void* diag,
+                                          const void* info) {
+  if (n < 1) return "n = " + std::to_string(n) + " < 1";
+  if (nrhs < 0) return "nrhs = " + std::to_string(nrhs) + " < 0";
+  if (nrhs > 0) {
+    const std::string bad = dm_toeplitz_check(n, nrhs, batch, col, b, info);
+    if (!bad.empty()) return bad;
+  } else if (dm_toeplitz_lds(n, 0) > DM_TOEPLITZ_LDS_BYTES) {
+    return "order " + std::to_string(n) + " needs " + std::to_string(dm_toeplitz_lds(n, 0)) + " bytes of LDS, a CU has " +
+           std::to_string(DM_TOEPLITZ_LDS_BYTES);
+  }
+  if (batch < 0) return "batch = " + std::to_string(batch) + " < 0";
+  if (batch > 0 && (!col || !diag || !info)) return "null pointer with batch > 0";
   return "";
 }

@@ -2,7 +2,8 @@
 
 The counterpart of ``drift.pipeline.pipeline.PipelineManager`` (drift/pipeline/pipeline.py:20-198), by behaviour: the same
 sections — ``config`` (the properties below), ``timestreams`` (entries with ``name``, ``directory``, optionally
-``output_directory``, ``mmode_ridge`` (this package: the ridge of the weighted m-modes of flagged data) and a ``simulate``
+``output_directory``, ``mmode_ridge`` (this package: the ridge of the weighted m-modes of flagged data),
+``flag_noise_bias_correct`` (this package: ``powerspectrum`` also subtracts the noise bias the flags add) and a ``simulate``
 block of arguments for ``timestream.simulate`` plus its ``product_directory``;
 the files of its ``maps`` and ``sources`` lists go through ``fixpath``)
 and optionally ``crosspower`` (entries with ``psname``, ``klname``, ``timestreams``, ``psfile``) — the same defaults,
@@ -87,6 +88,8 @@ class PipelineManager(config.Reader):
             ts.no_m_zero = self.no_m_zero
             if "mmode_ridge" in tsconf:   # Tikhonov term of the weighted m-modes of flagged data
                 ts.mmode_ridge = float(tsconf["mmode_ridge"])
+            if "flag_noise_bias_correct" in tsconf:   # powerspectrum() subtracts the noise bias of the flags too
+                ts.flag_noise_bias_correct = bool(tsconf["flag_noise_bias_correct"])
             self.timestreams[tsconf["name"]] = ts
             if "simulate" in tsconf:
                 self.simulations[tsconf["name"]] = tsconf["simulate"]

@@ -25,6 +25,7 @@ class Timestream(object):
     beamtransfer_dir = None
     no_m_zero = True
     mmode_ridge = 0.0   # Tikhonov term of the weighted m-mode estimate, relative to the mean weight
+    flag_noise_bias_correct = False   # powerspectrum() subtracts the noise bias of the flags too (`flag_noise_bias`)
 
     def __init__(self, tsdir, prodmanager):
         self.directory = os.path.abspath(tsdir)
@@ -71,21 +72,27 @@ class Timestream(object):
         return np.stack([ones if w is None else w for w in (self.weight_f(fi) for fi in fs)]) if len(fs) else \
             np.zeros((0, self.telescope.npairs, ntime), dtype=np.float64)
 
-    def _write_weight_summary(self, local_f, kept, info):
-        """Kept-sample counts and solver info (nfreq, npairs) of a weighted m-mode estimate, gathered from the ranks'
-        frequencies and written once to mmodes/weights.hdf5."""
+    def _write_weight_summary(self, local_f, kept, info, infl):
+        """Kept-sample counts, solver info and the mean and the largest noise inflation over the 2 mmax + 1 modes of a
+        row (all (nfreq, npairs)) of a weighted m-mode estimate, gathered from the ranks' frequencies and written once to
+        mmodes/weights.hdf5.  infl: (mmax + 1, len(local_f), 2, npairs)."""
         tel = self.telescope
-        parts = parallel.gather_objects((list(local_f), kept, info))
+        per_mode = np.concatenate([infl[:, :, 0], infl[1:, :, 1]], axis=0)      # (2 mmax + 1, len(local_f), npairs)
+        parts = parallel.gather_objects((list(local_f), kept, info, per_mode.mean(axis=0), per_mode.max(axis=0)))
         if parallel.rank0():
             nkept = np.zeros((tel.nfreq, tel.npairs), dtype=np.int64)
             infos = np.zeros((tel.nfreq, tel.npairs), dtype=np.int32)
-            for fs, k, i in parts:
+            imean = np.zeros((tel.nfreq, tel.npairs), dtype=np.float64)
+            imax = np.zeros((tel.nfreq, tel.npairs), dtype=np.float64)
+            for fs, k, i, a, b in parts:
                 if len(fs):
-                    nkept[fs], infos[fs] = k, i
+                    nkept[fs], infos[fs], imean[fs], imax[fs] = k, i, a, b
             os.makedirs(self.output_directory + "/mmodes", exist_ok=True)
             with storage.File(self.output_directory + "/mmodes/weights.hdf5", "w") as f:
                 f.create_dataset("nkept", data=nkept)
                 f.create_dataset("info", data=infos)
+                f.create_dataset("inflation_mean", data=imean)
+                f.create_dataset("inflation_max", data=imax)
                 f.attrs["ridge"] = float(self.mmode_ridge)
                 f.attrs["ntime"] = int(self.ntime)
 
@@ -101,10 +108,41 @@ class Timestream(object):
         with storage.File(self._mfile(mi), "r") as f:
             return f["mmode"][:]
 
+    def _inflfile(self, mi):
+        return self._mdir(mi) + "/inflation.hdf5"
+
+    def noise_inflation(self, mi):
+        """[nfreq, 2, npairs] float64: the noise variance of every entry of `mmode(mi)` relative to the nominal
+        `noisepower` — what the weighted estimate of flagged data wrote next to the mode file,
+        ones for data without weights (which writes no such file)."""
+        if not os.path.exists(self._inflfile(mi)):
+            tel = self.telescope
+            return np.ones((tel.nfreq, 2, tel.npairs), dtype=np.float64)
+        with storage.File(self._inflfile(mi), "r") as f:
+            return f["noise_inflation"][:]
+
+    def _write_inflation(self, infl, m_of, f_of, me, nranks):
+        """The noise inflation (mmax + 1, local frequencies, 2, npairs) of this rank's frequencies regrouped by m across
+        the ranks exactly as the modes are, one mmodes/<m>/inflation.hdf5 per m of this rank."""
+        tel = self.telescope
+        got = parallel.exchange([np.ascontiguousarray(infl[m_of[r]]) for r in range(nranks)])
+        mine = m_of[me]
+        if mine:
+            full = np.zeros((len(mine), tel.nfreq, 2, tel.npairs), dtype=np.float64)
+            for src, part in enumerate(got):
+                if len(f_of[src]):
+                    full[:, f_of[src]] = part
+            for k, mi in enumerate(mine):
+                os.makedirs(self._mdir(mi), exist_ok=True)
+                with storage.File(self._inflfile(mi), "w") as f:
+                    f.create_dataset("noise_inflation", data=np.ascontiguousarray(full[k]))
+                    f.attrs["m"] = mi
+
     def generate_mmodes(self):
         """FFT the timestreams along time and regroup by m: +m in slot 0, the conjugate of -m in slot 1.  When the files
         hold a dataset `weight` (flags) the modes are the weighted least-squares estimate instead (`mmodes_weighted_host`
-        with `mmode_ridge`; counts and solver info go to mmodes/weights.hdf5)."""
+        with `mmode_ridge`; counts, solver info and inflation summaries go to mmodes/weights.hdf5, and every m gets the
+        per-mode noise inflation of the estimate in mmodes/<m>/inflation.hdf5, `noise_inflation`)."""
         marker = self.output_directory + "/mmodes/COMPLETED_M"
         if os.path.exists(marker):
             return
@@ -122,9 +160,10 @@ class Timestream(object):
         weights = self._weights_of(local_f, ntime)
         if weights is not None:
             x = np.stack([self.timestream_f(fi) for fi in local_f]) if local_f else np.zeros((0, tel.npairs, ntime), complex)
-            modes, info = mmodes_weighted_host(x, weights, mmax, ridge=self.mmode_ridge)
+            modes, info, infl = mmodes_weighted_host(x, weights, mmax, ridge=self.mmode_ridge, inflation=True)
             pairs[:] = modes.transpose(1, 2, 3, 0)
-            self._write_weight_summary(local_f, np.count_nonzero(weights > 0, axis=-1), info)
+            self._write_weight_summary(local_f, np.count_nonzero(weights > 0, axis=-1), info, infl)
+            self._write_inflation(infl, m_of, f_of, me, nranks)
         else:
             for k, fi in enumerate(local_f):
                 row = np.fft.fft(self.timestream_f(fi), axis=-1) / ntime        # (npairs, ntime)
@@ -175,7 +214,8 @@ class Timestream(object):
         """`generate_mmodes` with the time -> m transform on the device (`Context.mmode_transform`: a pruned DFT as two
         strided-batched ZGEMMs against a twiddle table, written in the layout of the mode files); the regrouping across
         ranks and the files are the per-m route's.  Files with a dataset `weight` go through
-        `Context.mmode_transform_weighted` and leave mmodes/weights.hdf5."""
+        `Context.mmode_transform_weighted` and leave mmodes/weights.hdf5 and the per-m
+        inflation.hdf5 files of `generate_mmodes`."""
         marker = self.output_directory + "/mmodes/COMPLETED_M"
         if os.path.exists(marker):
             return {}
@@ -193,6 +233,7 @@ class Timestream(object):
         step = max(1, int(chunk_gb * (1 << 30) // max(per_f, 1)))
         weighted = self.weight_f(0) is not None
         kept, infos = [], []
+        infl = np.zeros((mmax + 1, len(local_f), 2, npairs), dtype=np.float64) if weighted else None
         if weighted:   # the weights, their product with the data and the right-hand sides share the chunk
             step = max(1, int(chunk_gb * (1 << 30) // max(per_f + 16 * npairs * (2 * ntime + 4 * mmax + 2), 1)))
         for c0 in range(0, len(local_f), step):
@@ -204,9 +245,10 @@ class Timestream(object):
                 X = ctx.to_device(host)
             with self._timed("device"):
                 if weighted:
-                    out, info = ctx.mmode_transform_weighted(X, wts, mmax, ridge=self.mmode_ridge)
+                    out, info, dinf = ctx.mmode_transform_weighted(X, wts, mmax, ridge=self.mmode_ridge, inflation=True)
                     kept.append(np.count_nonzero(wts > 0, axis=-1))
                     infos.append(info.cpu().numpy())
+                    infl[:, c0 : c0 + len(fs)] = dinf.cpu().numpy()
                 else:
                     out = ctx.mmode_transform(X, mmax)
             with self._timed("download"):
@@ -214,7 +256,8 @@ class Timestream(object):
             del X, out
         if weighted:
             self._write_weight_summary(local_f, np.concatenate(kept) if kept else np.zeros((0, npairs), np.int64),
-                                       np.concatenate(infos) if infos else np.zeros((0, npairs), np.int32))
+                                       np.concatenate(infos) if infos else np.zeros((0, npairs), np.int32), infl)
+            self._write_inflation(infl, m_of, f_of, me, nranks)
         got = parallel.exchange([np.ascontiguousarray(pairs[m_of[r]]) for r in range(nranks)])
         mine = m_of[me]
         if mine:
@@ -537,8 +580,67 @@ class Timestream(object):
     def set_psestimator(self, psname):
         self.psname = psname
 
+    def _has_inflation(self):
+        return any(os.path.exists(self._inflfile(mi)) for mi in range(self.telescope.mmax + 1))
+
+    def flag_noise_bias(self, inflation=None):
+        """The noise bias (nbands,) that the flags add to sum_m q_m beyond the `bias` of fisher.hdf5 (DESIGN.md section
+        4.16).  The weighted m-mode estimate of flagged data is unbiased, but entry j = (frequency, slot, pair) of the
+        m-mode vector carries noise of variance noisepower_j d_{m,j} instead of the nominal noisepower_j
+        (`noise_inflation`), diagonal within an m.  With P_m the map the data takes, telescope -> SVD -> KL
+        (`project_vectors_telescope_to_svd_device`, which whitens by noisepower^-1/2, then
+        `project_vectors_svd_to_kl_device`), E[q_a(P n)] = sum_j noisepower_j d_j q_a(P e_j), so
+
+            delta b_a = sum_m sum_j noisepower_j (d_{m,j} - 1) q_a(P_m e_j).
+
+        The columns P_m e_j are the identity pushed through the two batched projections, in chunks under the estimator's
+        `ps_chunk_gb`; their q come from `q_estimator_batch(..., noise=False)`; the weighted sum is taken on the host.
+        Entries with d = 1 need no column and an m whose d are all 1 is skipped.  The m are shared over the ranks and the
+        result is summed over them.  `inflation`: a function m -> (nfreq, 2, npairs) used in place of the files.
+
+        Only the expectation of the estimate is corrected: the Fisher matrix and the error bars still assume nominal
+        noise, and the correlations between different m (which do not enter the expectation of a sum of per-m quadratic
+        forms) are ignored.  The band powers become unbiased, not minimum-variance."""
+        ps = self.manager.psestimators[self.psname]
+        had_bands = ps.clarray is not None
+        if not had_bands:
+            ps.genbands()
+        ctx = get_context()
+        kl, bt, tel = ps.kltrans, ps.kltrans.beamtransfer, self.telescope
+        nfreq, ntel = int(tel.nfreq), int(bt.ntel)
+        npower = bt._noisew() ** -2.0                                             # (nfreq, ntel): noisepower of entry j
+        L = int(tel.lmax) + 1
+        total = np.zeros(ps.nbands, dtype=np.float64)
+        for mi in parallel.partition(_ps_mlist(tel.mmax, self.no_m_zero)):
+            d = self.noise_inflation(mi) if inflation is None else inflation(mi)
+            wj = (npower * (np.asarray(d, dtype=np.float64).reshape(nfreq, ntel) - 1.0)).ravel()
+            cols = np.flatnonzero(wj)
+            nd = int(bt.ndof(mi))
+            if cols.size == 0 or nd == 0:
+                continue
+            per_col = 16.0 * (nfreq * ntel + 2 * L * nfreq + 4 * nd) + 8.0 * ps.nbands * (L / 4.0 + 1.0)
+            step = int(max(1, min(cols.size, 0.5 * ps.ps_chunk_gb * (1 << 30) // per_col)))
+            for c0 in range(0, cols.size, step):
+                cc = cols[c0 : c0 + step]
+                eye = ctx.zeros((1, nfreq * ntel, len(cc)), np.complex128)
+                eye[0, ctx.to_device(cc), ctx.to_device(np.arange(len(cc)))] = 1.0
+                svec, off = bt.project_vectors_telescope_to_svd_device([mi], eye.view(1, nfreq, ntel, len(cc)))
+                kvec, _ = kl.project_vectors_svd_to_kl_device([mi], svec, off=off[:1])
+                del eye, svec
+                if kvec.shape[0] == 0:
+                    break
+                q = ps.q_estimator_batch([mi], [kvec], noise=False)[0]            # (nbands, len(cc))
+                total += q[: ps.nbands] @ wj[cc]
+        if not had_bands:
+            ps.delbands()
+        return parallel.allreduce_sum(total)
+
     def powerspectrum(self):
-        """Band powers p = F^-1 (sum_m q_m - bias) of this timestream's KL m-modes, written to `ps_<psname>.hdf5`."""
+        """Band powers p = F^-1 (sum_m q_m - bias) of this timestream's KL m-modes, written to `ps_<psname>.hdf5`.
+
+        With `flag_noise_bias_correct` (default False; the key of the same name in a `timestreams:` entry of the
+        pipeline file) and inflation files next to the modes, `bias + flag_noise_bias()` is subtracted and the file gets
+        `flag_bias` (nbands).  The Fisher matrix and the errors written still assume nominal noise."""
         if os.path.exists(self._psfile):
             return None
         ps = self.manager.psestimators[self.psname]
@@ -547,9 +649,13 @@ class Timestream(object):
         qs = ps.q_estimator_batch(mine, [self.mmode_kl(mi) for mi in mine])
         qtotal = parallel.allreduce_sum(np.sum(qs, axis=0) if qs else np.zeros(ps.nbands))
         fisher, bias = ps.fisher_bias()
+        flag_bias = None
+        if self.flag_noise_bias_correct and self._has_inflation():
+            flag_bias = self.flag_noise_bias()
+            bias = bias + flag_bias
         powerspectrum = np.dot(np.linalg.inv(fisher), qtotal - bias)
         if parallel.rank0():
-            _write_ps(self._psfile, fisher, ps.band_power, powerspectrum)
+            _write_ps(self._psfile, fisher, ps.band_power, powerspectrum, flag_bias=flag_bias)
         ps.delbands()
         parallel.barrier()
         return powerspectrum
@@ -604,13 +710,19 @@ class _StepTimer(object):
 
 
 # ---- m-modes of flagged timestreams: the host statement -------------------------------------
-def mmodes_weighted_host(x, w, mmax, ridge=0.0):
+def mmodes_weighted_host(x, w, mmax, ridge=0.0, inflation=False):
     """Weighted least-squares m-modes in numpy, the oracle of `Context.mmode_transform_weighted`: x (nf, npairs, ntime)
     complex, w >= 0 broadcastable to it from (nf, npairs, ntime), (nf, ntime) or (ntime,).  Per (frequency, pair) the normal
     equations A a = b are built from the explicit Fourier matrix F[t, k] = e^{2 pi i k t / ntime}, k = -mmax .. mmax,
     A = F^H diag(w) F / ntime + ridge mean(w) I, b = F^H (w x) / ntime, and solved with a dense solver (LAPACK's LU: not
     the device's algorithm).  Returns (modes (mmax + 1, nf, 2, npairs) in the layout of the mode files, info (nf, npairs)
-    int32: 0 solved, -1 fewer than 2 mmax + 1 samples of weight > 0 with ridge = 0, or none at all — not solved, zeros)."""
+    int32: 0 solved, -1 fewer than 2 mmax + 1 samples of weight > 0 with ridge = 0, or none at all — not solved, zeros).
+
+    inflation=True: a third value, float64 (mmax + 1, nf, 2, npairs) in the layout of the modes, the diagonal of the dense
+    inverse `np.linalg.inv(A)` at k = +m (slot 0) and k = -m (slot 1): with circular white noise of per-sample variance
+    ntime * noisepower on the data, noisepower times it is the noise variance of the mode (exact for ridge = 0, an upper
+    bound for ridge > 0).  1.0 at (m = 0, slot 1); exactly 1 / w_0 on a row of constant weight w_0 with ridge = 0 (as the
+    device, whose shortcut this restates); 0.0 on rows that are not solved."""
     x = np.asarray(x, dtype=np.complex128)
     if x.ndim != 3:
         raise ValueError("mmodes_weighted_host: x (nf, npairs, ntime) expected")
@@ -629,6 +741,8 @@ def mmodes_weighted_host(x, w, mmax, ridge=0.0):
     F = np.exp(2j * np.pi * ((np.arange(ntime)[:, None] * k[None, :]) % ntime) / ntime)       # (ntime, N)
     modes = np.zeros((mmax + 1, nf, 2, npairs), dtype=np.complex128)
     info = np.zeros((nf, npairs), dtype=np.int32)
+    infl = np.zeros((mmax + 1, nf, 2, npairs), dtype=np.float64)
+    infl[0, :, 1] = 1.0
     for fi in range(nf):
         for p in range(npairs):
             wr = w[fi, p]
@@ -639,7 +753,51 @@ def mmodes_weighted_host(x, w, mmax, ridge=0.0):
             a = np.linalg.solve(A, F.conj().T @ (wr * x[fi, p]) / ntime)
             modes[:, fi, 0, p] = a[mmax:]
             modes[1:, fi, 1, p] = a[:mmax][::-1].conj()
-    return modes, info
+            if inflation:
+                if wr.min() == wr.max():                                  # A = w_0 (1 + ridge) I exactly
+                    d = np.full(N, 1.0 / (wr[0] + ridge * wr[0]))
+                else:
+                    d = np.linalg.inv(A).diagonal().real
+                infl[:, fi, 0, p] = d[mmax:]
+                infl[1:, fi, 1, p] = d[:mmax][::-1]
+    return (modes, info, infl) if inflation else (modes, info)
+
+
+def toeplitz_inverse_diag_host(col):
+    """The diagonal of the inverse of a Hermitian positive-definite Toeplitz matrix as `dm_toeplitz_solve_diag` computes
+    it, restated in numpy (not its summation order): the recursion of `toeplitz_levinson_host` for f and beta, then the
+    Gohberg-Semencul prefix sum d_i = sum_{j <= i} (|f_j|^2 - |f_{n-j}|^2) / (beta c_0), f_n := 0.  col (n,) or (batch, n).
+    Returns (d float64 of col's shape, info int32 per system: 0, the failing step k, or n for c_0 <= 0; d = 0 on failure)."""
+    col = np.asarray(col, dtype=np.complex128)
+    single = col.ndim == 1
+    cols = col[None] if single else col
+    batch, n = cols.shape
+    ds = np.zeros((batch, n), dtype=np.float64)
+    info = np.zeros(batch, dtype=np.int32)
+    for s in range(batch):
+        c0 = cols[s, 0].real
+        if not (c0 > 0 and np.isfinite(c0)):
+            info[s] = n
+            continue
+        r = cols[s] / c0
+        r[0] = 1.0
+        f = np.zeros(n, dtype=np.complex128)
+        f[0] = 1.0
+        beta = 1.0
+        for k in range(1, n):
+            gamma = -np.dot(r[k:0:-1], f[:k]) / beta
+            f[: k + 1] = f[: k + 1] + gamma * f[k::-1].conj()
+            beta *= 1.0 - abs(gamma) ** 2
+            if not (beta > 0 and np.isfinite(beta)):
+                info[s] = k
+                break
+        if info[s]:
+            continue
+        p = f.real**2 + f.imag**2
+        g = p.copy()
+        g[1:] -= p[:0:-1]                                        # |f_{n-i}|^2, i = 1 .. n - 1
+        ds[s] = np.cumsum(g) / (beta * c0)
+    return (ds[0], info[0]) if single else (ds, info)
 
 
 def toeplitz_levinson_host(col, b):
@@ -703,7 +861,7 @@ def _ps_mlist(mmax, no_m_zero):
     return list(range(1 if no_m_zero else 0, mmax + 1))
 
 
-def _write_ps(psfile, fisher, band_power, powerspectrum):
+def _write_ps(psfile, fisher, band_power, powerspectrum, flag_bias=None):
     cv = np.linalg.inv(fisher)
     err = cv.diagonal() ** 0.5
     with storage.File(psfile, "w") as f:
@@ -713,6 +871,8 @@ def _write_ps(psfile, fisher, band_power, powerspectrum):
         f.create_dataset("correlation", data=cv / np.outer(err, err))
         f.create_dataset("bandpower", data=band_power)
         f.create_dataset("powerspectrum", data=powerspectrum)
+        if flag_bias is not None:
+            f.create_dataset("flag_bias", data=flag_bias)
 
 
 def cross_powerspectrum(timestreams, psname, psfile):

@@ -680,6 +680,20 @@ int dm_toeplitz_solve(dm_ctx* ctx, int n, int nrhs, int batch, const void* col_d
  * not even one right-hand side fits (n > 3410) or n < 1.  No counterpart in the reference. */
 int dm_toeplitz_max_rhs(int n);
 
+/* dm_toeplitz_solve_diag: dm_toeplitz_solve (the same solutions and info, bit for bit) that also writes the diagonal of
+ * the inverse of every system as given:
+ *   diag_dev  (batch, n) f64: d_i = (T_s^-1)[i, i].  After the last step of the recursion f / (beta c_0) is the first
+ *             column of the inverse, and the Gohberg-Semencul formula gives d_i = sum_{j <= i} (|f_j|^2 - |f_{n-j}|^2) /
+ *             (beta c_0) with f_n := 0: one prefix sum over values kept in LDS, whose order is a function of n alone (the
+ *             same bits alone, in any batch and at any position).  A system with info != 0 gets a diagonal of zeros.
+ * nrhs = 0 is allowed and gives the diagonal alone; b_dev is then not looked at (null or not) and the LDS need is that of
+ * r, f and the reduction rows, 32 n + 80 bytes.  Refused before any launch (dm_last_error): n < 1, nrhs < 0,
+ * nrhs > dm_toeplitz_max_rhs(n), an order whose LDS need exceeds a CU, batch < 0, a null col, diag or info (or b with
+ * nrhs > 0) with batch > 0.  With noise of per-sample variance ntime * noisepower on the data of a weighted m-mode
+ * estimate, noisepower * d is the noise variance of the estimated modes.  No counterpart in the reference. */
+int dm_toeplitz_solve_diag(dm_ctx* ctx, int n, int nrhs, int batch, const void* col_dev, void* b_dev, double* diag_dev,
+                           int* info_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,23 @@ int main() {
   CHECK(dm_toeplitz_check(4, 1, 0, nullptr, nullptr, nullptr).empty());   // batch = 0 is a no-op
   CHECK(dm_toeplitz_check(1, 1, 2147483647, p, p, p).empty());
   CHECK(dm_toeplitz_check(257, 8, 100000, p, p, p).empty());
+  // dm_toeplitz_solve_diag: nrhs = 0 allowed (b null or not), diag required, the same limits otherwise
+  CHECK(dm_toeplitz_check_diag(4, 0, 1, p, nullptr, p, p).empty());
+  CHECK(dm_toeplitz_check_diag(4, 0, 1, p, p, p, p).empty());
+  CHECK(dm_toeplitz_check_diag(4, 1, 1, p, p, p, p).empty());
+  CHECK(!dm_toeplitz_check_diag(4, -1, 1, p, p, p, p).empty());
+  CHECK(!dm_toeplitz_check_diag(4, 1, 1, p, nullptr, p, p).empty());
+  CHECK(!dm_toeplitz_check_diag(4, 0, 1, p, p, nullptr, p).empty());
+  CHECK(!dm_toeplitz_check_diag(4, 0, 1, nullptr, p, p, p).empty());
+  CHECK(!dm_toeplitz_check_diag(4, 0, 1, p, p, p, nullptr).empty());
+  CHECK(!dm_toeplitz_check_diag(0, 0, 1, p, p, p, p).empty());
+  CHECK(!dm_toeplitz_check_diag(4, 0, -1, p, p, p, p).empty());
+  CHECK(dm_toeplitz_check_diag(4, 0, 0, nullptr, nullptr, nullptr, nullptr).empty());
+  CHECK(!dm_toeplitz_check_diag(4, dm_toeplitz_max_rhs_of(4) + 1, 1, p, p, p, p).empty());
+  CHECK(dm_toeplitz_check_diag(5117, 0, 1, p, nullptr, p, p).empty() && dm_toeplitz_lds(5117, 0) <= DM_TOEPLITZ_LDS_BYTES);
+  CHECK(!dm_toeplitz_check_diag(5118, 0, 1, p, nullptr, p, p).empty() && dm_toeplitz_lds(5118, 0) > DM_TOEPLITZ_LDS_BYTES);
+  CHECK(!dm_toeplitz_check_diag(2147483647, 0, 1, p, nullptr, p, p).empty());
+  CHECK(!dm_toeplitz_check_diag(4, 2147483647, 1, p, p, p, p).empty());
   std::printf(failures ? "%d checks failed\n" : "toeplitz argument checks ok\n", failures);
   return failures ? EXIT_FAILURE : EXIT_SUCCESS;
 }
