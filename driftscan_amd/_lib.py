@@ -59,6 +59,16 @@ class JacobiOptions(ctypes.Structure):
                 ("subspace_margin", c_dbl)]
 
 
+class ZpotrfProblem(ctypes.Structure):
+    """dm_zpotrf_problem of include/driftmi.h."""
+    _fields_ = [("A", c_vp), ("n", c_int), ("ld", c_int)]
+
+
+class ZtrsmProblem(ctypes.Structure):
+    """dm_ztrsm_problem of include/driftmi.h."""
+    _fields_ = [("L", c_vp), ("ldl", c_int), ("n", c_int), ("B", c_vp), ("ldb", c_int), ("nrhs", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/driftmi.h one to one
 SIGNATURES = {
     "dm_ctx_create": (c_int, [c_int, c_sz, c_vp, ctypes.POINTER(c_vp)]),
@@ -83,6 +93,10 @@ SIGNATURES = {
     "dm_zpotrf_batched": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, ctypes.POINTER(c_int)]),
     "dm_ztrsm_left_lower_batched": (
         c_int, [c_vp, c_int, c_int, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int]),
+    "dm_zpotrf_problems": (c_int, [c_vp, c_int, ctypes.POINTER(ZpotrfProblem), ctypes.POINTER(c_int)]),
+    "dm_ztrsm_problems": (c_int, [c_vp, c_int, ctypes.POINTER(ZtrsmProblem), c_int, c_int]),
+    "dm_zpotrf_problems_check": (c_int, [c_int, ctypes.POINTER(ZpotrfProblem)]),
+    "dm_ztrsm_problems_check": (c_int, [c_int, ctypes.POINTER(ZtrsmProblem), c_int, c_int]),
     "dm_jacobi_rows_batched": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_i64, c_int, c_vp, ctypes.POINTER(c_int)]),
     "dm_jacobi_rows_problems": (
@@ -297,6 +311,62 @@ def zgemm_plan_info(problems):
             for o in out[:nl]]
 
 
+# ---- Cholesky and triangular solves for a ragged list of problems (dm_zpotrf_problems / dm_ztrsm_problems) ----------------
+# A factorisation problem is a dict: n, ld and a_off (element offset of the matrix in its tensor, 0); a solve: n, nrhs,
+# ldl, ldb, l_off (0), b_off (0).  The `Context` methods also want the tensors (A; L and B).  Without tensors (the host
+# checks) a matrix counts as present unless the dict says a_null / l_null / b_null.
+def zpotrf_check_view(p, nA):
+    """Host arithmetic only: raise ValueError unless the n x n window (leading dimension ld) at a_off lies inside a
+    buffer of nA elements.  Sizes the library refuses (ld < n) are left to the library."""
+    n, ld, off = int(p["n"]), int(p["ld"]), int(p.get("a_off", 0))
+    if min(n, ld, off) < 0:
+        raise ValueError("zpotrf_problems: negative size, leading dimension or offset")
+    if n > 0 and off + (n - 1) * ld + n > nA:
+        raise ValueError("zpotrf_problems: the matrix reaches outside its tensor")
+
+
+def ztrsm_check_views(p, nL, nB):
+    """The same for a solve: the n x n window of L (ldl, l_off) and the n x nrhs window of B (ldb, b_off)."""
+    n, nrhs, ldl, ldb = (int(p[k]) for k in ("n", "nrhs", "ldl", "ldb"))
+    l_off, b_off = int(p.get("l_off", 0)), int(p.get("b_off", 0))
+    if min(n, nrhs, ldl, ldb, l_off, b_off) < 0:
+        raise ValueError("ztrsm_problems: negative size, leading dimension or offset")
+    if n == 0 or nrhs == 0:
+        return
+    if l_off + (n - 1) * ldl + n > nL:
+        raise ValueError("ztrsm_problems: L reaches outside its tensor")
+    if b_off + (n - 1) * ldb + nrhs > nB:
+        raise ValueError("ztrsm_problems: B reaches outside its tensor")
+
+
+def _zpotrf_records(problems, ptrs=None):
+    arr = (ZpotrfProblem * max(len(problems), 1))()
+    for i, (q, p) in enumerate(zip(arr, problems)):
+        q.A = (ptrs[i] if ptrs is not None else (0 if p.get("a_null") else 16)) or None
+        q.n, q.ld = int(p["n"]), int(p["ld"])
+    return arr
+
+
+def _ztrsm_records(problems, ptrs=None):
+    arr = (ZtrsmProblem * max(len(problems), 1))()
+    for i, (q, p) in enumerate(zip(arr, problems)):
+        pl, pb = ptrs[i] if ptrs is not None else (0 if p.get("l_null") else 16, 0 if p.get("b_null") else 16)
+        q.L, q.B = pl or None, pb or None
+        q.ldl, q.n, q.ldb, q.nrhs = int(p["ldl"]), int(p["n"]), int(p["ldb"]), int(p["nrhs"])
+    return arr
+
+
+def zpotrf_problems_check(problems):
+    """Status of dm_zpotrf_problems_check for a list of problem dicts (0 or DM_EARG = -1; needs no GPU)."""
+    return int(load().dm_zpotrf_problems_check(len(problems), _zpotrf_records(problems)))
+
+
+def ztrsm_problems_check(problems, conjtrans=False, upper_only=False):
+    """Status of dm_ztrsm_problems_check for a list of problem dicts (0 or DM_EARG = -1; needs no GPU)."""
+    return int(load().dm_ztrsm_problems_check(len(problems), _ztrsm_records(problems), int(bool(conjtrans)),
+                                              int(bool(upper_only))))
+
+
 class Context(object):
     """One per GPU / process. Binds to torch's current stream on that device so
     that torch.cuda events bracket the work."""
@@ -459,6 +529,41 @@ class Context(object):
     def ztrsm(self, L, B, n, nrhs, ldl, ldb, conjtrans=False, strideL=0, strideB=0, batch=1):
         self.check(self.lib.dm_ztrsm_left_lower_batched(self.h, n, nrhs, self.ptr(L), ldl, strideL, self.ptr(B), ldb,
                                                         strideB, int(conjtrans), batch), "dm_ztrsm")
+
+    def _c128_device(self, t, what):
+        if not (t.is_complex() and t.element_size() == 16 and t.is_contiguous() and t.is_cuda):
+            raise ValueError("%s: contiguous complex128 device tensors expected" % what)
+
+    def zpotrf_problems(self, problems):
+        """Lower Cholesky factors of a ragged list of matrices in one chain of launches (dm_zpotrf_problems, exposed for
+        the parity tests).  Each problem is a dict with the device tensor A and n, ld, a_off (see `zpotrf_check_view`,
+        which every problem passes first: a wrong offset would be an out-of-bounds access on the device).  Returns the
+        `info` of every problem (0, or the 1-based index of the first failing pivot)."""
+        n = len(problems)
+        ptrs = []
+        for p in problems:
+            self._c128_device(p["A"], "zpotrf_problems")
+            zpotrf_check_view(p, int(p["A"].numel()))
+            ptrs.append(p["A"].data_ptr() + 16 * int(p.get("a_off", 0)) if int(p["n"]) > 0 else 0)
+        info = (c_int * max(n, 1))()
+        self.check(self.lib.dm_zpotrf_problems(self.h, n, _zpotrf_records(problems, ptrs), info), "dm_zpotrf_problems")
+        return np.array(info[:n], dtype=np.int64)
+
+    def ztrsm_problems(self, problems, conjtrans=False, upper_only=False):
+        """L X = B (or L^H X = B) for a ragged list of problems in one chain of launches (dm_ztrsm_problems, exposed for
+        the parity tests).  Each problem is a dict with the device tensors L and B and n, nrhs, ldl, ldb, l_off, b_off
+        (see `ztrsm_check_views`, which every problem passes first).  upper_only: forward solves with nrhs == n whose
+        result is wanted on and above the diagonal only."""
+        ptrs = []
+        for p in problems:
+            self._c128_device(p["L"], "ztrsm_problems")
+            self._c128_device(p["B"], "ztrsm_problems")
+            ztrsm_check_views(p, int(p["L"].numel()), int(p["B"].numel()))
+            full = int(p["n"]) > 0 and int(p["nrhs"]) > 0
+            ptrs.append((p["L"].data_ptr() + 16 * int(p.get("l_off", 0)) if full else 0,
+                         p["B"].data_ptr() + 16 * int(p.get("b_off", 0)) if full else 0))
+        self.check(self.lib.dm_ztrsm_problems(self.h, len(problems), _ztrsm_records(problems, ptrs),
+                                              int(bool(conjtrans)), int(bool(upper_only))), "dm_ztrsm_problems")
 
     def jacobi_rows(self, Z, rows, cols, gc0, gc1, ld, stride=0, batch=1):
         sigma = self.empty((batch, max(rows, 1)), np.float64)

@@ -156,6 +156,7 @@ int dm_zgemm_plan_info(int nprob, const dm_zgemm_problem_ex* probs, int max_laun
 int dm_zpotrf_batched(dm_ctx* ctx, int n, void* A, int ld, int64_t stride, int batch, int* info_host) {
   if (!ctx) return DM_EARG;
   DM_ARG(ctx, n >= 0 && batch >= 0 && A && info_host);
+  DM_ARG(ctx, ld >= n);  // a shorter row would put the factor outside the matrix
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
   const size_t mark = ws_scope__.mark;
   std::vector<dm_mat> mats(batch);
@@ -172,6 +173,7 @@ int dm_ztrsm_left_lower_batched(dm_ctx* ctx, int n, int nrhs, const void* L, int
                                 int ldb, int64_t strideB, int conjtrans, int batch) {
   if (!ctx) return DM_EARG;
   DM_ARG(ctx, n >= 0 && nrhs >= 0 && batch >= 0 && L && B);
+  DM_ARG(ctx, ldl >= n && ldb >= nrhs);
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
   const size_t mark = ws_scope__.mark;
   std::vector<dm_trsm_problem> ps(batch);
@@ -181,6 +183,55 @@ int dm_ztrsm_left_lower_batched(dm_ctx* ctx, int n, int nrhs, const void* L, int
   int rc = dm_trsm_left_lower_batched(ctx, ps, conjtrans != 0);
   dm_ws_release(ctx, mark);
   return rc;
+}
+
+// ---- Cholesky and triangular solves for a ragged list of problems (exposed for the parity tests) ----
+int dm_zpotrf_problems_check(int nprob, const dm_zpotrf_problem* probs) {
+  if (nprob < 0 || (nprob > 0 && !probs)) return DM_EARG;
+  for (int i = 0; i < nprob; ++i) {
+    const dm_zpotrf_problem& p = probs[i];
+    if (p.n < 0 || p.ld < 0) return DM_EARG;
+    if (p.n > 0 && (p.ld < p.n || !p.A)) return DM_EARG;
+  }
+  return DM_OK;
+}
+
+int dm_ztrsm_problems_check(int nprob, const dm_ztrsm_problem* probs, int conjtrans, int upper_only) {
+  if (nprob < 0 || (nprob > 0 && !probs)) return DM_EARG;
+  if (upper_only && conjtrans) return DM_EARG;
+  for (int i = 0; i < nprob; ++i) {
+    const dm_ztrsm_problem& p = probs[i];
+    if (p.n < 0 || p.nrhs < 0 || p.ldl < 0 || p.ldb < 0) return DM_EARG;
+    if (p.n > 0 && p.ldl < p.n) return DM_EARG;
+    if (p.nrhs > 0 && p.ldb < p.nrhs) return DM_EARG;
+    if (p.n > 0 && p.nrhs > 0 && (!p.L || !p.B)) return DM_EARG;
+    if (upper_only && p.nrhs != p.n) return DM_EARG;
+  }
+  return DM_OK;
+}
+
+int dm_zpotrf_problems(dm_ctx* ctx, int nprob, const dm_zpotrf_problem* probs, int* info_host) {
+  if (!ctx) return DM_EARG;
+  DM_ARG(ctx, dm_zpotrf_problems_check(nprob, probs) == DM_OK);
+  DM_ARG(ctx, nprob == 0 || info_host);
+  dm_ws_scope ws_scope__(ctx);  // releases on every return path
+  std::vector<dm_mat> mats(nprob);
+  for (int i = 0; i < nprob; ++i) mats[i] = dm_mat{reinterpret_cast<cplx*>(probs[i].A), probs[i].ld, probs[i].n};
+  int* info_dev = dm_ws_alloc_t<int>(ctx, nprob > 0 ? nprob : 1);
+  if (!info_dev) return DM_ENOMEM;
+  DM_TRY(dm_potrf_batched(ctx, mats, info_dev));
+  return dm_download(ctx, info_host, info_dev, sizeof(int) * nprob);
+}
+
+int dm_ztrsm_problems(dm_ctx* ctx, int nprob, const dm_ztrsm_problem* probs, int conjtrans, int upper_only) {
+  if (!ctx) return DM_EARG;
+  DM_ARG(ctx, dm_ztrsm_problems_check(nprob, probs, conjtrans, upper_only) == DM_OK);
+  dm_ws_scope ws_scope__(ctx);  // releases on every return path
+  std::vector<dm_trsm_problem> ps(nprob);
+  for (int i = 0; i < nprob; ++i)
+    ps[i] = dm_trsm_problem{reinterpret_cast<const cplx*>(probs[i].L), probs[i].ldl, probs[i].n,
+                            reinterpret_cast<cplx*>(probs[i].B), probs[i].ldb, probs[i].nrhs};
+  return dm_trsm_left_lower_batched(ctx, ps, conjtrans != 0, upper_only != 0);
 }
 
 int dm_jacobi_rows_batched(dm_ctx* ctx, int rows, int cols, int gc0, int gc1, void* Z, int ld, int64_t stride,

@@ -146,6 +146,8 @@ __global__ __launch_bounds__(256) void diag_solve_kernel(const trsm_desc* __rest
     k0 = (pn - 1 - (s - (nblk - pn))) * NB;
   }
   if (k0 >= d.n || k0 < 0) return;
+  // no column of this workgroup belongs to the problem: nothing to do, and with nrhs = 0 its L may be a null pointer
+  if ((int)blockIdx.x * 256 >= d.nrhs) return;   // (uniform over the workgroup)
   const int nb = min(NB, d.n - k0);
   const int col = blockIdx.x * 256 + threadIdx.x;
   // upper_only: only the columns >= the first row of the 64-row super block are wanted (and valid)
@@ -205,6 +207,7 @@ int dm_potrf_batched(dm_ctx* ctx, const std::vector<dm_mat>& mats, int* info_dev
   chol_desc* dd = dm_ws_upload(ctx, ds);
   if (!dd) return DM_ENOMEM;
   DM_HIP(ctx, hipMemsetAsync(info_dev, 0, sizeof(int) * nbatch, ctx->stream));
+  if (maxn == 0) return DM_OK;  // only empty matrices: info = 0, and zero_upper_kernel would get an empty grid
   // Two-level blocking: the LDS factor/substitution kernels work on 32-wide blocks, but the big
   // trailing update runs once per 64 columns so that the MFMA GEMM sees K = 64 and full tiles.
   // (two passes: the descriptors of all updates are recorded and sent in one copy, then everything is launched)
@@ -359,6 +362,8 @@ int dm_trsm_plan_build(dm_ctx* ctx, const std::vector<dm_trsm_problem>& probs, b
   // row block i then needs the rows j < i at columns >= i, which lie above the diagonal too, so
   // every update and substitution simply starts at the first column of its row block (1/3 of the flops).
   if (conjtrans) upper_only = false;
+  if (upper_only)
+    for (const auto& P : probs) DM_ARG(ctx, P.nrhs == P.n);
   plan.probs = probs;
   plan.conjtrans = conjtrans;
   plan.upper_only = upper_only;

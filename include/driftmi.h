@@ -168,6 +168,38 @@ int dm_zpotrf_batched(dm_ctx* ctx, int n, void* A_dev, int ld, int64_t stride, i
 int dm_ztrsm_left_lower_batched(dm_ctx* ctx, int n, int nrhs, const void* L_dev, int ldl, int64_t strideL,
                                 void* B_dev, int ldb, int64_t strideB, int conjtrans, int batch);
 
+/* The same two engines for a ragged list of problems, as dm_eigh_gen hands them (exposed for the parity tests):
+ * every problem has its own address, size and leading dimensions, and all of them share each launch.
+ * Factorisation: only the lower triangle of A is read (of the diagonal its real part); on return the lower triangle
+ * holds L with a real positive diagonal, the strictly upper triangle of the n x n window is zero, and nothing outside
+ * that window is written.  info_host[i] = 0, or the 1-based index of the first pivot that is not a positive finite
+ * number (a NaN or an Inf counts as a failure there); the window of a failed problem holds no usable factor, the
+ * other problems of the launch are not affected.  Synchronises. */
+typedef struct dm_zpotrf_problem {
+  void* A; /* device c128, row-major n x n, leading dimension ld >= n */
+  int n, ld;
+} dm_zpotrf_problem;
+int dm_zpotrf_problems(dm_ctx* ctx, int nprob, const dm_zpotrf_problem* probs_host, int* info_host);
+
+/* Solves: L X = B (conjtrans = 0) or L^H X = B (conjtrans = 1), X overwrites the n x nrhs window of B; of L only the
+ * lower triangle is read (of its diagonal the real part), and nothing outside the window of B is written.
+ * upper_only (forward solves with nrhs == n only): X is wanted on and above its diagonal only; the entries below it
+ * come back undefined (they stay inside the window).  Returns when the work is queued. */
+typedef struct dm_ztrsm_problem {
+  const void* L; /* device c128, row-major n x n, leading dimension ldl >= n */
+  int ldl, n;
+  void* B;       /* device c128, row-major n x nrhs, leading dimension ldb >= nrhs */
+  int ldb, nrhs;
+} dm_ztrsm_problem;
+int dm_ztrsm_problems(dm_ctx* ctx, int nprob, const dm_ztrsm_problem* probs_host, int conjtrans, int upper_only);
+
+/* The argument checks of the two entries above on their own.  Host only: no context, no device, and no pointer of a
+ * problem is followed (only NULL or not).  DM_EARG for a negative size, ld < n or ldl < n where n > 0, ldb < nrhs where
+ * nrhs > 0, a NULL matrix of a problem that is not empty (n > 0; for a solve n > 0 and nrhs > 0), upper_only together
+ * with conjtrans, or upper_only with nrhs != n; DM_OK otherwise. */
+int dm_zpotrf_problems_check(int nprob, const dm_zpotrf_problem* probs_host);
+int dm_ztrsm_problems_check(int nprob, const dm_ztrsm_problem* probs_host, int conjtrans, int upper_only);
+
 /* One-sided block-Jacobi SVD of `batch` row-major matrices (rows x cols, ld,
  * `stride` elements apart): the rows of each matrix are unitarily mixed in place
  * until mutually orthogonal with respect to the columns [gc0, gc1) and sorted by
