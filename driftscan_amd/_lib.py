@@ -204,6 +204,12 @@ SIGNATURES = {
     "dm_toeplitz_solve": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "dm_toeplitz_max_rhs": (c_int, [c_int]),
     "dm_toeplitz_solve_diag": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "dm_vis_stack": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp,
+                c_vp, c_vp, ctypes.POINTER(c_dbl), c_vp, c_vp, c_i64, c_i64]),
+    "dm_vis_expand": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp,
+                c_vp, c_i64, c_i64, c_int]),
 }
 
 _lib = None
@@ -930,6 +936,120 @@ def _ts_gain_apply(self, g, class_off, members, sky, out=None, accumulate=False)
 Context.ts_gain_coeff = _ts_gain_coeff
 Context.ts_gain_compose = _ts_gain_compose
 Context.ts_gain_apply = _ts_gain_apply
+
+
+def _rstride_of(t, complex_):
+    """`_rstride` for a (nreal, nf, rows, ntime) tensor of complex128 (complex_) or float64 elements."""
+    if not (hasattr(t, "data_ptr") and t.dim() == 4 and t.is_complex() == complex_
+            and t.element_size() == (16 if complex_ else 8)):
+        return None
+    nreal, nf, rows, ntime = (int(v) for v in t.shape)
+    if t.numel() and tuple(t.stride())[1:] != (rows * ntime, ntime, 1) and not t[0].is_contiguous():
+        return None
+    rs = int(t.stride(0)) if nreal > 1 else nf * rows * ntime
+    return rs if rs >= nf * rows * ntime else None
+
+
+def _class_table(who, class_off, members):
+    off, offp = _iarr(class_off)
+    mem, memp = _iarr(np.asarray(members, dtype=np.int32).reshape(-1, 2))
+    if off.ndim != 1 or off.shape[0] < 1 or mem.shape[0] != int(off[-1]):
+        raise ValueError("%s: class_off (npairs + 1) and members (class_off[-1], 2) expected" % who)
+    return off, offp, mem, memp
+
+
+def _vis_stack(self, vis, class_off, members, w=None, g=None, feed_weight=None, out=None, wout=None):
+    """Stack unstacked (per-feed-pair) visibilities into unique baselines (dm_vis_stack, DESIGN.md section 4.17;
+    `timestream.vis_stack_host` restates it): with the class table of `TransitTelescope.redundant_pairs`,
+
+        N = sum_{m in c} w_m conj(g_i) g_j V_m,  D = sum_{m in c} w_m |g_i|^2 |g_j|^2,  out = N / D,  wout = D / n_c
+
+    and both 0 where D == 0.  vis (nreal, nf, nmem, ntime) complex128, contiguous or a frequency slice of a contiguous
+    array; w float64 >= 0 (1 or nreal, nf, nmem, ntime), flags or inverse variances relative to the nominal per-pair
+    noise; g (1 or nreal, nf, nfeed, ntime) complex128 calibration gains; feed_weight (nfeed) >= 0 on the host (0: a dead
+    feed), the weight of a member is w_m feed_weight[i] feed_weight[j].  Returns (out complex128, wout float64), both
+    (nreal, nf, npairs, ntime) with one stride between realisations.  wout is the `weight` of section 4.16: the inverse
+    noise variance of out relative to the nominal one of the stacked baseline, exactly 1.0 for a complete class with
+    unit weights and no gains.  The bits of a class do not depend on the batch it is stacked in."""
+    rs = _rstride_of(vis, True)
+    if rs is None:
+        raise ValueError("vis_stack: complex128 tensor vis (nreal, nf, nmem, ntime) expected")
+    nreal, nf, nmem, ntime = (int(v) for v in vis.shape)
+    off, offp, mem, memp = _class_table("vis_stack", class_off, members)
+    npairs = off.shape[0] - 1
+    if mem.shape[0] != nmem:
+        raise ValueError("vis_stack: vis has %d rows, the table %d members" % (nmem, mem.shape[0]))
+    w_nreal = g_nreal = 1
+    nfeed = int(mem.max()) + 1 if mem.size else 0
+    if w is not None:
+        if not (hasattr(w, "data_ptr") and w.dim() == 4 and not w.is_complex() and w.element_size() == 8
+                and w.is_contiguous() and tuple(w.shape)[1:] == (nf, nmem, ntime) and int(w.shape[0]) in (1, nreal)):
+            raise ValueError("vis_stack: w must be a contiguous float64 tensor (1 or nreal, nf, nmem, ntime)")
+        w_nreal = int(w.shape[0])
+    if g is not None:
+        if not (_is_c128(g) and g.dim() == 4 and int(g.shape[1]) == nf and int(g.shape[3]) == ntime
+                and int(g.shape[0]) in (1, nreal)):
+            raise ValueError("vis_stack: g must be a contiguous complex128 tensor (1 or nreal, nf, nfeed, ntime)")
+        g_nreal, nfeed = int(g.shape[0]), int(g.shape[2])
+    fwp = None
+    if feed_weight is not None:
+        fw = np.ascontiguousarray(feed_weight, dtype=np.float64)
+        if fw.ndim != 1 or (g is not None and fw.shape[0] != nfeed) or fw.shape[0] < nfeed:
+            raise ValueError("vis_stack: feed_weight must have one entry per feed")
+        nfeed = int(fw.shape[0])
+        fwp = fw.ctypes.data_as(ctypes.POINTER(c_dbl))
+    if out is None:
+        out = self.empty((nreal, nf, npairs, ntime), np.complex128)
+    if wout is None:
+        wout = self.empty(tuple(out.shape), np.float64)
+        if nreal > 1 and out.stride(0) != wout.stride(0):
+            wout = self.torch.empty_strided(tuple(out.shape), tuple(out.stride()), dtype=self.torch.float64, device=out.device)
+    ors = _rstride_of(out, True)
+    if (ors is None or tuple(out.shape) != (nreal, nf, npairs, ntime) or tuple(wout.shape) != tuple(out.shape)
+            or _rstride_of(wout, False) != ors):
+        raise ValueError("vis_stack: out (complex128) and wout (float64) must be (nreal, nf, npairs, ntime) tensors with "
+                         "one stride between realisations")
+    rc = self.lib.dm_vis_stack(self.h, nreal, w_nreal, g_nreal, nf, nfeed, npairs, ntime, offp, memp, self.ptr(vis),
+                               self.ptr(w), self.ptr(g), fwp, self.ptr(out), self.ptr(wout), rs, ors)
+    self.check(rc, "dm_vis_stack")
+    return out, wout
+
+
+def _vis_expand(self, sky, class_off, members, g=None, out=None, accumulate=False):
+    """A stacked sky spread over the feed pairs (dm_vis_expand; `timestream.vis_expand_host`
+    restates it): out[r, f, m, t] (+)= g_i conj(g_j) sky[r, f, c(m), t] for member m = (i, j) of class c(m).  sky
+    (nreal, nf, npairs, ntime) and out (nreal, nf, nmem, ntime) complex128, contiguous or frequency slices of contiguous
+    arrays; g (1 or nreal, nf, nfeed, ntime) or None (the class row is copied).  accumulate=True adds to what out holds:
+    the noise `ts_noise` drew there at the per-member level, so the gains multiply the sky part only."""
+    rs = _rstride_of(sky, True)
+    if rs is None:
+        raise ValueError("vis_expand: complex128 tensor sky (nreal, nf, npairs, ntime) expected")
+    nreal, nf, npairs, ntime = (int(v) for v in sky.shape)
+    off, offp, mem, memp = _class_table("vis_expand", class_off, members)
+    if off.shape[0] != npairs + 1:
+        raise ValueError("vis_expand: sky has %d rows, the table %d classes" % (npairs, off.shape[0] - 1))
+    nmem = mem.shape[0]
+    g_nreal, nfeed = 1, (int(mem.max()) + 1 if mem.size else 0)
+    if g is not None:
+        if not (_is_c128(g) and g.dim() == 4 and int(g.shape[1]) == nf and int(g.shape[3]) == ntime
+                and int(g.shape[0]) in (1, nreal)):
+            raise ValueError("vis_expand: g must be a contiguous complex128 tensor (1 or nreal, nf, nfeed, ntime)")
+        g_nreal, nfeed = int(g.shape[0]), int(g.shape[2])
+    if out is None:
+        if accumulate:
+            raise ValueError("vis_expand: accumulate needs the buffer to add to")
+        out = self.empty((nreal, nf, nmem, ntime), np.complex128)
+    ors = _rstride_of(out, True)
+    if ors is None or tuple(out.shape) != (nreal, nf, nmem, ntime):
+        raise ValueError("vis_expand: out must be a complex128 tensor (nreal, nf, nmem, ntime)")
+    rc = self.lib.dm_vis_expand(self.h, nreal, g_nreal, nf, nfeed, npairs, ntime, offp, memp, self.ptr(g), self.ptr(sky),
+                                self.ptr(out), rs, ors, int(bool(accumulate)))
+    self.check(rc, "dm_vis_expand")
+    return out
+
+
+Context.vis_stack = _vis_stack
+Context.vis_expand = _vis_expand
 
 
 def _toeplitz_max_rhs(self, n):

@@ -5,7 +5,11 @@ sections — ``config`` (the properties below), ``timestreams`` (entries with ``
 ``output_directory``, ``mmode_ridge`` (this package: the ridge of the weighted m-modes of flagged data),
 ``flag_noise_bias_correct`` (this package: ``powerspectrum`` also subtracts the noise bias the flags add) and a ``simulate``
 block of arguments for ``timestream.simulate`` plus its ``product_directory``;
-the files of its ``maps`` and ``sources`` lists go through ``fixpath``)
+the files of its ``maps`` and ``sources`` lists go through ``fixpath``; with ``unstacked: true`` the block goes to
+``timestream.simulate_unstacked`` instead — one realisation of the device route of ``simulate_ensemble``, one row per feed
+pair; such an entry is kept in ``unstacked``, apart from the timestreams the stages run on — and an entry with
+``stack_from: {directory, calibrate: file|none, dead_feeds: [...]}`` is made from such a directory by
+``timestream.stack_baselines`` before the m-modes, when its own directory does not exist yet)
 and optionally ``crosspower`` (entries with ``psname``, ``klname``, ``timestreams``, ``psfile``) — the same defaults,
 exceptions and methods.  Two deliberate differences:
 
@@ -64,6 +68,8 @@ class PipelineManager(config.Reader):
     def __init__(self):
         self.timestreams = {}
         self.simulations = {}
+        self.stacks = {}
+        self.unstacked = {}
         self.crosspower = []
 
     @classmethod
@@ -90,9 +96,15 @@ class PipelineManager(config.Reader):
                 ts.mmode_ridge = float(tsconf["mmode_ridge"])
             if "flag_noise_bias_correct" in tsconf:   # powerspectrum() subtracts the noise bias of the flags too
                 ts.flag_noise_bias_correct = bool(tsconf["flag_noise_bias_correct"])
-            self.timestreams[tsconf["name"]] = ts
+            if (tsconf.get("simulate") or {}).get("unstacked", False):
+                # per-feed-pair data: the input of another entry's `stack_from`, not a timestream the stages below run on
+                self.unstacked[tsconf["name"]] = ts
+            else:
+                self.timestreams[tsconf["name"]] = ts
             if "simulate" in tsconf:
                 self.simulations[tsconf["name"]] = tsconf["simulate"]
+            if "stack_from" in tsconf:
+                self.stacks[tsconf["name"]] = dict(tsconf["stack_from"])
         if "crosspower" in yconf:
             self.crosspower = list(yconf["crosspower"] or [])
 
@@ -109,7 +121,7 @@ class PipelineManager(config.Reader):
     def simulate(self):
         """Make the timestreams that carry a `simulate` block and do not exist yet."""
         for tsname, simconf in self.simulations.items():
-            ts = self.timestreams[tsname]
+            ts = self.unstacked[tsname] if tsname in self.unstacked else self.timestreams[tsname]
             if os.path.exists(ts._ffile(0)):
                 logger.info("Timestream %s exists already, not simulated again.", tsname)
                 continue
@@ -119,11 +131,29 @@ class PipelineManager(config.Reader):
                 simconf["maps"] = [fixpath(m) for m in simconf["maps"]]
             if "sources" in simconf:
                 simconf["sources"] = [fixpath(c) for c in simconf["sources"]]
-            timestream.simulate(products, ts.directory, **simconf)
+            if simconf.pop("unstacked", False):
+                timestream.simulate_unstacked(products, ts.directory, **simconf)
+            else:
+                timestream.simulate(products, ts.directory, **simconf)
+
+    def stack(self):
+        """Make the timestreams that carry a `stack_from` block and whose directory does not exist yet: the unstacked
+        directory named there goes through `timestream.stack_baselines`."""
+        for tsname, conf in self.stacks.items():
+            ts = self.timestreams[tsname]
+            if os.path.exists(ts.directory):
+                logger.info("Timestream %s exists already, not stacked again.", tsname)
+                continue
+            calibrate = conf.get("calibrate", None)
+            timestream.stack_baselines(ts.manager, fixpath(conf["directory"]), ts.directory,
+                                       calibrate=None if calibrate in (None, "none") else calibrate,
+                                       dead_feeds=tuple(conf.get("dead_feeds", ()) or ()), chunk_gb=self.chunk_gb)
 
     def generate(self):
         """Run the stages that are switched on, for every timestream, in the reference's order: m-modes and SVD modes, KL
-        modes (collected into one file per filter if `collect_klmodes`), power spectra and cross-power spectra, maps."""
+        modes (collected into one file per filter if `collect_klmodes`), power spectra and cross-power spectra, maps.
+        Entries with a `stack_from` block are stacked first (`stack`)."""
+        self.stack()
         for tsobj in self.timestreams.values():
             os.makedirs(tsobj.output_directory, exist_ok=True)
         if self.generate_modes:

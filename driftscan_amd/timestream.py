@@ -63,6 +63,16 @@ class Timestream(object):
         with storage.File(self._ffile(fi), "r") as f:
             return np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f else None
 
+    def is_unstacked(self):
+        """Whether the files hold one row per feed pair (the attribute `unstacked`)."""
+        with storage.File(self._ffile(0), "r") as f:
+            return bool(f.attrs.get("unstacked", 0))
+
+    def _refuse_unstacked(self):
+        if os.path.exists(self._ffile(0)) and self.is_unstacked():
+            raise ValueError("%s holds unstacked (per-feed-pair) visibilities: stack them first with "
+                             "timestream.stack_baselines" % self.directory)
+
     def _weights_of(self, fs, ntime):
         """(len(fs), npairs, ntime) weights of the frequencies `fs` (ones for a file without the dataset) when the data
         is flagged — the file of frequency 0 holds `weight`, a choice every rank makes alike — else None."""
@@ -146,6 +156,7 @@ class Timestream(object):
         marker = self.output_directory + "/mmodes/COMPLETED_M"
         if os.path.exists(marker):
             return
+        self._refuse_unstacked()
         tel = self.telescope
         mmax, nfreq, ntime = tel.mmax, tel.nfreq, self.ntime
         # Each rank transforms ITS frequencies, the result is regrouped by m across ranks (the reference's MPI transpose,
@@ -219,6 +230,7 @@ class Timestream(object):
         marker = self.output_directory + "/mmodes/COMPLETED_M"
         if os.path.exists(marker):
             return {}
+        self._refuse_unstacked()
         ctx = get_context()
         tel = self.telescope
         mmax, nfreq, ntime, npairs = tel.mmax, tel.nfreq, self.ntime, tel.npairs
@@ -1256,8 +1268,191 @@ def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klnam
         yield r0, grp
 
 
+def _real_dtype(dtype):
+    return np.zeros(0, dtype=dtype).real.dtype
+
+
+def vis_expand_host(sky, class_off, members, g=None, out=None, accumulate=False, dtype=np.complex128):
+    """`Context.vis_expand` in numpy, computed in `dtype` (np.clongdouble for the tests): the statement
+    V[..., m, t] (+)= g[..., i, t] conj(g[..., j, t]) sky[..., c(m), t] of DESIGN.md section 4.17 for member m = (i, j) of
+    class c(m); sky [..., npairs, ntime], g [..., nfeed, ntime] broadcastable against it or None (ones)."""
+    class_off = np.asarray(class_off, dtype=np.int64)
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    n = np.diff(class_off)
+    if class_off[0] != 0 or np.any(n <= 0) or class_off[-1] != members.shape[0]:
+        raise ValueError("vis_expand_host: class offsets must start at 0, ascend strictly and end at len(members)")
+    cls = np.repeat(np.arange(n.shape[0]), n)
+    v = np.asarray(sky).astype(dtype)[..., cls, :]
+    if g is not None:
+        gl = np.asarray(g).astype(dtype)
+        v = gl[..., members[:, 0], :] * gl[..., members[:, 1], :].conj() * v
+    if accumulate:
+        v = np.asarray(out).astype(dtype) + v
+    return v
+
+
+def vis_stack_host(vis, class_off, members, w=None, g=None, feed_weight=None, dtype=np.complex128):
+    """`Context.vis_stack` in numpy, computed in `dtype`: (out, wout) [..., npairs, ntime] of the statement of DESIGN.md
+    section 4.17,
+
+        N_c = sum_{m in c} w_m conj(g_i) g_j V_m,  D_c = sum_{m in c} w_m |g_i|^2 |g_j|^2,  out = N / D,  wout = D / n_c
+
+    with w_m = w[..., m, t] feed_weight[i] feed_weight[j] (each factor 1 when not given) and both results 0 where
+    D == 0.  The members of a class are added in the table's order."""
+    class_off = np.asarray(class_off, dtype=np.int64)
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    n = np.diff(class_off)
+    if class_off[0] != 0 or np.any(n <= 0) or class_off[-1] != members.shape[0]:
+        raise ValueError("vis_stack_host: class offsets must start at 0, ascend strictly and end at len(members)")
+    real = _real_dtype(dtype)
+    i, j = members[:, 0], members[:, 1]
+    num = np.asarray(vis).astype(dtype)
+    den = np.ones(num.shape, dtype=real)
+    if g is not None:
+        gl = np.asarray(g).astype(dtype)
+        gi, gj = gl[..., i, :], gl[..., j, :]
+        num = gi.conj() * gj * num
+        den = den * ((gi.real**2 + gi.imag**2) * (gj.real**2 + gj.imag**2))
+    if w is not None:
+        wl = np.broadcast_to(np.asarray(w).astype(real), den.shape)
+        num, den = wl * num, wl * den
+    if feed_weight is not None:
+        fw = np.asarray(feed_weight).astype(real)
+        fac = (fw[i] * fw[j])[:, None]
+        num, den = fac * num, fac * den
+    N = np.add.reduceat(num, class_off[:-1], axis=-2)
+    D = np.add.reduceat(den, class_off[:-1], axis=-2)
+    some = D > 0
+    out = np.where(some, N / np.where(some, D, 1), 0).astype(dtype)
+    wout = np.where(some, D / n[:, None].astype(real), 0).astype(real)
+    return out, wout
+
+
+def _member_sigma(tel, freqs, ndays, ntime, class_off):
+    """sigma[f, m] = sqrt(n_c ntime noisepower(c, f, ndays)) of the unstacked noise: the plain mean of a complete class
+    then has the noise level of the stacked simulators."""
+    npairs = int(tel.npairs)
+    n = np.diff(class_off)
+    noise_ps = np.asarray(tel.noisepower(np.arange(npairs)[np.newaxis, :], np.array(freqs)[:, np.newaxis], ndays=ndays),
+                          dtype=np.float64).reshape(len(freqs), npairs)
+    return np.repeat(np.sqrt(n[np.newaxis, :] * ntime * noise_ps), n, axis=1)
+
+
+def _unstacked_chunks(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
+                      out=None, sources=(), gains=None, want_gains=False, weights=None):
+    """The passes of the unstacked simulators: yields (r0, f0, device tensor
+    (R, nfc, nmem, ntime), g) for realisations first + r0 .. first + r0 + R - 1 (R <= BLOCKVEC_MAX_R) and the frequencies
+    freqs[f0 : f0 + nfc]; g is the gain chunk (1 or R, nfc, nfeed, ntime) when `want_gains`, else None.  With `out`
+    (nreal, nf, nmem, ntime) the chunks are views of it; without, ONE buffer serves every chunk.
+
+    Per chunk of frequencies the stacked sky of a group comes from `_visibility_groups` (without noise, gains or flags),
+    the noise is drawn at the per-member level (`Context.ts_noise` with npairs := nmem, sigma of `_member_sigma`) and the
+    sky is spread over the members with the gains on it (`Context.vis_expand`, adding to the noise).  nfc is chosen so
+    that the unstacked chunk, the stacked sky and the three gain buffers of `skysim.gains_device` fit in `chunk_gb`, one
+    frequency at the least.  Every draw is counter based, so the chunking changes which calls make a row, not its
+    distribution or, for the noise, its bits."""
+    from . import skysim
+    from ._lib import BLOCKVEC_MAX_R
+
+    ctx = get_context()
+    tel = m.beamtransfer.telescope
+    npairs, nfeed = int(tel.npairs), int(tel.nfeed)
+    class_off, members = tel.redundant_pairs()
+    nmem = int(class_off[-1])
+    if ndays is None:
+        ndays = tel.ndays
+    ntime = _sim_ntime(tel, resolution)
+    nreal, first, nf = int(nreal), int(first), len(freqs)
+    if nf == 0 or nreal <= 0:
+        return
+    skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
+    have_sky = len(maps) > 0 or len(skymodels) > 0 or len(_as_sources(sources)) > 0
+    gains = skysim.as_gains(gains)
+    if gains is not None and not isinstance(gains, skysim.GainModel):
+        skysim.check_explicit_gains(gains, nreal, nf, nfeed, ntime)
+    Rmax = min(BLOCKVEC_MAX_R, nreal)
+    per_freq = 16.0 * Rmax * ntime * (nmem + npairs + (3 * nfeed if gains is not None else 0))
+    nfc = int(min(nf, max(1, chunk_gb * 2.0**30 // per_freq)))
+    log = sim_log
+    buf = None
+    for f0 in range(0, nf, nfc):
+        f1 = min(nf, f0 + nfc)
+        fs = freqs[f0:f1]
+        sigma = ctx.to_device(_member_sigma(tel, fs, ndays, ntime, class_off)) if ndays > 0 else None
+        flagged = None
+        if weights is not None:
+            wf = weights[f0:f1] if np.ndim(weights) == 3 else weights
+            flagged = ctx.to_device(np.ascontiguousarray(wf == 0))
+        for r0, sky in _visibility_groups(m, nreal, maps, 0, resolution, seed, skymodels, klname, sky_seed, first, fs,
+                                          chunk_gb, sources=sources):
+            R = int(sky.shape[0])
+            if out is not None:
+                grp = out[r0 : r0 + R, f0:f1]
+            else:
+                if buf is None:
+                    buf = ctx.empty((Rmax, nfc, nmem, ntime), np.complex128)
+                grp = buf[:R, : f1 - f0]
+            noisy = sigma is not None
+            if noisy:
+                with _StepTimer(log, "noise"):
+                    if grp.is_contiguous():
+                        ctx.ts_noise(sigma, fs, ntime, R, seed, first + r0, out=grp)
+                    else:   # a frequency slice of the result: ts_noise writes contiguous arrays
+                        grp.copy_(ctx.ts_noise(sigma, fs, ntime, R, seed, first + r0))
+            g = None
+            if gains is not None and (have_sky or want_gains):
+                with _StepTimer(log, "gains"):
+                    if isinstance(gains, skysim.GainModel):
+                        g = skysim.gains_device(gains, nfeed, fs, ntime, R, first + r0)
+                    else:
+                        g = skysim.explicit_gains(gains, nreal, nf, r0, R, range(f0, f1), nfeed, ntime)
+                        g = g.contiguous() if hasattr(g, "data_ptr") else ctx.to_device(np.ascontiguousarray(g))
+            with _StepTimer(log, "expand"):
+                if have_sky:
+                    ctx.vis_expand(sky, class_off, members, g=g, out=grp, accumulate=noisy)
+                elif not noisy:
+                    grp.zero_()
+            if flagged is not None:
+                grp.masked_fill_(flagged, 0.0)
+            yield r0, f0, grp, (g if want_gains else None)
+            del g
+
+
+def _write_sim_file(tstream, fi, data, tphi, gain=None, weight=None, table=None):
+    """One per-frequency file with the datasets and attributes of `simulate_ensemble`; `table` (class_off, members) marks
+    it unstacked (attribute `unstacked`, datasets `members` and `class_off`)."""
+    tel, bt = tstream.telescope, tstream.beamtransfer
+    os.makedirs(tstream._fdir(fi), exist_ok=True)
+    with storage.File(tstream._ffile(fi), "w") as f:
+        f.create_dataset("timestream", data=np.ascontiguousarray(data))
+        f.create_dataset("phi", data=tphi)
+        if gain is not None:
+            f.create_dataset("gain", data=np.ascontiguousarray(gain))
+        if weight is not None:
+            f.create_dataset("weight", data=np.ascontiguousarray(weight))
+        if table is not None:
+            f.create_dataset("class_off", data=np.asarray(table[0]))
+            f.create_dataset("members", data=np.asarray(table[1]))
+            f.attrs["unstacked"] = 1
+        f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
+        f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
+        f.create_dataset("feedmask", data=np.asarray(tel.feedmask))
+        f.create_dataset("uniquepairs", data=np.asarray(tel.uniquepairs))
+        f.create_dataset("baselines", data=np.asarray(tel.baselines))
+        f.attrs["beamtransfer_path"] = os.path.abspath(bt.directory)
+        f.attrs["ntime"] = int(data.shape[-1])
+
+
+def _unstacked_weights(tel, weights, freqs, ntime):
+    if weights is None:
+        return None
+    from . import skysim
+
+    return skysim.as_weights(weights, len(freqs), int(tel.redundant_pairs()[0][-1]), ntime, freqs)
+
+
 def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None, sky_seed=0,
-                          first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None):
+                          first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None, unstacked=False):
     """`nreal` simulated timestreams of the telescope of ProductManager `m` as ONE device tensor
     (nreal, len(freqs), npairs, ntime): what `simulate` writes per frequency, for many statistically independent data
     sets, without leaving the device between the draws and the result.
@@ -1288,10 +1483,25 @@ def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, s
 
     weights: flags — a `skysim.FlagModel` (or the dict of its arguments) or a float64 array >= 0
     of shape (len(freqs), npairs, ntime), (len(freqs), ntime) or (ntime,), the same for every realisation: samples of
-    weight 0 are set to exactly 0 after sky, gains and noise.  weights=None: none of this runs."""
+    weight 0 are set to exactly 0 after sky, gains and noise.  weights=None: none of this runs.
+
+    unstacked=True: one row per feed pair instead of one per unique baseline, in the order of
+    `members` of `TransitTelescope.redundant_pairs` — the result is (nreal, len(freqs), nmem, ntime) with
+    V_m = g_i conj(g_j) V_c^sky + n_m: the stacked sky spread over the members with the gains of `gains` on it
+    (`Context.vis_expand`), on noise of variance n_c ntime noisepower, so that the plain mean of a complete class has the
+    noise of the stacked result.  `weights` then has nmem rows.  The work goes in chunks of frequencies that fit in
+    `chunk_gb`.  unstacked=False: none of this runs."""
     ctx = get_context()
     tel = m.beamtransfer.telescope
     freqs = _sim_freqs(tel, freqs)
+    if unstacked:
+        ntime = _sim_ntime(tel, resolution)
+        weights = _unstacked_weights(tel, weights, freqs, ntime)
+        out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.redundant_pairs()[0][-1]), ntime), np.complex128)
+        for _ in _unstacked_chunks(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
+                                   chunk_gb, out=out, sources=sources, gains=gains, weights=weights):
+            pass
+        return out
     weights = _sim_weights(tel, weights, freqs, _sim_ntime(tel, resolution))
     out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.npairs), _sim_ntime(tel, resolution)), np.complex128)
     for _ in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
@@ -1301,7 +1511,7 @@ def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, s
 
 
 def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None,
-                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None):
+                      sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None, unstacked=False):
     """`simulate_visibilities` written out: realisation first + i as the Timestream directory
     `outdir/real_%04d` % (first + i), each with the per-frequency files, datasets and attributes of `simulate` and the
     saved object.  Every rank writes its own frequencies (one device-to-host copy per group of up to 8 realisations),
@@ -1319,6 +1529,11 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
             ts.set_kltransform("kl")
             ts.set_psestimator("ps")
             p = ts.powerspectrum()      # mean over the ensemble -> the injected band powers, scatter -> Fisher errors
+
+    unstacked=True (see `simulate_visibilities`): every per-frequency file holds `timestream`
+    (nmem, ntime), one row per feed pair, the attribute `unstacked` = 1 and the class table as the datasets `members` and
+    `class_off`, `weight` (nmem, ntime) when weights were given, and everything else as above (`gain` included: what
+    `stack_baselines(calibrate="file")` undoes).  Such a directory goes through `stack_baselines` before the m-modes.
     """
     ctx = get_context()
     bt = m.beamtransfer
@@ -1326,6 +1541,9 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
     freqs = _sim_freqs(tel, freqs)
     ntime = _sim_ntime(tel, resolution)
     nreal, first = int(nreal), int(first)
+    if unstacked:
+        return _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed,
+                                            first, freqs, chunk_gb, sources, gains, weights)
     weights = _sim_weights(tel, weights, freqs, ntime)
     weight_f = None if weights is None else np.broadcast_to(weights, (len(freqs), int(tel.npairs), ntime))
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
@@ -1371,3 +1589,158 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
             tstream.save()
     parallel.barrier()
     return tss
+
+
+def simulate_unstacked(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=(), klname=None, sky_seed=0,
+                       sky_realisation=0, sources=(), gains=None, weights=None, chunk_gb=4.0):
+    """One unstacked Timestream directory `outdir` with the arguments of `simulate`: realisation `sky_realisation` of
+    `simulate_ensemble(unstacked=True)`, written straight into `outdir` (what a `simulate:` block with
+    `unstacked: true` of the pipeline runs; seed=None is seed 0, the draws being counter based).  Returns the
+    Timestream."""
+    tel = m.beamtransfer.telescope
+    return _simulate_ensemble_unstacked(m, None, 1, maps, ndays, resolution, 0 if seed is None else seed, skymodels, klname,
+                                        sky_seed, int(sky_realisation), _sim_freqs(tel, None), chunk_gb, sources, gains,
+                                        weights, dirs=[outdir])[0]
+
+
+def _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first,
+                                 freqs, chunk_gb, sources, gains, weights, dirs=None):
+    """`simulate_ensemble(unstacked=True)`: the chunks of `_unstacked_chunks` written as they come, one device-to-host
+    copy per chunk (a group of realisations times a chunk of frequencies)."""
+    ctx = get_context()
+    tel = m.beamtransfer.telescope
+    ntime = _sim_ntime(tel, resolution)
+    table = tel.redundant_pairs()
+    nmem = int(table[0][-1])
+    weights = _unstacked_weights(tel, weights, freqs, ntime)
+    weight_f = None if weights is None else np.broadcast_to(weights, (len(freqs), nmem, ntime))
+    tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
+    if dirs is None:
+        dirs = [os.path.join(outdir, "real_%04d" % (first + i)) for i in range(max(nreal, 0))]
+    tss = [Timestream(d, m) for d in dirs]
+    for r0, f0, grp, g in _unstacked_chunks(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first,
+                                            freqs, chunk_gb, sources=sources, gains=gains, want_gains=gains is not None,
+                                            weights=weights):
+        with _StepTimer(sim_log, "download"):
+            host = ctx.to_host(grp)
+            gh = None if g is None else ctx.to_host(g)           # (1 or R, nfc, nfeed, ntime)
+        with _StepTimer(sim_log, "write"):
+            for r in range(host.shape[0]):
+                for k in range(host.shape[1]):
+                    _write_sim_file(tss[r0 + r], freqs[f0 + k], host[r, k], tphi,
+                                    gain=None if gh is None else gh[r if gh.shape[0] > 1 else 0, k],
+                                    weight=None if weight_f is None else weight_f[f0 + k], table=table)
+    parallel.barrier()
+    if parallel.rank0():
+        for tstream in tss:
+            os.makedirs(tstream.directory, exist_ok=True)
+            tstream.save()
+    parallel.barrier()
+    return tss
+
+
+def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0):
+    """Stack the unstacked Timestream directory `indir` (`simulate_ensemble(unstacked=True)`, or a correlator's per-pair
+    data in that layout) into the unique baselines of the telescope of ProductManager `m` and write them to `outdir` in
+    the layout of `simulate_ensemble`; returns the `Timestream` of `outdir`.
+
+    Per frequency the rows (nmem, ntime) go through `Context.vis_stack` with the file's `weight` (when it has one) as the
+    per-sample weights.  calibrate: None (or "none"), "file" — the dataset `gain` (nfeed, ntime) of every file — or an
+    explicit complex128 array / tensor (nfreq, nfeed, ntime) of calibration gains.  feed_weight (nfeed) >= 0 weights
+    every pair by the product of its two feeds' entries; dead_feeds lists feeds of weight 0.  Ranks take their own
+    frequencies, in chunks that fit in `chunk_gb`.
+
+    The stacked files hold `weight` (npairs, ntime) = sum_{m in c} w_m fw_i fw_j / n_c, the share of the class that is
+    there — for flags and dead feeds (n_c - k) / n_c exactly, the inverse noise variance relative to nominal of section
+    4.16 — only if some weight of some frequency is not exactly 1.0: complete, unflagged data goes on through the plain
+    m-mode path, calibrated or not, flagged or thinned data through the weighted one (a class that lost all its members
+    has weight 0 throughout and comes out of `generate_modes_batched` with info = -1).  The amplitudes of the calibration
+    gains are left out of the file's weight (`Context.vis_stack` keeps them in its own: mean |g_i|^2 |g_j|^2, which moves
+    the noise of a calibrated stack by the few per cent the amplitudes are off one); a sample the kernel could not form
+    (every gain product of its class zero) gets weight 0."""
+    ctx = get_context()
+    tel = m.beamtransfer.telescope
+    src = Timestream(indir, m)
+    if not src.is_unstacked():
+        raise ValueError("%s does not hold unstacked visibilities" % src.directory)
+    class_off, members = tel.redundant_pairs()
+    nmem, npairs, nfeed, nfreq = int(class_off[-1]), int(tel.npairs), int(tel.nfeed), int(tel.nfreq)
+    ntime = src.ntime
+    with storage.File(src._ffile(0), "r") as f:
+        if not (np.array_equal(f["class_off"][:], class_off) and np.array_equal(f["members"][:], members)):
+            raise ValueError("%s was written for another class table than this telescope's" % src.directory)
+    if isinstance(calibrate, str):
+        if calibrate not in ("file", "none"):
+            raise ValueError('calibrate is None, "none", "file" or an array (nfreq, nfeed, ntime)')
+        calibrate = None if calibrate == "none" else calibrate
+    elif calibrate is not None:
+        if hasattr(calibrate, "data_ptr"):
+            calibrate = calibrate.cpu().numpy()
+        calibrate = np.asarray(calibrate, dtype=np.complex128)
+        if calibrate.shape != (nfreq, nfeed, ntime):
+            raise ValueError("calibrate %s is not (nfreq, nfeed, ntime) = (%d, %d, %d)"
+                             % (calibrate.shape, nfreq, nfeed, ntime))
+    fw = None
+    if feed_weight is not None or len(dead_feeds) > 0:
+        fw = np.ones(nfeed, dtype=np.float64) if feed_weight is None else np.array(feed_weight, dtype=np.float64)
+        if fw.shape != (nfeed,) or not np.all(np.isfinite(fw) & (fw >= 0)):
+            raise ValueError("feed_weight must be (nfeed,) = (%d,), finite and not negative" % nfeed)
+        for a in dead_feeds:
+            if not 0 <= int(a) < nfeed:
+                raise ValueError("dead feed %d of %d" % (int(a), nfeed))
+            fw[int(a)] = 0.0
+    freqs = _sim_freqs(tel, None)
+    with storage.File(src._ffile(0), "r") as f:
+        weighted = "weight" in f
+    per_f = ntime * (16.0 * nmem + (8.0 * nmem if weighted else 0.0) + (16.0 * nfeed if calibrate is not None else 0.0)
+                     + 24.0 * npairs)
+    step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
+    log = sim_log
+    nmem_c = np.diff(class_off)[:, None].astype(np.float64)
+    stacked, wts = {}, {}
+    for c0 in range(0, len(freqs), step):
+        fs = freqs[c0 : c0 + step]
+        with _StepTimer(log, "read"):
+            vis, w, g = [], [], []
+            for fi in fs:
+                with storage.File(src._ffile(fi), "r") as f:
+                    vis.append(np.asarray(f["timestream"][:], dtype=np.complex128))
+                    if weighted:
+                        w.append(np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f
+                                 else np.ones((nmem, ntime), dtype=np.float64))
+                    if isinstance(calibrate, str):
+                        if "gain" not in f:
+                            raise ValueError('calibrate="file": %s holds no dataset `gain`' % src._ffile(fi))
+                        g.append(np.asarray(f["gain"][:], dtype=np.complex128))
+            if calibrate is not None and not isinstance(calibrate, str):
+                g = [calibrate[fi] for fi in fs]
+        with _StepTimer(log, "stack"):
+            out, wout = ctx.vis_stack(ctx.to_device(np.stack(vis)[None]), class_off, members,
+                                      w=ctx.to_device(np.stack(w)[None]) if weighted else None,
+                                      g=ctx.to_device(np.stack(g)[None]) if calibrate is not None else None, feed_weight=fw)
+            out, wout = ctx.to_host(out)[0], ctx.to_host(wout)[0]
+        share = np.ones((npairs, 1), dtype=np.float64)
+        if fw is not None:
+            share = np.add.reduceat((fw[members[:, 0]] * fw[members[:, 1]])[:, None], class_off[:-1], axis=0) / nmem_c
+        for k, fi in enumerate(fs):
+            if weighted:
+                fac = w[k] if fw is None else w[k] * (fw[members[:, 0]] * fw[members[:, 1]])[:, None]
+                share_k = np.add.reduceat(fac, class_off[:-1], axis=0) / nmem_c
+            else:
+                share_k = np.broadcast_to(share, (npairs, ntime))
+            stacked[fi], wts[fi] = out[k], np.where(wout[k] == 0, 0.0, share_k)
+    # every rank writes `weight` or none does: the m-mode routes choose their path by the file of frequency 0
+    mine = any(np.any(wv != 1.0) for wv in wts.values())
+    nranks = parallel.size() if parallel._dist() else 1
+    write_w = any(parallel.exchange([mine] * nranks))
+    dst = Timestream(outdir, m)
+    tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
+    with _StepTimer(log, "write"):
+        for fi in freqs:
+            _write_sim_file(dst, fi, stacked[fi], tphi, weight=wts[fi] if write_w else None)
+    parallel.barrier()
+    if parallel.rank0():
+        os.makedirs(dst.directory, exist_ok=True)
+        dst.save()
+    parallel.barrier()
+    return dst

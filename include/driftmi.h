@@ -726,6 +726,46 @@ int dm_toeplitz_max_rhs(int n);
 int dm_toeplitz_solve_diag(dm_ctx* ctx, int n, int nrhs, int batch, const void* col_dev, void* b_dev, double* diag_dev,
                            int* info_dev);
 
+/* ---- unstacked (per-feed-pair) visibilities --------------------------------------- */
+/* dm_vis_stack: the weighted, optionally calibrated mean of the redundant feed pairs of every unique baseline.  With the
+ * class table of TransitTelescope.redundant_pairs (class_off_host (npairs + 1), members_host (nmem, 2),
+ * nmem = class_off[npairs]; row m of the unstacked data is the feed pair (i, j) = members[m]):
+ *   N = sum_{m in c} w_m conj(g_i) g_j V_m,   D = sum_{m in c} w_m |g_i|^2 |g_j|^2,   w_m := w[m] fw[i] fw[j]
+ *   out[r, f, c, t] = N / D,   wout[r, f, c, t] = D / n_c;   both 0 where D == 0
+ *   vis_dev   (nreal, nf, nmem, ntime) c128, t fastest; vis_rstride elements between realisations (0: contiguous)
+ *   w_dev     contiguous (w_nreal, nf, nmem, ntime) f64 >= 0, w_nreal = 1 or nreal; null: ones, and no weight is read
+ *   g_dev     contiguous (g_nreal, nf, nfeed, ntime) c128 calibration gains, g_nreal = 1 or nreal; null: ones, and
+ *             neither LDS nor the member table is touched by the kernel
+ *   feed_weight_host (nfeed) f64 >= 0 (0: a dead feed), or null
+ *   out_dev   (nreal, nf, npairs, ntime) c128 and wout_dev f64 of the same shape, out_rstride elements between the
+ *             realisations of both (0: contiguous); every element is written
+ * out is the inverse-variance mean of the calibrated pairs V_m / (g_i conj g_j) without a division per member; its noise
+ * variance is the nominal one over wout, which is exactly 1.0 for a complete class with unit weights and no gains.  One
+ * workgroup per (realisation, frequency, tile of time samples, chunk of classes); the gains of the tile are staged in LDS
+ * (tile = dm_ts_gain_tile(nfeed) with gains, 16 samples without); every element of vis and w is loaded once, 16 bytes
+ * per lane.  The order of both sums of a class is a function of (n_c, nfeed) alone: the same bits alone, in any batch, at
+ * any position and for any realisation range.  Refused before any launch (dm_last_error): an empty class, class offsets
+ * that do not start at 0 or decrease, a feed index outside [0, nfeed), with gains an nfeed whose single-sample tile does
+ * not fit in LDS, negative sizes or feed weights, a null vis, out or wout with work to do, out or wout sharing an element
+ * with vis (judged on whole spans) or with each other.  nreal, nf, npairs or ntime = 0 is a no-op.  Returns when the work
+ * is queued on the context's stream.  No counterpart in the reference, whose data begins at stacked baselines. */
+int dm_vis_stack(dm_ctx* ctx, int nreal, int w_nreal, int g_nreal, int nf, int nfeed, int npairs, int ntime,
+                 const int* class_off_host, const int* members_host, const void* vis_dev, const double* w_dev,
+                 const void* g_dev, const double* feed_weight_host, void* out_dev, double* wout_dev, int64_t vis_rstride,
+                 int64_t out_rstride);
+
+/* dm_vis_expand: a stacked sky spread over the feed pairs, with the per-feed gains on it,
+ *   out[r, f, m, t] (+)= g[r, f, i, t] conj(g[r, f, j, t]) sky[r, f, c(m), t],  (i, j) = members[m]
+ *   g_dev     contiguous (g_nreal, nf, nfeed, ntime) c128, g_nreal = 1 or nreal; null: the class row is copied
+ *   sky_dev   (nreal, nf, npairs, ntime) c128, sky_rstride elements between realisations (0: contiguous)
+ *   out_dev   (nreal, nf, nmem, ntime) c128, out_rstride elements between realisations (0: contiguous)
+ * accumulate != 0 adds to out (the noise dm_ts_noise drew there at the per-member level: gains multiply the sky part
+ * only).  Table, layout and refusals of dm_vis_stack; one 16-byte store per lane and member.  Returns when the work is
+ * queued on the context's stream.  No counterpart in the reference. */
+int dm_vis_expand(dm_ctx* ctx, int nreal, int g_nreal, int nf, int nfeed, int npairs, int ntime,
+                  const int* class_off_host, const int* members_host, const void* g_dev, const void* sky_dev, void* out_dev,
+                  int64_t sky_rstride, int64_t out_rstride, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif
