@@ -210,6 +210,9 @@ SIGNATURES = {
     "dm_vis_expand": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp,
                 c_vp, c_i64, c_i64, c_int]),
+    "dm_redcal_solve": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp,
+                ctypes.POINTER(c_dbl), c_vp, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
 }
 
 _lib = None
@@ -1050,6 +1053,67 @@ def _vis_expand(self, sky, class_off, members, g=None, out=None, accumulate=Fals
 
 Context.vis_stack = _vis_stack
 Context.vis_expand = _vis_expand
+
+
+def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,
+                  out=None):
+    """Redundant-baseline calibration (dm_redcal_solve; `timestream.redcal_solve_host` restates
+    it): the per-feed gains g (nreal, nf, nfeed, ntime) and class visibilities y (nreal, nf, npairs, ntime) that minimise
+    sum_m omega_m |V_m - g_i conj(g_j) y_c|^2 per (realisation, frequency, time sample), by the damped alternating fixed
+    point from g0 (ones when None).  vis, w and feed_weight as for `vis_stack`; omega_m = w_m fw_i fw_j, 0 for
+    autocorrelations and for classes that constrain nothing.  Returns (g, y, info), info a dict of device tensors
+    (nreal, nf, ntime): `iters` int32, `step` (the last step; the sample converged iff step < tol) and `chi2` at the
+    result.  The solution carries the degeneracies of the table: `timestream.fix_degeneracies` removes them.  out: a dict
+    of preallocated contiguous tensors under the names g, y, iters, step, chi2 (any subset).  The bits of a sample do not
+    depend on the batch it is solved in."""
+    rs = _rstride_of(vis, True)
+    if rs is None:
+        raise ValueError("redcal_solve: complex128 tensor vis (nreal, nf, nmem, ntime) expected")
+    nreal, nf, nmem, ntime = (int(v) for v in vis.shape)
+    off, offp, mem, memp = _class_table("redcal_solve", class_off, members)
+    npairs = off.shape[0] - 1
+    if mem.shape[0] != nmem:
+        raise ValueError("redcal_solve: vis has %d rows, the table %d members" % (nmem, mem.shape[0]))
+    nfeed = int(mem.max()) + 1 if mem.size else 0
+    w_nreal = 1
+    if w is not None:
+        if not (hasattr(w, "data_ptr") and w.dim() == 4 and not w.is_complex() and w.element_size() == 8
+                and w.is_contiguous() and tuple(w.shape)[1:] == (nf, nmem, ntime) and int(w.shape[0]) in (1, nreal)):
+            raise ValueError("redcal_solve: w must be a contiguous float64 tensor (1 or nreal, nf, nmem, ntime)")
+        w_nreal = int(w.shape[0])
+    fwp = None
+    if feed_weight is not None:
+        fw = np.ascontiguousarray(feed_weight, dtype=np.float64)
+        if fw.ndim != 1 or fw.shape[0] < nfeed:
+            raise ValueError("redcal_solve: feed_weight must have one entry per feed")
+        nfeed = int(fw.shape[0])
+        fwp = fw.ctypes.data_as(ctypes.POINTER(c_dbl))
+    if g0 is not None:
+        if not (_is_c128(g0) and g0.dim() == 4 and (int(g0.shape[0]), int(g0.shape[1]), int(g0.shape[3])) == (nreal, nf, ntime)
+                and int(g0.shape[2]) >= nfeed and (feed_weight is None or int(g0.shape[2]) == nfeed)):
+            raise ValueError("redcal_solve: g0 must be a contiguous complex128 tensor (nreal, nf, nfeed, ntime)")
+        nfeed = int(g0.shape[2])
+    out = dict(out or {})
+    shapes = dict(g=((nreal, nf, nfeed, ntime), np.complex128), y=((nreal, nf, npairs, ntime), np.complex128),
+                  iters=((nreal, nf, ntime), np.int32), step=((nreal, nf, ntime), np.float64),
+                  chi2=((nreal, nf, ntime), np.float64))
+    if set(out) - set(shapes):
+        raise ValueError("redcal_solve: out holds %s" % sorted(set(out) - set(shapes)))
+    for name, (shape, dt) in shapes.items():
+        if out.get(name) is None:
+            out[name] = self.empty(shape, dt)
+        t = out[name]
+        if not (hasattr(t, "data_ptr") and tuple(t.shape) == shape and t.is_contiguous()
+                and t.dtype == self.empty((0,), dt).dtype):
+            raise ValueError("redcal_solve: out[%r] must be a contiguous %s tensor of shape %s" % (name, np.dtype(dt), shape))
+    rc = self.lib.dm_redcal_solve(self.h, nreal, w_nreal, nf, nfeed, npairs, ntime, offp, memp, self.ptr(vis), self.ptr(w),
+                                  fwp, self.ptr(g0), float(damping), float(tol), int(maxiter), self.ptr(out["g"]),
+                                  self.ptr(out["y"]), self.ptr(out["iters"]), self.ptr(out["step"]), self.ptr(out["chi2"]), rs)
+    self.check(rc, "dm_redcal_solve")
+    return out["g"], out["y"], dict(iters=out["iters"], step=out["step"], chi2=out["chi2"])
+
+
+Context.redcal_solve = _redcal_solve
 
 
 def _toeplitz_max_rhs(self, n):

@@ -12,6 +12,7 @@
 // lanes one contiguous run of TT x 16 bytes of a row.  TT = dm_gain_tile(nfeed) with gains, 16 without; the chunks
 // never cut a class.
 #include "dm_common.h"
+#include "dm_stack_sum.h"
 #include "dm_stack_table.h"
 #include "../../include/driftmi.h"
 
@@ -19,26 +20,14 @@
 
 namespace {
 
-// Waves per workgroup: 8 with gains, so that the two workgroups whose 64 KiB tiles fit in a CU's LDS keep four waves on
-// every SIMD (with 4 the stack ran at 1.4 waves per SIMD at 512 feeds, waiting 83 % of their cycles: DESIGN.md section
-// 4.17); 4 without.  The expansion takes 8 only on the tiles of 8 samples and fewer, where the LDS tile is what limits
-// the workgroups of a CU: on the 16-sample tile it measured slower with 8 (2.28 ms against 1.92 ms at 128 feeds).
-constexpr int stack_waves(bool has_g) { return has_g ? 8 : 4; }
+// Waves per workgroup: stack_waves (dm_stack_sum.h), 8 with gains and 4 without.  The expansion takes 8 only on the tiles
+// of 8 samples and fewer, where the LDS tile is what limits the workgroups of a CU: on the 16-sample tile it measured
+// slower with 8 (2.28 ms against 1.92 ms at 128 feeds).
 constexpr int expand_waves(bool has_g, int tt) { return has_g && tt <= 8 ? 8 : 4; }
 
-// The gains of one time tile into LDS: [feed][TT], zeros past ntime.
-template <int TT, int NW>
-__device__ __forceinline__ void stack_stage_gains(cplx* gtile, const cplx* __restrict__ g, size_t grow, uint32_t nfeed,
-                                                  uint32_t ntime, uint32_t tt, uint32_t t, bool live) {
-  constexpr uint32_t S = NW * 64 / TT;
-  for (uint32_t a = threadIdx.x / TT; a < nfeed; a += S)
-    gtile[a * TT + tt] = live ? dm_ldg(g, (grow + a) * ntime + t) : make_double2(0.0, 0.0);
-  __syncthreads();
-}
-
 // N = sum w conj(g_i) g_j V, D = sum w |g_i|^2 |g_j|^2 over the members of a class; out = N / D, wout = D / n_c, both 0
-// where D == 0.  Slot s adds its members in the table's order and the slots are added by an xor butterfly (s ^ 1, s ^ 2,
-// ...), so the order of both sums is a function of (n_c, W) and W of nfeed alone — never of the batch, the chunk, the
+// where D == 0; the sums are stack_class_sums of dm_stack_sum.h, which dm_redcal.hip shares.  Slot s adds its members in
+// the table's order and the slots are added by an xor butterfly (s ^ 1, s ^ 2, ...), so the order of both sums is a function of (n_c, W) and W of nfeed alone — never of the batch, the chunk, the
 // realisation or the other classes.  HAS_G false: no LDS and no table load (conj(g_i) g_j = 1); HAS_W false: no weight
 // load.  mfac (one f64 per member: the product of its two feed weights) is optional at run time.  Every element of vis
 // (and of w) is loaded once.
@@ -53,7 +42,6 @@ __global__ __launch_bounds__(stack_waves(HAS_G) * 64) void vis_stack_kernel(cons
                                                         uint32_t nf, uint32_t g_each, uint32_t w_each,
                                                         unsigned long long vstride, unsigned long long ostride) {
   extern __shared__ cplx gtile[];                                // [nfeed][TT], HAS_G only
-  constexpr uint32_t W = 64 / TT;
   constexpr int NW = stack_waves(HAS_G);
   const uint32_t cell = blockIdx.x / nchunks, chunk = blockIdx.x - cell * nchunks;
   const uint32_t rf = cell / ntiles, ti = cell - rf * ntiles;
@@ -69,34 +57,8 @@ __global__ __launch_bounds__(stack_waves(HAS_G) * 64) void vis_stack_kernel(cons
   const int c1 = chunk_off[chunk + 1];
   for (int c = chunk_off[chunk] + (int)wave; c < c1; c += NW) {
     const int m0 = class_off[c], m1 = class_off[c + 1];
-    double nx = 0.0, ny = 0.0, d = 0.0;
-    if (live) {
-#pragma unroll 4
-      for (int k = m0 + (int)s; k < m1; k += (int)W) {
-        const cplx v = dm_ldg(vis, vrow + (size_t)k * ntime);
-        double we = 1.0;
-        if constexpr (HAS_W) we = dm_ldg(w, wrow + (size_t)k * ntime);
-        if (mfac) we *= dm_ldg(mfac, (size_t)k);
-        if constexpr (HAS_G) {
-          const int2 m = members[k];
-          const cplx gi = gtile[(uint32_t)m.x * TT + tt], gj = gtile[(uint32_t)m.y * TT + tt];
-          const cplx p = cmul(cmulc(gj, gi), v);                 // conj(g_i) g_j V
-          nx = fma(we, p.x, nx);
-          ny = fma(we, p.y, ny);
-          d = fma(we, cabs2(gi) * cabs2(gj), d);
-        } else {
-          nx = fma(we, v.x, nx);
-          ny = fma(we, v.y, ny);
-          d += we;
-        }
-      }
-    }
-#pragma unroll
-    for (int o = TT; o < 64; o <<= 1) {
-      nx += __shfl_xor(nx, o, 64);
-      ny += __shfl_xor(ny, o, 64);
-      d += __shfl_xor(d, o, 64);
-    }
+    double nx, ny, d;
+    stack_class_sums<TT, HAS_G, HAS_W>(vis, w, mfac, members, gtile, vrow, wrow, ntime, m0, m1, s, tt, live, nx, ny, d);
     if (s == 0 && live) {
       const size_t e = (size_t)r * ostride + ((size_t)f * npairs + (uint32_t)c) * ntime + t;
       const bool some = d > 0.0;

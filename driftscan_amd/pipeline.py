@@ -8,8 +8,9 @@ block of arguments for ``timestream.simulate`` plus its ``product_directory``;
 the files of its ``maps`` and ``sources`` lists go through ``fixpath``; with ``unstacked: true`` the block goes to
 ``timestream.simulate_unstacked`` instead — one realisation of the device route of ``simulate_ensemble``, one row per feed
 pair; such an entry is kept in ``unstacked``, apart from the timestreams the stages run on — and an entry with
-``stack_from: {directory, calibrate: file|none, dead_feeds: [...]}`` is made from such a directory by
-``timestream.stack_baselines`` before the m-modes, when its own directory does not exist yet)
+``stack_from: {directory, calibrate: file|none|redundant, redcal: {...}, dead_feeds: [...]}`` is made from such a
+directory by ``timestream.stack_baselines`` before the m-modes, when its own directory does not exist yet; ``redcal``
+holds the solver's ``damping``, ``tol``, ``maxiter`` and ``reference`` (``file`` or absent) of ``calibrate: redundant``)
 and optionally ``crosspower`` (entries with ``psname``, ``klname``, ``timestreams``, ``psfile``) — the same defaults,
 exceptions and methods.  Two deliberate differences:
 
@@ -147,7 +148,8 @@ class PipelineManager(config.Reader):
             calibrate = conf.get("calibrate", None)
             timestream.stack_baselines(ts.manager, fixpath(conf["directory"]), ts.directory,
                                        calibrate=None if calibrate in (None, "none") else calibrate,
-                                       dead_feeds=tuple(conf.get("dead_feeds", ()) or ()), chunk_gb=self.chunk_gb)
+                                       dead_feeds=tuple(conf.get("dead_feeds", ()) or ()), chunk_gb=self.chunk_gb,
+                                       **({"redcal": dict(conf["redcal"])} if conf.get("redcal") else {}))
 
     def generate(self):
         """Run the stages that are switched on, for every timestream, in the reference's order: m-modes and SVD modes, KL

@@ -9,6 +9,7 @@ CONSUMERS of the per-m operators: every projecti
 ``healpix`` restatements of this package.  Ranks split frequencies and m as the reference does, but without its two
 MPI transposes: timestream files are per frequency and m-mode files per m, so a rank reads the frequencies it needs.
 """
+import logging
 import os
 import pickle
 import time
@@ -1328,6 +1329,178 @@ def vis_stack_host(vis, class_off, members, w=None, g=None, feed_weight=None, dt
     return out, wout
 
 
+def redcal_weights(class_off, members, nfeed, feed_weight=None):
+    """(yfac, gfac) float64 (nmem) of the redundant-calibration solver: yfac = fw_i fw_j, 0 for
+    an autocorrelation — the member factor of the y step; gfac = yfac, 0 on every member of a class with fewer than two
+    members of yfac > 0 — the factor of the gain step and of chi^2.  A function of the table and the feed weights."""
+    class_off = np.asarray(class_off, dtype=np.int64)
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    n = np.diff(class_off)
+    if class_off[0] != 0 or np.any(n <= 0) or class_off[-1] != members.shape[0]:
+        raise ValueError("redcal: class offsets must start at 0, ascend strictly and end at len(members)")
+    fw = np.ones(nfeed, dtype=np.float64) if feed_weight is None else np.asarray(feed_weight, dtype=np.float64)
+    if fw.shape != (nfeed,) or (members.size and members.max() >= nfeed) or np.any(fw < 0):
+        raise ValueError("redcal: feed_weight (nfeed) >= 0 and feed indices below nfeed expected")
+    i, j = members[:, 0], members[:, 1]
+    yfac = np.where(i != j, fw[i] * fw[j], 0.0)
+    live = np.add.reduceat((yfac > 0).astype(np.int64), class_off[:-1])
+    gfac = np.where(np.repeat(live, n) >= 2, yfac, 0.0)
+    return yfac, gfac
+
+
+def redcal_step_host(vis, class_off, members, g, w=None, feed_weight=None, damping=0.4, dtype=np.complex128):
+    """One iteration of `Context.redcal_solve` in numpy, computed in `dtype`: (g_new, y, step) of the statement of
+    DESIGN.md section 4.18 from the gains g [..., nfeed, ntime] —
+
+        y_c  = sum_{m in c} omega' conj(g_i) g_j V_m / sum_{m in c} omega' |g_i|^2 |g_j|^2        (0 where the denominator is 0)
+        gh_a = [sum_{m=(a,j)} omega V_m g_j conj(y_c) + sum_{m=(i,a)} omega conj(V_m) g_i y_c]
+               / [sum_{m=(a,j)} omega |g_j|^2 |y_c|^2 + sum_{m=(i,a)} omega |g_i|^2 |y_c|^2]       (g_a where the denominator is 0)
+        g_new = (1 - damping) g + damping gh,   step = max_a |g_new_a - g_a| / |g_a|  [..., ntime]
+
+    with omega' = w yfac and omega = w gfac of `redcal_weights`.  The y line is `vis_stack_host` with those weights."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    real = _real_dtype(dtype)
+    gl = np.asarray(g).astype(dtype)
+    nfeed = gl.shape[-2]
+    yfac, gfac = redcal_weights(class_off, members, nfeed, feed_weight)
+    n = np.diff(np.asarray(class_off, dtype=np.int64))
+    cls = np.repeat(np.arange(n.shape[0]), n)
+    wy = yfac[:, None].astype(real) if w is None else np.asarray(w).astype(real) * yfac[:, None].astype(real)
+    y, _ = vis_stack_host(vis, class_off, members, w=wy, g=gl, dtype=dtype)
+    use = np.nonzero(gfac > 0)[0]
+    i, j = members[use, 0], members[use, 1]
+    v = np.asarray(vis).astype(dtype)[..., use, :]
+    om = np.broadcast_to(gfac[use, None].astype(real), v.shape)
+    if w is not None:
+        om = om * np.broadcast_to(np.asarray(w).astype(real), np.shape(vis))[..., use, :]
+    gb = np.broadcast_to(gl, v.shape[:-2] + gl.shape[-2:])
+    gi, gj, yc = gb[..., i, :], gb[..., j, :], y[..., cls[use], :]
+    ay2 = yc.real**2 + yc.imag**2
+    num = np.zeros((nfeed,) + v.shape[:-2] + v.shape[-1:], dtype=dtype)
+    den = np.zeros(num.shape, dtype=real)
+    first = lambda x: np.moveaxis(x, -2, 0)
+    np.add.at(num, i, first(om * (v * gj * yc.conj())))
+    np.add.at(num, j, first(om * (v.conj() * gi * yc)))
+    np.add.at(den, i, first(om * ((gj.real**2 + gj.imag**2) * ay2)))
+    np.add.at(den, j, first(om * ((gi.real**2 + gi.imag**2) * ay2)))
+    num, den = np.moveaxis(num, 0, -2), np.moveaxis(den, 0, -2)
+    some = den > 0
+    gh = np.where(some, num / np.where(some, den, 1), gb)
+    gn = ((1 - real.type(damping)) * gb + real.type(damping) * gh).astype(dtype)
+    gn = np.where(some, gn, gb)
+    d = np.abs(gn - gb)
+    step = np.where(d == 0, 0, d / np.where(d == 0, 1, np.abs(gb))).max(axis=-2)
+    return gn, y, step
+
+
+def redcal_solve_host(vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,
+                      dtype=np.complex128, nfeed=None):
+    """`Context.redcal_solve` in numpy, computed in `dtype`: (g, y, info) with info = dict(iters, step, chi2), each
+    [..., ntime].  A sample freezes after the first iteration whose step is below tol (its y is then computed once more
+    from its final g); one that reaches maxiter with step >= tol keeps the y of its last iteration."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    real = _real_dtype(dtype)
+    vl = np.asarray(vis).astype(dtype)
+    if g0 is None:
+        nfeed = (int(members.max()) + 1 if members.size else 0) if nfeed is None else nfeed
+        if feed_weight is not None:
+            nfeed = len(feed_weight)
+        g = np.ones(vl.shape[:-2] + (nfeed, vl.shape[-1]), dtype=dtype)
+    else:
+        g = np.array(np.broadcast_to(np.asarray(g0).astype(dtype), vl.shape[:-2] + np.shape(g0)[-2:]))
+    if not (0 < damping <= 1) or not (tol >= 0 and np.isfinite(tol)) or maxiter < 1:
+        raise ValueError("redcal_solve_host: damping in (0, 1], tol >= 0 and finite, maxiter >= 1 expected")
+    sshape = vl.shape[:-2] + vl.shape[-1:]
+    active = np.ones(sshape, dtype=bool)
+    iters = np.zeros(sshape, dtype=np.int32)
+    step = np.zeros(sshape, dtype=real)
+    y = None
+    for k in range(1, maxiter + 1):
+        gn, yk, st = redcal_step_host(vl, class_off, members, g, w=w, feed_weight=feed_weight, damping=damping, dtype=dtype)
+        a = active[..., None, :]
+        y = yk if y is None else np.where(a, yk, y)
+        g = np.where(a, gn, g)
+        step = np.where(active, st, step)
+        iters[active] = k
+        active = active & ~(st < tol)
+        if not active.any():
+            break
+    done = ~active
+    if done.any():
+        _, yk, _ = redcal_step_host(vl, class_off, members, g, w=w, feed_weight=feed_weight, damping=damping, dtype=dtype)
+        y = np.where(done[..., None, :], yk, y)
+    return g, y, dict(iters=iters, step=step, chi2=redcal_chi2_host(vl, class_off, members, g, y, w=w, feed_weight=feed_weight,
+                                                                   dtype=dtype))
+
+
+def redcal_chi2_host(vis, class_off, members, g, y, w=None, feed_weight=None, dtype=np.complex128):
+    """chi^2 = sum_m omega_m |V_m - g_i conj(g_j) y_c|^2 [..., ntime] in `dtype`, omega = w gfac of `redcal_weights`."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    real = _real_dtype(dtype)
+    gl = np.asarray(g).astype(dtype)
+    _, gfac = redcal_weights(class_off, members, gl.shape[-2], feed_weight)
+    res = np.asarray(vis).astype(dtype) - vis_expand_host(y, class_off, members, g=gl, dtype=dtype)
+    om = gfac[:, None].astype(real)
+    if w is not None:
+        om = om * np.asarray(w).astype(real)
+    return (om * (res.real**2 + res.imag**2)).sum(axis=-2)
+
+
+def redcal_degeneracies(class_off, members, nfeed, feed_weight=None):
+    """(D_amp, D_ph): orthonormal bases (nfeed, k) of the gain transformations chi^2 of the redundant calibration cannot
+    see: ln |g_a| -> ln |g_a| + eta_a with eta_i + eta_j constant on every class, and
+    arg g_a -> arg g_a + psi_a with psi_i - psi_j constant on every class — the null spaces of the integer matrices with one
+    row per constrained member (gfac > 0 of `redcal_weights`) beyond the first of its class, e_i + e_j - e_i0 - e_j0 and
+    e_i - e_j - e_i0 + e_j0.  The nfeed x nfeed Gram matrices are accumulated from the four non-zeros of each row; kept
+    are the eigenvectors of `numpy.linalg.eigh` whose eigenvalue is at most 1e-9 of the largest."""
+    class_off = np.asarray(class_off, dtype=np.int64)
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    _, gfac = redcal_weights(class_off, members, nfeed, feed_weight)
+    n = np.diff(class_off)
+    cls = np.repeat(np.arange(n.shape[0]), n)
+    use = np.nonzero(gfac > 0)[0]
+    head = np.full(n.shape[0], -1, dtype=np.int64)
+    head[cls[use][::-1]] = use[::-1]                                        # the first constrained member of every class
+    rest = use[use != head[cls[use]]]
+    idx = np.concatenate([members[rest], members[head[cls[rest]]]], axis=1)  # (rows, 4): i, j, i0, j0
+    bases = []
+    for sign in (np.array([1.0, 1.0, -1.0, -1.0]), np.array([1.0, -1.0, -1.0, 1.0])):
+        gram = np.zeros((nfeed, nfeed))
+        np.add.at(gram, (idx[:, :, None], idx[:, None, :]), np.broadcast_to(np.outer(sign, sign), (idx.shape[0], 4, 4)))
+        lam, vec = np.linalg.eigh(gram)
+        bases.append(np.ascontiguousarray(vec[:, lam <= 1e-9 * max(lam.max(), 0.0)]) if nfeed else np.zeros((0, 0)))
+    return bases[0], bases[1]
+
+
+def fix_degeneracies(g, y, class_off, members, ref=None, feed_weight=None, bases=None):
+    """Take out of the solved gains g [..., nfeed, ntime] what the redundancy cannot determine, per sample: from
+    ln(g / ref) the projection of its real part on D_amp and of its imaginary part on D_ph (`redcal_degeneracies`, or
+    `bases` = (D_amp, D_ph)) is removed; ref (broadcastable against g) defaults to ones.  y_c [..., npairs, ntime] is
+    multiplied by the inverse factor of one weighted member of its class, so that every g_i conj(g_j) y_c is unchanged.
+    Returns (g, y) complex128.  The phase part assumes |arg(g / ref)| < pi.  Numpy on the host: not a kernel."""
+    class_off = np.asarray(class_off, dtype=np.int64)
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    g = np.asarray(g, dtype=np.complex128)
+    y = np.asarray(y, dtype=np.complex128)
+    nfeed = g.shape[-2]
+    d_amp, d_ph = redcal_degeneracies(class_off, members, nfeed, feed_weight) if bases is None else bases
+    ratio = g if ref is None else g / np.broadcast_to(np.asarray(ref, dtype=np.complex128), g.shape)
+    la, lp = np.log(np.abs(ratio)), np.angle(ratio)
+    pa = np.einsum("ab,cb,...ct->...at", d_amp, d_amp, la)
+    pp = np.einsum("ab,cb,...ct->...at", d_ph, d_ph, lp)
+    h = np.exp(-(pa + 1j * pp))                                             # g_new = h g
+    yfac, _ = redcal_weights(class_off, members, nfeed, feed_weight)
+    n = np.diff(class_off)
+    cls = np.repeat(np.arange(n.shape[0]), n)
+    use = np.nonzero(yfac > 0)[0]
+    head = np.full(n.shape[0], -1, dtype=np.int64)
+    head[cls[use][::-1]] = use[::-1]
+    has = head >= 0
+    fac = np.ones(y.shape, dtype=np.complex128)
+    fac[..., has, :] = h[..., members[head[has], 0], :] * h[..., members[head[has], 1], :].conj()
+    return h * g, y / fac
+
+
 def _member_sigma(tel, freqs, ndays, ntime, class_off):
     """sigma[f, m] = sqrt(n_c ntime noisepower(c, f, ndays)) of the unstacked noise: the plain mean of a complete class
     then has the noise level of the stacked simulators."""
@@ -1418,9 +1591,9 @@ def _unstacked_chunks(m, nreal, maps, ndays, resolution, seed, skymodels, klname
             del g
 
 
-def _write_sim_file(tstream, fi, data, tphi, gain=None, weight=None, table=None):
+def _write_sim_file(tstream, fi, data, tphi, gain=None, weight=None, table=None, extra=None):
     """One per-frequency file with the datasets and attributes of `simulate_ensemble`; `table` (class_off, members) marks
-    it unstacked (attribute `unstacked`, datasets `members` and `class_off`)."""
+    it unstacked (attribute `unstacked`, datasets `members` and `class_off`); `extra`: further datasets by name."""
     tel, bt = tstream.telescope, tstream.beamtransfer
     os.makedirs(tstream._fdir(fi), exist_ok=True)
     with storage.File(tstream._ffile(fi), "w") as f:
@@ -1430,6 +1603,8 @@ def _write_sim_file(tstream, fi, data, tphi, gain=None, weight=None, table=None)
             f.create_dataset("gain", data=np.ascontiguousarray(gain))
         if weight is not None:
             f.create_dataset("weight", data=np.ascontiguousarray(weight))
+        for name, value in (extra or {}).items():
+            f.create_dataset(name, data=np.ascontiguousarray(value))
         if table is not None:
             f.create_dataset("class_off", data=np.asarray(table[0]))
             f.create_dataset("members", data=np.asarray(table[1]))
@@ -1639,14 +1814,23 @@ def _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed
     return tss
 
 
-def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0):
+REDCAL_DEFAULTS = dict(damping=0.4, tol=1e-10, maxiter=500, reference=None)
+
+
+def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None):
     """Stack the unstacked Timestream directory `indir` (`simulate_ensemble(unstacked=True)`, or a correlator's per-pair
     data in that layout) into the unique baselines of the telescope of ProductManager `m` and write them to `outdir` in
     the layout of `simulate_ensemble`; returns the `Timestream` of `outdir`.
 
     Per frequency the rows (nmem, ntime) go through `Context.vis_stack` with the file's `weight` (when it has one) as the
-    per-sample weights.  calibrate: None (or "none"), "file" — the dataset `gain` (nfeed, ntime) of every file — or an
-    explicit complex128 array / tensor (nfreq, nfeed, ntime) of calibration gains.  feed_weight (nfeed) >= 0 weights
+    per-sample weights.  calibrate: None (or "none"), "file" — the dataset `gain` (nfeed, ntime) of every file — an
+    explicit complex128 array / tensor (nfreq, nfeed, ntime) of calibration gains, or "redundant": the gains are solved
+    from the redundancy of the data itself (`Context.redcal_solve`) per chunk of frequencies,
+    their degeneracies are fixed (`fix_degeneracies`) against the `reference` of the dict `redcal` — None: ones, "file":
+    the dataset `gain`, or an array (nfreq, nfeed, ntime) — and the stack runs with them; `redcal` also holds the
+    solver's `damping`, `tol` and `maxiter` (REDCAL_DEFAULTS).  A sample whose solve did not converge gets weight 0 and is
+    counted (a warning of the module's logger, and `redcal_not_converged` of `sim_log`); the stacked files then also hold
+    `gain_solution` (nfeed, ntime) and `redcal_iters` (ntime).  feed_weight (nfeed) >= 0 weights
     every pair by the product of its two feeds' entries; dead_feeds lists feeds of weight 0.  Ranks take their own
     frequencies, in chunks that fit in `chunk_gb`.
 
@@ -1670,8 +1854,8 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
         if not (np.array_equal(f["class_off"][:], class_off) and np.array_equal(f["members"][:], members)):
             raise ValueError("%s was written for another class table than this telescope's" % src.directory)
     if isinstance(calibrate, str):
-        if calibrate not in ("file", "none"):
-            raise ValueError('calibrate is None, "none", "file" or an array (nfreq, nfeed, ntime)')
+        if calibrate not in ("file", "none", "redundant"):
+            raise ValueError('calibrate is None, "none", "file", "redundant" or an array (nfreq, nfeed, ntime)')
         calibrate = None if calibrate == "none" else calibrate
     elif calibrate is not None:
         if hasattr(calibrate, "data_ptr"):
@@ -1680,6 +1864,24 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
         if calibrate.shape != (nfreq, nfeed, ntime):
             raise ValueError("calibrate %s is not (nfreq, nfeed, ntime) = (%d, %d, %d)"
                              % (calibrate.shape, nfreq, nfeed, ntime))
+    redundant = isinstance(calibrate, str) and calibrate == "redundant"
+    if redcal is not None and not redundant:
+        raise ValueError('redcal belongs to calibrate="redundant"')
+    if redundant:
+        if set(redcal or {}) - set(REDCAL_DEFAULTS):
+            raise ValueError("redcal holds %s, not in %s" % (sorted(set(redcal) - set(REDCAL_DEFAULTS)), sorted(REDCAL_DEFAULTS)))
+        rconf = dict(REDCAL_DEFAULTS, **(redcal or {}))
+        reference = rconf.pop("reference")
+        rconf = dict(damping=float(rconf["damping"]), tol=float(rconf["tol"]), maxiter=int(rconf["maxiter"]))
+        if isinstance(reference, str):
+            if reference not in ("file", "none"):
+                raise ValueError('redcal reference is None, "file" or an array (nfreq, nfeed, ntime)')
+            reference = None if reference == "none" else reference
+        elif reference is not None:
+            reference = np.asarray(reference.cpu().numpy() if hasattr(reference, "data_ptr") else reference, dtype=np.complex128)
+            if reference.shape != (nfreq, nfeed, ntime):
+                raise ValueError("redcal reference %s is not (nfreq, nfeed, ntime) = (%d, %d, %d)"
+                                 % (reference.shape, nfreq, nfeed, ntime))
     fw = None
     if feed_weight is not None or len(dead_feeds) > 0:
         fw = np.ones(nfeed, dtype=np.float64) if feed_weight is None else np.array(feed_weight, dtype=np.float64)
@@ -1694,6 +1896,10 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
         weighted = "weight" in f
     per_f = ntime * (16.0 * nmem + (8.0 * nmem if weighted else 0.0) + (16.0 * nfeed if calibrate is not None else 0.0)
                      + 24.0 * npairs)
+    if redundant:   # g, the second gain buffer and y of the solver, its three per-sample outputs and its state words
+        per_f += ntime * (32.0 * nfeed + 16.0 * npairs + 20.0 + 24.0)
+        bases = redcal_degeneracies(class_off, members, nfeed, fw)
+    solved, lost = {}, 0
     step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
     log = sim_log
     nmem_c = np.diff(class_off)[:, None].astype(np.float64)
@@ -1708,15 +1914,38 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
                     if weighted:
                         w.append(np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f
                                  else np.ones((nmem, ntime), dtype=np.float64))
-                    if isinstance(calibrate, str):
+                    if redundant:
+                        if isinstance(reference, str):
+                            if "gain" not in f:
+                                raise ValueError('redcal reference "file": %s holds no dataset `gain`' % src._ffile(fi))
+                            g.append(np.asarray(f["gain"][:], dtype=np.complex128))
+                    elif isinstance(calibrate, str):
                         if "gain" not in f:
                             raise ValueError('calibrate="file": %s holds no dataset `gain`' % src._ffile(fi))
                         g.append(np.asarray(f["gain"][:], dtype=np.complex128))
             if calibrate is not None and not isinstance(calibrate, str):
                 g = [calibrate[fi] for fi in fs]
+        vis_d = w_d = None
+        if redundant:
+            with _StepTimer(log, "redcal"):
+                vis_d = ctx.to_device(np.stack(vis)[None])
+                w_d = ctx.to_device(np.stack(w)[None]) if weighted else None
+                gs, ys, info = ctx.redcal_solve(vis_d, class_off, members, w=w_d,
+                                                feed_weight=np.ones(nfeed) if fw is None else fw, **rconf)
+                ref = np.stack(g) if isinstance(reference, str) else (None if reference is None else reference[list(fs)])
+                gfix, _ = fix_degeneracies(ctx.to_host(gs)[0], ctx.to_host(ys)[0], class_off, members, ref=ref,
+                                           feed_weight=fw, bases=bases)
+                its, failed = ctx.to_host(info["iters"])[0], ~(ctx.to_host(info["step"])[0] < rconf["tol"])
+                del gs, ys, info
+            g = list(gfix)
+            for k, fi in enumerate(fs):
+                solved[fi] = (gfix[k], its[k], failed[k])
+            lost += int(failed.sum())
         with _StepTimer(log, "stack"):
-            out, wout = ctx.vis_stack(ctx.to_device(np.stack(vis)[None]), class_off, members,
-                                      w=ctx.to_device(np.stack(w)[None]) if weighted else None,
+            if vis_d is None:
+                vis_d = ctx.to_device(np.stack(vis)[None])
+                w_d = ctx.to_device(np.stack(w)[None]) if weighted else None
+            out, wout = ctx.vis_stack(vis_d, class_off, members, w=w_d,
                                       g=ctx.to_device(np.stack(g)[None]) if calibrate is not None else None, feed_weight=fw)
             out, wout = ctx.to_host(out)[0], ctx.to_host(wout)[0]
         share = np.ones((npairs, 1), dtype=np.float64)
@@ -1729,6 +1958,8 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
             else:
                 share_k = np.broadcast_to(share, (npairs, ntime))
             stacked[fi], wts[fi] = out[k], np.where(wout[k] == 0, 0.0, share_k)
+            if redundant:
+                wts[fi] = np.where(solved[fi][2][None, :], 0.0, wts[fi])
     # every rank writes `weight` or none does: the m-mode routes choose their path by the file of frequency 0
     mine = any(np.any(wv != 1.0) for wv in wts.values())
     nranks = parallel.size() if parallel._dist() else 1
@@ -1737,7 +1968,14 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     with _StepTimer(log, "write"):
         for fi in freqs:
-            _write_sim_file(dst, fi, stacked[fi], tphi, weight=wts[fi] if write_w else None)
+            _write_sim_file(dst, fi, stacked[fi], tphi, weight=wts[fi] if write_w else None,
+                            extra=dict(gain_solution=solved[fi][0], redcal_iters=solved[fi][1]) if redundant else None)
+    if redundant and lost:
+        logging.getLogger(__name__).warning("stack_baselines: the redundant calibration of %d of %d samples did not converge "
+                                            "in %d iterations; they are written with weight 0", lost, len(freqs) * ntime,
+                                            rconf["maxiter"])
+        if log is not None:
+            log["redcal_not_converged"] = log.get("redcal_not_converged", 0) + lost
     parallel.barrier()
     if parallel.rank0():
         os.makedirs(dst.directory, exist_ok=True)

@@ -766,6 +766,39 @@ int dm_vis_expand(dm_ctx* ctx, int nreal, int g_nreal, int nf, int nfeed, int np
                   const int* class_off_host, const int* members_host, const void* g_dev, const void* sky_dev, void* out_dev,
                   int64_t sky_rstride, int64_t out_rstride, int accumulate);
 
+/* ---- redundant-baseline calibration -------------------------------------------------- */
+/* dm_redcal_solve: per-feed gains g and class visibilities y from the redundancy of the class table alone.  Every
+ * (realisation, frequency, time sample) is a problem of its own: minimise
+ *   chi^2 = sum_m omega_m |V_m - g_i conj(g_j) y_c|^2,   omega_m = w[m] fw[i] fw[j], but 0 for i == j and 0 on every
+ *   member of a class with fewer than two members of i != j and fw[i] fw[j] > 0 (a rule of the table and fw alone)
+ * by the damped alternating fixed point, from g0:
+ *   y_c = sum omega' conj(g_i) g_j V / sum omega' |g_i|^2 |g_j|^2 (0 where the denominator is 0; omega' is omega without
+ *         the second exclusion, so that a class that constrains nothing still gets its calibrated mean)
+ *   gh_a = [sum_{m=(a,j)} omega V conj(z) + sum_{m=(i,a)} omega conj(V) conj(z')] / [sum omega |z|^2 + sum omega |z'|^2],
+ *         z = conj(g_j) y_c, z' = conj(g_i y_c)  (g_a where the denominator is 0)
+ *   g_a <- (1 - damping) g_a + damping gh_a;   step = max_a |delta g_a| / |g_a|  (|g_a| before the update)
+ * A sample freezes after the first iteration whose step is below tol: its g no longer changes, its y is computed once
+ * more from the final g, iters is that iteration and step its step.  A sample that reaches maxiter with step >= tol
+ * keeps the y of its last iteration and reports iters = maxiter and that step: it is not converged, not refused.
+ *   vis_dev   (nreal, nf, nmem, ntime) c128, vis_rstride elements between realisations (0: contiguous)
+ *   w_dev     contiguous (w_nreal, nf, nmem, ntime) f64 >= 0, w_nreal = 1 or nreal; null: ones
+ *   feed_weight_host (nfeed) f64 >= 0 or null;   g0_dev contiguous (nreal, nf, nfeed, ntime) c128 or null: ones
+ *   g_dev (nreal, nf, nfeed, ntime) c128, y_dev (nreal, nf, npairs, ntime) c128, iters_dev i32, step_dev f64 and
+ *   chi2_dev f64 (nreal, nf, ntime), all contiguous; chi2 is chi^2 at the returned g and y; every element is written
+ * Two kernels per iteration on the context's stream: the y step with the arithmetic and summation order of dm_vis_stack,
+ * and the gain step, feed-major over an incidence table, which writes the new gains to a second buffer.  The host never
+ * waits inside the loop; every 16 iterations it asks, without waiting, whether a sample is left and stops launching
+ * once none is.  No floating-point atomics: g, y, iters, step and chi2 of a sample are the same bits alone, in any batch,
+ * at any position of a tile and beside any neighbours.  Refused before any launch (dm_last_error): everything
+ * dm_vis_stack refuses with gains, damping outside (0, 1], tol negative or not finite, maxiter < 1, a null output (or
+ * vis) with work to do, an output sharing an element with vis, w, g0 or another output.  nreal, nf or ntime = 0 is a
+ * no-op.  Returns when the last launch is queued.  No counterpart in the reference, whose data begins at stacked
+ * baselines. */
+int dm_redcal_solve(dm_ctx* ctx, int nreal, int w_nreal, int nf, int nfeed, int npairs, int ntime,
+                    const int* class_off_host, const int* members_host, const void* vis_dev, const double* w_dev,
+                    const double* feed_weight_host, const void* g0_dev, double damping, double tol, int maxiter,
+                    void* g_dev, void* y_dev, int* iters_dev, double* step_dev, double* chi2_dev, int64_t vis_rstride);
+
 #ifdef __cplusplus
 }
 #endif
