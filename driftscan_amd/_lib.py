@@ -213,6 +213,9 @@ SIGNATURES = {
     "dm_redcal_solve": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp,
                 ctypes.POINTER(c_dbl), c_vp, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "dm_sidereal_regrid": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
+    "dm_sidereal_max_taps": (c_int, []),
 }
 
 _lib = None
@@ -1053,6 +1056,55 @@ def _vis_expand(self, sky, class_off, members, g=None, out=None, accumulate=Fals
 
 Context.vis_stack = _vis_stack
 Context.vis_expand = _vis_expand
+
+
+def _sidereal_regrid(self, x, phi0, dphi, ntime, w=None, a=3, min_share=1.0, acc=None, variance=True):
+    """One day of every row resampled onto the sidereal grid and written to, or added to, the accumulators of the stack
+    (dm_sidereal_regrid; `timestream.sidereal_regrid_host` restates one day).  x (nf, nrow,
+    nt_in) complex128, contiguous, sampled at phi0 + j dphi; w float64 of that shape or None (ones): the inverse noise
+    variance of a sample relative to nominal, flagged where `w > 0` is false, and the data of a flagged sample reaches
+    nothing.  Returns the accumulator tuple (sum, wsum, sq, hits), each (nf, nrow, ntime): complex128, float64, float64
+    and int32.  acc=None allocates and writes it (sq and hits are None with variance=False); an `acc` given is added to
+    and returned, its samples that are not valid this day untouched.  mean = sum / wsum where wsum > 0, and
+    (sq - |sum|^2 / wsum) / (hits - 1) estimates the variance of one nominal input sample where hits >= 2.  wsum is the
+    diagonal weight only: neighbouring samples share taps and are correlated.  The bits of a row do not depend on the
+    batch it is in."""
+    if not (_is_c128(x) and x.dim() == 3):
+        raise ValueError("sidereal_regrid: contiguous complex128 tensor x (nf, nrow, nt_in) expected")
+    nf, nrow, nt_in = (int(v) for v in x.shape)
+    ntime = int(ntime)
+    if w is not None and not (hasattr(w, "data_ptr") and not w.is_complex() and w.element_size() == 8 and w.is_contiguous()
+                              and w.dtype.is_floating_point and tuple(w.shape) == tuple(x.shape)):
+        raise ValueError("sidereal_regrid: w must be a contiguous float64 tensor of x's shape")
+    shape = (nf, nrow, max(ntime, 0))
+    if acc is None:
+        accumulate = 0
+        acc = (self.empty(shape, np.complex128), self.empty(shape, np.float64),
+               self.empty(shape, np.float64) if variance else None,
+               self.torch.empty(shape, dtype=self.torch.int32, device=x.device) if variance else None)
+    else:
+        accumulate = 1
+        acc = tuple(acc)
+        if len(acc) != 4:
+            raise ValueError("sidereal_regrid: acc is the tuple (sum, wsum, sq, hits)")
+    s_, ws_, sq_, h_ = acc
+    ok = (_is_c128(s_) and tuple(s_.shape) == shape and hasattr(ws_, "data_ptr") and tuple(ws_.shape) == shape
+          and ws_.is_contiguous() and ws_.dtype == self.torch.float64)
+    ok = ok and (sq_ is None or (hasattr(sq_, "data_ptr") and tuple(sq_.shape) == shape and sq_.is_contiguous()
+                                 and sq_.dtype == self.torch.float64))
+    ok = ok and (h_ is None or (hasattr(h_, "data_ptr") and tuple(h_.shape) == shape and h_.is_contiguous()
+                                and h_.dtype == self.torch.int32))
+    if not ok:
+        raise ValueError("sidereal_regrid: acc must hold contiguous tensors (nf, nrow, ntime): sum complex128, wsum float64, "
+                         "sq float64 or None, hits int32 or None")
+    rc = self.lib.dm_sidereal_regrid(self.h, nf, nrow, nt_in, ntime, int(a), float(phi0), float(dphi), float(min_share),
+                                     self.ptr(x), self.ptr(w), self.ptr(s_), self.ptr(ws_), self.ptr(sq_), self.ptr(h_),
+                                     accumulate)
+    self.check(rc, "dm_sidereal_regrid")
+    return acc
+
+
+Context.sidereal_regrid = _sidereal_regrid
 
 
 def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,

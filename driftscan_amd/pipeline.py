@@ -71,6 +71,8 @@ class PipelineManager(config.Reader):
         self.simulations = {}
         self.stacks = {}
         self.unstacked = {}
+        self.sidereal = {}
+        self.days = {}
         self.crosspower = []
 
     @classmethod
@@ -106,6 +108,12 @@ class PipelineManager(config.Reader):
                 self.simulations[tsconf["name"]] = tsconf["simulate"]
             if "stack_from" in tsconf:
                 self.stacks[tsconf["name"]] = dict(tsconf["stack_from"])
+            if "sidereal_from" in tsconf:
+                self.sidereal[tsconf["name"]] = dict(tsconf["sidereal_from"])
+        # a stacked day of a `sidereal_from` entry is that entry's input, not a timestream the stages below run on
+        daydirs = {os.path.abspath(fixpath(d)) for conf in self.sidereal.values() for d in conf.get("days", ())}
+        for name in [n for n, ts in self.timestreams.items() if ts.directory in daydirs]:
+            self.days[name] = self.timestreams.pop(name)
         if "crosspower" in yconf:
             self.crosspower = list(yconf["crosspower"] or [])
 
@@ -141,7 +149,7 @@ class PipelineManager(config.Reader):
         """Make the timestreams that carry a `stack_from` block and whose directory does not exist yet: the unstacked
         directory named there goes through `timestream.stack_baselines`."""
         for tsname, conf in self.stacks.items():
-            ts = self.timestreams[tsname]
+            ts = self.days[tsname] if tsname in self.days else self.timestreams[tsname]
             if os.path.exists(ts.directory):
                 logger.info("Timestream %s exists already, not stacked again.", tsname)
                 continue
@@ -150,11 +158,21 @@ class PipelineManager(config.Reader):
                                        calibrate=None if calibrate in (None, "none") else calibrate,
                                        dead_feeds=tuple(conf.get("dead_feeds", ()) or ()), chunk_gb=self.chunk_gb,
                                        **({"redcal": dict(conf["redcal"])} if conf.get("redcal") else {}))
+        # `sidereal_from: {days: [dir, ...], a: 3, min_share: 1.0}`: the days, which may be the stacks made above, are
+        # regridded and averaged by `timestream.sidereal_stack`
+        for tsname, conf in self.sidereal.items():
+            ts = self.timestreams[tsname]
+            if os.path.exists(ts.directory):
+                logger.info("Timestream %s exists already, not stacked over its days again.", tsname)
+                continue
+            timestream.sidereal_stack(ts.manager, [fixpath(d) for d in conf["days"]], ts.directory,
+                                      ntime=conf.get("ntime", None), a=int(conf.get("a", 3)),
+                                      min_share=float(conf.get("min_share", 1.0)), chunk_gb=self.chunk_gb)
 
     def generate(self):
         """Run the stages that are switched on, for every timestream, in the reference's order: m-modes and SVD modes, KL
         modes (collected into one file per filter if `collect_klmodes`), power spectra and cross-power spectra, maps.
-        Entries with a `stack_from` block are stacked first (`stack`)."""
+        Entries with a `stack_from` block are stacked first, then those with a `sidereal_from` block (`stack`)."""
         self.stack()
         for tsobj in self.timestreams.values():
             os.makedirs(tsobj.output_directory, exist_ok=True)

@@ -1965,7 +1965,8 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     nranks = parallel.size() if parallel._dist() else 1
     write_w = any(parallel.exchange([mine] * nranks))
     dst = Timestream(outdir, m)
-    tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
+    with storage.File(src._ffile(0), "r") as f:   # a day keeps its own sample positions (section 4.19)
+        tphi = np.asarray(f["phi"][:]) if "phi" in f else np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     with _StepTimer(log, "write"):
         for fi in freqs:
             _write_sim_file(dst, fi, stacked[fi], tphi, weight=wts[fi] if write_w else None,
@@ -1982,3 +1983,337 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
         dst.save()
     parallel.barrier()
     return dst
+
+
+# ---- sidereal stacking -------------------------------------------------------------------
+
+SIDEREAL_SNAP = 1e-9          # positions are known to this fraction of a sample (what `sidereal_stack` asks of `phi`)
+T_SIDEREAL_DAY = 86164.0905   # seconds
+
+
+def _ld_pi():
+    return np.longdouble("3.14159265358979323846264338327950288")
+
+
+def _sidereal_stretch(step):
+    """s = max(1, (2 pi / ntime) / dphi): the kernel is stretched to the coarser of the two spacings; a ratio within
+    SIDEREAL_SNAP of 1 is 1."""
+    one = np.longdouble(1)
+    return one if (step <= one or abs(step - one) <= SIDEREAL_SNAP) else step
+
+
+def _ld_sinc(t):
+    """sin(pi t) / (pi t) in long double, sin taken of t - round(t) so that the zeros are exact."""
+    t = np.asarray(t, dtype=np.longdouble)
+    r = np.round(t)
+    sn = np.sin(_ld_pi() * (t - r))
+    sn = np.where(np.mod(np.abs(r), 2) == 1, -sn, sn)
+    safe = np.where(t == 0, np.longdouble(1), t)
+    return np.where(t == 0, np.longdouble(1), sn / (_ld_pi() * safe))
+
+
+def _dot2(c, x):
+    """sum_t c[..., t] x[..., t] over the last axis as if in twice the working precision (the error-free products and
+    sums of Ogita, Rump and Oishi's Dot2, products split after Veltkamp), in tap order: the tap sum of
+    dm_sidereal_regrid, which needs |xh|^2 to a few ulps even where the taps cancel.  c real, x real or complex."""
+    if np.iscomplexobj(x):
+        return _dot2(c, x.real) + 1j * _dot2(c, x.imag)
+    real = np.result_type(c, x).type
+    factor = real(2.0 ** ((np.finfo(real).nmant + 2) // 2) + 1.0)
+    shape = np.broadcast_shapes(c.shape, x.shape)[:-1]
+    s, e = np.zeros(shape, dtype=real), np.zeros(shape, dtype=real)
+    for t in range(c.shape[-1]):
+        a, b = c[..., t], x[..., t]
+        p = a * b
+        ca, cb = factor * a, factor * b
+        ah, bh = ca - (ca - a), cb - (cb - b)
+        al, bl = a - ah, b - bh
+        pe = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+        tt = s + p
+        z = tt - s
+        e = e + (((s - (tt - z)) + (p - z)) + pe)
+        s = tt
+    return s + e
+
+
+def sidereal_taps_host(nt_in, ntime, a, phi0, dphi):
+    """The tap geometry of one day (dm_sidereal_table.h restates it in C++), in long double: a
+    list over the grid samples k of (first, c) — c_j of the input samples j = first, first + 1, ..., with exact zeros
+    trimmed from both ends (a zero inside is not a tap); j may lie outside [0, nt_in)."""
+    ld = np.longdouble
+    twopi = 2 * _ld_pi()
+    nt_in, ntime, a = int(nt_in), int(ntime), int(a)
+    dp = ld(float(dphi))
+    if not (1 <= a <= 8):
+        raise ValueError("a outside 1..8")
+    if not (np.isfinite(float(phi0)) and np.isfinite(float(dphi)) and dp > 0):
+        raise ValueError("phi0 or dphi not finite, or dphi <= 0")
+    if ntime < 1 or nt_in < 0 or not (max(nt_in - 1, 0) * dp < twopi):
+        raise ValueError("ntime < 1, or the day is not less than one turn")
+    P, step = twopi / dp, (twopi / ntime) / dp
+    s = _sidereal_stretch(step)
+    p0 = np.fmod(ld(float(phi0)), twopi)
+    if p0 < 0:
+        p0 += twopi
+    taps = []
+    for k in range(ntime):
+        u = (twopi * k / ntime - p0) / dp
+        if u < 0:
+            u += P
+        r = np.round(u)
+        if abs(u - r) <= SIDEREAL_SNAP:
+            u = ld(0) if r >= P - SIDEREAL_SNAP else r
+        jlo, jhi = int(np.ceil(u - a * s)), int(np.floor(u + a * s))
+        j = np.arange(jlo, jhi + 1)
+        t = (u - j.astype(ld)) / s
+        c = np.where(np.abs(t) < a, _ld_sinc(t) * _ld_sinc(t / a), ld(0))
+        nz = np.nonzero(c)[0]
+        if nz.size:
+            taps.append((jlo + int(nz[0]), c[nz[0] : nz[-1] + 1]))
+        else:
+            taps.append((jlo, np.zeros(0, dtype=ld)))
+    return taps
+
+
+def sidereal_regrid_host(x, w, phi0, dphi, ntime, a=3, min_share=1.0, dtype=np.complex128, details=False):
+    """One day resampled onto the sidereal grid, the numpy statement of `Context.sidereal_regrid` (DESIGN.md section
+    4.19): x (..., nt_in) sampled at phi0 + j dphi, w of the same shape or None (ones).  Returns (xh, W), both
+    (..., ntime): the regridded value and its weight, 0 where the sample is not valid.  The geometry is made in long
+    double and rounded to double, as the device's table is: the rounded c_j ARE the coefficients of the method, for
+    every `dtype`.  The sums run in `dtype`, which may be np.clongdouble; the tap sum of x is compensated (`_dot2`).  details=True also returns a dict with `bound` = sum_j |c_j / S| |x_j| over the unflagged taps
+    and `ntaps` (ntime), the taps of every grid sample."""
+    if not (0.0 < float(min_share) <= 1.0):
+        raise ValueError("min_share outside (0, 1]")
+    real = _real_dtype(dtype).type
+    x = np.asarray(x, dtype=dtype)
+    nt_in = x.shape[-1]
+    ok = np.ones(x.shape, dtype=bool) if w is None else np.asarray(w) > 0
+    wi = np.ones(x.shape, dtype=real) if w is None else np.where(ok, 1 / np.where(ok, np.asarray(w, dtype=real), 1), 0)
+    xz = np.where(ok, x, 0)
+    taps = sidereal_taps_host(nt_in, ntime, a, phi0, dphi)
+    shape = x.shape[:-1] + (int(ntime),)
+    xh, W, bound = np.zeros(shape, dtype=dtype), np.zeros(shape, dtype=real), np.zeros(shape, dtype=real)
+    for k, (first, cl) in enumerate(taps):
+        c = cl.astype(np.float64).astype(real)
+        A_all, S_all, nt = real(np.float64(np.abs(cl).sum())), real(np.float64(cl.sum())), int(np.count_nonzero(cl))
+        j = first + np.arange(c.shape[0])
+        inside = (j >= 0) & (j < nt_in) & (c != 0)
+        ji, ci = j[inside], c[inside]
+        if ji.size == 0:
+            continue
+        here = ok[..., ji]
+        cm = np.where(here, ci, 0)
+        A, S, nu = np.abs(cm).sum(axis=-1), cm.sum(axis=-1), here.sum(axis=-1)
+        share = (nu == nt) | ((min_share < 1.0) & (A >= real(min_share) * A_all))
+        valid = (nu > 0) & share & (S >= S_all / 2) & (S > 0)
+        Ss = np.where(valid, S, 1)
+        sx = _dot2(cm, xz[..., ji]) / Ss
+        sv = (cm * cm * wi[..., ji]).sum(axis=-1)
+        xh[..., k] = np.where(valid, sx, 0)
+        Wk = Ss * Ss / np.where(valid, sv, 1)
+        if w is not None:   # one tap: S^2 / (c^2 / w) is w itself, bit for bit
+            Wk = np.where(nu == 1, np.where(here, np.where(here, np.asarray(w, dtype=real)[..., ji], 0), 0).sum(axis=-1), Wk)
+        W[..., k] = np.where(valid, Wk, 0)
+        bound[..., k] = np.where(valid, (np.abs(cm) * np.abs(xz[..., ji])).sum(axis=-1) / Ss, 0)
+    if details:
+        return xh, W, dict(bound=bound, ntaps=np.array([int(np.count_nonzero(c)) for _, c in taps]))
+    return xh, W
+
+
+def _day_phi(tstream):
+    """(phi0, dphi, nt_in) of a day directory from the dataset `phi` of its first file: uniformly spaced after unwrapping,
+    to SIDEREAL_SNAP of dphi."""
+    with storage.File(tstream._ffile(0), "r") as f:
+        phi = np.asarray(f["phi"][:], dtype=np.float64)
+    if phi.ndim != 1 or phi.shape[0] < 2:
+        raise ValueError("%s: the dataset phi needs two samples at the least" % tstream.directory)
+    ph = np.unwrap(phi)
+    n = ph.shape[0]
+    dphi = (ph[-1] - ph[0]) / (n - 1)
+    if not (np.all(np.isfinite(ph)) and dphi > 0
+            and np.max(np.abs(ph - (ph[0] + dphi * np.arange(n)))) <= SIDEREAL_SNAP * dphi):
+        raise ValueError("%s: phi is not uniformly spaced (to %g of its step)" % (tstream.directory, SIDEREAL_SNAP))
+    return float(phi[0]), float(dphi), n
+
+
+def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=4.0):
+    """Regrid the days `daydirs` onto the sidereal grid and average them with their weights.
+    Every entry is a Timestream directory, stacked or unstacked, all of one row layout (and one class table): a stretch
+    of samples at the positions of its dataset `phi` (uniformly spaced after unwrapping, else ValueError), with `weight`
+    where present.  Ranks take their own frequencies in chunks that fit `chunk_gb`; within a chunk the days go through
+    `Context.sidereal_regrid` one after the other into one accumulator.  `outdir` gets the layout of the simulators:
+    `timestream` the weighted mean (0 where no day reached the sample), `weight` = wsum / len(daydirs) (always written:
+    the data goes on through the weighted m-mode route, where its scale cancels; it is the diagonal only — neighbouring
+    samples share taps and are correlated), `day_hits` int32, `day_variance` — the day-to-day scatter
+    (sq - |sum|^2 / wsum) / (hits - 1), an estimate of the variance of one nominal input sample, 0 where hits < 2 —
+    when there is more than one day, and the attribute `ndays`.  ntime=None: `_sim_ntime(tel, 0)`.  Returns the
+    Timestream of `outdir`."""
+    ctx = get_context()
+    torch = ctx.torch
+    tel = m.beamtransfer.telescope
+    daydirs = list(daydirs)
+    if not daydirs:
+        raise ValueError("sidereal_stack: no days")
+    ntime = _sim_ntime(tel, 0) if ntime is None else int(ntime)
+    days = [Timestream(d, m) for d in daydirs]
+    geo = [_day_phi(d) for d in days]
+    unst = [d.is_unstacked() for d in days]
+    if any(u != unst[0] for u in unst):
+        raise ValueError("sidereal_stack: stacked and unstacked days cannot be mixed")
+    table = None
+    if unst[0]:
+        for d in days:
+            with storage.File(d._ffile(0), "r") as f:
+                t = (np.asarray(f["class_off"][:]), np.asarray(f["members"][:]))
+            if table is None:
+                table = t
+            elif not (np.array_equal(t[0], table[0]) and np.array_equal(t[1], table[1])):
+                raise ValueError("sidereal_stack: %s was written for another class table" % d.directory)
+    with storage.File(days[0]._ffile(0), "r") as f:
+        nrow = int(f["timestream"].shape[0])
+    freqs = _sim_freqs(tel, None)
+    nt_max = max(g[2] for g in geo)
+    per_f = nrow * (24.0 * nt_max + 36.0 * ntime + 16.0 * ntime)
+    step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
+    log = sim_log
+    dst = Timestream(outdir, m)
+    tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
+    nd = len(days)
+    for c0 in range(0, len(freqs), step):
+        fs = freqs[c0 : c0 + step]
+        acc = None
+        for d, (phi0, dphi, nt_in) in zip(days, geo):
+            with _StepTimer(log, "read"):
+                xs, ws, weighted = [], [], False
+                for fi in fs:
+                    with storage.File(d._ffile(fi), "r") as f:
+                        xd = np.asarray(f["timestream"][:], dtype=np.complex128)
+                        if xd.shape != (nrow, nt_in):
+                            raise ValueError("sidereal_stack: %s holds %s, not (%d, %d)" % (d._ffile(fi), xd.shape, nrow, nt_in))
+                        xs.append(xd)
+                        ws.append(np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f else None)
+                weighted = any(wv is not None for wv in ws)
+                if weighted:
+                    ws = [np.ones((nrow, nt_in), dtype=np.float64) if wv is None else wv for wv in ws]
+            with _StepTimer(log, "regrid"):
+                x_d = ctx.to_device(np.stack(xs))
+                w_d = ctx.to_device(np.stack(ws)) if weighted else None
+                acc = ctx.sidereal_regrid(x_d, phi0, dphi, ntime, w=w_d, a=a, min_share=min_share, acc=acc)
+                del x_d, w_d
+        with _StepTimer(log, "finish"):
+            s_, ws_, sq_, h_ = acc
+            some = ws_ > 0
+            wsafe = torch.where(some, ws_, torch.ones_like(ws_))
+            mean = torch.where(some, s_ / wsafe, torch.zeros_like(s_))
+            var = None
+            if nd > 1:
+                two = h_ >= 2
+                v = (sq_ - (s_.real**2 + s_.imag**2) / wsafe) / torch.where(two, h_ - 1, torch.ones_like(h_)).to(torch.float64)
+                var = ctx.to_host(torch.where(two & some, v, torch.zeros_like(v)))
+            mean_h, w_h, hits_h = ctx.to_host(mean), ctx.to_host(ws_ / float(nd)), ctx.to_host(h_)
+            del acc, s_, ws_, sq_, h_, mean
+        with _StepTimer(log, "write"):
+            for k, fi in enumerate(fs):
+                extra = dict(day_hits=hits_h[k].astype(np.int32))
+                if var is not None:
+                    extra["day_variance"] = var[k]
+                _write_sim_file(dst, fi, mean_h[k], tphi, weight=w_h[k], table=table, extra=extra)
+                with storage.File(dst._ffile(fi), "a") as f:
+                    f.attrs["ndays"] = nd
+    parallel.barrier()
+    if parallel.rank0():
+        os.makedirs(dst.directory, exist_ok=True)
+        dst.save()
+    parallel.barrier()
+    return dst
+
+
+def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, resolution=0, seed=0, skymodels=(),
+                  klname=None, sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None,
+                  unstacked=False):
+    """The days that `sidereal_stack` consumes: day d is written to `outdirs[d]` as `nsamples`
+    (one number, or one per day) samples at phi_j = starts[d] + j dphi, dphi = 2 pi cadence / T_SIDEREAL_DAY (cadence in
+    seconds), in the layout of the simulators with `phi` set to the day's own positions (taken modulo 2 pi).  The
+    remaining arguments are those of `simulate_visibilities`.
+
+    The noise-free sky of the device route on the sidereal grid (realisation `first`, ndays = 0) is band-limited, so its
+    value at every phi_j is exact: one FFT over the grid and one matrix product against e^{i m phi_j}, both in torch on
+    the device.  Unless ndays = 0, day d gets one day's receiver noise, realisation d of `seed`
+    (`Context.ts_noise`): sigma = sqrt((2 pi / dphi) noisepower(ndays=1)), the level of `simulate_visibilities` for a grid
+    of 2 pi / dphi samples per turn (times n_c per feed pair when unstacked).  weights: as for `simulate_visibilities`
+    with nsamples for ntime — one for all days, a list of one per day, or a FlagModel (or its dict), which day d
+    evaluates with seed + d; flagged samples are written as exact zeros with `weight` 0.  Returns the list of
+    Timestream."""
+    from . import skysim
+
+    ctx = get_context()
+    torch = ctx.torch
+    tel = m.beamtransfer.telescope
+    freqs = _sim_freqs(tel, freqs)
+    outdirs = list(outdirs)
+    nd = len(outdirs)
+    starts = [float(v) for v in starts]
+    nsamples = [int(nsamples)] * nd if np.ndim(nsamples) == 0 else [int(v) for v in nsamples]
+    if len(starts) != nd or len(nsamples) != nd:
+        raise ValueError("simulate_days: one start and one sample count per day expected")
+    dphi = 2.0 * np.pi * float(cadence) / T_SIDEREAL_DAY
+    if not (dphi > 0 and all(n >= 2 and (n - 1) * dphi < 2 * np.pi for n in nsamples)):
+        raise ValueError("simulate_days: a day holds two samples at the least and covers less than one turn")
+    if ndays is None:
+        ndays = 1
+    ntime = _sim_ntime(tel, resolution)
+    table = tel.redundant_pairs() if unstacked else None
+    nrow = int(table[0][-1]) if unstacked else int(tel.npairs)
+    if unstacked:
+        grid = ctx.empty((1, len(freqs), nrow, ntime), np.complex128)
+        for _ in _unstacked_chunks(m, 1, maps, 0, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
+                                   out=grid, sources=sources, gains=gains):
+            pass
+    else:
+        grid = ctx.empty((1, len(freqs), nrow, ntime), np.complex128)
+        for _ in _visibility_groups(m, 1, maps, 0, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
+                                    out=grid, sources=sources, gains=gains):
+            pass
+    tss = [Timestream(d, m) for d in outdirs]
+    if len(freqs):
+        modes = torch.fft.fft(grid[0], dim=-1) / ntime                                  # (nf, nrow, ntime)
+        mm = torch.from_numpy(np.fft.fftfreq(ntime, 1.0 / ntime)).to(grid.device)
+        if ntime % 2 == 0:   # the Nyquist mode has no sign: drop it (it is empty for a band-limited sky)
+            modes[..., ntime // 2] = 0
+        del grid
+        if ndays > 0:
+            per_turn = 2.0 * np.pi / dphi
+            if unstacked:
+                sigma = _member_sigma(tel, freqs, 1, per_turn, table[0])
+            else:
+                sigma = np.sqrt(per_turn * np.asarray(tel.noisepower(np.arange(nrow)[np.newaxis, :],
+                                                                      np.array(freqs)[:, np.newaxis], ndays=1),
+                                                       dtype=np.float64).reshape(len(freqs), nrow))
+            sigma = ctx.to_device(sigma)
+        for d in range(nd):
+            n = nsamples[d]
+            phi = starts[d] + dphi * np.arange(n)
+            E = torch.exp(1j * mm[:, None] * torch.from_numpy(phi).to(mm.device)[None, :])   # (ntime, n)
+            day = torch.matmul(modes, E).contiguous()                                       # (nf, nrow, n)
+            if ndays > 0:
+                day.add_(ctx.ts_noise(sigma, freqs, n, 1, seed, d)[0])
+            wd = weights[d] if isinstance(weights, (list, tuple)) else weights
+            if isinstance(wd, dict):
+                wd = skysim.FlagModel.from_config(wd)
+            if isinstance(wd, skysim.FlagModel):
+                wd = skysim.FlagModel(wd.fraction, wd.burst, wd.windows, wd.seed + d)
+            wh = None
+            if wd is not None:
+                wh = np.broadcast_to(skysim.as_weights(wd, len(freqs), nrow, n, freqs), (len(freqs), nrow, n))
+                day.masked_fill_(ctx.to_device(np.ascontiguousarray(wh == 0)), 0.0)
+            host = ctx.to_host(day)
+            del day, E
+            for k, fi in enumerate(freqs):
+                _write_sim_file(tss[d], fi, host[k], np.mod(phi, 2 * np.pi), weight=None if wh is None else wh[k], table=table)
+    parallel.barrier()
+    if parallel.rank0():
+        for ts in tss:
+            os.makedirs(ts.directory, exist_ok=True)
+            ts.save()
+    parallel.barrier()
+    return tss

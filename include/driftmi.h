@@ -799,6 +799,40 @@ int dm_redcal_solve(dm_ctx* ctx, int nreal, int w_nreal, int nf, int nfeed, int 
                     const double* feed_weight_host, const void* g0_dev, double damping, double tol, int maxiter,
                     void* g_dev, void* y_dev, int* iters_dev, double* step_dev, double* chi2_dev, int64_t vis_rstride);
 
+/* ---- sidereal stacking ----------------------------------------------------------------- */
+/* dm_sidereal_regrid: one day of every row, sampled at phi_j = phi0 + j dphi (j = 0 .. nt_in - 1, dphi > 0, less than
+ * one turn), resampled onto the sidereal grid phi_k = 2 pi k / ntime and written to, or added to, the accumulators of
+ * the stack.  With s = max(1, (2 pi / ntime) / dphi) and u = (phi_k + 2 pi n - phi0) / dphi in [0, 2 pi / dphi), the taps
+ * of k are the j in [ceil(u - a s), floor(u + a s)] with c_j = L_a((u - j) / s) != 0, L_a(t) = sinc(t) sinc(t / a) inside
+ * |t| < a; a tap outside [0, nt_in) exists and counts as flagged, as does one with w > 0 false (0, negative, NaN), whose
+ * data value reaches nothing.  With A, S = sum |c_j|, sum c_j over the unflagged taps and A_all, S_all over all, the
+ * sample is valid iff an unflagged tap exists, A >= min_share A_all (for min_share = 1: no tap is missing, decided by
+ * the count) and S >= S_all / 2; then xh = sum (c_j / S) x_j, W = 1 / sum ((c_j / S)^2 / w_j) and
+ *   sum += W xh,  wsum += W,  sq += W |xh|^2,  hits += 1;
+ * else W = 0 and nothing is added.  A u within 1e-9 of an integer is that integer and a cadence ratio within 1e-9 of 1
+ * is 1, so on-grid data at equal cadence has one tap of coefficient 1 and is copied whatever its neighbours' flags.
+ *   x_dev    (nf, nrow, nt_in) c128, contiguous, t fastest;   w_dev f64 of that shape or null: ones, no weight is read
+ *   sum_dev  (nf, nrow, ntime) c128, wsum_dev f64 of that shape; sq_dev f64 and hits_dev i32 of that shape, each may be
+ *            null and is then not kept
+ *   accumulate == 0: every element of every output given is written, zeros where the sample is not valid;
+ *   accumulate != 0: valid samples are added, all others are left bit for bit as they were
+ * The tap geometry depends on the day alone: it is made on the host in long double, rounded to double and uploaded once
+ * per call.  One workgroup per (frequency, tile of up to 16 rows, tile of up to 64 grid samples) stages the input span
+ * of its taps in LDS once, 16 bytes of x and 8 of w per lane with t contiguous across the lanes, so every element comes
+ * from HBM once up to the halo of a tile; a lane then owns one grid sample of up to 4 rows.  The tap sum of a sample runs
+ * in tap order whatever the row, batch or tile: the same bits alone, in any batch of rows or frequencies and at any
+ * position of a tile.  No atomics.  W is the diagonal weight only: neighbouring regridded samples share taps and are
+ * correlated.  Refused before any launch (dm_last_error): a outside 1..8, phi0 or dphi not finite or dphi <= 0,
+ * (nt_in - 1) dphi >= 2 pi, min_share outside (0, 1], ntime < 1, negative sizes, more than dm_sidereal_max_taps() taps
+ * (2 a s + 1), a null x, sum or wsum with work to do, an output sharing an element with x, w or another output.  nf, nrow
+ * or nt_in = 0 is a no-op, except that with accumulate == 0 the outputs are zeroed.  Returns when the work is queued on
+ * the context's stream.  No counterpart in the reference, whose data begins at the finished sidereal stream. */
+int dm_sidereal_regrid(dm_ctx* ctx, int nf, int nrow, int nt_in, int ntime, int a, double phi0, double dphi,
+                       double min_share, const void* x_dev, const double* w_dev, void* sum_dev, double* wsum_dev,
+                       double* sq_dev, int* hits_dev, int accumulate);
+/* the cap on 2 a s + 1, the taps of one grid sample (host only) */
+int dm_sidereal_max_taps(void);
+
 #ifdef __cplusplus
 }
 #endif
