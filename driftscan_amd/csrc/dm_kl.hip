@@ -371,11 +371,15 @@ int dm_eigh_gen(dm_ctx* ctx, int nblk, const int* n_host, void* A_dev, void* B_d
     const int b = cand[i];
     if (zflag[b]) {
       DM_TRY(dm_fill_zero(ctx, evals_dev + evoff_host[b], sizeof(double) * n_host[b]));
-      DM_TRY(dm_set_identity(ctx, E + off_host[b], n_host[b], n_host[b]));
-      if (nkeep_host && cut_mode) {  // all eigenvalues are 0: searchsorted gives 0 or n
+      int nk = n_host[b];
+      if (cut_mode) {  // all eigenvalues are 0: searchsorted gives 0 or n, the cut keeps every row or none
         const int cut = 0.0 >= cut_value ? 0 : n_host[b];
-        nkeep_host[b] = cut_mode == 1 ? n_host[b] - cut : cut;
+        nk = cut_mode == 1 ? n_host[b] - cut : cut;
+        if (nkeep_host) nkeep_host[b] = nk;
       }
+      // kept rows are rows of the identity, rows that a cut drops are zero like those of a solved block
+      if (nk > 0) DM_TRY(dm_set_identity(ctx, E + off_host[b], n_host[b], n_host[b]));
+      else DM_TRY(dm_fill_zero(ctx, E + off_host[b], sizeof(cplx) * (size_t)n_host[b] * n_host[b]));
     } else {
       work.push_back(b);
       info.push_back(info_c[i]);

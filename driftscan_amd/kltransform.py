@@ -202,7 +202,8 @@ class KLTransform(config.Reader):
         """`inv_gen(evecs).T` of the reference (kltransform.py:124-143, :346-347) for every block, on the device:
         the modes satisfy E (N + ac I) E^H = I, so E^-1 = (N + ac I) E^H and its transpose is conj(E (N + ac I)) —
         one grouped product instead of an LU inversion per m on the host.  The all-zero shortcut of eigh_gen
-        (kltransform.py:81-85) returns the identity, whose inverse is the identity."""
+        (kltransform.py:81-85) stands for the identity (it is called without a cut here), whose inverse is the identity:
+        those blocks are written from their all-zero eigenvalues, not from `evecs`."""
         import torch
 
         inv = ctx.empty((max(int(evecs.numel()), 1),), np.complex128)
