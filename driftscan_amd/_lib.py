@@ -216,6 +216,10 @@ SIGNATURES = {
     "dm_sidereal_regrid": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "dm_sidereal_max_taps": (c_int, []),
+    "dm_rfi_flag": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_dbl, c_int, ctypes.POINTER(c_int), c_dbl, c_dbl, c_int, c_dbl, c_int,
+                c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dm_rfi_max_segment": (c_int, []),
 }
 
 _lib = None
@@ -1105,6 +1109,51 @@ def _sidereal_regrid(self, x, phi0, dphi, ntime, w=None, a=3, min_share=1.0, acc
 
 
 Context.sidereal_regrid = _sidereal_regrid
+
+
+def _rfi_flag(self, x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4, 8, 16), chi1=6.0, rho=1.5, niter=3,
+              base=2.0, min_good=16, row_share=1.0, out=None):
+    """RFI flags of one day along time by an iterated SumThreshold (dm_rfi_flag, DESIGN.md section 4.20;
+    `timestream.rfi_flag_host` restates it).  x (nf, nrow, nt) complex128, contiguous; w float64 of that shape or None
+    (ones), flagged on input where `w > 0` is false, and the data of such a sample reaches nothing.  Every series is cut
+    into ceil(nt / segment) balanced segments that are judged independently.  Returns (w_out, noise, nflag, occupancy):
+    w_out (nf, nrow, nt) float64 is w (or 1) where the sample is kept and 0 where it is flagged; noise (nf, nrow, nseg)
+    float64 the noise scale of a segment, median |residual| / sqrt(ln 2), 0 where the segment had fewer than min_good
+    usable samples and is flagged whole; nflag (nf, nrow) int32 the new flags of detection; occupancy (nf, nt) int32 the
+    rows where detection flagged the sample anew.  With row_share < 1 a sample that detection flagged in more than
+    row_share of the rows where it was not input flagged is flagged in every row of its frequency.  `out` takes that
+    tuple of tensors to write into; its w_out may be w itself.  The bits of a row do not depend on the batch it is in."""
+    torch = self.torch
+    if not (_is_c128(x) and x.dim() == 3):
+        raise ValueError("rfi_flag: contiguous complex128 tensor x (nf, nrow, nt) expected")
+    nf, nrow, nt = (int(v) for v in x.shape)
+    if w is not None and not (hasattr(w, "data_ptr") and not w.is_complex() and w.element_size() == 8 and w.is_contiguous()
+                              and w.dtype.is_floating_point and tuple(w.shape) == tuple(x.shape)):
+        raise ValueError("rfi_flag: w must be a contiguous float64 tensor of x's shape")
+    segment = int(segment)
+    if segment < 1:
+        raise ValueError("rfi_flag: segment < 1")
+    windows = [int(v) for v in windows]
+    nseg = -(-nt // segment)
+    shapes = ((nf, nrow, nt), (nf, nrow, nseg), (nf, nrow), (nf, nt))
+    dtypes = (torch.float64, torch.float64, torch.int32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 4 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
+                                    for o, s, d in zip(out, shapes, dtypes)):
+            raise ValueError("rfi_flag: out must hold contiguous tensors w_out (nf, nrow, nt) float64, noise (nf, nrow, nseg) "
+                             "float64, nflag (nf, nrow) int32 and occupancy (nf, nt) int32")
+    win = (c_int * max(len(windows), 1))(*windows)
+    rc = self.lib.dm_rfi_flag(self.h, nf, nrow, nt, segment, float(kernel_sigma), len(windows), win, float(chi1), float(rho),
+                              int(niter), float(base), int(min_good), float(row_share), self.ptr(x), self.ptr(w),
+                              self.ptr(out[0]), self.ptr(out[1]), self.ptr(out[2]), self.ptr(out[3]))
+    self.check(rc, "dm_rfi_flag")
+    return out
+
+
+Context.rfi_flag = _rfi_flag
 
 
 def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,

@@ -108,14 +108,22 @@ class PipelineManager(config.Reader):
                 self.simulations[tsconf["name"]] = tsconf["simulate"]
             if "stack_from" in tsconf:
                 self.stacks[tsconf["name"]] = dict(tsconf["stack_from"])
+                self._check_rfi(self.stacks[tsconf["name"]])
             if "sidereal_from" in tsconf:
                 self.sidereal[tsconf["name"]] = dict(tsconf["sidereal_from"])
+                self._check_rfi(self.sidereal[tsconf["name"]])
         # a stacked day of a `sidereal_from` entry is that entry's input, not a timestream the stages below run on
         daydirs = {os.path.abspath(fixpath(d)) for conf in self.sidereal.values() for d in conf.get("days", ())}
         for name in [n for n, ts in self.timestreams.items() if ts.directory in daydirs]:
             self.days[name] = self.timestreams.pop(name)
         if "crosspower" in yconf:
             self.crosspower = list(yconf["crosspower"] or [])
+
+    @staticmethod
+    def _check_rfi(conf):
+        """The `rfi` dict of a `stack_from` or `sidereal_from` block, defaults filled in; an unknown key raises ValueError."""
+        if conf.get("rfi") is not None:
+            conf["rfi"] = timestream.rfi_params(conf["rfi"])
 
     def _products(self, directory):
         """The ProductManager of a product directory (opened once per directory: its objects hold caches and device
@@ -157,8 +165,9 @@ class PipelineManager(config.Reader):
             timestream.stack_baselines(ts.manager, fixpath(conf["directory"]), ts.directory,
                                        calibrate=None if calibrate in (None, "none") else calibrate,
                                        dead_feeds=tuple(conf.get("dead_feeds", ()) or ()), chunk_gb=self.chunk_gb,
-                                       **({"redcal": dict(conf["redcal"])} if conf.get("redcal") else {}))
-        # `sidereal_from: {days: [dir, ...], a: 3, min_share: 1.0}`: the days, which may be the stacks made above, are
+                                       **({"redcal": dict(conf["redcal"])} if conf.get("redcal") else {}),
+                                       **({"rfi": conf["rfi"]} if conf.get("rfi") is not None else {}))
+        # `sidereal_from: {days: [dir, ...], a: 3, min_share: 1.0, rfi: {...}}`: the days, which may be the stacks made above, are
         # regridded and averaged by `timestream.sidereal_stack`
         for tsname, conf in self.sidereal.items():
             ts = self.timestreams[tsname]
@@ -167,7 +176,8 @@ class PipelineManager(config.Reader):
                 continue
             timestream.sidereal_stack(ts.manager, [fixpath(d) for d in conf["days"]], ts.directory,
                                       ntime=conf.get("ntime", None), a=int(conf.get("a", 3)),
-                                      min_share=float(conf.get("min_share", 1.0)), chunk_gb=self.chunk_gb)
+                                      min_share=float(conf.get("min_share", 1.0)), chunk_gb=self.chunk_gb,
+                                      rfi=conf.get("rfi", None))
 
     def generate(self):
         """Run the stages that are switched on, for every timestream, in the reference's order: m-modes and SVD modes, KL

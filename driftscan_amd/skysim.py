@@ -269,6 +269,80 @@ class FlagModel:
         return np.where(flagged, 0.0, 1.0)
 
 
+STREAM_TS_RFI = 28           # interference bursts: apart from 0, 1, 2, 16, 17 and 24-27
+
+
+class RFIModel:
+    """Interference added to a simulated day, so that a flagger has ground truth.  Host only.
+
+    Bursts are placed as in `FlagModel`: a run of ``burst`` samples, cyclic over the day, starts at sample s of global
+    frequency f when u(seed, f, s) < p with 1 - (1 - p)^burst = ``fraction``; u is the uniform of Philox4x32-10 with key
+    ``seed`` and counter (s, f, 0, 28).  The same samples are hit in every row of a frequency.  Every sample of a burst
+    adds ``amplitude`` x the row's noise sigma x e^{i theta}, theta = 2 pi u of counter (s, f, row + 1, 28): one phase
+    per (row, burst); bursts that overlap add up.  A frequency depends on (seed, global frequency) alone, so frequency
+    subsets reproduce the rows of the full call."""
+
+    def __init__(self, fraction=0.0, burst=1, amplitude=10.0, seed=0):
+        self.fraction, self.burst, self.amplitude, self.seed = float(fraction), int(burst), float(amplitude), int(seed)
+        if not 0.0 <= self.fraction < 1.0:
+            raise ValueError("RFIModel: fraction must lie in [0, 1)")
+        if self.burst < 1:
+            raise ValueError("RFIModel: burst must be at least 1")
+        if not (np.isfinite(self.amplitude) and self.amplitude >= 0.0):
+            raise ValueError("RFIModel: amplitude must be finite and not negative")
+
+    @classmethod
+    def from_config(cls, conf):
+        conf = dict(conf)
+        unknown = set(conf) - {"fraction", "burst", "amplitude", "seed"}
+        if unknown:
+            raise ValueError("RFIModel: unknown keys %s" % sorted(unknown))
+        return cls(**conf)
+
+    def __repr__(self):
+        return "RFIModel(fraction=%r, burst=%r, amplitude=%r, seed=%r)" % (self.fraction, self.burst, self.amplitude, self.seed)
+
+    def start_probability(self):
+        """p with 1 - (1 - p)^burst = fraction."""
+        return 1.0 - (1.0 - self.fraction) ** (1.0 / self.burst)
+
+    def _key(self):
+        seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        return (seed & 0xFFFFFFFF, seed >> 32)
+
+    def starts(self, ntime, fglobal):
+        """(nf, ntime) bool: the samples where a burst starts."""
+        fg = np.asarray(fglobal, dtype=np.uint64).reshape(-1)
+        if not (self.fraction > 0.0 and ntime > 0 and fg.shape[0] > 0):
+            return np.zeros((fg.shape[0], int(ntime)), dtype=bool)
+        f, s = np.meshgrid(fg, np.arange(int(ntime), dtype=np.uint64), indexing="ij")
+        w = _philox4x32_10([s, f, np.zeros_like(s), np.full_like(s, STREAM_TS_RFI)], self._key())
+        return _u53(w[0], w[1]) < self.start_probability()
+
+    def mask(self, ntime, fglobal):
+        """(nf, ntime) bool, True where a burst hits: the truth."""
+        start = self.starts(ntime, fglobal)
+        hit = np.zeros_like(start)
+        for d in range(min(self.burst, int(ntime))):
+            hit |= np.roll(start, d, axis=1)
+        return hit
+
+    def bursts(self, ntime, fglobal, nrow):
+        """(nf, nrow, ntime) complex128: what the bursts add to data of unit noise sigma."""
+        ntime, nrow = int(ntime), int(nrow)
+        fg = np.asarray(fglobal, dtype=np.uint64).reshape(-1)
+        start = self.starts(ntime, fg)
+        out = np.zeros((fg.shape[0], nrow, ntime), dtype=np.complex128)
+        for i, s in zip(*np.nonzero(start)):
+            rows = np.arange(1, nrow + 1, dtype=np.uint64)
+            w = _philox4x32_10([np.full_like(rows, s), np.full_like(rows, fg[i]), rows, np.full_like(rows, STREAM_TS_RFI)],
+                               self._key())
+            ph = self.amplitude * np.exp(1j * 6.283185307179586 * _u53(w[0], w[1]))
+            for d in range(min(self.burst, ntime)):
+                out[i, :, (s + d) % ntime] += ph
+        return out
+
+
 def as_weights(weights, nf, npairs, ntime, fglobal):
     """The `weights` argument of the simulators as a float64 array broadcastable to (nf, npairs, ntime) — (nf, npairs,
     ntime), (nf, 1, ntime) from a FlagModel, a dict of its arguments or an (nf, ntime) array, or (ntime,) — checked."""

@@ -1817,7 +1817,7 @@ def _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed
 REDCAL_DEFAULTS = dict(damping=0.4, tol=1e-10, maxiter=500, reference=None)
 
 
-def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None):
+def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None, rfi=None):
     """Stack the unstacked Timestream directory `indir` (`simulate_ensemble(unstacked=True)`, or a correlator's per-pair
     data in that layout) into the unique baselines of the telescope of ProductManager `m` and write them to `outdir` in
     the layout of `simulate_ensemble`; returns the `Timestream` of `outdir`.
@@ -1841,7 +1841,12 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     has weight 0 throughout and comes out of `generate_modes_batched` with info = -1).  The amplitudes of the calibration
     gains are left out of the file's weight (`Context.vis_stack` keeps them in its own: mean |g_i|^2 |g_j|^2, which moves
     the noise of a calibrated stack by the few per cent the amplitudes are off one); a sample the kernel could not form
-    (every gain product of its class zero) gets weight 0."""
+    (every gain product of its class zero) gets weight 0.
+
+    rfi: a dict of the parameters of `Context.rfi_flag` (an unknown key raises ValueError).  The feed-pair data of every
+    frequency is then flagged on the device before anything is solved or summed, and the flags
+    go on as weights 0 of the members, as the file's own flags do."""
+    rfi_p = None if rfi is None else rfi_params(rfi)
     ctx = get_context()
     tel = m.beamtransfer.telescope
     src = Timestream(indir, m)
@@ -1893,7 +1898,7 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
             fw[int(a)] = 0.0
     freqs = _sim_freqs(tel, None)
     with storage.File(src._ffile(0), "r") as f:
-        weighted = "weight" in f
+        weighted = "weight" in f or rfi_p is not None
     per_f = ntime * (16.0 * nmem + (8.0 * nmem if weighted else 0.0) + (16.0 * nfeed if calibrate is not None else 0.0)
                      + 24.0 * npairs)
     if redundant:   # g, the second gain buffer and y of the solver, its three per-sample outputs and its state words
@@ -1925,6 +1930,11 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
                         g.append(np.asarray(f["gain"][:], dtype=np.complex128))
             if calibrate is not None and not isinstance(calibrate, str):
                 g = [calibrate[fi] for fi in fs]
+        if rfi_p is not None:
+            with _StepTimer(log, "rfi"):
+                x_d = ctx.to_device(np.stack(vis))
+                w = list(ctx.to_host(ctx.rfi_flag(x_d, w=ctx.to_device(np.stack(w)), **rfi_p)[0]))
+                del x_d
         vis_d = w_d = None
         if redundant:
             with _StepTimer(log, "redcal"):
@@ -2136,7 +2146,7 @@ def _day_phi(tstream):
     return float(phi[0]), float(dphi), n
 
 
-def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=4.0):
+def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=4.0, rfi=None):
     """Regrid the days `daydirs` onto the sidereal grid and average them with their weights.
     Every entry is a Timestream directory, stacked or unstacked, all of one row layout (and one class table): a stretch
     of samples at the positions of its dataset `phi` (uniformly spaced after unwrapping, else ValueError), with `weight`
@@ -2146,8 +2156,11 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
     the data goes on through the weighted m-mode route, where its scale cancels; it is the diagonal only — neighbouring
     samples share taps and are correlated), `day_hits` int32, `day_variance` — the day-to-day scatter
     (sq - |sum|^2 / wsum) / (hits - 1), an estimate of the variance of one nominal input sample, 0 where hits < 2 —
-    when there is more than one day, and the attribute `ndays`.  ntime=None: `_sim_ntime(tel, 0)`.  Returns the
-    Timestream of `outdir`."""
+    when there is more than one day, and the attribute `ndays`.  ntime=None: `_sim_ntime(tel, 0)`.  rfi: a dict of the parameters of
+    `Context.rfi_flag` (an empty one: the defaults; an unknown key raises ValueError): every day is then flagged on the
+    device between the read and the regridding, its weights are the day's own with the flagged
+    samples at 0, and nothing is written for the days.  Returns the Timestream of `outdir`."""
+    rfi_p = None if rfi is None else rfi_params(rfi)
     ctx = get_context()
     torch = ctx.torch
     tel = m.beamtransfer.telescope
@@ -2173,7 +2186,7 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
         nrow = int(f["timestream"].shape[0])
     freqs = _sim_freqs(tel, None)
     nt_max = max(g[2] for g in geo)
-    per_f = nrow * (24.0 * nt_max + 36.0 * ntime + 16.0 * ntime)
+    per_f = nrow * ((24.0 if rfi is None else 32.0) * nt_max + 36.0 * ntime + 16.0 * ntime)
     step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
     log = sim_log
     dst = Timestream(outdir, m)
@@ -2198,6 +2211,8 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
             with _StepTimer(log, "regrid"):
                 x_d = ctx.to_device(np.stack(xs))
                 w_d = ctx.to_device(np.stack(ws)) if weighted else None
+                if rfi_p is not None:
+                    w_d = ctx.rfi_flag(x_d, w=w_d, **rfi_p)[0]
                 acc = ctx.sidereal_regrid(x_d, phi0, dphi, ntime, w=w_d, a=a, min_share=min_share, acc=acc)
                 del x_d, w_d
         with _StepTimer(log, "finish"):
@@ -2230,7 +2245,7 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
 
 def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, resolution=0, seed=0, skymodels=(),
                   klname=None, sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None,
-                  unstacked=False):
+                  unstacked=False, rfi=None):
     """The days that `sidereal_stack` consumes: day d is written to `outdirs[d]` as `nsamples`
     (one number, or one per day) samples at phi_j = starts[d] + j dphi, dphi = 2 pi cadence / T_SIDEREAL_DAY (cadence in
     seconds), in the layout of the simulators with `phi` set to the day's own positions (taken modulo 2 pi).  The
@@ -2242,8 +2257,9 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
     (`Context.ts_noise`): sigma = sqrt((2 pi / dphi) noisepower(ndays=1)), the level of `simulate_visibilities` for a grid
     of 2 pi / dphi samples per turn (times n_c per feed pair when unstacked).  weights: as for `simulate_visibilities`
     with nsamples for ntime — one for all days, a list of one per day, or a FlagModel (or its dict), which day d
-    evaluates with seed + d; flagged samples are written as exact zeros with `weight` 0.  Returns the list of
-    Timestream."""
+    evaluates with seed + d; flagged samples are written as exact zeros with `weight` 0.  rfi: a `skysim.RFIModel` (or
+    its dict), which day d evaluates with seed + d: its bursts, in units of the row's one-day noise sigma, are added to
+    the day and are NOT flagged.  Returns the list of Timestream."""
     from . import skysim
 
     ctx = get_context()
@@ -2281,7 +2297,9 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
         if ntime % 2 == 0:   # the Nyquist mode has no sign: drop it (it is empty for a band-limited sky)
             modes[..., ntime // 2] = 0
         del grid
-        if ndays > 0:
+        if isinstance(rfi, dict):
+            rfi = skysim.RFIModel.from_config(rfi)
+        if ndays > 0 or rfi is not None:
             per_turn = 2.0 * np.pi / dphi
             if unstacked:
                 sigma = _member_sigma(tel, freqs, 1, per_turn, table[0])
@@ -2297,6 +2315,9 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
             day = torch.matmul(modes, E).contiguous()                                       # (nf, nrow, n)
             if ndays > 0:
                 day.add_(ctx.ts_noise(sigma, freqs, n, 1, seed, d)[0])
+            if rfi is not None:
+                rd = skysim.RFIModel(rfi.fraction, rfi.burst, rfi.amplitude, rfi.seed + d)
+                day.add_(ctx.to_device(rd.bursts(n, freqs, nrow)) * sigma[:, :, None])
             wd = weights[d] if isinstance(weights, (list, tuple)) else weights
             if isinstance(wd, dict):
                 wd = skysim.FlagModel.from_config(wd)
@@ -2317,3 +2338,224 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
             ts.save()
     parallel.barrier()
     return tss
+
+
+# ---- RFI flagging along time ---------------------------------------------------------------
+RFI_DEFAULTS = dict(segment=1024, kernel_sigma=2.5, windows=(1, 2, 4, 8, 16), chi1=6.0, rho=1.5, niter=3, base=2.0,
+                    min_good=16, row_share=1.0)
+RFI_MAX_H, RFI_MAX_WINDOW, RFI_MAX_ITER = 32, 64, 8
+RFI_SQRT_LN2 = 0.83255461115769775635   # sigma = median / sqrt(ln 2) for a Rayleigh amplitude
+
+
+def rfi_params(params=None):
+    """The parameters of the RFI flagger with their defaults filled in; an unknown key raises ValueError."""
+    params = dict(params or {})
+    unknown = sorted(set(params) - set(RFI_DEFAULTS))
+    if unknown:
+        raise ValueError("rfi: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(sorted(RFI_DEFAULTS))))
+    out = dict(RFI_DEFAULTS)
+    out.update(params)
+    out["windows"] = tuple(int(v) for v in out["windows"])
+    return out
+
+
+def rfi_tables_host(kernel_sigma=2.5, windows=(1, 2, 4, 8, 16), chi1=6.0, rho=1.5, niter=3, base=2.0):
+    """The two tables of the RFI flagger (dm_rfi_table.h), made in long double and rounded to double once: g (H + 1,), the
+    background kernel exp(-d^2 / (2 kernel_sigma^2)), and t (niter, len(windows)), the thresholds
+    alpha + chi1 rho^(-log2 M) base^(niter - 1 - it) beta in units of the median amplitude.  Refuses what dm_rfi_flag
+    refuses about these parameters."""
+    L = np.longdouble
+    windows = [int(v) for v in windows]
+    if not (np.isfinite(kernel_sigma) and kernel_sigma > 0):
+        raise ValueError("rfi: kernel_sigma not finite or <= 0")
+    H = int(np.ceil(L(3) * L(kernel_sigma)))
+    if H > RFI_MAX_H:
+        raise ValueError("rfi: H = ceil(3 kernel_sigma) > %d" % RFI_MAX_H)
+    if not (1 <= len(windows) <= 7) or any(M < 1 or M > RFI_MAX_WINDOW or M & (M - 1) for M in windows) or \
+            any(b <= a for a, b in zip(windows, windows[1:])):
+        raise ValueError("rfi: windows are not ascending powers of two <= %d" % RFI_MAX_WINDOW)
+    if not (np.isfinite(chi1) and chi1 > 0 and np.isfinite(rho) and rho >= 1 and np.isfinite(base) and base >= 1):
+        raise ValueError("rfi: chi1 <= 0, rho < 1 or base < 1, or one of them not finite")
+    if not (1 <= int(niter) <= RFI_MAX_ITER):
+        raise ValueError("rfi: niter outside 1..%d" % RFI_MAX_ITER)
+    pi, ln2 = L("3.14159265358979323846264338327950288"), L("0.693147180559945309417232121458176568")
+    alpha, beta = np.sqrt(pi / (L(4) * ln2)), np.sqrt((L(1) - pi / L(4)) / ln2)
+    d = np.arange(H + 1).astype(L)
+    g = np.exp(-(d * d) / (L(2) * L(kernel_sigma) * L(kernel_sigma))).astype(np.float64)
+    t = np.zeros((int(niter), len(windows)), dtype=np.float64)
+    for it in range(int(niter)):
+        for i, M in enumerate(windows):
+            chi = L(chi1) * np.power(L(rho), -L(M.bit_length() - 1))
+            t[it, i] = np.float64(alpha + chi * np.power(L(base), L(int(niter) - 1 - it)) * beta)
+    return g, t
+
+
+def rfi_segments(nt, segment):
+    """The balanced segments of a series of nt samples: [(j0, j1)], nseg = ceil(nt / segment)."""
+    nseg = -(-int(nt) // int(segment))
+    return [((s * nt) // nseg, ((s + 1) * nt) // nseg) for s in range(nseg)]
+
+
+def rfi_flag_host(x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4, 8, 16), chi1=6.0, rho=1.5, niter=3, base=2.0,
+                  min_good=16, row_share=1.0, dtype=np.float64, details=False):
+    """The numpy statement of `Context.rfi_flag`: x (nf, nrow, nt) complex, w of that shape or
+    None.  Returns (w_out, noise, nflag, occupancy) as the device does.  The tables are those of `rfi_tables_host` for
+    every `dtype`; the sums, the amplitudes and the comparisons run in `dtype`, np.float64 or np.longdouble.
+    details=True also returns a dict per segment, each (nf, nrow, nseg): `eps` = (2H + 17) 2^-53 max_j (sum g |x| /
+    sum g + |x_j|), the error a double evaluation of an amplitude can have; `margin`, the smallest
+    |S - c m t| - c eps (1 + t) over every window decision of every pass (inf where none was made); and `decided` =
+    margin > 0: no rounding of that size can change a flag of the segment.  `row_flags` (nf, nrow, nt) are the flags
+    before the occupancy step."""
+    real = np.dtype(dtype).type
+    cdt = np.clongdouble if real is np.longdouble else np.complex128
+    x = np.asarray(x)
+    if x.ndim != 3:
+        raise ValueError("rfi_flag_host: x (nf, nrow, nt) expected")
+    segment, niter, min_good = int(segment), int(niter), int(min_good)
+    if segment < 1 or min_good < 1 or not (0.0 < float(row_share) <= 1.0):
+        raise ValueError("rfi: segment < 1, min_good < 1 or row_share outside (0, 1]")
+    windows = [int(v) for v in windows]
+    g64, t64 = rfi_tables_host(kernel_sigma, windows, chi1, rho, niter, base)
+    g, tt = g64.astype(real), t64.astype(real)
+    H = g.shape[0] - 1
+    nf, nrow, nt = x.shape
+    inflag = np.zeros(x.shape, dtype=bool) if w is None else ~(np.asarray(w) > 0)
+    xz = np.where(inflag, 0, x).astype(cdt)
+    segs = rfi_segments(nt, segment) if nt else []
+    nseg = len(segs)
+    flags = np.zeros(x.shape, dtype=bool)
+    noise = np.zeros((nf, nrow, nseg), dtype=real)
+    eps_o = np.zeros((nf, nrow, nseg), dtype=np.float64)
+    margin_o = np.full((nf, nrow, nseg), np.inf, dtype=np.float64)
+    for s, (j0, j1) in enumerate(segs):
+        n = j1 - j0
+        X = xz[..., j0:j1].reshape(nf * nrow, n)
+        I = inflag[..., j0:j1].reshape(nf * nrow, n)
+        R = X.shape[0]
+        B = I.copy()
+        active, allflag = np.ones(R, dtype=bool), np.zeros(R, dtype=bool)
+        med = np.zeros(R, dtype=real)
+        eps = np.zeros(R, dtype=np.float64)
+        margin = np.full(R, np.inf, dtype=np.float64)
+        absX = np.abs(X).astype(np.float64)
+        for it in range(niter):
+            cnt = (~B).sum(axis=1)
+            dead = active & (cnt < min_good)
+            allflag |= dead
+            active &= ~dead
+            if not active.any():
+                break
+            sx, sg, sa = np.zeros((R, n), dtype=cdt), np.zeros((R, n), dtype=real), np.zeros((R, n), dtype=np.float64)
+            used = np.zeros((R, n), dtype=np.int64)
+            for d in range(-H, H + 1):
+                lo, hi = max(0, -d), min(n, n - d)   # j in [lo, hi): k = j + d inside the segment
+                if hi <= lo:
+                    continue
+                ok = ~B[:, lo + d : hi + d]
+                gd = g[abs(d)]
+                sx[:, lo:hi] += np.where(ok, gd * X[:, lo + d : hi + d], 0)
+                sg[:, lo:hi] += np.where(ok, gd, 0)
+                sa[:, lo:hi] += np.where(ok, np.float64(gd) * absX[:, lo + d : hi + d], 0)
+                used[:, lo:hi] += ok
+            unj = ~I & (used == 0)
+            sgs = np.where(used > 0, sg, 1)
+            r = X - sx / sgs
+            a = np.where(I | unj, 0, np.sqrt(r.real * r.real + r.imag * r.imag)).astype(real)
+            e_it = np.where(I | unj, 0, sa / sgs.astype(np.float64) + absX).max(axis=1) * (2 * H + 17) * 2.0**-53
+            eps = np.where(active, np.maximum(eps, e_it), eps)
+            srt = np.sort(np.where(B, np.inf, a), axis=1)
+            m_it = srt[np.arange(R), np.maximum(cnt - 1, 0) // 2]
+            med = np.where(active, m_it, med)
+            D = I | unj
+            for i, M in enumerate(windows):
+                if M > n:
+                    break
+                nst = n - M + 1
+                notD = ~D
+                c = np.zeros((R, nst), dtype=np.int64)
+                S = np.zeros((R, nst), dtype=real)
+                for k in range(M):
+                    c += notD[:, k : k + nst]
+                    S = S + np.where(notD[:, k : k + nst], a[:, k : k + nst], 0)
+                thr = m_it * tt[it, i]
+                lim = c.astype(real) * thr[:, None]
+                hit = (c >= 1) & (S > lim)
+                mg = np.where(c >= 1, np.abs(S - lim).astype(np.float64) - c * e_it[:, None] * (1.0 + t64[it, i]), np.inf)
+                margin = np.where(active, np.minimum(margin, mg.min(axis=1)), margin)
+                newD = D.copy()
+                for k in range(M):
+                    newD[:, k : k + nst] |= hit
+                D = newD
+            B = np.where(active[:, None], D, B)
+        fl = B | allflag[:, None]
+        flags[..., j0:j1] = fl.reshape(nf, nrow, n)
+        noise[..., s] = np.where(allflag, 0, med / real(RFI_SQRT_LN2)).reshape(nf, nrow)
+        eps_o[..., s] = eps.reshape(nf, nrow)
+        margin_o[..., s] = margin.reshape(nf, nrow)
+    new = flags & ~inflag
+    nflag = new.sum(axis=2).astype(np.int32)
+    occupancy = new.sum(axis=1).astype(np.int32)
+    n_in = (~inflag).sum(axis=1)
+    col = (n_in > 0) & (occupancy.astype(np.float64) > np.float64(row_share) * n_in.astype(np.float64))
+    final = flags | col[:, None, :]
+    wv = np.ones(x.shape, dtype=np.float64) if w is None else np.asarray(w, dtype=np.float64)
+    w_out = np.where(final, 0.0, wv)
+    if details:
+        return w_out, noise, nflag, occupancy, dict(eps=eps_o, margin=margin_o, decided=margin_o > 0, row_flags=flags)
+    return w_out, noise, nflag, occupancy
+
+
+def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, **params):
+    """Flag the interference in the Timestream directory `indir`, stacked or unstacked, along time on the device
+    (`Context.rfi_flag`) and write the result to `outdir` (None: in place).  `params` are the
+    parameters of `Context.rfi_flag` (an unknown key raises ValueError).  Every file keeps all its datasets and
+    attributes; `weight` becomes the file's weight (ones where it had none) with the flagged samples at 0, the input
+    weight is kept as `weight_input` when one was present, and `rfi_noise` (nrow, nseg), `rfi_nflag` (nrow,) and
+    `rfi_occupancy` (ntime,) are the flagger's other outputs.  Ranks take their own frequencies in chunks that fit
+    `chunk_gb`.  Returns the Timestream of the output."""
+    p = rfi_params(params)
+    ctx = get_context()
+    tel = m.beamtransfer.telescope
+    src = Timestream(indir, m)
+    inplace = outdir is None or os.path.abspath(outdir) == os.path.abspath(src.directory)
+    dst = src if inplace else Timestream(outdir, m)
+    freqs = _sim_freqs(tel, None)
+    with storage.File(src._ffile(0), "r") as f:
+        nrow, nt = (int(v) for v in f["timestream"].shape)
+    step = max(1, int(chunk_gb * 2.0**30 // max(nrow * nt * 32.0, 1.0)))
+    log = sim_log
+    for c0 in range(0, len(freqs), step):
+        fs = freqs[c0 : c0 + step]
+        with _StepTimer(log, "read"):
+            files = []
+            for fi in fs:
+                with storage.File(src._ffile(fi), "r") as f:
+                    files.append(({k: np.asarray(f[k][:]) for k in f.keys()}, dict(f.attrs)))
+                if files[-1][0]["timestream"].shape != (nrow, nt):
+                    raise ValueError("rfi_flag: %s holds %s, not (%d, %d)" % (src._ffile(fi), files[-1][0]["timestream"].shape, nrow, nt))
+            weighted = any("weight" in d for d, _ in files)
+        with _StepTimer(log, "rfi"):
+            x_d = ctx.to_device(np.stack([np.asarray(d["timestream"], dtype=np.complex128) for d, _ in files]))
+            w_d = None
+            if weighted:
+                w_d = ctx.to_device(np.stack([np.asarray(d["weight"], dtype=np.float64) if "weight" in d
+                                              else np.ones((nrow, nt), dtype=np.float64) for d, _ in files]))
+            out = [ctx.to_host(t) for t in ctx.rfi_flag(x_d, w=w_d, **p)]
+            del x_d, w_d
+        with _StepTimer(log, "write"):
+            for k, (fi, (data, attrs)) in enumerate(zip(fs, files)):
+                if "weight" in data and "weight_input" not in data:   # a second pass keeps the first input
+                    data["weight_input"] = data["weight"]
+                data.update(weight=out[0][k], rfi_noise=out[1][k], rfi_nflag=out[2][k], rfi_occupancy=out[3][k])
+                os.makedirs(dst._fdir(fi), exist_ok=True)
+                with storage.File(dst._ffile(fi), "w") as f:
+                    for name, value in data.items():
+                        f.create_dataset(name, data=np.ascontiguousarray(value))
+                    for name, value in attrs.items():
+                        f.attrs[name] = value
+    parallel.barrier()
+    if not inplace and parallel.rank0():
+        os.makedirs(dst.directory, exist_ok=True)
+        dst.save()
+    parallel.barrier()
+    return dst

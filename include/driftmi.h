@@ -833,6 +833,42 @@ int dm_sidereal_regrid(dm_ctx* ctx, int nf, int nrow, int nt_in, int ntime, int 
 /* the cap on 2 a s + 1, the taps of one grid sample (host only) */
 int dm_sidereal_max_taps(void);
 
+/* ---- RFI flagging along time ---------------------------------------------------------- */
+/* dm_rfi_flag: an iterated SumThreshold (Offringa et al. 2010) on every (frequency, row) series of one day, and the
+ * weights of the day with the flagged samples at 0.  x (nf, nrow, nt) complex128 and w (nf, nrow, nt) float64 or null
+ * (ones), contiguous; a sample with w > 0 false (0, negative, NaN) is input flagged (the set I) and its data value, NaN
+ * included, reaches nothing.  A series is cut into nseg = ceil(nt / segment) balanced segments
+ * [floor(s nt / nseg), floor((s + 1) nt / nseg)), which are independent; windows are truncated at their edges.
+ * Tables, made on the host in long double and rounded to double once: g_d = exp(-d^2 / (2 kernel_sigma^2)), d = 0 .. H,
+ * H = ceil(3 kernel_sigma); t[it][M] = alpha + chi1 rho^(-log2 M) base^(niter - 1 - it) beta with
+ * alpha = sqrt(pi / (4 ln 2)), beta = sqrt((1 - pi / 4) / ln 2), the mean and the standard deviation of a Rayleigh
+ * amplitude in units of its median.  Per segment, with B = I at the start, for it = 0 .. niter - 1: (1) fewer than
+ * min_good samples outside B: the whole segment is flagged, its noise is 0, stop; (2) for j outside I the background
+ * b_j = sum g_|d| x_{j+d} / sum g_|d| over d = -H .. H ascending, over the samples inside the segment and outside B, one
+ * FMA per component and term, and a_j = sqrt(re(r)^2 + im(r)^2), r = x_j - b_j; a sample with no usable sample in its
+ * window is unjudgeable; (3) m = the lower median of a_j over j outside B (rank (c - 1) / 2 of c), an exact order
+ * statistic; (4) D = I and the unjudgeable samples; for every window length M <= n in ascending order, every window
+ * [j, j + M) of the segment: over its samples outside D as D stood at the start of the pass, c their count and S the sum
+ * of a_k in ascending k; the window hits iff c >= 1 and S > c (m t[it][M]); after the pass all samples of hitting
+ * windows join D; (5) B = D.  The flags of the segment are the last B and noise = m / sqrt(ln 2).
+ * Occupancy: with n_in the rows of a frequency where sample j is outside I and n_new the rows where detection flagged
+ * it anew, j is flagged in every row of the frequency when n_in > 0 and n_new > row_share n_in (row_share = 1: never).
+ * Outputs: w_out (nf, nrow, nt) = w (or 1) where kept, bit for bit, and 0 where flagged, and it may be w itself;
+ * noise (nf, nrow, nseg); nflag (nf, nrow) int32, the new flags of detection in the row; occupancy (nf, nt) int32, n_new.
+ * A row has the same bits in w_out and noise alone, in any batch, at any row index and with any other frequency.  No
+ * floating-point atomics.  Refused before any launch (dm_last_error): negative sizes, segment outside
+ * 1 .. dm_rfi_max_segment(), kernel_sigma not finite or <= 0 or H > 32, nwin outside 1..7 or windows that are not
+ * ascending powers of two <= 64, chi1 <= 0, rho < 1, base < 1 or any of them not finite, niter outside 1..8,
+ * min_good < 1, row_share outside (0, 1], a null x or output with work to do, an output sharing an element with x, w
+ * (other than w_out == w) or another output.  nf, nrow or nt = 0 is a no-op.  Returns when the work is queued on the
+ * context's stream.  No counterpart in the reference, whose data begins at the finished sidereal stream. */
+int dm_rfi_flag(dm_ctx* ctx, int nf, int nrow, int nt, int segment, double kernel_sigma, int nwin,
+                const int* windows_host, double chi1, double rho, int niter, double base, int min_good, double row_share,
+                const void* x_dev, const double* w_dev, double* wout_dev, double* noise_dev, int* nflag_dev,
+                int* occupancy_dev);
+/* the cap on `segment`, set by the LDS layout of the row kernel (host only) */
+int dm_rfi_max_segment(void);
+
 #ifdef __cplusplus
 }
 #endif
