@@ -189,6 +189,9 @@ SIGNATURES = {
     "dm_bt_alias_info": (
         c_int, [c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_int, ctypes.POINTER(c_int),
                 ctypes.POINTER(c_int)]),
+    "dm_bt_ring_plan_info": (
+        c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "dm_bit_truncate_max_complex": (c_int, [c_vp, c_vp, c_i64, c_int, c_i64, c_dbl, c_dbl]),
     "dm_blockvec_grouped": (c_int, [c_vp, c_int, ctypes.POINTER(ZgemmProblem)]),
     "dm_mmode_twiddle": (c_int, [c_vp, c_int, c_int, c_vp]),
@@ -1912,6 +1915,21 @@ def bt_alias_info(nside, cth, sth, polarised, lmax_grp):
     if rc != 0:
         raise DriftMIError("dm_bt_alias_info failed (%d)" % rc)
     return nr.value, mc.value
+
+
+def bt_ring_plan_info(nside, polarised, m_lo, m_hi, lmax_grp, complex_beams, ncol):
+    """What the fused ring transform of `Context.bt_columns` launches for a call (dm_bt_ring_plan_info; host only): a dict
+    with use_fft, fft_npt, fft_cpw (0 without FFT), nring_dft (rings left to the matrix form) and dft_row =
+    (dft2, P, NMG, NCG) or None where no ring is left to it."""
+    uf, npt, cpw, nrd = c_int(0), c_int(0), c_int(0), c_int(0)
+    row = (c_int * 4)()
+    rc = load().dm_bt_ring_plan_info(int(nside), int(bool(polarised)), int(m_lo), int(m_hi), int(lmax_grp),
+                                     int(bool(complex_beams)), int(ncol), ctypes.byref(uf), ctypes.byref(npt),
+                                     ctypes.byref(cpw), ctypes.byref(nrd), row)
+    if rc != 0:
+        raise DriftMIError("dm_bt_ring_plan_info failed (%d)" % rc)
+    return dict(use_fft=bool(uf.value), fft_npt=npt.value, fft_cpw=cpw.value, nring_dft=nrd.value,
+                dft_row=(bool(row[0]), row[1], row[2], row[3]) if nrd.value > 0 else None)
 
 
 Context.bt_columns = _bt_columns

@@ -1109,15 +1109,16 @@ frame3 make_frame(const double* xhat, const double* yhat, const double* zhat) {
 using bt_dft_fn = decltype(&bt_fused_dft_kernel<1, 1, 8>);   // (bt_fused_dft2_kernel has the same signature)
 using bt_fft_fn = decltype(&bt_fused_fft_kernel<1, 1, 256>);
 // fn[1]: complex field patterns
-struct bt_dft_row { int P, nmg_from, cgw, mgw; bt_dft_fn fn[2]; };   // a workgroup takes cgw column groups, mgw groups of four m
+// a workgroup takes cgw column groups, mgw groups of four m; (dft2, NMG, NCG) name the instantiation (dm_bt_ring_plan_info)
+struct bt_dft_row { int P, nmg_from, cgw, mgw; bt_dft_fn fn[2]; int dft2, nmg, ncg; };
 struct bt_fft_row { int P, npt; bt_fft_fn fn[2]; };
 template <int P, int NMG, int NCG>
 bt_dft_row bt_dft_of(int nmg_from) {
-  return {P, nmg_from, 4 * NCG, NMG, {bt_fused_dft_kernel<P, NMG, NCG>, bt_fused_dft_kernel<P, NMG, NCG, true>}};
+  return {P, nmg_from, 4 * NCG, NMG, {bt_fused_dft_kernel<P, NMG, NCG>, bt_fused_dft_kernel<P, NMG, NCG, true>}, 0, NMG, NCG};
 }
 template <int P, int NMG, int NCG>
 bt_dft_row bt_dft2_of(int nmg_from) {
-  return {P, nmg_from, NCG, 4 * NMG, {bt_fused_dft2_kernel<P, NMG, NCG>, bt_fused_dft2_kernel<P, NMG, NCG, true>}};
+  return {P, nmg_from, NCG, 4 * NMG, {bt_fused_dft2_kernel<P, NMG, NCG>, bt_fused_dft2_kernel<P, NMG, NCG, true>}, 1, NMG, NCG};
 }
 template <int P, int NPT>
 bt_fft_row bt_fft_of() {
@@ -1136,6 +1137,65 @@ static const bt_dft_row bt_dft_rows[] = {bt_dft2_of<4, 2, 1>(3), bt_dft_of<4, 2,
 // N = 512 is <4, 2>, N = 2048 <1, 8>; 4096 x 4 maps does not fit the LDS.
 static const bt_fft_row bt_fft_rows[] = {bt_fft_of<4, 1>(), bt_fft_of<4, 2>(), bt_fft_of<4, 4>(), bt_fft_of<4, 8>(), bt_fft_of<1, 1>(),
                                          bt_fft_of<1, 2>(), bt_fft_of<1, 4>(), bt_fft_of<1, 8>(), bt_fft_of<1, 16>()};
+
+// What the fused ring transform launches for a call with `cnt` m-values (cnt > 0) on `ncol` columns of P maps: the one
+// place where the choice is made — bt_ring_fused launches it, dm_bt_ring_plan_info reports it.
+struct bt_ring_plan {
+  bool narrow, use_fft;
+  size_t fft_lds;
+  const bt_fft_row* fft;   // the belt kernel (use_fft), cpw columns per workgroup
+  int cpw;
+  dim3 fft_grid;
+  int nring_dft;           // rings left to the matrix form: all of them, or the two caps
+  const bt_dft_row* dft;   // (nring_dft > 0)
+  dim3 dft_grid;
+};
+// false: the belt would go by FFT but no row of bt_fft_rows fits
+static bool bt_ring_plan_make(int nside, int P, int cnt, int ncol, bt_ring_plan& pl) {
+  const int nring = 4 * nside - 1, ncol16 = (ncol + 15) / 16;
+  const int nmg = (2 * std::max(cnt, 1) + 3) / 4;  // groups of four m-values
+  // The belt (rings nside - 1 .. 3 nside - 1, all with N = 4 nside pixels) goes by FFT when N is a power of two and the
+  // P maps of a column fit the LDS; the matrix-form kernels below then see the rings of the two caps only.  The choice
+  // depends on nside, P and on whether the call is narrow (below) — not on WHICH m it asks for.
+  static const bool fft_off = getenv("DM_BT_FFT") && atoi(getenv("DM_BT_FFT")) == 0;
+  const int N = 4 * nside;
+  int fft_logn = 0;
+  while ((1 << fft_logn) < N) ++fft_logn;
+  const int fft_sh = std::max(5, fft_logn - 6);   // padding of the LDS arrays, as in the kernel
+  pl.fft_lds = sizeof(cplx) * ((size_t)P * (N + (N >> fft_sh) + 1) + (N / 2 + ((N / 2) >> fft_sh) + 1));
+  // A NARROW call (at most DM_BT_NARROW = 8 m-values: one pass of the shared-synthesis kernel) keeps the matrix form on
+  // the belt too: the FFT computes every m of a ring whether wanted or not — 14 CU-cycles per (pixel, column) at nside
+  // 512 with four maps (150 KB of LDS: one workgroup per CU) against ~1 per group of four m-rows on the matrix pipe.
+  // One m-block of configs[4] (59.6 GB: a rank holds one or two at a time) 24.8 -> 4.6 s of ring transform
+  // (scratch/btgen_narrow_probe.py: 784 -> 146 ms on 8 of the 256 frequencies; 4 m-values 833 -> 229, 8: 1039 -> 555).
+  // The two forms round differently (2e-13 of the largest coefficient): blocks are the same BITS for any partition
+  // of m whose calls are all wide, and equal to rounding when narrow calls are involved.
+  static const int narrow_max = getenv("DM_BT_NARROW") ? atoi(getenv("DM_BT_NARROW")) : 8;
+  pl.narrow = cnt <= narrow_max;
+  pl.use_fft = !fft_off && !pl.narrow && nside >= 2 && (N & (N - 1)) == 0 && N <= 4096 && pl.fft_lds <= 160u * 1024u - 256u;
+  pl.fft = nullptr;
+  pl.cpw = 0;
+  pl.fft_grid = dim3(0, 0, 0);
+  pl.nring_dft = nring;
+  if (pl.use_fft) {
+    pl.nring_dft = 2 * nside - 2;   // rings r < nside - 1 and r > 3 nside - 1
+    const int nring_eq = 2 * nside + 1;
+    pl.cpw = std::max(4, std::min(32, (int)(((size_t)ncol * nring_eq) / 4096)));
+    pl.fft_grid = dim3((unsigned)((ncol + pl.cpw - 1) / pl.cpw), (unsigned)nring_eq);
+    for (const bt_fft_row& k : bt_fft_rows)
+      if (k.P == P && k.npt == std::max(1, N / 256)) pl.fft = &k;
+    if (!pl.fft) return false;
+  }
+  pl.dft = nullptr;
+  pl.dft_grid = dim3(0, 0, 0);
+  if (pl.nring_dft > 0) {
+    const bt_dft_row* k = bt_dft_rows;
+    while (k->P != P || nmg < k->nmg_from) ++k;   // (the last row of each P takes any nmg)
+    pl.dft = k;
+    pl.dft_grid = dim3((unsigned)((ncol16 + k->cgw - 1) / k->cgw), (unsigned)pl.nring_dft, (unsigned)((nmg + k->mgw - 1) / k->mgw));
+  }
+  return true;
+}
 
 }  // namespace
 
@@ -1401,47 +1461,23 @@ static int bt_ring_fused(dm_ctx* ctx, const bt_sht_args& a, const bt_sht_ws& w) 
     if (!d_rw) return DM_ENOMEM;
   }
   if (!d_fc) return DM_ENOMEM;
-  const int nmg = (w.nm + 3) / 4;  // groups of four m-values
-  // The belt (rings nside - 1 .. 3 nside - 1, all with N = 4 nside pixels) goes by FFT when N is a power of two and the
-  // P maps of a column fit the LDS; the matrix-form kernels below then see the rings of the two caps only.  The choice
-  // depends on nside, P and on whether the call is narrow (below) — not on WHICH m it asks for.
-  static const bool fft_off = getenv("DM_BT_FFT") && atoi(getenv("DM_BT_FFT")) == 0;
-  const int N = 4 * nside;
-  int fft_logn = 0;
-  while ((1 << fft_logn) < N) ++fft_logn;
-  const int fft_sh = std::max(5, fft_logn - 6);   // padding of the LDS arrays, as in the kernel
-  const size_t fft_lds = sizeof(cplx) * ((size_t)P * (N + (N >> fft_sh) + 1) + (N / 2 + ((N / 2) >> fft_sh) + 1));
-  // A NARROW call (at most DM_BT_NARROW = 8 m-values: one pass of the shared-synthesis kernel) keeps the matrix form on
-  // the belt too: the FFT computes every m of a ring whether wanted or not — 14 CU-cycles per (pixel, column) at nside
-  // 512 with four maps (150 KB of LDS: one workgroup per CU) against ~1 per group of four m-rows on the matrix pipe.
-  // One m-block of configs[4] (59.6 GB: a rank holds one or two at a time) 24.8 -> 4.6 s of ring transform
-  // (scratch/btgen_narrow_probe.py: 784 -> 146 ms on 8 of the 256 frequencies; 4 m-values 833 -> 229, 8: 1039 -> 555).
-  // The two forms round differently (2e-13 of the largest coefficient): blocks are the same BITS for any partition
-  // of m whose calls are all wide, and equal to rounding when narrow calls are involved.
-  static const int narrow_max = getenv("DM_BT_NARROW") ? atoi(getenv("DM_BT_NARROW")) : 8;
-  const bool narrow = w.cnt <= narrow_max;
-  const bool use_fft = !fft_off && !narrow && nside >= 2 && (N & (N - 1)) == 0 && N <= 4096 && fft_lds <= 160u * 1024u - 256u;
-  int nring_dft = nring;
+  bt_ring_plan pl;
+  DM_ARG(ctx, bt_ring_plan_make(nside, P, w.cnt, ncol, pl));   // narrow or wide, the belt by FFT or not, the kernels and grids
+  const int nring_dft = pl.nring_dft;
   const int* d_caps = nullptr;
-  if (use_fft) {
+  if (pl.use_fft) {
     std::vector<int> caps;
     for (int r = 0; r < nring; ++r)
       if (r < nside - 1 || r > 3 * nside - 1) caps.push_back(r);
-    nring_dft = (int)caps.size();
+    DM_ARG(ctx, (int)caps.size() == nring_dft);
     if (nring_dft > 0) {
       d_caps = dm_ws_upload(ctx, caps);
       if (!d_caps) return DM_ENOMEM;
     }
-    const int nring_eq = 2 * nside + 1;
-    const int cpw = std::max(4, std::min(32, (int)(((size_t)ncol * nring_eq) / 4096)));
-    const dim3 grid((unsigned)((ncol + cpw - 1) / cpw), (unsigned)nring_eq);
-    bt_fft_fn kern = nullptr;
-    for (const bt_fft_row& k : bt_fft_rows)
-      if (k.P == P && k.npt == std::max(1, N / 256)) kern = k.fn[cbm];
-    DM_ARG(ctx, kern != nullptr);
-    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds));
-    DM_PLAUNCH(ctx, DM_PROF_BT_RING, kern, grid, dim3(256), fft_lds, ctx->stream, w.gh.g, fr, syn->beams_dev, bstride, d_fc, ncol, a.m_lo,
-                       w.cnt, d_rw, w.G, w.ncp, nside - 1, cpw);
+    bt_fft_fn kern = pl.fft->fn[cbm];
+    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.fft_lds));
+    DM_PLAUNCH(ctx, DM_PROF_BT_RING, kern, pl.fft_grid, dim3(256), pl.fft_lds, ctx->stream, w.gh.g, fr, syn->beams_dev, bstride, d_fc, ncol, a.m_lo,
+                       w.cnt, d_rw, w.G, w.ncp, nside - 1, pl.cpw);
   }
   // (m, ring) pairs below rounding: exact zeros, no work (bt_ring_skip_lookup; DM_BT_RING_SKIP=0 computes them all)
   const bool ring_skip_off = getenv("DM_BT_RING_SKIP") && atoi(getenv("DM_BT_RING_SKIP")) == 0;   // (read per call: the tests flip it)
@@ -1450,13 +1486,9 @@ static int bt_ring_fused(dm_ctx* ctx, const bt_sht_args& a, const bt_sht_ws& w) 
     d_mskip = dm_ws_upload(ctx, bt_ring_skip_lookup(nside, a.lmax_grp, a.polarised != 0, a.ring_cth_host, a.ring_sth_host));
     if (!d_mskip) return DM_ENOMEM;
   }
-  if (nring_dft > 0) {
-    const bt_dft_row* k = bt_dft_rows;
-    while (k->P != P || nmg < k->nmg_from) ++k;   // (the last row of each P takes any nmg)
-    const dim3 grid((unsigned)((ncol16 + k->cgw - 1) / k->cgw), (unsigned)nring_dft, (unsigned)((nmg + k->mgw - 1) / k->mgw));
-    DM_PLAUNCH(ctx, DM_PROF_BT_RING, k->fn[cbm], grid, dim3(256), 0, ctx->stream, w.gh.g, fr, syn->beams_dev, bstride, d_fc, ncol16, a.m_lo,
+  if (nring_dft > 0)
+    DM_PLAUNCH(ctx, DM_PROF_BT_RING, pl.dft->fn[cbm], pl.dft_grid, dim3(256), 0, ctx->stream, w.gh.g, fr, syn->beams_dev, bstride, d_fc, ncol16, a.m_lo,
                        w.cnt, d_rw, w.G, w.ncp, d_caps, d_mskip);
-  }
   DM_HIP(ctx, hipGetLastError());
   return DM_OK;
 }
@@ -1937,6 +1969,37 @@ int dm_bt_alias_info(int nside, const double* ring_cth_host, const double* ring_
   const bt_alias_info& al = bt_alias_lookup(nside, lmax_grp, polarised != 0, ring_cth_host, ring_sth_host);
   *n_alias_rings = al.ia;
   *mcut = al.ia > 0 ? std::min(al.mcut, lmax_grp) : -1;
+  return DM_OK;
+}
+
+// What the fused ring transform of dm_bt_columns / dm_bt_columns_c launches for a call (bt_ring_plan_make, the function the
+// launch itself goes through): whether the belt goes by FFT, that kernel's pixels per thread and columns per workgroup,
+// the rings left to the matrix form and its kernel as dft_row = (shared-synthesis form?, P, NMG, NCG).  A call without
+// content (m_lo above lmax_grp, no columns) launches nothing: everything is zero.  complex_beams picks the variant of
+// each kernel, not the row.
+int dm_bt_ring_plan_info(int nside, int polarised, int m_lo, int m_hi, int lmax_grp, int complex_beams, int ncol, int* use_fft,
+                         int* fft_npt, int* fft_cpw, int* nring_dft, int* dft_row) {
+  if (nside <= 0 || nside > (1 << 24) || m_lo < 0 || m_hi < m_lo || lmax_grp < 0 || ncol < 0 || (complex_beams != 0 && complex_beams != 1) ||
+      !use_fft || !fft_npt || !fft_cpw || !nring_dft || !dft_row)
+    return DM_EARG;
+  *use_fft = *fft_npt = *fft_cpw = *nring_dft = 0;
+  for (int i = 0; i < 4; ++i) dft_row[i] = 0;
+  const int cnt = std::max(std::min(m_hi, lmax_grp) - m_lo + 1, 0);   // as bt_sht_run
+  if (cnt == 0 || ncol == 0) return DM_OK;
+  bt_ring_plan pl;
+  if (!bt_ring_plan_make(nside, polarised ? 4 : 1, cnt, ncol, pl)) return DM_EARG;
+  if (pl.use_fft) {
+    *use_fft = 1;
+    *fft_npt = pl.fft->npt;
+    *fft_cpw = pl.cpw;
+  }
+  *nring_dft = pl.nring_dft;
+  if (pl.dft) {
+    dft_row[0] = pl.dft->dft2;
+    dft_row[1] = pl.dft->P;
+    dft_row[2] = pl.dft->nmg;
+    dft_row[3] = pl.dft->ncg;
+  }
   return DM_OK;
 }
 

@@ -610,6 +610,15 @@ int dm_bt_columns_iter(dm_ctx* ctx, int nside, const double* ring_cth_host, cons
 int dm_bt_alias_info(int nside, const double* ring_cth_host, const double* ring_sth_host, int polarised, int lmax_grp,
                      int* n_alias_rings, int* mcut);
 
+/* dm_bt_ring_plan_info: what the fused ring transform of dm_bt_columns / dm_bt_columns_c launches for a call (host only,
+ * no GPU work; the launch goes through the same function).  use_fft: the belt rings go by the LDS FFT, with fft_npt
+ * pixels per thread and fft_cpw columns per workgroup (both 0 without FFT); nring_dft: rings left to the matrix form;
+ * dft_row (4 ints): its kernel as (1 for the shared-synthesis form else 0, P, NMG, NCG), zeros where nring_dft is 0.
+ * A call without content (m_lo > lmax_grp or ncol = 0) launches nothing and reports zeros.  DM_BT_FFT and
+ * DM_BT_NARROW are honoured as by the launch (both read once per process). */
+int dm_bt_ring_plan_info(int nside, int polarised, int m_lo, int m_hi, int lmax_grp, int complex_beams, int ncol,
+                         int* use_fft, int* fft_npt, int* fft_cpw, int* nring_dft, int* dft_row);
+
 /* ---- bit truncation of beam-transfer blocks before they are written ------------------------------- */
 /* In place on `nrows` rows of `ncols` complex128 values (`ld` elements between rows): every real and
  * imaginary part is rounded to the coarsest multiple of a power of two that keeps its error below
