@@ -216,6 +216,9 @@ SIGNATURES = {
     "dm_redcal_solve": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp,
                 ctypes.POINTER(c_dbl), c_vp, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "dm_modelcal_solve": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                c_vp, c_vp, c_vp, ctypes.POINTER(c_dbl), c_vp, c_vp, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
     "dm_sidereal_regrid": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "dm_sidereal_max_taps": (c_int, []),
@@ -1218,6 +1221,80 @@ def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=No
 
 
 Context.redcal_solve = _redcal_solve
+
+
+def _modelcal_solve(self, vis, model, class_off, members, interval, w=None, feed_weight=None, g0=None, active=None,
+                    damping=0.5, tol=1e-10, maxiter=500, out=None):
+    """Sky-model gain calibration (dm_modelcal_solve; `timestream.modelcal_solve_host` restates
+    it): the per-feed gains g (nreal, nf, nfeed, nint), constant over a solution interval of `interval` consecutive samples
+    (nint = ceil(ntime / interval), the last one may be shorter), that minimise sum_{t in q} sum_m omega_m |V_m - g_i
+    conj(g_j) M_c|^2 per (realisation, frequency, interval) against the stacked model M (1 or nreal, nf, npairs, ntime), by
+    the damped StEFCal fixed point from g0 (ones when None).  vis, w and feed_weight as for `vis_stack`; omega_m = w_m fw_i
+    fw_j, 0 for autocorrelations.  active: an int32 tensor (nf, nint) or None; an interval whose entry is 0 is not solved
+    and returns g0, iters 0, step 0, chi2 0 and gweight 0.  Returns (g, info), info a dict of device tensors: `iters`
+    int32, `step` (the last step; the interval converged iff step < tol) and `chi2` at the result, each (nreal, nf, nint),
+    and `gweight` (nreal, nf, nfeed, nint), the denominator of every gain at the result: the information it carries, 0
+    where the gain is unconstrained.  A fixed model leaves one phase per connected component of the feed graph free:
+    `timestream.modelcal_fix_phase` removes it.  out: a dict of preallocated contiguous tensors under the names g, iters,
+    step, chi2, gweight (any subset).  The bits of an interval do not depend on the batch it is solved in."""
+    rs = _rstride_of(vis, True)
+    if rs is None:
+        raise ValueError("modelcal_solve: complex128 tensor vis (nreal, nf, nmem, ntime) expected")
+    nreal, nf, nmem, ntime = (int(v) for v in vis.shape)
+    off, offp, mem, memp = _class_table("modelcal_solve", class_off, members)
+    npairs = off.shape[0] - 1
+    if mem.shape[0] != nmem:
+        raise ValueError("modelcal_solve: vis has %d rows, the table %d members" % (nmem, mem.shape[0]))
+    if not (_is_c128(model) and model.dim() == 4 and tuple(model.shape)[1:] == (nf, npairs, ntime)
+            and int(model.shape[0]) in (1, nreal)):
+        raise ValueError("modelcal_solve: model must be a contiguous complex128 tensor (1 or nreal, nf, npairs, ntime)")
+    m_nreal = int(model.shape[0])
+    interval = int(interval)
+    nint = -(-ntime // interval) if interval >= 1 else 0
+    nfeed = int(mem.max()) + 1 if mem.size else 0
+    w_nreal = 1
+    if w is not None:
+        if not (hasattr(w, "data_ptr") and w.dim() == 4 and not w.is_complex() and w.element_size() == 8
+                and w.is_contiguous() and tuple(w.shape)[1:] == (nf, nmem, ntime) and int(w.shape[0]) in (1, nreal)):
+            raise ValueError("modelcal_solve: w must be a contiguous float64 tensor (1 or nreal, nf, nmem, ntime)")
+        w_nreal = int(w.shape[0])
+    fwp = None
+    if feed_weight is not None:
+        fw = np.ascontiguousarray(feed_weight, dtype=np.float64)
+        if fw.ndim != 1 or fw.shape[0] < nfeed:
+            raise ValueError("modelcal_solve: feed_weight must have one entry per feed")
+        nfeed = int(fw.shape[0])
+        fwp = fw.ctypes.data_as(ctypes.POINTER(c_dbl))
+    if g0 is not None:
+        if not (_is_c128(g0) and g0.dim() == 4 and (int(g0.shape[0]), int(g0.shape[1]), int(g0.shape[3])) == (nreal, nf, nint)
+                and int(g0.shape[2]) >= nfeed and (feed_weight is None or int(g0.shape[2]) == nfeed)):
+            raise ValueError("modelcal_solve: g0 must be a contiguous complex128 tensor (nreal, nf, nfeed, nint)")
+        nfeed = int(g0.shape[2])
+    if active is not None and not (hasattr(active, "data_ptr") and active.dtype == self.torch.int32 and active.is_contiguous()
+                                   and tuple(active.shape) == (nf, nint)):
+        raise ValueError("modelcal_solve: active must be a contiguous int32 tensor (nf, nint)")
+    out = dict(out or {})
+    shapes = dict(g=((nreal, nf, nfeed, nint), np.complex128), iters=((nreal, nf, nint), np.int32),
+                  step=((nreal, nf, nint), np.float64), chi2=((nreal, nf, nint), np.float64),
+                  gweight=((nreal, nf, nfeed, nint), np.float64))
+    if set(out) - set(shapes):
+        raise ValueError("modelcal_solve: out holds %s" % sorted(set(out) - set(shapes)))
+    for name, (shape, dt) in shapes.items():
+        if out.get(name) is None:
+            out[name] = self.empty(shape, dt)
+        t = out[name]
+        if not (hasattr(t, "data_ptr") and tuple(t.shape) == shape and t.is_contiguous()
+                and t.dtype == self.empty((0,), dt).dtype):
+            raise ValueError("modelcal_solve: out[%r] must be a contiguous %s tensor of shape %s" % (name, np.dtype(dt), shape))
+    rc = self.lib.dm_modelcal_solve(self.h, nreal, w_nreal, m_nreal, nf, nfeed, npairs, ntime, interval, offp, memp,
+                                    self.ptr(vis), self.ptr(model), self.ptr(w), fwp, self.ptr(g0), self.ptr(active),
+                                    float(damping), float(tol), int(maxiter), self.ptr(out["g"]), self.ptr(out["iters"]),
+                                    self.ptr(out["step"]), self.ptr(out["chi2"]), self.ptr(out["gweight"]), rs)
+    self.check(rc, "dm_modelcal_solve")
+    return out["g"], dict(iters=out["iters"], step=out["step"], chi2=out["chi2"], gweight=out["gweight"])
+
+
+Context.modelcal_solve = _modelcal_solve
 
 
 def _toeplitz_max_rhs(self, n):

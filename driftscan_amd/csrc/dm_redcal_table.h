@@ -22,14 +22,16 @@ struct dm_redcal_table {
   std::vector<double> gfac;          // (nmem) yfac, 0 on the members of an unconstrained class: gain step and chi^2
   std::vector<int> inc_off;          // (nfeed + 1)
   std::vector<dm_redcal_inc> inc;    // per feed, in member order, its members with gfac > 0
-  int nconstrained = 0;              // classes with at least two members of yfac > 0
+  int nconstrained = 0;              // classes with at least min_live (two) members of yfac > 0
 };
 
 // The factors and the incidence table for a checked class table (dm_stack_table_check) and feed weights >= 0 or null
 // (ones).  A class constrains the gains when at least two of its members join different feeds of positive weight;
 // every member of any other class gets gfac = 0 and is not listed.  A function of the table and the feed weights alone.
+// min_live = 1 drops that rule (dm_modelcal_solve, section 4.21: against a given model a class of one member constrains
+// its two feeds), so that gfac == yfac and every member of yfac > 0 is listed.
 inline dm_redcal_table dm_redcal_build(int nfeed, int npairs, const int* class_off, const int* members,
-                                       const double* feed_weight) {
+                                       const double* feed_weight, int min_live = 2) {
   dm_redcal_table t;
   const int64_t nmem = npairs > 0 ? class_off[npairs] : 0;
   t.yfac.assign((size_t)nmem, 0.0);
@@ -45,7 +47,7 @@ inline dm_redcal_table dm_redcal_build(int nfeed, int npairs, const int* class_o
         ++live;
       }
     }
-    if (live < 2) continue;
+    if (live < min_live) continue;
     ++t.nconstrained;
     for (int k = class_off[c]; k < class_off[c + 1]; ++k)
       if (t.yfac[k] > 0.0) {

@@ -8,9 +8,12 @@ block of arguments for ``timestream.simulate`` plus its ``product_directory``;
 the files of its ``maps`` and ``sources`` lists go through ``fixpath``; with ``unstacked: true`` the block goes to
 ``timestream.simulate_unstacked`` instead — one realisation of the device route of ``simulate_ensemble``, one row per feed
 pair; such an entry is kept in ``unstacked``, apart from the timestreams the stages run on — and an entry with
-``stack_from: {directory, calibrate: file|none|redundant, redcal: {...}, dead_feeds: [...]}`` is made from such a
-directory by ``timestream.stack_baselines`` before the m-modes, when its own directory does not exist yet; ``redcal``
-holds the solver's ``damping``, ``tol``, ``maxiter`` and ``reference`` (``file`` or absent) of ``calibrate: redundant``)
+``stack_from: {directory, calibrate: file|none|redundant|model, redcal: {...}, modelcal: {...}, dead_feeds: [...]}`` is
+made from such a directory by ``timestream.stack_baselines`` before the m-modes, when its own directory does not exist
+yet; ``redcal`` holds the solver's ``damping``, ``tol``, ``maxiter`` and ``reference`` (``file``, ``model`` or absent) of
+``calibrate: redundant``; ``modelcal`` holds the ``model`` (a stacked timestream directory, through ``fixpath``),
+``interval``, ``damping``, ``tol``, ``maxiter``, ``edge_floor`` and ``min_model`` of ``calibrate: model`` and of
+``reference: model``)
 and optionally ``crosspower`` (entries with ``psname``, ``klname``, ``timestreams``, ``psfile``) — the same defaults,
 exceptions and methods.  Two deliberate differences:
 
@@ -153,6 +156,14 @@ class PipelineManager(config.Reader):
             else:
                 timestream.simulate(products, ts.directory, **simconf)
 
+    @staticmethod
+    def _modelcal(conf):
+        """The `modelcal` block of a `stack_from` entry: the path of its `model` directory resolved."""
+        conf = dict(conf)
+        if isinstance(conf.get("model"), str):
+            conf["model"] = fixpath(conf["model"])
+        return conf
+
     def stack(self):
         """Make the timestreams that carry a `stack_from` block and whose directory does not exist yet: the unstacked
         directory named there goes through `timestream.stack_baselines`."""
@@ -166,6 +177,7 @@ class PipelineManager(config.Reader):
                                        calibrate=None if calibrate in (None, "none") else calibrate,
                                        dead_feeds=tuple(conf.get("dead_feeds", ()) or ()), chunk_gb=self.chunk_gb,
                                        **({"redcal": dict(conf["redcal"])} if conf.get("redcal") else {}),
+                                       **({"modelcal": self._modelcal(conf["modelcal"])} if conf.get("modelcal") else {}),
                                        **({"rfi": conf["rfi"]} if conf.get("rfi") is not None else {}))
         # `sidereal_from: {days: [dir, ...], a: 3, min_share: 1.0, rfi: {...}}`: the days, which may be the stacks made above, are
         # regridded and averaged by `timestream.sidereal_stack`

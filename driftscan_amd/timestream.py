@@ -1501,6 +1501,206 @@ def fix_degeneracies(g, y, class_off, members, ref=None, feed_weight=None, bases
     return h * g, y / fac
 
 
+def modelcal_weights(class_off, members, nfeed, feed_weight=None):
+    """The member factor fw_i fw_j float64 (nmem) of the sky-model calibration, 0 for an
+    autocorrelation: `yfac` of `redcal_weights`.  The "fewer than two members" exclusion does not apply: against a given
+    model a class of one member constrains its two feeds."""
+    return redcal_weights(class_off, members, nfeed, feed_weight)[0]
+
+
+def _modelcal_nint(ntime, interval):
+    if int(interval) < 1:
+        raise ValueError("modelcal: interval must be at least 1")
+    return -(-int(ntime) // int(interval))
+
+
+def _modelcal_sums(vis, model, class_off, members, g, interval, w, feed_weight, dtype):
+    """(g, num, den) [..., nfeed, nint] in `dtype`: numerator and denominator of the gain line of section 4.21 at the
+    gains g, summed over the incidences of every feed and the samples of every interval."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    real = _real_dtype(dtype)
+    gl = np.asarray(g).astype(dtype)
+    vl = np.asarray(vis).astype(dtype)
+    nfeed, ntime = gl.shape[-2], vl.shape[-1]
+    if gl.shape[-1] != _modelcal_nint(ntime, interval):
+        raise ValueError("modelcal: g has %d intervals, %d samples of interval %d make %d"
+                         % (gl.shape[-1], ntime, interval, _modelcal_nint(ntime, interval)))
+    fac = modelcal_weights(class_off, members, nfeed, feed_weight)
+    n = np.diff(np.asarray(class_off, dtype=np.int64))
+    cls = np.repeat(np.arange(n.shape[0]), n)
+    use = np.nonzero(fac > 0)[0]
+    i, j = members[use, 0], members[use, 1]
+    v = vl[..., use, :]
+    om = np.broadcast_to(fac[use, None].astype(real), v.shape)
+    if w is not None:
+        om = om * np.broadcast_to(np.asarray(w).astype(real), vl.shape)[..., use, :]
+    gb = np.broadcast_to(gl, v.shape[:-2] + gl.shape[-2:])
+    gs = gb[..., np.arange(ntime) // int(interval)]                         # every sample takes its interval's gain
+    ml = np.asarray(model).astype(dtype)
+    mc = np.broadcast_to(ml, v.shape[:-2] + ml.shape[-2:])[..., cls[use], :]
+    gi, gj = gs[..., i, :], gs[..., j, :]
+    am2 = mc.real**2 + mc.imag**2
+    num = np.zeros((nfeed,) + gb.shape[:-2] + gb.shape[-1:], dtype=dtype)
+    den = np.zeros(num.shape, dtype=real)
+    starts = np.arange(0, ntime, int(interval))
+    if ntime and use.size:                                                  # the samples of an interval first, then the feeds
+        first = lambda x: np.moveaxis(np.add.reduceat(x, starts, axis=-1), -2, 0)
+        np.add.at(num, i, first(om * (v * gj * mc.conj())))
+        np.add.at(num, j, first(om * (v.conj() * gi * mc)))
+        np.add.at(den, i, first(om * ((gj.real**2 + gj.imag**2) * am2)))
+        np.add.at(den, j, first(om * ((gi.real**2 + gi.imag**2) * am2)))
+    return gb, np.moveaxis(num, 0, -2), np.moveaxis(den, 0, -2)
+
+
+def modelcal_step_host(vis, model, class_off, members, g, interval, w=None, feed_weight=None, damping=0.5,
+                       dtype=np.complex128):
+    """One iteration of `Context.modelcal_solve` in numpy, computed in `dtype`: (g_new, step, den) of the statement of
+    DESIGN.md section 4.21 from the gains g [..., nfeed, nint] —
+
+        gh_a = [sum_t sum_{m=(a,j)} omega V_m g_j conj(M_c) + sum_t sum_{m=(i,a)} omega conj(V_m) g_i M_c]
+               / [sum_t sum_{m=(a,j)} omega |g_j|^2 |M_c|^2 + sum_t sum_{m=(i,a)} omega |g_i|^2 |M_c|^2]   (g_a where it is 0)
+        g_new = (1 - damping) g + damping gh,   step = max_a |g_new_a - g_a| / |g_a|  [..., nint]
+
+    with omega = w `modelcal_weights`, t over the samples q L <= t < min((q + 1) L, ntime) of interval q, vis [..., nmem,
+    ntime] and the stacked model [..., npairs, ntime] broadcastable against it.  den [..., nfeed, nint] is the denominator
+    at g: `gweight` of the solver when g is its result."""
+    real = _real_dtype(dtype)
+    gb, num, den = _modelcal_sums(vis, model, class_off, members, g, interval, w, feed_weight, dtype)
+    some = den > 0
+    gh = np.where(some, num / np.where(some, den, 1), gb)
+    gn = ((1 - real.type(damping)) * gb + real.type(damping) * gh).astype(dtype)
+    gn = np.where(some, gn, gb)
+    d = np.abs(gn - gb)
+    step = np.where(d == 0, 0, d / np.where(d == 0, 1, np.abs(gb)))
+    step = step.max(axis=-2) if step.shape[-2] else np.zeros(step.shape[:-2] + step.shape[-1:], dtype=real)
+    return gn, step, den
+
+
+def modelcal_chi2_host(vis, model, class_off, members, g, interval, w=None, feed_weight=None, dtype=np.complex128):
+    """chi^2 = sum_{t in q} sum_m omega_m |V_m - g_i conj(g_j) M_c|^2 [..., nint] in `dtype`, omega = w
+    `modelcal_weights`, g [..., nfeed, nint]."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    real = _real_dtype(dtype)
+    gl = np.asarray(g).astype(dtype)
+    vl = np.asarray(vis).astype(dtype)
+    ntime = vl.shape[-1]
+    fac = modelcal_weights(class_off, members, gl.shape[-2], feed_weight)
+    gs = gl[..., np.arange(ntime) // int(interval)]
+    res = vl - vis_expand_host(model, class_off, members, g=gs, dtype=dtype)
+    om = fac[:, None].astype(real)
+    if w is not None:
+        om = om * np.asarray(w).astype(real)
+    per = (om * (res.real**2 + res.imag**2)).sum(axis=-2)
+    return np.add.reduceat(per, np.arange(0, ntime, int(interval)), axis=-1) if ntime else per
+
+
+def modelcal_solve_host(vis, model, class_off, members, interval, w=None, feed_weight=None, g0=None, active=None,
+                        damping=0.5, tol=1e-10, maxiter=500, dtype=np.complex128, nfeed=None):
+    """`Context.modelcal_solve` in numpy, computed in `dtype`: (g, info) with g [..., nfeed, nint] and info =
+    dict(iters, step, chi2 [..., nint], gweight [..., nfeed, nint]).  An interval freezes after the first iteration whose
+    step is below tol; one that reaches maxiter with step >= tol reports iters = maxiter.  active [nf, nint] (or
+    broadcastable against [..., nint]): an interval whose entry is 0 keeps g0 and reports 0 throughout."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    real = _real_dtype(dtype)
+    vl = np.asarray(vis).astype(dtype)
+    nint = _modelcal_nint(vl.shape[-1], interval)
+    if g0 is None:
+        nfeed = (int(members.max()) + 1 if members.size else 0) if nfeed is None else nfeed
+        if feed_weight is not None:
+            nfeed = len(feed_weight)
+        g = np.ones(vl.shape[:-2] + (nfeed, nint), dtype=dtype)
+    else:
+        g = np.array(np.broadcast_to(np.asarray(g0).astype(dtype), vl.shape[:-2] + np.shape(g0)[-2:]))
+    if not (0 < damping <= 1) or not (tol >= 0 and np.isfinite(tol)) or maxiter < 1:
+        raise ValueError("modelcal_solve_host: damping in (0, 1], tol >= 0 and finite, maxiter >= 1 expected")
+    sshape = vl.shape[:-2] + (nint,)
+    asked = np.ones(sshape, dtype=bool) if active is None else np.array(np.broadcast_to(np.asarray(active) != 0, sshape))
+    live = asked.copy()
+    iters = np.zeros(sshape, dtype=np.int32)
+    step = np.zeros(sshape, dtype=real)
+    for k in range(1, maxiter + 1):
+        if not live.any():
+            break
+        gn, st, _ = modelcal_step_host(vl, model, class_off, members, g, interval, w=w, feed_weight=feed_weight,
+                                       damping=damping, dtype=dtype)
+        g = np.where(live[..., None, :], gn, g)
+        step = np.where(live, st, step)
+        iters[live] = k
+        live = live & ~(st < tol)
+    _, _, den = _modelcal_sums(vl, model, class_off, members, g, interval, w, feed_weight, dtype)
+    chi2 = modelcal_chi2_host(vl, model, class_off, members, g, interval, w=w, feed_weight=feed_weight, dtype=dtype)
+    return g, dict(iters=iters, step=step, chi2=np.where(asked, chi2, 0), gweight=np.where(asked[..., None, :], den, 0))
+
+
+def modelcal_components(class_off, members, nfeed, model_power, feed_weight=None, edge_floor=1e-6):
+    """Labels (nfeed) int64 of the connected components of the feed graph a model connects: the
+    edges are the members of `modelcal_weights` > 0 whose class has model_power[c] = sum_t |M_c|^2 of the interval of at
+    least edge_floor times the largest class (and above 0).  A fixed model leaves one free phase per component: an
+    unpolarised source on a polarised array has no XY model, so the X and the Y feeds are two components.  The labels
+    count the components from 0 in the order of their first feed; a feed no edge reaches is a component of its own."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+    power = np.asarray(model_power, dtype=np.float64)
+    n = np.diff(np.asarray(class_off, dtype=np.int64))
+    if power.shape != n.shape:
+        raise ValueError("modelcal_components: model_power (npairs,) expected")
+    fac = modelcal_weights(class_off, members, nfeed, feed_weight)
+    top = power.max() if power.size else 0.0
+    keep = np.repeat((power >= edge_floor * top) & (power > 0), n) & (fac > 0)
+    root = np.arange(nfeed)
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+
+    for i, j in members[keep]:
+        ri, rj = find(i), find(j)
+        if ri != rj:
+            root[max(ri, rj)] = min(ri, rj)
+    heads = np.array([find(a) for a in range(nfeed)], dtype=np.int64)
+    return np.unique(heads, return_inverse=True)[1].astype(np.int64).reshape(nfeed)
+
+
+def modelcal_fix_phase(g, components, ref=None, feed_weight=None):
+    """Remove the only freedom a fixed model leaves in the gains g [..., nfeed, nint]: per interval and component
+    (`modelcal_components`: labels (nfeed,), or an array broadcastable against g when they differ between intervals) g is
+    rotated so that sum_a fw_a g_a conj(ref_a) over the component is real and positive; ref (broadcastable against g)
+    defaults to ones.  A component whose sum is 0 is left alone.  Every g_i conj(g_j) inside a component is unchanged.
+    Returns complex128.  Numpy on the host: not a kernel."""
+    g = np.asarray(g, dtype=np.complex128)
+    nfeed = g.shape[-2]
+    comp = np.asarray(components, dtype=np.int64)
+    comp = np.broadcast_to(comp[:, None] if comp.ndim == 1 else comp, g.shape)
+    fw = np.ones(nfeed) if feed_weight is None else np.asarray(feed_weight, dtype=np.float64)
+    r = np.ones(g.shape, dtype=np.complex128) if ref is None else np.broadcast_to(np.asarray(ref, dtype=np.complex128), g.shape)
+    prod = fw[:, None] * g * r.conj()
+    out = g.copy()
+    for label in np.unique(comp):
+        mask = comp == label
+        s = np.where(mask, prod, 0).sum(axis=-2, keepdims=True)
+        mag = np.abs(s)
+        rot = np.where(mag > 0, s.conj() / np.where(mag > 0, mag, 1), 1.0)
+        out = np.where(mask, g * rot, out)
+    return out
+
+
+def modelcal_spread(g, valid, interval, ntime):
+    """Interval gains g (nfeed, nint) spread over their samples: (gains (nfeed, ntime) complex128, found).  Sample t takes
+    the gain of interval t // interval; an interval that is not `valid` (nint) takes the gain of the nearest valid one, the
+    earlier on a tie.  Where no interval is valid the gains are all ones and `found` is False."""
+    g = np.asarray(g, dtype=np.complex128)
+    valid = np.asarray(valid, dtype=bool)
+    nint = _modelcal_nint(ntime, interval)
+    if g.ndim != 2 or g.shape[1] != nint or valid.shape != (nint,):
+        raise ValueError("modelcal_spread: g (nfeed, nint) and valid (nint) expected, nint = %d" % nint)
+    good = np.nonzero(valid)[0]
+    if good.size == 0:
+        return np.ones((g.shape[0], int(ntime)), dtype=np.complex128), False
+    src = good[np.abs(np.arange(nint)[:, None] - good[None, :]).argmin(axis=1)]   # argmin: the first, so the earlier
+    return np.ascontiguousarray(g[:, src[np.arange(int(ntime)) // int(interval)]]), True
+
+
 def _member_sigma(tel, freqs, ndays, ntime, class_off):
     """sigma[f, m] = sqrt(n_c ntime noisepower(c, f, ndays)) of the unstacked noise: the plain mean of a complete class
     then has the noise level of the stacked simulators."""
@@ -1817,7 +2017,92 @@ def _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed
 REDCAL_DEFAULTS = dict(damping=0.4, tol=1e-10, maxiter=500, reference=None)
 
 
-def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None, rfi=None):
+MODELCAL_DEFAULTS = dict(model=None, interval=16, damping=0.5, tol=1e-10, maxiter=500, edge_floor=1e-6, min_model=0.0)
+
+
+def _modelcal_conf(modelcal, m, nfreq, npairs, ntime, tphi):
+    """The checked dict `modelcal` of `stack_baselines`: (solver keywords, edge_floor, min_model, model(fi) -> (npairs,
+    ntime) complex128)."""
+    if set(modelcal or {}) - set(MODELCAL_DEFAULTS):
+        raise ValueError("modelcal holds %s, not in %s" % (sorted(set(modelcal) - set(MODELCAL_DEFAULTS)), sorted(MODELCAL_DEFAULTS)))
+    conf = dict(MODELCAL_DEFAULTS, **(modelcal or {}))
+    model = conf.pop("model")
+    if model is None:
+        raise ValueError("modelcal needs `model`: a stacked Timestream directory or an array (nfreq, npairs, ntime)")
+    edge_floor, min_model = float(conf.pop("edge_floor")), float(conf.pop("min_model"))
+    if not (0 <= edge_floor <= 1 and 0 <= min_model <= 1):
+        raise ValueError("modelcal edge_floor and min_model lie in [0, 1]")
+    solver = dict(interval=int(conf["interval"]), damping=float(conf["damping"]), tol=float(conf["tol"]),
+                  maxiter=int(conf["maxiter"]))
+    if solver["interval"] < 1:
+        raise ValueError("modelcal interval must be at least 1")
+    if isinstance(model, (str, os.PathLike)):
+        mts = Timestream(os.fspath(model), m)
+        if not os.path.exists(mts._ffile(0)):
+            raise ValueError("modelcal model: %s holds no timestream" % mts.directory)
+        if mts.is_unstacked():
+            raise ValueError("modelcal model: %s holds unstacked visibilities, the stacked model is expected" % mts.directory)
+        with storage.File(mts._ffile(0), "r") as f:
+            mphi = np.asarray(f["phi"][:]) if "phi" in f else np.linspace(0, 2 * np.pi, int(f.attrs["ntime"]), endpoint=False)
+        if mphi.shape != tphi.shape or not np.array_equal(mphi, tphi):
+            raise ValueError("modelcal model: %s is sampled at other positions `phi` than the data" % mts.directory)
+
+        def model_f(fi):
+            v = np.asarray(mts.timestream_f(fi), dtype=np.complex128)
+            if v.shape != (npairs, ntime):
+                raise ValueError("modelcal model: %s is %s, not (npairs, ntime) = (%d, %d)" % (mts._ffile(fi), v.shape, npairs, ntime))
+            return v
+    else:
+        arr = np.asarray(model.cpu().numpy() if hasattr(model, "data_ptr") else model, dtype=np.complex128)
+        if arr.shape != (nfreq, npairs, ntime):
+            raise ValueError("modelcal model %s is not (nfreq, npairs, ntime) = (%d, %d, %d)" % (arr.shape, nfreq, npairs, ntime))
+        model_f = lambda fi: arr[fi]
+    return solver, edge_floor, min_model, model_f
+
+
+def _modelcal_chunk(ctx, vis_d, w_d, model, class_off, members, nfeed, fw, solver, edge_floor, min_model):
+    """The sky-model solve of one chunk of frequencies: vis_d (1, nfc, nmem, ntime) and w_d on
+    the device, model (nfc, npairs, ntime) on the host.  Per frequency and interval the classes under edge_floor of the
+    largest are zeroed in the copy of the model that goes to the device, the intervals under min_model of the strongest
+    are not solved, the free phase of every connected component is fixed against ones and the interval gains are spread
+    over their samples.  Returns (gains (nfc, nfeed, ntime), gq (nfc, nfeed, nint), iters (nfc, nint), valid (nfc, nint),
+    frequencies without any valid interval)."""
+    nfc, npairs, ntime = model.shape
+    L = solver["interval"]
+    starts = np.arange(0, ntime, L)
+    tq = np.arange(ntime) // L
+    power = np.add.reduceat(model.real**2 + model.imag**2, starts, axis=-1)             # (nfc, npairs, nint)
+    top = power.max(axis=1, keepdims=True) if npairs else np.zeros((nfc, 1, starts.shape[0]))
+    keep = (power >= edge_floor * top) & (power > 0)
+    model = np.where(keep[..., tq], model, 0.0)
+    total = np.where(keep, power, 0.0).sum(axis=1)                                      # (nfc, nint)
+    active = total >= min_model * total.max(axis=1, keepdims=True)          # min_model = 0 solves all
+    g_d, info = ctx.modelcal_solve(vis_d, ctx.to_device(model[None]), class_off, members, L, w=w_d,
+                                   feed_weight=np.ones(nfeed) if fw is None else fw,
+                                   active=ctx.to_device(active.astype(np.int32)), damping=solver["damping"],
+                                   tol=solver["tol"], maxiter=solver["maxiter"])
+    gq, its = ctx.to_host(g_d)[0], ctx.to_host(info["iters"])[0]
+    live = np.ones(nfeed, dtype=bool) if fw is None else fw > 0
+    valid = active & (ctx.to_host(info["step"])[0] < solver["tol"]) & np.all(ctx.to_host(info["gweight"])[0][:, live] > 0, axis=1)
+    gains = np.empty((nfc, nfeed, ntime), dtype=np.complex128)
+    fixed = np.empty_like(gq)
+    seen, blind = {}, 0
+    for k in range(nfc):
+        comp = np.empty((nfeed, starts.shape[0]), dtype=np.int64)
+        for q in range(starts.shape[0]):                                               # few distinct patterns: solved once each
+            key = keep[k, :, q].tobytes()
+            if key not in seen:
+                seen[key] = modelcal_components(class_off, members, nfeed, keep[k, :, q].astype(np.float64), feed_weight=fw,
+                                                edge_floor=0.5)
+            comp[:, q] = seen[key]
+        fixed[k] = modelcal_fix_phase(gq[k], comp, feed_weight=fw)
+        gains[k], found = modelcal_spread(fixed[k], valid[k], L, ntime)
+        blind += 0 if found else 1
+    return gains, fixed, its, valid, blind
+
+
+def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None, rfi=None,
+                    modelcal=None):
     """Stack the unstacked Timestream directory `indir` (`simulate_ensemble(unstacked=True)`, or a correlator's per-pair
     data in that layout) into the unique baselines of the telescope of ProductManager `m` and write them to `outdir` in
     the layout of `simulate_ensemble`; returns the `Timestream` of `outdir`.
@@ -1833,6 +2118,21 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     `gain_solution` (nfeed, ntime) and `redcal_iters` (ntime).  feed_weight (nfeed) >= 0 weights
     every pair by the product of its two feeds' entries; dead_feeds lists feeds of weight 0.  Ranks take their own
     frequencies, in chunks that fit in `chunk_gb`.
+
+    calibrate="model" solves the gains against a trusted sky model (`Context.modelcal_solve`),
+    constant over solution intervals.  The dict `modelcal` (MODELCAL_DEFAULTS; an unknown key raises ValueError) holds
+    `model` — a stacked Timestream directory on the same sample positions `phi` (another `phi` raises ValueError), or an
+    array / tensor (nfreq, npairs, ntime) — `interval`, the solver's `damping`, `tol` and `maxiter`, `edge_floor` (a class
+    whose sum_t |M_c|^2 over an interval is under this share of the interval's largest class has its model zeroed, so that
+    weakly coupled components of the feed graph decouple exactly) and `min_model` (an interval whose model power is under
+    this share of the frequency's strongest interval is not solved; 0 solves all).  The free phase of every connected
+    component is fixed against ones (`modelcal_fix_phase`).  An interval is valid when it was solved, converged and every
+    feed of weight > 0 has gweight > 0; an invalid one takes the gains of the nearest valid one (`modelcal_spread`) and is
+    counted (a warning of the module's logger, and `modelcal_invalid` of `sim_log`).  The stack runs with the spread
+    gains; the files also hold `gain_solution` (nfeed, ntime), `modelcal_gain` (nfeed, nint), `modelcal_iters` (nint) and
+    `modelcal_valid` (nint).  With calibrate="redundant" and `reference: "model"` in `redcal`, the redundant solve runs
+    per sample as described above and the spread model gains are the reference of `fix_degeneracies`: the model supplies
+    only the degenerate part.
 
     The stacked files hold `weight` (npairs, ntime) = sum_{m in c} w_m fw_i fw_j / n_c, the share of the class that is
     there — for flags and dead feeds (n_c - k) / n_c exactly, the inverse noise variance relative to nominal of section
@@ -1859,7 +2159,7 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
         if not (np.array_equal(f["class_off"][:], class_off) and np.array_equal(f["members"][:], members)):
             raise ValueError("%s was written for another class table than this telescope's" % src.directory)
     if isinstance(calibrate, str):
-        if calibrate not in ("file", "none", "redundant"):
+        if calibrate not in ("file", "none", "redundant", "model"):
             raise ValueError('calibrate is None, "none", "file", "redundant" or an array (nfreq, nfeed, ntime)')
         calibrate = None if calibrate == "none" else calibrate
     elif calibrate is not None:
@@ -1870,15 +2170,20 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
             raise ValueError("calibrate %s is not (nfreq, nfeed, ntime) = (%d, %d, %d)"
                              % (calibrate.shape, nfreq, nfeed, ntime))
     redundant = isinstance(calibrate, str) and calibrate == "redundant"
+    by_model = isinstance(calibrate, str) and calibrate == "model"
     if redcal is not None and not redundant:
         raise ValueError('redcal belongs to calibrate="redundant"')
+    ref_model = False
     if redundant:
         if set(redcal or {}) - set(REDCAL_DEFAULTS):
             raise ValueError("redcal holds %s, not in %s" % (sorted(set(redcal) - set(REDCAL_DEFAULTS)), sorted(REDCAL_DEFAULTS)))
         rconf = dict(REDCAL_DEFAULTS, **(redcal or {}))
         reference = rconf.pop("reference")
         rconf = dict(damping=float(rconf["damping"]), tol=float(rconf["tol"]), maxiter=int(rconf["maxiter"]))
-        if isinstance(reference, str):
+        ref_model = isinstance(reference, str) and reference == "model"
+        if ref_model:
+            reference = None
+        elif isinstance(reference, str):
             if reference not in ("file", "none"):
                 raise ValueError('redcal reference is None, "file" or an array (nfreq, nfeed, ntime)')
             reference = None if reference == "none" else reference
@@ -1887,6 +2192,14 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
             if reference.shape != (nfreq, nfeed, ntime):
                 raise ValueError("redcal reference %s is not (nfreq, nfeed, ntime) = (%d, %d, %d)"
                                  % (reference.shape, nfreq, nfeed, ntime))
+    if modelcal is not None and not (by_model or ref_model):
+        raise ValueError('modelcal belongs to calibrate="model" or to the redcal reference "model"')
+    mconf = None
+    if by_model or ref_model:
+        with storage.File(src._ffile(0), "r") as f:
+            sphi = np.asarray(f["phi"][:]) if "phi" in f else np.linspace(0, 2 * np.pi, ntime, endpoint=False)
+        mconf = _modelcal_conf(modelcal, m, nfreq, npairs, ntime, sphi)
+        mnint = _modelcal_nint(ntime, mconf[0]["interval"])
     fw = None
     if feed_weight is not None or len(dead_feeds) > 0:
         fw = np.ones(nfeed, dtype=np.float64) if feed_weight is None else np.array(feed_weight, dtype=np.float64)
@@ -1904,7 +2217,10 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     if redundant:   # g, the second gain buffer and y of the solver, its three per-sample outputs and its state words
         per_f += ntime * (32.0 * nfeed + 16.0 * npairs + 20.0 + 24.0)
         bases = redcal_degeneracies(class_off, members, nfeed, fw)
+    if mconf is not None:   # the model and its device copy, the solver's three gain buffers and gweight, its words
+        per_f += ntime * 32.0 * npairs + mnint * (56.0 * nfeed + 64.0) + (0.0 if by_model else 16.0 * nfeed * ntime)
     solved, lost = {}, 0
+    msolved, minvalid, mblind = {}, 0, 0
     step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
     log = sim_log
     nmem_c = np.diff(class_off)[:, None].astype(np.float64)
@@ -1924,7 +2240,7 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
                             if "gain" not in f:
                                 raise ValueError('redcal reference "file": %s holds no dataset `gain`' % src._ffile(fi))
                             g.append(np.asarray(f["gain"][:], dtype=np.complex128))
-                    elif isinstance(calibrate, str):
+                    elif isinstance(calibrate, str) and not by_model:
                         if "gain" not in f:
                             raise ValueError('calibrate="file": %s holds no dataset `gain`' % src._ffile(fi))
                         g.append(np.asarray(f["gain"][:], dtype=np.complex128))
@@ -1935,14 +2251,30 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
                 x_d = ctx.to_device(np.stack(vis))
                 w = list(ctx.to_host(ctx.rfi_flag(x_d, w=ctx.to_device(np.stack(w)), **rfi_p)[0]))
                 del x_d
-        vis_d = w_d = None
-        if redundant:
-            with _StepTimer(log, "redcal"):
+        vis_d = w_d = mref = None
+        if mconf is not None:
+            with _StepTimer(log, "modelcal"):
                 vis_d = ctx.to_device(np.stack(vis)[None])
                 w_d = ctx.to_device(np.stack(w)[None]) if weighted else None
+                mg, mq, mits, mvalid, blind = _modelcal_chunk(ctx, vis_d, w_d, np.stack([mconf[3](fi) for fi in fs]), class_off,
+                                                              members, nfeed, fw, mconf[0], mconf[1], mconf[2])
+            for k, fi in enumerate(fs):
+                msolved[fi] = (mg[k], mq[k], mits[k], mvalid[k])
+            minvalid, mblind = minvalid + int((~mvalid).sum()), mblind + blind
+            if by_model:
+                g = list(mg)
+            else:
+                mref = mg
+        if redundant:
+            with _StepTimer(log, "redcal"):
+                if vis_d is None:
+                    vis_d = ctx.to_device(np.stack(vis)[None])
+                    w_d = ctx.to_device(np.stack(w)[None]) if weighted else None
                 gs, ys, info = ctx.redcal_solve(vis_d, class_off, members, w=w_d,
                                                 feed_weight=np.ones(nfeed) if fw is None else fw, **rconf)
                 ref = np.stack(g) if isinstance(reference, str) else (None if reference is None else reference[list(fs)])
+                if ref_model:
+                    ref = mref
                 gfix, _ = fix_degeneracies(ctx.to_host(gs)[0], ctx.to_host(ys)[0], class_off, members, ref=ref,
                                            feed_weight=fw, bases=bases)
                 its, failed = ctx.to_host(info["iters"])[0], ~(ctx.to_host(info["step"])[0] < rconf["tol"])
@@ -1979,14 +2311,25 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
         tphi = np.asarray(f["phi"][:]) if "phi" in f else np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     with _StepTimer(log, "write"):
         for fi in freqs:
-            _write_sim_file(dst, fi, stacked[fi], tphi, weight=wts[fi] if write_w else None,
-                            extra=dict(gain_solution=solved[fi][0], redcal_iters=solved[fi][1]) if redundant else None)
+            extra = dict(gain_solution=solved[fi][0], redcal_iters=solved[fi][1]) if redundant else None
+            if mconf is not None:
+                extra = dict(extra or dict(gain_solution=msolved[fi][0]), modelcal_gain=msolved[fi][1],
+                             modelcal_iters=msolved[fi][2], modelcal_valid=msolved[fi][3].astype(np.int32))
+            _write_sim_file(dst, fi, stacked[fi], tphi, weight=wts[fi] if write_w else None, extra=extra)
     if redundant and lost:
         logging.getLogger(__name__).warning("stack_baselines: the redundant calibration of %d of %d samples did not converge "
                                             "in %d iterations; they are written with weight 0", lost, len(freqs) * ntime,
                                             rconf["maxiter"])
         if log is not None:
             log["redcal_not_converged"] = log.get("redcal_not_converged", 0) + lost
+    if mconf is not None and minvalid:
+        logging.getLogger(__name__).warning("stack_baselines: %d of %d solution intervals of the sky-model calibration are not "
+                                            "valid (not solved, not converged in %d iterations or with an unconstrained "
+                                            "gain) and take the gains of the nearest valid interval; %d frequencies have "
+                                            "none and are stacked with gains of one", minvalid, len(freqs) * mnint,
+                                            mconf[0]["maxiter"], mblind)
+        if log is not None:
+            log["modelcal_invalid"] = log.get("modelcal_invalid", 0) + minvalid
     parallel.barrier()
     if parallel.rank0():
         os.makedirs(dst.directory, exist_ok=True)

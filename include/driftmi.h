@@ -808,6 +808,42 @@ int dm_redcal_solve(dm_ctx* ctx, int nreal, int w_nreal, int nf, int nfeed, int 
                     const double* feed_weight_host, const void* g0_dev, double damping, double tol, int maxiter,
                     void* g_dev, void* y_dev, int* iters_dev, double* step_dev, double* chi2_dev, int64_t vis_rstride);
 
+/* ---- sky-model gain calibration ---------------------------------------------------------- */
+/* dm_modelcal_solve: per-feed gains against a given stacked model M, constant over a solution interval of `interval`
+ * consecutive samples: interval q holds the samples q L <= t < min((q + 1) L, ntime), nint = ceil(ntime / L).  Every
+ * (realisation, frequency, interval) is a problem of its own: minimise
+ *   chi^2 = sum_{t in q} sum_m omega_m(t) |V_m(t) - g_i conj(g_j) M_c(m)(t)|^2,  omega = w[m, t] fw[i] fw[j], 0 for i == j
+ * (a class of one member constrains its two feeds: the "fewer than two" rule of dm_redcal_solve does not apply) by the
+ * damped StEFCal fixed point, from g0:
+ *   gh_a = [sum_t sum_{m=(a,j)} omega V conj(z) + sum_t sum_{m=(i,a)} omega conj(V) conj(z')]
+ *          / [sum omega |z|^2 + sum omega |z'|^2],   z = conj(g_j) M_c, z' = conj(g_i M_c)   (g_a where the denominator is 0)
+ *   g_a <- (1 - damping) g_a + damping gh_a;   step = max_a |delta g_a| / |g_a|  (|g_a| before the update)
+ * An interval freezes after the first iteration whose step is below tol: iters is that iteration and step its step.  One
+ * that reaches maxiter with step >= tol reports iters = maxiter and that step: it is not converged, not refused.
+ *   vis_dev    (nreal, nf, nmem, ntime) c128, vis_rstride elements between realisations (0: contiguous)
+ *   model_dev  contiguous (m_nreal, nf, npairs, ntime) c128, m_nreal = 1 or nreal
+ *   w_dev      contiguous (w_nreal, nf, nmem, ntime) f64 >= 0, w_nreal = 1 or nreal; null: ones
+ *   feed_weight_host (nfeed) f64 >= 0 or null;   g0_dev contiguous (nreal, nf, nfeed, nint) c128 or null: ones
+ *   active_dev contiguous (nf, nint) i32 or null: an interval whose entry is 0 is not solved and returns g0, iters 0,
+ *              step 0, chi2 0 and gweight 0
+ *   g_dev (nreal, nf, nfeed, nint) c128; iters_dev i32, step_dev f64 and chi2_dev f64 (nreal, nf, nint); gweight_dev
+ *   (nreal, nf, nfeed, nint) f64, all contiguous; chi2 is chi^2 and gweight the denominator of every feed at the returned
+ *   g (0: the gain is unconstrained); every element is written
+ * One kernel per iteration on the context's stream, feed-major over an incidence table, which writes the new gains to a
+ * second buffer; one closing kernel for chi2, gweight and g.  The host never waits inside the loop; every 16 iterations
+ * it asks, without waiting, whether an interval is left and stops launching once none is.  No floating-point atomics: the
+ * five outputs of an interval are the same bits alone, in any batch and beside any neighbours.  Refused before any launch
+ * (dm_last_error): everything dm_vis_stack refuses with gains, an nfeed whose gains of one interval (16 nfeed + 64 bytes)
+ * do not fit in 64 KiB of LDS, interval < 1, damping outside (0, 1], tol negative or not finite, maxiter < 1, w_nreal or
+ * m_nreal neither 1 nor nreal, a null output (or vis, model) with work to do, an output sharing an element with vis,
+ * model, w, g0, active or another output.  nreal, nf or ntime = 0 is a no-op.  Returns when the last launch is queued.
+ * No counterpart in the reference, whose data begins at stacked, calibrated baselines. */
+int dm_modelcal_solve(dm_ctx* ctx, int nreal, int w_nreal, int m_nreal, int nf, int nfeed, int npairs, int ntime,
+                      int interval, const int* class_off_host, const int* members_host, const void* vis_dev,
+                      const void* model_dev, const double* w_dev, const double* feed_weight_host, const void* g0_dev,
+                      const int* active_dev, double damping, double tol, int maxiter, void* g_dev, int* iters_dev,
+                      double* step_dev, double* chi2_dev, double* gweight_dev, int64_t vis_rstride);
+
 /* ---- sidereal stacking ----------------------------------------------------------------- */
 /* dm_sidereal_regrid: one day of every row, sampled at phi_j = phi0 + j dphi (j = 0 .. nt_in - 1, dphi > 0, less than
  * one turn), resampled onto the sidereal grid phi_k = 2 pi k / ntime and written to, or added to, the accumulators of

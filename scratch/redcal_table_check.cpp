@@ -1,9 +1,10 @@
 // Stand-alone check of the host side of dm_redcal_solve (driftscan_amd/csrc/dm_redcal_table.h): the member factors with
-// the "fewer than two" rule, the feed-major incidence table, the argument checks and the split of the feeds, meant to be
+// the "fewer than two" rule, the feed-major incidence table, the argument checks and the split of the feeds, and of
+// dm_modelcal_solve (dm_modelcal_table.h: the same table without that rule, the intervals, its argument checks), meant to be
 // built with the address and undefined-behaviour sanitizers on the CPU:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all scratch/redcal_table_check.cpp -o redcal_table_check
 // Every table is a heap allocation of exactly its size, so a read past a table's end is reported.
-#include "../driftscan_amd/csrc/dm_redcal_table.h"
+#include "../driftscan_amd/csrc/dm_modelcal_table.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -20,9 +21,10 @@ static void check(const char* what, bool ok) {
 
 // What the kernels rely on: inc_off ascends from 0 to the number of incidences, every constrained member is listed once
 // under each of its two feeds, in member order, with the right partner, class and side, and nothing else is listed.
-static bool table_sound(int nfeed, const std::vector<int>& off, const std::vector<int>& mem, const std::vector<double>& fw) {
+static bool table_sound(int nfeed, const std::vector<int>& off, const std::vector<int>& mem, const std::vector<double>& fw,
+                        int min_live = 2) {
   const int npairs = (int)off.size() - 1;
-  const dm_redcal_table t = dm_redcal_build(nfeed, npairs, off.data(), mem.data(), fw.empty() ? nullptr : fw.data());
+  const dm_redcal_table t = dm_redcal_build(nfeed, npairs, off.data(), mem.data(), fw.empty() ? nullptr : fw.data(), min_live);
   const int nmem = off.back();
   if ((int)t.yfac.size() != nmem || (int)t.gfac.size() != nmem || (int)t.inc_off.size() != nfeed + 1) return false;
   if (t.inc_off[0] != 0 || t.inc_off[nfeed] != (int)t.inc.size()) return false;
@@ -38,9 +40,9 @@ static bool table_sound(int nfeed, const std::vector<int>& off, const std::vecto
       if (t.yfac[k] != want) return false;
       live += want > 0.0;
     }
-    constrained += live >= 2;
+    constrained += live >= min_live;
     for (int k = off[c]; k < off[c + 1]; ++k)
-      if (t.gfac[k] != (live >= 2 ? t.yfac[k] : 0.0)) return false;
+      if (t.gfac[k] != (live >= min_live ? t.yfac[k] : 0.0)) return false;
   }
   if (constrained != t.nconstrained) return false;
   std::vector<int> seen((size_t)nmem, 0);
@@ -92,6 +94,7 @@ int main() {
     if (trial % 2)
       for (int a = 0; a < nfeed; ++a) fw.push_back(rng() % 5 ? 0.5 + (rng() % 100) / 100.0 : 0.0);
     check("random table", table_sound(nfeed, off, mem, fw));
+    check("random table, every class of a live member counts", table_sound(nfeed, off, mem, fw, 1));
   }
   {  // a table that needs several chunks: 600 feeds, 40000 members
     const int nfeed = 600;
@@ -101,6 +104,18 @@ int main() {
     check("40000 members of 600 feeds", table_sound(nfeed, off, mem, {}));
     const dm_redcal_table t = dm_redcal_build(nfeed, 400, off.data(), mem.data(), nullptr);
     check("  ... split into more than one chunk for one cell", dm_redcal_chunks(nfeed, t.inc_off.data(), 1).size() > 2);
+  }
+  {  // without the "fewer than two" rule (dm_modelcal_solve): the long baseline of the 3-feed line and a single cross pair count
+    const dm_redcal_table t = dm_redcal_build(3, 3, off3.data(), mem3.data(), nullptr, 1);
+    check("3-feed line, min_live 1: two classes, 6 incidences", t.nconstrained == 2 && t.inc.size() == 6 && t.gfac[5] == 1.0 &&
+                                                                    t.gfac[0] == 0.0);
+    check("two feeds, min_live 1", table_sound(2, {0, 2, 3, 4}, {0, 0, 1, 1, 1, 0, 0, 1}, {}, 1));
+    check("intervals", dm_modelcal_nint(150, 64) == 3 && dm_modelcal_nint(17, 4) == 5 && dm_modelcal_nint(5, 1) == 5 &&
+                           dm_modelcal_nint(3, 100) == 1 && dm_modelcal_nint(0, 4) == 0);
+    check("modelcal: sound arguments", dm_modelcal_args_check(4092, 1, 0.5, 1e-10, 500).empty());
+    check("modelcal: interval 0", dm_modelcal_args_check(12, 0, 0.5, 1e-10, 500).find("interval") != std::string::npos);
+    check("modelcal: 4093 feeds", dm_modelcal_args_check(4093, 16, 0.5, 1e-10, 500).find("does not fit") != std::string::npos);
+    check("modelcal: damping 0", dm_modelcal_args_check(12, 16, 0.0, 1e-10, 500).find("damping") != std::string::npos);
   }
   const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
   check("sound arguments", dm_redcal_args_check(0.4, 1e-10, 500).empty() && dm_redcal_args_check(1.0, 0.0, 1).empty());
