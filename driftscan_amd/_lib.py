@@ -854,27 +854,84 @@ def _is_c128(t, shape=None):
             and (shape is None or tuple(t.shape) == tuple(shape)))
 
 
-def _rstride(t):
-    """Element stride between the realisations of a (nreal, nf, npairs, ntime) c128 tensor that is contiguous apart from
-    it (a frequency slice of a contiguous array), or None."""
-    if not (hasattr(t, "data_ptr") and t.is_complex() and t.element_size() == 16 and t.dim() == 4):
+def _rstride_of(t, complex_):
+    """Element stride between the realisations of a (nreal, nf, rows, ntime) tensor of complex128 (complex_) or float64
+    elements that is contiguous apart from it (a frequency slice of a contiguous array), or None."""
+    if not (hasattr(t, "data_ptr") and t.dim() == 4 and t.is_complex() == complex_
+            and t.element_size() == (16 if complex_ else 8)):
         return None
-    nreal, nf, npairs, ntime = (int(v) for v in t.shape)
-    if t.numel() and tuple(t.stride())[1:] != (npairs * ntime, ntime, 1) and not t[0].is_contiguous():
+    nreal, nf, rows, ntime = (int(v) for v in t.shape)
+    if t.numel() and tuple(t.stride())[1:] != (rows * ntime, ntime, 1) and not t[0].is_contiguous():
         return None
-    rs = int(t.stride(0)) if nreal > 1 else nf * npairs * ntime
-    return rs if rs >= nf * npairs * ntime else None
+    rs = int(t.stride(0)) if nreal > 1 else nf * rows * ntime
+    return rs if rs >= nf * rows * ntime else None
 
 
 def _rows_overlap(a, b):
-    """Whether two tensors that `_rstride` accepts, of one shape and (beyond one realisation) one stride, share an
+    """Whether two tensors that `_rstride_of` accepts, of one shape and (beyond one realisation) one stride, share an
     element: some row of `b` begins less than a row's length from some row of `a`."""
     nreal, row = int(a.shape[0]), 16 * int(a[0].numel())
     if row == 0 or nreal == 0:
         return False
-    rs, d = 16 * _rstride(a), b.data_ptr() - a.data_ptr()
+    rs, d = 16 * _rstride_of(a, True), b.data_ptr() - a.data_ptr()
     near = -d // rs                                         # d + k rs is smallest in size at k = near or near + 1
     return any(abs(d + min(max(k, 1 - nreal), nreal - 1) * rs) < row for k in (near, near + 1))
+
+
+def _class_table(who, class_off, members):
+    off, offp = _iarr(class_off)
+    mem, memp = _iarr(np.asarray(members, dtype=np.int32).reshape(-1, 2))
+    if off.ndim != 1 or off.shape[0] < 1 or mem.shape[0] != int(off[-1]):
+        raise ValueError("%s: class_off (npairs + 1) and members (class_off[-1], 2) expected" % who)
+    return off, offp, mem, memp
+
+
+def _weights_arg(who, w, shape, nreal=None):
+    """The float64 weights of the feed-pair chain: of exactly `shape` (x's), or with `nreal` (1 or nreal, *shape); returns
+    the number of realisations they hold."""
+    ok = hasattr(w, "data_ptr") and not w.is_complex() and w.element_size() == 8 and w.is_contiguous()
+    if nreal is None:
+        if not (ok and w.dtype.is_floating_point and tuple(w.shape) == tuple(shape)):
+            raise ValueError("%s: w must be a contiguous float64 tensor of x's shape" % who)
+        return None
+    if not (ok and w.dim() == 4 and tuple(w.shape)[1:] == tuple(shape) and int(w.shape[0]) in (1, nreal)):
+        raise ValueError("%s: w must be a contiguous float64 tensor (1 or nreal, nf, nmem, ntime)" % who)
+    return int(w.shape[0])
+
+
+def _gains_arg(who, g, nreal, nf, ntime):
+    """The calibration gains (1 or nreal, nf, nfeed, ntime); returns (g_nreal, nfeed)."""
+    if not (_is_c128(g) and g.dim() == 4 and int(g.shape[1]) == nf and int(g.shape[3]) == ntime
+            and int(g.shape[0]) in (1, nreal)):
+        raise ValueError("%s: g must be a contiguous complex128 tensor (1 or nreal, nf, nfeed, ntime)" % who)
+    return int(g.shape[0]), int(g.shape[2])
+
+
+def _feed_weight_arg(who, feed_weight, nfeed, exact=False):
+    """feed_weight with one entry per feed, at least `nfeed` of them (exactly, with `exact`); returns (the array, which
+    the caller keeps until the call is over, its pointer, nfeed) — (None, None, nfeed) without feed_weight."""
+    if feed_weight is None:
+        return None, None, nfeed
+    fw = np.ascontiguousarray(feed_weight, dtype=np.float64)
+    if fw.ndim != 1 or (exact and fw.shape[0] != nfeed) or fw.shape[0] < nfeed:
+        raise ValueError("%s: feed_weight must have one entry per feed" % who)
+    return fw, fw.ctypes.data_as(ctypes.POINTER(c_dbl)), int(fw.shape[0])
+
+
+def _out_arg(ctx, who, out, shapes):
+    """`out` of the solvers, a dict of preallocated tensors under names of `shapes` (name -> (shape, dtype)), filled with
+    new tensors where a name is missing."""
+    out = dict(out or {})
+    if set(out) - set(shapes):
+        raise ValueError("%s: out holds %s" % (who, sorted(set(out) - set(shapes))))
+    for name, (shape, dt) in shapes.items():
+        if out.get(name) is None:
+            out[name] = ctx.empty(shape, dt)
+        t = out[name]
+        if not (hasattr(t, "data_ptr") and tuple(t.shape) == shape and t.is_contiguous()
+                and t.dtype == ctx.empty((0,), dt).dtype):
+            raise ValueError("%s: out[%r] must be a contiguous %s tensor of shape %s" % (who, name, np.dtype(dt), shape))
+    return out
 
 
 def _ts_gain_coeff(self, nreal, fglobal, nfeed, ck, sigma, seed, first=0, stream=25, broadband=False, out=None):
@@ -924,27 +981,26 @@ def _ts_gain_apply(self, g, class_off, members, sky, out=None, accumulate=False)
     the noise `ts_noise` drew there, so the gains multiply the sky part only and the noise keeps its level — the convention
     of this package.  An empty class, a feed index outside g or more feeds than one time sample of LDS holds are refused before
     anything is launched."""
-    if not (_is_c128(g) and g.dim() == 4) or _rstride(sky) is None:
+    if not (_is_c128(g) and g.dim() == 4) or _rstride_of(sky, True) is None:
         raise ValueError("ts_gain_apply: complex128 tensors g (g_nreal, nf, nfeed, ntime) and sky "
                          "(nreal, nf, npairs, ntime) expected")
     g_nreal, nf, nfeed, ntime = (int(v) for v in g.shape)
     nreal, _, npairs, _ = (int(v) for v in sky.shape)
-    off, offp = _iarr(class_off)
-    mem, memp = _iarr(np.asarray(members, dtype=np.int32).reshape(-1, 2))
     if tuple(sky.shape) != (nreal, nf, npairs, ntime) or g_nreal not in (1, nreal):
         raise ValueError("ts_gain_apply: g %s does not fit sky %s" % (tuple(g.shape), tuple(sky.shape)))
-    if off.shape != (npairs + 1,) or mem.shape[0] != int(off[-1]):
+    off, offp, mem, memp = _class_table("ts_gain_apply", class_off, members)
+    if off.shape[0] != npairs + 1:
         raise ValueError("ts_gain_apply: class_off (npairs + 1) and members (class_off[-1], 2) expected")
     if out is None:
         if accumulate:
             raise ValueError("ts_gain_apply: accumulate needs the buffer to add to")
         out = self.empty((nreal, nf, npairs, ntime), np.complex128)
-    if (_rstride(out) is None or tuple(out.shape) != tuple(sky.shape) or (nreal > 1 and _rstride(out) != _rstride(sky))
+    if (_rstride_of(out, True) is None or tuple(out.shape) != tuple(sky.shape) or (nreal > 1 and _rstride_of(out, True) != _rstride_of(sky, True))
             or _rows_overlap(sky, out)):
         raise ValueError("ts_gain_apply: out must be a complex128 tensor of sky's shape and strides that shares no "
                          "element with sky")
     rc = self.lib.dm_ts_gain_apply(self.h, nreal, g_nreal, nf, nfeed, npairs, ntime, offp, memp, self.ptr(g), self.ptr(sky),
-                                   self.ptr(out), _rstride(sky), int(bool(accumulate)))
+                                   self.ptr(out), _rstride_of(sky, True), int(bool(accumulate)))
     self.check(rc, "dm_ts_gain_apply")
     return out
 
@@ -952,26 +1008,6 @@ def _ts_gain_apply(self, g, class_off, members, sky, out=None, accumulate=False)
 Context.ts_gain_coeff = _ts_gain_coeff
 Context.ts_gain_compose = _ts_gain_compose
 Context.ts_gain_apply = _ts_gain_apply
-
-
-def _rstride_of(t, complex_):
-    """`_rstride` for a (nreal, nf, rows, ntime) tensor of complex128 (complex_) or float64 elements."""
-    if not (hasattr(t, "data_ptr") and t.dim() == 4 and t.is_complex() == complex_
-            and t.element_size() == (16 if complex_ else 8)):
-        return None
-    nreal, nf, rows, ntime = (int(v) for v in t.shape)
-    if t.numel() and tuple(t.stride())[1:] != (rows * ntime, ntime, 1) and not t[0].is_contiguous():
-        return None
-    rs = int(t.stride(0)) if nreal > 1 else nf * rows * ntime
-    return rs if rs >= nf * rows * ntime else None
-
-
-def _class_table(who, class_off, members):
-    off, offp = _iarr(class_off)
-    mem, memp = _iarr(np.asarray(members, dtype=np.int32).reshape(-1, 2))
-    if off.ndim != 1 or off.shape[0] < 1 or mem.shape[0] != int(off[-1]):
-        raise ValueError("%s: class_off (npairs + 1) and members (class_off[-1], 2) expected" % who)
-    return off, offp, mem, memp
 
 
 def _vis_stack(self, vis, class_off, members, w=None, g=None, feed_weight=None, out=None, wout=None):
@@ -998,22 +1034,10 @@ def _vis_stack(self, vis, class_off, members, w=None, g=None, feed_weight=None, 
     w_nreal = g_nreal = 1
     nfeed = int(mem.max()) + 1 if mem.size else 0
     if w is not None:
-        if not (hasattr(w, "data_ptr") and w.dim() == 4 and not w.is_complex() and w.element_size() == 8
-                and w.is_contiguous() and tuple(w.shape)[1:] == (nf, nmem, ntime) and int(w.shape[0]) in (1, nreal)):
-            raise ValueError("vis_stack: w must be a contiguous float64 tensor (1 or nreal, nf, nmem, ntime)")
-        w_nreal = int(w.shape[0])
+        w_nreal = _weights_arg("vis_stack", w, (nf, nmem, ntime), nreal)
     if g is not None:
-        if not (_is_c128(g) and g.dim() == 4 and int(g.shape[1]) == nf and int(g.shape[3]) == ntime
-                and int(g.shape[0]) in (1, nreal)):
-            raise ValueError("vis_stack: g must be a contiguous complex128 tensor (1 or nreal, nf, nfeed, ntime)")
-        g_nreal, nfeed = int(g.shape[0]), int(g.shape[2])
-    fwp = None
-    if feed_weight is not None:
-        fw = np.ascontiguousarray(feed_weight, dtype=np.float64)
-        if fw.ndim != 1 or (g is not None and fw.shape[0] != nfeed) or fw.shape[0] < nfeed:
-            raise ValueError("vis_stack: feed_weight must have one entry per feed")
-        nfeed = int(fw.shape[0])
-        fwp = fw.ctypes.data_as(ctypes.POINTER(c_dbl))
+        g_nreal, nfeed = _gains_arg("vis_stack", g, nreal, nf, ntime)
+    fw, fwp, nfeed = _feed_weight_arg("vis_stack", feed_weight, nfeed, exact=g is not None)
     if out is None:
         out = self.empty((nreal, nf, npairs, ntime), np.complex128)
     if wout is None:
@@ -1047,10 +1071,7 @@ def _vis_expand(self, sky, class_off, members, g=None, out=None, accumulate=Fals
     nmem = mem.shape[0]
     g_nreal, nfeed = 1, (int(mem.max()) + 1 if mem.size else 0)
     if g is not None:
-        if not (_is_c128(g) and g.dim() == 4 and int(g.shape[1]) == nf and int(g.shape[3]) == ntime
-                and int(g.shape[0]) in (1, nreal)):
-            raise ValueError("vis_expand: g must be a contiguous complex128 tensor (1 or nreal, nf, nfeed, ntime)")
-        g_nreal, nfeed = int(g.shape[0]), int(g.shape[2])
+        g_nreal, nfeed = _gains_arg("vis_expand", g, nreal, nf, ntime)
     if out is None:
         if accumulate:
             raise ValueError("vis_expand: accumulate needs the buffer to add to")
@@ -1083,9 +1104,8 @@ def _sidereal_regrid(self, x, phi0, dphi, ntime, w=None, a=3, min_share=1.0, acc
         raise ValueError("sidereal_regrid: contiguous complex128 tensor x (nf, nrow, nt_in) expected")
     nf, nrow, nt_in = (int(v) for v in x.shape)
     ntime = int(ntime)
-    if w is not None and not (hasattr(w, "data_ptr") and not w.is_complex() and w.element_size() == 8 and w.is_contiguous()
-                              and w.dtype.is_floating_point and tuple(w.shape) == tuple(x.shape)):
-        raise ValueError("sidereal_regrid: w must be a contiguous float64 tensor of x's shape")
+    if w is not None:
+        _weights_arg("sidereal_regrid", w, x.shape)
     shape = (nf, nrow, max(ntime, 0))
     if acc is None:
         accumulate = 0
@@ -1133,9 +1153,8 @@ def _rfi_flag(self, x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4,
     if not (_is_c128(x) and x.dim() == 3):
         raise ValueError("rfi_flag: contiguous complex128 tensor x (nf, nrow, nt) expected")
     nf, nrow, nt = (int(v) for v in x.shape)
-    if w is not None and not (hasattr(w, "data_ptr") and not w.is_complex() and w.element_size() == 8 and w.is_contiguous()
-                              and w.dtype.is_floating_point and tuple(w.shape) == tuple(x.shape)):
-        raise ValueError("rfi_flag: w must be a contiguous float64 tensor of x's shape")
+    if w is not None:
+        _weights_arg("rfi_flag", w, x.shape)
     segment = int(segment)
     if segment < 1:
         raise ValueError("rfi_flag: segment < 1")
@@ -1184,35 +1203,17 @@ def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=No
     nfeed = int(mem.max()) + 1 if mem.size else 0
     w_nreal = 1
     if w is not None:
-        if not (hasattr(w, "data_ptr") and w.dim() == 4 and not w.is_complex() and w.element_size() == 8
-                and w.is_contiguous() and tuple(w.shape)[1:] == (nf, nmem, ntime) and int(w.shape[0]) in (1, nreal)):
-            raise ValueError("redcal_solve: w must be a contiguous float64 tensor (1 or nreal, nf, nmem, ntime)")
-        w_nreal = int(w.shape[0])
-    fwp = None
-    if feed_weight is not None:
-        fw = np.ascontiguousarray(feed_weight, dtype=np.float64)
-        if fw.ndim != 1 or fw.shape[0] < nfeed:
-            raise ValueError("redcal_solve: feed_weight must have one entry per feed")
-        nfeed = int(fw.shape[0])
-        fwp = fw.ctypes.data_as(ctypes.POINTER(c_dbl))
+        w_nreal = _weights_arg("redcal_solve", w, (nf, nmem, ntime), nreal)
+    fw, fwp, nfeed = _feed_weight_arg("redcal_solve", feed_weight, nfeed)
     if g0 is not None:
         if not (_is_c128(g0) and g0.dim() == 4 and (int(g0.shape[0]), int(g0.shape[1]), int(g0.shape[3])) == (nreal, nf, ntime)
                 and int(g0.shape[2]) >= nfeed and (feed_weight is None or int(g0.shape[2]) == nfeed)):
             raise ValueError("redcal_solve: g0 must be a contiguous complex128 tensor (nreal, nf, nfeed, ntime)")
         nfeed = int(g0.shape[2])
-    out = dict(out or {})
     shapes = dict(g=((nreal, nf, nfeed, ntime), np.complex128), y=((nreal, nf, npairs, ntime), np.complex128),
                   iters=((nreal, nf, ntime), np.int32), step=((nreal, nf, ntime), np.float64),
                   chi2=((nreal, nf, ntime), np.float64))
-    if set(out) - set(shapes):
-        raise ValueError("redcal_solve: out holds %s" % sorted(set(out) - set(shapes)))
-    for name, (shape, dt) in shapes.items():
-        if out.get(name) is None:
-            out[name] = self.empty(shape, dt)
-        t = out[name]
-        if not (hasattr(t, "data_ptr") and tuple(t.shape) == shape and t.is_contiguous()
-                and t.dtype == self.empty((0,), dt).dtype):
-            raise ValueError("redcal_solve: out[%r] must be a contiguous %s tensor of shape %s" % (name, np.dtype(dt), shape))
+    out = _out_arg(self, "redcal_solve", out, shapes)
     rc = self.lib.dm_redcal_solve(self.h, nreal, w_nreal, nf, nfeed, npairs, ntime, offp, memp, self.ptr(vis), self.ptr(w),
                                   fwp, self.ptr(g0), float(damping), float(tol), int(maxiter), self.ptr(out["g"]),
                                   self.ptr(out["y"]), self.ptr(out["iters"]), self.ptr(out["step"]), self.ptr(out["chi2"]), rs)
@@ -1254,17 +1255,8 @@ def _modelcal_solve(self, vis, model, class_off, members, interval, w=None, feed
     nfeed = int(mem.max()) + 1 if mem.size else 0
     w_nreal = 1
     if w is not None:
-        if not (hasattr(w, "data_ptr") and w.dim() == 4 and not w.is_complex() and w.element_size() == 8
-                and w.is_contiguous() and tuple(w.shape)[1:] == (nf, nmem, ntime) and int(w.shape[0]) in (1, nreal)):
-            raise ValueError("modelcal_solve: w must be a contiguous float64 tensor (1 or nreal, nf, nmem, ntime)")
-        w_nreal = int(w.shape[0])
-    fwp = None
-    if feed_weight is not None:
-        fw = np.ascontiguousarray(feed_weight, dtype=np.float64)
-        if fw.ndim != 1 or fw.shape[0] < nfeed:
-            raise ValueError("modelcal_solve: feed_weight must have one entry per feed")
-        nfeed = int(fw.shape[0])
-        fwp = fw.ctypes.data_as(ctypes.POINTER(c_dbl))
+        w_nreal = _weights_arg("modelcal_solve", w, (nf, nmem, ntime), nreal)
+    fw, fwp, nfeed = _feed_weight_arg("modelcal_solve", feed_weight, nfeed)
     if g0 is not None:
         if not (_is_c128(g0) and g0.dim() == 4 and (int(g0.shape[0]), int(g0.shape[1]), int(g0.shape[3])) == (nreal, nf, nint)
                 and int(g0.shape[2]) >= nfeed and (feed_weight is None or int(g0.shape[2]) == nfeed)):
@@ -1273,19 +1265,10 @@ def _modelcal_solve(self, vis, model, class_off, members, interval, w=None, feed
     if active is not None and not (hasattr(active, "data_ptr") and active.dtype == self.torch.int32 and active.is_contiguous()
                                    and tuple(active.shape) == (nf, nint)):
         raise ValueError("modelcal_solve: active must be a contiguous int32 tensor (nf, nint)")
-    out = dict(out or {})
     shapes = dict(g=((nreal, nf, nfeed, nint), np.complex128), iters=((nreal, nf, nint), np.int32),
                   step=((nreal, nf, nint), np.float64), chi2=((nreal, nf, nint), np.float64),
                   gweight=((nreal, nf, nfeed, nint), np.float64))
-    if set(out) - set(shapes):
-        raise ValueError("modelcal_solve: out holds %s" % sorted(set(out) - set(shapes)))
-    for name, (shape, dt) in shapes.items():
-        if out.get(name) is None:
-            out[name] = self.empty(shape, dt)
-        t = out[name]
-        if not (hasattr(t, "data_ptr") and tuple(t.shape) == shape and t.is_contiguous()
-                and t.dtype == self.empty((0,), dt).dtype):
-            raise ValueError("modelcal_solve: out[%r] must be a contiguous %s tensor of shape %s" % (name, np.dtype(dt), shape))
+    out = _out_arg(self, "modelcal_solve", out, shapes)
     rc = self.lib.dm_modelcal_solve(self.h, nreal, w_nreal, m_nreal, nf, nfeed, npairs, ntime, interval, offp, memp,
                                     self.ptr(vis), self.ptr(model), self.ptr(w), fwp, self.ptr(g0), self.ptr(active),
                                     float(damping), float(tol), int(maxiter), self.ptr(out["g"]), self.ptr(out["iters"]),

@@ -22,6 +22,7 @@
 // The design is for intervals of 16 samples and more (a transit lasts many samples).  Shorter ones are correct but slow:
 // at L = 1 neighbouring lanes read vis, w and the model ntime elements apart, one 16-byte element per 128-byte line.
 #include "dm_common.h"
+#include "dm_feedpair.h"
 #include "dm_modelcal_table.h"
 #include "../../include/driftmi.h"
 
@@ -30,7 +31,6 @@
 namespace {
 
 constexpr int MC_NW = 8;       // waves per workgroup, as the gain step of section 4.18
-constexpr int MC_CHECK = 16;   // every so many iterations the host asks (without waiting) whether any interval is left
 
 // The state of an interval entering iteration `iter`, from its state and its step after iteration iter - 1.  Before the
 // first iteration the words hold 0 (to solve) or 2 (not asked for).  `last`: the closing pass.
@@ -252,10 +252,7 @@ __global__ __launch_bounds__(MC_NW * 64) void modelcal_close_kernel(
   }
 }
 
-int modelcal_refuse(dm_ctx* ctx, const std::string& what) {
-  ctx->err = "dm_modelcal_solve: " + what;
-  return DM_EARG;
-}
+constexpr const char* MC_WHO = "dm_modelcal_solve";
 
 struct modelcal_args {
   const cplx *vis, *model, *g0;
@@ -282,19 +279,14 @@ int modelcal_run(dm_ctx* ctx, const modelcal_args& a) {
   const int64_t cells = (int64_t)a.nreal * nf * nint;
   const std::vector<int> gchunk = dm_redcal_chunks(a.nfeed, tb.inc_off.data(), cells);
   const int64_t ngc = (int64_t)gchunk.size() - 1;
-  if (cells * ngc >= (1LL << 31)) return modelcal_refuse(ctx, "too many workgroups for one launch");
+  if (cells * ngc >= (1LL << 31)) return dm_refuse(ctx, MC_WHO, "too many workgroups for one launch");
   const size_t ncells = (size_t)cells, ng = ncells * nfeed;
   const size_t lds = (size_t)nfeed * sizeof(cplx), lds_close = lds + (size_t)MC_NW * sizeof(double);
   // tables: the factors and incidences without the "fewer than two" rule, the members with their class
   const int* gch = dm_ws_upload(ctx, gchunk);
   const double* fac = dm_ws_upload(ctx, tb.gfac);
   const int* inc_off = dm_ws_upload(ctx, tb.inc_off);
-  std::vector<int> flat(4 * tb.inc.size());
-  for (size_t k = 0; k < tb.inc.size(); ++k) {
-    flat[4 * k] = tb.inc[k].row, flat[4 * k + 1] = tb.inc[k].partner;
-    flat[4 * k + 2] = tb.inc[k].cls, flat[4 * k + 3] = tb.inc[k].side;
-  }
-  const int4* inc = reinterpret_cast<const int4*>(dm_ws_upload(ctx, flat));
+  const int4* inc = reinterpret_cast<const int4*>(dm_ws_upload(ctx, tb.inc));
   std::vector<int> mrow(4 * (size_t)nmem, 0);
   for (uint32_t c = 0; c < npairs; ++c)
     for (int k = a.class_off_host[c]; k < a.class_off_host[c + 1]; ++k)
@@ -303,7 +295,7 @@ int modelcal_run(dm_ctx* ctx, const modelcal_args& a) {
   const int4* mem = reinterpret_cast<const int4*>(dm_ws_upload(ctx, mrow));
   // two gain buffers [cell][feed], three sets of step words, two of state words, the counters of the host's checks
   cplx* gws = dm_ws_alloc_t<cplx>(ctx, 2 * ng + 1);
-  const int nslots = a.maxiter / MC_CHECK + 1;
+  const int nslots = dm_poll_slots(a.maxiter);
   const size_t words = 3 * ncells * sizeof(unsigned long long) + 2 * ncells * sizeof(int) + (size_t)nslots * sizeof(int);
   char* state = reinterpret_cast<char*>(dm_ws_alloc(ctx, words));
   if (!gch || !fac || !inc_off || !inc || !mem || !gws || !state) return DM_ENOMEM;
@@ -318,39 +310,18 @@ int modelcal_run(dm_ctx* ctx, const modelcal_args& a) {
              a.active, G[0], G[1], st[0], (unsigned long long)ng, (unsigned long long)ncells, nfeed, (uint32_t)nint, nf);
   DM_HIP(ctx, hipGetLastError());
   const dim3 grid((unsigned)(cells * ngc)), block(MC_NW * 64);
-  const int* landed = nullptr;   // the host copy of the counter of the check in flight
-  bool all_done = false;
-  int k_last = 0;
-  auto iterate = [&]() -> int {
-    for (int k = 1; k <= a.maxiter && !all_done; ++k) {
-      int* count = nullptr;
-      if (k % MC_CHECK == 0 && !landed) count = pending + k / MC_CHECK;
-      // iteration k reads G, st and sb of k - 1, writes G and st of k, joins the steps into sb of k and clears sb of k + 1
-      DM_PLAUNCH(ctx, DM_PROF_UTIL, (modelcal_g_kernel<HAS_W>), grid, block, lds, ctx->stream, a.vis, a.w, a.model,
-                 (const cplx*)G[(k - 1) & 1], G[k & 1], fac, inc_off, inc, gch, (const int*)st[(k - 1) & 1], st[k & 1],
-                 (const unsigned long long*)sb[(k - 1) % 3], sb[k % 3], sb[(k + 1) % 3], a.iters, a.step, count, nfeed, npairs,
-                 nmem, ntime, (uint32_t)nint, (uint32_t)a.interval, (uint32_t)ngc, nf, a.w_each, a.m_each, a.vstride,
-                 a.damping, a.tol, k);
-      DM_HIP(ctx, hipGetLastError());
-      k_last = k;
-      if (count) {
-        const void* host = nullptr;
-        DM_TRY(dm_download_queue(ctx, count, sizeof(int), &host));
-        landed = static_cast<const int*>(host);
-      } else if (landed && ctx->dl_ev && hipEventQuery(ctx->dl_ev) == hipSuccess) {   // asked, never waited for
-        all_done = *landed == 0;
-        DM_TRY(dm_download_wait(ctx));
-        landed = nullptr;
-      }
-    }
+  // iteration k reads G, st and sb of k - 1, writes G and st of k, joins the steps into sb of k and clears sb of k + 1
+  const dm_poll_result run = dm_poll_iterate(ctx, a.maxiter, pending, [&](int k, int* count) -> int {
+    DM_PLAUNCH(ctx, DM_PROF_UTIL, (modelcal_g_kernel<HAS_W>), grid, block, lds, ctx->stream, a.vis, a.w, a.model,
+               (const cplx*)G[(k - 1) & 1], G[k & 1], fac, inc_off, inc, gch, (const int*)st[(k - 1) & 1], st[k & 1],
+               (const unsigned long long*)sb[(k - 1) % 3], sb[k % 3], sb[(k + 1) % 3], a.iters, a.step, count, nfeed, npairs,
+               nmem, ntime, (uint32_t)nint, (uint32_t)a.interval, (uint32_t)ngc, nf, a.w_each, a.m_each, a.vstride,
+               a.damping, a.tol, k);
+    DM_HIP(ctx, hipGetLastError());
     return DM_OK;
-  };
-  const int rc = iterate();
-  if (rc != DM_OK) {
-    dm_download_abandon(ctx);
-    return rc;
-  }
-  if (landed) DM_TRY(dm_download_wait(ctx));
+  });
+  DM_TRY(run.rc);
+  const int k_last = run.k_last;
   // both gain buffers hold the gains of every finished interval; the one iteration k_last wrote also holds the rest
   DM_PLAUNCH(ctx, DM_PROF_UTIL, (modelcal_close_kernel<HAS_W>), grid, block, lds_close, ctx->stream, a.vis, a.w, a.model,
              (const cplx*)G[k_last & 1], fac, inc_off, inc, gch, mem, (const int*)st[k_last & 1],
@@ -369,46 +340,33 @@ extern "C" int dm_modelcal_solve(dm_ctx* ctx, int nreal, int w_nreal, int m_nrea
                                  void* g_dev, int* iters_dev, double* step_dev, double* chi2_dev, double* gweight_dev,
                                  int64_t vis_rstride) {
   if (!ctx) return DM_EARG;
-  if (nreal < 0 || nf < 0 || nfeed < 0 || npairs < 0 || ntime < 0 || vis_rstride < 0)
-    return modelcal_refuse(ctx, "negative size");
   const bool has_w = w_dev != nullptr;
-  if (has_w && w_nreal != 1 && w_nreal != nreal) return modelcal_refuse(ctx, "w_nreal must be 1 or nreal");
-  if (m_nreal != 1 && m_nreal != nreal) return modelcal_refuse(ctx, "m_nreal must be 1 or nreal");
-  const std::string bad = dm_stack_table_check(nfeed, npairs, class_off_host, members_host, true);
-  if (!bad.empty()) return modelcal_refuse(ctx, bad);
-  if (feed_weight_host)
-    for (int a = 0; a < nfeed; ++a)
-      if (!(feed_weight_host[a] >= 0.0)) return modelcal_refuse(ctx, "feed weight " + std::to_string(a) + " is negative");
+  const std::string bad = dm_pair_args_check(nreal, nf, nfeed, npairs, ntime, vis_rstride, has_w ? &w_nreal : nullptr, &m_nreal,
+                                             class_off_host, members_host, true, feed_weight_host);
+  if (!bad.empty()) return dm_refuse(ctx, MC_WHO, bad);
   const std::string worse = dm_modelcal_args_check(nfeed, interval, damping, tol, maxiter);
-  if (!worse.empty()) return modelcal_refuse(ctx, worse);
+  if (!worse.empty()) return dm_refuse(ctx, MC_WHO, worse);
   const int64_t nmem = npairs > 0 ? class_off_host[npairs] : 0;
   const uint64_t vrow = (uint64_t)nf * nmem * ntime;
   if (vis_rstride == 0) vis_rstride = (int64_t)vrow;
-  if ((uint64_t)vis_rstride < vrow) return modelcal_refuse(ctx, "vis_rstride is shorter than a realisation");
+  if ((uint64_t)vis_rstride < vrow) return dm_refuse(ctx, MC_WHO, "vis_rstride is shorter than a realisation");
   if (nreal == 0 || nf == 0 || ntime == 0) return DM_OK;
   const uint64_t nint = (uint64_t)dm_modelcal_nint(ntime, interval);
-  if (nint * (uint64_t)nreal * nf >= (1ull << 31)) return modelcal_refuse(ctx, "too many intervals for one call");
+  if (nint * (uint64_t)nreal * nf >= (1ull << 31)) return dm_refuse(ctx, MC_WHO, "too many intervals for one call");
   const uint64_t ncell = (uint64_t)nreal * nf * nint;
   if ((nmem > 0 && (!vis_dev || !model_dev)) || (nfeed > 0 && (!g_dev || !gweight_dev)) || !iters_dev || !step_dev ||
       !chi2_dev)
-    return modelcal_refuse(ctx, "null pointer with work to do");
+    return dm_refuse(ctx, MC_WHO, "null pointer with work to do");
   // outputs against the inputs and against each other, on whole spans
-  struct span { const void* p; uint64_t bytes; const char* name; };
-  const span in[5] = {{vis_dev, 16 * ((uint64_t)(nreal - 1) * vis_rstride + vrow), "vis"},
+  const dm_span in[5] = {{vis_dev, 16 * ((uint64_t)(nreal - 1) * vis_rstride + vrow), "vis"},
                       {model_dev, 16 * (uint64_t)m_nreal * nf * npairs * ntime, "model"},
                       {w_dev, 8 * (uint64_t)(has_w ? w_nreal : 0) * vrow, "w"},
                       {g0_dev, g0_dev ? 16 * ncell * nfeed : 0, "g0"},
                       {active_dev, active_dev ? 4 * (uint64_t)nf * nint : 0, "active"}};
-  const span out[5] = {{g_dev, 16 * ncell * nfeed, "g"}, {iters_dev, 4 * ncell, "iters"}, {step_dev, 8 * ncell, "step"},
+  const dm_span out[5] = {{g_dev, 16 * ncell * nfeed, "g"}, {iters_dev, 4 * ncell, "iters"}, {step_dev, 8 * ncell, "step"},
                        {chi2_dev, 8 * ncell, "chi2"}, {gweight_dev, 8 * ncell * nfeed, "gweight"}};
-  for (int o = 0; o < 5; ++o) {
-    for (int i = 0; i < 5; ++i)
-      if (dm_spans_overlap((uint64_t)out[o].p, out[o].bytes, 0, (uint64_t)in[i].p, in[i].bytes, 0, 1))
-        return modelcal_refuse(ctx, std::string(out[o].name) + " shares an element with " + in[i].name);
-    for (int p = 0; p < o; ++p)
-      if (dm_spans_overlap((uint64_t)out[o].p, out[o].bytes, 0, (uint64_t)out[p].p, out[p].bytes, 0, 1))
-        return modelcal_refuse(ctx, std::string(out[o].name) + " shares an element with " + out[p].name);
-  }
+  const std::string shared = dm_spans_shared(in, 5, out, 5);
+  if (!shared.empty()) return dm_refuse(ctx, MC_WHO, shared);
   DM_HIP(ctx, hipSetDevice(ctx->device));
   dm_ws_scope ws(ctx);
   const dm_redcal_table table = dm_redcal_build(nfeed, npairs, class_off_host, members_host, feed_weight_host, 1);

@@ -16,6 +16,7 @@
 // workgroups by an integer atomicMax on the bit pattern of a non-negative double, which is the same in any order.  There
 // is no floating-point atomic, and every sum lives inside one wave in an order that (d_a, nfeed) or (n_c, nfeed) fix.
 #include "dm_common.h"
+#include "dm_feedpair.h"
 #include "dm_stack_sum.h"
 #include "dm_redcal_table.h"
 #include "../../include/driftmi.h"
@@ -25,7 +26,6 @@
 namespace {
 
 constexpr int RC_NW = stack_waves(true);   // 8 waves per workgroup: the reason measured in section 4.17
-constexpr int RC_CHECK = 16;               // every so many iterations the host asks (without waiting) whether any sample is left
 
 // The state of a sample entering iteration `iter`, from its state and its step after iteration iter - 1.  `last`: the
 // pass behind the last iteration, which only closes the books.
@@ -217,10 +217,7 @@ __global__ __launch_bounds__(RC_NW * 64) void redcal_chi2_kernel(
   }
 }
 
-int redcal_refuse(dm_ctx* ctx, const std::string& what) {
-  ctx->err = "dm_redcal_solve: " + what;
-  return DM_EARG;
-}
+constexpr const char* RC_WHO = "dm_redcal_solve";
 
 struct redcal_args {
   const cplx *vis, *g0;
@@ -237,14 +234,6 @@ struct redcal_args {
   double damping, tol;
 };
 
-template <typename K>
-int redcal_lds_attr(dm_ctx* ctx, K kernel, size_t lds) {
-  if (lds > (size_t)DM_GAIN_LDS_SHARED)
-    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-  return DM_OK;
-}
-
 template <int TT, bool HAS_W>
 int redcal_run(dm_ctx* ctx, const redcal_args& a) {
   const dm_redcal_table& tb = *a.table;
@@ -256,10 +245,10 @@ int redcal_run(dm_ctx* ctx, const redcal_args& a) {
   const std::vector<int> gchunk = dm_redcal_chunks(a.nfeed, tb.inc_off.data(), cells);
   const int64_t nyc = (int64_t)ychunk.size() - 1, ngc = (int64_t)gchunk.size() - 1;
   if (cells * nyc >= (1LL << 31) || cells * ngc >= (1LL << 31) || (int64_t)a.nreal * nf >= (1LL << 31))
-    return redcal_refuse(ctx, "too many workgroups for one launch");
+    return dm_refuse(ctx, RC_WHO, "too many workgroups for one launch");
   const size_t nsamp = (size_t)a.nreal * nf * ntime, ng = nsamp * nfeed;
   const size_t lds = (size_t)nfeed * TT * sizeof(cplx), lds_chi = lds + (size_t)RC_NW * TT * sizeof(double);
-  if (lds_chi > (size_t)DM_GAIN_LDS_BYTES) return redcal_refuse(ctx, "the g tile and the chi^2 sums do not fit in LDS");
+  if (lds_chi > (size_t)DM_GAIN_LDS_BYTES) return dm_refuse(ctx, RC_WHO, "the g tile and the chi^2 sums do not fit in LDS");
   // tables
   const int* off = dm_ws_upload(ctx, std::vector<int>(a.class_off_host, a.class_off_host + npairs + 1));
   const int2* mem = reinterpret_cast<const int2*>(
@@ -269,15 +258,10 @@ int redcal_run(dm_ctx* ctx, const redcal_args& a) {
   const double* yfac = dm_ws_upload(ctx, tb.yfac);
   const double* gfac = dm_ws_upload(ctx, tb.gfac);
   const int* inc_off = dm_ws_upload(ctx, tb.inc_off);
-  std::vector<int> flat(4 * tb.inc.size());
-  for (size_t k = 0; k < tb.inc.size(); ++k) {
-    flat[4 * k] = tb.inc[k].row, flat[4 * k + 1] = tb.inc[k].partner;
-    flat[4 * k + 2] = tb.inc[k].cls, flat[4 * k + 3] = tb.inc[k].side;
-  }
-  const int4* inc = reinterpret_cast<const int4*>(dm_ws_upload(ctx, flat));
+  const int4* inc = reinterpret_cast<const int4*>(dm_ws_upload(ctx, tb.inc));
   // the second gain buffer, two sets of state and step words, the counters of the host's checks
   cplx* gws = dm_ws_alloc_t<cplx>(ctx, ng ? ng : 1);
-  const int nslots = a.maxiter / RC_CHECK + 1;
+  const int nslots = dm_poll_slots(a.maxiter);
   const size_t words = 2 * nsamp * sizeof(unsigned long long) + 2 * nsamp * sizeof(int) + (size_t)nslots * sizeof(int);
   char* state = reinterpret_cast<char*>(dm_ws_alloc(ctx, words));
   if (!off || !mem || !ych || !gch || !yfac || !gfac || !inc_off || !inc || !gws || !state) return DM_ENOMEM;
@@ -290,9 +274,9 @@ int redcal_run(dm_ctx* ctx, const redcal_args& a) {
   cplx* G[2];
   G[a.maxiter & 1] = a.g;
   G[(a.maxiter & 1) ^ 1] = gws;
-  DM_TRY(redcal_lds_attr(ctx, &redcal_y_kernel<TT, HAS_W>, lds));
-  DM_TRY(redcal_lds_attr(ctx, &redcal_g_kernel<TT, HAS_W>, lds));
-  DM_TRY(redcal_lds_attr(ctx, &redcal_chi2_kernel<TT, HAS_W>, lds_chi));
+  DM_TRY(dm_lds_attr(ctx, &redcal_y_kernel<TT, HAS_W>, lds));
+  DM_TRY(dm_lds_attr(ctx, &redcal_g_kernel<TT, HAS_W>, lds));
+  DM_TRY(dm_lds_attr(ctx, &redcal_chi2_kernel<TT, HAS_W>, lds_chi));
   if (ng) {
     DM_PLAUNCH(ctx, DM_PROF_UTIL, redcal_init_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, ctx->stream, a.g0,
                G[0], (unsigned long long)ng);
@@ -307,37 +291,17 @@ int redcal_run(dm_ctx* ctx, const redcal_args& a) {
     DM_HIP(ctx, hipGetLastError());
     return DM_OK;
   };
-  const int* landed = nullptr;   // the host copy of the counter of the check in flight
-  bool all_done = false;
-  auto iterate = [&]() -> int {
-    for (int k = 1; k <= a.maxiter && !all_done; ++k) {
-      int* count = nullptr;
-      if (k % RC_CHECK == 0 && !landed) count = pending + k / RC_CHECK;
-      DM_TRY(y_pass(k, 0, count));
-      DM_PLAUNCH(ctx, DM_PROF_UTIL, (redcal_g_kernel<TT, HAS_W>), ggrid, block, lds, ctx->stream, a.vis, a.w,
-                 (const cplx*)G[(k - 1) & 1], G[k & 1], gfac, (const cplx*)a.y, inc_off, inc, gch, (const int*)st[k & 1],
-                 sb[k & 1], nfeed, npairs, nmem, ntime, (uint32_t)ntiles, (uint32_t)ngc, nf, a.w_each, a.vstride, a.damping);
-      DM_HIP(ctx, hipGetLastError());
-      if (count) {
-        const void* host = nullptr;
-        DM_TRY(dm_download_queue(ctx, count, sizeof(int), &host));
-        landed = static_cast<const int*>(host);
-      } else if (landed && ctx->dl_ev && hipEventQuery(ctx->dl_ev) == hipSuccess) {   // asked, never waited for
-        all_done = *landed == 0;
-        DM_TRY(dm_download_wait(ctx));
-        landed = nullptr;
-      }
-    }
+  const dm_poll_result run = dm_poll_iterate(ctx, a.maxiter, pending, [&](int k, int* count) -> int {
+    DM_TRY(y_pass(k, 0, count));
+    DM_PLAUNCH(ctx, DM_PROF_UTIL, (redcal_g_kernel<TT, HAS_W>), ggrid, block, lds, ctx->stream, a.vis, a.w,
+               (const cplx*)G[(k - 1) & 1], G[k & 1], gfac, (const cplx*)a.y, inc_off, inc, gch, (const int*)st[k & 1],
+               sb[k & 1], nfeed, npairs, nmem, ntime, (uint32_t)ntiles, (uint32_t)ngc, nf, a.w_each, a.vstride, a.damping);
+    DM_HIP(ctx, hipGetLastError());
     return DM_OK;
-  };
-  const int rc = iterate();
-  if (rc != DM_OK) {
-    dm_download_abandon(ctx);
-    return rc;
-  }
-  if (landed) DM_TRY(dm_download_wait(ctx));
+  });
+  DM_TRY(run.rc);
   // every sample was done (state 2) when the host stopped early; otherwise close the books of the last iteration
-  if (!all_done) DM_TRY(y_pass(a.maxiter + 1, 1, nullptr));
+  if (!run.all_done) DM_TRY(y_pass(a.maxiter + 1, 1, nullptr));
   DM_PLAUNCH(ctx, DM_PROF_UTIL, (redcal_chi2_kernel<TT, HAS_W>), dim3((unsigned)cells), block, lds_chi, ctx->stream, a.vis,
              a.w, (const cplx*)a.g, gfac, (const cplx*)a.y, off, mem, a.chi2, nfeed, npairs, nmem, ntime, (uint32_t)ntiles, nf,
              a.w_each, a.vstride);
@@ -353,39 +317,28 @@ extern "C" int dm_redcal_solve(dm_ctx* ctx, int nreal, int w_nreal, int nf, int 
                                void* g_dev, void* y_dev, int* iters_dev, double* step_dev, double* chi2_dev,
                                int64_t vis_rstride) {
   if (!ctx) return DM_EARG;
-  if (nreal < 0 || nf < 0 || nfeed < 0 || npairs < 0 || ntime < 0 || vis_rstride < 0) return redcal_refuse(ctx, "negative size");
   const bool has_w = w_dev != nullptr;
-  if (has_w && w_nreal != 1 && w_nreal != nreal) return redcal_refuse(ctx, "w_nreal must be 1 or nreal");
-  const std::string bad = dm_stack_table_check(nfeed, npairs, class_off_host, members_host, true);
-  if (!bad.empty()) return redcal_refuse(ctx, bad);
-  if (feed_weight_host)
-    for (int a = 0; a < nfeed; ++a)
-      if (!(feed_weight_host[a] >= 0.0)) return redcal_refuse(ctx, "feed weight " + std::to_string(a) + " is negative");
+  const std::string bad = dm_pair_args_check(nreal, nf, nfeed, npairs, ntime, vis_rstride, has_w ? &w_nreal : nullptr, nullptr,
+                                             class_off_host, members_host, true, feed_weight_host);
+  if (!bad.empty()) return dm_refuse(ctx, RC_WHO, bad);
   const std::string worse = dm_redcal_args_check(damping, tol, maxiter);
-  if (!worse.empty()) return redcal_refuse(ctx, worse);
+  if (!worse.empty()) return dm_refuse(ctx, RC_WHO, worse);
   const int64_t nmem = npairs > 0 ? class_off_host[npairs] : 0;
   const uint64_t vrow = (uint64_t)nf * nmem * ntime;
   if (vis_rstride == 0) vis_rstride = (int64_t)vrow;
-  if ((uint64_t)vis_rstride < vrow) return redcal_refuse(ctx, "vis_rstride is shorter than a realisation");
+  if ((uint64_t)vis_rstride < vrow) return dm_refuse(ctx, RC_WHO, "vis_rstride is shorter than a realisation");
   if (nreal == 0 || nf == 0 || ntime == 0) return DM_OK;
   const uint64_t nsamp = (uint64_t)nreal * nf * ntime;
   if ((nmem > 0 && !vis_dev) || (nfeed > 0 && !g_dev) || (npairs > 0 && !y_dev) || !iters_dev || !step_dev || !chi2_dev)
-    return redcal_refuse(ctx, "null pointer with work to do");
+    return dm_refuse(ctx, RC_WHO, "null pointer with work to do");
   // outputs against the inputs and against each other, on whole spans
-  struct span { const void* p; uint64_t bytes; const char* name; };
-  const span in[3] = {{vis_dev, 16 * ((uint64_t)(nreal - 1) * vis_rstride + vrow), "vis"},
+  const dm_span in[3] = {{vis_dev, 16 * ((uint64_t)(nreal - 1) * vis_rstride + vrow), "vis"},
                       {w_dev, 8 * (uint64_t)(has_w ? w_nreal : 0) * vrow, "w"},
                       {g0_dev, g0_dev ? 16 * nsamp * nfeed : 0, "g0"}};
-  const span out[5] = {{g_dev, 16 * nsamp * nfeed, "g"}, {y_dev, 16 * nsamp * npairs, "y"}, {iters_dev, 4 * nsamp, "iters"},
+  const dm_span out[5] = {{g_dev, 16 * nsamp * nfeed, "g"}, {y_dev, 16 * nsamp * npairs, "y"}, {iters_dev, 4 * nsamp, "iters"},
                        {step_dev, 8 * nsamp, "step"}, {chi2_dev, 8 * nsamp, "chi2"}};
-  for (int o = 0; o < 5; ++o) {
-    for (int i = 0; i < 3; ++i)
-      if (dm_spans_overlap((uint64_t)out[o].p, out[o].bytes, 0, (uint64_t)in[i].p, in[i].bytes, 0, 1))
-        return redcal_refuse(ctx, std::string(out[o].name) + " shares an element with " + in[i].name);
-    for (int p = 0; p < o; ++p)
-      if (dm_spans_overlap((uint64_t)out[o].p, out[o].bytes, 0, (uint64_t)out[p].p, out[p].bytes, 0, 1))
-        return redcal_refuse(ctx, std::string(out[o].name) + " shares an element with " + out[p].name);
-  }
+  const std::string shared = dm_spans_shared(in, 3, out, 5);
+  if (!shared.empty()) return dm_refuse(ctx, RC_WHO, shared);
   DM_HIP(ctx, hipSetDevice(ctx->device));
   dm_ws_scope ws(ctx);
   const dm_redcal_table table = dm_redcal_build(nfeed, npairs, class_off_host, members_host, feed_weight_host);

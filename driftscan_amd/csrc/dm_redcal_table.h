@@ -8,6 +8,7 @@
 #include "dm_stack_table.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -16,6 +17,10 @@
 struct dm_redcal_inc {
   int row, partner, cls, side;
 };
+// the table is uploaded as it is and the kernels read an incidence as one int4: x = row, y = partner, z = cls, w = side
+static_assert(sizeof(dm_redcal_inc) == 16 && offsetof(dm_redcal_inc, row) == 0 && offsetof(dm_redcal_inc, partner) == 4 &&
+                  offsetof(dm_redcal_inc, cls) == 8 && offsetof(dm_redcal_inc, side) == 12,
+              "dm_redcal_inc is the int4 (row, partner, cls, side) of the kernels");
 
 struct dm_redcal_table {
   std::vector<double> yfac;          // (nmem) fw_i fw_j, 0 for an autocorrelation: the factor of the y step

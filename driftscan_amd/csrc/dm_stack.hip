@@ -12,10 +12,12 @@
 // lanes one contiguous run of TT x 16 bytes of a row.  TT = dm_gain_tile(nfeed) with gains, 16 without; the chunks
 // never cut a class.
 #include "dm_common.h"
+#include "dm_feedpair.h"
 #include "dm_stack_sum.h"
 #include "dm_stack_table.h"
 #include "../../include/driftmi.h"
 
+#include <algorithm>
 #include <vector>
 
 namespace {
@@ -148,19 +150,11 @@ int stack_plan_make(dm_ctx* ctx, const char* who, int nreal, int nf, int nfeed, 
   return p->off && p->mem && p->chunk ? DM_OK : DM_ENOMEM;
 }
 
-template <typename K>
-int stack_lds_attr(dm_ctx* ctx, K kernel, size_t lds) {
-  if (lds > (size_t)DM_GAIN_LDS_SHARED)
-    DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-  return DM_OK;
-}
-
 template <int TT, bool HAS_G, bool HAS_W>
 int vis_stack_launch(dm_ctx* ctx, const stack_plan& p, const cplx* vis, const double* w, const cplx* g, const double* mfac,
                      cplx* out, double* wout, uint32_t nfeed, uint32_t npairs, uint32_t ntime, uint32_t nf, uint32_t g_each,
                      uint32_t w_each, unsigned long long vstride, unsigned long long ostride) {
-  DM_TRY(stack_lds_attr(ctx, &vis_stack_kernel<TT, HAS_G, HAS_W>, p.lds));
+  DM_TRY(dm_lds_attr(ctx, &vis_stack_kernel<TT, HAS_G, HAS_W>, p.lds));
   constexpr unsigned threads = stack_waves(HAS_G) * 64;
   DM_PLAUNCH(ctx, DM_PROF_UTIL, (vis_stack_kernel<TT, HAS_G, HAS_W>), dim3(p.nblocks), dim3(threads), p.lds, ctx->stream, vis, w,
              g, mfac, out, wout, p.off, p.mem, p.chunk, nfeed, npairs, p.nmem, ntime, p.ntiles, p.nchunks, nf, g_each,
@@ -173,18 +167,13 @@ template <int TT, bool HAS_G>
 int vis_expand_launch(dm_ctx* ctx, const stack_plan& p, const cplx* sky, const cplx* g, cplx* out, uint32_t nfeed,
                       uint32_t npairs, uint32_t ntime, uint32_t nf, uint32_t g_each, unsigned long long sstride,
                       unsigned long long ostride, int accumulate) {
-  DM_TRY(stack_lds_attr(ctx, &vis_expand_kernel<TT, HAS_G>, p.lds));
+  DM_TRY(dm_lds_attr(ctx, &vis_expand_kernel<TT, HAS_G>, p.lds));
   constexpr unsigned threads = expand_waves(HAS_G, TT) * 64;
   DM_PLAUNCH(ctx, DM_PROF_UTIL, (vis_expand_kernel<TT, HAS_G>), dim3(p.nblocks), dim3(threads), p.lds, ctx->stream, sky, g, out,
              p.off, p.mem, p.chunk, nfeed, npairs, p.nmem, ntime, p.ntiles, p.nchunks, nf, g_each, sstride, ostride,
              accumulate);
   DM_HIP(ctx, hipGetLastError());
   return DM_OK;
-}
-
-int stack_refuse(dm_ctx* ctx, const char* who, const std::string& what) {
-  ctx->err = std::string(who) + ": " + what;
-  return DM_EARG;
 }
 
 }  // namespace
@@ -195,31 +184,27 @@ extern "C" int dm_vis_stack(dm_ctx* ctx, int nreal, int w_nreal, int g_nreal, in
                             int64_t vis_rstride, int64_t out_rstride) {
   if (!ctx) return DM_EARG;
   const char* who = "dm_vis_stack";
-  if (nreal < 0 || nf < 0 || nfeed < 0 || npairs < 0 || ntime < 0 || vis_rstride < 0 || out_rstride < 0)
-    return stack_refuse(ctx, who, "negative size");
   const bool has_g = g_dev != nullptr, has_w = w_dev != nullptr;
+  const std::string bad = dm_pair_args_check(nreal, nf, nfeed, npairs, ntime, std::min(vis_rstride, out_rstride), nullptr,
+                                             nullptr, class_off_host, members_host, has_g, feed_weight_host);
+  if (!bad.empty()) return dm_refuse(ctx, who, bad);
   DM_ARG(ctx, !has_w || w_nreal == 1 || w_nreal == nreal);
   DM_ARG(ctx, !has_g || g_nreal == 1 || g_nreal == nreal);
-  const std::string bad = dm_stack_table_check(nfeed, npairs, class_off_host, members_host, has_g);
-  if (!bad.empty()) return stack_refuse(ctx, who, bad);
-  if (feed_weight_host)
-    for (int a = 0; a < nfeed; ++a)
-      if (!(feed_weight_host[a] >= 0.0)) return stack_refuse(ctx, who, "feed weight " + std::to_string(a) + " is negative");
   const int64_t nmem = npairs > 0 ? class_off_host[npairs] : 0;
   if (vis_rstride == 0) vis_rstride = (int64_t)nf * nmem * ntime;
   if (out_rstride == 0) out_rstride = (int64_t)nf * npairs * ntime;
   DM_ARG(ctx, vis_rstride >= (int64_t)nf * nmem * ntime && out_rstride >= (int64_t)nf * npairs * ntime);
   if (nreal == 0 || nf == 0 || npairs == 0 || ntime == 0) return DM_OK;
-  if (!vis_dev || !out_dev || !wout_dev) return stack_refuse(ctx, who, "null pointer with work to do");
+  if (!vis_dev || !out_dev || !wout_dev) return dm_refuse(ctx, who, "null pointer with work to do");
   const uint64_t vrow = (uint64_t)nf * nmem * ntime, orow = (uint64_t)nf * npairs * ntime;
   if (dm_spans_overlap((uint64_t)vis_dev, 16 * vrow, 16 * (uint64_t)vis_rstride, (uint64_t)out_dev, 16 * orow,
                        16 * (uint64_t)out_rstride, nreal) ||
       dm_spans_overlap((uint64_t)vis_dev, 16 * vrow, 16 * (uint64_t)vis_rstride, (uint64_t)wout_dev, 8 * orow,
                        8 * (uint64_t)out_rstride, nreal))
-    return stack_refuse(ctx, who, "out or wout shares an element with vis");
+    return dm_refuse(ctx, who, "out or wout shares an element with vis");
   if (dm_spans_overlap((uint64_t)out_dev, 16 * orow, 16 * (uint64_t)out_rstride, (uint64_t)wout_dev, 8 * orow,
                        8 * (uint64_t)out_rstride, nreal))
-    return stack_refuse(ctx, who, "out shares an element with wout");
+    return dm_refuse(ctx, who, "out shares an element with wout");
   DM_HIP(ctx, hipSetDevice(ctx->device));
   dm_ws_scope ws(ctx);
   stack_plan p;
@@ -261,21 +246,20 @@ extern "C" int dm_vis_expand(dm_ctx* ctx, int nreal, int g_nreal, int nf, int nf
                              void* out_dev, int64_t sky_rstride, int64_t out_rstride, int accumulate) {
   if (!ctx) return DM_EARG;
   const char* who = "dm_vis_expand";
-  if (nreal < 0 || nf < 0 || nfeed < 0 || npairs < 0 || ntime < 0 || sky_rstride < 0 || out_rstride < 0)
-    return stack_refuse(ctx, who, "negative size");
   const bool has_g = g_dev != nullptr;
+  const std::string bad = dm_pair_args_check(nreal, nf, nfeed, npairs, ntime, std::min(sky_rstride, out_rstride), nullptr,
+                                             nullptr, class_off_host, members_host, has_g, nullptr);
+  if (!bad.empty()) return dm_refuse(ctx, who, bad);
   DM_ARG(ctx, !has_g || g_nreal == 1 || g_nreal == nreal);
-  const std::string bad = dm_stack_table_check(nfeed, npairs, class_off_host, members_host, has_g);
-  if (!bad.empty()) return stack_refuse(ctx, who, bad);
   const int64_t nmem = npairs > 0 ? class_off_host[npairs] : 0;
   if (sky_rstride == 0) sky_rstride = (int64_t)nf * npairs * ntime;
   if (out_rstride == 0) out_rstride = (int64_t)nf * nmem * ntime;
   DM_ARG(ctx, sky_rstride >= (int64_t)nf * npairs * ntime && out_rstride >= (int64_t)nf * nmem * ntime);
   if (nreal == 0 || nf == 0 || npairs == 0 || ntime == 0) return DM_OK;
-  if (!sky_dev || !out_dev) return stack_refuse(ctx, who, "null pointer with work to do");
+  if (!sky_dev || !out_dev) return dm_refuse(ctx, who, "null pointer with work to do");
   if (dm_spans_overlap((uint64_t)sky_dev, 16 * (uint64_t)nf * npairs * ntime, 16 * (uint64_t)sky_rstride, (uint64_t)out_dev,
                        16 * (uint64_t)nf * nmem * ntime, 16 * (uint64_t)out_rstride, nreal))
-    return stack_refuse(ctx, who, "out shares an element with sky");
+    return dm_refuse(ctx, who, "out shares an element with sky");
   DM_HIP(ctx, hipSetDevice(ctx->device));
   dm_ws_scope ws(ctx);
   stack_plan p;

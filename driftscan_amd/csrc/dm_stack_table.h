@@ -1,5 +1,6 @@
-// dm_stack_table.h — host-side checks of dm_vis_stack and dm_vis_expand: the class table of
-// unstacked (per-feed-pair) visibilities, the split of the classes over workgroups and the overlap of two buffers.  Plain
+// dm_stack_table.h — host-side checks of the feed-pair entries (dm_vis_stack and dm_vis_expand, DESIGN.md section 4.17;
+// dm_redcal_solve, 4.18; dm_modelcal_solve, 4.21): the arguments they share, the class table of unstacked
+// (per-feed-pair) visibilities, the split of the classes over workgroups and the overlap of buffers.  Plain
 // C++ with no HIP in it, so a stand-alone program can compile and call it (scratch/stack_table_check.cpp does, under the
 // address and undefined-behaviour sanitizers); dm_stack.hip includes the same text.
 #pragma once
@@ -38,6 +39,24 @@ inline std::string dm_stack_table_check(int nfeed, int npairs, const int* class_
   return "";
 }
 
+// What every feed-pair entry checks first, in this order: the sizes and the strides between realisations (`rstride_min`,
+// the smallest of them) are not negative; the realisations of the weights and of the model (w_nreal, m_nreal: null where
+// the entry has none, or checks it itself) are 1 or nreal; the class table; the feed weights (null: ones) are not
+// negative (a NaN is refused too).  Returns an empty string, or what is wrong.
+inline std::string dm_pair_args_check(int nreal, int nf, int nfeed, int npairs, int ntime, int64_t rstride_min,
+                                      const int* w_nreal, const int* m_nreal, const int* class_off, const int* members,
+                                      bool has_g, const double* feed_weight) {
+  if (nreal < 0 || nf < 0 || nfeed < 0 || npairs < 0 || ntime < 0 || rstride_min < 0) return "negative size";
+  if (w_nreal && *w_nreal != 1 && *w_nreal != nreal) return "w_nreal must be 1 or nreal";
+  if (m_nreal && *m_nreal != 1 && *m_nreal != nreal) return "m_nreal must be 1 or nreal";
+  const std::string bad = dm_stack_table_check(nfeed, npairs, class_off, members, has_g);
+  if (!bad.empty()) return bad;
+  if (feed_weight)
+    for (int a = 0; a < nfeed; ++a)
+      if (!(feed_weight[a] >= 0.0)) return "feed weight " + std::to_string(a) + " is negative";
+  return "";
+}
+
 // Class ranges of the workgroups of one (realisation, frequency, time tile): chunk q takes the classes
 // [chunk[q], chunk[q + 1]).  A class is never cut (its sum stays inside one wave, so the split changes no bit); the cuts
 // fall where the member count passes multiples of nmem / nchunks.  `cells` is the number of (realisation, frequency,
@@ -69,4 +88,24 @@ inline bool dm_spans_overlap(uint64_t a, uint64_t a_row, uint64_t a_stride, uint
   const uint64_t a_end = a + (uint64_t)(nreal - 1) * a_stride + a_row;
   const uint64_t b_end = b + (uint64_t)(nreal - 1) * b_stride + b_row;
   return a < b_end && b < a_end;
+}
+
+// One contiguous buffer of an entry, by the name its refusal uses; p may be null when bytes is 0.
+struct dm_span {
+  const void* p;
+  uint64_t bytes;
+  const char* name;
+};
+
+// That no output shares an element with an input or with an output before it: an empty string, or "<output> shares an
+// element with <the other>" for the first pair that does (outputs in their order, against the inputs first).  A span of
+// no bytes shares nothing.
+inline std::string dm_spans_shared(const dm_span* in, int nin, const dm_span* out, int nout) {
+  for (int o = 0; o < nout; ++o)
+    for (int i = 0; i < nin + o; ++i) {
+      const dm_span& other = i < nin ? in[i] : out[i - nin];
+      if (dm_spans_overlap((uint64_t)out[o].p, out[o].bytes, 0, (uint64_t)other.p, other.bytes, 0, 1))
+        return std::string(out[o].name) + " shares an element with " + other.name;
+    }
+  return "";
 }

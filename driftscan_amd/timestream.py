@@ -13,6 +13,7 @@ import logging
 import os
 import pickle
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -1818,6 +1819,49 @@ def _write_sim_file(tstream, fi, data, tphi, gain=None, weight=None, table=None,
         f.attrs["ntime"] = int(data.shape[-1])
 
 
+def _conf_filled(given, defaults, complaint, show=sorted):
+    """`defaults` with the entries of the dict `given` (or None) over them; a key that `defaults` lacks raises ValueError:
+    `complaint` % (the unknown keys, the known ones), each through `show`."""
+    given = dict(given or {})
+    unknown = sorted(set(given) - set(defaults))
+    if unknown:
+        raise ValueError(complaint % (show(unknown), show(sorted(defaults))))
+    return dict(defaults, **given)
+
+
+def _host_c128(x, shape, what, names):
+    """The tensor or array `x` as a complex128 host array of `shape` (its axes are `names`), else ValueError."""
+    arr = np.asarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=np.complex128)
+    if arr.shape != tuple(shape):
+        raise ValueError("%s %s is not (%s) = (%s)" % (what, arr.shape, names, ", ".join("%d" % v for v in shape)))
+    return arr
+
+
+def _dir_phi(tstream, ntime=None):
+    """The sample positions of a Timestream directory: the dataset `phi` of its first file, or the uniform grid of
+    `ntime` samples (None: the file's attribute `ntime`)."""
+    with storage.File(tstream._ffile(0), "r") as f:
+        if "phi" in f:
+            return np.asarray(f["phi"][:])
+        return np.linspace(0, 2 * np.pi, int(f.attrs["ntime"]) if ntime is None else ntime, endpoint=False)
+
+
+def _freq_chunks(freqs, chunk_gb, per_f):
+    """`freqs` in runs that fit `chunk_gb` at `per_f` bytes a frequency, one frequency at the least."""
+    step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
+    return [freqs[c0 : c0 + step] for c0 in range(0, len(freqs), step)]
+
+
+def _save_all(tss):
+    """How every driver ends: once all ranks have written their files, rank 0 saves the Timestream objects."""
+    parallel.barrier()
+    if parallel.rank0():
+        for ts in tss:
+            os.makedirs(ts.directory, exist_ok=True)
+            ts.save()
+    parallel.barrier()
+
+
 def _unstacked_weights(tel, weights, freqs, ntime):
     if weights is None:
         return None
@@ -1957,12 +2001,7 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
                         f.create_dataset("baselines", data=np.asarray(tel.baselines))
                         f.attrs["beamtransfer_path"] = os.path.abspath(bt.directory)
                         f.attrs["ntime"] = ntime
-    parallel.barrier()
-    if parallel.rank0():
-        for tstream in tss:
-            os.makedirs(tstream.directory, exist_ok=True)
-            tstream.save()
-    parallel.barrier()
+    _save_all(tss)
     return tss
 
 
@@ -2005,12 +2044,7 @@ def _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed
                     _write_sim_file(tss[r0 + r], freqs[f0 + k], host[r, k], tphi,
                                     gain=None if gh is None else gh[r if gh.shape[0] > 1 else 0, k],
                                     weight=None if weight_f is None else weight_f[f0 + k], table=table)
-    parallel.barrier()
-    if parallel.rank0():
-        for tstream in tss:
-            os.makedirs(tstream.directory, exist_ok=True)
-            tstream.save()
-    parallel.barrier()
+    _save_all(tss)
     return tss
 
 
@@ -2021,11 +2055,9 @@ MODELCAL_DEFAULTS = dict(model=None, interval=16, damping=0.5, tol=1e-10, maxite
 
 
 def _modelcal_conf(modelcal, m, nfreq, npairs, ntime, tphi):
-    """The checked dict `modelcal` of `stack_baselines`: (solver keywords, edge_floor, min_model, model(fi) -> (npairs,
-    ntime) complex128)."""
-    if set(modelcal or {}) - set(MODELCAL_DEFAULTS):
-        raise ValueError("modelcal holds %s, not in %s" % (sorted(set(modelcal) - set(MODELCAL_DEFAULTS)), sorted(MODELCAL_DEFAULTS)))
-    conf = dict(MODELCAL_DEFAULTS, **(modelcal or {}))
+    """The checked dict `modelcal` of `stack_baselines` as a namespace: solver (the solver's keywords), edge_floor,
+    min_model, model (fi -> (npairs, ntime) complex128) and nint, the solution intervals of a frequency."""
+    conf = _conf_filled(modelcal, MODELCAL_DEFAULTS, "modelcal holds %s, not in %s")
     model = conf.pop("model")
     if model is None:
         raise ValueError("modelcal needs `model`: a stacked Timestream directory or an array (nfreq, npairs, ntime)")
@@ -2042,8 +2074,7 @@ def _modelcal_conf(modelcal, m, nfreq, npairs, ntime, tphi):
             raise ValueError("modelcal model: %s holds no timestream" % mts.directory)
         if mts.is_unstacked():
             raise ValueError("modelcal model: %s holds unstacked visibilities, the stacked model is expected" % mts.directory)
-        with storage.File(mts._ffile(0), "r") as f:
-            mphi = np.asarray(f["phi"][:]) if "phi" in f else np.linspace(0, 2 * np.pi, int(f.attrs["ntime"]), endpoint=False)
+        mphi = _dir_phi(mts)
         if mphi.shape != tphi.shape or not np.array_equal(mphi, tphi):
             raise ValueError("modelcal model: %s is sampled at other positions `phi` than the data" % mts.directory)
 
@@ -2053,11 +2084,10 @@ def _modelcal_conf(modelcal, m, nfreq, npairs, ntime, tphi):
                 raise ValueError("modelcal model: %s is %s, not (npairs, ntime) = (%d, %d)" % (mts._ffile(fi), v.shape, npairs, ntime))
             return v
     else:
-        arr = np.asarray(model.cpu().numpy() if hasattr(model, "data_ptr") else model, dtype=np.complex128)
-        if arr.shape != (nfreq, npairs, ntime):
-            raise ValueError("modelcal model %s is not (nfreq, npairs, ntime) = (%d, %d, %d)" % (arr.shape, nfreq, npairs, ntime))
+        arr = _host_c128(model, (nfreq, npairs, ntime), "modelcal model", "nfreq, npairs, ntime")
         model_f = lambda fi: arr[fi]
-    return solver, edge_floor, min_model, model_f
+    return SimpleNamespace(solver=solver, edge_floor=edge_floor, min_model=min_model, model=model_f,
+                           nint=_modelcal_nint(ntime, solver["interval"]))
 
 
 def _modelcal_chunk(ctx, vis_d, w_d, model, class_off, members, nfeed, fw, solver, edge_floor, min_model):
@@ -2099,6 +2129,210 @@ def _modelcal_chunk(ctx, vis_d, w_d, model, class_off, members, nfeed, fw, solve
         gains[k], found = modelcal_spread(fixed[k], valid[k], L, ntime)
         blind += 0 if found else 1
     return gains, fixed, its, valid, blind
+
+
+def _stack_gains_arg(calibrate, shape):
+    """`calibrate` of `stack_baselines` checked: None, "file", "redundant", "model" or a host array of `shape`."""
+    if isinstance(calibrate, str):
+        if calibrate not in ("file", "none", "redundant", "model"):
+            raise ValueError('calibrate is None, "none", "file", "redundant" or an array (nfreq, nfeed, ntime)')
+        return None if calibrate == "none" else calibrate
+    return None if calibrate is None else _host_c128(calibrate, shape, "calibrate", "nfreq, nfeed, ntime")
+
+
+def _redcal_conf(redcal, shape):
+    """The checked dict `redcal` of `stack_baselines`: (solver keywords, reference — None, "file", "model" or a host
+    array of `shape`)."""
+    conf = _conf_filled(redcal, REDCAL_DEFAULTS, "redcal holds %s, not in %s")
+    reference = conf.pop("reference")
+    solver = dict(damping=float(conf["damping"]), tol=float(conf["tol"]), maxiter=int(conf["maxiter"]))
+    if isinstance(reference, str):
+        if reference not in ("file", "none", "model"):
+            raise ValueError('redcal reference is None, "file" or an array (nfreq, nfeed, ntime)')
+        reference = None if reference == "none" else reference
+    elif reference is not None:
+        reference = _host_c128(reference, shape, "redcal reference", "nfreq, nfeed, ntime")
+    return solver, reference
+
+
+def _feed_weights(feed_weight, dead_feeds, nfeed):
+    """feed_weight (nfeed) with the `dead_feeds` at 0, or None when neither is given."""
+    if feed_weight is None and len(dead_feeds) == 0:
+        return None
+    fw = np.ones(nfeed, dtype=np.float64) if feed_weight is None else np.array(feed_weight, dtype=np.float64)
+    if fw.shape != (nfeed,) or not np.all(np.isfinite(fw) & (fw >= 0)):
+        raise ValueError("feed_weight must be (nfeed,) = (%d,), finite and not negative" % nfeed)
+    for a in dead_feeds:
+        if not 0 <= int(a) < nfeed:
+            raise ValueError("dead feed %d of %d" % (int(a), nfeed))
+        fw[int(a)] = 0.0
+    return fw
+
+
+def _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelcal):
+    """The arguments of `stack_baselines` checked once and its modes resolved.  Fields: the class table (class_off,
+    members) and nmem, npairs, nfeed, nfreq, ntime; phi, the sample positions of `src`; rfi, the flagger's parameters or
+    None; redundant, by_model, ref_model: which solvers run and what the model's gains are for; redcal, the redundant
+    solver's keywords; bases, its degeneracies; modelcal, the namespace of `_modelcal_conf`, or None; calibrated: the
+    stack takes gains; file_gain: the files' `gain` is read, and under which name its absence is refused; given_gain: an
+    array (nfreq, nfeed, ntime) handed over — both are the reference on the redundant route and the stack's gains
+    otherwise; fw, the feed weights or None; weighted: the chunks carry per-sample weights."""
+    c = SimpleNamespace(rfi=None if rfi is None else rfi_params(rfi))
+    tel = m.beamtransfer.telescope
+    if not src.is_unstacked():
+        raise ValueError("%s does not hold unstacked visibilities" % src.directory)
+    c.class_off, c.members = tel.redundant_pairs()
+    c.nmem, c.npairs, c.nfeed, c.nfreq, c.ntime = int(c.class_off[-1]), int(tel.npairs), int(tel.nfeed), int(tel.nfreq), src.ntime
+    with storage.File(src._ffile(0), "r") as f:
+        if not (np.array_equal(f["class_off"][:], c.class_off) and np.array_equal(f["members"][:], c.members)):
+            raise ValueError("%s was written for another class table than this telescope's" % src.directory)
+    shape = (c.nfreq, c.nfeed, c.ntime)
+    calibrate = _stack_gains_arg(calibrate, shape)
+    c.calibrated = calibrate is not None
+    c.redundant, c.by_model = (isinstance(calibrate, str) and calibrate == mode for mode in ("redundant", "model"))
+    if redcal is not None and not c.redundant:
+        raise ValueError('redcal belongs to calibrate="redundant"')
+    c.redcal, reference = _redcal_conf(redcal, shape) if c.redundant else (None, calibrate)
+    c.ref_model = c.redundant and isinstance(reference, str) and reference == "model"
+    c.file_gain = None
+    if isinstance(reference, str) and reference == "file":
+        c.file_gain = 'redcal reference "file"' if c.redundant else 'calibrate="file"'
+    c.given_gain = None if reference is None or isinstance(reference, str) else reference
+    if modelcal is not None and not (c.by_model or c.ref_model):
+        raise ValueError('modelcal belongs to calibrate="model" or to the redcal reference "model"')
+    c.phi = _dir_phi(src, c.ntime)   # a day keeps its own sample positions (section 4.19)
+    c.modelcal = _modelcal_conf(modelcal, m, c.nfreq, c.npairs, c.ntime, c.phi) if c.by_model or c.ref_model else None
+    c.fw = _feed_weights(feed_weight, dead_feeds, c.nfeed)
+    c.bases = redcal_degeneracies(c.class_off, c.members, c.nfeed, c.fw) if c.redundant else None
+    with storage.File(src._ffile(0), "r") as f:
+        c.weighted = "weight" in f or c.rfi is not None
+    return c
+
+
+def _stack_per_f(c):
+    """Bytes one frequency of a chunk of `stack_baselines` takes, on the host and on the device."""
+    per_f = c.ntime * (16.0 * c.nmem + (8.0 * c.nmem if c.weighted else 0.0) + (16.0 * c.nfeed if c.calibrated else 0.0)
+                       + 24.0 * c.npairs)
+    if c.redundant:   # g, the second gain buffer and y of the solver, its three per-sample outputs and its state words
+        per_f += c.ntime * (32.0 * c.nfeed + 16.0 * c.npairs + 20.0 + 24.0)
+    if c.modelcal is not None:   # the model and its device copy, the solver's three gain buffers and gweight, its words
+        per_f += (c.ntime * 32.0 * c.npairs + c.modelcal.nint * (56.0 * c.nfeed + 64.0)
+                  + (0.0 if c.by_model else 16.0 * c.nfeed * c.ntime))
+    return per_f
+
+
+def _stack_read(src, fs, c):
+    """The frequencies `fs` of the unstacked directory `src` as one chunk of per-frequency lists: vis (nmem, ntime); w of
+    that shape, ones where a file has none, or None when the run is not weighted; g (nfeed, ntime), the gains of the
+    files or of the array handed over, or None; vis_d and w_d, the device copies (1, nfc, nmem, ntime) that
+    `_stack_on_device` makes."""
+    vis, w, g = [], [], []
+    for fi in fs:
+        with storage.File(src._ffile(fi), "r") as f:
+            vis.append(np.asarray(f["timestream"][:], dtype=np.complex128))
+            if c.weighted:
+                w.append(np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f
+                         else np.ones((c.nmem, c.ntime), dtype=np.float64))
+            if c.file_gain is not None:
+                if "gain" not in f:
+                    raise ValueError("%s: %s holds no dataset `gain`" % (c.file_gain, src._ffile(fi)))
+                g.append(np.asarray(f["gain"][:], dtype=np.complex128))
+    if c.given_gain is not None:
+        g = [c.given_gain[fi] for fi in fs]
+    return SimpleNamespace(fs=fs, vis=vis, w=w if c.weighted else None, g=g or None, vis_d=None, w_d=None)
+
+
+def _stack_on_device(ctx, chunk):
+    """(vis_d, w_d) of a chunk: uploaded once, by the first stage that needs them (after the flagging)."""
+    if chunk.vis_d is None:
+        chunk.vis_d = ctx.to_device(np.stack(chunk.vis)[None])
+        chunk.w_d = None if chunk.w is None else ctx.to_device(np.stack(chunk.w)[None])
+    return chunk.vis_d, chunk.w_d
+
+
+def _stack_flag(ctx, chunk, rfi_p):
+    """The RFI pass over a chunk: its weights with the flagged samples at 0, on the host."""
+    x_d = ctx.to_device(np.stack(chunk.vis))
+    return list(ctx.to_host(ctx.rfi_flag(x_d, w=ctx.to_device(np.stack(chunk.w)), **rfi_p)[0]))
+
+
+def _stack_model_solve(ctx, chunk, c):
+    """The sky-model solve of a chunk: (spread gains (nfc, nfeed, ntime), the datasets it adds to every frequency's file,
+    invalid intervals, frequencies without a valid one)."""
+    mc = c.modelcal
+    vis_d, w_d = _stack_on_device(ctx, chunk)
+    mg, mq, mits, mvalid, blind = _modelcal_chunk(ctx, vis_d, w_d, np.stack([mc.model(fi) for fi in chunk.fs]), c.class_off,
+                                                  c.members, c.nfeed, c.fw, mc.solver, mc.edge_floor, mc.min_model)
+    datasets = [dict(gain_solution=mg[k], modelcal_gain=mq[k], modelcal_iters=mits[k], modelcal_valid=mvalid[k].astype(np.int32))
+                for k in range(len(chunk.fs))]
+    return mg, datasets, int((~mvalid).sum()), blind
+
+
+def _stack_redundant_solve(ctx, chunk, c, ref):
+    """The redundant solve of a chunk with its degeneracies fixed against `ref` (nfc, nfeed, ntime), an array or a list
+    over the frequencies, or against ones (None): (gains (nfc, nfeed, ntime), the datasets it adds to every frequency's
+    file, failed (nfc, ntime): the samples that did not converge)."""
+    vis_d, w_d = _stack_on_device(ctx, chunk)
+    gs, ys, info = ctx.redcal_solve(vis_d, c.class_off, c.members, w=w_d, feed_weight=np.ones(c.nfeed) if c.fw is None else c.fw,
+                                    **c.redcal)
+    gfix, _ = fix_degeneracies(ctx.to_host(gs)[0], ctx.to_host(ys)[0], c.class_off, c.members,
+                               ref=None if ref is None else np.asarray(ref), feed_weight=c.fw, bases=c.bases)
+    its, failed = ctx.to_host(info["iters"])[0], ~(ctx.to_host(info["step"])[0] < c.redcal["tol"])
+    return gfix, [dict(gain_solution=gfix[k], redcal_iters=its[k]) for k in range(len(chunk.fs))], failed
+
+
+def _stack_sum(ctx, chunk, c, g, log):
+    """`Context.vis_stack` of a chunk with the gains g (nfc, nfeed, ntime), an array or a list over the frequencies, or
+    None: (stacked (nfc, npairs, ntime), weight of that shape: the share of every class that is there, 0 where the kernel
+    formed no sample)."""
+    with _StepTimer(log, "stack"):
+        vis_d, w_d = _stack_on_device(ctx, chunk)
+        g_d = None if g is None else ctx.to_device(np.asarray(g)[None])
+        out, wout = ctx.vis_stack(vis_d, c.class_off, c.members, w=w_d, g=g_d, feed_weight=c.fw)
+        out, wout = ctx.to_host(out)[0], ctx.to_host(wout)[0]
+    nmem_c = np.diff(c.class_off)[:, None].astype(np.float64)
+    mfac = None if c.fw is None else (c.fw[c.members[:, 0]] * c.fw[c.members[:, 1]])[:, None]
+    share = np.ones((c.npairs, 1)) if mfac is None else np.add.reduceat(mfac, c.class_off[:-1], axis=0) / nmem_c
+    wts = np.empty(wout.shape, dtype=np.float64)
+    for k in range(len(chunk.fs)):
+        if c.weighted:
+            fac = chunk.w[k] if mfac is None else chunk.w[k] * mfac
+            share_k = np.add.reduceat(fac, c.class_off[:-1], axis=0) / nmem_c
+        else:
+            share_k = np.broadcast_to(share, (c.npairs, c.ntime))
+        wts[k] = np.where(wout[k] == 0, 0.0, share_k)
+    return out, wts
+
+
+def _stack_write(dst, freqs, records, phi, log):
+    """The stacked files of this rank's frequencies from their records (timestream, weight, datasets)."""
+    # every rank writes `weight` or none does: the m-mode routes choose their path by the file of frequency 0
+    mine = any(np.any(rec["weight"] != 1.0) for rec in records.values())
+    nranks = parallel.size() if parallel._dist() else 1
+    write_w = any(parallel.exchange([mine] * nranks))
+    with _StepTimer(log, "write"):
+        for fi in freqs:
+            rec = records[fi]
+            _write_sim_file(dst, fi, rec["timestream"], phi, weight=rec["weight"] if write_w else None,
+                            extra=rec["datasets"] or None)
+
+
+def _stack_report(c, nfreq, lost, minvalid, mblind, log):
+    """The warnings and the counters of `sim_log` for what the solvers of `stack_baselines` left undone."""
+    if c.redundant and lost:
+        logging.getLogger(__name__).warning("stack_baselines: the redundant calibration of %d of %d samples did not converge "
+                                            "in %d iterations; they are written with weight 0", lost, nfreq * c.ntime,
+                                            c.redcal["maxiter"])
+        if log is not None:
+            log["redcal_not_converged"] = log.get("redcal_not_converged", 0) + lost
+    if c.modelcal is not None and minvalid:
+        logging.getLogger(__name__).warning("stack_baselines: %d of %d solution intervals of the sky-model calibration are not "
+                                            "valid (not solved, not converged in %d iterations or with an unconstrained "
+                                            "gain) and take the gains of the nearest valid interval; %d frequencies have "
+                                            "none and are stacked with gains of one", minvalid, nfreq * c.modelcal.nint,
+                                            c.modelcal.solver["maxiter"], mblind)
+        if log is not None:
+            log["modelcal_invalid"] = log.get("modelcal_invalid", 0) + minvalid
 
 
 def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None, rfi=None,
@@ -2146,195 +2380,37 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     rfi: a dict of the parameters of `Context.rfi_flag` (an unknown key raises ValueError).  The feed-pair data of every
     frequency is then flagged on the device before anything is solved or summed, and the flags
     go on as weights 0 of the members, as the file's own flags do."""
-    rfi_p = None if rfi is None else rfi_params(rfi)
-    ctx = get_context()
-    tel = m.beamtransfer.telescope
     src = Timestream(indir, m)
-    if not src.is_unstacked():
-        raise ValueError("%s does not hold unstacked visibilities" % src.directory)
-    class_off, members = tel.redundant_pairs()
-    nmem, npairs, nfeed, nfreq = int(class_off[-1]), int(tel.npairs), int(tel.nfeed), int(tel.nfreq)
-    ntime = src.ntime
-    with storage.File(src._ffile(0), "r") as f:
-        if not (np.array_equal(f["class_off"][:], class_off) and np.array_equal(f["members"][:], members)):
-            raise ValueError("%s was written for another class table than this telescope's" % src.directory)
-    if isinstance(calibrate, str):
-        if calibrate not in ("file", "none", "redundant", "model"):
-            raise ValueError('calibrate is None, "none", "file", "redundant" or an array (nfreq, nfeed, ntime)')
-        calibrate = None if calibrate == "none" else calibrate
-    elif calibrate is not None:
-        if hasattr(calibrate, "data_ptr"):
-            calibrate = calibrate.cpu().numpy()
-        calibrate = np.asarray(calibrate, dtype=np.complex128)
-        if calibrate.shape != (nfreq, nfeed, ntime):
-            raise ValueError("calibrate %s is not (nfreq, nfeed, ntime) = (%d, %d, %d)"
-                             % (calibrate.shape, nfreq, nfeed, ntime))
-    redundant = isinstance(calibrate, str) and calibrate == "redundant"
-    by_model = isinstance(calibrate, str) and calibrate == "model"
-    if redcal is not None and not redundant:
-        raise ValueError('redcal belongs to calibrate="redundant"')
-    ref_model = False
-    if redundant:
-        if set(redcal or {}) - set(REDCAL_DEFAULTS):
-            raise ValueError("redcal holds %s, not in %s" % (sorted(set(redcal) - set(REDCAL_DEFAULTS)), sorted(REDCAL_DEFAULTS)))
-        rconf = dict(REDCAL_DEFAULTS, **(redcal or {}))
-        reference = rconf.pop("reference")
-        rconf = dict(damping=float(rconf["damping"]), tol=float(rconf["tol"]), maxiter=int(rconf["maxiter"]))
-        ref_model = isinstance(reference, str) and reference == "model"
-        if ref_model:
-            reference = None
-        elif isinstance(reference, str):
-            if reference not in ("file", "none"):
-                raise ValueError('redcal reference is None, "file" or an array (nfreq, nfeed, ntime)')
-            reference = None if reference == "none" else reference
-        elif reference is not None:
-            reference = np.asarray(reference.cpu().numpy() if hasattr(reference, "data_ptr") else reference, dtype=np.complex128)
-            if reference.shape != (nfreq, nfeed, ntime):
-                raise ValueError("redcal reference %s is not (nfreq, nfeed, ntime) = (%d, %d, %d)"
-                                 % (reference.shape, nfreq, nfeed, ntime))
-    if modelcal is not None and not (by_model or ref_model):
-        raise ValueError('modelcal belongs to calibrate="model" or to the redcal reference "model"')
-    mconf = None
-    if by_model or ref_model:
-        with storage.File(src._ffile(0), "r") as f:
-            sphi = np.asarray(f["phi"][:]) if "phi" in f else np.linspace(0, 2 * np.pi, ntime, endpoint=False)
-        mconf = _modelcal_conf(modelcal, m, nfreq, npairs, ntime, sphi)
-        mnint = _modelcal_nint(ntime, mconf[0]["interval"])
-    fw = None
-    if feed_weight is not None or len(dead_feeds) > 0:
-        fw = np.ones(nfeed, dtype=np.float64) if feed_weight is None else np.array(feed_weight, dtype=np.float64)
-        if fw.shape != (nfeed,) or not np.all(np.isfinite(fw) & (fw >= 0)):
-            raise ValueError("feed_weight must be (nfeed,) = (%d,), finite and not negative" % nfeed)
-        for a in dead_feeds:
-            if not 0 <= int(a) < nfeed:
-                raise ValueError("dead feed %d of %d" % (int(a), nfeed))
-            fw[int(a)] = 0.0
-    freqs = _sim_freqs(tel, None)
-    with storage.File(src._ffile(0), "r") as f:
-        weighted = "weight" in f or rfi_p is not None
-    per_f = ntime * (16.0 * nmem + (8.0 * nmem if weighted else 0.0) + (16.0 * nfeed if calibrate is not None else 0.0)
-                     + 24.0 * npairs)
-    if redundant:   # g, the second gain buffer and y of the solver, its three per-sample outputs and its state words
-        per_f += ntime * (32.0 * nfeed + 16.0 * npairs + 20.0 + 24.0)
-        bases = redcal_degeneracies(class_off, members, nfeed, fw)
-    if mconf is not None:   # the model and its device copy, the solver's three gain buffers and gweight, its words
-        per_f += ntime * 32.0 * npairs + mnint * (56.0 * nfeed + 64.0) + (0.0 if by_model else 16.0 * nfeed * ntime)
-    solved, lost = {}, 0
-    msolved, minvalid, mblind = {}, 0, 0
-    step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
+    c = _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelcal)
+    ctx = get_context()
+    freqs = _sim_freqs(m.beamtransfer.telescope, None)
     log = sim_log
-    nmem_c = np.diff(class_off)[:, None].astype(np.float64)
-    stacked, wts = {}, {}
-    for c0 in range(0, len(freqs), step):
-        fs = freqs[c0 : c0 + step]
+    records, lost, minvalid, mblind = {}, 0, 0, 0
+    for fs in _freq_chunks(freqs, chunk_gb, _stack_per_f(c)):
         with _StepTimer(log, "read"):
-            vis, w, g = [], [], []
-            for fi in fs:
-                with storage.File(src._ffile(fi), "r") as f:
-                    vis.append(np.asarray(f["timestream"][:], dtype=np.complex128))
-                    if weighted:
-                        w.append(np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f
-                                 else np.ones((nmem, ntime), dtype=np.float64))
-                    if redundant:
-                        if isinstance(reference, str):
-                            if "gain" not in f:
-                                raise ValueError('redcal reference "file": %s holds no dataset `gain`' % src._ffile(fi))
-                            g.append(np.asarray(f["gain"][:], dtype=np.complex128))
-                    elif isinstance(calibrate, str) and not by_model:
-                        if "gain" not in f:
-                            raise ValueError('calibrate="file": %s holds no dataset `gain`' % src._ffile(fi))
-                        g.append(np.asarray(f["gain"][:], dtype=np.complex128))
-            if calibrate is not None and not isinstance(calibrate, str):
-                g = [calibrate[fi] for fi in fs]
-        if rfi_p is not None:
+            chunk = _stack_read(src, fs, c)
+        if c.rfi is not None:
             with _StepTimer(log, "rfi"):
-                x_d = ctx.to_device(np.stack(vis))
-                w = list(ctx.to_host(ctx.rfi_flag(x_d, w=ctx.to_device(np.stack(w)), **rfi_p)[0]))
-                del x_d
-        vis_d = w_d = mref = None
-        if mconf is not None:
+                chunk.w = _stack_flag(ctx, chunk, c.rfi)
+        g, datasets, failed = chunk.g, [{} for _ in fs], None
+        if c.modelcal is not None:
             with _StepTimer(log, "modelcal"):
-                vis_d = ctx.to_device(np.stack(vis)[None])
-                w_d = ctx.to_device(np.stack(w)[None]) if weighted else None
-                mg, mq, mits, mvalid, blind = _modelcal_chunk(ctx, vis_d, w_d, np.stack([mconf[3](fi) for fi in fs]), class_off,
-                                                              members, nfeed, fw, mconf[0], mconf[1], mconf[2])
-            for k, fi in enumerate(fs):
-                msolved[fi] = (mg[k], mq[k], mits[k], mvalid[k])
-            minvalid, mblind = minvalid + int((~mvalid).sum()), mblind + blind
-            if by_model:
-                g = list(mg)
-            else:
-                mref = mg
-        if redundant:
+                mg, datasets, bad, blind = _stack_model_solve(ctx, chunk, c)
+            minvalid, mblind = minvalid + bad, mblind + blind
+            g = mg if c.by_model else g
+        if c.redundant:
             with _StepTimer(log, "redcal"):
-                if vis_d is None:
-                    vis_d = ctx.to_device(np.stack(vis)[None])
-                    w_d = ctx.to_device(np.stack(w)[None]) if weighted else None
-                gs, ys, info = ctx.redcal_solve(vis_d, class_off, members, w=w_d,
-                                                feed_weight=np.ones(nfeed) if fw is None else fw, **rconf)
-                ref = np.stack(g) if isinstance(reference, str) else (None if reference is None else reference[list(fs)])
-                if ref_model:
-                    ref = mref
-                gfix, _ = fix_degeneracies(ctx.to_host(gs)[0], ctx.to_host(ys)[0], class_off, members, ref=ref,
-                                           feed_weight=fw, bases=bases)
-                its, failed = ctx.to_host(info["iters"])[0], ~(ctx.to_host(info["step"])[0] < rconf["tol"])
-                del gs, ys, info
-            g = list(gfix)
-            for k, fi in enumerate(fs):
-                solved[fi] = (gfix[k], its[k], failed[k])
+                g, solved, failed = _stack_redundant_solve(ctx, chunk, c, mg if c.ref_model else g)
+            datasets = [dict(r, **{name: v for name, v in d.items() if name not in r}) for r, d in zip(solved, datasets)]
             lost += int(failed.sum())
-        with _StepTimer(log, "stack"):
-            if vis_d is None:
-                vis_d = ctx.to_device(np.stack(vis)[None])
-                w_d = ctx.to_device(np.stack(w)[None]) if weighted else None
-            out, wout = ctx.vis_stack(vis_d, class_off, members, w=w_d,
-                                      g=ctx.to_device(np.stack(g)[None]) if calibrate is not None else None, feed_weight=fw)
-            out, wout = ctx.to_host(out)[0], ctx.to_host(wout)[0]
-        share = np.ones((npairs, 1), dtype=np.float64)
-        if fw is not None:
-            share = np.add.reduceat((fw[members[:, 0]] * fw[members[:, 1]])[:, None], class_off[:-1], axis=0) / nmem_c
+        out, wts = _stack_sum(ctx, chunk, c, g, log)
         for k, fi in enumerate(fs):
-            if weighted:
-                fac = w[k] if fw is None else w[k] * (fw[members[:, 0]] * fw[members[:, 1]])[:, None]
-                share_k = np.add.reduceat(fac, class_off[:-1], axis=0) / nmem_c
-            else:
-                share_k = np.broadcast_to(share, (npairs, ntime))
-            stacked[fi], wts[fi] = out[k], np.where(wout[k] == 0, 0.0, share_k)
-            if redundant:
-                wts[fi] = np.where(solved[fi][2][None, :], 0.0, wts[fi])
-    # every rank writes `weight` or none does: the m-mode routes choose their path by the file of frequency 0
-    mine = any(np.any(wv != 1.0) for wv in wts.values())
-    nranks = parallel.size() if parallel._dist() else 1
-    write_w = any(parallel.exchange([mine] * nranks))
+            weight = wts[k] if failed is None else np.where(failed[k][None, :], 0.0, wts[k])
+            records[fi] = dict(timestream=out[k], weight=weight, datasets=datasets[k])
     dst = Timestream(outdir, m)
-    with storage.File(src._ffile(0), "r") as f:   # a day keeps its own sample positions (section 4.19)
-        tphi = np.asarray(f["phi"][:]) if "phi" in f else np.linspace(0, 2 * np.pi, ntime, endpoint=False)
-    with _StepTimer(log, "write"):
-        for fi in freqs:
-            extra = dict(gain_solution=solved[fi][0], redcal_iters=solved[fi][1]) if redundant else None
-            if mconf is not None:
-                extra = dict(extra or dict(gain_solution=msolved[fi][0]), modelcal_gain=msolved[fi][1],
-                             modelcal_iters=msolved[fi][2], modelcal_valid=msolved[fi][3].astype(np.int32))
-            _write_sim_file(dst, fi, stacked[fi], tphi, weight=wts[fi] if write_w else None, extra=extra)
-    if redundant and lost:
-        logging.getLogger(__name__).warning("stack_baselines: the redundant calibration of %d of %d samples did not converge "
-                                            "in %d iterations; they are written with weight 0", lost, len(freqs) * ntime,
-                                            rconf["maxiter"])
-        if log is not None:
-            log["redcal_not_converged"] = log.get("redcal_not_converged", 0) + lost
-    if mconf is not None and minvalid:
-        logging.getLogger(__name__).warning("stack_baselines: %d of %d solution intervals of the sky-model calibration are not "
-                                            "valid (not solved, not converged in %d iterations or with an unconstrained "
-                                            "gain) and take the gains of the nearest valid interval; %d frequencies have "
-                                            "none and are stacked with gains of one", minvalid, len(freqs) * mnint,
-                                            mconf[0]["maxiter"], mblind)
-        if log is not None:
-            log["modelcal_invalid"] = log.get("modelcal_invalid", 0) + minvalid
-    parallel.barrier()
-    if parallel.rank0():
-        os.makedirs(dst.directory, exist_ok=True)
-        dst.save()
-    parallel.barrier()
+    _stack_write(dst, freqs, records, c.phi, log)
+    _stack_report(c, len(freqs), lost, minvalid, mblind, log)
+    _save_all([dst])
     return dst
 
 
@@ -2530,13 +2606,11 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
     freqs = _sim_freqs(tel, None)
     nt_max = max(g[2] for g in geo)
     per_f = nrow * ((24.0 if rfi is None else 32.0) * nt_max + 36.0 * ntime + 16.0 * ntime)
-    step = max(1, int(chunk_gb * 2.0**30 // max(per_f, 1.0)))
     log = sim_log
     dst = Timestream(outdir, m)
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     nd = len(days)
-    for c0 in range(0, len(freqs), step):
-        fs = freqs[c0 : c0 + step]
+    for fs in _freq_chunks(freqs, chunk_gb, per_f):
         acc = None
         for d, (phi0, dphi, nt_in) in zip(days, geo):
             with _StepTimer(log, "read"):
@@ -2578,11 +2652,7 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
                 _write_sim_file(dst, fi, mean_h[k], tphi, weight=w_h[k], table=table, extra=extra)
                 with storage.File(dst._ffile(fi), "a") as f:
                     f.attrs["ndays"] = nd
-    parallel.barrier()
-    if parallel.rank0():
-        os.makedirs(dst.directory, exist_ok=True)
-        dst.save()
-    parallel.barrier()
+    _save_all([dst])
     return dst
 
 
@@ -2674,12 +2744,7 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
             del day, E
             for k, fi in enumerate(freqs):
                 _write_sim_file(tss[d], fi, host[k], np.mod(phi, 2 * np.pi), weight=None if wh is None else wh[k], table=table)
-    parallel.barrier()
-    if parallel.rank0():
-        for ts in tss:
-            os.makedirs(ts.directory, exist_ok=True)
-            ts.save()
-    parallel.barrier()
+    _save_all(tss)
     return tss
 
 
@@ -2692,12 +2757,7 @@ RFI_SQRT_LN2 = 0.83255461115769775635   # sigma = median / sqrt(ln 2) for a Rayl
 
 def rfi_params(params=None):
     """The parameters of the RFI flagger with their defaults filled in; an unknown key raises ValueError."""
-    params = dict(params or {})
-    unknown = sorted(set(params) - set(RFI_DEFAULTS))
-    if unknown:
-        raise ValueError("rfi: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(sorted(RFI_DEFAULTS))))
-    out = dict(RFI_DEFAULTS)
-    out.update(params)
+    out = _conf_filled(params, RFI_DEFAULTS, "rfi: unknown key(s) %s (known: %s)", show=", ".join)
     out["windows"] = tuple(int(v) for v in out["windows"])
     return out
 
@@ -2865,10 +2925,8 @@ def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, **params):
     freqs = _sim_freqs(tel, None)
     with storage.File(src._ffile(0), "r") as f:
         nrow, nt = (int(v) for v in f["timestream"].shape)
-    step = max(1, int(chunk_gb * 2.0**30 // max(nrow * nt * 32.0, 1.0)))
     log = sim_log
-    for c0 in range(0, len(freqs), step):
-        fs = freqs[c0 : c0 + step]
+    for fs in _freq_chunks(freqs, chunk_gb, nrow * nt * 32.0):
         with _StepTimer(log, "read"):
             files = []
             for fi in fs:
@@ -2896,9 +2954,5 @@ def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, **params):
                         f.create_dataset(name, data=np.ascontiguousarray(value))
                     for name, value in attrs.items():
                         f.attrs[name] = value
-    parallel.barrier()
-    if not inplace and parallel.rank0():
-        os.makedirs(dst.directory, exist_ok=True)
-        dst.save()
-    parallel.barrier()
+    _save_all([] if inplace else [dst])
     return dst

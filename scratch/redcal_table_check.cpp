@@ -8,6 +8,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <random>
 #include <vector>
@@ -116,6 +117,40 @@ int main() {
     check("modelcal: interval 0", dm_modelcal_args_check(12, 0, 0.5, 1e-10, 500).find("interval") != std::string::npos);
     check("modelcal: 4093 feeds", dm_modelcal_args_check(4093, 16, 0.5, 1e-10, 500).find("does not fit") != std::string::npos);
     check("modelcal: damping 0", dm_modelcal_args_check(12, 16, 0.0, 1e-10, 500).find("damping") != std::string::npos);
+  }
+  {  // the table goes to the device as it is: an incidence read as four ints is (row, partner, cls, side)
+    const dm_redcal_table t = dm_redcal_build(3, 3, off3.data(), mem3.data(), nullptr, 1);
+    std::vector<int> flat(4 * t.inc.size());
+    std::memcpy(flat.data(), t.inc.data(), flat.size() * sizeof(int));
+    bool same = !t.inc.empty();
+    for (size_t k = 0; k < t.inc.size(); ++k)
+      same = same && flat[4 * k] == t.inc[k].row && flat[4 * k + 1] == t.inc[k].partner && flat[4 * k + 2] == t.inc[k].cls &&
+             flat[4 * k + 3] == t.inc[k].side;
+    check("an incidence is the int4 (row, partner, cls, side)", same);
+  }
+  {  // the opening of the two solvers: the shared argument check and the spans of dm_redcal_solve
+    const int two = 2, three = 3;
+    const double dead[3] = {1.0, 0.0, 1.0}, minus[3] = {1.0, 1.0, -1.0};
+    auto open = [&](int nreal, int64_t rs, const int* wn, const int* mn, const double* fw) {
+      return dm_pair_args_check(nreal, 1, 3, 3, 5, rs, wn, mn, off3.data(), mem3.data(), true, fw);
+    };
+    check("solver opening: sound", open(2, 0, &two, &two, dead).empty() && open(2, 0, nullptr, nullptr, nullptr).empty());
+    check("solver opening: negative size", open(-1, 0, nullptr, nullptr, nullptr) == "negative size" &&
+                                               open(2, -1, nullptr, nullptr, nullptr) == "negative size");
+    check("solver opening: w_nreal", open(2, 0, &three, &two, nullptr) == "w_nreal must be 1 or nreal");
+    check("solver opening: m_nreal", open(2, 0, &two, &three, nullptr) == "m_nreal must be 1 or nreal");
+    check("solver opening: feed weight", open(2, 0, nullptr, nullptr, minus) == "feed weight 2 is negative");
+    std::vector<char> buf(1000);
+    const char* b = buf.data();
+    const dm_span in[3] = {{b, 300, "vis"}, {nullptr, 0, "w"}, {nullptr, 0, "g0"}};
+    const dm_span apart[5] = {{b + 300, 100, "g"}, {b + 400, 100, "y"}, {b + 500, 20, "iters"}, {b + 520, 40, "step"}, {b + 560, 40, "chi2"}};
+    const dm_span on_vis[5] = {{b + 300, 100, "g"}, {b + 299, 100, "y"}, {b + 500, 20, "iters"}, {b + 520, 40, "step"}, {b + 560, 40, "chi2"}};
+    const dm_span on_out[5] = {{b + 300, 100, "g"}, {b + 400, 100, "y"}, {b + 500, 20, "iters"}, {b + 519, 40, "step"}, {b + 560, 40, "chi2"}};
+    const dm_span none[5] = {{b, 0, "g"}, {b, 0, "y"}, {b, 0, "iters"}, {b, 0, "step"}, {b, 0, "chi2"}};
+    check("spans: disjoint", dm_spans_shared(in, 3, apart, 5).empty());
+    check("spans: y on vis (the input is named first)", dm_spans_shared(in, 3, on_vis, 5) == "y shares an element with vis");
+    check("spans: step on iters", dm_spans_shared(in, 3, on_out, 5) == "step shares an element with iters");
+    check("spans: zero-length outputs", dm_spans_shared(in, 3, none, 5).empty());
   }
   const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
   check("sound arguments", dm_redcal_args_check(0.4, 1e-10, 500).empty() && dm_redcal_args_check(1.0, 0.0, 1).empty());

@@ -4,6 +4,7 @@
 // Every table is a heap allocation of exactly its size, so a read past a table's end is reported.
 #include "../driftscan_amd/csrc/dm_stack_table.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -78,6 +79,61 @@ int main() {
       std::printf("dm_spans_overlap FAIL at a = %llu, b = %llu\n", (unsigned long long)s.a, (unsigned long long)s.b);
       ++failures;
     }
+  // the arguments the feed-pair entries share: each refusal once, in the order of the checks, and a sound call
+  {
+    const std::vector<int> off{0, 2, 3}, mem{0, 1, 1, 2, 0, 2}, empty_class{0, 2, 2};
+    const std::vector<double> fw{1.0, 0.0, 2.0}, fw_neg{1.0, -0.5, 2.0}, fw_nan{1.0, 1.0, std::nan("")};
+    const int one = 1, two = 2, three = 3;
+    struct {
+      const char* what;
+      int nreal, ntime;
+      int64_t rstride;
+      const int *w_nreal, *m_nreal, *off;
+      const double* fw;
+      const char* needle;
+    } args[] = {{"sound, nothing optional", 2, 5, 0, nullptr, nullptr, off.data(), nullptr, nullptr},
+                {"sound, w and model per realisation", 2, 5, 64, &two, &two, off.data(), fw.data(), nullptr},
+                {"sound, w and model shared", 2, 5, 64, &one, &one, off.data(), fw.data(), nullptr},
+                {"negative ntime", 2, -1, 0, nullptr, nullptr, off.data(), nullptr, "negative size"},
+                {"negative stride", 2, 5, -1, nullptr, nullptr, off.data(), nullptr, "negative size"},
+                {"w_nreal 3 of 2", 2, 5, 0, &three, &two, off.data(), nullptr, "w_nreal must be 1 or nreal"},
+                {"m_nreal 3 of 2", 2, 5, 0, &two, &three, off.data(), nullptr, "m_nreal must be 1 or nreal"},
+                {"an empty class", 2, 5, 0, nullptr, nullptr, empty_class.data(), nullptr, "class 1 is empty"},
+                {"a negative feed weight", 2, 5, 0, nullptr, nullptr, off.data(), fw_neg.data(), "feed weight 1 is negative"},
+                {"a NaN feed weight", 2, 5, 0, nullptr, nullptr, off.data(), fw_nan.data(), "feed weight 2 is negative"}};
+    for (const auto& a : args) {
+      const std::string r = dm_pair_args_check(a.nreal, 1, 3, 2, a.ntime, a.rstride, a.w_nreal, a.m_nreal, a.off, mem.data(), true, a.fw);
+      const bool ok = a.needle ? r == a.needle : r.empty();
+      std::printf("%-34s %s  [%s]\n", a.what, ok ? "ok  " : "FAIL", r.c_str());
+      if (!ok) ++failures;
+    }
+  }
+  // named spans: disjoint, an output on an input, an output on an earlier output, zero-length spans anywhere
+  {
+    std::vector<char> buf(400);
+    const char* b = buf.data();
+    struct {
+      const char* what;
+      dm_span in[2], out[2];
+      const char* want;
+    } cases[] = {{"disjoint", {{b, 100, "vis"}, {b + 100, 100, "w"}}, {{b + 200, 100, "g"}, {b + 300, 100, "y"}}, ""},
+                 {"g ends inside w", {{b, 100, "vis"}, {b + 150, 100, "w"}}, {{b + 100, 51, "g"}, {b + 300, 100, "y"}},
+                  "g shares an element with w"},
+                 {"y begins inside g", {{b, 100, "vis"}, {b + 100, 100, "w"}}, {{b + 200, 100, "g"}, {b + 299, 100, "y"}},
+                  "y shares an element with g"},
+                 {"inputs may overlap", {{b, 100, "vis"}, {b + 50, 100, "w"}}, {{b + 200, 100, "g"}, {b + 300, 100, "y"}}, ""},
+                 {"zero-length spans", {{b + 250, 0, "vis"}, {nullptr, 0, "w"}}, {{b + 200, 100, "g"}, {b + 210, 0, "y"}}, ""}};
+    for (const auto& c : cases) {
+      const std::string r = dm_spans_shared(c.in, 2, c.out, 2);
+      const bool ok = r == c.want;
+      std::printf("%-34s %s  [%s]\n", c.what, ok ? "ok  " : "FAIL", r.c_str());
+      if (!ok) ++failures;
+    }
+    if (!dm_spans_shared(nullptr, 0, nullptr, 0).empty()) {
+      std::printf("dm_spans_shared of nothing FAIL\n");
+      ++failures;
+    }
+  }
   std::printf("%d failures\n", failures);
   return failures ? EXIT_FAILURE : EXIT_SUCCESS;
 }

@@ -614,3 +614,101 @@ def test_unstacked_weights_chunks_and_the_pipeline(routes, skyfile, tmp_path):
         v, c = s.timestream_f(fi), routes["cal"].timestream_f(fi)            # the same two calls once more
         assert np.abs(v - c).max() <= 1e-12 * np.abs(c).max()
     assert os.path.exists(s._mfile(0))
+
+
+# ---- the drivers over more than one chunk of frequencies ------------------------------------------------------------------
+CHUNK_RFI = dict(chi1=5.5, segment=512)
+CHUNK_CADENCE = 120.0   # 718 samples per turn, as in tests/test_gpu_sidereal.py
+
+
+def _same_directories(a, b, tel):
+    """Every dataset and attribute of every per-frequency file of the Timestreams a and b, bit for bit."""
+    from driftscan_amd import storage
+
+    for fi in range(tel.nfreq):
+        with storage.File(a._ffile(fi), "r") as f, storage.File(b._ffile(fi), "r") as g:
+            assert sorted(f.keys()) == sorted(g.keys()) and sorted(f.attrs.keys()) == sorted(g.attrs.keys())
+            for name in f.keys():
+                x, y = f[name][:], g[name][:]
+                assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), (fi, name)
+            for name in f.attrs.keys():
+                assert np.array_equal(f.attrs[name], g.attrs[name]), (fi, name)
+
+
+def _chunked_redundant(routes, name, chunk_gb):
+    from driftscan_amd import timestream
+
+    return timestream.stack_baselines(routes["pm"], routes["uns"].directory, str(routes["d"] / name), calibrate="redundant",
+                                      redcal={"reference": "file"}, rfi=dict(CHUNK_RFI),
+                                      dead_feeds=[_dead_feed(routes["tel"])[0]], chunk_gb=chunk_gb)
+
+
+def _chunked_model(routes, name, chunk_gb):
+    """The data and the model of the fixture `sky_model` of tests/test_gpu_modelcal.py: explicit gains constant over
+    intervals of 16 samples, the `ideal` directory as the model."""
+    from driftscan_amd import timestream
+
+    pm, d, tel, ntime, kw, ideal = (routes[k] for k in ("pm", "d", "tel", "ntime", "kw", "ideal"))
+    if "chunk_uns" not in routes:
+        rng = np.random.default_rng(23)
+        nint = -(-ntime // 16)
+        gq = (1 + 0.05 * rng.uniform(-1, 1, (tel.nfreq, tel.nfeed, nint))) * np.exp(0.1j * rng.uniform(-1, 1, (tel.nfreq, tel.nfeed, nint)))
+        gains = np.ascontiguousarray(gq[..., np.arange(ntime) // 16])
+        routes["chunk_uns"] = timestream.simulate_ensemble(pm, str(d / "chunk_uns"), 1, gains=gains, unstacked=True, **kw)[0]
+    return timestream.stack_baselines(pm, routes["chunk_uns"].directory, str(d / name), calibrate="model", rfi=dict(CHUNK_RFI),
+                                      dead_feeds=[_dead_feed(tel)[0]],
+                                      modelcal=dict(interval=16, tol=1e-12, maxiter=2000, model=ideal.directory),
+                                      chunk_gb=chunk_gb)
+
+
+def _chunk_days(routes):
+    """Two days of 4 / 5 turn at this telescope with one day's noise and interference bursts; (directories, nsamples)."""
+    from driftscan_amd import skysim, timestream
+
+    nsamp = int(0.8 * timestream.T_SIDEREAL_DAY / CHUNK_CADENCE)
+    if "chunk_days" not in routes:
+        dirs = [str(routes["d"] / ("chunk_day%d" % i)) for i in range(2)]
+        timestream.simulate_days(routes["pm"], dirs, (0.3, 2.7), nsamp, CHUNK_CADENCE, seed=3,
+                                 rfi=skysim.RFIModel(fraction=0.005, burst=4, amplitude=30.0, seed=11))
+        routes["chunk_days"] = dirs
+    return routes["chunk_days"], nsamp
+
+
+def _chunked_sidereal(routes, name, chunk_gb):
+    from driftscan_amd import timestream
+
+    tel, ntime = routes["tel"], routes["ntime"]
+    dirs, nsamp = _chunk_days(routes)
+    if chunk_gb is None:   # two frequencies fit, the third makes the second chunk: the driver's own estimate per frequency
+        chunk_gb = 2.5 * int(tel.npairs) * (32.0 * nsamp + 36.0 * ntime + 16.0 * ntime) / 2.0**30
+    return timestream.sidereal_stack(routes["pm"], dirs, str(routes["d"] / name), ntime=ntime, a=3, rfi=dict(CHUNK_RFI),
+                                     chunk_gb=chunk_gb)
+
+
+def _chunked_rfi(routes, name, chunk_gb):
+    from driftscan_amd import timestream
+
+    dirs, nsamp = _chunk_days(routes)
+    if chunk_gb is None:
+        chunk_gb = 2.5 * int(routes["tel"].npairs) * nsamp * 32.0 / 2.0**30
+    return timestream.rfi_flag(routes["pm"], dirs[0], str(routes["d"] / name), chunk_gb=chunk_gb, **CHUNK_RFI)
+
+
+@pytest.mark.parametrize("driver,small", [(_chunked_redundant, 1e-9), (_chunked_model, 1e-9), (_chunked_sidereal, None),
+                                          (_chunked_rfi, None)], ids=["redundant", "model", "sidereal", "rfi"])
+def test_the_chunks_of_frequencies_change_no_bit(routes, driver, small):
+    """`stack_baselines` (flagged, one dead feed, calibrate="redundant" with the reference of the files, and
+    calibrate="model") with all three frequencies in one chunk and with one frequency per chunk, `sidereal_stack` and
+    `rfi_flag` in one chunk and in two: every dataset of every output file is bitwise equal.  Every kernel of the chain
+    documents that the bits of a row, sample or interval do not depend on the batch; this holds the drivers to it."""
+    from driftscan_amd import timestream
+
+    log = {}
+    timestream.sim_log = log
+    try:
+        one = driver(routes, driver.__name__ + "_one", 4.0)
+        many = driver(routes, driver.__name__ + "_many", small)
+    finally:
+        timestream.sim_log = None
+    assert log["read"] > 0 and log["write"] > 0
+    _same_directories(one, many, routes["tel"])
