@@ -993,26 +993,21 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
     lmax, mmax, nfreq, npol = tel.lmax, tel.mmax, tel.nfreq, tel.num_pol_sky
     if ndays is None:
         ndays = tel.ndays
-    ntime = 2 * mmax + 1 if resolution == 0 else int(np.round(24 * 3600.0 / resolution))
+    ntime = _sim_ntime(tel, resolution)
     nranks = parallel.size() if parallel._dist() else 1
     me = parallel.rank() if parallel._dist() else 0
-    local_freq = parallel.partition_for(list(range(nfreq)), me, nranks)
+    local_freq = _sim_freqs(tel, None)
     lfreq = len(local_freq)
     col_vis = np.zeros((tel.npairs, lfreq, ntime), dtype=np.complex128)
 
-    skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
-    sources = _as_sources(sources)
+    skymodels, sources = _as_models(skymodels), _as_sources(sources)
     if len(maps) > 0 or len(skymodels) > 0 or len(sources) > 0:
         # The reference's two MPI transposes (timestream.py:700-760): every rank transforms the maps of ITS frequencies,
         # the a_lm are regrouped by m, every rank projects ITS m through the beam (all frequencies of an m in one grouped
         # product on the device), and the visibilities come back regrouped by frequency.
         m_of = [parallel.partition_for(list(range(mmax + 1)), r, nranks) for r in range(nranks)]
         f_of = [parallel.partition_for(list(range(nfreq)), r, nranks) for r in range(nranks)]
-        skymap = None
-        for mapfile in maps:
-            with storage.File(mapfile, "r") as f:
-                part = f["map"][local_freq[0] : local_freq[-1] + 1] if lfreq else None
-            skymap = part if skymap is None else skymap + part
+        skymap = _read_maps(maps, local_freq)
         alm_loc = (healpix.sphtrans_sky(skymap, lmax) if lfreq and len(maps) > 0 else
                    np.zeros((lfreq, npol, lmax + 1, lmax + 1), dtype=np.complex128))   # (lfreq, npol, L, L): [l, m]
         for model in skymodels:
@@ -1044,8 +1039,7 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
                     col_vis[..., -mi] = vis[:, 1].T.conj()   # conjugate only, not (-1)^m (timestream.py:759-761)
 
     if ndays > 0 and lfreq > 0:
-        noise_ps = np.asarray(tel.noisepower(np.arange(tel.npairs)[:, np.newaxis], np.array(local_freq)[np.newaxis, :],
-                                             ndays=ndays)).reshape(tel.npairs, lfreq)[:, :, np.newaxis]
+        noise_ps = _noisepower(tel, local_freq, ndays).T[:, :, np.newaxis]
         if seed is not None:
             np.random.seed(seed + parallel.rank())   # ranks must not share a noise realisation
         noise_vis = (np.array([1.0, 1.0j]) * np.random.standard_normal(col_vis.shape + (2,))).sum(axis=-1)
@@ -1083,21 +1077,8 @@ def simulate(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     tstream = Timestream(outdir, m)
     for lfi, fi in enumerate(local_freq):
-        os.makedirs(tstream._fdir(fi), exist_ok=True)
-        with storage.File(tstream._ffile(fi), "w") as f:
-            f.create_dataset("timestream", data=np.ascontiguousarray(vis_stream[:, lfi]))
-            f.create_dataset("phi", data=tphi)
-            if gain_f is not None:
-                f.create_dataset("gain", data=np.ascontiguousarray(gain_f[lfi]))
-            if weight_f is not None:
-                f.create_dataset("weight", data=np.ascontiguousarray(weight_f[lfi]))
-            f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
-            f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
-            f.create_dataset("feedmask", data=np.asarray(tel.feedmask))
-            f.create_dataset("uniquepairs", data=np.asarray(tel.uniquepairs))
-            f.create_dataset("baselines", data=np.asarray(tel.baselines))
-            f.attrs["beamtransfer_path"] = os.path.abspath(bt.directory)
-            f.attrs["ntime"] = ntime
+        _write_sim_file(tstream, fi, vis_stream[:, lfi], tphi, gain=None if gain_f is None else gain_f[lfi],
+                        weight=None if weight_f is None else weight_f[lfi])
     parallel.barrier()
     tstream.save()
     parallel.barrier()
@@ -1127,140 +1108,206 @@ def _sim_ntime(tel, resolution):
     return 2 * tel.mmax + 1 if resolution == 0 else int(np.round(24 * 3600.0 / resolution))
 
 
-def _sim_weights(tel, weights, freqs, ntime):
-    """`weights` of `simulate_visibilities` / `simulate_ensemble` as a host array broadcastable to (nf, npairs, ntime) over
-    the rows `freqs`: a FlagModel is evaluated for their global frequency indices, an array has one row per entry."""
+def _as_models(skymodels):
+    return (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
+
+
+def _read_maps(maps, freqs):
+    """Sum of the datasets `map` [freq, pol, pixel] of the files `maps` at the sorted frequencies `freqs`; None when
+    either is empty."""
+    skymap = None
+    for mapfile in maps if len(freqs) else ():
+        with storage.File(mapfile, "r") as f:
+            part = f["map"][freqs[0] : freqs[-1] + 1][[fi - freqs[0] for fi in freqs]]
+        skymap = part if skymap is None else skymap + part
+    return skymap
+
+
+def _noisepower(tel, freqs, ndays):
+    """`tel.noisepower` of every unique pair at the frequencies `freqs`: (nf, npairs) float64."""
+    npairs = int(tel.npairs)
+    return np.asarray(tel.noisepower(np.arange(npairs)[np.newaxis, :], np.array(freqs)[:, np.newaxis], ndays=ndays),
+                      dtype=np.float64).reshape(len(freqs), npairs)
+
+
+def _sim_conf(m, freqs, resolution, ndays, default_ndays=None, **given):
+    """The arguments of the device simulators checked once.  `given`: nreal, first, seed, sky_seed, klname, maps,
+    skymodels, sources, gains and chunk_gb of the caller, all of them.  Fields: m, bt and tel; freqs, the sorted rows
+    (None: this rank's share); ntime; ndays, with `default_ndays` (None: the telescope's) for None; nreal, first, seed,
+    sky_seed, klname and chunk_gb; maps, skymodels and sources as tuples, and have_sky; gains after `skysim.as_gains`;
+    the class table (class_off, members), nfeed, npairs and nmem; rmax, the realisations of a full group.
+
+    Refused here, before any work: `freqs` that are not sorted indices, ntime < 2 mmax + 1, and explicit gains of another
+    shape than the call's.  The names in `skymodels` and `klname` are refused by `_sky_covariance`, which the sky
+    preparation (`_sim_sky`) calls first for every model."""
+    from . import skysim
+    from ._lib import BLOCKVEC_MAX_R
+
+    c = SimpleNamespace(m=m, bt=m.beamtransfer, tel=m.beamtransfer.telescope, **given)
+    c.freqs = _sim_freqs(c.tel, freqs)
+    c.ntime = _sim_ntime(c.tel, resolution)
+    if c.ntime < 2 * int(c.tel.mmax) + 1:
+        raise ValueError("%d time samples cannot hold m up to %d" % (c.ntime, int(c.tel.mmax)))
+    c.ndays = ndays if ndays is not None else c.tel.ndays if default_ndays is None else default_ndays
+    c.nreal, c.first = int(c.nreal), int(c.first)
+    c.maps, c.skymodels, c.sources = tuple(c.maps), _as_models(c.skymodels), _as_sources(c.sources)
+    c.have_sky = len(c.maps) > 0 or len(c.skymodels) > 0 or len(c.sources) > 0
+    c.class_off, c.members = c.tel.redundant_pairs()
+    c.nfeed, c.npairs, c.nmem = int(c.tel.nfeed), int(c.tel.npairs), int(c.class_off[-1])
+    c.rmax = min(BLOCKVEC_MAX_R, c.nreal)
+    c.gains = skysim.as_gains(c.gains)
+    if c.gains is not None and not isinstance(c.gains, skysim.GainModel) and len(c.freqs) and c.nreal > 0:
+        skysim.check_explicit_gains(c.gains, c.nreal, len(c.freqs), c.nfeed, c.ntime)   # before any work
+    return c
+
+
+def _sim_weights(c, weights, nrow, ntime=None):
+    """`weights` of the simulators as a host array broadcastable to (nf, nrow, ntime) over the rows `c.freqs` (ntime=None:
+    c.ntime): a FlagModel is evaluated for their global frequency indices, an array has one row per entry."""
     if weights is None:
         return None
     from . import skysim
 
-    return skysim.as_weights(weights, len(freqs), int(tel.npairs), ntime, freqs)
+    return skysim.as_weights(weights, len(c.freqs), nrow, c.ntime if ntime is None else ntime, c.freqs)
 
 
-def _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
-                       out=None, sources=(), gains=None, gain_sink=None, weights=None):
-    """The passes of `simulate_visibilities`: yields (r0, device tensor (R, nf, npairs, ntime)) for the realisations
-    first + r0 .. first + r0 + R - 1, R <= BLOCKVEC_MAX_R.  With `out` (nreal, nf, npairs, ntime) the groups are views of
-    it; without, ONE buffer is used for every group (the caller is done with a group when it asks for the next).
+def _sim_flagged(weights, f0, f1):
+    """The samples of weight 0 of the rows f0:f1 of `weights` (`_sim_weights`) as a device mask, or None."""
+    if weights is None:
+        return None
+    wf = weights[f0:f1] if np.ndim(weights) == 3 else weights
+    return get_context().to_device(np.ascontiguousarray(wf == 0))
 
-    With `gains` the sky of a group is synthesised into a scratch buffer of the group's size and reaches the result
+
+def _sim_sigma(c, freqs, members=False, ndays=None, ntime=None):
+    """The noise level on the host, sigma[f, p] = sqrt(ntime noisepower(p, f, ndays)) (nf, npairs); with `members`
+    sigma[f, m] = sqrt(n_c ntime noisepower(c, f, ndays)) (nf, nmem): the plain mean of a complete class then has the
+    noise level of the stacked simulators.  ndays, ntime: c's, or those given (`simulate_days`: samples per turn)."""
+    ntime = c.ntime if ntime is None else ntime
+    noise_ps = _noisepower(c.tel, freqs, c.ndays if ndays is None else ndays)
+    if not members:
+        return np.sqrt(ntime * noise_ps)
+    n = np.diff(c.class_off)
+    return np.repeat(np.sqrt(n[np.newaxis, :] * ntime * noise_ps), n, axis=1)
+
+
+def _sim_sky(c, freqs):
+    """Sky preparation for the rows `freqs`: fixed, the a_lm (nf, npol, lmax + 1, mmax + 1) of maps and sources on the
+    device (or None); models, (covariance, stream, roots) of every sky model; batches, the m whose beam blocks fit
+    `chunk_gb` together.  None without a sky."""
+    if not c.have_sky:
+        return None
+    from . import skysim
+
+    ctx = get_context()
+    lmax, mmax = int(c.tel.lmax), int(c.tel.mmax)
+    fixed, models = None, []
+    with _StepTimer(sim_log, "sky"):
+        if len(c.maps) > 0:
+            alm = healpix.sphtrans_sky(_read_maps(c.maps, freqs), lmax)            # (nf, npol, L, L): [l, m]
+            fixed = ctx.to_device(np.ascontiguousarray(alm[..., : mmax + 1]))
+        if len(c.sources) > 0:   # fixed like the maps, and never on the host
+            a = _sources_alm(c.sources, c.tel, freqs, False)
+            fixed = a if fixed is None else fixed.add_(a)
+        for model in c.skymodels:
+            stream = skysim.STREAM_SKY_SIGNAL if model == "signal" else skysim.STREAM_SKY_FOREGROUND
+            cv = _sky_covariance(c.m, model, c.klname)
+            models.append((cv, stream, skysim.covariance_roots(cv)))
+    batches = m_batches(list(range(mmax + 1)), lambda mi: 16.0 * len(freqs) * c.bt.ntel * c.bt.nsky, c.chunk_gb)
+    return SimpleNamespace(fixed=fixed, models=models, batches=batches)
+
+
+def _sim_group_sky(c, freqs, sky, r0, out, accumulate):
+    """The sky (`_sim_sky` of `freqs`) of the realisations first + r0 .. first + r0 + R - 1 into `out` (R, nf, npairs,
+    ntime), adding to it with `accumulate`: the a_lm are drawn, the fixed ones added, projected batch by batch
+    (`BeamTransfer.project_vectors_sky_to_telescope_device`) and synthesised (`Context.mmode_synthesis`)."""
+    from . import skysim
+
+    ctx, bt, log = get_context(), c.bt, sim_log
+    lmax, mmax, npol, nf, R = int(c.tel.lmax), int(c.tel.mmax), int(c.tel.num_pol_sky), len(freqs), int(out.shape[0])
+    with _StepTimer(log, "sky"):
+        alm = ctx.zeros((R, nf, npol, lmax + 1, mmax + 1), np.complex128) if not sky.models else None
+        for cv, stream, roots in sky.models:
+            a = skysim.draw_alm(cv, R, c.sky_seed, stream, c.first + r0, mmax, freqs, to_host=False, roots=roots)
+            alm = a if alm is None else alm.add_(a)
+        if sky.fixed is not None:
+            alm.add_(sky.fixed[None])
+        alm_m = alm.permute(4, 1, 2, 3, 0).contiguous()                # (m, nf, npol, L, R)
+        del alm
+    vis = ctx.empty((mmax + 1, nf, bt.ntel, R), np.complex128)
+    for batch in sky.batches:
+        with _StepTimer(log, "beam"):
+            beam = bt._device_beam_blocks_of(batch, freqs)
+        with _StepTimer(log, "project"):
+            vis[batch[0] : batch[-1] + 1] = bt.project_vectors_sky_to_telescope_device(
+                batch, alm_m[batch[0] : batch[-1] + 1], freqs=freqs, products=beam)
+        del beam
+    del alm_m
+    with _StepTimer(log, "synthesis"):
+        cols = vis.view(mmax + 1, nf, 2, c.npairs, R)
+        for r in range(R):
+            ctx.mmode_synthesis(cols[..., r], c.ntime, out=out[r], accumulate=accumulate)
+
+
+def _sim_gain_chunk(c, freqs, f0, f1, r0, R):
+    """The gains (1 or R, f1 - f0, nfeed, ntime) of the rows f0:f1 of `freqs` for realisations first + r0 ..
+    first + r0 + R - 1 on the device: the model's (`skysim.gains_device`) or the rows of the explicit array."""
+    from . import skysim
+
+    if isinstance(c.gains, skysim.GainModel):
+        return skysim.gains_device(c.gains, c.nfeed, freqs[f0:f1], c.ntime, R, c.first + r0)
+    g = skysim.explicit_gains(c.gains, c.nreal, len(freqs), r0, R, range(f0, f1), c.nfeed, c.ntime)
+    return g.contiguous() if hasattr(g, "data_ptr") else get_context().to_device(np.ascontiguousarray(g))
+
+
+def _visibility_groups(c, freqs, out=None, gain_sink=None, weights=None, noise=True):
+    """The passes of `simulate_visibilities` over the rows `freqs` of the run `c` (`_sim_conf`): yields (r0, device tensor
+    (R, nf, npairs, ntime)) for the realisations first + r0 .. first + r0 + R - 1, R <= BLOCKVEC_MAX_R.  With `out`
+    (nreal, nf, npairs, ntime) the groups are views of it; without, ONE buffer is used for every group (the caller is
+    done with a group when it asks for the next).  noise=False: as with ndays = 0.
+
+    With gains the sky of a group is synthesised into a scratch buffer of the group's size and reaches the result
     through `Context.ts_gain_apply` (adding to the noise when there is any).  The gains g (1 or R, nfc, nfeed, ntime) are
     made for chunks of nfc frequencies at a time (`skysim.gains_device`, which needs three buffers of that size) so that
     they fit in `chunk_gb` together with the scratch buffer — one frequency at the least; `gain_sink(r0, f0, g)` is
     called with every chunk.  `weights`: a host array broadcastable to (nf, npairs, ntime) (`_sim_weights`); the samples
     of weight 0 of every group are set to exactly 0, last of all."""
-    from . import skysim
     from ._lib import BLOCKVEC_MAX_R
 
-    ctx = get_context()
-    bt = m.beamtransfer
-    tel = bt.telescope
-    lmax, mmax, npol, npairs = int(tel.lmax), int(tel.mmax), int(tel.num_pol_sky), int(tel.npairs)
-    if ndays is None:
-        ndays = tel.ndays
-    ntime = _sim_ntime(tel, resolution)
-    if ntime < 2 * mmax + 1:
-        raise ValueError("%d time samples cannot hold m up to %d" % (ntime, mmax))
-    nreal, first = int(nreal), int(first)
-    nf = len(freqs)
-    skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
-    sources = _as_sources(sources)
-    have_sky = len(maps) > 0 or len(skymodels) > 0 or len(sources) > 0
-    if nf == 0 or nreal <= 0:
+    ctx, log, nf = get_context(), sim_log, len(freqs)
+    if nf == 0 or c.nreal <= 0:
         return
-    log = sim_log
-    gains = skysim.as_gains(gains)
-    if gains is not None:
-        nfeed = int(tel.nfeed)
-        class_off, members = tel.redundant_pairs()
-        if not isinstance(gains, skysim.GainModel):
-            skysim.check_explicit_gains(gains, nreal, nf, nfeed, ntime)   # before any work
-        scratch_bytes = 16.0 * min(BLOCKVEC_MAX_R, nreal) * nf * npairs * ntime
-        per_freq = 3 * 16.0 * min(BLOCKVEC_MAX_R, nreal) * nfeed * ntime
-        nfc = int(min(nf, max(1, (chunk_gb * 2.0**30 - scratch_bytes) // per_freq)))
-    skybuf = None
-    flagged = None if weights is None else ctx.to_device(np.ascontiguousarray(weights == 0))
-
-    sigma = None
-    if ndays > 0:
-        noise_ps = np.asarray(tel.noisepower(np.arange(npairs)[np.newaxis, :], np.array(freqs)[:, np.newaxis],
-                                             ndays=ndays), dtype=np.float64).reshape(nf, npairs)
-        sigma = ctx.to_device(np.sqrt(ntime * noise_ps))
-
-    fixed, models = None, []
-    if have_sky:
-        with _StepTimer(log, "sky"):
-            if len(maps) > 0:
-                skymap = None
-                for mapfile in maps:
-                    with storage.File(mapfile, "r") as f:
-                        part = f["map"][freqs[0] : freqs[-1] + 1][[fi - freqs[0] for fi in freqs]]
-                    skymap = part if skymap is None else skymap + part
-                alm = healpix.sphtrans_sky(skymap, lmax)                       # (nf, npol, L, L): [l, m]
-                fixed = ctx.to_device(np.ascontiguousarray(alm[..., : mmax + 1]))
-            if len(sources) > 0:   # fixed like the maps, and never on the host
-                a = _sources_alm(sources, tel, freqs, False)
-                fixed = a if fixed is None else fixed.add_(a)
-            for model in skymodels:
-                stream = skysim.STREAM_SKY_SIGNAL if model == "signal" else skysim.STREAM_SKY_FOREGROUND
-                cv = _sky_covariance(m, model, klname)
-                models.append((cv, stream, skysim.covariance_roots(cv)))
-        batches = m_batches(list(range(mmax + 1)), lambda mi: 16.0 * nf * bt.ntel * bt.nsky, chunk_gb)
-
-    buf = None
-    for r0 in range(0, nreal, BLOCKVEC_MAX_R):
-        R = min(BLOCKVEC_MAX_R, nreal - r0)
-        if out is not None:
-            grp = out[r0 : r0 + R]
-        else:
-            if buf is None:
-                buf = ctx.empty((min(BLOCKVEC_MAX_R, nreal), nf, npairs, ntime), np.complex128)
-            grp = buf[:R]
+    if c.gains is not None:
+        scratch_bytes = 16.0 * c.rmax * nf * c.npairs * c.ntime
+        per_freq = 3 * 16.0 * c.rmax * c.nfeed * c.ntime
+        nfc = int(min(nf, max(1, (c.chunk_gb * 2.0**30 - scratch_bytes) // per_freq)))
+    flagged = _sim_flagged(weights, 0, nf)
+    sigma = ctx.to_device(_sim_sigma(c, freqs)) if noise and c.ndays > 0 else None
+    sky = _sim_sky(c, freqs)
+    buf = skybuf = None
+    for r0 in range(0, c.nreal, BLOCKVEC_MAX_R):
+        R = min(BLOCKVEC_MAX_R, c.nreal - r0)
+        if out is None and buf is None:
+            buf = ctx.empty((c.rmax, nf, c.npairs, c.ntime), np.complex128)
+        grp = buf[:R] if out is None else out[r0 : r0 + R]
         if sigma is not None:
             with _StepTimer(log, "noise"):
-                ctx.ts_noise(sigma, freqs, ntime, R, seed, first + r0, out=grp)
-        elif not have_sky:
+                ctx.ts_noise(sigma, freqs, c.ntime, R, c.seed, c.first + r0, out=grp)
+        elif sky is None:
             grp.zero_()
-        if have_sky:
-            with _StepTimer(log, "sky"):
-                alm = ctx.zeros((R, nf, npol, lmax + 1, mmax + 1), np.complex128) if not models else None
-                for cv, stream, roots in models:
-                    a = skysim.draw_alm(cv, R, sky_seed, stream, first + r0, mmax, freqs, to_host=False, roots=roots)
-                    alm = a if alm is None else alm.add_(a)
-                if fixed is not None:
-                    alm.add_(fixed[None])
-                alm_m = alm.permute(4, 1, 2, 3, 0).contiguous()                # (m, nf, npol, L, R)
-                del alm
-            vis = ctx.empty((mmax + 1, nf, bt.ntel, R), np.complex128)
-            for batch in batches:
-                with _StepTimer(log, "beam"):
-                    beam = bt._device_beam_blocks_of(batch, freqs)
-                with _StepTimer(log, "project"):
-                    vis[batch[0] : batch[-1] + 1] = bt.project_vectors_sky_to_telescope_device(
-                        batch, alm_m[batch[0] : batch[-1] + 1], freqs=freqs, products=beam)
-                del beam
-            del alm_m
-            if gains is not None and skybuf is None:
-                skybuf = ctx.empty((min(BLOCKVEC_MAX_R, nreal), nf, npairs, ntime), np.complex128)
-            with _StepTimer(log, "synthesis"):
-                cols = vis.view(mmax + 1, nf, 2, npairs, R)
-                for r in range(R):
-                    if gains is None:
-                        ctx.mmode_synthesis(cols[..., r], ntime, out=grp[r], accumulate=sigma is not None)
-                    else:
-                        ctx.mmode_synthesis(cols[..., r], ntime, out=skybuf[r])
-            del vis, cols
-        if gains is not None and (have_sky or gain_sink is not None):
+        if sky is not None and c.gains is None:
+            _sim_group_sky(c, freqs, sky, r0, grp, sigma is not None)
+        elif sky is not None:
+            if skybuf is None:
+                skybuf = ctx.empty((c.rmax, nf, c.npairs, c.ntime), np.complex128)
+            _sim_group_sky(c, freqs, sky, r0, skybuf[:R], False)
+        if c.gains is not None and (sky is not None or gain_sink is not None):
             with _StepTimer(log, "gains"):
                 for f0 in range(0, nf, nfc):
                     f1 = min(nf, f0 + nfc)
-                    if isinstance(gains, skysim.GainModel):
-                        g = skysim.gains_device(gains, nfeed, freqs[f0:f1], ntime, R, first + r0)
-                    else:
-                        g = skysim.explicit_gains(gains, nreal, nf, r0, R, range(f0, f1), nfeed, ntime)
-                        g = g.contiguous() if hasattr(g, "data_ptr") else ctx.to_device(np.ascontiguousarray(g))
-                    if have_sky:
-                        ctx.ts_gain_apply(g, class_off, members, skybuf[:R, f0:f1], out=grp[:, f0:f1],
+                    g = _sim_gain_chunk(c, freqs, f0, f1, r0, R)
+                    if sky is not None:
+                        ctx.ts_gain_apply(g, c.class_off, c.members, skybuf[:R, f0:f1], out=grp[:, f0:f1],
                                           accumulate=sigma is not None)
                     if gain_sink is not None:
                         gain_sink(r0, f0, g)
@@ -1702,89 +1749,57 @@ def modelcal_spread(g, valid, interval, ntime):
     return np.ascontiguousarray(g[:, src[np.arange(int(ntime)) // int(interval)]]), True
 
 
-def _member_sigma(tel, freqs, ndays, ntime, class_off):
-    """sigma[f, m] = sqrt(n_c ntime noisepower(c, f, ndays)) of the unstacked noise: the plain mean of a complete class
-    then has the noise level of the stacked simulators."""
-    npairs = int(tel.npairs)
-    n = np.diff(class_off)
-    noise_ps = np.asarray(tel.noisepower(np.arange(npairs)[np.newaxis, :], np.array(freqs)[:, np.newaxis], ndays=ndays),
-                          dtype=np.float64).reshape(len(freqs), npairs)
-    return np.repeat(np.sqrt(n[np.newaxis, :] * ntime * noise_ps), n, axis=1)
+def _unstacked_chunks(c, freqs, out=None, want_gains=False, weights=None, noise=True):
+    """The passes of the unstacked simulators over the rows `freqs` of the run `c` (`_sim_conf`):
+    yields (r0, f0, device tensor (R, nfc, nmem, ntime), g) for realisations first + r0 .. first + r0 + R - 1
+    (R <= BLOCKVEC_MAX_R) and the frequencies freqs[f0 : f0 + nfc]; g is the gain chunk (1 or R, nfc, nfeed, ntime) when
+    `want_gains`, else None.  With `out` (nreal, nf, nmem, ntime) the chunks are views of it; without, ONE buffer serves
+    every chunk.  noise=False: as with ndays = 0.
 
-
-def _unstacked_chunks(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
-                      out=None, sources=(), gains=None, want_gains=False, weights=None):
-    """The passes of the unstacked simulators: yields (r0, f0, device tensor
-    (R, nfc, nmem, ntime), g) for realisations first + r0 .. first + r0 + R - 1 (R <= BLOCKVEC_MAX_R) and the frequencies
-    freqs[f0 : f0 + nfc]; g is the gain chunk (1 or R, nfc, nfeed, ntime) when `want_gains`, else None.  With `out`
-    (nreal, nf, nmem, ntime) the chunks are views of it; without, ONE buffer serves every chunk.
-
-    Per chunk of frequencies the stacked sky of a group comes from `_visibility_groups` (without noise, gains or flags),
-    the noise is drawn at the per-member level (`Context.ts_noise` with npairs := nmem, sigma of `_member_sigma`) and the
-    sky is spread over the members with the gains on it (`Context.vis_expand`, adding to the noise).  nfc is chosen so
-    that the unstacked chunk, the stacked sky and the three gain buffers of `skysim.gains_device` fit in `chunk_gb`, one
-    frequency at the least.  Every draw is counter based, so the chunking changes which calls make a row, not its
-    distribution or, for the noise, its bits."""
-    from . import skysim
+    Per chunk of frequencies the stacked sky of a group is made as in `_visibility_groups` (`_sim_sky`,
+    `_sim_group_sky`: no noise, gains or flags on it), the noise is drawn at the per-member level (`Context.ts_noise` with
+    npairs := nmem, sigma of `_sim_sigma`) and the sky is spread over the members with the gains on it
+    (`Context.vis_expand`, adding to the noise).  nfc is chosen so that the unstacked chunk, the stacked sky and the
+    three gain buffers of `skysim.gains_device` fit in `chunk_gb`, one frequency at the least.  Every draw is counter
+    based, so the chunking changes which calls make a row, not its distribution or, for the noise, its bits."""
     from ._lib import BLOCKVEC_MAX_R
 
-    ctx = get_context()
-    tel = m.beamtransfer.telescope
-    npairs, nfeed = int(tel.npairs), int(tel.nfeed)
-    class_off, members = tel.redundant_pairs()
-    nmem = int(class_off[-1])
-    if ndays is None:
-        ndays = tel.ndays
-    ntime = _sim_ntime(tel, resolution)
-    nreal, first, nf = int(nreal), int(first), len(freqs)
-    if nf == 0 or nreal <= 0:
+    ctx, log, nf = get_context(), sim_log, len(freqs)
+    if nf == 0 or c.nreal <= 0:
         return
-    skymodels = (skymodels,) if isinstance(skymodels, str) else tuple(skymodels)
-    have_sky = len(maps) > 0 or len(skymodels) > 0 or len(_as_sources(sources)) > 0
-    gains = skysim.as_gains(gains)
-    if gains is not None and not isinstance(gains, skysim.GainModel):
-        skysim.check_explicit_gains(gains, nreal, nf, nfeed, ntime)
-    Rmax = min(BLOCKVEC_MAX_R, nreal)
-    per_freq = 16.0 * Rmax * ntime * (nmem + npairs + (3 * nfeed if gains is not None else 0))
-    nfc = int(min(nf, max(1, chunk_gb * 2.0**30 // per_freq)))
-    log = sim_log
+    per_freq = 16.0 * c.rmax * c.ntime * (c.nmem + c.npairs + (3 * c.nfeed if c.gains is not None else 0))
+    nfc = int(min(nf, max(1, c.chunk_gb * 2.0**30 // per_freq)))
     buf = None
     for f0 in range(0, nf, nfc):
         f1 = min(nf, f0 + nfc)
         fs = freqs[f0:f1]
-        sigma = ctx.to_device(_member_sigma(tel, fs, ndays, ntime, class_off)) if ndays > 0 else None
-        flagged = None
-        if weights is not None:
-            wf = weights[f0:f1] if np.ndim(weights) == 3 else weights
-            flagged = ctx.to_device(np.ascontiguousarray(wf == 0))
-        for r0, sky in _visibility_groups(m, nreal, maps, 0, resolution, seed, skymodels, klname, sky_seed, first, fs,
-                                          chunk_gb, sources=sources):
-            R = int(sky.shape[0])
-            if out is not None:
-                grp = out[r0 : r0 + R, f0:f1]
-            else:
-                if buf is None:
-                    buf = ctx.empty((Rmax, nfc, nmem, ntime), np.complex128)
-                grp = buf[:R, : f1 - f0]
-            noisy = sigma is not None
-            if noisy:
+        sigma = ctx.to_device(_sim_sigma(c, fs, members=True)) if noise and c.ndays > 0 else None
+        flagged = _sim_flagged(weights, f0, f1)
+        sky = _sim_sky(c, fs)
+        skybuf = None
+        for r0 in range(0, c.nreal, BLOCKVEC_MAX_R):
+            R = min(BLOCKVEC_MAX_R, c.nreal - r0)
+            if sky is not None:
+                if skybuf is None:
+                    skybuf = ctx.empty((c.rmax, f1 - f0, c.npairs, c.ntime), np.complex128)
+                _sim_group_sky(c, fs, sky, r0, skybuf[:R], False)
+            if out is None and buf is None:
+                buf = ctx.empty((c.rmax, nfc, c.nmem, c.ntime), np.complex128)
+            grp = buf[:R, : f1 - f0] if out is None else out[r0 : r0 + R, f0:f1]
+            if sigma is not None:
                 with _StepTimer(log, "noise"):
                     if grp.is_contiguous():
-                        ctx.ts_noise(sigma, fs, ntime, R, seed, first + r0, out=grp)
+                        ctx.ts_noise(sigma, fs, c.ntime, R, c.seed, c.first + r0, out=grp)
                     else:   # a frequency slice of the result: ts_noise writes contiguous arrays
-                        grp.copy_(ctx.ts_noise(sigma, fs, ntime, R, seed, first + r0))
+                        grp.copy_(ctx.ts_noise(sigma, fs, c.ntime, R, c.seed, c.first + r0))
             g = None
-            if gains is not None and (have_sky or want_gains):
+            if c.gains is not None and (sky is not None or want_gains):
                 with _StepTimer(log, "gains"):
-                    if isinstance(gains, skysim.GainModel):
-                        g = skysim.gains_device(gains, nfeed, fs, ntime, R, first + r0)
-                    else:
-                        g = skysim.explicit_gains(gains, nreal, nf, r0, R, range(f0, f1), nfeed, ntime)
-                        g = g.contiguous() if hasattr(g, "data_ptr") else ctx.to_device(np.ascontiguousarray(g))
+                    g = _sim_gain_chunk(c, freqs, f0, f1, r0, R)
             with _StepTimer(log, "expand"):
-                if have_sky:
-                    ctx.vis_expand(sky, class_off, members, g=g, out=grp, accumulate=noisy)
-                elif not noisy:
+                if sky is not None:
+                    ctx.vis_expand(skybuf[:R], c.class_off, c.members, g=g, out=grp, accumulate=sigma is not None)
+                elif sigma is None:
                     grp.zero_()
             if flagged is not None:
                 grp.masked_fill_(flagged, 0.0)
@@ -1862,12 +1877,51 @@ def _save_all(tss):
     parallel.barrier()
 
 
-def _unstacked_weights(tel, weights, freqs, ntime):
-    if weights is None:
-        return None
-    from . import skysim
+def _sim_filled(c, unstacked, weights=None, noise=True):
+    """The tensor (nreal, nf, npairs or nmem, ntime) of the run `c`, filled by the generator of its layout; `weights` as
+    given to the simulators."""
+    nrow = c.nmem if unstacked else c.npairs
+    weights = _sim_weights(c, weights, nrow)
+    out = get_context().empty((max(c.nreal, 0), len(c.freqs), nrow, c.ntime), np.complex128)
+    for _ in (_unstacked_chunks if unstacked else _visibility_groups)(c, c.freqs, out=out, weights=weights, noise=noise):
+        pass
+    return out
 
-    return skysim.as_weights(weights, len(freqs), int(tel.redundant_pairs()[0][-1]), ntime, freqs)
+
+def _sim_written(c, dirs, weights, unstacked):
+    """The realisations of the run `c` written to the Timestream directories `dirs` as they come off the device, one
+    device-to-host copy per group of realisations (and, unstacked, per chunk of frequencies); returns the Timestreams."""
+    ctx, freqs = get_context(), c.freqs
+    nrow, table = (c.nmem, (c.class_off, c.members)) if unstacked else (c.npairs, None)
+    weights = _sim_weights(c, weights, nrow)
+    weight_f = None if weights is None else np.broadcast_to(weights, (len(freqs), nrow, c.ntime))
+    tphi = np.linspace(0, 2 * np.pi, c.ntime, endpoint=False)
+    tss = [Timestream(d, c.m) for d in dirs]
+
+    def write(r0, f0, host, gh):   # host (R, nfc, nrow, ntime) from row f0 on, gh (1 or R, nfc, nfeed, ntime) or None
+        with _StepTimer(sim_log, "write"):
+            for r in range(host.shape[0]):
+                for k in range(host.shape[1]):
+                    _write_sim_file(tss[r0 + r], freqs[f0 + k], host[r, k], tphi,
+                                    gain=None if gh is None else gh[r if gh.shape[0] > 1 else 0, k],
+                                    weight=None if weight_f is None else weight_f[f0 + k], table=table)
+
+    if unstacked:
+        for r0, f0, grp, g in _unstacked_chunks(c, freqs, want_gains=c.gains is not None, weights=weights):
+            with _StepTimer(sim_log, "download"):
+                host = ctx.to_host(grp)
+                gh = None if g is None else ctx.to_host(g)
+            write(r0, f0, host, gh)
+    else:
+        chunks = []   # the gain chunks of a group in the order of their frequencies, on the host
+        sink = None if c.gains is None else lambda r0, f0, g: chunks.append(ctx.to_host(g))
+        for r0, grp in _visibility_groups(c, freqs, gain_sink=sink, weights=weights):
+            with _StepTimer(sim_log, "download"):
+                host = ctx.to_host(grp)
+            write(r0, 0, host, np.concatenate(chunks, axis=1) if chunks else None)
+            chunks.clear()
+    _save_all(tss)
+    return tss
 
 
 def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None, sky_seed=0,
@@ -1910,23 +1964,9 @@ def simulate_visibilities(m, nreal, maps=(), ndays=None, resolution=0, seed=0, s
     (`Context.vis_expand`), on noise of variance n_c ntime noisepower, so that the plain mean of a complete class has the
     noise of the stacked result.  `weights` then has nmem rows.  The work goes in chunks of frequencies that fit in
     `chunk_gb`.  unstacked=False: none of this runs."""
-    ctx = get_context()
-    tel = m.beamtransfer.telescope
-    freqs = _sim_freqs(tel, freqs)
-    if unstacked:
-        ntime = _sim_ntime(tel, resolution)
-        weights = _unstacked_weights(tel, weights, freqs, ntime)
-        out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.redundant_pairs()[0][-1]), ntime), np.complex128)
-        for _ in _unstacked_chunks(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                   chunk_gb, out=out, sources=sources, gains=gains, weights=weights):
-            pass
-        return out
-    weights = _sim_weights(tel, weights, freqs, _sim_ntime(tel, resolution))
-    out = ctx.empty((max(int(nreal), 0), len(freqs), int(tel.npairs), _sim_ntime(tel, resolution)), np.complex128)
-    for _ in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                chunk_gb, out=out, sources=sources, gains=gains, weights=weights):
-        pass
-    return out
+    c = _sim_conf(m, freqs, resolution, ndays, nreal=nreal, first=first, seed=seed, sky_seed=sky_seed, klname=klname, maps=maps,
+                  skymodels=skymodels, sources=sources, gains=gains, chunk_gb=chunk_gb)
+    return _sim_filled(c, unstacked, weights)
 
 
 def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=0, skymodels=(), klname=None,
@@ -1954,55 +1994,10 @@ def simulate_ensemble(m, outdir, nreal, maps=(), ndays=None, resolution=0, seed=
     `class_off`, `weight` (nmem, ntime) when weights were given, and everything else as above (`gain` included: what
     `stack_baselines(calibrate="file")` undoes).  Such a directory goes through `stack_baselines` before the m-modes.
     """
-    ctx = get_context()
-    bt = m.beamtransfer
-    tel = bt.telescope
-    freqs = _sim_freqs(tel, freqs)
-    ntime = _sim_ntime(tel, resolution)
-    nreal, first = int(nreal), int(first)
-    if unstacked:
-        return _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed,
-                                            first, freqs, chunk_gb, sources, gains, weights)
-    weights = _sim_weights(tel, weights, freqs, ntime)
-    weight_f = None if weights is None else np.broadcast_to(weights, (len(freqs), int(tel.npairs), ntime))
-    tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
-    tss = [Timestream(os.path.join(outdir, "real_%04d" % (first + i)), m) for i in range(max(nreal, 0))]
-    gain_host = {}
-
-    def gain_sink(r0, f0, g):
-        gain_host[f0] = ctx.to_host(g)
-
-    for r0, grp in _visibility_groups(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first, freqs,
-                                      chunk_gb, sources=sources, gains=gains,
-                                      gain_sink=gain_sink if gains is not None else None, weights=weights):
-        with _StepTimer(sim_log, "download"):
-            host = ctx.to_host(grp)
-        gain_at = {}
-        for f0, gh in gain_host.items():
-            for k in range(gh.shape[1]):
-                gain_at[f0 + k] = gh[:, k]                      # (1 or R, nfeed, ntime)
-        gain_host.clear()
-        with _StepTimer(sim_log, "write"):
-            for r in range(host.shape[0]):
-                tstream = tss[r0 + r]
-                for lfi, fi in enumerate(freqs):
-                    os.makedirs(tstream._fdir(fi), exist_ok=True)
-                    with storage.File(tstream._ffile(fi), "w") as f:
-                        f.create_dataset("timestream", data=np.ascontiguousarray(host[r, lfi]))
-                        f.create_dataset("phi", data=tphi)
-                        if lfi in gain_at:
-                            f.create_dataset("gain", data=np.ascontiguousarray(gain_at[lfi][r if gain_at[lfi].shape[0] > 1 else 0]))
-                        if weight_f is not None:
-                            f.create_dataset("weight", data=np.ascontiguousarray(weight_f[lfi]))
-                        f.create_dataset("feedmap", data=np.asarray(tel.feedmap))
-                        f.create_dataset("feedconj", data=np.asarray(tel.feedconj))
-                        f.create_dataset("feedmask", data=np.asarray(tel.feedmask))
-                        f.create_dataset("uniquepairs", data=np.asarray(tel.uniquepairs))
-                        f.create_dataset("baselines", data=np.asarray(tel.baselines))
-                        f.attrs["beamtransfer_path"] = os.path.abspath(bt.directory)
-                        f.attrs["ntime"] = ntime
-    _save_all(tss)
-    return tss
+    c = _sim_conf(m, freqs, resolution, ndays, nreal=nreal, first=first, seed=seed, sky_seed=sky_seed, klname=klname, maps=maps,
+                  skymodels=skymodels, sources=sources, gains=gains, chunk_gb=chunk_gb)
+    dirs = [os.path.join(outdir, "real_%04d" % (c.first + i)) for i in range(max(c.nreal, 0))]
+    return _sim_written(c, dirs, weights, unstacked)
 
 
 def simulate_unstacked(m, outdir, maps=(), ndays=None, resolution=0, seed=None, skymodels=(), klname=None, sky_seed=0,
@@ -2011,41 +2006,10 @@ def simulate_unstacked(m, outdir, maps=(), ndays=None, resolution=0, seed=None, 
     `simulate_ensemble(unstacked=True)`, written straight into `outdir` (what a `simulate:` block with
     `unstacked: true` of the pipeline runs; seed=None is seed 0, the draws being counter based).  Returns the
     Timestream."""
-    tel = m.beamtransfer.telescope
-    return _simulate_ensemble_unstacked(m, None, 1, maps, ndays, resolution, 0 if seed is None else seed, skymodels, klname,
-                                        sky_seed, int(sky_realisation), _sim_freqs(tel, None), chunk_gb, sources, gains,
-                                        weights, dirs=[outdir])[0]
-
-
-def _simulate_ensemble_unstacked(m, outdir, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first,
-                                 freqs, chunk_gb, sources, gains, weights, dirs=None):
-    """`simulate_ensemble(unstacked=True)`: the chunks of `_unstacked_chunks` written as they come, one device-to-host
-    copy per chunk (a group of realisations times a chunk of frequencies)."""
-    ctx = get_context()
-    tel = m.beamtransfer.telescope
-    ntime = _sim_ntime(tel, resolution)
-    table = tel.redundant_pairs()
-    nmem = int(table[0][-1])
-    weights = _unstacked_weights(tel, weights, freqs, ntime)
-    weight_f = None if weights is None else np.broadcast_to(weights, (len(freqs), nmem, ntime))
-    tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
-    if dirs is None:
-        dirs = [os.path.join(outdir, "real_%04d" % (first + i)) for i in range(max(nreal, 0))]
-    tss = [Timestream(d, m) for d in dirs]
-    for r0, f0, grp, g in _unstacked_chunks(m, nreal, maps, ndays, resolution, seed, skymodels, klname, sky_seed, first,
-                                            freqs, chunk_gb, sources=sources, gains=gains, want_gains=gains is not None,
-                                            weights=weights):
-        with _StepTimer(sim_log, "download"):
-            host = ctx.to_host(grp)
-            gh = None if g is None else ctx.to_host(g)           # (1 or R, nfc, nfeed, ntime)
-        with _StepTimer(sim_log, "write"):
-            for r in range(host.shape[0]):
-                for k in range(host.shape[1]):
-                    _write_sim_file(tss[r0 + r], freqs[f0 + k], host[r, k], tphi,
-                                    gain=None if gh is None else gh[r if gh.shape[0] > 1 else 0, k],
-                                    weight=None if weight_f is None else weight_f[f0 + k], table=table)
-    _save_all(tss)
-    return tss
+    c = _sim_conf(m, None, resolution, ndays, nreal=1, first=sky_realisation, seed=0 if seed is None else seed,
+                  sky_seed=sky_seed, klname=klname, maps=maps, skymodels=skymodels, sources=sources, gains=gains,
+                  chunk_gb=chunk_gb)
+    return _sim_written(c, [outdir], weights, True)[0]
 
 
 REDCAL_DEFAULTS = dict(damping=0.4, tol=1e-10, maxiter=500, reference=None)
@@ -2656,6 +2620,18 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
     return dst
 
 
+def _day_weights(weights, d):
+    """The `weights` of `simulate_days` for day d: the d-th of a list, and a FlagModel (or its dict) with seed + d."""
+    from . import skysim
+
+    wd = weights[d] if isinstance(weights, (list, tuple)) else weights
+    if isinstance(wd, dict):
+        wd = skysim.FlagModel.from_config(wd)
+    if isinstance(wd, skysim.FlagModel):
+        wd = skysim.FlagModel(wd.fraction, wd.burst, wd.windows, wd.seed + d)
+    return wd
+
+
 def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, resolution=0, seed=0, skymodels=(),
                   klname=None, sky_seed=0, first=0, freqs=None, chunk_gb=4.0, sources=(), gains=None, weights=None,
                   unstacked=False, rfi=None):
@@ -2677,8 +2653,9 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
 
     ctx = get_context()
     torch = ctx.torch
-    tel = m.beamtransfer.telescope
-    freqs = _sim_freqs(tel, freqs)
+    c = _sim_conf(m, freqs, resolution, ndays, default_ndays=1, nreal=1, first=first, seed=seed, sky_seed=sky_seed,
+                  klname=klname, maps=maps, skymodels=skymodels, sources=sources, gains=gains, chunk_gb=chunk_gb)
+    freqs, ntime, ndays = c.freqs, c.ntime, c.ndays
     outdirs = list(outdirs)
     nd = len(outdirs)
     starts = [float(v) for v in starts]
@@ -2688,21 +2665,8 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
     dphi = 2.0 * np.pi * float(cadence) / T_SIDEREAL_DAY
     if not (dphi > 0 and all(n >= 2 and (n - 1) * dphi < 2 * np.pi for n in nsamples)):
         raise ValueError("simulate_days: a day holds two samples at the least and covers less than one turn")
-    if ndays is None:
-        ndays = 1
-    ntime = _sim_ntime(tel, resolution)
-    table = tel.redundant_pairs() if unstacked else None
-    nrow = int(table[0][-1]) if unstacked else int(tel.npairs)
-    if unstacked:
-        grid = ctx.empty((1, len(freqs), nrow, ntime), np.complex128)
-        for _ in _unstacked_chunks(m, 1, maps, 0, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
-                                   out=grid, sources=sources, gains=gains):
-            pass
-    else:
-        grid = ctx.empty((1, len(freqs), nrow, ntime), np.complex128)
-        for _ in _visibility_groups(m, 1, maps, 0, resolution, seed, skymodels, klname, sky_seed, first, freqs, chunk_gb,
-                                    out=grid, sources=sources, gains=gains):
-            pass
+    nrow, table = (c.nmem, (c.class_off, c.members)) if unstacked else (c.npairs, None)
+    grid = _sim_filled(c, unstacked, noise=False)
     tss = [Timestream(d, m) for d in outdirs]
     if len(freqs):
         modes = torch.fft.fft(grid[0], dim=-1) / ntime                                  # (nf, nrow, ntime)
@@ -2713,14 +2677,7 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
         if isinstance(rfi, dict):
             rfi = skysim.RFIModel.from_config(rfi)
         if ndays > 0 or rfi is not None:
-            per_turn = 2.0 * np.pi / dphi
-            if unstacked:
-                sigma = _member_sigma(tel, freqs, 1, per_turn, table[0])
-            else:
-                sigma = np.sqrt(per_turn * np.asarray(tel.noisepower(np.arange(nrow)[np.newaxis, :],
-                                                                      np.array(freqs)[:, np.newaxis], ndays=1),
-                                                       dtype=np.float64).reshape(len(freqs), nrow))
-            sigma = ctx.to_device(sigma)
+            sigma = ctx.to_device(_sim_sigma(c, freqs, members=unstacked, ndays=1, ntime=2.0 * np.pi / dphi))
         for d in range(nd):
             n = nsamples[d]
             phi = starts[d] + dphi * np.arange(n)
@@ -2731,14 +2688,9 @@ def simulate_days(m, outdirs, starts, nsamples, cadence, maps=(), ndays=None, re
             if rfi is not None:
                 rd = skysim.RFIModel(rfi.fraction, rfi.burst, rfi.amplitude, rfi.seed + d)
                 day.add_(ctx.to_device(rd.bursts(n, freqs, nrow)) * sigma[:, :, None])
-            wd = weights[d] if isinstance(weights, (list, tuple)) else weights
-            if isinstance(wd, dict):
-                wd = skysim.FlagModel.from_config(wd)
-            if isinstance(wd, skysim.FlagModel):
-                wd = skysim.FlagModel(wd.fraction, wd.burst, wd.windows, wd.seed + d)
-            wh = None
-            if wd is not None:
-                wh = np.broadcast_to(skysim.as_weights(wd, len(freqs), nrow, n, freqs), (len(freqs), nrow, n))
+            wh = _sim_weights(c, _day_weights(weights, d), nrow, n)
+            if wh is not None:
+                wh = np.broadcast_to(wh, (len(freqs), nrow, n))
                 day.masked_fill_(ctx.to_device(np.ascontiguousarray(wh == 0)), 0.0)
             host = ctx.to_host(day)
             del day, E

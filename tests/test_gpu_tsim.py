@@ -376,3 +376,52 @@ def test_sky_and_noise_split_by_frequency(prod, skyfile):
     resid = np.abs((full - noise) - ctx.to_host(sky))
     assert np.all(resid <= bound + 4 * EPS * (np.abs(full) + np.abs(noise)))
     assert np.abs(ctx.to_host(sky)).max() > 0
+
+
+def test_ensemble_files_are_the_visibilities_with_everything_on(prod, skyfile):
+    """`simulate_ensemble` writes what `simulate_visibilities` returns with every option at once: maps and a model, noise,
+    a GainModel, weights with zeros and 9 realisations (one more than BLOCKVEC_MAX_R, so a second group reuses the
+    ensemble's one buffer), stacked and unstacked, the latter also in chunks of one frequency.  Bit for bit: two
+    identical calls agreed in every bit, sky part included, in three runs of the commit before the simulators were
+    staged, so equality is what is asserted, not the synthesis bound of `test_sky_and_noise_split_by_frequency`."""
+    from driftscan_amd import _lib, skysim, storage, timestream
+
+    pm, d = prod
+    tel = pm.telescope
+    ctx = _ctx()
+    nreal, nf, nfeed, ntime, first = _lib.BLOCKVEC_MAX_R + 1, tel.nfreq, tel.nfeed, 2 * tel.mmax + 1, 1
+    class_off, members = tel.redundant_pairs()
+    rng = np.random.default_rng(17)
+    gains = skysim.GainModel(sigma_amp=0.05, sigma_phase=0.05, corr_time=3600.0, seed=2)
+    kw = dict(maps=[skyfile], skymodels=("signal",), ndays=10, seed=5, sky_seed=3, first=first, gains=gains)
+    ref = timestream.simulate(pm, str(d / "all_ref"), maps=[skyfile], gains=gains, ndays=10, seed=1,
+                              weights=np.ones((nf, tel.npairs, ntime)))
+    with storage.File(ref._ffile(0), "r") as f:
+        names = set(f.keys())
+    assert {"timestream", "phi", "gain", "weight"} <= names
+    for tag, extra in (("stacked", {}), ("unstacked", dict(unstacked=True)),
+                       ("unstacked_chunks", dict(unstacked=True, chunk_gb=1e-9))):
+        nrow = int(class_off[-1]) if extra else tel.npairs
+        w = (rng.uniform(size=(nf, nrow, ntime)) > 0.2) * rng.uniform(0.5, 2.0, size=(nf, nrow, ntime))
+        assert (w == 0).any()
+        X = ctx.to_host(timestream.simulate_visibilities(pm, nreal, weights=w, **kw, **extra))
+        assert X.shape == (nreal, nf, nrow, ntime) and not X[w[None].repeat(nreal, 0) == 0].any()
+        tss = timestream.simulate_ensemble(pm, str(d / ("all_" + tag)), nreal, weights=w, **kw, **extra)
+        assert len(tss) == nreal
+        worst = 0.0
+        for i, ts in enumerate(tss):
+            assert ts.directory.endswith("real_%04d" % (first + i)) and ts.is_unstacked() == bool(extra)
+            for fi in range(nf):
+                with storage.File(ts._ffile(fi), "r") as f:
+                    v = f["timestream"][:]
+                    worst = max(worst, float(np.abs(v - X[i, fi]).max()))
+                    assert np.array_equal(v, X[i, fi]), (tag, i, fi)
+                    assert np.array_equal(f["weight"][:], w[fi])
+                    assert f["gain"].shape == (nfeed, ntime) and f["gain"].dtype == np.complex128
+                    assert int(f.attrs["ntime"]) == ntime
+                    if extra:
+                        assert set(f.keys()) == names | {"class_off", "members"} and int(f.attrs["unstacked"]) == 1
+                        assert np.array_equal(f["class_off"][:], class_off) and np.array_equal(f["members"][:], members)
+                    else:
+                        assert set(f.keys()) == names and "unstacked" not in f.attrs
+        print("ensemble files vs simulate_visibilities (%s): max |delta| = %.3g" % (tag, worst))
