@@ -226,6 +226,12 @@ SIGNATURES = {
         c_int, [c_vp, c_int, c_int, c_int, c_int, c_dbl, c_int, ctypes.POINTER(c_int), c_dbl, c_dbl, c_int, c_dbl, c_int,
                 c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dm_rfi_max_segment": (c_int, []),
+    "dm_rfi_flag_freq": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_dbl, c_int, ctypes.POINTER(c_int), c_dbl, c_dbl, c_int, c_dbl, c_int,
+                c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dm_rfi_freq_tile": (c_int, [c_int]),
+    "dm_rfi_dilate": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
+    "dm_rfi_dilate_max_length": (c_int, [c_int]),
 }
 
 _lib = None
@@ -1179,6 +1185,83 @@ def _rfi_flag(self, x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4,
 
 
 Context.rfi_flag = _rfi_flag
+
+
+def _rfi_flag_freq(self, x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4, 8, 16), chi1=6.0, rho=1.5, niter=3,
+                   base=2.0, min_good=16, row_share=1.0, out=None):
+    """RFI flags along frequency (dm_rfi_flag_freq; `timestream.rfi_flag_freq_host` restates it):
+    the method and the parameters of `rfi_flag` on the series x[:, row, j], with nf in the place of nt.  x (nf, nrow, nt)
+    complex128, contiguous; w float64 of that shape or None.  Returns (w_out, noise, nflag, occupancy): w_out
+    (nf, nrow, nt) float64; noise (nseg, nrow, nt) float64, nseg = ceil(nf / segment); nflag (nrow, nt) int32, the new
+    flags of every series; occupancy (nf, nt) int32 — bit for bit what `rfi_flag` returns for the data transposed to
+    (nt, nrow, nf), transposed back.  `out` takes that tuple of tensors to write into; its w_out may be w itself."""
+    torch = self.torch
+    if not (_is_c128(x) and x.dim() == 3):
+        raise ValueError("rfi_flag_freq: contiguous complex128 tensor x (nf, nrow, nt) expected")
+    nf, nrow, nt = (int(v) for v in x.shape)
+    if w is not None:
+        _weights_arg("rfi_flag_freq", w, x.shape)
+    segment = int(segment)
+    if segment < 1:
+        raise ValueError("rfi_flag_freq: segment < 1")
+    windows = [int(v) for v in windows]
+    nseg = -(-nf // segment)
+    shapes = ((nf, nrow, nt), (nseg, nrow, nt), (nrow, nt), (nf, nt))
+    dtypes = (torch.float64, torch.float64, torch.int32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 4 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
+                                    for o, s, d in zip(out, shapes, dtypes)):
+            raise ValueError("rfi_flag_freq: out must hold contiguous tensors w_out (nf, nrow, nt) float64, noise "
+                             "(nseg, nrow, nt) float64, nflag (nrow, nt) int32 and occupancy (nf, nt) int32")
+    win = (c_int * max(len(windows), 1))(*windows)
+    rc = self.lib.dm_rfi_flag_freq(self.h, nf, nrow, nt, segment, float(kernel_sigma), len(windows), win, float(chi1),
+                                   float(rho), int(niter), float(base), int(min_good), float(row_share), self.ptr(x),
+                                   self.ptr(w), self.ptr(out[0]), self.ptr(out[1]), self.ptr(out[2]), self.ptr(out[3]))
+    self.check(rc, "dm_rfi_flag_freq")
+    return out
+
+
+Context.rfi_flag_freq = _rfi_flag_freq
+
+RFI_AXES = {"time": 0, "freq": 1}
+
+
+def _rfi_dilate(self, w, eta, axis="time", ref=None, out=None):
+    """Dilate the flags of w (nf, nrow, nt) float64 along `axis`, "time" or "freq", by the scale-invariant rank operator
+    in exact integers (dm_rfi_dilate; `timestream.rfi_dilate_host` restates it): a sample is
+    flagged when some window of its series that holds it has at least the share rint((1 - eta) 65536) / 65536 of its
+    samples flagged.  eta in [0, 1); 0 changes nothing.  ref, of the shape of w or None: the samples where `ref > 0` is
+    false are missing — they stay as they are and count neither as flags nor as length.  Returns (w_out, nadded): w_out is
+    w where kept and 0 where newly flagged; nadded int32, the new flags of every series, (nf, nrow) along time and
+    (nrow, nt) along frequency.  `out` takes that tuple of tensors to write into; its w_out may be w itself."""
+    torch = self.torch
+    if axis not in RFI_AXES:
+        raise ValueError('rfi_dilate: axis is "time" or "freq"')
+    if not (hasattr(w, "data_ptr") and w.dim() == 3 and w.dtype == torch.float64 and w.is_contiguous()):
+        raise ValueError("rfi_dilate: contiguous float64 tensor w (nf, nrow, nt) expected")
+    nf, nrow, nt = (int(v) for v in w.shape)
+    if ref is not None:
+        _weights_arg("rfi_dilate", ref, w.shape)
+    shapes = ((nf, nrow, nt), (nf, nrow) if axis == "time" else (nrow, nt))
+    dtypes = (torch.float64, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=w.device) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 2 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
+                                    for o, s, d in zip(out, shapes, dtypes)):
+            raise ValueError("rfi_dilate: out must hold contiguous tensors w_out (nf, nrow, nt) float64 and nadded int32, "
+                             "(nf, nrow) along time or (nrow, nt) along frequency")
+    rc = self.lib.dm_rfi_dilate(self.h, nf, nrow, nt, RFI_AXES[axis], float(eta), self.ptr(w), self.ptr(ref),
+                                self.ptr(out[0]), self.ptr(out[1]))
+    self.check(rc, "dm_rfi_dilate")
+    return out
+
+
+Context.rfi_dilate = _rfi_dilate
 
 
 def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,

@@ -124,9 +124,18 @@ class PipelineManager(config.Reader):
 
     @staticmethod
     def _check_rfi(conf):
-        """The `rfi` dict of a `stack_from` or `sidereal_from` block, defaults filled in; an unknown key raises ValueError."""
-        if conf.get("rfi") is not None:
-            conf["rfi"] = timestream.rfi_params(conf["rfi"])
+        """The `rfi`, `rfi_freq` and `rfi_dilate` dicts of a `stack_from` or `sidereal_from` block, defaults filled in; an
+        unknown key raises ValueError."""
+        for key in ("rfi", "rfi_freq"):
+            if conf.get(key) is not None:
+                conf[key] = timestream.rfi_params(conf[key])
+        if conf.get("rfi_dilate") is not None:
+            conf["rfi_dilate"] = timestream.rfi_dilate_params(conf["rfi_dilate"])
+
+    @staticmethod
+    def _rfi_more(conf):
+        """The `rfi_freq` and `rfi_dilate` keywords of a block, only when present."""
+        return {key: conf[key] for key in ("rfi_freq", "rfi_dilate") if conf.get(key) is not None}
 
     def _products(self, directory):
         """The ProductManager of a product directory (opened once per directory: its objects hold caches and device
@@ -178,9 +187,9 @@ class PipelineManager(config.Reader):
                                        dead_feeds=tuple(conf.get("dead_feeds", ()) or ()), chunk_gb=self.chunk_gb,
                                        **({"redcal": dict(conf["redcal"])} if conf.get("redcal") else {}),
                                        **({"modelcal": self._modelcal(conf["modelcal"])} if conf.get("modelcal") else {}),
-                                       **({"rfi": conf["rfi"]} if conf.get("rfi") is not None else {}))
-        # `sidereal_from: {days: [dir, ...], a: 3, min_share: 1.0, rfi: {...}}`: the days, which may be the stacks made above, are
-        # regridded and averaged by `timestream.sidereal_stack`
+                                       **({"rfi": conf["rfi"]} if conf.get("rfi") is not None else {}), **self._rfi_more(conf))
+        # `sidereal_from: {days: [dir, ...], a: 3, min_share: 1.0, rfi: {...}, rfi_freq: {...}, rfi_dilate: {...}}`: the days,
+        # which may be the stacks made above, are regridded and averaged by `timestream.sidereal_stack`
         for tsname, conf in self.sidereal.items():
             ts = self.timestreams[tsname]
             if os.path.exists(ts.directory):
@@ -189,7 +198,7 @@ class PipelineManager(config.Reader):
             timestream.sidereal_stack(ts.manager, [fixpath(d) for d in conf["days"]], ts.directory,
                                       ntime=conf.get("ntime", None), a=int(conf.get("a", 3)),
                                       min_share=float(conf.get("min_share", 1.0)), chunk_gb=self.chunk_gb,
-                                      rfi=conf.get("rfi", None))
+                                      rfi=conf.get("rfi", None), **self._rfi_more(conf))
 
     def generate(self):
         """Run the stages that are switched on, for every timestream, in the reference's order: m-modes and SVD modes, KL

@@ -2133,15 +2133,16 @@ def _feed_weights(feed_weight, dead_feeds, nfeed):
     return fw
 
 
-def _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelcal):
+def _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelcal, rfi_freq=None, rfi_dilate=None):
     """The arguments of `stack_baselines` checked once and its modes resolved.  Fields: the class table (class_off,
     members) and nmem, npairs, nfeed, nfreq, ntime; phi, the sample positions of `src`; rfi, the flagger's parameters or
-    None; redundant, by_model, ref_model: which solvers run and what the model's gains are for; redcal, the redundant
+    None; flagging, the steps of `_rfi_route`; redundant, by_model, ref_model: which solvers run and what the model's gains are for; redcal, the redundant
     solver's keywords; bases, its degeneracies; modelcal, the namespace of `_modelcal_conf`, or None; calibrated: the
     stack takes gains; file_gain: the files' `gain` is read, and under which name its absence is refused; given_gain: an
     array (nfreq, nfeed, ntime) handed over — both are the reference on the redundant route and the stack's gains
     otherwise; fw, the feed weights or None; weighted: the chunks carry per-sample weights."""
     c = SimpleNamespace(rfi=None if rfi is None else rfi_params(rfi))
+    c.flagging = _rfi_route(rfi, rfi_freq, rfi_dilate)
     tel = m.beamtransfer.telescope
     if not src.is_unstacked():
         raise ValueError("%s does not hold unstacked visibilities" % src.directory)
@@ -2169,7 +2170,7 @@ def _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelca
     c.fw = _feed_weights(feed_weight, dead_feeds, c.nfeed)
     c.bases = redcal_degeneracies(c.class_off, c.members, c.nfeed, c.fw) if c.redundant else None
     with storage.File(src._ffile(0), "r") as f:
-        c.weighted = "weight" in f or c.rfi is not None
+        c.weighted = "weight" in f or c.flagging.any
     return c
 
 
@@ -2177,6 +2178,8 @@ def _stack_per_f(c):
     """Bytes one frequency of a chunk of `stack_baselines` takes, on the host and on the device."""
     per_f = c.ntime * (16.0 * c.nmem + (8.0 * c.nmem if c.weighted else 0.0) + (16.0 * c.nfeed if c.calibrated else 0.0)
                        + 24.0 * c.npairs)
+    if c.flagging.freq is not None or c.flagging.dilate is not None:   # the weights between the steps
+        per_f += c.ntime * 16.0 * c.nmem
     if c.redundant:   # g, the second gain buffer and y of the solver, its three per-sample outputs and its state words
         per_f += c.ntime * (32.0 * c.nfeed + 16.0 * c.npairs + 20.0 + 24.0)
     if c.modelcal is not None:   # the model and its device copy, the solver's three gain buffers and gweight, its words
@@ -2214,10 +2217,11 @@ def _stack_on_device(ctx, chunk):
     return chunk.vis_d, chunk.w_d
 
 
-def _stack_flag(ctx, chunk, rfi_p):
-    """The RFI pass over a chunk: its weights with the flagged samples at 0, on the host."""
+def _stack_flag(ctx, chunk, route):
+    """The RFI steps over a chunk (DESIGN.md sections 4.20 and 4.22): its weights with the flagged samples at 0, on the
+    host."""
     x_d = ctx.to_device(np.stack(chunk.vis))
-    return list(ctx.to_host(ctx.rfi_flag(x_d, w=ctx.to_device(np.stack(chunk.w)), **rfi_p)[0]))
+    return list(ctx.to_host(_rfi_steps(ctx, x_d, ctx.to_device(np.stack(chunk.w)), route)[0]))
 
 
 def _stack_model_solve(ctx, chunk, c):
@@ -2300,7 +2304,7 @@ def _stack_report(c, nfreq, lost, minvalid, mblind, log):
 
 
 def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None, rfi=None,
-                    modelcal=None):
+                    modelcal=None, rfi_freq=None, rfi_dilate=None):
     """Stack the unstacked Timestream directory `indir` (`simulate_ensemble(unstacked=True)`, or a correlator's per-pair
     data in that layout) into the unique baselines of the telescope of ProductManager `m` and write them to `outdir` in
     the layout of `simulate_ensemble`; returns the `Timestream` of `outdir`.
@@ -2343,19 +2347,24 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
 
     rfi: a dict of the parameters of `Context.rfi_flag` (an unknown key raises ValueError).  The feed-pair data of every
     frequency is then flagged on the device before anything is solved or summed, and the flags
-    go on as weights 0 of the members, as the file's own flags do."""
+    go on as weights 0 of the members, as the file's own flags do.  rfi_freq: a dict of the same keys for the pass along
+    frequency (`Context.rfi_flag_freq`), run on the weights of the time pass; rfi_dilate: a dict of `rfi_dilate_params`,
+    the dilation of the flags along time, then along frequency.  A step along frequency needs
+    every frequency on one device: the one chunk is then all frequencies, and a `chunk_gb` that does not hold them, or
+    more than one rank, raises ValueError."""
     src = Timestream(indir, m)
-    c = _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelcal)
-    ctx = get_context()
+    c = _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelcal, rfi_freq, rfi_dilate)
     freqs = _sim_freqs(m.beamtransfer.telescope, None)
+    chunks = _rfi_chunks("stack_baselines", freqs, chunk_gb, _stack_per_f(c), c.flagging)
+    ctx = get_context()
     log = sim_log
     records, lost, minvalid, mblind = {}, 0, 0, 0
-    for fs in _freq_chunks(freqs, chunk_gb, _stack_per_f(c)):
+    for fs in chunks:
         with _StepTimer(log, "read"):
             chunk = _stack_read(src, fs, c)
-        if c.rfi is not None:
+        if c.flagging.any:
             with _StepTimer(log, "rfi"):
-                chunk.w = _stack_flag(ctx, chunk, c.rfi)
+                chunk.w = _stack_flag(ctx, chunk, c.flagging)
         g, datasets, failed = chunk.g, [{} for _ in fs], None
         if c.modelcal is not None:
             with _StepTimer(log, "modelcal"):
@@ -2529,7 +2538,8 @@ def _day_phi(tstream):
     return float(phi[0]), float(dphi), n
 
 
-def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=4.0, rfi=None):
+def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=4.0, rfi=None, rfi_freq=None,
+                   rfi_dilate=None):
     """Regrid the days `daydirs` onto the sidereal grid and average them with their weights.
     Every entry is a Timestream directory, stacked or unstacked, all of one row layout (and one class table): a stretch
     of samples at the positions of its dataset `phi` (uniformly spaced after unwrapping, else ValueError), with `weight`
@@ -2542,10 +2552,12 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
     when there is more than one day, and the attribute `ndays`.  ntime=None: `_sim_ntime(tel, 0)`.  rfi: a dict of the parameters of
     `Context.rfi_flag` (an empty one: the defaults; an unknown key raises ValueError): every day is then flagged on the
     device between the read and the regridding, its weights are the day's own with the flagged
-    samples at 0, and nothing is written for the days.  Returns the Timestream of `outdir`."""
-    rfi_p = None if rfi is None else rfi_params(rfi)
-    ctx = get_context()
-    torch = ctx.torch
+    samples at 0, and nothing is written for the days.  rfi_freq: a dict of the same keys for the pass along frequency
+    (`Context.rfi_flag_freq`), which runs on the weights of the time pass; rfi_dilate: a dict of `rfi_dilate_params`, the
+    dilation of the flags along time, then along frequency.  A step along frequency needs every
+    frequency of a day on one device: the one chunk is then all frequencies, and a `chunk_gb` that does not hold them, or
+    more than one rank, raises ValueError.  Returns the Timestream of `outdir`."""
+    route = _rfi_route(rfi, rfi_freq, rfi_dilate)
     tel = m.beamtransfer.telescope
     daydirs = list(daydirs)
     if not daydirs:
@@ -2569,12 +2581,16 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
         nrow = int(f["timestream"].shape[0])
     freqs = _sim_freqs(tel, None)
     nt_max = max(g[2] for g in geo)
-    per_f = nrow * ((24.0 if rfi is None else 32.0) * nt_max + 36.0 * ntime + 16.0 * ntime)
+    extra_steps = route.freq is not None or route.dilate is not None
+    per_f = nrow * ((48.0 if extra_steps else 24.0 if rfi is None else 32.0) * nt_max + 36.0 * ntime + 16.0 * ntime)
     log = sim_log
     dst = Timestream(outdir, m)
     tphi = np.linspace(0, 2 * np.pi, ntime, endpoint=False)
     nd = len(days)
-    for fs in _freq_chunks(freqs, chunk_gb, per_f):
+    chunks = _rfi_chunks("sidereal_stack", freqs, chunk_gb, per_f, route)
+    ctx = get_context()
+    torch = ctx.torch
+    for fs in chunks:
         acc = None
         for d, (phi0, dphi, nt_in) in zip(days, geo):
             with _StepTimer(log, "read"):
@@ -2592,8 +2608,8 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
             with _StepTimer(log, "regrid"):
                 x_d = ctx.to_device(np.stack(xs))
                 w_d = ctx.to_device(np.stack(ws)) if weighted else None
-                if rfi_p is not None:
-                    w_d = ctx.rfi_flag(x_d, w=w_d, **rfi_p)[0]
+                if route.any:
+                    w_d = _rfi_steps(ctx, x_d, w_d, route)[0]
                 acc = ctx.sidereal_regrid(x_d, phi0, dphi, ntime, w=w_d, a=a, min_share=min_share, acc=acc)
                 del x_d, w_d
         with _StepTimer(log, "finish"):
@@ -2860,16 +2876,146 @@ def rfi_flag_host(x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4, 8
     return w_out, noise, nflag, occupancy
 
 
-def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, **params):
+# ---- RFI flagging along frequency and the dilation of flags -------------------------------
+RFI_DILATE_DEFAULTS = dict(time=0.0, freq=0.0, new_only=True)
+RFI_DILATE_ONE = 65536   # shares of flagged samples are compared in units of 1 / 65536
+
+
+def rfi_flag_freq_host(x, w=None, dtype=np.float64, details=False, **params):
+    """The numpy statement of `Context.rfi_flag_freq`: `rfi_flag_host` on the data transposed
+    to (nt, nrow, nf), and its answer transposed back: (w_out (nf, nrow, nt), noise (nseg, nrow, nt), nflag (nrow, nt),
+    occupancy (nf, nt)), and with details=True the dict of `rfi_flag_host` with eps, margin and decided
+    (nseg, nrow, nt) and row_flags (nf, nrow, nt)."""
+    x = np.asarray(x)
+    if x.ndim != 3:
+        raise ValueError("rfi_flag_freq_host: x (nf, nrow, nt) expected")
+    back = lambda a: np.ascontiguousarray(np.transpose(a))   # reverses the axes
+    out = rfi_flag_host(back(x), None if w is None else back(np.asarray(w)), dtype=dtype, details=details, **params)
+    res = tuple(back(a) for a in out[:4])
+    return res + ({k: back(v) for k, v in out[4].items()},) if details else res
+
+
+def rfi_dilate_kappa(eta):
+    """kappa = rint((1 - eta) 65536), the share of flagged samples a window needs, in units of 1 / 65536; ValueError for
+    an eta that is not finite, outside [0, 1) or so close to 1 that kappa < 1."""
+    eta = float(eta)
+    if not (np.isfinite(eta) and 0.0 <= eta < 1.0):
+        raise ValueError("rfi_dilate: eta not finite or outside [0, 1)")
+    kappa = int(np.rint((1.0 - eta) * float(RFI_DILATE_ONE)))
+    if kappa < 1:
+        raise ValueError("rfi_dilate: kappa = rint((1 - eta) 65536) < 1")
+    return kappa
+
+
+def rfi_dilate_host(w, eta, axis="time", ref=None):
+    """The numpy statement of `Context.rfi_dilate`, in the two-scan form: w (nf, nrow, nt); on
+    every series along `axis` ("time" or "freq") F = the samples where `w > 0` is false, I = those where `ref > 0` is
+    false (none without ref), psi = 0 on I, 65536 - kappa on F \\ I and -kappa elsewhere, P its prefix sums from P_0 = 0;
+    sample j outside I is flagged iff max_{b > j} P_b >= min_{a <= j} P_a.  Returns (w_out, nadded): w where kept and 0
+    where newly flagged; the new flags of every series, int32, (nf, nrow) along time and (nrow, nt) along frequency."""
+    if axis not in ("time", "freq"):
+        raise ValueError('rfi_dilate: axis is "time" or "freq"')
+    kappa = rfi_dilate_kappa(eta)
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 3 or (ref is not None and np.shape(ref) != w.shape):
+        raise ValueError("rfi_dilate_host: w (nf, nrow, nt) and ref of that shape or None expected")
+    ax = 2 if axis == "time" else 0
+    F = np.moveaxis(~(w > 0), ax, -1)
+    I = np.zeros(F.shape, dtype=bool) if ref is None else np.moveaxis(~(np.asarray(ref) > 0), ax, -1)
+    psi = np.where(I, 0, np.where(F, RFI_DILATE_ONE - kappa, -kappa)).astype(np.int64)
+    P = np.concatenate([np.zeros(psi.shape[:-1] + (1,), dtype=np.int64), np.cumsum(psi, axis=-1)], axis=-1)
+    lo = np.minimum.accumulate(P[..., :-1], axis=-1)                           # min_{a <= j} P_a
+    hi = np.maximum.accumulate(P[..., :0:-1], axis=-1)[..., ::-1]              # max_{b > j} P_b
+    new = ~I & ~F & (hi >= lo)
+    nadded = new.sum(axis=-1).astype(np.int32)
+    new = np.moveaxis(new, -1, ax)
+    return np.where(new, 0.0, w), nadded
+
+
+def rfi_dilate_params(d=None):
+    """The dilation of a route with its defaults filled in: `time` and `freq`, the eta of `Context.rfi_dilate` along each
+    axis (0: off), and `new_only` (True: the flags the data arrived with are the missing set, so that a daytime cut is
+    not grown by eta / (1 - eta) of its length; False: they dilate too).  An unknown key raises ValueError, and so does
+    an eta `rfi_dilate_kappa` refuses."""
+    out = _conf_filled(d, RFI_DILATE_DEFAULTS, "rfi_dilate: unknown key(s) %s (known: %s)", show=", ".join)
+    out["time"], out["freq"], out["new_only"] = float(out["time"]), float(out["freq"]), bool(out["new_only"])
+    rfi_dilate_kappa(out["time"])
+    rfi_dilate_kappa(out["freq"])
+    return out
+
+
+def _rfi_route(rfi, rfi_freq, rfi_dilate):
+    """What a route was asked to flag: the parameters of the time pass and of the frequency pass (None: not run), the
+    dilation (None: neither axis), and whether a step needs every frequency on one device at once."""
+    r = SimpleNamespace(time=None if rfi is None else rfi_params(rfi), freq=None if rfi_freq is None else rfi_params(rfi_freq),
+                        dilate=None if rfi_dilate is None else rfi_dilate_params(rfi_dilate))
+    if r.dilate is not None and not (r.dilate["time"] > 0 or r.dilate["freq"] > 0):
+        r.dilate = None
+    r.any = r.time is not None or r.freq is not None or r.dilate is not None
+    r.all_freqs = r.freq is not None or (r.dilate is not None and r.dilate["freq"] > 0)
+    return r
+
+
+def _rfi_chunks(who, freqs, chunk_gb, per_f, route):
+    """`_freq_chunks`, unless a step of `route` runs along frequency: the one chunk is then all frequencies, and a
+    `chunk_gb` it does not fit or more than one rank is a ValueError (ranks own frequencies, files are read whole)."""
+    if not route.all_freqs:
+        return _freq_chunks(freqs, chunk_gb, per_f)
+    if parallel.size() > 1:
+        raise ValueError("%s: flagging or dilation along frequency needs every frequency on one device, and this run has "
+                         "%d ranks that own frequencies; run it on one rank" % (who, parallel.size()))
+    need = per_f * len(freqs) / 2.0**30
+    if need > chunk_gb:
+        raise ValueError("%s: flagging or dilation along frequency needs every frequency on one device: chunk_gb >= %.4g "
+                         "(given: %g)" % (who, need * 1.001, chunk_gb))
+    return [freqs] if freqs else []
+
+
+def _rfi_steps(ctx, x_d, w_d, route):
+    """The steps of `route` on one chunk on the device, in their order: the time pass, the frequency pass on its
+    weights, dilation along time, dilation along frequency.  Returns (w_d, the outputs of the time pass or None,
+    the new flags of the frequency pass (nf, nrow) int32 or None, those added by dilation or None)."""
+    torch = ctx.torch
+
+    def fresh(before, after):
+        new = (after == 0) if before is None else (after == 0) & (before > 0)
+        return new.sum(dim=2).to(torch.int32)
+
+    ref, tout, nfreq, ndil = w_d, None, None, None
+    if route.time is not None:
+        tout = ctx.rfi_flag(x_d, w=w_d, **route.time)
+        w_d = tout[0]
+    if route.freq is not None:
+        w1 = ctx.rfi_flag_freq(x_d, w=w_d, **route.freq)[0]
+        nfreq, w_d = fresh(w_d, w1), w1
+    if route.dilate is not None:
+        w0 = w_d
+        if w_d is None:
+            w_d = torch.ones(tuple(x_d.shape), dtype=torch.float64, device=x_d.device)
+        for axis in ("time", "freq"):
+            if route.dilate[axis] > 0:
+                w_d = ctx.rfi_dilate(w_d, route.dilate[axis], axis=axis, ref=ref if route.dilate["new_only"] else None)[0]
+        ndil = fresh(w0, w_d)
+    return w_d, tout, nfreq, ndil
+
+
+def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, freq=None, dilate=None, **params):
     """Flag the interference in the Timestream directory `indir`, stacked or unstacked, along time on the device
     (`Context.rfi_flag`) and write the result to `outdir` (None: in place).  `params` are the
     parameters of `Context.rfi_flag` (an unknown key raises ValueError).  Every file keeps all its datasets and
     attributes; `weight` becomes the file's weight (ones where it had none) with the flagged samples at 0, the input
     weight is kept as `weight_input` when one was present, and `rfi_noise` (nrow, nseg), `rfi_nflag` (nrow,) and
     `rfi_occupancy` (ntime,) are the flagger's other outputs.  Ranks take their own frequencies in chunks that fit
-    `chunk_gb`.  Returns the Timestream of the output."""
+    `chunk_gb`.  Returns the Timestream of the output.
+
+    freq: a dict of the parameters of `Context.rfi_flag_freq` (the keys of `params`): the frequency pass then runs on the
+    weights of the time pass.  dilate: a dict of `rfi_dilate_params` — the flags are then dilated along time, then along
+    frequency.  Each file then also holds `rfi_freq_nflag` (nrow,) int32, the new flags of the
+    frequency pass in that file, and `rfi_dilate_nflag` (nrow,), those added by dilation, for the steps that ran.  A step
+    along frequency needs every frequency on one device: the one chunk is then all frequencies, and a `chunk_gb` that
+    does not hold them, or more than one rank, raises ValueError."""
     p = rfi_params(params)
-    ctx = get_context()
+    route = _rfi_route(p, freq, dilate)
     tel = m.beamtransfer.telescope
     src = Timestream(indir, m)
     inplace = outdir is None or os.path.abspath(outdir) == os.path.abspath(src.directory)
@@ -2878,7 +3024,10 @@ def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, **params):
     with storage.File(src._ffile(0), "r") as f:
         nrow, nt = (int(v) for v in f["timestream"].shape)
     log = sim_log
-    for fs in _freq_chunks(freqs, chunk_gb, nrow * nt * 32.0):
+    extra_steps = route.freq is not None or route.dilate is not None
+    chunks = _rfi_chunks("rfi_flag", freqs, chunk_gb, nrow * nt * (48.0 if extra_steps else 32.0), route)
+    ctx = get_context()
+    for fs in chunks:
         with _StepTimer(log, "read"):
             files = []
             for fi in fs:
@@ -2893,13 +3042,16 @@ def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, **params):
             if weighted:
                 w_d = ctx.to_device(np.stack([np.asarray(d["weight"], dtype=np.float64) if "weight" in d
                                               else np.ones((nrow, nt), dtype=np.float64) for d, _ in files]))
-            out = [ctx.to_host(t) for t in ctx.rfi_flag(x_d, w=w_d, **p)]
-            del x_d, w_d
+            w_last, tout, nfreq, ndil = _rfi_steps(ctx, x_d, w_d, route)
+            out = [ctx.to_host(w_last)] + [ctx.to_host(t) for t in tout[1:]]
+            more = {name: ctx.to_host(t) for name, t in (("rfi_freq_nflag", nfreq), ("rfi_dilate_nflag", ndil)) if t is not None}
+            del x_d, w_d, w_last, tout, nfreq, ndil
         with _StepTimer(log, "write"):
             for k, (fi, (data, attrs)) in enumerate(zip(fs, files)):
                 if "weight" in data and "weight_input" not in data:   # a second pass keeps the first input
                     data["weight_input"] = data["weight"]
                 data.update(weight=out[0][k], rfi_noise=out[1][k], rfi_nflag=out[2][k], rfi_occupancy=out[3][k])
+                data.update({name: v[k] for name, v in more.items()})
                 os.makedirs(dst._fdir(fi), exist_ok=True)
                 with storage.File(dst._ffile(fi), "w") as f:
                     for name, value in data.items():

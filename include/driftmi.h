@@ -914,6 +914,41 @@ int dm_rfi_flag(dm_ctx* ctx, int nf, int nrow, int nt, int segment, double kerne
 /* the cap on `segment`, set by the LDS layout of the row kernel (host only) */
 int dm_rfi_max_segment(void);
 
+/* ---- RFI flagging along frequency and the dilation of flags ---------------------------- */
+/* dm_rfi_flag_freq: the method of dm_rfi_flag, word for word, on the series x[:, row, j] of every (row, j): nf takes
+ * the place of nt in the segments (nseg = ceil(nf / segment) balanced segments over the frequencies), in the
+ * background, the median, the window passes and min_good; the occupancy rule runs over the rows of a (f, j) as it does
+ * there.  With xt = x transposed to (nt, nrow, nf) and wt likewise, the outputs are those of dm_rfi_flag(xt, wt)
+ * transposed back, bit for bit: w_out (nf, nrow, nt), which may be w itself; noise (nseg, nrow, nt); nflag (nrow, nt)
+ * int32, the new flags of every series; occupancy (nf, nt) int32.  No floating-point atomics.  Refused before any launch
+ * (dm_last_error): what dm_rfi_flag refuses, with nf in the place of nt.  nf, nrow or nt = 0 is a no-op.  Returns when
+ * the work is queued on the context's stream.  No counterpart in the reference. */
+int dm_rfi_flag_freq(dm_ctx* ctx, int nf, int nrow, int nt, int segment, double kernel_sigma, int nwin,
+                     const int* windows_host, double chi1, double rho, int niter, double base, int min_good,
+                     double row_share, const void* x_dev, const double* w_dev, double* wout_dev, double* noise_dev,
+                     int* nflag_dev, int* occupancy_dev);
+/* the series of consecutive j that one workgroup of dm_rfi_flag_freq takes when the longest balanced segment,
+ * ceil(nf / nseg), has segment_len samples: 8 up to 512, 4 up to 1024, 2 up to dm_rfi_max_segment(); 0 for a length it
+ * does not take (host only) */
+int dm_rfi_freq_tile(int segment_len);
+/* dm_rfi_dilate: the scale-invariant rank operator (Offringa, van de Gronde & Roerdink 2012) in exact integers on every
+ * series of w (nf, nrow, nt) float64 along axis 0 (time: the series w[f, row, :]) or 1 (frequency: w[:, row, j]).  F =
+ * the samples where w > 0 is false; I = those where w_ref > 0 is false (w_ref of the shape of w, or null: none): they
+ * are missing, stay as they are and count neither as flags nor as length.  kappa = rint((1 - eta) 65536), in double;
+ * psi_i = 0 on I, 65536 - kappa on F \ I, -kappa elsewhere; P_0 = 0, P_{k+1} = P_k + psi_k; a sample j outside I is
+ * flagged iff max_{b > j} P_b >= min_{a <= j} P_a: some window holding j has at least the share kappa / 65536 of its
+ * present samples flagged.  The whole series is one unit.  w_out = w bit for bit where kept and 0 where newly flagged,
+ * and it may be w itself; nadded int32, the newly flagged samples of every series: (nf, nrow) along time, (nrow, nt)
+ * along frequency.  Refused before any launch (dm_last_error): negative sizes, another axis, eta not finite or outside
+ * [0, 1), kappa < 1, a series longer than dm_rfi_dilate_max_length(axis), a null w, w_out or nadded with work to do, an
+ * output sharing an element with w or w_ref (other than w_out == w) or with the other output.  nf, nrow or nt = 0 is a
+ * no-op.  Returns when the work is queued on the context's stream.  No counterpart in the reference. */
+int dm_rfi_dilate(dm_ctx* ctx, int nf, int nrow, int nt, int axis, double eta, const double* w_dev,
+                  const double* wref_dev, double* wout_dev, int* nadded_dev);
+/* the longest series dm_rfi_dilate takes along the axis: 16384 along time (0), dm_rfi_max_segment() along frequency
+ * (1); 0 for another axis (host only) */
+int dm_rfi_dilate_max_length(int axis);
+
 #ifdef __cplusplus
 }
 #endif
