@@ -232,6 +232,12 @@ SIGNATURES = {
     "dm_rfi_freq_tile": (c_int, [c_int]),
     "dm_rfi_dilate": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     "dm_rfi_dilate_max_length": (c_int, [c_int]),
+    "dm_delay_fit": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_dbl, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_vp, c_vp,
+                c_vp, c_vp]),
+    "dm_delay_max_nf": (c_int, []),
+    "dm_delay_max_rank": (c_int, []),
+    "dm_delay_tile": (c_int, [c_int, c_int]),
 }
 
 _lib = None
@@ -1262,6 +1268,81 @@ def _rfi_dilate(self, w, eta, axis="time", ref=None, out=None):
 
 
 Context.rfi_dilate = _rfi_dilate
+
+DELAY_MODES = {"model": 0, "filter": 1, "inpaint": 2}
+
+
+def _delay_pack(self, bases, device=None):
+    """The basis table of `delay_fit` from a sequence of real matrices A_k (nf, r_k), numpy or torch: (table, ranks) with
+    table a float64 device tensor that holds basis k as (r_k, nf) row-major behind the bases before it."""
+    import numpy as np
+
+    torch = self.torch
+    mats = [np.ascontiguousarray(np.asarray(b.detach().cpu().numpy() if hasattr(b, "detach") else b, dtype=np.float64))
+            for b in bases]
+    if not mats or any(a.ndim != 2 for a in mats) or len({a.shape[0] for a in mats}) != 1:
+        raise ValueError("delay_fit: basis must be a sequence of real matrices (nf, r_k) of one nf")
+    table = np.concatenate([a.T.reshape(-1) for a in mats])
+    dev = device if device is not None else "cuda:%d" % self.device
+    return torch.from_numpy(table).to(dev), [int(a.shape[1]) for a in mats]
+
+
+Context.delay_pack = _delay_pack
+
+
+def _delay_fit(self, x, w=None, basis=None, basis_of=None, mode="inpaint", ridge=0.0, min_valid=None, out=None):
+    """The band-limited weighted least-squares fit along frequency (dm_delay_fit, DESIGN.md section 4.23;
+    `timestream.delay_fit_host` restates it).  x (nf, nrow, nt) complex128, contiguous; w float64 of that shape or None
+    (ones): a sample is kept iff w > 0.  basis: a sequence of real matrices A_k (nf, r_k), or the pair (table, ranks)
+    of `delay_pack`; basis_of (nrow,) int32 tensor (or a sequence of ints), the basis of every row.  mode "model",
+    "filter" or "inpaint"; ridge >= 0, relative to the mean weight; min_valid: the kept samples a series needs to be
+    solved (None: the rank).  Returns (x_out, w_out, info): x_out complex128 and w_out float64 of x's shape, info
+    (nrow, nt) int32: 0 solved, -1 too few kept samples, -2 a basis_of entry outside the table, j + 1 a pivot of the
+    Cholesky factorisation that was not positive at column j.  `out` takes that tuple of tensors to write into; its
+    x_out may be x and its w_out may be w."""
+    torch = self.torch
+    if mode not in DELAY_MODES:
+        raise ValueError('delay_fit: mode is "model", "filter" or "inpaint"')
+    if not (_is_c128(x) and x.dim() == 3):
+        raise ValueError("delay_fit: contiguous complex128 tensor x (nf, nrow, nt) expected")
+    nf, nrow, nt = (int(v) for v in x.shape)
+    if w is not None:
+        _weights_arg("delay_fit", w, x.shape)
+    if basis is None or basis_of is None:
+        raise ValueError("delay_fit: basis and basis_of are required")
+    if isinstance(basis, tuple) and len(basis) == 2 and hasattr(basis[0], "data_ptr") and basis[0].dim() == 1:
+        table, ranks = basis[0], [int(r) for r in basis[1]]
+    else:
+        table, ranks = self.delay_pack(basis, device=x.device)
+        if int(table.numel()) != nf * sum(ranks):
+            raise ValueError("delay_fit: basis must be a sequence of real matrices (nf, r_k) with x's nf")
+    if not (table.dtype == torch.float64 and table.is_contiguous() and int(table.numel()) == nf * sum(ranks)):
+        raise ValueError("delay_fit: the basis table must be a contiguous float64 tensor of nf * sum(ranks) elements")
+    if not hasattr(basis_of, "data_ptr"):
+        basis_of = torch.tensor([int(v) for v in basis_of], dtype=torch.int32, device=x.device)
+    if not (basis_of.dtype == torch.int32 and basis_of.is_contiguous() and tuple(basis_of.shape) == (nrow,)):
+        raise ValueError("delay_fit: basis_of must be a contiguous int32 tensor (nrow,)")
+    shapes = ((nf, nrow, nt), (nf, nrow, nt), (nrow, nt))
+    dtypes = (torch.complex128, torch.float64, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 3 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
+                                    for o, s, d in zip(out, shapes, dtypes)):
+            raise ValueError("delay_fit: out must hold contiguous tensors x_out (nf, nrow, nt) complex128, w_out "
+                             "(nf, nrow, nt) float64 and info (nrow, nt) int32")
+    if not all(t is None or (t.is_cuda and t.device == x.device) for t in (x, w, table, basis_of) + out):
+        raise ValueError("delay_fit: x, w, the basis table, basis_of and out must be tensors on one GPU")
+    rk = (c_int * max(len(ranks), 1))(*ranks)
+    rc = self.lib.dm_delay_fit(self.h, nf, nrow, nt, DELAY_MODES[mode], float(ridge), 0 if min_valid is None else int(min_valid),
+                               len(ranks), rk, self.ptr(table), self.ptr(basis_of), self.ptr(x), self.ptr(w),
+                               self.ptr(out[0]), self.ptr(out[1]), self.ptr(out[2]))
+    self.check(rc, "dm_delay_fit")
+    return out
+
+
+Context.delay_fit = _delay_fit
 
 
 def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,

@@ -124,18 +124,20 @@ class PipelineManager(config.Reader):
 
     @staticmethod
     def _check_rfi(conf):
-        """The `rfi`, `rfi_freq` and `rfi_dilate` dicts of a `stack_from` or `sidereal_from` block, defaults filled in; an
+        """The `rfi`, `rfi_freq`, `rfi_dilate` and `delay` dicts of a `stack_from` or `sidereal_from` block, defaults filled in; an
         unknown key raises ValueError."""
         for key in ("rfi", "rfi_freq"):
             if conf.get(key) is not None:
                 conf[key] = timestream.rfi_params(conf[key])
         if conf.get("rfi_dilate") is not None:
             conf["rfi_dilate"] = timestream.rfi_dilate_params(conf["rfi_dilate"])
+        if conf.get("delay") is not None:
+            conf["delay"] = timestream.delay_params(conf["delay"])
 
     @staticmethod
     def _rfi_more(conf):
-        """The `rfi_freq` and `rfi_dilate` keywords of a block, only when present."""
-        return {key: conf[key] for key in ("rfi_freq", "rfi_dilate") if conf.get(key) is not None}
+        """The `rfi_freq`, `rfi_dilate` and `delay` keywords of a block, only when present."""
+        return {key: conf[key] for key in ("rfi_freq", "rfi_dilate", "delay") if conf.get(key) is not None}
 
     def _products(self, directory):
         """The ProductManager of a product directory (opened once per directory: its objects hold caches and device

@@ -2304,7 +2304,7 @@ def _stack_report(c, nfreq, lost, minvalid, mblind, log):
 
 
 def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_feeds=(), chunk_gb=4.0, redcal=None, rfi=None,
-                    modelcal=None, rfi_freq=None, rfi_dilate=None):
+                    modelcal=None, rfi_freq=None, rfi_dilate=None, delay=None):
     """Stack the unstacked Timestream directory `indir` (`simulate_ensemble(unstacked=True)`, or a correlator's per-pair
     data in that layout) into the unique baselines of the telescope of ProductManager `m` and write them to `outdir` in
     the layout of `simulate_ensemble`; returns the `Timestream` of `outdir`.
@@ -2351,7 +2351,11 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     frequency (`Context.rfi_flag_freq`), run on the weights of the time pass; rfi_dilate: a dict of `rfi_dilate_params`,
     the dilation of the flags along time, then along frequency.  A step along frequency needs
     every frequency on one device: the one chunk is then all frequencies, and a `chunk_gb` that does not hold them, or
-    more than one rank, raises ValueError."""
+    more than one rank, raises ValueError.  delay: a dict of `delay_params`: `delay_filter` then runs in place on the
+    stacked output, with this call's `chunk_gb`."""
+    delay = None if delay is None else delay_params(delay)
+    if delay is not None:
+        _delay_one_rank("stack_baselines")
     src = Timestream(indir, m)
     c = _stack_conf(m, src, calibrate, feed_weight, dead_feeds, redcal, rfi, modelcal, rfi_freq, rfi_dilate)
     freqs = _sim_freqs(m.beamtransfer.telescope, None)
@@ -2384,6 +2388,8 @@ def stack_baselines(m, indir, outdir, calibrate=None, feed_weight=None, dead_fee
     _stack_write(dst, freqs, records, c.phi, log)
     _stack_report(c, len(freqs), lost, minvalid, mblind, log)
     _save_all([dst])
+    if delay is not None:
+        delay_filter(m, outdir, None, chunk_gb=chunk_gb, **delay)
     return dst
 
 
@@ -2539,7 +2545,7 @@ def _day_phi(tstream):
 
 
 def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=4.0, rfi=None, rfi_freq=None,
-                   rfi_dilate=None):
+                   rfi_dilate=None, delay=None):
     """Regrid the days `daydirs` onto the sidereal grid and average them with their weights.
     Every entry is a Timestream directory, stacked or unstacked, all of one row layout (and one class table): a stretch
     of samples at the positions of its dataset `phi` (uniformly spaced after unwrapping, else ValueError), with `weight`
@@ -2556,7 +2562,12 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
     (`Context.rfi_flag_freq`), which runs on the weights of the time pass; rfi_dilate: a dict of `rfi_dilate_params`, the
     dilation of the flags along time, then along frequency.  A step along frequency needs every
     frequency of a day on one device: the one chunk is then all frequencies, and a `chunk_gb` that does not hold them, or
-    more than one rank, raises ValueError.  Returns the Timestream of `outdir`."""
+    more than one rank, raises ValueError.  delay: a dict of `delay_params`: `delay_filter` then runs in place on the
+    combined days (stacked days only), with this call's `chunk_gb`.  Returns the Timestream of
+    `outdir`."""
+    delay = None if delay is None else delay_params(delay)
+    if delay is not None:
+        _delay_one_rank("sidereal_stack")
     route = _rfi_route(rfi, rfi_freq, rfi_dilate)
     tel = m.beamtransfer.telescope
     daydirs = list(daydirs)
@@ -2568,6 +2579,8 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
     unst = [d.is_unstacked() for d in days]
     if any(u != unst[0] for u in unst):
         raise ValueError("sidereal_stack: stacked and unstacked days cannot be mixed")
+    if delay is not None and unst[0]:
+        raise ValueError("sidereal_stack: delay needs stacked days: stack them first with timestream.stack_baselines")
     table = None
     if unst[0]:
         for d in days:
@@ -2633,6 +2646,8 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
                 with storage.File(dst._ffile(fi), "a") as f:
                     f.attrs["ndays"] = nd
     _save_all([dst])
+    if delay is not None:
+        delay_filter(m, outdir, None, chunk_gb=chunk_gb, **delay)
     return dst
 
 
@@ -3058,5 +3073,306 @@ def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, freq=None, dilate=None, **para
                         f.create_dataset(name, data=np.ascontiguousarray(value))
                     for name, value in attrs.items():
                         f.attrs[name] = value
+    _save_all([] if inplace else [dst])
+    return dst
+
+
+# ---- the delay fit along frequency -------------------------------------------------------
+
+DELAY_MODES = ("model", "filter", "inpaint")
+DELAY_C = 299.792458   # metres per microsecond
+DELAY_DEFAULTS = dict(mode="inpaint", ridge=0.0, min_valid=None, horizon=1.0, buffer=2.0, nclass=8, eigencut=1e-10)
+
+
+def _delay_limits():
+    """(the most frequencies, the largest rank) `Context.delay_fit` takes: host-only queries of the library."""
+    from . import _lib
+
+    lib = _lib.load()
+    return int(lib.dm_delay_max_nf()), int(lib.dm_delay_max_rank())
+
+
+def _delay_cholesky_host(G):
+    """Row by row (Cholesky-Banachiewicz) in the dtype of G: (L, info) with info = 0, or j + 1 for the first column j
+    whose pivot is not finite or not > 0 (L is then filled up to that column only)."""
+    r = G.shape[0]
+    L = np.zeros_like(G)
+    for j in range(r):
+        d = G[j, j] - np.dot(L[j, :j], L[j, :j])
+        if not (d > 0 and np.isfinite(d)):
+            return L, j + 1
+        L[j, j] = np.sqrt(d)
+        if j + 1 < r:
+            L[j + 1 :, j] = (G[j + 1 :, j] - L[j + 1 :, :j] @ L[j, :j]) / L[j, j]
+    return L, 0
+
+
+def _delay_lower_solve_host(L, B, transpose=False):
+    """L Y = B (or L^T Y = B) by substitution in the dtype of L; B (r, n)."""
+    r = L.shape[0]
+    Y = np.array(B, dtype=np.result_type(L.dtype, B.dtype), copy=True)
+    order = range(r - 1, -1, -1) if transpose else range(r)
+    for j in order:
+        Y[j] = Y[j] / L[j, j]
+        if transpose:
+            Y[:j] -= np.outer(L[j, :j], Y[j])
+        else:
+            Y[j + 1 :] -= np.outer(L[j + 1 :, j], Y[j])
+    return Y
+
+
+def delay_fit_host(x, w, basis, basis_of, mode="inpaint", ridge=0.0, min_valid=None, dtype=np.float64, details=False):
+    """The numpy statement of `Context.delay_fit`: x (nf, nrow, nt) complex, w of that shape or
+    None, basis a sequence of real matrices A_k (nf, r_k), basis_of (nrow,) ints.  Per (row, t): kept iff w > 0, omega =
+    w on kept samples and 0 elsewhere, x under a flag is selected out; nvalid < min_valid (None or <= 0: the rank) or
+    nvalid = 0 gives info = -1; G = A^T diag(omega) A + ridge mean(omega) I; a Cholesky pivot that is not finite or not
+    > 0 at column j gives info = j + 1; c = G^-1 A^T diag(omega) x, model = A c, v_f = a_f^T G^-1 a_f; a basis_of entry
+    outside the table gives info = -2.  dtype float64 solves with LAPACK (`numpy.linalg.solve`), longdouble with the
+    factor in long double.  Returns (x_out, w_out, info) as the modes of the device define them, x_out complex of twice
+    `dtype`'s width; with details=True also a dict with model (nf, nrow, nt), c (nrow, nt, rmax), v (nf, nrow, nt), kappa
+    (nrow, nt) — kappa_2(G) — kept (nf, nrow, nt), and anorm (nf, nrow), |a_f|_2 of the row's basis."""
+    if mode not in DELAY_MODES:
+        raise ValueError('delay_fit: mode is "model", "filter" or "inpaint"')
+    real = np.dtype(dtype).type
+    if real not in (np.float64, np.longdouble):
+        raise ValueError("delay_fit_host: dtype is float64 or longdouble")
+    ctype = np.complex128 if real is np.float64 else np.clongdouble
+    if not (np.isfinite(ridge) and ridge >= 0):
+        raise ValueError("delay_fit: ridge not finite or negative")
+    x = np.asarray(x)
+    if x.ndim != 3 or (w is not None and np.shape(w) != x.shape):
+        raise ValueError("delay_fit_host: x (nf, nrow, nt) and w of that shape or None expected")
+    nf, nrow, nt = x.shape
+    bases = [np.asarray(a, dtype=np.float64) for a in basis]
+    if any(a.ndim != 2 or a.shape[0] != nf or not 1 <= a.shape[1] <= nf for a in bases):
+        raise ValueError("delay_fit_host: basis must be a sequence of real matrices (nf, r_k), 1 <= r_k <= nf")
+    rmax = max([a.shape[1] for a in bases] + [1])
+    wv = np.ones(x.shape) if w is None else np.asarray(w, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        kept = wv > 0
+    om = np.where(kept, wv, 0.0)
+    xk = np.where(kept, x, 0.0).astype(ctype)
+    x_out = np.zeros(x.shape, dtype=ctype) if mode == "model" else xk.copy()
+    w_out = om.astype(real)
+    info = np.zeros((nrow, nt), dtype=np.int32)
+    model = np.zeros(x.shape, dtype=ctype)
+    cs = np.zeros((nrow, nt, rmax), dtype=ctype)
+    v = np.zeros(x.shape, dtype=real)
+    kappa = np.zeros((nrow, nt))
+    anorm = np.zeros((nf, nrow))
+    for row in range(nrow):
+        k = int(basis_of[row])
+        if not 0 <= k < len(bases):
+            info[row] = -2
+            continue
+        A = bases[k].astype(real)
+        r = A.shape[1]
+        anorm[:, row] = np.sqrt((bases[k] ** 2).sum(axis=1))
+        need = r if min_valid is None or int(min_valid) <= 0 else int(min_valid)
+        for t in range(nt):
+            o = om[:, row, t].astype(real)
+            nvalid = int(kept[:, row, t].sum())
+            if nvalid < need or nvalid == 0:
+                info[row, t] = -1
+                continue
+            G = (A * o[:, None]).T @ A + real(ridge) * (o.sum() / real(nf)) * np.eye(r, dtype=real)
+            L, bad = _delay_cholesky_host(G)
+            if bad:
+                info[row, t] = bad
+                continue
+            rhs = A.T @ (o * xk[:, row, t])
+            if real is np.float64:
+                sol = np.linalg.solve(G, np.concatenate([rhs[:, None], A.T.astype(ctype)], axis=1))
+                c, Z = sol[:, 0], sol[:, 1:].real
+                vf = np.einsum("fr,rf->f", A, Z)
+            else:
+                c = _delay_lower_solve_host(L, _delay_lower_solve_host(L, rhs[:, None]), transpose=True)[:, 0]
+                Y = _delay_lower_solve_host(L, A.T)
+                vf = (Y * Y).sum(axis=0)
+            mod = A @ c
+            model[:, row, t], cs[row, t, :r], v[:, row, t] = mod, c, vf
+            kappa[row, t] = np.linalg.cond(G.astype(np.float64))
+            kp = kept[:, row, t]
+            if mode == "model":
+                x_out[:, row, t] = mod
+            elif mode == "filter":
+                x_out[kp, row, t] = xk[kp, row, t] - mod[kp]
+            else:
+                x_out[~kp, row, t] = mod[~kp]
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    fill = np.where((vf > 0) & np.isfinite(vf), 1 / vf, 0)
+                w_out[~kp, row, t] = fill[~kp]
+    if details:
+        return x_out, w_out, info, dict(model=model, c=cs, v=v, kappa=kappa, kept=kept, anorm=anorm)
+    return x_out, w_out, info
+
+
+def delay_basis(freqs_mhz, tau_us, eigencut=1e-10):
+    """The band-limited basis of the delays |tau| <= tau_us on the frequency grid freqs_mhz (any grid, gaps included):
+    the eigenvectors of S_ij = sinc(2 tau (nu_i - nu_j)) (numpy's normalised sinc: the covariance of a flat delay
+    spectrum over the band) with eigenvalue >= eigencut lambda_max, in descending order.  Returns (A (nf, r), the r
+    eigenvalues).  A rank above `dm_delay_max_rank()` raises ValueError."""
+    nu = np.asarray(freqs_mhz, dtype=np.float64).reshape(-1)
+    tau = float(tau_us)
+    if nu.size < 1 or not (np.isfinite(tau) and tau >= 0) or not (0 < eigencut < 1):
+        raise ValueError("delay_basis: at least one frequency, a finite tau >= 0 and 0 < eigencut < 1 expected")
+    S = np.sinc(2.0 * tau * (nu[:, None] - nu[None, :]))
+    lam, vec = np.linalg.eigh(S)
+    lam, vec = lam[::-1], vec[:, ::-1]
+    r = int((lam >= eigencut * lam[0]).sum())
+    rmax = _delay_limits()[1]
+    if r > rmax:
+        raise ValueError("delay_basis: rank %d > %d: the bandwidth x delay product 2 B tau = %.4g (B = %.6g MHz, tau = %.6g us) "
+                         "is too large; lower the horizon or buffer, raise eigencut or fit fewer frequencies"
+                         % (r, rmax, 2.0 * (nu.max() - nu.min()) * tau, nu.max() - nu.min(), tau))
+    return np.ascontiguousarray(vec[:, :r]), lam[:r].copy()
+
+
+def delay_class_ceilings(tau, nclass=8):
+    """At most nclass ceilings equally spaced over [min tau, max tau] (the last one max tau itself) and, per row, the
+    index of the smallest ceiling >= its tau among those in use: (ceilings in use, ascending; basis_of int32)."""
+    tau = np.asarray(tau, dtype=np.float64).reshape(-1)
+    nclass = int(nclass)
+    if nclass < 1 or tau.size < 1 or not np.all(np.isfinite(tau)):
+        raise ValueError("delay_classes: nclass >= 1 and finite tau expected")
+    lo, hi = float(tau.min()), float(tau.max())
+    ceil = np.array([lo + (hi - lo) * (k + 1) / nclass for k in range(nclass)])
+    ceil[-1] = hi
+    ceil = np.maximum.accumulate(ceil)
+    which = np.array([int(np.nonzero(ceil >= t)[0][0]) for t in tau])
+    used = np.unique(which)
+    return ceil[used], np.searchsorted(used, which).astype(np.int32)
+
+
+def delay_classes(tel, horizon=1.0, buffer=2.0, nclass=8, eigencut=1e-10):
+    """The delay classes of the stacked rows of telescope `tel`: tau_row = horizon |b_row| / c + buffer / (nf dnu) in
+    microseconds (c = 299.792458 m / us; the buffer in delay-resolution elements of the band), binned by
+    `delay_class_ceilings`, one `delay_basis` per ceiling in use.  Returns (table, ranks, basis_of, tau): the packed
+    table of `Context.delay_fit` (float64, basis k as (r_k, nf) row-major behind the bases before it), ranks int32,
+    basis_of (nrow,) int32 and the tau of every row."""
+    nu = np.asarray(tel.frequencies, dtype=np.float64)
+    nf = nu.size
+    if nf < 2:
+        raise ValueError("delay_classes: at least two frequencies expected")
+    if not (np.isfinite(horizon) and horizon >= 0 and np.isfinite(buffer) and buffer >= 0):
+        raise ValueError("delay_classes: horizon and buffer must be finite and >= 0")
+    dnu = float(np.median(np.abs(np.diff(nu))))
+    blen = np.sqrt((np.asarray(tel.baselines, dtype=np.float64) ** 2).sum(axis=1))
+    tau = float(horizon) * blen / DELAY_C + float(buffer) / (nf * dnu)
+    ceil, basis_of = delay_class_ceilings(tau, nclass)
+    bases = [delay_basis(nu, t, eigencut)[0] for t in ceil]
+    table = np.concatenate([a.T.reshape(-1) for a in bases])
+    return table, np.array([a.shape[1] for a in bases], dtype=np.int32), basis_of, tau
+
+
+def delay_params(d=None):
+    """The `delay` dict of a route with its defaults filled in: `mode`, `ridge` and `min_valid` of `Context.delay_fit`,
+    `horizon`, `buffer`, `nclass` and `eigencut` of `delay_classes`.  An unknown key raises ValueError, and so does a
+    value the steps refuse."""
+    out = _conf_filled(d, DELAY_DEFAULTS, "delay: unknown key(s) %s (known: %s)", show=", ".join)
+    if out["mode"] not in DELAY_MODES:
+        raise ValueError('delay: mode is "model", "filter" or "inpaint"')
+    out["ridge"], out["horizon"], out["buffer"] = float(out["ridge"]), float(out["horizon"]), float(out["buffer"])
+    out["eigencut"], out["nclass"] = float(out["eigencut"]), int(out["nclass"])
+    out["min_valid"] = None if out["min_valid"] is None else int(out["min_valid"])
+    if not (np.isfinite(out["ridge"]) and out["ridge"] >= 0):
+        raise ValueError("delay: ridge not finite or negative")
+    if not (np.isfinite(out["horizon"]) and out["horizon"] >= 0 and np.isfinite(out["buffer"]) and out["buffer"] >= 0):
+        raise ValueError("delay: horizon and buffer must be finite and >= 0")
+    if out["nclass"] < 1 or not 0 < out["eigencut"] < 1:
+        raise ValueError("delay: nclass >= 1 and 0 < eigencut < 1 expected")
+    return out
+
+
+def _delay_one_rank(who):
+    if parallel.size() > 1:
+        raise ValueError("%s: the fit along frequency needs every frequency on one device, and this run has "
+                         "%d ranks that own frequencies; run it on one rank" % (who, parallel.size()))
+
+
+def delay_filter(m, indir, outdir=None, mode="inpaint", chunk_gb=4.0, ridge=0.0, min_valid=None, **classes):
+    """The delay fit along frequency on the stacked Timestream directory `indir` (`Context.delay_fit`, DESIGN.md section
+    4.23), written to `outdir` (None: in place): every row is fitted with the band-limited basis of its delay class
+    (`delay_classes` with the keywords `classes`), and by `mode` the flagged samples are filled from the fit
+    ("inpaint"), the fit is subtracted ("filter") or the fit replaces the data ("model").  Every file keeps its datasets
+    and attributes; `timestream` and `weight` are replaced (ones where the file had no weight), the first input weight
+    is kept as `weight_input`, and `delay_filled` (nrow,) int32 counts the samples of the file that were filled.
+    `delay_fit.hdf5` at the root of the output holds `info` (nrow, ntime) int32, `basis_of`, `tau`, `rank` and the
+    parameters as attributes.  The fit needs every frequency of a row at once, so the device takes chunks of rows over
+    all frequency files that fit `chunk_gb`; more than one rank raises ValueError, and so does an unstacked directory.
+    `chunk_gb` bounds the device only: the host holds every dataset of every frequency file and the two outputs at
+    once, a little over twice the directory.  Returns the Timestream of the output."""
+    p = delay_params(dict(classes, mode=mode, ridge=ridge, min_valid=min_valid))
+    _delay_one_rank("delay_filter")
+    tel = m.beamtransfer.telescope
+    src = Timestream(indir, m)
+    src._refuse_unstacked()
+    inplace = outdir is None or os.path.abspath(outdir) == os.path.abspath(src.directory)
+    dst = src if inplace else Timestream(outdir, m)
+    freqs = list(range(tel.nfreq))
+    table, ranks, basis_of, tau = delay_classes(tel, horizon=p["horizon"], buffer=p["buffer"], nclass=p["nclass"],
+                                                eigencut=p["eigencut"])
+    log = sim_log
+    with _StepTimer(log, "read"):
+        files = []
+        for fi in freqs:
+            with storage.File(src._ffile(fi), "r") as f:
+                files.append(({k: np.asarray(f[k][:]) for k in f.keys()}, dict(f.attrs)))
+        nrow, nt = (int(v) for v in files[0][0]["timestream"].shape)
+        for fi, (d, _) in zip(freqs, files):
+            if d["timestream"].shape != (nrow, nt):
+                raise ValueError("delay_filter: %s holds %s, not (%d, %d)" % (src._ffile(fi), d["timestream"].shape, nrow, nt))
+        if nrow != basis_of.shape[0]:
+            raise ValueError("delay_filter: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, basis_of.shape[0]))
+        weighted = any("weight" in d for d, _ in files)
+    nf = len(freqs)
+    rows_per = int(chunk_gb * 2.0**30 // (48.0 * nf * nt))
+    if rows_per < 1:
+        raise ValueError("delay_filter: one row over all frequencies needs chunk_gb >= %.4g (given: %g)"
+                         % (48.0 * nf * nt / 2.0**30 * 1.001, chunk_gb))
+    ctx = get_context()
+    torch = ctx.torch
+    x_out = np.empty((nf, nrow, nt), dtype=np.complex128)
+    w_out = np.empty((nf, nrow, nt), dtype=np.float64)
+    info = np.empty((nrow, nt), dtype=np.int32)
+    filled = np.zeros((nf, nrow), dtype=np.int32)
+    with _StepTimer(log, "delay"):
+        table_d = ctx.to_device(table)
+        for r0 in range(0, nrow, rows_per):
+            r1 = min(nrow, r0 + rows_per)
+            x_d = ctx.to_device(np.stack([np.asarray(d["timestream"][r0:r1], dtype=np.complex128) for d, _ in files]))
+            w_d = None
+            if weighted:
+                w_d = ctx.to_device(np.stack([np.asarray(d["weight"][r0:r1], dtype=np.float64) if "weight" in d
+                                              else np.ones((r1 - r0, nt), dtype=np.float64) for d, _ in files]))
+            of_d = ctx.to_device(np.ascontiguousarray(basis_of[r0:r1]))
+            xo, wo, io = ctx.delay_fit(x_d, w=w_d, basis=(table_d, ranks), basis_of=of_d, mode=p["mode"], ridge=p["ridge"],
+                                       min_valid=p["min_valid"])
+            if p["mode"] == "inpaint" and w_d is not None:
+                filled[:, r0:r1] = ctx.to_host((~(w_d > 0) & (io == 0)[None]).sum(dim=2).to(torch.int32))
+            x_out[:, r0:r1], w_out[:, r0:r1], info[r0:r1] = ctx.to_host(xo), ctx.to_host(wo), ctx.to_host(io)
+            del x_d, w_d, of_d, xo, wo, io
+    with _StepTimer(log, "write"):
+        for k, (fi, (data, attrs)) in enumerate(zip(freqs, files)):
+            if "weight" in data and "weight_input" not in data:   # a second pass keeps the first input
+                data["weight_input"] = data["weight"]
+            data.update(timestream=x_out[k], weight=w_out[k], delay_filled=filled[k])
+            os.makedirs(dst._fdir(fi), exist_ok=True)
+            with storage.File(dst._ffile(fi), "w") as f:
+                for name, value in data.items():
+                    f.create_dataset(name, data=np.ascontiguousarray(value))
+                for name, value in attrs.items():
+                    f.attrs[name] = value
+        os.makedirs(dst.directory, exist_ok=True)
+        with storage.File(os.path.join(dst.directory, "delay_fit.hdf5"), "w") as f:
+            f.create_dataset("info", data=info)
+            f.create_dataset("basis_of", data=basis_of)
+            f.create_dataset("tau", data=tau)
+            f.create_dataset("rank", data=ranks)
+            for name, value in p.items():
+                f.attrs[name] = -1 if value is None else value
+    unsolved = int((info != 0).sum())
+    if unsolved:
+        logging.getLogger(__name__).warning("delay_filter: %d of %d series were not solved (info in delay_fit.hdf5)", unsolved, info.size)
     _save_all([] if inplace else [dst])
     return dst

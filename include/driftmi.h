@@ -949,6 +949,36 @@ int dm_rfi_dilate(dm_ctx* ctx, int nf, int nrow, int nt, int axis, double eta, c
  * (1); 0 for another axis (host only) */
 int dm_rfi_dilate_max_length(int axis);
 
+/* ---- the delay fit along frequency ------------------------------------------------------ */
+/* dm_delay_fit: one weighted least-squares fit of a band-limited basis per series x[:, row, t] of x (nf, nrow, nt)
+ * complex128.  w (nf, nrow, nt) float64 or null (ones); a sample is kept iff w > 0 (false for 0, negatives and NaN),
+ * omega_f = w_f on kept samples and 0 elsewhere, and x of a sample that is not kept is never read into arithmetic.
+ * nbasis real bases, basis k of rank rank_host[k] stored (r_k, nf) row-major from nf sum_{j<k} r_j doubles of basis_dev;
+ * basis_of_dev (nrow,) int32 names the basis of a row.  With A the basis of the row, a_f its row f and r its rank:
+ * nvalid = the kept samples, s = sum_f omega_f / nf; nvalid < min_valid (min_valid <= 0: r) or nvalid = 0 gives
+ * info = -1; G = sum_f omega_f a_f a_f^T + ridge s I = L L^T, a pivot that is not finite or not > 0 at column j gives
+ * info = j + 1; c = G^-1 sum_f omega_f a_f x_f, model_f = a_f^T c, v_f = |L^-1 a_f|^2.  mode 0 (model): x_out = model
+ * everywhere, w_out = w on kept samples and 0 on flagged ones; 1 (filter): x_out = x - model on kept samples and 0 on
+ * flagged, w_out as before; 2 (inpaint): x_out = x bit for bit on kept samples and model on flagged, w_out = w on kept
+ * and 1 / v_f on flagged (0 where v_f is not finite and positive).  A series that is not solved (info != 0) gives
+ * x_out = x on kept samples (0 in mode 0) and 0 on flagged, w_out = w on kept and 0 on flagged.  A basis_of entry
+ * outside [0, nbasis) gives info = -2 for the series of its row, which are handled as not solved.  info (nrow, nt) int32.
+ * x_out may be x and w_out may be w.  No floating-point atomics; the bits of a (row, t) depend on nothing else in the
+ * launch; the accumulation orders are those of section 4.23.  Refused before any launch (dm_last_error): negative sizes,
+ * another mode, a ridge that is not finite or negative, and with work to do: nf > dm_delay_max_nf(), nbasis < 1 or
+ * > 256, a rank < 1, > nf or > dm_delay_max_rank(), a null pointer other than w, an output sharing an element with an
+ * input (other than x_out == x, w_out == w) or with another output.  nf, nrow or nt = 0 is a no-op.  Returns when the
+ * work is queued on the context's stream.  No counterpart in the reference. */
+int dm_delay_fit(dm_ctx* ctx, int nf, int nrow, int nt, int mode, double ridge, int min_valid, int nbasis,
+                 const int* rank_host, const double* basis_dev, const int* basis_of_dev, const void* x_dev,
+                 const double* w_dev, void* xout_dev, double* wout_dev, int* info_dev);
+/* the most frequencies and the largest rank dm_delay_fit takes (host only) */
+int dm_delay_max_nf(void);
+int dm_delay_max_rank(void);
+/* the series of consecutive t that one workgroup of dm_delay_fit takes for nf frequencies and a largest rank max_rank
+ * in the table; 0 for a pair it does not take (host only) */
+int dm_delay_tile(int nf, int max_rank);
+
 #ifdef __cplusplus
 }
 #endif
