@@ -149,6 +149,9 @@ SIGNATURES = {
         c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_i64, ctypes.POINTER(c_int), ctypes.POINTER(c_i64), c_int, c_int,
                 c_int, ctypes.c_uint64, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64]),
     "dm_source_alm": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_sz]),
+    "dm_alm_at_points": (
+        c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64,
+                c_i64, c_vp, c_int, c_sz]),
     "dm_bt_beam_cyl": (
         c_int, [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int,
                 ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), c_int, c_dbl, c_vp]),
@@ -1859,6 +1862,46 @@ def _source_alm(self, z, sth, phi, flux, lmax, m_lo, m_hi, out=None, max_bytes=2
     return out
 
 
+def _alm_at_points(self, z, sth, phi, ms, alm, lmax, nf, npol, strides, out=None, accumulate=False, max_bytes=2 << 30):
+    """Values (npts, npol, nf) f64 on the device of the coefficients `alm` at the points (z, sth, phi) (npts each; numpy or
+    float64 device tensors): `alm` is a contiguous complex128 device tensor of any shape and a^p_lm(f) of column j
+    (m = ms[j]) sits at f strides[0] + p strides[1] + l strides[2] + j strides[3] complex elements in it
+    (dm_alm_at_points in include/driftmi.h).  Every element the call addresses must lie inside `alm`: checked here."""
+    def dev(a):
+        if not hasattr(a, "data_ptr"):
+            a = self.to_device(np.asarray(a, dtype=np.float64))
+        if a.dtype != self.torch.float64:
+            raise ValueError("alm_at_points: float64 expected")
+        return a.contiguous()
+
+    z, sth, phi = dev(z), dev(sth), dev(phi)
+    npts = int(z.shape[0]) if z.dim() == 1 else -1
+    if npts < 0 or not (tuple(sth.shape) == tuple(phi.shape) == (npts,)):
+        raise ValueError("alm_at_points: z, sth and phi need one entry per point")
+    mm, mmp = _iarr(ms)
+    nm, lmax, nf, npol = int(mm.shape[0]), int(lmax), int(nf), int(npol)
+    sf, sp, sl, sm = [int(v) for v in strides]
+    if not (alm.is_cuda and alm.is_complex() and alm.element_size() == 16 and alm.is_contiguous()):
+        raise ValueError("alm_at_points: the coefficients must be a contiguous complex128 device tensor")
+    if lmax < 0 or min(sf, sp, sl, sm) < 0:
+        raise ValueError("alm_at_points: lmax >= 0 and non-negative strides expected")
+    if nm and nf > 0 and npol > 0:
+        last = (nf - 1) * sf + (npol - 1) * sp + lmax * sl + (nm - 1) * sm
+        if last >= alm.numel():
+            raise ValueError("alm_at_points: the call would read outside its coefficients")
+    shape = (max(npts, 0), max(npol, 0), max(nf, 0))
+    if out is None:
+        if accumulate:
+            raise ValueError("alm_at_points: accumulate needs the output to add to")
+        out = self.empty(shape, np.float64)
+    if tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != self.torch.float64:
+        raise ValueError("alm_at_points: out must be a contiguous %s float64 tensor" % (shape,))
+    rc = self.lib.dm_alm_at_points(self.h, npts, self.ptr(z), self.ptr(sth), self.ptr(phi), nm, mmp, lmax, nf, npol, self.ptr(alm),
+                                   sf, sp, sl, sm, self.ptr(out), int(bool(accumulate)), int(max_bytes))
+    self.check(rc, "dm_alm_at_points")
+    return out
+
+
 def _psmc_moments(self, q):
     """(mean (nblk, nq), covariance (nblk, nq, nq)) on the device of q (nblk, nq, ns) f64; see dm_psmc_moments."""
     nblk, nq, ns = [int(x_) for x_ in q.shape]
@@ -1888,6 +1931,7 @@ Context.psmc_moments = _psmc_moments
 Context.psmc_alt = _psmc_alt
 Context.sky_draw = _sky_draw
 Context.source_alm = _source_alm
+Context.alm_at_points = _alm_at_points
 
 
 def _project_diag(self, beam_ut, svnum, dmat, out, out_off, alpha=1.0, accumulate=False):

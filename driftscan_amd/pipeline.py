@@ -24,7 +24,10 @@ exceptions and methods.  Two deliberate differences:
 
 One knob of this package: ``batched`` (default True) runs the m-mode chain and the a_lm stage of the SVD / KL map-makers
 in device batches (``Timestream.generate_modes_batched``, ``mapmake_svd_batched``, ``mapmake_kl_batched``); False runs the
-per-m methods.  Both write the same files.
+per-m methods.  Both write the same files.  And one list beside ``klmaps``: ``catalogues``, entries ``{name, file, source:
+svd | <klname>, wiener, stack: {halfwidth, ...}}``, each of which writes ``spectra_<name>.hdf5`` per timestream in the maps
+stage — the spectrum of the estimated sky at every position of the catalogue ``file`` and, when the catalogue carries
+redshifts, their stack (``Timestream.catalogue_spectra``; needs ``batched``).  The default ``[]`` changes nothing.
 
     python -m driftscan_amd.pipeline params.yaml
 """
@@ -57,6 +60,9 @@ class PipelineManager(config.Reader):
     klmodes = config.Property(proptype=list, default=[])
     powerspectra = config.Property(proptype=list, default=[])
     klmaps = config.Property(proptype=list, default=[])
+    # spectra at catalogue positions and their stack (not in the reference): entries {name, file, source: svd | <klname>,
+    # wiener, stack: {halfwidth, line_mhz, source_weight, channel_weight}}; run in the maps stage when `batched` is on
+    catalogues = config.Property(proptype=list, default=[])
 
     nside = config.Property(proptype=int, default=128)
     wiener = config.Property(proptype=bool, default=False)
@@ -253,6 +259,8 @@ class PipelineManager(config.Reader):
                         tsobj.mapmake_kl_batched(self.nside, "map_%s.hdf5" % klname, wiener=self.wiener, chunk_gb=self.chunk_gb)
                     else:
                         tsobj.mapmake_kl(self.nside, "map_%s.hdf5" % klname, wiener=self.wiener)
+                for entry in self.catalogues:
+                    self._catalogue(tsname, tsobj, entry)
                 logger.info("Generating SVD map (%s)", tsname)
                 if self.batched:
                     tsobj.mapmake_svd_batched(self.nside, "map_svd.hdf5", chunk_gb=self.chunk_gb)
@@ -260,6 +268,23 @@ class PipelineManager(config.Reader):
                     tsobj.mapmake_svd(self.nside, "map_svd.hdf5")
                 logger.info("Generating full map (%s)", tsname)
                 tsobj.mapmake_full(self.nside, "map_full.hdf5")
+
+    def _catalogue(self, tsname, tsobj, entry):
+        """One entry of `catalogues` on one timestream: `Timestream.catalogue_spectra` writes spectra_<name>.hdf5."""
+        entry = dict(entry)
+        unknown = set(entry) - {"name", "file", "source", "wiener", "stack"}
+        if unknown or "name" not in entry or "file" not in entry:
+            raise ValueError("catalogues: an entry needs name and file, and may carry source, wiener and stack; got %s"
+                             % sorted(entry))
+        if not self.batched:
+            raise ValueError("catalogues: the spectra at catalogue positions need the batched device route (batched: true)")
+        source = entry.get("source", "svd")
+        logger.info("Spectra at the positions of %s (%s:%s)", entry["name"], tsname, source)
+        if source != "svd":
+            tsobj.set_kltransform(source)
+        tsobj.catalogue_spectra(fixpath(entry["file"]), source="svd" if source == "svd" else "kl",
+                                wiener=bool(entry.get("wiener", self.wiener)), chunk_gb=self.chunk_gb, name=entry["name"],
+                                stack=entry.get("stack", None))
 
     run = generate
 

@@ -581,13 +581,13 @@ _CAT_KEYS = ("theta", "phi", "flux", "nu0", "index", "curvature")
 
 def read_catalogue(cat):
     """A catalogue as a dict of float64 arrays: ``theta``, ``phi`` (nsrc, rad), ``flux`` (nsrc, 1 or 4) in Jy at ``nu0``
-    (MHz, a scalar or one per source), ``index`` and ``curvature`` (nsrc; the latter 0 when absent).  ``cat``: such a dict,
+    (MHz, a scalar or one per source), ``index`` and ``curvature`` (nsrc; the latter 0 when absent), and ``redshift`` (nsrc) only when the catalogue carries it.  ``cat``: such a dict,
     or the name of a file written by `write_catalogue` (`.npz` or HDF5 through `storage.File`)."""
     if isinstance(cat, (str, bytes)) or hasattr(cat, "__fspath__"):
         from . import storage
 
         with storage.File(cat, "r") as f:
-            cat = {k: np.asarray(f[k][:]) for k in _CAT_KEYS if k in f}
+            cat = {k: np.asarray(f[k][:]) for k in _CAT_KEYS + ("redshift",) if k in f}
     missing = [k for k in ("theta", "phi", "flux", "nu0", "index") if k not in cat]
     if missing:
         raise ValueError("source catalogue without %s" % ", ".join(missing))
@@ -607,6 +607,11 @@ def read_catalogue(cat):
         raise ValueError("source catalogue: theta outside [0, pi]")
     if n and not np.all(out["nu0"] > 0.0):
         raise ValueError("source catalogue: nu0 must be positive")
+    if cat.get("redshift", None) is not None:   # optional: the objects of a stacking catalogue (`Timestream.catalogue_spectra`)
+        red = np.asarray(cat["redshift"], dtype=np.float64).reshape(-1)
+        if red.shape != (n,):
+            raise ValueError("source catalogue: redshift needs one value per source")
+        out["redshift"] = red.copy()
     return out
 
 
@@ -616,7 +621,7 @@ def write_catalogue(fname, cat):
 
     cat = read_catalogue(cat)
     with storage.File(fname, "w") as f:
-        for k in _CAT_KEYS:
+        for k in _CAT_KEYS + (("redshift",) if "redshift" in cat else ()):
             f.create_dataset(k, data=cat[k])
 
 
@@ -753,3 +758,203 @@ def source_alm(cat_or_arrays, lmax, frequencies=None, mmax=None, m_range=None, f
     ctx = get_context()
     out = ctx.source_alm(z, sth, phi, flux, lmax, m_lo, m_hi, max_bytes=max_bytes)
     return ctx.to_host(out) if to_host else out
+
+
+# ---- coefficients at catalogue positions and their stack --------------------------------------
+POINTS_FBLOCK = 8            # frequencies of one call are cut in multiples of this: the blocks of dm_points.hip (8 and 4)
+LINE_21CM_MHZ = 1420.40575177
+
+
+def _point_arrays(theta, phi, npol):
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    phi = np.mod(np.asarray(phi, dtype=np.float64).reshape(-1), 2.0 * np.pi)            # [0, 2 pi) on entry
+    phi = np.where(phi >= 2.0 * np.pi, 0.0, phi)
+    if theta.shape != phi.shape:
+        raise ValueError("points: theta and phi need one entry per point")
+    if theta.size and not (np.all(theta >= 0.0) and np.all(theta <= np.pi)):
+        raise ValueError("points: theta outside [0, pi]")
+    z, sth = np.cos(theta), np.sin(theta)
+    if npol == 4:
+        bad = np.nonzero(sth == 0.0)[0]
+        if bad.size:
+            raise ValueError("points: point %d lies at a pole (sin theta = 0): Q and U are undefined there" % bad[0])
+    return z, sth, phi
+
+
+def _points_ms(ms, nm, lmax):
+    ms = np.arange(nm, dtype=np.int64) if ms is None else np.asarray(ms, dtype=np.int64).reshape(-1)
+    if ms.shape != (nm,):
+        raise ValueError("points: ms needs one m per column of the coefficients (%d), got %d" % (nm, ms.size))
+    if nm and (ms.min() < 0 or ms.max() > lmax or np.unique(ms).size != nm):
+        raise ValueError("points: the m of ms must be distinct and within 0 .. lmax = %d" % lmax)
+    return ms
+
+
+def read_positions(cat_or_arrays):
+    """(theta, phi, redshift or None) of a stacking catalogue: arrays ``(theta, phi)`` or ``(theta, phi, redshift)``, a
+    dict with those keys, or the name of a file that holds them (a file of `write_catalogue` is one).  Fluxes and spectra
+    are not needed and not looked at."""
+    if isinstance(cat_or_arrays, (tuple, list)):
+        if len(cat_or_arrays) not in (2, 3):
+            raise ValueError("points: (theta, phi) or (theta, phi, redshift) expected")
+        cat = dict(zip(("theta", "phi", "redshift"), cat_or_arrays))
+    elif isinstance(cat_or_arrays, (str, bytes)) or hasattr(cat_or_arrays, "__fspath__"):
+        from . import storage
+
+        with storage.File(cat_or_arrays, "r") as f:
+            cat = {k: np.asarray(f[k][:]) for k in ("theta", "phi", "redshift") if k in f}
+    else:
+        cat = cat_or_arrays
+    if "theta" not in cat or "phi" not in cat:
+        raise ValueError("points: a catalogue needs theta and phi")
+    theta = np.asarray(cat["theta"], dtype=np.float64).reshape(-1)
+    phi = np.asarray(cat["phi"], dtype=np.float64).reshape(-1)
+    red = cat.get("redshift", None)
+    if red is not None:
+        red = np.asarray(red, dtype=np.float64).reshape(-1)
+        if red.shape != theta.shape:
+            raise ValueError("points: redshift needs one entry per point")
+    return theta, phi, red
+
+
+def alm_at_points_host(alm, theta, phi, ms=None):
+    """The coefficients ``alm`` (nf, npol, lmax + 1, nm), npol = 1 (T) or 4 (T, E, B, V), column j holding m = ms[j]
+    (default j), evaluated at the points (theta, phi): (npts, npol, nf) float64, polarisations T or T, Q, U, V.  With
+    fac = 1 for m = 0 and 2 otherwise
+
+        F^T_m(s) = sum_l a^T_lm lambda_lm(z_s)  (F^V alike)
+        F^Q_m(s) = sum_l a^E_lm W_lm + i a^B_lm X_lm,    F^U_m(s) = sum_l a^B_lm W_lm - i a^E_lm X_lm
+        value_p(s, f) = sum_m fac_m Re(F^p_m(s) e^{+i m phi_s})
+
+    the value of `healpix.sphtrans_inv_sky_host` with (z, phi) of a point in the place of (ring, pixel), and the adjoint of
+    `source_alm_host`.  z = cos(theta), phi reduced to [0, 2 pi), the phase argument the float64 product m * phi.  A
+    subset ``ms`` gives a partial sum.  Plain numpy: the oracle of `alm_at_points`, for any input."""
+    from . import healpix
+
+    alm = np.asarray(alm, dtype=np.complex128)
+    if alm.ndim != 4 or alm.shape[1] not in (1, 4):
+        raise ValueError("points: coefficients (nf, 1 or 4, lmax + 1, nm) expected, got %s" % (alm.shape,))
+    nf, npol, L, nm = alm.shape
+    lmax = L - 1
+    ms = _points_ms(ms, nm, lmax)
+    z, sth, phi = _point_arrays(theta, phi, npol)
+    out = np.zeros((nf, npol, z.size))
+    for j, m in enumerate(int(v) for v in ms):
+        lam = healpix.lambda_lm(lmax, m, z)                          # (L - m, npts)
+        a = alm[:, :, m:, j]
+        F = np.zeros((nf, npol, z.size), dtype=np.complex128)
+        F[:, 0] = a[:, 0] @ lam
+        if npol == 4:
+            W, X = healpix.wx_lm(lmax, m, z)
+            F[:, 1] = a[:, 1] @ W + 1j * (a[:, 2] @ X)
+            F[:, 2] = a[:, 2] @ W - 1j * (a[:, 1] @ X)
+            F[:, 3] = a[:, 3] @ lam
+        arg = m * phi
+        out += (1.0 if m == 0 else 2.0) * (F.real * np.cos(arg) - F.imag * np.sin(arg))
+    return np.ascontiguousarray(out.transpose(2, 1, 0))
+
+
+def alm_at_points(alm, cat_or_arrays, ms=None, to_host=True, max_bytes=2 << 30, out=None, accumulate=False):
+    """`alm_at_points_host` on the device (`dm_alm_at_points`: one fused kernel, the recurrence in registers and no table
+    in memory): (npts, npol, nf) float64 — a spectrum per object, no map and no nside.  ``alm`` (nf, npol, lmax + 1, nm):
+    numpy, or a complex128 device tensor (any strides of a contiguous tensor's view are not followed: it is made
+    contiguous).  ``cat_or_arrays``: see `read_positions`.  ``to_host=False`` returns the device tensor; ``out`` (such a
+    tensor) with ``accumulate`` adds the values of this call to it.  ``max_bytes`` bounds the coefficients alive on the
+    device beyond ``alm`` itself — host coefficients go up in runs of whole blocks of `POINTS_FBLOCK` frequencies — and
+    has no influence on the bits, and neither has the set of points of a call."""
+    from .device import get_context
+
+    theta, phi, _ = read_positions(cat_or_arrays)
+    on_device = bool(getattr(alm, "is_cuda", False))
+    if on_device and not (alm.is_complex() and alm.element_size() == 16):
+        raise ValueError("alm_at_points: a device tensor must be complex128, got %s" % (alm.dtype,))
+    if not on_device:
+        alm = np.asarray(alm, dtype=np.complex128)
+    if len(alm.shape) != 4 or int(alm.shape[1]) not in (1, 4):
+        raise ValueError("points: coefficients (nf, 1 or 4, lmax + 1, nm) expected, got %s" % (tuple(alm.shape),))
+    nf, npol, L, nm = [int(v) for v in alm.shape]
+    ms = _points_ms(ms, nm, L - 1)
+    z, sth, phi = _point_arrays(theta, phi, npol)
+    ctx = get_context()
+    npts = z.size
+    if out is None:
+        if accumulate:
+            raise ValueError("alm_at_points: accumulate needs the output to add to")
+        out = ctx.empty((npts, npol, nf), np.float64)
+    if npts and nf:
+        if nm == 0:
+            if not accumulate:
+                out.zero_()
+        elif on_device:
+            a = alm.contiguous()
+            ctx.alm_at_points(z, sth, phi, ms, a, L - 1, nf, npol, (npol * L * nm, L * nm, nm, 1), out=out,
+                              accumulate=accumulate, max_bytes=max_bytes)
+        else:
+            dz, ds, dp = ctx.to_device(z), ctx.to_device(sth), ctx.to_device(phi)
+            per_f = 2 * 16 * npol * L * nm                                             # the upload and its re-ordered copy
+            step = max(1, int(max_bytes // (POINTS_FBLOCK * per_f))) * POINTS_FBLOCK
+            for f0 in range(0, nf, step):
+                f1 = min(nf, f0 + step)
+                a = ctx.to_device(alm[f0:f1])
+                part = out if (f0, f1) == (0, nf) else ctx.empty((npts, npol, f1 - f0), np.float64)
+                if part is not out and accumulate:
+                    part.copy_(out[:, :, f0:f1])
+                ctx.alm_at_points(dz, ds, dp, ms, a, L - 1, f1 - f0, npol, (npol * L * nm, L * nm, nm, 1), out=part,
+                                  accumulate=accumulate, max_bytes=max(max_bytes // 2, 1))
+                if part is not out:
+                    out[:, :, f0:f1] = part
+                del a, part
+    return ctx.to_host(out) if to_host else out
+
+
+def stack_spectra(spectra, freqs_mhz, line_mhz, halfwidth, source_weight=None, channel_weight=None):
+    """Stack spectra (nsrc, npol, nf) on the channel of each source's line.  ``freqs_mhz`` (nf >= 2, strictly ascending or
+    descending) are the channel centres, ``line_mhz`` (nsrc) the observed frequency of the line of every source
+    (`LINE_21CM_MHZ` / (1 + redshift) for 21 cm).  The channel of a source is c_s = argmin_f |nu_f - nu_s|; a source
+    whose line lies more than half a channel (half the spacing of the two end channels) outside the band is dropped.
+    For the offsets k = -K .. K, K = ``halfwidth``, counted along the axis as stored,
+
+        stack[p, k] = sum_s w_s omega_{c_s + k} T[s, p, c_s + k] / sum_s w_s omega_{c_s + k}
+
+    over the kept sources whose channel c_s + k exists and has omega > 0; ``source_weight`` w (nsrc, default 1, >= 0) and
+    ``channel_weight`` omega (nf, default 1, >= 0).  Returns a dict: ``stack`` (npol, 2K + 1; 0 where nothing
+    contributed), ``hits`` (2K + 1: the number of terms with non-zero weight), ``weight`` (2K + 1: the denominators),
+    ``offsets`` (-K .. K), ``channel`` (nsrc: c_s, -1 for dropped sources).  No sub-channel interpolation.  Host numpy: one
+    pass over an array the size of the input."""
+    T = np.asarray(spectra, dtype=np.float64)
+    nu = np.asarray(freqs_mhz, dtype=np.float64).reshape(-1)
+    line = np.asarray(line_mhz, dtype=np.float64).reshape(-1)
+    K = int(halfwidth)
+    if T.ndim != 3 or T.shape[2] != nu.size or T.shape[0] != line.size:
+        raise ValueError("stack_spectra: spectra (nsrc, npol, nf) with nf frequencies and nsrc lines expected")
+    if K < 0 or nu.size < 2:
+        raise ValueError("stack_spectra: halfwidth >= 0 and two frequencies at least expected")
+    d = np.diff(nu)
+    if not (np.all(d > 0.0) or np.all(d < 0.0)):
+        raise ValueError("stack_spectra: frequencies must ascend or descend strictly")
+    nsrc, npol, nf = T.shape
+    w = np.ones(nsrc) if source_weight is None else np.asarray(source_weight, dtype=np.float64).reshape(-1)
+    om = np.ones(nf) if channel_weight is None else np.asarray(channel_weight, dtype=np.float64).reshape(-1)
+    if w.shape != (nsrc,) or om.shape != (nf,) or (w < 0.0).any() or (om < 0.0).any():
+        raise ValueError("stack_spectra: non-negative weights, one per source and one per channel, expected")
+    offsets = np.arange(-K, K + 1)
+    if nsrc == 0:
+        chan = np.zeros(0, dtype=np.int64)
+    else:
+        chan = np.argmin(np.abs(nu[None, :] - line[:, None]), axis=1)
+        # the band ends half a channel beyond the centres of its end channels
+        lo, hi = (0, nf - 1) if d[0] > 0.0 else (nf - 1, 0)
+        below = line < nu[lo] - 0.5 * abs(d[0] if lo == 0 else d[-1])
+        above = line > nu[hi] + 0.5 * abs(d[-1] if hi == nf - 1 else d[0])
+        chan = np.where(below | above | ~np.isfinite(line), -1, chan)
+    idx = chan[:, None] + offsets[None, :]                                               # (nsrc, 2K + 1)
+    ok = (chan[:, None] >= 0) & (idx >= 0) & (idx < nf)
+    idc = np.where(ok, idx, 0)
+    wt = np.where(ok, w[:, None] * om[idc], 0.0)                                         # (nsrc, 2K + 1)
+    vals = np.take_along_axis(T, np.broadcast_to(idc[:, None, :], (nsrc, npol, offsets.size)), axis=2) if nsrc else \
+        np.zeros((0, npol, offsets.size))
+    num = np.einsum("sk,spk->pk", wt, np.where(wt[:, None, :] > 0.0, vals, 0.0))
+    den = wt.sum(axis=0)
+    stack = np.where(den > 0.0, num / np.where(den > 0.0, den, 1.0), 0.0)
+    return dict(stack=stack, hits=np.count_nonzero(wt > 0.0, axis=0).astype(np.int64), weight=den, offsets=offsets,
+                channel=chan.astype(np.int64))

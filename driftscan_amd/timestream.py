@@ -415,10 +415,12 @@ class Timestream(object):
         self._alm_to_map(lambda mi: self.beamtransfer.project_vector_svd_to_sky(mi, self.mmode_svd(mi)), nside, mapname)
 
     # ---- batched map-making: the a_lm stage of mapmake_svd / mapmake_kl in device batches ----------------------------
-    def _alm_batches(self, mlist, vectors, chunk_gb, extra_bytes=None):
+    def _alm_batches(self, mlist, vectors, chunk_gb, extra_bytes=None, on_batch=None):
         """[(m, a_lm (nfreq, npol, lmax + 1))] for the m of this rank: `vectors(batch)` gives the packed SVD vectors of a
         batch on the device (rows, 1) and their row offsets; `invbeam_svd` of the batch is uploaded once and applied in
-        one launch."""
+        one launch.  With `on_batch`, every batch is handed on as `on_batch(batch, a_lm)` — the list of its m and the
+        device tensor (len(batch), nfreq, npol, lmax + 1, 1) — instead of being brought to the host, and the list that
+        comes back is empty."""
         ctx = get_context()
         bt, tel = self.beamtransfer, self.telescope
 
@@ -428,7 +430,11 @@ class Timestream(object):
         out = []
         for batch in self._m_batches(parallel.partition(mlist), per_m, chunk_gb):
             svec, off = vectors(batch)
-            alm = ctx.to_host(bt.project_vectors_svd_to_sky_device(batch, svec, off=off))[..., 0]
+            dev = bt.project_vectors_svd_to_sky_device(batch, svec, off=off)
+            if on_batch is not None:
+                on_batch(list(batch), dev)
+                continue
+            alm = ctx.to_host(dev)[..., 0]
             out.extend((mi, np.ascontiguousarray(alm[i])) for i, mi in enumerate(batch))
         return out
 
@@ -438,15 +444,19 @@ class Timestream(object):
         packed = np.concatenate(list(vecs) + [np.zeros((1,), dtype=np.complex128)])   # (never empty)
         return get_context().to_device(packed[:, None]), off
 
-    def alm_svd_batched(self, mlist=None, chunk_gb=4.0):
-        """The a_lm stage of `mapmake_svd` for this rank's share of `mlist`: [(m, (nfreq, npol, lmax + 1))]."""
+    def alm_svd_batched(self, mlist=None, chunk_gb=4.0, on_batch=None):
+        """The a_lm stage of `mapmake_svd` for this rank's share of `mlist`: [(m, (nfreq, npol, lmax + 1))].  `on_batch`:
+        a function (batch, device tensor (len(batch), nfreq, npol, lmax + 1, 1)) that takes every batch on the device
+        instead; the list is then empty."""
         mlist = list(range(self.telescope.mmax + 1)) if mlist is None else list(mlist)
-        return self._alm_batches(mlist, lambda batch: self._packed_device([self.mmode_svd(mi) for mi in batch]), chunk_gb)
+        return self._alm_batches(mlist, lambda batch: self._packed_device([self.mmode_svd(mi) for mi in batch]), chunk_gb,
+                                 on_batch=on_batch)
 
-    def alm_kl_batched(self, mlist=None, wiener=False, chunk_gb=4.0):
+    def alm_kl_batched(self, mlist=None, wiener=False, chunk_gb=4.0, on_batch=None):
         """The a_lm stage of `mapmake_kl` for this rank's share of `mlist` (default: all m but m = 0 under `no_m_zero`):
         KL modes, optionally Wiener weighted by lambda / (1 + lambda), through the stored inverse modes back to the SVD
-        basis and through `invbeam_svd` to the sky, without leaving the device in between."""
+        basis and through `invbeam_svd` to the sky, without leaving the device in between.  `on_batch` as in
+        `alm_svd_batched`."""
         kl = self.manager.kltransforms[self.klname]
         thr = self.klthreshold
         bt = self.beamtransfer
@@ -468,7 +478,89 @@ class Timestream(object):
         def extra(mi):
             return 16.0 * float(bt.ndof(mi)) ** 2
 
-        return self._alm_batches(mlist, vectors, chunk_gb, extra_bytes=extra)
+        return self._alm_batches(mlist, vectors, chunk_gb, extra_bytes=extra, on_batch=on_batch)
+
+    # ---- spectra at catalogue positions ---------------------------------------------------------
+    def catalogue_spectra(self, cat, source="svd", wiener=False, chunk_gb=4.0, name=None, stack=None):
+        """The spectrum of the estimated sky at every position of a catalogue, and the stack of those spectra on each
+        object's line: `spectra_<name>.hdf5` in the output directory; returns its path, at once if the file exists.
+
+        The a_lm are those of `mapmake_svd_batched` (``source="svd"``) or `mapmake_kl_batched` (``source="kl"``: the KL
+        transform set by `set_kltransform`, which needs `inverse`; ``wiener`` as there; m = 0 left out under
+        `no_m_zero`).  Every batch of m stays on the device and goes through `skysim.alm_at_points`' kernel at the
+        positions of ``cat`` (`skysim.read_positions`: arrays, a dict or a file) — no map, no nside, a source sits where
+        the catalogue puts it.  A rank sums over its own m, batch after batch; the partial sums are added on rank 0 in
+        rank order.  Datasets: ``spectra`` (nsrc, npol, nfreq) with polarisations T or T, Q, U, V, ``theta``, ``phi``,
+        ``freq`` (MHz), ``ms_used``.  When the catalogue has ``redshift`` or ``stack`` (a dict) is given, also ``stack``
+        (npol, 2 K + 1), ``hits``, ``offsets``, ``stack_weight`` and ``channel`` of `skysim.stack_spectra` with
+        K = stack["halfwidth"] (default 2), lines at stack["line_mhz"] (default the 21 cm line) / (1 + redshift) and the
+        optional stack["source_weight"] and stack["channel_weight"].  ``name`` defaults to the source (and the KL name)."""
+        from . import skysim
+
+        if source not in ("svd", "kl"):
+            raise ValueError("catalogue_spectra: source is 'svd' or 'kl', got %r" % (source,))
+        if name is None:
+            name = "svd" if source == "svd" else "kl_%s" % self.klname
+        fname = self.output_directory + "/spectra_%s.hdf5" % name
+        if os.path.exists(fname):
+            return fname
+        theta, phi, red = skysim.read_positions(cat)
+        if stack is not None and red is None:
+            raise ValueError("catalogue_spectra: a stack needs the redshifts of the catalogue")
+        conf = dict(stack or {})
+        unknown = set(conf) - {"halfwidth", "line_mhz", "source_weight", "channel_weight"}
+        if unknown:
+            raise ValueError("catalogue_spectra: unknown stack key(s) %s" % ", ".join(sorted(unknown)))
+        tel = self.telescope
+        npol, nfreq = int(tel.num_pol_sky), int(tel.nfreq)
+        z, sth, phr = skysim._point_arrays(theta, phi, npol)
+        ctx = get_context()
+        nsrc = z.size
+        acc = ctx.zeros((nsrc, npol, nfreq), np.float64)
+        dz, ds, dp = (ctx.to_device(z), ctx.to_device(sth), ctx.to_device(phr)) if nsrc else (None, None, None)
+        L = int(tel.lmax) + 1
+        used = []
+
+        def on_batch(batch, alm):
+            used.extend(int(mi) for mi in batch)
+            if nsrc and len(batch):
+                ctx.alm_at_points(dz, ds, dp, batch, alm, L - 1, nfreq, npol, (npol * L, L, 1, nfreq * npol * L), out=acc,
+                                  accumulate=True, max_bytes=int(chunk_gb * (1 << 30)))
+
+        if source == "svd":
+            self.generate_modes_batched(chunk_gb=chunk_gb)
+            self.alm_svd_batched(chunk_gb=chunk_gb, on_batch=on_batch)
+        else:
+            if not self.manager.kltransforms[self.klname].inverse:
+                raise Exception("Need the inverse to evaluate the KL-filtered sky.")
+            self.alm_kl_batched(wiener=wiener, chunk_gb=chunk_gb, on_batch=on_batch)
+        parts = parallel.gather_objects((ctx.to_host(acc), used))
+        if parallel.rank0():
+            spectra = np.zeros((nsrc, npol, nfreq), dtype=np.float64)
+            ms_used = []
+            for part, ms in parts:                        # in rank order
+                spectra += part
+                ms_used.extend(ms)
+            freq = np.asarray(tel.frequencies, dtype=np.float64)
+            os.makedirs(self.output_directory, exist_ok=True)
+            with storage.File(fname, "w") as f:
+                f.create_dataset("spectra", data=spectra)
+                f.create_dataset("theta", data=np.asarray(theta, dtype=np.float64))
+                f.create_dataset("phi", data=np.asarray(phi, dtype=np.float64))
+                f.create_dataset("freq", data=freq)
+                f.create_dataset("ms_used", data=np.asarray(sorted(ms_used), dtype=np.int64))
+                if red is not None:
+                    line = float(conf.get("line_mhz", skysim.LINE_21CM_MHZ)) / (1.0 + red)
+                    st = skysim.stack_spectra(spectra, freq, line, int(conf.get("halfwidth", 2)),
+                                              source_weight=conf.get("source_weight"), channel_weight=conf.get("channel_weight"))
+                    f.create_dataset("redshift", data=red)
+                    f.create_dataset("stack", data=st["stack"])
+                    f.create_dataset("hits", data=st["hits"])
+                    f.create_dataset("offsets", data=st["offsets"].astype(np.int64))
+                    f.create_dataset("stack_weight", data=st["weight"])
+                    f.create_dataset("channel", data=st["channel"])
+        parallel.barrier()
+        return fname
 
     def _write_map(self, parts, nside, mapname):
         tel = self.telescope

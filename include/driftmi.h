@@ -484,6 +484,30 @@ int dm_sky_draw(dm_ctx* ctx, int n, int L, int M, const double* T_dev, int ldT, 
 int dm_source_alm(dm_ctx* ctx, int nsrc, const double* z_dev, const double* sth_dev, const double* phi_dev, int nf,
                   int npol, const double* flux_dev, int lmax, int m_lo, int m_hi, void* alm_dev, size_t max_bytes);
 
+/* dm_alm_at_points: spherical-harmonic coefficients evaluated at npts points — the adjoint of dm_source_alm and the
+ * synthesis of dm_sht_synth with (z, phi) of a point in the place of (ring, pixel).  With fac = 1 for m = 0, 2 otherwise:
+ *   F^T_m(s) = sum_l a^T_lm lambda_lm(z_s)   (F^V alike)
+ *   F^Q_m(s) = sum_l a^E_lm W_lm(s) + i a^B_lm X_lm(s),   F^U_m(s) = sum_l a^B_lm W_lm(s) - i a^E_lm X_lm(s)
+ *   value_p(s, f) = sum_{j < nm} fac_m Re(F^p_m(s) e^{+i m phi_s}),  m = ms[j]
+ *   z_dev, sth_dev, phi_dev  (npts) f64: cos and sin of the colatitude, and the longitude reduced to [0, 2 pi)
+ *   ms_host                  (nm) the m of column j of the coefficients: distinct, 0 .. lmax, any order (nm = 0: no term)
+ *   alm_dev                  c128: a^p_lm(f) at f stride_f + p stride_p + l stride_l + j stride_m complex elements,
+ *                            p = (T) or (T, E, B, V); elements with l < m are not read
+ *   out_dev                  (npts, npol, nf) f64, polarisations (T) or (T, Q, U, V): the layout of a spectrum per object
+ *   accumulate               0: out = value; otherwise out += value (the sum over the m of the call is formed first)
+ * A partial `ms` gives a partial sum; partial sums over disjoint subsets add up to the whole.  One fused kernel runs the
+ * recurrence of the Legendre tables in registers, a lane per point and block of frequencies (8 for npol = 1, 4 for
+ * npol = 4): no table is written.  A lane adds l ascending inside an m and the m in the order of ms, so the bits of a
+ * value do not depend on the other points, on cutting the points or (in multiples of the block) the frequencies into
+ * several calls, or on max_bytes, which bounds the re-ordered copy of the coefficients (one block of frequencies at
+ * least; the recurrence coefficients, 32 bytes per (l, m), come on top).  The phase is sincos of the double product
+ * m * phi.  Errors, with nothing launched or written: npol other than 1 or 4; npts or nf below 1; an m of ms outside
+ * 0 .. lmax or repeated; npol = 4 and a point with sin theta = 0 (for npol = 1 a pole is fine).  Synchronises. */
+int dm_alm_at_points(dm_ctx* ctx, int npts, const double* z_dev, const double* sth_dev, const double* phi_dev, int nm,
+                     const int* ms_host, int lmax, int nf, int npol, const void* alm_dev, int64_t stride_f,
+                     int64_t stride_p, int64_t stride_l, int64_t stride_m, double* out_dev, int accumulate,
+                     size_t max_bytes);
+
 /* ---- beam-transfer generation (cylinder telescopes) --------------------------- */
 /* Host geometry shared by the three calls below: ring_cth_host / ring_sth_host hold
  * cos / sin of the colatitude of the 4*nside-1 HEALPix rings; frame_host (9 doubles)
