@@ -241,6 +241,9 @@ SIGNATURES = {
     "dm_delay_max_nf": (c_int, []),
     "dm_delay_max_rank": (c_int, []),
     "dm_delay_tile": (c_int, [c_int, c_int]),
+    "dm_ringmap": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_int, c_vp,
+                c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None
@@ -1346,6 +1349,66 @@ def _delay_fit(self, x, w=None, basis=None, basis_of=None, mode="inpaint", ridge
 
 
 Context.delay_fit = _delay_fit
+
+
+def _ringmap(self, vis, group_off, members, v, scale, sinza, w=None, taper=None, parts=1, out=None, norm=None, norm2=None):
+    """Ring maps: the stacked visibilities of every sample beamformed north-south (dm_ringmap, DESIGN.md section 4.25;
+    `timestream.ringmap_host` restates it).  vis (nf, nrow, nt) complex128, contiguous; w float64 of that shape or None
+    (ones): a sample is kept iff w > 0.  group_off (ngroup + 1) and members (group_off[-1]) are host integers: group g
+    is the rows members[group_off[g]:group_off[g + 1]] of vis.  v and taper (per member; taper None: ones), scale (nf,)
+    and sinza (nel,) are float64 device tensors, or anything numpy turns into such arrays.  parts 1 (the real part) or
+    2 (real and imaginary part).  Returns (map, norm, norm2): map (nf, ngroup, parts, nel, nt) and norm = D,
+    norm2 = D2 (nf, ngroup, nt), float64.  `out`, `norm` and `norm2` take tensors to write into; norm=False or
+    norm2=False leaves that output out (None is returned in its place)."""
+    torch = self.torch
+    if not (_is_c128(vis) and vis.dim() == 3):
+        raise ValueError("ringmap: contiguous complex128 tensor vis (nf, nrow, nt) expected")
+    nf, nrow, nt = (int(s) for s in vis.shape)
+    if w is not None:
+        _weights_arg("ringmap", w, vis.shape)
+    if parts not in (1, 2):
+        raise ValueError("ringmap: parts is 1 or 2")
+    off, offp = _iarr(group_off)
+    mem, memp = _iarr(members)
+    if off.ndim != 1 or off.shape[0] < 1 or mem.ndim != 1 or off[0] != 0 or np.any(np.diff(off) < 0) or mem.shape[0] != int(off[-1]):
+        raise ValueError("ringmap: group_off (ngroup + 1), from 0 and not decreasing, and members (group_off[-1]) expected")
+    if mem.size and (mem.min() < 0 or mem.max() >= nrow):
+        raise ValueError("ringmap: a member is no row of vis")
+    ngroup, nmem = off.shape[0] - 1, mem.shape[0]
+
+    def table(t, n, name):
+        if not hasattr(t, "data_ptr"):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))).to(vis.device)
+        if not (t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and n in (None, int(t.shape[0]))):
+            raise ValueError("ringmap: %s must be a contiguous float64 tensor (%s,)" % (name, "nel" if n is None else n))
+        return t
+
+    v = table(v, nmem, "v")
+    taper = None if taper is None else table(taper, nmem, "taper")
+    scale = table(scale, nf, "scale")
+    sinza = table(sinza, None, "sinza")
+    nel = int(sinza.shape[0])
+
+    def output(t, shape, name):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float64, device=vis.device)
+        if not (hasattr(t, "data_ptr") and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("ringmap: %s must be a contiguous float64 tensor %s" % (name, shape))
+        return t
+
+    out = output(out, (nf, ngroup, parts, nel, nt), "out")
+    norm = None if norm is False else output(norm, (nf, ngroup, nt), "norm")
+    norm2 = None if norm2 is False else output(norm2, (nf, ngroup, nt), "norm2")
+    if not all(t is None or (t.is_cuda and t.device == vis.device) for t in (vis, w, v, taper, scale, sinza, out, norm, norm2)):
+        raise ValueError("ringmap: vis, w, v, taper, scale, sinza and the outputs must be tensors on one GPU")
+    rc = self.lib.dm_ringmap(self.h, nf, nrow, nt, ngroup, offp, memp, self.ptr(v), self.ptr(taper), self.ptr(scale), nel,
+                             self.ptr(sinza), int(parts), self.ptr(vis), self.ptr(w), self.ptr(out), self.ptr(norm),
+                             self.ptr(norm2))
+    self.check(rc, "dm_ringmap")
+    return out, norm, norm2
+
+
+Context.ringmap = _ringmap
 
 
 def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,

@@ -28,6 +28,10 @@ per-m methods.  Both write the same files.  And one list beside ``klmaps``: ``ca
 svd | <klname>, wiener, stack: {halfwidth, ...}}``, each of which writes ``spectra_<name>.hdf5`` per timestream in the maps
 stage — the spectrum of the estimated sky at every position of the catalogue ``file`` and, when the catalogue carries
 redshifts, their stack (``Timestream.catalogue_spectra``; needs ``batched``).  The default ``[]`` changes nothing.
+And ``ringmaps``, entries ``{name, nel, weighting: natural | uniform, window: hann | blackman, ew: [...], intracyl, parts,
+collapse_ew}`` (all optional), each of which writes ``ringmap_<name>.hdf5`` per frequency and at the root of every timestream
+in the maps stage: its stacked visibilities beamformed north-south, sample by sample (``timestream.ringmap``).  It needs no
+products beyond the telescope; an unknown key raises ValueError.
 
     python -m driftscan_amd.pipeline params.yaml
 """
@@ -63,6 +67,8 @@ class PipelineManager(config.Reader):
     # spectra at catalogue positions and their stack (not in the reference): entries {name, file, source: svd | <klname>,
     # wiener, stack: {halfwidth, line_mhz, source_weight, channel_weight}}; run in the maps stage when `batched` is on
     catalogues = config.Property(proptype=list, default=[])
+    # ring maps (not in the reference): entries {name, nel, weighting, window, ew, intracyl, parts, collapse_ew}
+    ringmaps = config.Property(proptype=list, default=[])
 
     nside = config.Property(proptype=int, default=128)
     wiener = config.Property(proptype=bool, default=False)
@@ -96,6 +102,8 @@ class PipelineManager(config.Reader):
         if not yconf or "config" not in yconf:
             raise Exception("Configuration file must have an 'config' section.")
         self.read_config(yconf["config"])
+        for entry in self.ringmaps:   # an unknown key is refused before anything runs
+            timestream.ringmap_params(entry)
         self.product_directory = fixpath(self.product_directory) if self.product_directory else self.product_directory
         if "timestreams" not in yconf:
             raise Exception("Configuration file must have an 'timestream' section.")
@@ -252,6 +260,10 @@ class PipelineManager(config.Reader):
                 timestream.cross_powerspectrum(tslist, xp["psname"], os.path.abspath(fixpath(xp["psfile"])))
         if self.generate_maps:
             for tsname, tsobj in self.timestreams.items():
+                for entry in self.ringmaps:
+                    entry = timestream.ringmap_params(entry)
+                    logger.info("Generating ring map %s (%s)", entry["name"], tsname)
+                    timestream.ringmap(tsobj.manager, tsobj.directory, chunk_gb=self.chunk_gb, **entry)
                 for klname in self.klmaps:
                     logger.info("Generating KL map (%s:%s)", tsname, klname)
                     tsobj.set_kltransform(klname)

@@ -3468,3 +3468,242 @@ def delay_filter(m, indir, outdir=None, mode="inpaint", chunk_gb=4.0, ridge=0.0,
         logging.getLogger(__name__).warning("delay_filter: %d of %d series were not solved (info in delay_fit.hdf5)", unsolved, info.size)
     _save_all([] if inplace else [dst])
     return dst
+
+
+# ---- ring maps: the north-south beamformer of stacked visibilities -----------------------
+
+RINGMAP_WEIGHTINGS = ("natural", "uniform")
+RINGMAP_WINDOWS = (None, "hann", "blackman")
+
+
+def ringmap_groups(tel, ew=None, intracyl=True):
+    """The groups of a ring map of telescope `tel` (any TransitTelescope): a group is the set of unique baselines with
+    the same (beam class of feed i, beam class of feed j, rounded east-west separation u).  Returns a dict: `group_off`
+    (ngroup + 1) int32, `members` int32 (rows of the stacked data) and `v` (their signed north-south separation in m,
+    north positive), and per group `u` (m) and `pol` (ngroup, 2), the class pair.  Groups are ordered by (class pair, u),
+    the members of a group by v, then index.  `ew` picks east-west separations (in m, compared as the baselines are:
+    rounded to the telescope's tolerance); intracyl=False drops u = 0."""
+    pairs = np.asarray(tel.uniquepairs).reshape(-1, 2)
+    cls = np.asarray(tel.beamclass)
+    bl = np.asarray(tel.baselines, dtype=np.float64).reshape(-1, 2)
+    tol = int(getattr(tel, "_bl_tol", 6))
+    u = np.around(bl[:, 0], tol) + 0.0   # -0 -> 0
+    keep = np.ones(u.shape[0], dtype=bool)
+    if ew is not None:
+        want = np.around(np.atleast_1d(np.asarray(ew, dtype=np.float64)), tol)
+        if want.ndim != 1:
+            raise ValueError("ringmap_groups: ew must be a list of east-west separations")
+        keep &= np.isin(u, want)
+    if not intracyl:
+        keep &= u != 0
+    idx = np.nonzero(keep)[0]
+    ci, cj = cls[pairs[idx, 0]], cls[pairs[idx, 1]]
+    order = np.lexsort((idx, bl[idx, 1], u[idx], cj, ci))   # last key first: (ci, cj, u, v, index)
+    idx, ci, cj = idx[order], ci[order], cj[order]
+    ug = u[idx]
+    new = np.ones(idx.shape[0], dtype=bool)
+    new[1:] = (ci[1:] != ci[:-1]) | (cj[1:] != cj[:-1]) | (ug[1:] != ug[:-1])
+    first = np.nonzero(new)[0]
+    return dict(group_off=np.concatenate([first, [idx.shape[0]]]).astype(np.int32), members=idx.astype(np.int32),
+                v=np.ascontiguousarray(bl[idx, 1]), u=np.ascontiguousarray(ug[first]),
+                pol=np.stack([ci[first], cj[first]], axis=1).astype(np.int32).reshape(-1, 2))
+
+
+def ringmap_taper(tel, groups, weighting="natural", window=None):
+    """The taper T_b of every member of `groups` (`ringmap_groups`): the redundancy of the baseline ("natural") or 1
+    ("uniform"), times the window "hann" or "blackman" evaluated at v / v_edge; v_edge is the largest |v| plus the
+    smallest nonzero |v| of the table, so that no baseline gets weight 0."""
+    if weighting not in RINGMAP_WEIGHTINGS:
+        raise ValueError('ringmap_taper: weighting is "natural" or "uniform"')
+    if window not in RINGMAP_WINDOWS:
+        raise ValueError('ringmap_taper: window is None, "hann" or "blackman"')
+    members, v = np.asarray(groups["members"]), np.asarray(groups["v"], dtype=np.float64)
+    t = np.asarray(tel.redundancy, dtype=np.float64)[members] if weighting == "natural" else np.ones(members.shape[0])
+    if window is not None and v.size:
+        av = np.abs(v)
+        edge = av.max() + (av[av > 0].min() if np.any(av > 0) else 0.0)
+        x = v / edge if edge > 0 else np.zeros_like(v)
+        if window == "hann":
+            t = t * (0.5 + 0.5 * np.cos(np.pi * x))
+        else:
+            t = t * (0.42 + 0.5 * np.cos(np.pi * x) + 0.08 * np.cos(2 * np.pi * x))
+    return np.ascontiguousarray(t, dtype=np.float64)
+
+
+def ringmap_sinza(tel, groups, nel=None):
+    """`nel` points uniform on [-1, 1], the sin(zenith angle) grid of a ring map (north positive).  The default is the
+    smallest odd count (3 at the least) with two points per period of the finest fringe, that of the largest |v| of
+    `groups` at the highest frequency: a step of at most 1 / (2 |v| nu / c)."""
+    if nel is None:
+        v = np.asarray(groups["v"], dtype=np.float64)
+        turns = float(np.abs(v).max() / np.min(tel.wavelengths)) if v.size else 0.0   # the fringe rate over s, periods per unit
+        nel = max(3, int(np.ceil(4.0 * turns)) + 1)
+        nel += 1 - nel % 2
+    nel = int(nel)
+    if nel < 1:
+        raise ValueError("ringmap_sinza: nel < 1")
+    return np.linspace(-1.0, 1.0, nel) if nel > 1 else np.zeros(1)
+
+
+def ringmap_host(vis, w, group_off, members, v, scale, sinza, taper=None, parts=1, dtype=np.float64):
+    """The numpy statement of `Context.ringmap` in `dtype`, np.float64 or np.longdouble: for
+    frequency f, group g, elevation e and sample t
+        x_b(t) = T_b w_b(t) where w_b(t) > 0 and 0 elsewhere,   D = sum_b x_b,   D2 = sum_b T_b x_b,
+        tau = (scale_f v_b) s_e,   phi = tau - rint(tau),   map[0] = sum_b x_b Re(V_b exp(-2 pi i phi)) / D,
+        map[1] the imaginary part (parts = 2); 0 where D = 0,
+    with cos and sin of pi (2 phi) taken of the fraction of a turn, never of the large argument.  vis (nf, nrow, nt)
+    complex, w of that shape or None (ones), taper per member or None (ones).  Samples that are not kept enter no
+    arithmetic.  Returns (map (nf, ngroup, parts, nel, nt), D, D2 (nf, ngroup, nt))."""
+    if dtype not in (np.float64, np.longdouble):
+        raise ValueError("ringmap_host: dtype is np.float64 or np.longdouble")
+    if parts not in (1, 2):
+        raise ValueError("ringmap_host: parts is 1 or 2")
+    vis = np.asarray(vis)
+    if vis.ndim != 3 or not np.iscomplexobj(vis):
+        raise ValueError("ringmap_host: complex vis (nf, nrow, nt) expected")
+    nf, nrow, nt = vis.shape
+    if w is not None and np.shape(w) != vis.shape:
+        raise ValueError("ringmap_host: w must have the shape of vis")
+    off, mem = np.asarray(group_off, dtype=np.int64), np.asarray(members, dtype=np.int64)
+    if off.ndim != 1 or off.size < 1 or mem.ndim != 1 or off[0] != 0 or np.any(np.diff(off) < 0) or mem.size != off[-1]:
+        raise ValueError("ringmap_host: group_off (ngroup + 1), from 0 and not decreasing, and members (group_off[-1]) expected")
+    if mem.size and (mem.min() < 0 or mem.max() >= nrow):
+        raise ValueError("ringmap_host: a member is no row of vis")
+    v, scale, sinza = (np.asarray(a, dtype=np.float64) for a in (v, scale, sinza))
+    if v.shape != mem.shape or scale.shape != (nf,) or sinza.ndim != 1:
+        raise ValueError("ringmap_host: v per member, scale (nf,) and sinza (nel,) expected")
+    if taper is not None and np.shape(taper) != mem.shape:
+        raise ValueError("ringmap_host: taper must hold one value per member")
+    T = np.ones(mem.size, dtype=dtype) if taper is None else np.asarray(taper, dtype=np.float64).astype(dtype)
+    ngroup, nel = off.size - 1, sinza.size
+    pi = _ld_pi() if dtype is np.longdouble else np.pi
+    out = np.zeros((nf, ngroup, parts, nel, nt), dtype=dtype)
+    D, D2 = np.zeros((nf, ngroup, nt), dtype=dtype), np.zeros((nf, ngroup, nt), dtype=dtype)
+    for f in range(nf):
+        for g in range(ngroup):
+            sl = slice(off[g], off[g + 1])
+            rows = mem[sl]
+            if rows.size == 0:
+                continue
+            kept = np.ones((rows.size, nt), dtype=bool) if w is None else np.asarray(w[f, rows]) > 0
+            wg = np.ones((rows.size, nt), dtype=dtype) if w is None else np.where(kept, np.asarray(w[f, rows]), 0.0).astype(dtype)
+            x = np.where(kept, T[sl, None] * wg, 0)
+            xr = np.where(kept, x * np.where(kept, vis[f, rows].real, 0).astype(dtype), 0)
+            xi = np.where(kept, x * np.where(kept, vis[f, rows].imag, 0).astype(dtype), 0)
+            tau = (scale[f].astype(dtype) * v[sl].astype(dtype))[:, None] * sinza.astype(dtype)[None, :]   # (nb, nel)
+            ph = pi * (2 * (tau - np.rint(tau)))   # sincospi of twice the exact fraction of a turn
+            c, s = np.cos(ph), np.sin(ph)
+            d = x.sum(axis=0) if dtype is np.longdouble else np.add.accumulate(x, axis=0)[-1]
+            d2 = (T[sl, None] * x).sum(axis=0) if dtype is np.longdouble else np.add.accumulate(T[sl, None] * x, axis=0)[-1]
+            ok = d != 0
+            dd = np.where(ok, d, 1)
+            out[f, g, 0] = np.where(ok, (c.T @ xr + s.T @ xi) / dd, 0)
+            if parts == 2:
+                out[f, g, 1] = np.where(ok, (c.T @ xi - s.T @ xr) / dd, 0)
+            D[f, g], D2[f, g] = np.where(ok, d, 0), np.where(ok, d2, 0)
+    return out, D, D2
+
+
+RINGMAP_DEFAULTS = dict(name="ringmap", nel=None, weighting="natural", window=None, ew=None, intracyl=True, parts=1,
+                        collapse_ew=False)
+
+
+def ringmap_params(d=None):
+    """One entry of the pipeline's `ringmaps` list with its defaults filled in; an unknown key raises ValueError."""
+    out = _conf_filled(d, RINGMAP_DEFAULTS, "ringmaps: unknown key(s) %s (known: %s)", show=", ".join)
+    if out["weighting"] not in RINGMAP_WEIGHTINGS or out["window"] not in RINGMAP_WINDOWS or out["parts"] not in (1, 2):
+        raise ValueError('ringmaps: weighting is "natural" or "uniform", window None, "hann" or "blackman", parts 1 or 2')
+    return out
+
+
+def ringmap(m, indir, name="ringmap", nel=None, sinza=None, weighting="natural", window=None, ew=None, intracyl=True,
+            parts=1, collapse_ew=False, chunk_gb=4.0):
+    """Ring maps of the stacked Timestream directory `indir` (`Context.ringmap`): the
+    visibilities of every sample beamformed north-south onto the grid `sinza` (None: `ringmap_sinza` with `nel`), one
+    map per frequency and group of `ringmap_groups(tel, ew, intracyl)`, tapered by `ringmap_taper(weighting, window)`.
+    It needs no products beyond the telescope; the dataset `weight` of a file is honoured sample by sample.  Ranks take
+    their own frequencies in chunks that fit `chunk_gb`; each frequency gets `ringmap_<name>.hdf5` beside its
+    timestream file, holding `map` (ngroup, parts, nel, ntime), `norm` and `norm2` (ngroup, ntime), and with
+    collapse_ew `map_sum` (npol, parts, nel, ntime): the groups of one class pair combined as sum_g D_g map_g / sum_g D_g
+    (0 where that sum is 0) and `norm_sum`.  Rank 0 writes `ringmap_<name>.hdf5` at the root: `sinza`, `phi`,
+    `group_off`, `members`, `v`, `u`, `pol`, `taper`, with collapse_ew `pol_sum` and `group_pol` (the row of `map_sum`
+    every group goes to), and the parameters as attributes.  The written bits do not depend on `chunk_gb`.  An unstacked
+    directory raises ValueError.  Returns the path of the root file."""
+    if weighting not in RINGMAP_WEIGHTINGS or window not in RINGMAP_WINDOWS or parts not in (1, 2):
+        raise ValueError('ringmap: weighting is "natural" or "uniform", window None, "hann" or "blackman", parts 1 or 2')
+    tel = m.beamtransfer.telescope
+    src = Timestream(indir, m)
+    src._refuse_unstacked()
+    groups = ringmap_groups(tel, ew=ew, intracyl=intracyl)
+    ngroup = groups["group_off"].shape[0] - 1
+    if ngroup == 0:
+        raise ValueError("ringmap: no baseline is selected (ew = %s, intracyl = %s)" % (ew, intracyl))
+    taper = ringmap_taper(tel, groups, weighting=weighting, window=window)
+    sinza = ringmap_sinza(tel, groups, nel) if sinza is None else np.ascontiguousarray(sinza, dtype=np.float64)
+    if sinza.ndim != 1 or sinza.size < 1 or (nel is not None and int(nel) != sinza.size) or not np.all(np.abs(sinza) <= 1):
+        raise ValueError("ringmap: sinza must be a list of values in [-1, 1]%s" % ("" if nel is None else " of nel entries"))
+    nel = int(sinza.size)
+    scale = np.ascontiguousarray(1.0 / np.asarray(tel.wavelengths, dtype=np.float64))
+    freqs = _sim_freqs(tel, None)
+    with storage.File(src._ffile(0), "r") as f:
+        nrow, nt = (int(s) for s in f["timestream"].shape)
+    if nrow != int(tel.npairs):
+        raise ValueError("ringmap: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, int(tel.npairs)))
+    upol, group_pol = np.unique(groups["pol"], axis=0, return_inverse=True)
+    group_pol = np.asarray(group_pol).reshape(-1)
+    per_f = 24.0 * nrow * nt + 8.0 * ngroup * nt * (parts * nel + 2) + (16.0 * len(upol) * nt * parts * nel if collapse_ew else 0.0)
+    log = sim_log
+    ctx = get_context()
+    torch = ctx.torch
+    tabs = {k: ctx.to_device(a) for k, a in (("v", groups["v"]), ("taper", taper), ("sinza", sinza))}
+    for fs in _freq_chunks(freqs, chunk_gb, per_f):
+        with _StepTimer(log, "read"):
+            x = np.stack([np.asarray(src.timestream_f(fi), dtype=np.complex128) for fi in fs])
+            ws = [src.weight_f(fi) for fi in fs]
+            if x.shape[1:] != (nrow, nt):
+                raise ValueError("ringmap: a file of %s holds %s, not (%d, %d)" % (src.directory, x.shape[1:], nrow, nt))
+        with _StepTimer(log, "ringmap"):
+            x_d = ctx.to_device(x)
+            w_d = None
+            if any(wf is not None for wf in ws):
+                w_d = ctx.to_device(np.stack([np.ones((nrow, nt)) if wf is None else wf for wf in ws]))
+            mp, nm, nm2 = ctx.ringmap(x_d, groups["group_off"], groups["members"], tabs["v"], ctx.to_device(scale[fs]),
+                                      tabs["sinza"], w=w_d, taper=tabs["taper"], parts=parts)
+            data = dict(map=ctx.to_host(mp), norm=ctx.to_host(nm), norm2=ctx.to_host(nm2))
+            if collapse_ew:
+                msum = torch.zeros((len(fs), len(upol), parts, nel, nt), dtype=torch.float64, device=mp.device)
+                dsum = torch.zeros((len(fs), len(upol), nt), dtype=torch.float64, device=mp.device)
+                for g in range(ngroup):   # in group order: the bits of a sum do not depend on the chunk
+                    msum[:, group_pol[g]] += nm[:, g, None, None, :] * mp[:, g]
+                    dsum[:, group_pol[g]] += nm[:, g]
+                ok = dsum != 0
+                msum = torch.where(ok[:, :, None, None, :], msum / torch.where(ok, dsum, torch.ones_like(dsum))[:, :, None, None, :],
+                                   torch.zeros_like(msum))
+                data.update(map_sum=ctx.to_host(msum), norm_sum=ctx.to_host(dsum))
+                del msum, dsum
+            del x_d, w_d, mp, nm, nm2
+        with _StepTimer(log, "write"):
+            for k, fi in enumerate(fs):
+                os.makedirs(src._fdir(fi), exist_ok=True)
+                with storage.File(os.path.join(src._fdir(fi), "ringmap_%s.hdf5" % name), "w") as f:
+                    for key, value in data.items():
+                        f.create_dataset(key, data=np.ascontiguousarray(value[k]))
+                    f.attrs["frequency"] = float(tel.frequencies[fi])
+    root = os.path.join(src.directory, "ringmap_%s.hdf5" % name)
+    if parallel.rank0():
+        with storage.File(root, "w") as f:
+            f.create_dataset("sinza", data=sinza)
+            f.create_dataset("phi", data=_dir_phi(src, nt))
+            for key in ("group_off", "members", "v", "u", "pol"):
+                f.create_dataset(key, data=groups[key])
+            f.create_dataset("taper", data=taper)
+            if collapse_ew:
+                f.create_dataset("pol_sum", data=upol.astype(np.int32))
+                f.create_dataset("group_pol", data=group_pol.astype(np.int32))
+            if ew is not None:
+                f.create_dataset("ew", data=np.atleast_1d(np.asarray(ew, dtype=np.float64)))
+            for key, value in dict(nel=nel, weighting=weighting, window=window or "none", intracyl=int(bool(intracyl)),
+                                   parts=int(parts), collapse_ew=int(bool(collapse_ew)), ntime=nt).items():
+                f.attrs[key] = value
+    parallel.barrier()
+    return root

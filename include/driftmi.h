@@ -1003,6 +1003,30 @@ int dm_delay_max_rank(void);
  * in the table; 0 for a pair it does not take (host only) */
 int dm_delay_tile(int nf, int max_rank);
 
+/* ---- ring maps: the north-south beamformer of stacked visibilities ---------------------- */
+/* dm_ringmap: for every frequency f, group g, elevation e and sample t
+ *   map[f, g, 0, e, t] = sum_b x_b(t) Re(V_b(t) exp(-2 pi i tau_be)) / D(t),   map[f, g, 1, e, t] the same with Im
+ *   (parts = 2 only),   x_b(t) = taper_b w_b(t),   D(t) = sum_b x_b(t),   D2(t) = sum_b taper_b x_b(t),
+ *   tau_be = (scale[f] v_b) sinza[e] in turns, taken as tau - rint(tau) into sincospi,
+ * the sums over the members b of the group: group g lists the rows members[group_off[g] .. group_off[g + 1]) of vis
+ * (nf, nrow, nt) complex128; a row may sit in several groups and the rows of a group need not be contiguous.
+ * group_off (ngroup + 1) and members (group_off[ngroup]) int32 are HOST tables; v and taper (per member, float64,
+ * taper null: ones), scale (nf) and sinza (nel, any values) are on the device.  w (nf, nrow, nt) float64 or null
+ * (ones): a sample is kept iff w > 0 (false for 0, negatives and NaN), and vis and w of a sample that is not kept
+ * reach no arithmetic.  map (nf, ngroup, parts, nel, nt), norm = D and norm2 = D2 (nf, ngroup, nt) float64, either of
+ * the two null: not written.  Where D(t) = 0 the map, D and D2 are exactly 0.  An output is one fp64 MFMA accumulator
+ * walked through the members in list order, four at a time; D and D2 are sequential sums in list order: the bits of
+ * (f, g, ., e, t) depend on nothing else in the launch, and plane 0 of parts = 2 is the parts = 1 result.  No table in
+ * memory, no weighted copy, no atomics; no limit on the group size or nel.  Refused before any launch (dm_last_error):
+ * negative sizes, parts outside {1, 2}, and with work to do: a null group_off, scale, sinza or map, null members, v or
+ * vis with members listed, group_off[0] < 0, a decreasing group_off, a member outside [0, nrow), an output sharing an
+ * element with an input or another output, more than 2^31 - 1 workgroups (128 elevations x 128 samples each).
+ * nf, nt, ngroup or nel = 0 is a no-op.  Returns when the work is queued on the context's stream.  No counterpart in
+ * the reference. */
+int dm_ringmap(dm_ctx* ctx, int nf, int nrow, int nt, int ngroup, const int* group_off_host, const int* members_host,
+               const double* v_dev, const double* taper_dev, const double* scale_dev, int nel, const double* sinza_dev,
+               int parts, const void* vis_dev, const double* w_dev, double* map_dev, double* norm_dev, double* norm2_dev);
+
 #ifdef __cplusplus
 }
 #endif
