@@ -244,6 +244,12 @@ SIGNATURES = {
     "dm_ringmap": (
         c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_int, c_vp,
                 c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dm_formed_beam": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                ctypes.POINTER(c_int), c_int, c_vp, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_dbl), c_int, ctypes.POINTER(c_int),
+                ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dm_formedbeam_block": (c_int, []),
+    "dm_formedbeam_max_nu": (c_int, []),
 }
 
 _lib = None
@@ -1409,6 +1415,87 @@ def _ringmap(self, vis, group_off, members, v, scale, sinza, w=None, taper=None,
 
 
 Context.ringmap = _ringmap
+
+
+def _formed_beam(self, vis, group_off, members, iu, iv, uvals, vvals, scale, env, k0, half, turn, sinth, yc0, yc1, w=None,
+                 taper=None, parts=1, out=None, norm=None, norm2=None):
+    """Formed beams: a tracking beam on every catalogue position from stacked visibilities (dm_formed_beam, DESIGN.md
+    section 4.26; `timestream.formed_beam_host` restates it).  vis (nf, nrow, nt) complex128, contiguous; w float64 of
+    that shape or None (ones): a sample is kept iff w > 0.  group_off (ngroup + 1), members, iu and iv (group_off[-1]),
+    k0 and half (nsrc) are host integers and env (nf) host float64: group p is the rows
+    members[group_off[p]:group_off[p + 1]] of vis, member m has u = uvals[iu[m]] and v = vvals[iv[m]], source s takes the
+    samples k0[s] - half[s] .. k0[s] + half[s] (mod nt), half = -1 drops it.  uvals, vvals, taper (per member; None:
+    ones), scale (nf,), turn, sinth, yc0 and yc1 (nsrc,) are float64 device tensors, or anything numpy turns into such
+    arrays.  parts 1 (the real part) or 2.  Returns (beam, norm, norm2): beam (nf, ngroup, parts, nsrc), norm = D and
+    norm2 = D2 (nf, ngroup, nsrc), float64.  `out`, `norm` and `norm2` take tensors to write into; norm=False or
+    norm2=False leaves that output out (None is returned in its place)."""
+    torch = self.torch
+    if not (_is_c128(vis) and vis.dim() == 3):
+        raise ValueError("formed_beam: contiguous complex128 tensor vis (nf, nrow, nt) expected")
+    nf, nrow, nt = (int(s) for s in vis.shape)
+    if w is not None:
+        _weights_arg("formed_beam", w, vis.shape)
+    if parts not in (1, 2):
+        raise ValueError("formed_beam: parts is 1 or 2")
+    off, offp = _iarr(group_off)
+    mem, memp = _iarr(members)
+    iu, iup = _iarr(iu)
+    iv, ivp = _iarr(iv)
+    if off.ndim != 1 or off.shape[0] < 1 or mem.ndim != 1 or off[0] != 0 or np.any(np.diff(off) < 0) or mem.shape[0] != int(off[-1]):
+        raise ValueError("formed_beam: group_off (ngroup + 1), from 0 and not decreasing, and members (group_off[-1]) expected")
+    if mem.size and (mem.min() < 0 or mem.max() >= nrow):
+        raise ValueError("formed_beam: a member is no row of vis")
+    if iu.shape != mem.shape or iv.shape != mem.shape:
+        raise ValueError("formed_beam: iu and iv hold one index per member")
+    ngroup, nmem = off.shape[0] - 1, mem.shape[0]
+    k0, k0p = _iarr(k0)
+    half, halfp = _iarr(half)
+    if k0.ndim != 1 or half.shape != k0.shape:
+        raise ValueError("formed_beam: k0 and half (nsrc,) expected")
+    nsrc = k0.shape[0]
+    if nsrc and (k0.min() < 0 or k0.max() >= max(nt, 1) or half.min() < -1 or 2 * int(half.max()) + 1 > nt):
+        raise ValueError("formed_beam: k0 in [0, nt), half >= -1 and 2 half + 1 <= nt expected")
+    env = np.ascontiguousarray(env, dtype=np.float64)
+    if env.shape != (nf,) or not np.all(np.isfinite(env) & (env >= 0)):
+        raise ValueError("formed_beam: env holds one finite value >= 0 per frequency")
+
+    def table(t, n, name):
+        if not hasattr(t, "data_ptr"):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))).to(vis.device)
+        if not (t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and n in (None, int(t.shape[0]))):
+            raise ValueError("formed_beam: %s must be a contiguous float64 tensor (%s,)" % (name, "n" if n is None else n))
+        return t
+
+    uvals, vvals = table(uvals, None, "uvals"), table(vvals, None, "vvals")
+    nu, nv = int(uvals.shape[0]), int(vvals.shape[0])
+    if nmem and (iu.min() < 0 or iu.max() >= nu or iv.min() < 0 or iv.max() >= nv):
+        raise ValueError("formed_beam: iu or iv points outside uvals or vvals")
+    taper = None if taper is None else table(taper, nmem, "taper")
+    scale = table(scale, nf, "scale")
+    turn, sinth, yc0, yc1 = (table(t, nsrc, n) for t, n in ((turn, "turn"), (sinth, "sinth"), (yc0, "yc0"), (yc1, "yc1")))
+
+    def output(t, shape, name):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float64, device=vis.device)
+        if not (hasattr(t, "data_ptr") and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("formed_beam: %s must be a contiguous float64 tensor %s" % (name, shape))
+        return t
+
+    out = output(out, (nf, ngroup, parts, nsrc), "out")
+    norm = None if norm is False else output(norm, (nf, ngroup, nsrc), "norm")
+    norm2 = None if norm2 is False else output(norm2, (nf, ngroup, nsrc), "norm2")
+    if not all(t is None or (t.is_cuda and t.device == vis.device)
+               for t in (vis, w, uvals, vvals, taper, scale, turn, sinth, yc0, yc1, out, norm, norm2)):
+        raise ValueError("formed_beam: vis, w, the tables and the outputs must be tensors on one GPU")
+    rc = self.lib.dm_formed_beam(self.h, nf, nrow, nt, ngroup, offp, memp, iup, ivp, nu, self.ptr(uvals), nv, self.ptr(vvals),
+                                 self.ptr(taper), self.ptr(scale), env.ctypes.data_as(ctypes.POINTER(c_dbl)), nsrc, k0p, halfp,
+                                 self.ptr(turn), self.ptr(sinth), self.ptr(yc0), self.ptr(yc1), int(parts), self.ptr(vis),
+                                 self.ptr(w), self.ptr(out), self.ptr(norm), self.ptr(norm2))
+    self.check(rc, "dm_formed_beam")
+    return out, norm, norm2
+
+
+Context.formed_beam = _formed_beam
 
 
 def _redcal_solve(self, vis, class_off, members, w=None, feed_weight=None, g0=None, damping=0.4, tol=1e-10, maxiter=500,

@@ -32,6 +32,11 @@ And ``ringmaps``, entries ``{name, nel, weighting: natural | uniform, window: ha
 collapse_ew}`` (all optional), each of which writes ``ringmap_<name>.hdf5`` per frequency and at the root of every timestream
 in the maps stage: its stacked visibilities beamformed north-south, sample by sample (``timestream.ringmap``).  It needs no
 products beyond the telescope; an unknown key raises ValueError.
+And ``formedbeams``, entries ``{name, catalogue, ha_max, envelope_fwhm, weighting, window, ew: [...], intracyl, parts, stack:
+{halfwidth, line_mhz, source_weight, channel_weight}}`` (``catalogue``, a file of positions, is required), each of which
+writes ``formedbeam_<name>.hdf5`` per frequency and at the root of every timestream in the maps stage: a tracking beam
+formed on every catalogue position from the stacked visibilities, one spectrum per object and class pair, and with
+redshifts in the catalogue their stack (``timestream.formed_beam``).  It needs no products beyond the telescope either.
 
     python -m driftscan_amd.pipeline params.yaml
 """
@@ -69,6 +74,9 @@ class PipelineManager(config.Reader):
     catalogues = config.Property(proptype=list, default=[])
     # ring maps (not in the reference): entries {name, nel, weighting, window, ew, intracyl, parts, collapse_ew}
     ringmaps = config.Property(proptype=list, default=[])
+    # formed beams on catalogue positions (not in the reference): entries {name, catalogue, ha_max, envelope_fwhm, weighting,
+    # window, ew, intracyl, parts, stack}
+    formedbeams = config.Property(proptype=list, default=[])
 
     nside = config.Property(proptype=int, default=128)
     wiener = config.Property(proptype=bool, default=False)
@@ -104,6 +112,9 @@ class PipelineManager(config.Reader):
         self.read_config(yconf["config"])
         for entry in self.ringmaps:   # an unknown key is refused before anything runs
             timestream.ringmap_params(entry)
+        for entry in self.formedbeams:
+            if timestream.formedbeam_params(entry)["catalogue"] is None:
+                raise ValueError("formedbeams: an entry needs `catalogue`, a file of positions")
         self.product_directory = fixpath(self.product_directory) if self.product_directory else self.product_directory
         if "timestreams" not in yconf:
             raise Exception("Configuration file must have an 'timestream' section.")
@@ -264,6 +275,11 @@ class PipelineManager(config.Reader):
                     entry = timestream.ringmap_params(entry)
                     logger.info("Generating ring map %s (%s)", entry["name"], tsname)
                     timestream.ringmap(tsobj.manager, tsobj.directory, chunk_gb=self.chunk_gb, **entry)
+                for entry in self.formedbeams:
+                    entry = timestream.formedbeam_params(entry)
+                    logger.info("Forming beams %s (%s)", entry["name"], tsname)
+                    timestream.formed_beam(tsobj.manager, tsobj.directory, os.path.abspath(fixpath(entry.pop("catalogue"))),
+                                           chunk_gb=self.chunk_gb, **entry)
                 for klname in self.klmaps:
                     logger.info("Generating KL map (%s:%s)", tsname, klname)
                     tsobj.set_kltransform(klname)

@@ -3707,3 +3707,316 @@ def ringmap(m, indir, name="ringmap", nel=None, sinza=None, weighting="natural",
                 f.attrs[key] = value
     parallel.barrier()
     return root
+
+
+# ---- formed beams: tracking beams on catalogue positions from stacked visibilities --------
+
+def formedbeam_groups(tel, ew=None, intracyl=True):
+    """The groups of a formed beam of telescope `tel`: a group is a beam-class pair, the groups of `ringmap_groups` (same
+    selection `ew`, `intracyl`) merged over u.  Returns a dict: `group_off` (ngroup + 1) int32, `members` int32 (rows of
+    the stacked data), `u` and `v` per member (m, east and north positive, both rounded to the telescope's tolerance, so
+    that baselines the telescope holds equal share their phase), `pol` (ngroup, 2), and the distinct values `uvals`,
+    `vvals` (ascending) with `iu`, `iv` int32 per member: uvals[iu] == u and vvals[iv] == v exactly.  Groups are ordered
+    by class pair, the members of a group by (v, u, index): runs of equal v are neighbours."""
+    rg = ringmap_groups(tel, ew=ew, intracyl=intracyl)
+    rows = np.asarray(rg["members"], dtype=np.int64)
+    cls = np.asarray(tel.beamclass)
+    pairs = np.asarray(tel.uniquepairs).reshape(-1, 2)
+    bl = np.asarray(tel.baselines, dtype=np.float64).reshape(-1, 2)
+    tol = int(getattr(tel, "_bl_tol", 6))
+    u, v = np.around(bl[rows, 0], tol) + 0.0, np.around(bl[rows, 1], tol) + 0.0
+    ci, cj = cls[pairs[rows, 0]], cls[pairs[rows, 1]]
+    order = np.lexsort((rows, u, v, cj, ci))
+    rows, u, v, ci, cj = rows[order], u[order], v[order], ci[order], cj[order]
+    new = np.ones(rows.shape[0], dtype=bool)
+    new[1:] = (ci[1:] != ci[:-1]) | (cj[1:] != cj[:-1])
+    first = np.nonzero(new)[0]
+    uvals, iu = np.unique(u, return_inverse=True)
+    vvals, iv = np.unique(v, return_inverse=True)
+    return dict(group_off=np.concatenate([first, [rows.shape[0]]]).astype(np.int32), members=rows.astype(np.int32),
+                u=np.ascontiguousarray(u), v=np.ascontiguousarray(v),
+                pol=np.stack([ci[first], cj[first]], axis=1).astype(np.int32).reshape(-1, 2),
+                uvals=np.ascontiguousarray(uvals, dtype=np.float64), vvals=np.ascontiguousarray(vvals, dtype=np.float64),
+                iu=np.asarray(iu).reshape(-1).astype(np.int32), iv=np.asarray(iv).reshape(-1).astype(np.int32))
+
+
+def formedbeam_tables(theta_zenith, theta):
+    """The per-source constants of the formed beam for sources at polar angle `theta` under a zenith at `theta_zenith`,
+    computed in long double and rounded to float64: `sinth` = sin(theta), `yc0` = sin(theta_z) cos(theta), `yc1` =
+    cos(theta_z) sin(theta) (y = yc0 - yc1 cos(D)), `zc0` = cos(theta_z) cos(theta), `zc1` = sin(theta_z) sin(theta)
+    (z = zc0 + zc1 cos(D))."""
+    ld = np.longdouble
+    tz, th = ld(theta_zenith), np.asarray(theta, dtype=np.float64).reshape(-1).astype(ld)
+    f64 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=ld).astype(np.float64))
+    return dict(sinth=f64(np.sin(th)), yc0=f64(np.sin(tz) * np.cos(th)), yc1=f64(np.cos(tz) * np.sin(th)),
+                zc0=f64(np.cos(tz) * np.cos(th)), zc1=f64(np.sin(tz) * np.sin(th)))
+
+
+def formedbeam_z(tabs, turn, k, ntime):
+    """z = zc0 + zc1 cos(2 pi (turn - k / ntime)) of every source at its sample k, in long double from the tables."""
+    ld = np.longdouble
+    d = np.asarray(turn, dtype=np.float64).astype(ld) - np.asarray(k).astype(ld) / ld(ntime)
+    d = d - np.rint(d)
+    return tabs["zc0"].astype(ld) + tabs["zc1"].astype(ld) * np.cos(2 * _ld_pi() * d)
+
+
+def formedbeam_windows(tel, theta, phi, ntime, ha_max, zmin=0.05, scale_dec=True):
+    """The windows of the sources at (theta, phi) in data of `ntime` uniform samples (the zenith is at phi_k = 2 pi k /
+    ntime at sample k): a dict with `turn` (phi as a fraction of a turn in [0, 1), float64), `k0` = rint(turn ntime) mod
+    ntime and `half` = H, int32; source s takes the samples k0 - H .. k0 + H (mod ntime).  H = floor(ha / (2 pi / ntime))
+    with ha = ha_max, or with scale_dec ha_max / sin(theta) capped at a quarter turn (the same arc on the sky at every
+    declination); 2 H + 1 <= ntime; H is then lowered until z >= zmin at both ends of the window, to -1 (the source is
+    dropped) where even the transit sample is below zmin.  Computed in long double from the float64 tables."""
+    ld = np.longdouble
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    phi = np.asarray(phi, dtype=np.float64).reshape(-1)
+    ntime = int(ntime)
+    if theta.shape != phi.shape or ntime < 1 or not ha_max >= 0:
+        raise ValueError("formedbeam_windows: theta and phi of one length, ntime >= 1 and ha_max >= 0 expected")
+    two_pi = 2 * _ld_pi()
+    t = phi.astype(ld) / two_pi
+    turn = np.asarray(t - np.floor(t), dtype=ld).astype(np.float64)
+    turn = np.where(turn >= 1.0, 0.0, turn)
+    k0 = np.rint(turn.astype(ld) * ntime).astype(np.int64) % ntime
+    steps = np.full(theta.shape, ld(ha_max) / (two_pi / ntime), dtype=ld)
+    cap = (ntime - 1) // 2
+    if scale_dec:
+        sth = np.abs(np.sin(theta.astype(ld)))
+        steps = np.where(sth * ntime > steps, steps / np.where(sth > 0, sth, 1), ntime)
+        cap = min(cap, ntime // 4)
+    half = np.minimum(np.floor(np.minimum(steps, ntime)).astype(np.int64), cap)
+    tabs = formedbeam_tables(tel.zenith[0], theta)
+    while True:
+        live = half >= 0
+        hh = np.where(live, half, 0)
+        low = live & ((formedbeam_z(tabs, turn, k0 - hh, ntime) < zmin) | (formedbeam_z(tabs, turn, k0 + hh, ntime) < zmin))
+        if not low.any():
+            break
+        half = np.where(low, half - 1, half)
+    return dict(turn=np.ascontiguousarray(turn), k0=k0.astype(np.int32), half=half.astype(np.int32))
+
+
+def formedbeam_env(wavelengths, envelope_fwhm):
+    """env_f = 4 ln 2 / (envelope_fwhm lambda_f)^2, the exponent of the east-west envelope exp(-env x^2) whose full width
+    at half maximum in the direction cosine x is envelope_fwhm per metre of wavelength; None: zeros (no envelope)."""
+    lam = np.asarray(wavelengths, dtype=np.float64).reshape(-1)
+    if envelope_fwhm is None:
+        return np.zeros(lam.shape)
+    if not envelope_fwhm > 0:
+        raise ValueError("formedbeam: envelope_fwhm is None or > 0")
+    return 4.0 * np.log(2.0) / (float(envelope_fwhm) * lam) ** 2
+
+
+def formed_beam_host(vis, w, group_off, members, u, v, scale, env, k0, half, turn, sinth, yc0, yc1, taper=None, parts=1,
+                     dtype=np.float64):
+    """The numpy statement of `Context.formed_beam` in `dtype`, np.float64 or np.longdouble: for
+    frequency f, group p and source s, over the samples k = k0_s + j (mod nt), j = -H_s .. H_s, and the members b
+        D = turn_s - k / nt reduced to [-1/2, 1/2],   x = sinth_s sin(2 pi D),   y = yc0_s - yc1_s cos(2 pi D),
+        A = exp(-env_f x^2),   x_b(k) = T_b w_b(k) where w_b(k) > 0 and 0 elsewhere,
+        tau = (scale_f u_b) x + (scale_f v_b) y, each product reduced by rint,
+        num = sum A x_b Re(V_b(k) exp(-2 pi i tau)),   D = sum A x_b,   D2 = sum A^2 x_b,   beam = num / D
+    and the imaginary part in plane 1 with parts = 2; beam, D and D2 are 0 where D = 0 and for H_s = -1.  cos and sin are
+    taken of pi times twice a fraction of a turn, never of a large argument.  Samples that are not kept enter no
+    arithmetic.  vis (nf, nrow, nt) complex, w of that shape or None (ones), u, v and taper (None: ones) per member.
+    Returns (beam (nf, ngroup, parts, nsrc), D, D2 (nf, ngroup, nsrc))."""
+    if dtype not in (np.float64, np.longdouble):
+        raise ValueError("formed_beam_host: dtype is np.float64 or np.longdouble")
+    if parts not in (1, 2):
+        raise ValueError("formed_beam_host: parts is 1 or 2")
+    vis = np.asarray(vis)
+    if vis.ndim != 3 or not np.iscomplexobj(vis):
+        raise ValueError("formed_beam_host: complex vis (nf, nrow, nt) expected")
+    nf, nrow, nt = vis.shape
+    if w is not None and np.shape(w) != vis.shape:
+        raise ValueError("formed_beam_host: w must have the shape of vis")
+    off, mem = np.asarray(group_off, dtype=np.int64), np.asarray(members, dtype=np.int64)
+    if off.ndim != 1 or off.size < 1 or mem.ndim != 1 or off[0] != 0 or np.any(np.diff(off) < 0) or mem.size != off[-1]:
+        raise ValueError("formed_beam_host: group_off (ngroup + 1), from 0 and not decreasing, and members (group_off[-1]) expected")
+    if mem.size and (mem.min() < 0 or mem.max() >= nrow):
+        raise ValueError("formed_beam_host: a member is no row of vis")
+    u, v, scale, env = (np.asarray(a, dtype=np.float64) for a in (u, v, scale, env))
+    if u.shape != mem.shape or v.shape != mem.shape or scale.shape != (nf,) or env.shape != (nf,):
+        raise ValueError("formed_beam_host: u and v per member, scale and env (nf,) expected")
+    if not np.all(np.isfinite(env) & (env >= 0)):
+        raise ValueError("formed_beam_host: env holds finite values >= 0")
+    if taper is not None and np.shape(taper) != mem.shape:
+        raise ValueError("formed_beam_host: taper must hold one value per member")
+    k0, half = np.asarray(k0, dtype=np.int64), np.asarray(half, dtype=np.int64)
+    turn, sinth, yc0, yc1 = (np.asarray(a, dtype=np.float64) for a in (turn, sinth, yc0, yc1))
+    nsrc = k0.size
+    if k0.ndim != 1 or any(a.shape != (nsrc,) for a in (half, turn, sinth, yc0, yc1)):
+        raise ValueError("formed_beam_host: k0, half, turn, sinth, yc0 and yc1 (nsrc,) expected")
+    if nsrc and (k0.min() < 0 or k0.max() >= max(nt, 1) or half.min() < -1 or 2 * half.max() + 1 > nt):
+        raise ValueError("formed_beam_host: k0 in [0, nt), half >= -1 and 2 half + 1 <= nt expected")
+    T = np.ones(mem.size, dtype=dtype) if taper is None else np.asarray(taper, dtype=np.float64).astype(dtype)
+    ngroup = off.size - 1
+    pi = _ld_pi() if dtype is np.longdouble else np.pi
+    beam = np.zeros((nf, ngroup, parts, nsrc), dtype=dtype)
+    D, D2 = np.zeros((nf, ngroup, nsrc), dtype=dtype), np.zeros((nf, ngroup, nsrc), dtype=dtype)
+    for s in range(nsrc):
+        if half[s] < 0:
+            continue
+        ks = (k0[s] + np.arange(-half[s], half[s] + 1)) % nt
+        d = turn[s].astype(dtype) - ks.astype(dtype) / dtype(nt)
+        d = d - np.rint(d)
+        x = sinth[s].astype(dtype) * np.sin(pi * (2 * d))
+        y = yc0[s].astype(dtype) - yc1[s].astype(dtype) * np.cos(pi * (2 * d))
+        for f in range(nf):
+            A = np.exp(-(env[f].astype(dtype) * (x * x))) if env[f] != 0 else np.ones(ks.size, dtype=dtype)
+            for p in range(ngroup):
+                sl = slice(off[p], off[p + 1])
+                rows = mem[sl]
+                if rows.size == 0:
+                    continue
+                kept = np.ones((rows.size, ks.size), dtype=bool) if w is None else np.asarray(w[f][np.ix_(rows, ks)]) > 0
+                wg = np.ones(kept.shape, dtype=dtype) if w is None else np.where(kept, w[f][np.ix_(rows, ks)], 0.0).astype(dtype)
+                xb = np.where(kept, T[sl, None] * wg, 0)
+                V = np.where(kept, vis[f][np.ix_(rows, ks)], 0)
+                xr, xi = xb * V.real.astype(dtype), xb * V.imag.astype(dtype)
+                tu = (scale[f].astype(dtype) * u[sl].astype(dtype))[:, None] * x[None, :]
+                tv = (scale[f].astype(dtype) * v[sl].astype(dtype))[:, None] * y[None, :]
+                ph = pi * (2 * ((tu - np.rint(tu)) + (tv - np.rint(tv))))
+                c, sn = np.cos(ph), np.sin(ph)
+                d1 = (A[None, :] * xb).sum()
+                if d1 == 0:
+                    continue
+                beam[f, p, 0, s] = (A[None, :] * (xr * c + xi * sn)).sum() / d1
+                if parts == 2:
+                    beam[f, p, 1, s] = (A[None, :] * (xi * c - xr * sn)).sum() / d1
+                D[f, p, s], D2[f, p, s] = d1, ((A * A)[None, :] * xb).sum()
+    return beam, D, D2
+
+
+FORMEDBEAM_DEFAULTS = dict(name="formedbeam", catalogue=None, ha_max=0.05, envelope_fwhm=None, weighting="natural", window=None,
+                           ew=None, intracyl=True, parts=1, stack=None)
+FORMEDBEAM_STACK_KEYS = ("halfwidth", "line_mhz", "source_weight", "channel_weight")
+
+
+def formedbeam_params(d=None):
+    """One entry of the pipeline's `formedbeams` list with its defaults filled in; an unknown key raises ValueError."""
+    out = _conf_filled(d, FORMEDBEAM_DEFAULTS, "formedbeams: unknown key(s) %s (known: %s)", show=", ".join)
+    if out["weighting"] not in RINGMAP_WEIGHTINGS or out["window"] not in RINGMAP_WINDOWS or out["parts"] not in (1, 2):
+        raise ValueError('formedbeams: weighting is "natural" or "uniform", window None, "hann" or "blackman", parts 1 or 2')
+    if out["stack"] is not None:
+        _conf_filled(out["stack"], dict.fromkeys(FORMEDBEAM_STACK_KEYS), "formedbeams: unknown stack key(s) %s (known: %s)",
+                     show=", ".join)
+    if not (out["ha_max"] >= 0) or (out["envelope_fwhm"] is not None and not out["envelope_fwhm"] > 0):
+        raise ValueError("formedbeams: ha_max >= 0 and envelope_fwhm None or > 0 expected")
+    return out
+
+
+def formed_beam(m, indir, cat, name="formedbeam", ha_max=0.05, envelope_fwhm=None, weighting="natural", window=None, ew=None,
+                intracyl=True, parts=1, stack=None, zmin=0.05, scale_dec=True, chunk_gb=4.0):
+    """Formed beams of the stacked Timestream directory `indir` on the positions of the catalogue `cat`
+    (`skysim.read_positions`: arrays, a dict or a file): every baseline is fringestopped at the object's position while
+    it drifts through the primary beam and the weighted sum over the baselines of a class pair (`formedbeam_groups(tel,
+    ew, intracyl)`, tapered by `ringmap_taper(weighting, window)`) and over the samples of the transit
+    (`formedbeam_windows(ha_max, zmin, scale_dec)`; ha_max in radians of hour angle at the equator) gives one spectrum per
+    object (`Context.formed_beam`).  `envelope_fwhm` (direction cosine per metre of wavelength)
+    weights the samples by a Gaussian east-west envelope; None: none.  It needs no products beyond the telescope; the
+    dataset `weight` of a file is honoured sample by sample.  Ranks take their own frequencies in chunks that fit
+    `chunk_gb`; each frequency gets `formedbeam_<name>.hdf5` beside its timestream file, holding `beam` (ngroup, parts,
+    nsrc), `norm` and `norm2` (ngroup, nsrc).  After the barrier rank 0 writes `formedbeam_<name>.hdf5` at the root:
+    `beam` (nsrc, ngroup, nfreq) (plane 0; `beam_imag` with parts = 2), `norm`, `norm2` of that shape, `theta`, `phi`,
+    `freq` (MHz), `k0`, `half`, `pol`, the parameters as attributes, and — when the catalogue has `redshift` or `stack` (a
+    dict: `halfwidth` (2), `line_mhz` (the 21 cm line), `source_weight` (the mean of `norm` over groups and frequencies, so
+    that dropped sources weigh 0), `channel_weight`) is given — `redshift`, `stack`, `hits`, `offsets`, `stack_weight` and
+    `channel` of `skysim.stack_spectra` on `beam`.  The written bits do not depend on `chunk_gb`.  An unstacked directory
+    raises ValueError.  Returns the path of the root file."""
+    from . import skysim
+
+    if weighting not in RINGMAP_WEIGHTINGS or window not in RINGMAP_WINDOWS or parts not in (1, 2):
+        raise ValueError('formed_beam: weighting is "natural" or "uniform", window None, "hann" or "blackman", parts 1 or 2')
+    conf = _conf_filled(stack, dict.fromkeys(FORMEDBEAM_STACK_KEYS), "formed_beam: unknown stack key(s) %s (known: %s)",
+                        show=", ".join)
+    theta, phi, red = skysim.read_positions(cat)
+    if stack is not None and red is None:
+        raise ValueError("formed_beam: a stack needs the redshifts of the catalogue")
+    tel = m.beamtransfer.telescope
+    src = Timestream(indir, m)
+    src._refuse_unstacked()
+    groups = formedbeam_groups(tel, ew=ew, intracyl=intracyl)
+    ngroup = groups["group_off"].shape[0] - 1
+    if ngroup == 0:
+        raise ValueError("formed_beam: no baseline is selected (ew = %s, intracyl = %s)" % (ew, intracyl))
+    taper = ringmap_taper(tel, groups, weighting=weighting, window=window)
+    scale = np.ascontiguousarray(1.0 / np.asarray(tel.wavelengths, dtype=np.float64))
+    env = formedbeam_env(tel.wavelengths, envelope_fwhm)
+    freqs = _sim_freqs(tel, None)
+    with storage.File(src._ffile(0), "r") as f:
+        nrow, nt = (int(s) for s in f["timestream"].shape)
+    if nrow != int(tel.npairs):
+        raise ValueError("formed_beam: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, int(tel.npairs)))
+    win = formedbeam_windows(tel, theta, phi, nt, ha_max, zmin=zmin, scale_dec=scale_dec)
+    tabs = formedbeam_tables(tel.zenith[0], theta)
+    nsrc = theta.size
+    per_f = 24.0 * nrow * nt + 8.0 * ngroup * nsrc * (parts + 2)
+    log = sim_log
+    ctx = get_context()
+    dev = {k: ctx.to_device(a) for k, a in (("uvals", groups["uvals"]), ("vvals", groups["vvals"]), ("taper", taper),
+                                            ("turn", win["turn"]), ("sinth", tabs["sinth"]), ("yc0", tabs["yc0"]),
+                                            ("yc1", tabs["yc1"]))} if nsrc else {}
+    for fs in _freq_chunks(freqs, chunk_gb, per_f):
+        with _StepTimer(log, "read"):
+            x = np.stack([np.asarray(src.timestream_f(fi), dtype=np.complex128) for fi in fs])
+            ws = [src.weight_f(fi) for fi in fs]
+            if x.shape[1:] != (nrow, nt):
+                raise ValueError("formed_beam: a file of %s holds %s, not (%d, %d)" % (src.directory, x.shape[1:], nrow, nt))
+        with _StepTimer(log, "formed_beam"):
+            if nsrc:
+                x_d = ctx.to_device(x)
+                w_d = None
+                if any(wf is not None for wf in ws):
+                    w_d = ctx.to_device(np.stack([np.ones((nrow, nt)) if wf is None else wf for wf in ws]))
+                bm, nm, nm2 = ctx.formed_beam(x_d, groups["group_off"], groups["members"], groups["iu"], groups["iv"], dev["uvals"],
+                                              dev["vvals"], ctx.to_device(scale[fs]), env[fs], win["k0"], win["half"], dev["turn"],
+                                              dev["sinth"], dev["yc0"], dev["yc1"], w=w_d, taper=dev["taper"], parts=parts)
+                data = dict(beam=ctx.to_host(bm), norm=ctx.to_host(nm), norm2=ctx.to_host(nm2))
+                del x_d, w_d, bm, nm, nm2
+            else:
+                data = dict(beam=np.zeros((len(fs), ngroup, parts, 0)), norm=np.zeros((len(fs), ngroup, 0)),
+                            norm2=np.zeros((len(fs), ngroup, 0)))
+        with _StepTimer(log, "write"):
+            for k, fi in enumerate(fs):
+                os.makedirs(src._fdir(fi), exist_ok=True)
+                with storage.File(os.path.join(src._fdir(fi), "formedbeam_%s.hdf5" % name), "w") as f:
+                    for key, value in data.items():
+                        f.create_dataset(key, data=np.ascontiguousarray(value[k]))
+                    f.attrs["frequency"] = float(tel.frequencies[fi])
+    parallel.barrier()
+    root = os.path.join(src.directory, "formedbeam_%s.hdf5" % name)
+    if parallel.rank0():
+        nfreq = int(tel.nfreq)
+        beam = np.zeros((nsrc, ngroup, parts, nfreq))
+        norm, norm2 = np.zeros((nsrc, ngroup, nfreq)), np.zeros((nsrc, ngroup, nfreq))
+        for fi in range(nfreq):
+            with storage.File(os.path.join(src._fdir(fi), "formedbeam_%s.hdf5" % name), "r") as f:
+                beam[..., fi] = np.moveaxis(np.asarray(f["beam"][:]), 2, 0)
+                norm[..., fi], norm2[..., fi] = np.asarray(f["norm"][:]).T, np.asarray(f["norm2"][:]).T
+        freq = np.asarray(tel.frequencies, dtype=np.float64)
+        with storage.File(root, "w") as f:
+            f.create_dataset("beam", data=np.ascontiguousarray(beam[:, :, 0]))
+            if parts == 2:
+                f.create_dataset("beam_imag", data=np.ascontiguousarray(beam[:, :, 1]))
+            for key, value in (("norm", norm), ("norm2", norm2), ("theta", theta), ("phi", phi), ("freq", freq),
+                               ("k0", win["k0"]), ("half", win["half"]), ("pol", groups["pol"])):
+                f.create_dataset(key, data=value)
+            if ew is not None:
+                f.create_dataset("ew", data=np.atleast_1d(np.asarray(ew, dtype=np.float64)))
+            for key, value in dict(ha_max=float(ha_max), envelope_fwhm=0.0 if envelope_fwhm is None else float(envelope_fwhm),
+                                   weighting=weighting, window=window or "none", intracyl=int(bool(intracyl)), parts=int(parts),
+                                   zmin=float(zmin), scale_dec=int(bool(scale_dec)), ntime=nt).items():
+                f.attrs[key] = value
+            if red is not None:
+                line = float(skysim.LINE_21CM_MHZ if conf["line_mhz"] is None else conf["line_mhz"]) / (1.0 + red)
+                sw = norm.mean(axis=(1, 2)) if conf["source_weight"] is None else conf["source_weight"]
+                st = skysim.stack_spectra(beam[:, :, 0], freq, line, 2 if conf["halfwidth"] is None else int(conf["halfwidth"]),
+                                          source_weight=sw, channel_weight=conf["channel_weight"])
+                f.create_dataset("redshift", data=red)
+                f.create_dataset("stack", data=st["stack"])
+                f.create_dataset("hits", data=st["hits"])
+                f.create_dataset("offsets", data=st["offsets"].astype(np.int64))
+                f.create_dataset("stack_weight", data=st["weight"])
+                f.create_dataset("channel", data=st["channel"])
+    parallel.barrier()
+    return root

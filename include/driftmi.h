@@ -1027,6 +1027,45 @@ int dm_ringmap(dm_ctx* ctx, int nf, int nrow, int nt, int ngroup, const int* gro
                const double* v_dev, const double* taper_dev, const double* scale_dev, int nel, const double* sinza_dev,
                int parts, const void* vis_dev, const double* w_dev, double* map_dev, double* norm_dev, double* norm2_dev);
 
+/* ---- formed beams: tracking beams on catalogue positions from stacked visibilities ------ */
+/* dm_formed_beam: for every frequency f, group p and source s, over the samples k = k0[s] + j (mod nt), j = -half[s] ..
+ * half[s], and the members b of the group
+ *   D = turn[s] - k / nt reduced to [-1/2, 1/2],   x = sinth[s] sin(2 pi D),   y = yc0[s] - yc1[s] cos(2 pi D),
+ *   A = exp(-env[f] x x)  (1 where env[f] = 0),   x_b(k) = taper_b w_b(k),
+ *   tau = (scale[f] u_b) x + (scale[f] v_b) y in turns, each product taken as t - rint(t) into sincospi,
+ *   beam[f, p, 0, s] = sum_k sum_b A x_b(k) Re(V_b(k) exp(-2 pi i tau)) / D,   beam[f, p, 1, s] the same with Im
+ *   (parts = 2 only),   D = sum_k sum_b A x_b(k),   D2 = sum_k sum_b A A x_b(k).
+ * Group p lists the rows members[group_off[p] .. group_off[p + 1]) of vis (nf, nrow, nt) complex128; member m has
+ * u = uvals[iu[m]] and v = vvals[iv[m]] (m).  group_off (ngroup + 1), members, iu, iv (group_off[ngroup]), k0 and half
+ * (nsrc) int32 and env (nf) float64 are HOST tables; uvals (nu), vvals (nv), taper (per member, null: ones), scale (nf),
+ * turn, sinth, yc0 and yc1 (nsrc) float64 are on the device.  w (nf, nrow, nt) float64 or null (ones): a sample is kept
+ * iff w > 0 (false for 0, negatives and NaN), and vis and w of a sample that is not kept reach no arithmetic.  half[s] =
+ * -1 drops the source.  beam (nf, ngroup, parts, nsrc), norm = D and norm2 = D2 (nf, ngroup, nsrc) float64, either of the
+ * two null: not written; where D = 0 all three are exactly 0.  A workgroup takes one (f, p) and dm_formedbeam_block()
+ * sources of the catalogue sorted by k0 (the sort is made here) and walks the union of their windows; a tile of x V is
+ * staged in LDS once for all of them.  A group with at most dm_formedbeam_max_nu() distinct u takes the factorised path
+ * (cos / sin once per distinct u and per run of equal v, a complex multiply per member), any other the direct one (one
+ * sincospi per member).  The result of (f, p, ., s) is summed in a fixed order that depends on the window of s and the
+ * member list of p only: its bits do not depend on the other sources, their order, the other
+ * groups or frequencies of the launch, or on norm / norm2 being null, and plane 0 of parts = 2 is the parts = 1 result.
+ * No phase table and no weighted copy in memory, no floating-point atomics.  Refused before any launch (dm_last_error):
+ * negative sizes, parts outside {1, 2}, and with work to do: a null group_off, scale, env, k0, half, turn, sinth, yc0,
+ * yc1 or beam, a negative or non-finite env, half < -1 or 2 half + 1 > nt, k0 outside [0, nt), null members, iu, iv,
+ * uvals, vvals or vis with members listed, group_off[0] < 0, a decreasing group_off, a member outside [0, nrow), iu or iv
+ * outside its table, an output sharing an element with an input or another output, more than 2^31 - 1 workgroups.
+ * nf, nt, ngroup or nsrc = 0 is a no-op.  Returns when the work is queued on the context's stream.  No counterpart in
+ * the reference. */
+int dm_formed_beam(dm_ctx* ctx, int nf, int nrow, int nt, int ngroup, const int* group_off_host, const int* members_host,
+                   const int* iu_host, const int* iv_host, int nu, const double* uvals_dev, int nv, const double* vvals_dev,
+                   const double* taper_dev, const double* scale_dev, const double* env_host, int nsrc, const int* k0_host,
+                   const int* half_host, const double* turn_dev, const double* sinth_dev, const double* yc0_dev,
+                   const double* yc1_dev, int parts, const void* vis_dev, const double* w_dev, double* beam_dev,
+                   double* norm_dev, double* norm2_dev);
+/* the sources of a workgroup of dm_formed_beam, and the distinct u of a group up to which it takes the factorised path
+ * (host only) */
+int dm_formedbeam_block(void);
+int dm_formedbeam_max_nu(void);
+
 #ifdef __cplusplus
 }
 #endif
