@@ -30,7 +30,8 @@ __global__ __launch_bounds__(256) void psmc_draw_kernel(const draw_desc* __restr
   const size_t tot = (size_t)d.n * R;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) {
     const int i = (int)(e / R), r = (int)(e - (size_t)i * R);
-    uint32_t c[4] = {(uint32_t)i, (uint32_t)(s0 + r), (uint32_t)d.m, stream};
+    // the sample number in uint32_t: s0 + r may pass 2^31 (dm_psmc_draw admits s0 + R <= 2^32), which an int sum must not
+    uint32_t c[4] = {(uint32_t)i, (uint32_t)s0 + (uint32_t)r, (uint32_t)d.m, stream};
     philox4x32_10(c, k0, k1);
     double sc = 1.0;
     if (power > 0) sc = sqrt(d.lam[i] + 1.0);
@@ -229,7 +230,7 @@ extern "C" int dm_psmc_alt(dm_ctx* ctx, int nblk, int F, int K, int P, int L, co
   double* tab = dm_ws_alloc_t<double>(ctx, (size_t)nbands * L * F * F);
   int* d_l0 = dm_ws_upload(ctx, l0eff);
   if (!x1 || !x2 || !z || !y1 || !v || !w || !tab || !d_l0) return DM_ENOMEM;
-  if (v_dev) DM_TRY(dm_fill_zero(ctx, v, sizeof(cplx) * std::max<size_t>(totv, 1) * nbands));
+  if (v_dev && totv > 0) DM_TRY(dm_fill_zero(ctx, v, sizeof(cplx) * totv * nbands));   // (nbands, T): nothing where T = 0
 
   dm_band_tables(ctx, cl_bands_dev, tab, nbands, F, L);
   // x1 = E^H X (the draws carry their C^-1/2 weight already), x2 = B^H x1, Z_a = C_a x2 for every band

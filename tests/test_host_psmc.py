@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from test_host_qestimator import q_estimate, sky_to_svd, svd_to_sky
+from test_host_qestimator import _as, q_estimate, sky_to_svd, svd_to_sky
 
 M32 = np.uint64(0xFFFFFFFF)
 
@@ -52,21 +52,24 @@ def draws(seed, m, nmodes, nsamples, stream, kind=0, power=0, evals=None, start=
     return z
 
 
-def alt_vecs(evals, evecs, beam_svd, svnum, clarray, signs):
-    """v_a = cf E B C_a B^H E^H cf xv (psmc.py:111-161), clarray (nbands, L, F, F)."""
+def alt_vecs(evals, evecs, beam_svd, svnum, clarray, signs, dtype=np.complex128):
+    """v_a = cf E B C_a B^H E^H cf xv (psmc.py:111-161), clarray (nbands, L, F, F).  `dtype`: the complex type of the
+    arithmetic (np.clongdouble for an extended-precision reference)."""
+    evecs, beam_svd, signs, evals, clarray = _as(dtype, (evecs, beam_svd, signs), (evals, clarray))
     cf = (evals + 1.0) ** -0.5
-    x3 = svd_to_sky(beam_svd, svnum, evecs.conj().T @ (cf[:, np.newaxis] * signs))   # (F, L, ns)
+    x3 = svd_to_sky(beam_svd, svnum, evecs.conj().T @ (cf[:, np.newaxis] * signs), dtype=dtype)   # (F, L, ns)
     out = []
     for a in range(clarray.shape[0]):
         x4 = np.einsum("lfg,gls->fls", clarray[a], x3)
-        x5 = sky_to_svd(beam_svd, svnum, x4[:, np.newaxis])
+        x5 = sky_to_svd(beam_svd, svnum, x4[:, np.newaxis], dtype=dtype)
         out.append(cf[:, np.newaxis] * (evecs @ x5))
     return out
 
 
-def alt_fisher(vecs, ns):
+def alt_fisher(vecs, ns, dtype=np.complex128):
     nb = len(vecs)
-    f = np.zeros((nb, nb), dtype=np.complex128)
+    vecs = _as(dtype, vecs)
+    f = np.zeros((nb, nb), dtype=dtype)
     for a in range(nb):
         for b in range(a + 1):
             f[a, b] = np.sum(vecs[a] * vecs[b].conj()) / ns

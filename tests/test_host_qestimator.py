@@ -8,37 +8,52 @@ import numpy as np
 import pytest
 
 
-def sky_to_svd(beam_svd, svnum, a):
-    """(F, P, L, ...) sky vector -> SVD basis (temperature only): x[f-range] = B_f[:, 0, :] a[f, 0]."""
+def _as(dtype, cplx, real=()):
+    """The arrays `cplx` in the complex `dtype` and `real` in its real type (None stays None); untouched for complex128,
+    so that the float64 statement is exactly what it was."""
+    if np.dtype(dtype) == np.complex128:
+        return list(cplx) + list(real)
+    rd = np.zeros(0, dtype=dtype).real.dtype
+    return ([None if v is None else np.asarray(v, dtype=dtype) for v in cplx]
+            + [np.asarray(v, dtype=rd) for v in real])
+
+
+def sky_to_svd(beam_svd, svnum, a, dtype=np.complex128):
+    """(F, P, L, ...) sky vector -> SVD basis (temperature only): x[f-range] = B_f[:, 0, :] a[f, 0].  `dtype`: the
+    complex type of the arithmetic (np.clongdouble for an extended-precision reference)."""
+    beam_svd, a = _as(dtype, (beam_svd, a))
     bounds = np.concatenate([[0], np.cumsum(svnum)])
-    out = np.zeros((bounds[-1],) + a.shape[3:], dtype=np.complex128)
+    out = np.zeros((bounds[-1],) + a.shape[3:], dtype=dtype)
     for f in range(len(svnum)):
         out[bounds[f] : bounds[f + 1]] = np.tensordot(beam_svd[f, : svnum[f], 0, :], a[f, 0], axes=(1, 0))
     return out
 
 
-def svd_to_sky(beam_svd, svnum, x):
+def svd_to_sky(beam_svd, svnum, x, dtype=np.complex128):
     """SVD basis -> (F, L, ...) sky vector through B^H (temperature only)."""
+    beam_svd, x = _as(dtype, (beam_svd, x))
     bounds = np.concatenate([[0], np.cumsum(svnum)])
     F, L = beam_svd.shape[0], beam_svd.shape[-1]
-    out = np.zeros((F, L) + x.shape[1:], dtype=np.complex128)
+    out = np.zeros((F, L) + x.shape[1:], dtype=dtype)
     for f in range(F):
         out[f] = np.tensordot(beam_svd[f, : svnum[f], 0, :].conj(), x[bounds[f] : bounds[f + 1]], axes=(0, 0))
     return out
 
 
-def q_estimate(evals, evecs, beam_svd, svnum, clarray, x, y=None, noise=False, crosspower=False, zero_mean=True):
+def q_estimate(evals, evecs, beam_svd, svnum, clarray, x, y=None, noise=False, crosspower=False, zero_mean=True,
+               dtype=np.complex128):
     """q (nbands [+1], ...) of KL data x (and y); evecs (nmodes, ndof) rows = modes, clarray (nbands, L, F, F)."""
+    evecs, beam_svd, x, y, evals, clarray = _as(dtype, (evecs, beam_svd, x, y), (evals, clarray))
     w = 1.0 / (evals + 1.0)
     x0 = (x.T * w).T
-    x2 = svd_to_sky(beam_svd, svnum, evecs.conj().T @ x0)
+    x2 = svd_to_sky(beam_svd, svnum, evecs.conj().T @ x0, dtype=dtype)
     if y is None:
         y0, y2 = x0, x2
     else:
         y0 = (y.T * w).T
-        y2 = svd_to_sky(beam_svd, svnum, evecs.conj().T @ y0)
+        y2 = svd_to_sky(beam_svd, svnum, evecs.conj().T @ y0, dtype=dtype)
     nb = clarray.shape[0]
-    q = np.zeros((nb + (1 if noise else 0),) + x.shape[1:])
+    q = np.zeros((nb + (1 if noise else 0),) + x.shape[1:], dtype=np.zeros(0, dtype=dtype).real.dtype)
     for a in range(nb):
         # sum over l, f, f' of conj(y2[f, l]) C[a, l, f, f'] x2[f', l]
         q[a] = np.einsum("fl...,lfg,gl...->...", y2.conj(), clarray[a], x2).real
