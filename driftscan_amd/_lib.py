@@ -250,6 +250,12 @@ SIGNATURES = {
                 ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dm_formedbeam_block": (c_int, []),
     "dm_formedbeam_max_nu": (c_int, []),
+    "dm_delay_spectrum": (
+        c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, ctypes.POINTER(c_int), c_vp, c_vp,
+                c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dm_delayspec_max_nf": (c_int, []),
+    "dm_delayspec_max_nd": (c_int, []),
+    "dm_delayspec_segments": (c_int, [c_int, ctypes.POINTER(c_int)]),
 }
 
 _lib = None
@@ -1415,6 +1421,90 @@ def _ringmap(self, vis, group_off, members, v, scale, sinza, w=None, taper=None,
 
 
 Context.ringmap = _ringmap
+
+DELAYSPEC_WEIGHTINGS = {"mask": 0, "weight": 1}
+
+
+def delayspec_bins(nt, bins=None):
+    """The bin table of `Context.delay_spectrum` as int32 (nbin + 1): None is one bin over all nt samples, an int bins of
+    that many samples (the last one short), an array the table itself (ascending, within [0, nt])."""
+    nt = int(nt)
+    if bins is None:
+        off = np.array([0, nt], dtype=np.int32)
+    elif np.ndim(bins) == 0:
+        n = int(bins)
+        if n < 1:
+            raise ValueError("delay_spectrum: bins of at least one sample expected")
+        off = np.append(np.arange(0, nt, n), nt).astype(np.int32)
+    else:
+        off = np.ascontiguousarray(np.asarray(bins).reshape(-1), dtype=np.int32)
+        if not np.array_equal(off, np.asarray(bins).reshape(-1)):
+            raise ValueError("delay_spectrum: the bin table must hold integers")
+    if off.shape[0] < 1 or off[0] < 0 or off[-1] > nt or np.any(np.diff(off) < 0):
+        raise ValueError("delay_spectrum: the bin table (nbin + 1) must ascend within [0, nt]")
+    return off
+
+
+def _delay_spectrum(self, x, w=None, taper=None, step=None, nd=None, a0=None, weighting="mask", min_valid=1, bins=None,
+                    out=None):
+    """Delay power spectra with their window function (dm_delay_spectrum, DESIGN.md section 4.27;
+    `timestream.delay_spectrum_host` restates it).  x (nf, nrow, nt) complex128, contiguous; w float64 of that shape or
+    None (ones): a sample is kept iff w > 0.  taper (nf,) or None (ones) and step (nf,), the turns per delay step of every
+    channel ((nu_f - nu_ref) dtau, `timestream.delay_grid`), are float64 device tensors, or anything numpy turns into
+    such arrays.  nd delays a = 0 .. nd - 1 at (a - a0) steps (a0 None: nd // 2) and lags 0 .. nd - 1.  weighting "mask"
+    (omega = 1 on kept samples) or "weight" (omega = w); a series with fewer than min_valid kept channels is dropped.
+    bins: None (one bin over all samples), an int (bins of that many samples, the last one short) or the table (nbin + 1)
+    of ascending sample offsets.  Returns (q, h, s1, s2, count): q and h (nrow, nbin, nd), s1 and s2 (nrow, nbin) float64,
+    count (nrow, nbin) int32.  `out` takes that tuple of tensors to write into; None in the place of h, s1, s2 or count
+    leaves that output out (None is returned in its place)."""
+    torch = self.torch
+    if weighting not in DELAYSPEC_WEIGHTINGS:
+        raise ValueError('delay_spectrum: weighting is "mask" or "weight"')
+    if not (_is_c128(x) and x.dim() == 3):
+        raise ValueError("delay_spectrum: contiguous complex128 tensor x (nf, nrow, nt) expected")
+    nf, nrow, nt = (int(s) for s in x.shape)
+    if w is not None:
+        _weights_arg("delay_spectrum", w, x.shape)
+    if step is None or nd is None:
+        raise ValueError("delay_spectrum: step and nd are required")
+    nd = int(nd)
+    a0 = nd // 2 if a0 is None else int(a0)
+    min_valid = int(min_valid)
+    if nd < 0 or (nd > 0 and not 0 <= a0 < nd) or min_valid < 1:
+        raise ValueError("delay_spectrum: nd >= 0, a0 in [0, nd) and min_valid >= 1 expected")
+    off = delayspec_bins(nt, bins)
+    nbin = int(off.shape[0]) - 1
+
+    def table(t, name):
+        if not hasattr(t, "data_ptr"):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))).to(x.device)
+        if not (t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (nf,)):
+            raise ValueError("delay_spectrum: %s must be a contiguous float64 tensor (nf,)" % name)
+        return t
+
+    step = table(step, "step")
+    taper = None if taper is None else table(taper, "taper")
+    shapes = ((nrow, nbin, nd), (nrow, nbin, nd), (nrow, nbin), (nrow, nbin), (nrow, nbin))
+    dtypes = (torch.float64,) * 4 + (torch.int32,)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 5 or out[0] is None or not all(
+                o is None or (hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous())
+                for o, s, d in zip(out, shapes, dtypes)):
+            raise ValueError("delay_spectrum: out must hold contiguous tensors q, h (nrow, nbin, nd), s1, s2 (nrow, nbin) "
+                             "float64 and count (nrow, nbin) int32 (None for h, s1, s2 or count: not written)")
+    if not all(t is None or (t.is_cuda and t.device == x.device) for t in (x, w, taper, step) + out):
+        raise ValueError("delay_spectrum: x, w, taper, step and the outputs must be tensors on one GPU")
+    rc = self.lib.dm_delay_spectrum(self.h, nf, nrow, nt, nd, a0, DELAYSPEC_WEIGHTINGS[weighting], min_valid,
+                                    self.ptr(taper), self.ptr(step), nbin, off.ctypes.data_as(ctypes.POINTER(c_int)),
+                                    self.ptr(x), self.ptr(w), *(self.ptr(o) for o in out))
+    self.check(rc, "dm_delay_spectrum")
+    return out
+
+
+Context.delay_spectrum = _delay_spectrum
 
 
 def _formed_beam(self, vis, group_off, members, iu, iv, uvals, vvals, scale, env, k0, half, turn, sinth, yc0, yc1, w=None,

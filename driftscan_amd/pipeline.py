@@ -32,6 +32,10 @@ And ``ringmaps``, entries ``{name, nel, weighting: natural | uniform, window: ha
 collapse_ew}`` (all optional), each of which writes ``ringmap_<name>.hdf5`` per frequency and at the root of every timestream
 in the maps stage: its stacked visibilities beamformed north-south, sample by sample (``timestream.ringmap``).  It needs no
 products beyond the telescope; an unknown key raises ValueError.
+And ``delayspectra``, entries ``{name, nd, oversample, tau_max, taper, weighting: mask | weight, norm: window | inverse, ridge,
+min_valid, tbin, blen_bins}`` (all optional), each of which writes ``delayspectrum_<name>.hdf5`` at the root of every
+timestream in the maps stage: the delay power spectrum of every stacked baseline with its window function
+(``timestream.delay_spectrum``); an unknown key raises ValueError.
 And ``formedbeams``, entries ``{name, catalogue, ha_max, envelope_fwhm, weighting, window, ew: [...], intracyl, parts, stack:
 {halfwidth, line_mhz, source_weight, channel_weight}}`` (``catalogue``, a file of positions, is required), each of which
 writes ``formedbeam_<name>.hdf5`` per frequency and at the root of every timestream in the maps stage: a tracking beam
@@ -77,6 +81,9 @@ class PipelineManager(config.Reader):
     # formed beams on catalogue positions (not in the reference): entries {name, catalogue, ha_max, envelope_fwhm, weighting,
     # window, ew, intracyl, parts, stack}
     formedbeams = config.Property(proptype=list, default=[])
+    # delay power spectra (not in the reference): entries {name, nd, oversample, tau_max, taper, weighting, norm, ridge,
+    # min_valid, tbin, blen_bins}
+    delayspectra = config.Property(proptype=list, default=[])
 
     nside = config.Property(proptype=int, default=128)
     wiener = config.Property(proptype=bool, default=False)
@@ -112,6 +119,8 @@ class PipelineManager(config.Reader):
         self.read_config(yconf["config"])
         for entry in self.ringmaps:   # an unknown key is refused before anything runs
             timestream.ringmap_params(entry)
+        for entry in self.delayspectra:
+            timestream.delayspectrum_params(entry)
         for entry in self.formedbeams:
             if timestream.formedbeam_params(entry)["catalogue"] is None:
                 raise ValueError("formedbeams: an entry needs `catalogue`, a file of positions")
@@ -275,6 +284,10 @@ class PipelineManager(config.Reader):
                     entry = timestream.ringmap_params(entry)
                     logger.info("Generating ring map %s (%s)", entry["name"], tsname)
                     timestream.ringmap(tsobj.manager, tsobj.directory, chunk_gb=self.chunk_gb, **entry)
+                for entry in self.delayspectra:
+                    entry = timestream.delayspectrum_params(entry)
+                    logger.info("Generating delay spectrum %s (%s)", entry["name"], tsname)
+                    timestream.delay_spectrum(tsobj.manager, tsobj.directory, chunk_gb=self.chunk_gb, **entry)
                 for entry in self.formedbeams:
                     entry = timestream.formedbeam_params(entry)
                     logger.info("Forming beams %s (%s)", entry["name"], tsname)

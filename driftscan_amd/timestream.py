@@ -4020,3 +4020,317 @@ def formed_beam(m, indir, cat, name="formedbeam", ha_max=0.05, envelope_fwhm=Non
                 f.create_dataset("channel", data=st["channel"])
     parallel.barrier()
     return root
+
+
+# ---- delay power spectra of stacked visibilities with their window function ---------------
+
+DELAYSPEC_WEIGHTINGS = ("mask", "weight")
+DELAYSPEC_TAPERS = (None, "hann", "blackman", "blackman-harris")
+DELAYSPEC_NORMS = ("window", "inverse")
+
+
+def delay_spectrum_host(x, w, taper, step, nd, a0, weighting, min_valid, bin_off, dtype=np.float64):
+    """The numpy statement of `Context.delay_spectrum` in `dtype`, np.float64 or np.longdouble:
+        y_f = T_f omega_f (omega = 1 with weighting "mask", w with "weight", on the samples with w > 0; 0 elsewhere),
+        phi_fk = step_f k, taken as phi - rint(phi) into cos and sin of pi (2 .),
+        D_a(t) = sum_f y_f x_f exp(2 pi i phi_f,(a - a0)),   W_d(t) = sum_f y_f exp(2 pi i phi_f,d),
+        q = sum_t |D_a|^2, h = sum_t |W_d|^2, s1 = sum_t sum_f T_f^2 omega_f, s2 = sum_t sum_f T_f^2 omega_f^2
+    over the series of every bin (bin_off (nbin + 1), ascending within [0, nt]) that have at least min_valid kept
+    channels; count is their number.  x (nf, nrow, nt) complex, w of that shape or None (ones), taper (nf,) or None
+    (ones), step (nf,).  In long double step_f k is exact for |k| < 2^11.  Samples that are not kept enter no arithmetic.
+    Returns (q, h (nrow, nbin, nd), s1, s2 (nrow, nbin), count int32)."""
+    if dtype not in (np.float64, np.longdouble):
+        raise ValueError("delay_spectrum_host: dtype is np.float64 or np.longdouble")
+    if weighting not in DELAYSPEC_WEIGHTINGS:
+        raise ValueError('delay_spectrum_host: weighting is "mask" or "weight"')
+    x = np.asarray(x)
+    if x.ndim != 3 or not np.iscomplexobj(x) or (w is not None and np.shape(w) != x.shape):
+        raise ValueError("delay_spectrum_host: complex x (nf, nrow, nt) and w of that shape or None expected")
+    nf, nrow, nt = x.shape
+    nd, a0, min_valid = int(nd), int(a0), int(min_valid)
+    step = np.asarray(step, dtype=np.float64)
+    off = np.asarray(bin_off, dtype=np.int64).reshape(-1)
+    if step.shape != (nf,) or (taper is not None and np.shape(taper) != (nf,)):
+        raise ValueError("delay_spectrum_host: step and taper hold one value per frequency")
+    if nd < 0 or (nd > 0 and not 0 <= a0 < nd) or min_valid < 1:
+        raise ValueError("delay_spectrum_host: nd >= 0, a0 in [0, nd) and min_valid >= 1 expected")
+    if off.size < 1 or off[0] < 0 or off[-1] > nt or np.any(np.diff(off) < 0):
+        raise ValueError("delay_spectrum_host: bin_off (nbin + 1) must ascend within [0, nt]")
+    nbin = off.size - 1
+    ctype = np.complex128 if dtype is np.float64 else np.clongdouble
+    pi = _ld_pi() if dtype is np.longdouble else np.pi
+    T = np.ones(nf, dtype=dtype) if taper is None else np.asarray(taper, dtype=np.float64).astype(dtype)
+    with np.errstate(invalid="ignore"):
+        kept = np.ones(x.shape, dtype=bool) if w is None else np.asarray(w) > 0
+    om = kept.astype(dtype) if (w is None or weighting == "mask") else np.where(kept, np.asarray(w), 0.0).astype(dtype)
+    y = np.where(kept, T[:, None, None] * om, 0)
+    yx = np.where(kept, y * np.where(kept, x, 0).astype(ctype), 0)
+    used = kept.sum(axis=0) >= min_valid   # (nrow, nt)
+
+    def phases(k):
+        phi = step.astype(dtype)[:, None] * k.astype(dtype)[None, :]
+        ang = pi * (2 * (phi - np.rint(phi)))
+        return (np.cos(ang) + 1j * np.sin(ang)).astype(ctype)   # (nf, len k)
+
+    Ea, Ew = phases(np.arange(nd) - a0), phases(np.arange(nd))
+    q, h = np.zeros((nrow, nbin, nd), dtype=dtype), np.zeros((nrow, nbin, nd), dtype=dtype)
+    s1, s2 = np.zeros((nrow, nbin), dtype=dtype), np.zeros((nrow, nbin), dtype=dtype)
+    count = np.zeros((nrow, nbin), dtype=np.int32)
+    for r in range(nrow):
+        for b in range(nbin):
+            ts = np.arange(off[b], off[b + 1])[used[r, off[b] : off[b + 1]]]
+            count[r, b] = ts.size
+            if ts.size == 0 or nf == 0:
+                continue
+            D = Ea.T @ yx[:, r, ts]
+            W = Ew.T @ y[:, r, ts].astype(ctype)
+            q[r, b] = (D.real * D.real + D.imag * D.imag).sum(axis=1)
+            h[r, b] = (W.real * W.real + W.imag * W.imag).sum(axis=1)
+            s1[r, b] = (T[:, None] * y[:, r, ts]).sum()
+            s2[r, b] = (y[:, r, ts] * y[:, r, ts]).sum()
+    return q, h, s1, s2, count
+
+
+def delay_grid(tel, nd=None, oversample=1.0, tau_max=None):
+    """The uniform delay grid of `delay_spectrum` for telescope `tel` (or an array of frequencies in MHz): the step
+    dtau = 1 / (oversample nf dnu) in microseconds, dnu the median channel spacing as in `delay_classes`; nd delays
+    (default nf, or with tau_max the 2 ceil(tau_max / dtau) + 1 that reach it on both sides) centred on a0 = nd // 2;
+    step_f = (nu_f - nu_ref) dtau turns per delay step, nu_ref the band centre.  Returns (tau_us (nd,), step (nf,), a0,
+    dtau).  Non-finite values and fewer than two frequencies raise ValueError."""
+    nu = np.asarray(getattr(tel, "frequencies", tel), dtype=np.float64).reshape(-1)
+    if nu.size < 2 or not np.all(np.isfinite(nu)):
+        raise ValueError("delay_grid: at least two finite frequencies expected")
+    dnu = float(np.median(np.abs(np.diff(nu))))
+    oversample = float(oversample)
+    if not (np.isfinite(oversample) and oversample > 0 and dnu > 0):
+        raise ValueError("delay_grid: a finite oversample > 0 and distinct frequencies expected")
+    dtau = 1.0 / (oversample * nu.size * dnu)
+    if tau_max is not None:
+        tau_max = float(tau_max)
+        if not (np.isfinite(tau_max) and tau_max >= 0):
+            raise ValueError("delay_grid: tau_max must be finite and >= 0")
+        if nd is None:
+            nd = 2 * int(np.ceil(tau_max / dtau)) + 1
+    nd = nu.size if nd is None else int(nd)
+    if nd < 1:
+        raise ValueError("delay_grid: nd < 1")
+    a0 = nd // 2
+    ref = 0.5 * (nu.min() + nu.max())
+    return (np.arange(nd) - a0) * dtau, np.ascontiguousarray((nu - ref) * dtau), a0, dtau
+
+
+def delay_taper(nf, kind=None):
+    """The frequency taper of a delay spectrum at the channel centres x = (f + 1/2) / nf (no channel gets weight 0): None
+    (ones), "hann", "blackman" or "blackman-harris" (four terms, -92 dB)."""
+    nf = int(nf)
+    if nf < 1 or kind not in DELAYSPEC_TAPERS:
+        raise ValueError('delay_taper: nf >= 1 and kind None, "hann", "blackman" or "blackman-harris" expected')
+    coef = {None: (1.0,), "hann": (0.5, -0.5), "blackman": (0.42, -0.5, 0.08),
+            "blackman-harris": (0.35875, -0.48829, 0.14128, -0.01168)}[kind]
+    x = (np.arange(nf) + 0.5) / nf
+    return np.ascontiguousarray(sum(c * np.cos(2.0 * np.pi * k * x) for k, c in enumerate(coef)) + np.zeros(nf))
+
+
+def delay_normalise(q, h, s, norm="window", ridge=0.0):
+    """The delay spectrum from the quadratic sums of `delay_spectrum`: q and h (..., nd) and the noise bias s (...) (s1 or
+    s2).  h is the first column of the window matrix F_ab = H_|a - b| of q (real, symmetric, Toeplitz).  norm "window":
+    p_a = q_a / sum_b H_|a - b| (every estimate keeps its window, normalised to unit sum); "inverse": p = (F + ridge H_0
+    I)^-1 q, the windows undone.  The noise floor is s put through the same operator (the bias of every q_a is s).
+    Device tensors go through `Context.toeplitz_solve` (q and the floor as two right-hand sides of one batched call),
+    host arrays through `toeplitz_levinson_host`.  Returns (spectrum, noise (..., nd), info (...) int32): info = 0, or the
+    code of the Toeplitz solve (nd for H_0 <= 0, as in a bin without data, with "window" too); where info != 0 spectrum
+    and noise are NaN."""
+    if norm not in DELAYSPEC_NORMS:
+        raise ValueError('delay_normalise: norm is "window" or "inverse"')
+    ridge = float(ridge)
+    if not (np.isfinite(ridge) and ridge >= 0):
+        raise ValueError("delay_normalise: ridge not finite or negative")
+    on_device = hasattr(q, "data_ptr")
+    if tuple(q.shape) != tuple(h.shape) or tuple(s.shape) != tuple(q.shape[:-1]) or len(q.shape) < 1:
+        raise ValueError("delay_normalise: q and h (..., nd) and s (...) expected")
+    lead, nd = tuple(q.shape[:-1]), int(q.shape[-1])
+    if on_device:
+        ctx = get_context()
+        torch = ctx.torch
+        q2, h2, s2 = q.reshape(-1, nd), h.reshape(-1, nd), s.reshape(-1)
+        batch = int(q2.shape[0])
+        if batch == 0 or nd == 0:
+            return torch.zeros_like(q), torch.zeros_like(q), torch.zeros(lead, dtype=torch.int32, device=q.device)
+        nan = torch.full_like(q2, float("nan"))
+        if norm == "window":
+            cum = torch.cumsum(h2, dim=1)   # sum_b H_|a - b| = C_a + C_(nd - 1 - a) - H_0, C the running sum of H
+            rows = cum + torch.flip(cum, dims=(1,)) - h2[:, :1]
+            info = torch.where(h2[:, 0] > 0, 0, nd).to(torch.int32)
+            ok = (info == 0)[:, None]
+            safe = torch.where(ok, rows, torch.ones_like(rows))
+            p, n = torch.where(ok, q2 / safe, nan), torch.where(ok, s2[:, None] / safe, nan)
+        else:
+            b = torch.stack([q2, s2[:, None].expand(batch, nd)], dim=1).to(torch.complex128)
+            xs, info = ctx.toeplitz_solve(h2.to(torch.complex128), b, ridge=ridge)
+            ok = (info == 0)[:, None]
+            p, n = torch.where(ok, xs[:, 0].real, nan), torch.where(ok, xs[:, 1].real, nan)
+        return p.reshape(lead + (nd,)), n.reshape(lead + (nd,)), info.reshape(lead)
+    q2, h2 = np.asarray(q, dtype=np.float64).reshape(-1, nd), np.asarray(h, dtype=np.float64).reshape(-1, nd)
+    s2 = np.asarray(s, dtype=np.float64).reshape(-1)
+    batch = q2.shape[0]
+    p, n = np.full((batch, nd), np.nan), np.full((batch, nd), np.nan)
+    info = np.zeros(batch, dtype=np.int32)
+    if batch and nd:
+        if norm == "window":
+            cum = np.cumsum(h2, axis=1)   # sum_b H_|a - b| = C_a + C_(nd - 1 - a) - H_0, C the running sum of H
+            rows = cum + cum[:, ::-1] - h2[:, :1]
+            info[:] = np.where(h2[:, 0] > 0, 0, nd)
+            ok = info == 0
+            p[ok], n[ok] = q2[ok] / rows[ok], s2[ok, None] / rows[ok]
+        else:
+            col = h2.astype(np.complex128)
+            col[:, 0] += ridge * col[:, 0].real
+            b = np.stack([q2, np.broadcast_to(s2[:, None], (batch, nd))], axis=1)
+            xs, info = toeplitz_levinson_host(col, b)
+            info = np.asarray(info, dtype=np.int32).reshape(batch)
+            ok = info == 0
+            p[ok], n[ok] = xs[ok, 0].real, xs[ok, 1].real
+    return p.reshape(lead + (nd,)), n.reshape(lead + (nd,)), info.reshape(lead)
+
+
+DELAYSPECTRUM_DEFAULTS = dict(name="delayspectrum", nd=None, oversample=1.0, tau_max=None, taper="blackman-harris",
+                              weighting="mask", norm="window", ridge=0.0, min_valid=None, tbin=None, blen_bins=None)
+
+
+def delayspectrum_params(d=None):
+    """One entry of the pipeline's `delayspectra` list with its defaults filled in; an unknown key raises ValueError, and
+    so does a value the steps refuse."""
+    out = _conf_filled(d, DELAYSPECTRUM_DEFAULTS, "delayspectra: unknown key(s) %s (known: %s)", show=", ".join)
+    if out["taper"] in ("none", "None"):
+        out["taper"] = None
+    if out["taper"] not in DELAYSPEC_TAPERS or out["weighting"] not in DELAYSPEC_WEIGHTINGS or out["norm"] not in DELAYSPEC_NORMS:
+        raise ValueError('delayspectra: taper is None, "hann", "blackman" or "blackman-harris", weighting "mask" or "weight", '
+                         'norm "window" or "inverse"')
+    out["ridge"], out["oversample"] = float(out["ridge"]), float(out["oversample"])
+    if not (np.isfinite(out["ridge"]) and out["ridge"] >= 0 and np.isfinite(out["oversample"]) and out["oversample"] > 0):
+        raise ValueError("delayspectra: ridge >= 0 and oversample > 0, both finite, expected")
+    for key in ("nd", "min_valid", "tbin"):
+        if out[key] is not None:
+            out[key] = int(out[key])
+            if out[key] < 1:
+                raise ValueError("delayspectra: %s < 1" % key)
+    if out["tau_max"] is not None and not (np.isfinite(float(out["tau_max"])) and float(out["tau_max"]) >= 0):
+        raise ValueError("delayspectra: tau_max must be finite and >= 0")
+    return out
+
+
+def _delayspec_blen_edges(blen, blen_bins):
+    """The edges of the baseline-length bins: an int gives that many equal bins over [0, max |b|], an array the edges."""
+    if np.ndim(blen_bins) == 0:
+        n = int(blen_bins)
+        if n < 1:
+            raise ValueError("delay_spectrum: blen_bins < 1")
+        top = float(blen.max()) if blen.size else 0.0
+        return np.linspace(0.0, top if top > 0 else 1.0, n + 1)
+    edges = np.asarray(blen_bins, dtype=np.float64).reshape(-1)
+    if edges.size < 2 or not np.all(np.isfinite(edges)) or np.any(np.diff(edges) <= 0):
+        raise ValueError("delay_spectrum: blen_bins must be a count or at least two ascending finite edges")
+    return edges
+
+
+def delay_spectrum(m, indir, name="delayspectrum", nd=None, oversample=1.0, tau_max=None, taper="blackman-harris",
+                   weighting="mask", norm="window", ridge=0.0, min_valid=None, tbin=None, blen_bins=None, chunk_gb=4.0):
+    """The delay power spectrum of every row of the stacked Timestream directory `indir` (`Context.delay_spectrum`,
+    DESIGN.md section 4.27): the quadratic estimator along frequency with the flags honoured, on the grid
+    `delay_grid(tel, nd, oversample, tau_max)` with the taper `delay_taper(nf, taper)`, summed over time bins of `tbin`
+    samples (None: the whole directory is one bin) and normalised by `delay_normalise(norm, ridge)`.  weighting "mask"
+    uses the flags only, "weight" the weights themselves; a series with fewer than `min_valid` (None: 1) kept channels
+    is dropped.  The spectrum needs every frequency of a row at once, so the device takes chunks of rows over all
+    frequency files that fit `chunk_gb`; more than one rank raises ValueError, and so does an unstacked directory.
+    Writes `delayspectrum_<name>.hdf5` at the root of the directory: `tau` (nd, microseconds), `q`, `window` (= h),
+    `spectrum` and `noise` (the normalised s1 for "weight", s2 for "mask") (nrow, nbin, nd), `s1`, `s2`, `count` and
+    `info` (nrow, nbin), `bin_off`, `step`, `taper`, `blen` (m) and `horizon` (|b| / c in microseconds) per row, with
+    `blen_bins` (a count of equal bins up to the longest baseline, or the edges) `blen_edges`, `wedge` (nblen, nbin, nd),
+    the count-weighted mean of `spectrum` over the solved rows of each length bin (NaN where none), and `wedge_hits`
+    (nblen, nbin), the series behind it; and the parameters as attributes.  The written bits do not depend on
+    `chunk_gb`.  Returns the path of the file."""
+    p = delayspectrum_params(dict(name=name, nd=nd, oversample=oversample, tau_max=tau_max, taper=taper, weighting=weighting,
+                                  norm=norm, ridge=ridge, min_valid=min_valid, tbin=tbin, blen_bins=blen_bins))
+    _delay_one_rank("delay_spectrum")
+    tel = m.beamtransfer.telescope
+    src = Timestream(indir, m)
+    src._refuse_unstacked()
+    freqs = list(range(tel.nfreq))
+    nf = len(freqs)
+    tau, step, a0, dtau = delay_grid(tel, nd=p["nd"], oversample=p["oversample"], tau_max=p["tau_max"])
+    nd = int(tau.size)
+    tap = delay_taper(nf, p["taper"])
+    need = 1 if p["min_valid"] is None else p["min_valid"]
+    log = sim_log
+    with _StepTimer(log, "read"):
+        xs, ws = [], []
+        for fi in freqs:
+            xs.append(np.asarray(src.timestream_f(fi), dtype=np.complex128))
+            ws.append(src.weight_f(fi))
+        nrow, nt = (int(v) for v in xs[0].shape)
+        if any(a.shape != (nrow, nt) for a in xs):
+            raise ValueError("delay_spectrum: the files of %s do not hold one shape" % src.directory)
+        if nrow != int(tel.npairs):
+            raise ValueError("delay_spectrum: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, int(tel.npairs)))
+        weighted = any(wf is not None for wf in ws)
+    from ._lib import delayspec_bins
+
+    off = delayspec_bins(nt, p["tbin"])
+    nbin = int(off.size) - 1
+    rows_per = int(chunk_gb * 2.0**30 // (24.0 * nf * nt + 40.0 * nbin * nd + 64.0))
+    if rows_per < 1:
+        raise ValueError("delay_spectrum: one row over all frequencies needs chunk_gb >= %.4g (given: %g)"
+                         % ((24.0 * nf * nt + 40.0 * nbin * nd + 64.0) / 2.0**30 * 1.001, chunk_gb))
+    ctx = get_context()
+    out = dict(q=np.empty((nrow, nbin, nd)), window=np.empty((nrow, nbin, nd)), spectrum=np.empty((nrow, nbin, nd)),
+               noise=np.empty((nrow, nbin, nd)), s1=np.empty((nrow, nbin)), s2=np.empty((nrow, nbin)),
+               count=np.empty((nrow, nbin), dtype=np.int32), info=np.empty((nrow, nbin), dtype=np.int32))
+    with _StepTimer(log, "delay_spectrum"):
+        tap_d, step_d = ctx.to_device(tap), ctx.to_device(step)
+        for r0 in range(0, nrow, rows_per):
+            r1 = min(nrow, r0 + rows_per)
+            x_d = ctx.to_device(np.stack([a[r0:r1] for a in xs]))
+            w_d = None
+            if weighted:
+                w_d = ctx.to_device(np.stack([np.ones((r1 - r0, nt)) if wf is None else np.asarray(wf[r0:r1], dtype=np.float64)
+                                              for wf in ws]))
+            q, h, s1, s2, cnt = ctx.delay_spectrum(x_d, w=w_d, taper=tap_d, step=step_d, nd=nd, a0=a0, weighting=p["weighting"],
+                                                   min_valid=need, bins=off)
+            sp, ns, info = delay_normalise(q, h, s1 if p["weighting"] == "weight" else s2, norm=p["norm"], ridge=p["ridge"])
+            for key, value in (("q", q), ("window", h), ("spectrum", sp), ("noise", ns), ("s1", s1), ("s2", s2), ("count", cnt),
+                               ("info", info)):
+                out[key][r0:r1] = ctx.to_host(value)
+            del x_d, w_d, q, h, s1, s2, cnt, sp, ns, info
+    blen = np.sqrt((np.asarray(tel.baselines, dtype=np.float64).reshape(nrow, -1) ** 2).sum(axis=1))
+    root = os.path.join(src.directory, "delayspectrum_%s.hdf5" % p["name"])
+    with _StepTimer(log, "write"):
+        with storage.File(root, "w") as f:
+            f.create_dataset("tau", data=tau)
+            for key, value in out.items():
+                f.create_dataset(key, data=value)
+            for key, value in (("bin_off", off), ("step", step), ("taper", tap), ("blen", blen), ("horizon", blen / DELAY_C)):
+                f.create_dataset(key, data=value)
+            if p["blen_bins"] is not None:
+                edges = _delayspec_blen_edges(blen, p["blen_bins"])
+                which = np.clip(np.searchsorted(edges, blen, side="right") - 1, -1, edges.size - 2)
+                which[(blen < edges[0]) | (blen > edges[-1])] = -1
+                good = (out["info"] == 0) & (out["count"] > 0)
+                wgt = np.where(good, out["count"], 0).astype(np.float64)
+                wedge = np.full((edges.size - 1, nbin, nd), np.nan)
+                hits = np.zeros((edges.size - 1, nbin), dtype=np.int64)
+                for j in range(edges.size - 1):   # in row order: the bits do not depend on the chunk
+                    rows = np.nonzero(which == j)[0]
+                    num, den = np.zeros((nbin, nd)), np.zeros(nbin)
+                    for r in rows:
+                        num += wgt[r][:, None] * np.where(good[r][:, None], out["spectrum"][r], 0.0)
+                        den += wgt[r]
+                    wedge[j] = np.where(den[:, None] > 0, num / np.where(den > 0, den, 1.0)[:, None], np.nan)
+                    hits[j] = den.astype(np.int64)
+                f.create_dataset("blen_edges", data=edges)
+                f.create_dataset("wedge", data=wedge)
+                f.create_dataset("wedge_hits", data=hits)
+            for key, value in dict(nd=nd, a0=int(a0), dtau=float(dtau), oversample=p["oversample"], taper=p["taper"] or "none",
+                                   weighting=p["weighting"], norm=p["norm"], ridge=p["ridge"], min_valid=int(need),
+                                   tbin=-1 if p["tbin"] is None else p["tbin"], ntime=nt).items():
+                f.attrs[key] = value
+    return root

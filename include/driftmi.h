@@ -1066,6 +1066,46 @@ int dm_formed_beam(dm_ctx* ctx, int nf, int nrow, int nt, int ngroup, const int*
 int dm_formedbeam_block(void);
 int dm_formedbeam_max_nu(void);
 
+/* ---- delay power spectra of stacked visibilities with their window function ------------- */
+/* dm_delay_spectrum: for every row r, sample t, delay a = 0 .. nd - 1 and lag d = 0 .. nd - 1
+ *   y_f = T_f omega_f,   omega_f = 1 (weighting 0) or w_f (weighting 1) on kept samples and 0 elsewhere,
+ *   phi_fk = step_f k, one rounded product, reduced as phi - rint(phi) (exact) into sincospi,
+ *   D_a(t) = sum_f y_f x_f exp(2 pi i phi_f,(a - a0)),
+ *   W_d(t) = sum_f y_f exp(2 pi i phi_f,d),
+ * and for every bin b of samples, over its used series (those with at least min_valid >= 1 kept channels)
+ *   q[r, b, a] = sum_t |D_a(t)|^2,   h[r, b, d] = sum_t |W_d(t)|^2,
+ *   s1[r, b] = sum_t sum_f T_f^2 omega_f,   s2[r, b] = sum_t sum_f T_f^2 omega_f^2,   count[r, b] = the used series.
+ * x (nf, nrow, nt) complex128; w (nf, nrow, nt) float64 or null (ones): a sample is kept iff w > 0 (false for 0,
+ * negatives and NaN), and x and w of a sample that is not kept reach no arithmetic.  taper (nf, null: ones) and step
+ * (nf, turns per delay step of every channel: (nu_f - nu_ref) dtau) float64 are on the device.  bin_off (nbin + 1) int32
+ * is a HOST table: bin b holds the samples bin_off[b] .. bin_off[b + 1] - 1, ascending and within [0, nt]; the samples
+ * outside every bin are not used.  q and h (nrow, nbin, nd), s1 and s2 (nrow, nbin) float64, count (nrow, nbin) int32;
+ * h, s1, s2 and count may be null: not written.  A bin with no used series gives exact zeros everywhere.  With real
+ * weights the window matrix of q, F_ab = sum_t |W_(a - b)(t)|^2, depends on |a - b| alone: h is the first column of
+ * that symmetric Toeplitz matrix, and s1 (inverse-variance weights) or s2 (unit weights, uniform variance) the noise
+ * bias of q.
+ * The products run on the fp64 MFMA with the phases made in registers and the weighting on the way into LDS: no phase
+ * table, no weighted copy and no transformed cube in memory, no floating-point atomics.  The order of every sum is a
+ * function of nf and of the bin's sample range alone (dm_delayspec.hip states it; a bin of more than 128 samples is cut
+ * into dm_delayspec_segments() segments whose partial sums a second kernel adds in ascending order from scratch memory
+ * of at most 4 (2 nd + 2) doubles per (row, bin)): the bits of (r, b, .) do not depend on the other rows and bins, on nd
+ * (a smaller nd gives a prefix of h, and of q for the same a0) or on which optional outputs are null.  Refused before
+ * any launch (dm_last_error): negative sizes, weighting outside {0, 1}, nf > dm_delayspec_max_nf(), nd >
+ * dm_delayspec_max_nd(), min_valid < 1, a0 outside [0, nd) (for nd > 0), and with work to do: a null x, step, bin_off
+ * or q, a bin_off that decreases or leaves [0, nt], an output sharing an element with an input or another output, nrow
+ * or nbin > 65535.  nf, nrow, nt, nbin or nd = 0 is a no-op.  Returns when the work is queued on the context's stream.
+ * No counterpart in the reference. */
+int dm_delay_spectrum(dm_ctx* ctx, int nf, int nrow, int nt, int nd, int a0, int weighting, int min_valid,
+                      const double* taper_dev, const double* step_dev, int nbin, const int* bin_off_host,
+                      const void* x_dev, const double* w_dev, double* q_dev, double* h_dev, double* s1_dev,
+                      double* s2_dev, int* count_dev);
+/* the most frequencies and delays dm_delay_spectrum takes (host only) */
+int dm_delayspec_max_nf(void);
+int dm_delayspec_max_nd(void);
+/* the segments that dm_delay_spectrum cuts a bin of nsamples samples into, and in *length (may be null) the samples of
+ * each but the last (host only; 0 for nsamples <= 0) */
+int dm_delayspec_segments(int nsamples, int* length);
+
 #ifdef __cplusplus
 }
 #endif
