@@ -964,6 +964,79 @@ def _out_arg(ctx, who, out, shapes):
     return out
 
 
+# ---- the arguments of the kernels that take a data cube (nf, nrow, nt) of a Timestream directory ----------------------
+def _cube_arg(who, x, w, name="x"):
+    """The cube `name`, a contiguous complex128 tensor (nf, nrow, nt), and its weights `w`, float64 of that shape or
+    None; returns (nf, nrow, nt)."""
+    if not (_is_c128(x) and x.dim() == 3):
+        raise ValueError("%s: contiguous complex128 tensor %s (nf, nrow, nt) expected" % (who, name))
+    if w is not None:
+        _weights_arg(who, w, x.shape)
+    return tuple(int(v) for v in x.shape)
+
+
+def _is_tensor(t, dtype, shape):
+    return hasattr(t, "data_ptr") and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+
+
+def _out_tuple(who, out, shapes, dtypes, device, optional=(), expected=""):
+    """The tuple of outputs of a kernel: new tensors of `shapes` and `dtypes` on `device` when `out` is None, else `out`
+    itself once every entry is such a tensor (None is allowed at the positions `optional`: that output is not written).
+    `expected` is what the ValueError says after `who`."""
+    import torch
+
+    if out is None:
+        return tuple(torch.empty(s, dtype=d, device=device) for s, d in zip(shapes, dtypes))
+    out = tuple(out)
+    if len(out) != len(shapes) or not all((o is None and i in optional) or _is_tensor(o, d, s)
+                                          for i, (o, s, d) in enumerate(zip(out, shapes, dtypes))):
+        raise ValueError("%s: %s" % (who, expected))
+    return out
+
+
+def _f64_table(who, t, n, name, device):
+    """The table `name` of `n` float64 values (None: of any length) on `device`: a tensor as it is, anything else through
+    numpy."""
+    import torch
+
+    if not hasattr(t, "data_ptr"):
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))).to(device)
+    if not (t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and n in (None, int(t.shape[0]))):
+        raise ValueError("%s: %s must be a contiguous float64 tensor (%s,)" % (who, name, "n" if n is None else n))
+    return t
+
+
+def _f64_out(who, t, shape, name, device):
+    """The float64 output `name` of `shape`: `t`, or a new tensor on `device` when it is None."""
+    import torch
+
+    if t is None:
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if not _is_tensor(t, torch.float64, shape):
+        raise ValueError("%s: %s must be a contiguous float64 tensor %s" % (who, name, shape))
+    return t
+
+
+def _group_table(who, group_off, members, nrow):
+    """The groups of rows of a cube as host integers: group g is members[group_off[g]:group_off[g + 1]], every member a
+    row below `nrow`; returns (group_off, its pointer, members, its pointer)."""
+    off, offp = _iarr(group_off)
+    mem, memp = _iarr(members)
+    if off.ndim != 1 or off.shape[0] < 1 or mem.ndim != 1 or off[0] != 0 or np.any(np.diff(off) < 0) or mem.shape[0] != int(off[-1]):
+        raise ValueError("%s: group_off (ngroup + 1), from 0 and not decreasing, and members (group_off[-1]) expected" % who)
+    if mem.size and (mem.min() < 0 or mem.max() >= nrow):
+        raise ValueError("%s: a member is no row of vis" % who)
+    return off, offp, mem, memp
+
+
+def _same_gpu(who, tensors, what):
+    """Every tensor of `tensors` (None: left out) is on the GPU of the first one, the cube; else ValueError naming `what`.
+    A kernel gets nothing but `data_ptr()`, so a host tensor must stop here."""
+    dev = tensors[0].device
+    if not all(t is None or (t.is_cuda and t.device == dev) for t in tensors):
+        raise ValueError("%s: %s must be tensors on one GPU" % (who, what))
+
+
 def _ts_gain_coeff(self, nreal, fglobal, nfeed, ck, sigma, seed, first=0, stream=25, broadband=False, out=None):
     """Fourier coefficients out[r, i, a, k] = sigma ck[k] (A_k - i B_k) of one component of the feed gains on the device
     (dm_ts_gain_coeff; `skysim.gain_coeff_host` restates it): `fglobal` the global frequency index of every row i, `ck`
@@ -1130,33 +1203,19 @@ def _sidereal_regrid(self, x, phi0, dphi, ntime, w=None, a=3, min_share=1.0, acc
     (sq - |sum|^2 / wsum) / (hits - 1) estimates the variance of one nominal input sample where hits >= 2.  wsum is the
     diagonal weight only: neighbouring samples share taps and are correlated.  The bits of a row do not depend on the
     batch it is in."""
-    if not (_is_c128(x) and x.dim() == 3):
-        raise ValueError("sidereal_regrid: contiguous complex128 tensor x (nf, nrow, nt_in) expected")
-    nf, nrow, nt_in = (int(v) for v in x.shape)
+    torch = self.torch
+    nf, nrow, nt_in = _cube_arg("sidereal_regrid", x, w)
     ntime = int(ntime)
-    if w is not None:
-        _weights_arg("sidereal_regrid", w, x.shape)
     shape = (nf, nrow, max(ntime, 0))
-    if acc is None:
-        accumulate = 0
-        acc = (self.empty(shape, np.complex128), self.empty(shape, np.float64),
-               self.empty(shape, np.float64) if variance else None,
-               self.torch.empty(shape, dtype=self.torch.int32, device=x.device) if variance else None)
-    else:
-        accumulate = 1
-        acc = tuple(acc)
-        if len(acc) != 4:
-            raise ValueError("sidereal_regrid: acc is the tuple (sum, wsum, sq, hits)")
+    accumulate = int(acc is not None)
+    if acc is None and not variance:
+        acc = (torch.empty(shape, dtype=torch.complex128, device=x.device),
+               torch.empty(shape, dtype=torch.float64, device=x.device), None, None)
+    acc = _out_tuple("sidereal_regrid", acc, (shape,) * 4, (torch.complex128, torch.float64, torch.float64, torch.int32),
+                     x.device, optional=(2, 3), expected="acc must hold contiguous tensors (nf, nrow, ntime): sum complex128, "
+                     "wsum float64, sq float64 or None, hits int32 or None")
+    _same_gpu("sidereal_regrid", (x, w) + acc, "x, w and acc")
     s_, ws_, sq_, h_ = acc
-    ok = (_is_c128(s_) and tuple(s_.shape) == shape and hasattr(ws_, "data_ptr") and tuple(ws_.shape) == shape
-          and ws_.is_contiguous() and ws_.dtype == self.torch.float64)
-    ok = ok and (sq_ is None or (hasattr(sq_, "data_ptr") and tuple(sq_.shape) == shape and sq_.is_contiguous()
-                                 and sq_.dtype == self.torch.float64))
-    ok = ok and (h_ is None or (hasattr(h_, "data_ptr") and tuple(h_.shape) == shape and h_.is_contiguous()
-                                and h_.dtype == self.torch.int32))
-    if not ok:
-        raise ValueError("sidereal_regrid: acc must hold contiguous tensors (nf, nrow, ntime): sum complex128, wsum float64, "
-                         "sq float64 or None, hits int32 or None")
     rc = self.lib.dm_sidereal_regrid(self.h, nf, nrow, nt_in, ntime, int(a), float(phi0), float(dphi), float(min_share),
                                      self.ptr(x), self.ptr(w), self.ptr(s_), self.ptr(ws_), self.ptr(sq_), self.ptr(h_),
                                      accumulate)
@@ -1179,36 +1238,7 @@ def _rfi_flag(self, x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4,
     rows where detection flagged the sample anew.  With row_share < 1 a sample that detection flagged in more than
     row_share of the rows where it was not input flagged is flagged in every row of its frequency.  `out` takes that
     tuple of tensors to write into; its w_out may be w itself.  The bits of a row do not depend on the batch it is in."""
-    torch = self.torch
-    if not (_is_c128(x) and x.dim() == 3):
-        raise ValueError("rfi_flag: contiguous complex128 tensor x (nf, nrow, nt) expected")
-    nf, nrow, nt = (int(v) for v in x.shape)
-    if w is not None:
-        _weights_arg("rfi_flag", w, x.shape)
-    segment = int(segment)
-    if segment < 1:
-        raise ValueError("rfi_flag: segment < 1")
-    windows = [int(v) for v in windows]
-    nseg = -(-nt // segment)
-    shapes = ((nf, nrow, nt), (nf, nrow, nseg), (nf, nrow), (nf, nt))
-    dtypes = (torch.float64, torch.float64, torch.int32, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != 4 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
-                                    for o, s, d in zip(out, shapes, dtypes)):
-            raise ValueError("rfi_flag: out must hold contiguous tensors w_out (nf, nrow, nt) float64, noise (nf, nrow, nseg) "
-                             "float64, nflag (nf, nrow) int32 and occupancy (nf, nt) int32")
-    win = (c_int * max(len(windows), 1))(*windows)
-    rc = self.lib.dm_rfi_flag(self.h, nf, nrow, nt, segment, float(kernel_sigma), len(windows), win, float(chi1), float(rho),
-                              int(niter), float(base), int(min_good), float(row_share), self.ptr(x), self.ptr(w),
-                              self.ptr(out[0]), self.ptr(out[1]), self.ptr(out[2]), self.ptr(out[3]))
-    self.check(rc, "dm_rfi_flag")
-    return out
-
-
-Context.rfi_flag = _rfi_flag
+    return _rfi_flag_along(self, "time", x, w, segment, kernel_sigma, windows, chi1, rho, niter, base, min_good, row_share, out)
 
 
 def _rfi_flag_freq(self, x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 2, 4, 8, 16), chi1=6.0, rho=1.5, niter=3,
@@ -1219,35 +1249,36 @@ def _rfi_flag_freq(self, x, w=None, segment=1024, kernel_sigma=2.5, windows=(1, 
     (nf, nrow, nt) float64; noise (nseg, nrow, nt) float64, nseg = ceil(nf / segment); nflag (nrow, nt) int32, the new
     flags of every series; occupancy (nf, nt) int32 — bit for bit what `rfi_flag` returns for the data transposed to
     (nt, nrow, nf), transposed back.  `out` takes that tuple of tensors to write into; its w_out may be w itself."""
+    return _rfi_flag_along(self, "freq", x, w, segment, kernel_sigma, windows, chi1, rho, niter, base, min_good, row_share, out)
+
+
+def _rfi_flag_along(self, axis, x, w, segment, kernel_sigma, windows, chi1, rho, niter, base, min_good, row_share, out):
+    """The body of `rfi_flag` ("time") and `rfi_flag_freq` ("freq"): one method, and noise and nflag take the shape of x
+    with the flagged axis cut into segments and dropped."""
     torch = self.torch
-    if not (_is_c128(x) and x.dim() == 3):
-        raise ValueError("rfi_flag_freq: contiguous complex128 tensor x (nf, nrow, nt) expected")
-    nf, nrow, nt = (int(v) for v in x.shape)
-    if w is not None:
-        _weights_arg("rfi_flag_freq", w, x.shape)
+    who = "rfi_flag" if axis == "time" else "rfi_flag_freq"
+    nf, nrow, nt = _cube_arg(who, x, w)
     segment = int(segment)
     if segment < 1:
-        raise ValueError("rfi_flag_freq: segment < 1")
+        raise ValueError("%s: segment < 1" % who)
     windows = [int(v) for v in windows]
-    nseg = -(-nf // segment)
-    shapes = ((nf, nrow, nt), (nseg, nrow, nt), (nrow, nt), (nf, nt))
-    dtypes = (torch.float64, torch.float64, torch.int32, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
+    if axis == "time":
+        shapes, said = ((nf, nrow, -(-nt // segment)), (nf, nrow)), "noise (nf, nrow, nseg) float64, nflag (nf, nrow)"
     else:
-        out = tuple(out)
-        if len(out) != 4 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
-                                    for o, s, d in zip(out, shapes, dtypes)):
-            raise ValueError("rfi_flag_freq: out must hold contiguous tensors w_out (nf, nrow, nt) float64, noise "
-                             "(nseg, nrow, nt) float64, nflag (nrow, nt) int32 and occupancy (nf, nt) int32")
+        shapes, said = ((-(-nf // segment), nrow, nt), (nrow, nt)), "noise (nseg, nrow, nt) float64, nflag (nrow, nt)"
+    out = _out_tuple(who, out, ((nf, nrow, nt),) + shapes + ((nf, nt),), (torch.float64, torch.float64, torch.int32, torch.int32),
+                     x.device, expected="out must hold contiguous tensors w_out (nf, nrow, nt) float64, %s int32 and occupancy "
+                     "(nf, nt) int32" % said)
+    _same_gpu(who, (x, w) + out, "x, w and out")
     win = (c_int * max(len(windows), 1))(*windows)
-    rc = self.lib.dm_rfi_flag_freq(self.h, nf, nrow, nt, segment, float(kernel_sigma), len(windows), win, float(chi1),
-                                   float(rho), int(niter), float(base), int(min_good), float(row_share), self.ptr(x),
-                                   self.ptr(w), self.ptr(out[0]), self.ptr(out[1]), self.ptr(out[2]), self.ptr(out[3]))
-    self.check(rc, "dm_rfi_flag_freq")
+    rc = getattr(self.lib, "dm_" + who)(self.h, nf, nrow, nt, segment, float(kernel_sigma), len(windows), win, float(chi1),
+                                        float(rho), int(niter), float(base), int(min_good), float(row_share), self.ptr(x),
+                                        self.ptr(w), *(self.ptr(o) for o in out))
+    self.check(rc, "dm_" + who)
     return out
 
 
+Context.rfi_flag = _rfi_flag
 Context.rfi_flag_freq = _rfi_flag_freq
 
 RFI_AXES = {"time": 0, "freq": 1}
@@ -1269,16 +1300,10 @@ def _rfi_dilate(self, w, eta, axis="time", ref=None, out=None):
     nf, nrow, nt = (int(v) for v in w.shape)
     if ref is not None:
         _weights_arg("rfi_dilate", ref, w.shape)
-    shapes = ((nf, nrow, nt), (nf, nrow) if axis == "time" else (nrow, nt))
-    dtypes = (torch.float64, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=w.device) for s, d in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != 2 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
-                                    for o, s, d in zip(out, shapes, dtypes)):
-            raise ValueError("rfi_dilate: out must hold contiguous tensors w_out (nf, nrow, nt) float64 and nadded int32, "
-                             "(nf, nrow) along time or (nrow, nt) along frequency")
+    out = _out_tuple("rfi_dilate", out, ((nf, nrow, nt), (nf, nrow) if axis == "time" else (nrow, nt)), (torch.float64, torch.int32),
+                     w.device, expected="out must hold contiguous tensors w_out (nf, nrow, nt) float64 and nadded int32, "
+                     "(nf, nrow) along time or (nrow, nt) along frequency")
+    _same_gpu("rfi_dilate", (w, ref) + out, "w, ref and out")
     rc = self.lib.dm_rfi_dilate(self.h, nf, nrow, nt, RFI_AXES[axis], float(eta), self.ptr(w), self.ptr(ref),
                                 self.ptr(out[0]), self.ptr(out[1]))
     self.check(rc, "dm_rfi_dilate")
@@ -1321,11 +1346,7 @@ def _delay_fit(self, x, w=None, basis=None, basis_of=None, mode="inpaint", ridge
     torch = self.torch
     if mode not in DELAY_MODES:
         raise ValueError('delay_fit: mode is "model", "filter" or "inpaint"')
-    if not (_is_c128(x) and x.dim() == 3):
-        raise ValueError("delay_fit: contiguous complex128 tensor x (nf, nrow, nt) expected")
-    nf, nrow, nt = (int(v) for v in x.shape)
-    if w is not None:
-        _weights_arg("delay_fit", w, x.shape)
+    nf, nrow, nt = _cube_arg("delay_fit", x, w)
     if basis is None or basis_of is None:
         raise ValueError("delay_fit: basis and basis_of are required")
     if isinstance(basis, tuple) and len(basis) == 2 and hasattr(basis[0], "data_ptr") and basis[0].dim() == 1:
@@ -1340,18 +1361,10 @@ def _delay_fit(self, x, w=None, basis=None, basis_of=None, mode="inpaint", ridge
         basis_of = torch.tensor([int(v) for v in basis_of], dtype=torch.int32, device=x.device)
     if not (basis_of.dtype == torch.int32 and basis_of.is_contiguous() and tuple(basis_of.shape) == (nrow,)):
         raise ValueError("delay_fit: basis_of must be a contiguous int32 tensor (nrow,)")
-    shapes = ((nf, nrow, nt), (nf, nrow, nt), (nrow, nt))
-    dtypes = (torch.complex128, torch.float64, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != 3 or not all(hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous()
-                                    for o, s, d in zip(out, shapes, dtypes)):
-            raise ValueError("delay_fit: out must hold contiguous tensors x_out (nf, nrow, nt) complex128, w_out "
-                             "(nf, nrow, nt) float64 and info (nrow, nt) int32")
-    if not all(t is None or (t.is_cuda and t.device == x.device) for t in (x, w, table, basis_of) + out):
-        raise ValueError("delay_fit: x, w, the basis table, basis_of and out must be tensors on one GPU")
+    out = _out_tuple("delay_fit", out, ((nf, nrow, nt), (nf, nrow, nt), (nrow, nt)), (torch.complex128, torch.float64, torch.int32),
+                     x.device, expected="out must hold contiguous tensors x_out (nf, nrow, nt) complex128, w_out "
+                     "(nf, nrow, nt) float64 and info (nrow, nt) int32")
+    _same_gpu("delay_fit", (x, w, table, basis_of) + out, "x, w, the basis table, basis_of and out")
     rk = (c_int * max(len(ranks), 1))(*ranks)
     rc = self.lib.dm_delay_fit(self.h, nf, nrow, nt, DELAY_MODES[mode], float(ridge), 0 if min_valid is None else int(min_valid),
                                len(ranks), rk, self.ptr(table), self.ptr(basis_of), self.ptr(x), self.ptr(w),
@@ -1372,47 +1385,22 @@ def _ringmap(self, vis, group_off, members, v, scale, sinza, w=None, taper=None,
     2 (real and imaginary part).  Returns (map, norm, norm2): map (nf, ngroup, parts, nel, nt) and norm = D,
     norm2 = D2 (nf, ngroup, nt), float64.  `out`, `norm` and `norm2` take tensors to write into; norm=False or
     norm2=False leaves that output out (None is returned in its place)."""
-    torch = self.torch
-    if not (_is_c128(vis) and vis.dim() == 3):
-        raise ValueError("ringmap: contiguous complex128 tensor vis (nf, nrow, nt) expected")
-    nf, nrow, nt = (int(s) for s in vis.shape)
-    if w is not None:
-        _weights_arg("ringmap", w, vis.shape)
+    who = "ringmap"
+    nf, nrow, nt = _cube_arg(who, vis, w, "vis")
+    dev = vis.device
     if parts not in (1, 2):
         raise ValueError("ringmap: parts is 1 or 2")
-    off, offp = _iarr(group_off)
-    mem, memp = _iarr(members)
-    if off.ndim != 1 or off.shape[0] < 1 or mem.ndim != 1 or off[0] != 0 or np.any(np.diff(off) < 0) or mem.shape[0] != int(off[-1]):
-        raise ValueError("ringmap: group_off (ngroup + 1), from 0 and not decreasing, and members (group_off[-1]) expected")
-    if mem.size and (mem.min() < 0 or mem.max() >= nrow):
-        raise ValueError("ringmap: a member is no row of vis")
+    off, offp, mem, memp = _group_table(who, group_off, members, nrow)
     ngroup, nmem = off.shape[0] - 1, mem.shape[0]
-
-    def table(t, n, name):
-        if not hasattr(t, "data_ptr"):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))).to(vis.device)
-        if not (t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and n in (None, int(t.shape[0]))):
-            raise ValueError("ringmap: %s must be a contiguous float64 tensor (%s,)" % (name, "nel" if n is None else n))
-        return t
-
-    v = table(v, nmem, "v")
-    taper = None if taper is None else table(taper, nmem, "taper")
-    scale = table(scale, nf, "scale")
-    sinza = table(sinza, None, "sinza")
+    v = _f64_table(who, v, nmem, "v", dev)
+    taper = None if taper is None else _f64_table(who, taper, nmem, "taper", dev)
+    scale = _f64_table(who, scale, nf, "scale", dev)
+    sinza = _f64_table(who, sinza, None, "sinza", dev)
     nel = int(sinza.shape[0])
-
-    def output(t, shape, name):
-        if t is None:
-            return torch.empty(shape, dtype=torch.float64, device=vis.device)
-        if not (hasattr(t, "data_ptr") and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError("ringmap: %s must be a contiguous float64 tensor %s" % (name, shape))
-        return t
-
-    out = output(out, (nf, ngroup, parts, nel, nt), "out")
-    norm = None if norm is False else output(norm, (nf, ngroup, nt), "norm")
-    norm2 = None if norm2 is False else output(norm2, (nf, ngroup, nt), "norm2")
-    if not all(t is None or (t.is_cuda and t.device == vis.device) for t in (vis, w, v, taper, scale, sinza, out, norm, norm2)):
-        raise ValueError("ringmap: vis, w, v, taper, scale, sinza and the outputs must be tensors on one GPU")
+    out = _f64_out(who, out, (nf, ngroup, parts, nel, nt), "out", dev)
+    norm = None if norm is False else _f64_out(who, norm, (nf, ngroup, nt), "norm", dev)
+    norm2 = None if norm2 is False else _f64_out(who, norm2, (nf, ngroup, nt), "norm2", dev)
+    _same_gpu(who, (vis, w, v, taper, scale, sinza, out, norm, norm2), "vis, w, v, taper, scale, sinza and the outputs")
     rc = self.lib.dm_ringmap(self.h, nf, nrow, nt, ngroup, offp, memp, self.ptr(v), self.ptr(taper), self.ptr(scale), nel,
                              self.ptr(sinza), int(parts), self.ptr(vis), self.ptr(w), self.ptr(out), self.ptr(norm),
                              self.ptr(norm2))
@@ -1460,11 +1448,7 @@ def _delay_spectrum(self, x, w=None, taper=None, step=None, nd=None, a0=None, we
     torch = self.torch
     if weighting not in DELAYSPEC_WEIGHTINGS:
         raise ValueError('delay_spectrum: weighting is "mask" or "weight"')
-    if not (_is_c128(x) and x.dim() == 3):
-        raise ValueError("delay_spectrum: contiguous complex128 tensor x (nf, nrow, nt) expected")
-    nf, nrow, nt = (int(s) for s in x.shape)
-    if w is not None:
-        _weights_arg("delay_spectrum", w, x.shape)
+    nf, nrow, nt = _cube_arg("delay_spectrum", x, w)
     if step is None or nd is None:
         raise ValueError("delay_spectrum: step and nd are required")
     nd = int(nd)
@@ -1474,29 +1458,12 @@ def _delay_spectrum(self, x, w=None, taper=None, step=None, nd=None, a0=None, we
         raise ValueError("delay_spectrum: nd >= 0, a0 in [0, nd) and min_valid >= 1 expected")
     off = delayspec_bins(nt, bins)
     nbin = int(off.shape[0]) - 1
-
-    def table(t, name):
-        if not hasattr(t, "data_ptr"):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))).to(x.device)
-        if not (t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (nf,)):
-            raise ValueError("delay_spectrum: %s must be a contiguous float64 tensor (nf,)" % name)
-        return t
-
-    step = table(step, "step")
-    taper = None if taper is None else table(taper, "taper")
-    shapes = ((nrow, nbin, nd), (nrow, nbin, nd), (nrow, nbin), (nrow, nbin), (nrow, nbin))
-    dtypes = (torch.float64,) * 4 + (torch.int32,)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=x.device) for s, d in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != 5 or out[0] is None or not all(
-                o is None or (hasattr(o, "data_ptr") and tuple(o.shape) == s and o.dtype == d and o.is_contiguous())
-                for o, s, d in zip(out, shapes, dtypes)):
-            raise ValueError("delay_spectrum: out must hold contiguous tensors q, h (nrow, nbin, nd), s1, s2 (nrow, nbin) "
-                             "float64 and count (nrow, nbin) int32 (None for h, s1, s2 or count: not written)")
-    if not all(t is None or (t.is_cuda and t.device == x.device) for t in (x, w, taper, step) + out):
-        raise ValueError("delay_spectrum: x, w, taper, step and the outputs must be tensors on one GPU")
+    step = _f64_table("delay_spectrum", step, nf, "step", x.device)
+    taper = None if taper is None else _f64_table("delay_spectrum", taper, nf, "taper", x.device)
+    out = _out_tuple("delay_spectrum", out, ((nrow, nbin, nd),) * 2 + ((nrow, nbin),) * 3, (torch.float64,) * 4 + (torch.int32,),
+                     x.device, optional=(1, 2, 3, 4), expected="out must hold contiguous tensors q, h (nrow, nbin, nd), s1, s2 "
+                     "(nrow, nbin) float64 and count (nrow, nbin) int32 (None for h, s1, s2 or count: not written)")
+    _same_gpu("delay_spectrum", (x, w, taper, step) + out, "x, w, taper, step and the outputs")
     rc = self.lib.dm_delay_spectrum(self.h, nf, nrow, nt, nd, a0, DELAYSPEC_WEIGHTINGS[weighting], min_valid,
                                     self.ptr(taper), self.ptr(step), nbin, off.ctypes.data_as(ctypes.POINTER(c_int)),
                                     self.ptr(x), self.ptr(w), *(self.ptr(o) for o in out))
@@ -1519,22 +1486,14 @@ def _formed_beam(self, vis, group_off, members, iu, iv, uvals, vvals, scale, env
     arrays.  parts 1 (the real part) or 2.  Returns (beam, norm, norm2): beam (nf, ngroup, parts, nsrc), norm = D and
     norm2 = D2 (nf, ngroup, nsrc), float64.  `out`, `norm` and `norm2` take tensors to write into; norm=False or
     norm2=False leaves that output out (None is returned in its place)."""
-    torch = self.torch
-    if not (_is_c128(vis) and vis.dim() == 3):
-        raise ValueError("formed_beam: contiguous complex128 tensor vis (nf, nrow, nt) expected")
-    nf, nrow, nt = (int(s) for s in vis.shape)
-    if w is not None:
-        _weights_arg("formed_beam", w, vis.shape)
+    who = "formed_beam"
+    nf, nrow, nt = _cube_arg(who, vis, w, "vis")
+    dev = vis.device
     if parts not in (1, 2):
         raise ValueError("formed_beam: parts is 1 or 2")
-    off, offp = _iarr(group_off)
-    mem, memp = _iarr(members)
+    off, offp, mem, memp = _group_table(who, group_off, members, nrow)
     iu, iup = _iarr(iu)
     iv, ivp = _iarr(iv)
-    if off.ndim != 1 or off.shape[0] < 1 or mem.ndim != 1 or off[0] != 0 or np.any(np.diff(off) < 0) or mem.shape[0] != int(off[-1]):
-        raise ValueError("formed_beam: group_off (ngroup + 1), from 0 and not decreasing, and members (group_off[-1]) expected")
-    if mem.size and (mem.min() < 0 or mem.max() >= nrow):
-        raise ValueError("formed_beam: a member is no row of vis")
     if iu.shape != mem.shape or iv.shape != mem.shape:
         raise ValueError("formed_beam: iu and iv hold one index per member")
     ngroup, nmem = off.shape[0] - 1, mem.shape[0]
@@ -1548,35 +1507,18 @@ def _formed_beam(self, vis, group_off, members, iu, iv, uvals, vvals, scale, env
     env = np.ascontiguousarray(env, dtype=np.float64)
     if env.shape != (nf,) or not np.all(np.isfinite(env) & (env >= 0)):
         raise ValueError("formed_beam: env holds one finite value >= 0 per frequency")
-
-    def table(t, n, name):
-        if not hasattr(t, "data_ptr"):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))).to(vis.device)
-        if not (t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and n in (None, int(t.shape[0]))):
-            raise ValueError("formed_beam: %s must be a contiguous float64 tensor (%s,)" % (name, "n" if n is None else n))
-        return t
-
-    uvals, vvals = table(uvals, None, "uvals"), table(vvals, None, "vvals")
+    uvals, vvals = _f64_table(who, uvals, None, "uvals", dev), _f64_table(who, vvals, None, "vvals", dev)
     nu, nv = int(uvals.shape[0]), int(vvals.shape[0])
     if nmem and (iu.min() < 0 or iu.max() >= nu or iv.min() < 0 or iv.max() >= nv):
         raise ValueError("formed_beam: iu or iv points outside uvals or vvals")
-    taper = None if taper is None else table(taper, nmem, "taper")
-    scale = table(scale, nf, "scale")
-    turn, sinth, yc0, yc1 = (table(t, nsrc, n) for t, n in ((turn, "turn"), (sinth, "sinth"), (yc0, "yc0"), (yc1, "yc1")))
-
-    def output(t, shape, name):
-        if t is None:
-            return torch.empty(shape, dtype=torch.float64, device=vis.device)
-        if not (hasattr(t, "data_ptr") and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError("formed_beam: %s must be a contiguous float64 tensor %s" % (name, shape))
-        return t
-
-    out = output(out, (nf, ngroup, parts, nsrc), "out")
-    norm = None if norm is False else output(norm, (nf, ngroup, nsrc), "norm")
-    norm2 = None if norm2 is False else output(norm2, (nf, ngroup, nsrc), "norm2")
-    if not all(t is None or (t.is_cuda and t.device == vis.device)
-               for t in (vis, w, uvals, vvals, taper, scale, turn, sinth, yc0, yc1, out, norm, norm2)):
-        raise ValueError("formed_beam: vis, w, the tables and the outputs must be tensors on one GPU")
+    taper = None if taper is None else _f64_table(who, taper, nmem, "taper", dev)
+    scale = _f64_table(who, scale, nf, "scale", dev)
+    turn, sinth, yc0, yc1 = (_f64_table(who, t, nsrc, n, dev)
+                             for t, n in ((turn, "turn"), (sinth, "sinth"), (yc0, "yc0"), (yc1, "yc1")))
+    out = _f64_out(who, out, (nf, ngroup, parts, nsrc), "out", dev)
+    norm = None if norm is False else _f64_out(who, norm, (nf, ngroup, nsrc), "norm", dev)
+    norm2 = None if norm2 is False else _f64_out(who, norm2, (nf, ngroup, nsrc), "norm2", dev)
+    _same_gpu(who, (vis, w, uvals, vvals, taper, scale, turn, sinth, yc0, yc1, out, norm, norm2), "vis, w, the tables and the outputs")
     rc = self.lib.dm_formed_beam(self.h, nf, nrow, nt, ngroup, offp, memp, iup, ivp, nu, self.ptr(uvals), nv, self.ptr(vvals),
                                  self.ptr(taper), self.ptr(scale), env.ctypes.data_as(ctypes.POINTER(c_dbl)), nsrc, k0p, halfp,
                                  self.ptr(turn), self.ptr(sinth), self.ptr(yc0), self.ptr(yc1), int(parts), self.ptr(vis),

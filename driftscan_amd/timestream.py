@@ -1969,6 +1969,94 @@ def _save_all(tss):
     parallel.barrier()
 
 
+# ---- the I/O stages of the routes that take a Timestream directory through one device kernel:
+# ---- sidereal_stack, rfi_flag, delay_filter, ringmap, formed_beam and delay_spectrum ----------------------------------
+def _route_open(who, m, indir, stacked_only=True, rows=True):
+    """The source of a route: (the Timestream of `indir`, nrow, nt), the shape of the `timestream` of its file 0.  With
+    `stacked_only` an unstacked directory is refused, with `rows` a row count other than the telescope's baselines."""
+    src = Timestream(indir, m)
+    if stacked_only:
+        src._refuse_unstacked()
+    with storage.File(src._ffile(0), "r") as f:
+        nrow, nt = (int(v) for v in f["timestream"].shape)
+    npairs = int(m.beamtransfer.telescope.npairs)
+    if rows and nrow != npairs:
+        raise ValueError("%s: %s holds %d rows, the telescope has %d baselines" % (who, src.directory, nrow, npairs))
+    return src, nrow, nt
+
+
+def _route_read(who, src, fs, nrow, nt, whole=False):
+    """The frequencies `fs` of `src` as one chunk, every file opened once: `x`, per file the `timestream` (nrow, nt) as
+    complex128, and `w`, per file the float64 `weight` — ones for a file without one, and None in place of the list when
+    no file of the chunk has one.  With `whole` also `files`, per file (every dataset, the attributes), for
+    `_route_rewrite`.  A file of another shape raises the ValueError that names it."""
+    x, w, files = [], [], []
+    for fi in fs:
+        with storage.File(src._ffile(fi), "r") as f:
+            data = {k: np.asarray(f[k][:]) for k in (f.keys() if whole else ("timestream", "weight")) if k in f}
+            files.append((data, dict(f.attrs) if whole else None))
+        if data["timestream"].shape != (nrow, nt):
+            raise ValueError("%s: %s holds %s, not (%d, %d)" % (who, src._ffile(fi), data["timestream"].shape, nrow, nt))
+        x.append(np.asarray(data["timestream"], dtype=np.complex128))
+        w.append(np.asarray(data["weight"], dtype=np.float64) if "weight" in data else None)
+    if all(v is None for v in w):
+        w = None
+    else:
+        ones = np.ones((nrow, nt), dtype=np.float64)
+        w = [ones if v is None else v for v in w]
+    return SimpleNamespace(fs=list(fs), x=x, w=w, files=files if whole else None)
+
+
+def _route_upload(ctx, chunk, r0=None, r1=None):
+    """(x_d, w_d) of a chunk on the device, (len(fs), rows, nt) complex128 and float64 or None: all rows, or r0:r1."""
+    x_d = ctx.to_device(np.stack([a[r0:r1] for a in chunk.x]))
+    return x_d, None if chunk.w is None else ctx.to_device(np.stack([a[r0:r1] for a in chunk.w]))
+
+
+def _row_chunks(who, nrow, chunk_gb, bytes_per_row):
+    """The rows 0 .. nrow as ranges (r0, r1) that fit `chunk_gb` at `bytes_per_row` over all frequencies."""
+    rows_per = int(chunk_gb * 2.0**30 // bytes_per_row)
+    if rows_per < 1:
+        raise ValueError("%s: one row over all frequencies needs chunk_gb >= %.4g (given: %g)"
+                         % (who, bytes_per_row / 2.0**30 * 1.001, chunk_gb))
+    return [(r0, min(nrow, r0 + rows_per)) for r0 in range(0, nrow, rows_per)]
+
+
+def _write_hdf5(path, datasets, attrs):
+    """One file from a dict of arrays (written contiguous) and a dict of attributes: a root file, or one of the two
+    below."""
+    with storage.File(path, "w") as f:
+        for name, value in datasets.items():
+            f.create_dataset(name, data=np.ascontiguousarray(value))
+        for name, value in attrs.items():
+            f.attrs[name] = value
+
+
+def _product_file(src, fi, prefix, name):
+    return os.path.join(src._fdir(fi), "%s_%s.hdf5" % (prefix, name))
+
+
+def _route_write_products(src, fs, prefix, name, data):
+    """`<prefix>_<name>.hdf5` beside the timestream file of every frequency of `fs`: entry k of every array of `data`
+    (their first axis is the chunk), and the attribute `frequency`."""
+    for k, fi in enumerate(fs):
+        os.makedirs(src._fdir(fi), exist_ok=True)
+        _write_hdf5(_product_file(src, fi, prefix, name), {key: value[k] for key, value in data.items()},
+                    dict(frequency=float(src.telescope.frequencies[fi])))
+
+
+def _route_rewrite(dst, chunk, updates):
+    """The files of a chunk read `whole`, written to `dst` with entry k of every array of `updates` over the datasets of
+    file k; every other dataset and all attributes are kept.  The weight a file arrived with is kept as `weight_input`,
+    unless it holds one already: a second pass keeps the first input."""
+    for k, (fi, (data, attrs)) in enumerate(zip(chunk.fs, chunk.files)):
+        if "weight" in data and "weight_input" not in data:
+            data["weight_input"] = data["weight"]
+        data.update({name: value[k] for name, value in updates.items()})
+        os.makedirs(dst._fdir(fi), exist_ok=True)
+        _write_hdf5(dst._ffile(fi), data, attrs)
+
+
 def _sim_filled(c, unstacked, weights=None, noise=True):
     """The tensor (nreal, nf, npairs or nmem, ntime) of the run `c`, filled by the generator of its layout; `weights` as
     given to the simulators."""
@@ -2666,7 +2754,8 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
     if not daydirs:
         raise ValueError("sidereal_stack: no days")
     ntime = _sim_ntime(tel, 0) if ntime is None else int(ntime)
-    days = [Timestream(d, m) for d in daydirs]
+    opened = [_route_open("sidereal_stack", m, d, stacked_only=False, rows=False) for d in daydirs]
+    days, nrow = [o[0] for o in opened], opened[0][1]
     geo = [_day_phi(d) for d in days]
     unst = [d.is_unstacked() for d in days]
     if any(u != unst[0] for u in unst):
@@ -2682,8 +2771,6 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
                 table = t
             elif not (np.array_equal(t[0], table[0]) and np.array_equal(t[1], table[1])):
                 raise ValueError("sidereal_stack: %s was written for another class table" % d.directory)
-    with storage.File(days[0]._ffile(0), "r") as f:
-        nrow = int(f["timestream"].shape[0])
     freqs = _sim_freqs(tel, None)
     nt_max = max(g[2] for g in geo)
     extra_steps = route.freq is not None or route.dilate is not None
@@ -2699,20 +2786,9 @@ def sidereal_stack(m, daydirs, outdir, ntime=None, a=3, min_share=1.0, chunk_gb=
         acc = None
         for d, (phi0, dphi, nt_in) in zip(days, geo):
             with _StepTimer(log, "read"):
-                xs, ws, weighted = [], [], False
-                for fi in fs:
-                    with storage.File(d._ffile(fi), "r") as f:
-                        xd = np.asarray(f["timestream"][:], dtype=np.complex128)
-                        if xd.shape != (nrow, nt_in):
-                            raise ValueError("sidereal_stack: %s holds %s, not (%d, %d)" % (d._ffile(fi), xd.shape, nrow, nt_in))
-                        xs.append(xd)
-                        ws.append(np.asarray(f["weight"][:], dtype=np.float64) if "weight" in f else None)
-                weighted = any(wv is not None for wv in ws)
-                if weighted:
-                    ws = [np.ones((nrow, nt_in), dtype=np.float64) if wv is None else wv for wv in ws]
+                chunk = _route_read("sidereal_stack", d, fs, nrow, nt_in)
             with _StepTimer(log, "regrid"):
-                x_d = ctx.to_device(np.stack(xs))
-                w_d = ctx.to_device(np.stack(ws)) if weighted else None
+                x_d, w_d = _route_upload(ctx, chunk)
                 if route.any:
                     w_d = _rfi_steps(ctx, x_d, w_d, route)[0]
                 acc = ctx.sidereal_regrid(x_d, phi0, dphi, ntime, w=w_d, a=a, min_share=min_share, acc=acc)
@@ -3124,47 +3200,25 @@ def rfi_flag(m, indir, outdir=None, chunk_gb=4.0, freq=None, dilate=None, **para
     p = rfi_params(params)
     route = _rfi_route(p, freq, dilate)
     tel = m.beamtransfer.telescope
-    src = Timestream(indir, m)
+    src, nrow, nt = _route_open("rfi_flag", m, indir, stacked_only=False, rows=False)
     inplace = outdir is None or os.path.abspath(outdir) == os.path.abspath(src.directory)
     dst = src if inplace else Timestream(outdir, m)
     freqs = _sim_freqs(tel, None)
-    with storage.File(src._ffile(0), "r") as f:
-        nrow, nt = (int(v) for v in f["timestream"].shape)
     log = sim_log
     extra_steps = route.freq is not None or route.dilate is not None
     chunks = _rfi_chunks("rfi_flag", freqs, chunk_gb, nrow * nt * (48.0 if extra_steps else 32.0), route)
     ctx = get_context()
     for fs in chunks:
         with _StepTimer(log, "read"):
-            files = []
-            for fi in fs:
-                with storage.File(src._ffile(fi), "r") as f:
-                    files.append(({k: np.asarray(f[k][:]) for k in f.keys()}, dict(f.attrs)))
-                if files[-1][0]["timestream"].shape != (nrow, nt):
-                    raise ValueError("rfi_flag: %s holds %s, not (%d, %d)" % (src._ffile(fi), files[-1][0]["timestream"].shape, nrow, nt))
-            weighted = any("weight" in d for d, _ in files)
+            chunk = _route_read("rfi_flag", src, fs, nrow, nt, whole=True)
         with _StepTimer(log, "rfi"):
-            x_d = ctx.to_device(np.stack([np.asarray(d["timestream"], dtype=np.complex128) for d, _ in files]))
-            w_d = None
-            if weighted:
-                w_d = ctx.to_device(np.stack([np.asarray(d["weight"], dtype=np.float64) if "weight" in d
-                                              else np.ones((nrow, nt), dtype=np.float64) for d, _ in files]))
+            x_d, w_d = _route_upload(ctx, chunk)
             w_last, tout, nfreq, ndil = _rfi_steps(ctx, x_d, w_d, route)
-            out = [ctx.to_host(w_last)] + [ctx.to_host(t) for t in tout[1:]]
-            more = {name: ctx.to_host(t) for name, t in (("rfi_freq_nflag", nfreq), ("rfi_dilate_nflag", ndil)) if t is not None}
+            names = ("weight", "rfi_noise", "rfi_nflag", "rfi_occupancy", "rfi_freq_nflag", "rfi_dilate_nflag")
+            new = {name: ctx.to_host(t) for name, t in zip(names, (w_last,) + tuple(tout[1:]) + (nfreq, ndil)) if t is not None}
             del x_d, w_d, w_last, tout, nfreq, ndil
         with _StepTimer(log, "write"):
-            for k, (fi, (data, attrs)) in enumerate(zip(fs, files)):
-                if "weight" in data and "weight_input" not in data:   # a second pass keeps the first input
-                    data["weight_input"] = data["weight"]
-                data.update(weight=out[0][k], rfi_noise=out[1][k], rfi_nflag=out[2][k], rfi_occupancy=out[3][k])
-                data.update({name: v[k] for name, v in more.items()})
-                os.makedirs(dst._fdir(fi), exist_ok=True)
-                with storage.File(dst._ffile(fi), "w") as f:
-                    for name, value in data.items():
-                        f.create_dataset(name, data=np.ascontiguousarray(value))
-                    for name, value in attrs.items():
-                        f.attrs[name] = value
+            _route_rewrite(dst, chunk, new)
     _save_all([] if inplace else [dst])
     return dst
 
@@ -3397,31 +3451,16 @@ def delay_filter(m, indir, outdir=None, mode="inpaint", chunk_gb=4.0, ridge=0.0,
     p = delay_params(dict(classes, mode=mode, ridge=ridge, min_valid=min_valid))
     _delay_one_rank("delay_filter")
     tel = m.beamtransfer.telescope
-    src = Timestream(indir, m)
-    src._refuse_unstacked()
+    src, nrow, nt = _route_open("delay_filter", m, indir)
     inplace = outdir is None or os.path.abspath(outdir) == os.path.abspath(src.directory)
     dst = src if inplace else Timestream(outdir, m)
-    freqs = list(range(tel.nfreq))
+    nf = int(tel.nfreq)
     table, ranks, basis_of, tau = delay_classes(tel, horizon=p["horizon"], buffer=p["buffer"], nclass=p["nclass"],
                                                 eigencut=p["eigencut"])
     log = sim_log
     with _StepTimer(log, "read"):
-        files = []
-        for fi in freqs:
-            with storage.File(src._ffile(fi), "r") as f:
-                files.append(({k: np.asarray(f[k][:]) for k in f.keys()}, dict(f.attrs)))
-        nrow, nt = (int(v) for v in files[0][0]["timestream"].shape)
-        for fi, (d, _) in zip(freqs, files):
-            if d["timestream"].shape != (nrow, nt):
-                raise ValueError("delay_filter: %s holds %s, not (%d, %d)" % (src._ffile(fi), d["timestream"].shape, nrow, nt))
-        if nrow != basis_of.shape[0]:
-            raise ValueError("delay_filter: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, basis_of.shape[0]))
-        weighted = any("weight" in d for d, _ in files)
-    nf = len(freqs)
-    rows_per = int(chunk_gb * 2.0**30 // (48.0 * nf * nt))
-    if rows_per < 1:
-        raise ValueError("delay_filter: one row over all frequencies needs chunk_gb >= %.4g (given: %g)"
-                         % (48.0 * nf * nt / 2.0**30 * 1.001, chunk_gb))
+        chunk = _route_read("delay_filter", src, range(nf), nrow, nt, whole=True)
+    ranges = _row_chunks("delay_filter", nrow, chunk_gb, 48.0 * nf * nt)
     ctx = get_context()
     torch = ctx.torch
     x_out = np.empty((nf, nrow, nt), dtype=np.complex128)
@@ -3430,13 +3469,8 @@ def delay_filter(m, indir, outdir=None, mode="inpaint", chunk_gb=4.0, ridge=0.0,
     filled = np.zeros((nf, nrow), dtype=np.int32)
     with _StepTimer(log, "delay"):
         table_d = ctx.to_device(table)
-        for r0 in range(0, nrow, rows_per):
-            r1 = min(nrow, r0 + rows_per)
-            x_d = ctx.to_device(np.stack([np.asarray(d["timestream"][r0:r1], dtype=np.complex128) for d, _ in files]))
-            w_d = None
-            if weighted:
-                w_d = ctx.to_device(np.stack([np.asarray(d["weight"][r0:r1], dtype=np.float64) if "weight" in d
-                                              else np.ones((r1 - r0, nt), dtype=np.float64) for d, _ in files]))
+        for r0, r1 in ranges:
+            x_d, w_d = _route_upload(ctx, chunk, r0, r1)
             of_d = ctx.to_device(np.ascontiguousarray(basis_of[r0:r1]))
             xo, wo, io = ctx.delay_fit(x_d, w=w_d, basis=(table_d, ranks), basis_of=of_d, mode=p["mode"], ridge=p["ridge"],
                                        min_valid=p["min_valid"])
@@ -3445,24 +3479,10 @@ def delay_filter(m, indir, outdir=None, mode="inpaint", chunk_gb=4.0, ridge=0.0,
             x_out[:, r0:r1], w_out[:, r0:r1], info[r0:r1] = ctx.to_host(xo), ctx.to_host(wo), ctx.to_host(io)
             del x_d, w_d, of_d, xo, wo, io
     with _StepTimer(log, "write"):
-        for k, (fi, (data, attrs)) in enumerate(zip(freqs, files)):
-            if "weight" in data and "weight_input" not in data:   # a second pass keeps the first input
-                data["weight_input"] = data["weight"]
-            data.update(timestream=x_out[k], weight=w_out[k], delay_filled=filled[k])
-            os.makedirs(dst._fdir(fi), exist_ok=True)
-            with storage.File(dst._ffile(fi), "w") as f:
-                for name, value in data.items():
-                    f.create_dataset(name, data=np.ascontiguousarray(value))
-                for name, value in attrs.items():
-                    f.attrs[name] = value
+        _route_rewrite(dst, chunk, dict(timestream=x_out, weight=w_out, delay_filled=filled))
         os.makedirs(dst.directory, exist_ok=True)
-        with storage.File(os.path.join(dst.directory, "delay_fit.hdf5"), "w") as f:
-            f.create_dataset("info", data=info)
-            f.create_dataset("basis_of", data=basis_of)
-            f.create_dataset("tau", data=tau)
-            f.create_dataset("rank", data=ranks)
-            for name, value in p.items():
-                f.attrs[name] = -1 if value is None else value
+        _write_hdf5(os.path.join(dst.directory, "delay_fit.hdf5"), dict(info=info, basis_of=basis_of, tau=tau, rank=ranks),
+                    {name: -1 if value is None else value for name, value in p.items()})
     unsolved = int((info != 0).sum())
     if unsolved:
         logging.getLogger(__name__).warning("delay_filter: %d of %d series were not solved (info in delay_fit.hdf5)", unsolved, info.size)
@@ -3629,11 +3649,9 @@ def ringmap(m, indir, name="ringmap", nel=None, sinza=None, weighting="natural",
     `group_off`, `members`, `v`, `u`, `pol`, `taper`, with collapse_ew `pol_sum` and `group_pol` (the row of `map_sum`
     every group goes to), and the parameters as attributes.  The written bits do not depend on `chunk_gb`.  An unstacked
     directory raises ValueError.  Returns the path of the root file."""
-    if weighting not in RINGMAP_WEIGHTINGS or window not in RINGMAP_WINDOWS or parts not in (1, 2):
-        raise ValueError('ringmap: weighting is "natural" or "uniform", window None, "hann" or "blackman", parts 1 or 2')
+    ringmap_params(dict(weighting=weighting, window=window, parts=parts))
     tel = m.beamtransfer.telescope
-    src = Timestream(indir, m)
-    src._refuse_unstacked()
+    src, nrow, nt = _route_open("ringmap", m, indir)
     groups = ringmap_groups(tel, ew=ew, intracyl=intracyl)
     ngroup = groups["group_off"].shape[0] - 1
     if ngroup == 0:
@@ -3645,10 +3663,6 @@ def ringmap(m, indir, name="ringmap", nel=None, sinza=None, weighting="natural",
     nel = int(sinza.size)
     scale = np.ascontiguousarray(1.0 / np.asarray(tel.wavelengths, dtype=np.float64))
     freqs = _sim_freqs(tel, None)
-    with storage.File(src._ffile(0), "r") as f:
-        nrow, nt = (int(s) for s in f["timestream"].shape)
-    if nrow != int(tel.npairs):
-        raise ValueError("ringmap: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, int(tel.npairs)))
     upol, group_pol = np.unique(groups["pol"], axis=0, return_inverse=True)
     group_pol = np.asarray(group_pol).reshape(-1)
     per_f = 24.0 * nrow * nt + 8.0 * ngroup * nt * (parts * nel + 2) + (16.0 * len(upol) * nt * parts * nel if collapse_ew else 0.0)
@@ -3658,15 +3672,9 @@ def ringmap(m, indir, name="ringmap", nel=None, sinza=None, weighting="natural",
     tabs = {k: ctx.to_device(a) for k, a in (("v", groups["v"]), ("taper", taper), ("sinza", sinza))}
     for fs in _freq_chunks(freqs, chunk_gb, per_f):
         with _StepTimer(log, "read"):
-            x = np.stack([np.asarray(src.timestream_f(fi), dtype=np.complex128) for fi in fs])
-            ws = [src.weight_f(fi) for fi in fs]
-            if x.shape[1:] != (nrow, nt):
-                raise ValueError("ringmap: a file of %s holds %s, not (%d, %d)" % (src.directory, x.shape[1:], nrow, nt))
+            chunk = _route_read("ringmap", src, fs, nrow, nt)
         with _StepTimer(log, "ringmap"):
-            x_d = ctx.to_device(x)
-            w_d = None
-            if any(wf is not None for wf in ws):
-                w_d = ctx.to_device(np.stack([np.ones((nrow, nt)) if wf is None else wf for wf in ws]))
+            x_d, w_d = _route_upload(ctx, chunk)
             mp, nm, nm2 = ctx.ringmap(x_d, groups["group_off"], groups["members"], tabs["v"], ctx.to_device(scale[fs]),
                                       tabs["sinza"], w=w_d, taper=tabs["taper"], parts=parts)
             data = dict(map=ctx.to_host(mp), norm=ctx.to_host(nm), norm2=ctx.to_host(nm2))
@@ -3683,28 +3691,17 @@ def ringmap(m, indir, name="ringmap", nel=None, sinza=None, weighting="natural",
                 del msum, dsum
             del x_d, w_d, mp, nm, nm2
         with _StepTimer(log, "write"):
-            for k, fi in enumerate(fs):
-                os.makedirs(src._fdir(fi), exist_ok=True)
-                with storage.File(os.path.join(src._fdir(fi), "ringmap_%s.hdf5" % name), "w") as f:
-                    for key, value in data.items():
-                        f.create_dataset(key, data=np.ascontiguousarray(value[k]))
-                    f.attrs["frequency"] = float(tel.frequencies[fi])
+            _route_write_products(src, fs, "ringmap", name, data)
     root = os.path.join(src.directory, "ringmap_%s.hdf5" % name)
     if parallel.rank0():
-        with storage.File(root, "w") as f:
-            f.create_dataset("sinza", data=sinza)
-            f.create_dataset("phi", data=_dir_phi(src, nt))
-            for key in ("group_off", "members", "v", "u", "pol"):
-                f.create_dataset(key, data=groups[key])
-            f.create_dataset("taper", data=taper)
-            if collapse_ew:
-                f.create_dataset("pol_sum", data=upol.astype(np.int32))
-                f.create_dataset("group_pol", data=group_pol.astype(np.int32))
-            if ew is not None:
-                f.create_dataset("ew", data=np.atleast_1d(np.asarray(ew, dtype=np.float64)))
-            for key, value in dict(nel=nel, weighting=weighting, window=window or "none", intracyl=int(bool(intracyl)),
-                                   parts=int(parts), collapse_ew=int(bool(collapse_ew)), ntime=nt).items():
-                f.attrs[key] = value
+        tables = dict({key: groups[key] for key in ("group_off", "members", "v", "u", "pol")}, sinza=sinza, phi=_dir_phi(src, nt),
+                      taper=taper)
+        if collapse_ew:
+            tables.update(pol_sum=upol.astype(np.int32), group_pol=group_pol.astype(np.int32))
+        if ew is not None:
+            tables["ew"] = np.atleast_1d(np.asarray(ew, dtype=np.float64))
+        _write_hdf5(root, tables, dict(nel=nel, weighting=weighting, window=window or "none", intracyl=int(bool(intracyl)),
+                                       parts=int(parts), collapse_ew=int(bool(collapse_ew)), ntime=nt))
     parallel.barrier()
     return root
 
@@ -3925,16 +3922,13 @@ def formed_beam(m, indir, cat, name="formedbeam", ha_max=0.05, envelope_fwhm=Non
     raises ValueError.  Returns the path of the root file."""
     from . import skysim
 
-    if weighting not in RINGMAP_WEIGHTINGS or window not in RINGMAP_WINDOWS or parts not in (1, 2):
-        raise ValueError('formed_beam: weighting is "natural" or "uniform", window None, "hann" or "blackman", parts 1 or 2')
-    conf = _conf_filled(stack, dict.fromkeys(FORMEDBEAM_STACK_KEYS), "formed_beam: unknown stack key(s) %s (known: %s)",
-                        show=", ".join)
+    formedbeam_params(dict(ha_max=ha_max, envelope_fwhm=envelope_fwhm, weighting=weighting, window=window, parts=parts, stack=stack))
+    conf = dict(dict.fromkeys(FORMEDBEAM_STACK_KEYS), **(stack or {}))
     theta, phi, red = skysim.read_positions(cat)
     if stack is not None and red is None:
         raise ValueError("formed_beam: a stack needs the redshifts of the catalogue")
     tel = m.beamtransfer.telescope
-    src = Timestream(indir, m)
-    src._refuse_unstacked()
+    src, nrow, nt = _route_open("formed_beam", m, indir)
     groups = formedbeam_groups(tel, ew=ew, intracyl=intracyl)
     ngroup = groups["group_off"].shape[0] - 1
     if ngroup == 0:
@@ -3943,10 +3937,6 @@ def formed_beam(m, indir, cat, name="formedbeam", ha_max=0.05, envelope_fwhm=Non
     scale = np.ascontiguousarray(1.0 / np.asarray(tel.wavelengths, dtype=np.float64))
     env = formedbeam_env(tel.wavelengths, envelope_fwhm)
     freqs = _sim_freqs(tel, None)
-    with storage.File(src._ffile(0), "r") as f:
-        nrow, nt = (int(s) for s in f["timestream"].shape)
-    if nrow != int(tel.npairs):
-        raise ValueError("formed_beam: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, int(tel.npairs)))
     win = formedbeam_windows(tel, theta, phi, nt, ha_max, zmin=zmin, scale_dec=scale_dec)
     tabs = formedbeam_tables(tel.zenith[0], theta)
     nsrc = theta.size
@@ -3958,16 +3948,10 @@ def formed_beam(m, indir, cat, name="formedbeam", ha_max=0.05, envelope_fwhm=Non
                                             ("yc1", tabs["yc1"]))} if nsrc else {}
     for fs in _freq_chunks(freqs, chunk_gb, per_f):
         with _StepTimer(log, "read"):
-            x = np.stack([np.asarray(src.timestream_f(fi), dtype=np.complex128) for fi in fs])
-            ws = [src.weight_f(fi) for fi in fs]
-            if x.shape[1:] != (nrow, nt):
-                raise ValueError("formed_beam: a file of %s holds %s, not (%d, %d)" % (src.directory, x.shape[1:], nrow, nt))
+            chunk = _route_read("formed_beam", src, fs, nrow, nt)
         with _StepTimer(log, "formed_beam"):
             if nsrc:
-                x_d = ctx.to_device(x)
-                w_d = None
-                if any(wf is not None for wf in ws):
-                    w_d = ctx.to_device(np.stack([np.ones((nrow, nt)) if wf is None else wf for wf in ws]))
+                x_d, w_d = _route_upload(ctx, chunk)
                 bm, nm, nm2 = ctx.formed_beam(x_d, groups["group_off"], groups["members"], groups["iu"], groups["iv"], dev["uvals"],
                                               dev["vvals"], ctx.to_device(scale[fs]), env[fs], win["k0"], win["half"], dev["turn"],
                                               dev["sinth"], dev["yc0"], dev["yc1"], w=w_d, taper=dev["taper"], parts=parts)
@@ -3977,12 +3961,7 @@ def formed_beam(m, indir, cat, name="formedbeam", ha_max=0.05, envelope_fwhm=Non
                 data = dict(beam=np.zeros((len(fs), ngroup, parts, 0)), norm=np.zeros((len(fs), ngroup, 0)),
                             norm2=np.zeros((len(fs), ngroup, 0)))
         with _StepTimer(log, "write"):
-            for k, fi in enumerate(fs):
-                os.makedirs(src._fdir(fi), exist_ok=True)
-                with storage.File(os.path.join(src._fdir(fi), "formedbeam_%s.hdf5" % name), "w") as f:
-                    for key, value in data.items():
-                        f.create_dataset(key, data=np.ascontiguousarray(value[k]))
-                    f.attrs["frequency"] = float(tel.frequencies[fi])
+            _route_write_products(src, fs, "formedbeam", name, data)
     parallel.barrier()
     root = os.path.join(src.directory, "formedbeam_%s.hdf5" % name)
     if parallel.rank0():
@@ -3990,34 +3969,26 @@ def formed_beam(m, indir, cat, name="formedbeam", ha_max=0.05, envelope_fwhm=Non
         beam = np.zeros((nsrc, ngroup, parts, nfreq))
         norm, norm2 = np.zeros((nsrc, ngroup, nfreq)), np.zeros((nsrc, ngroup, nfreq))
         for fi in range(nfreq):
-            with storage.File(os.path.join(src._fdir(fi), "formedbeam_%s.hdf5" % name), "r") as f:
+            with storage.File(_product_file(src, fi, "formedbeam", name), "r") as f:
                 beam[..., fi] = np.moveaxis(np.asarray(f["beam"][:]), 2, 0)
                 norm[..., fi], norm2[..., fi] = np.asarray(f["norm"][:]).T, np.asarray(f["norm2"][:]).T
         freq = np.asarray(tel.frequencies, dtype=np.float64)
-        with storage.File(root, "w") as f:
-            f.create_dataset("beam", data=np.ascontiguousarray(beam[:, :, 0]))
-            if parts == 2:
-                f.create_dataset("beam_imag", data=np.ascontiguousarray(beam[:, :, 1]))
-            for key, value in (("norm", norm), ("norm2", norm2), ("theta", theta), ("phi", phi), ("freq", freq),
-                               ("k0", win["k0"]), ("half", win["half"]), ("pol", groups["pol"])):
-                f.create_dataset(key, data=value)
-            if ew is not None:
-                f.create_dataset("ew", data=np.atleast_1d(np.asarray(ew, dtype=np.float64)))
-            for key, value in dict(ha_max=float(ha_max), envelope_fwhm=0.0 if envelope_fwhm is None else float(envelope_fwhm),
-                                   weighting=weighting, window=window or "none", intracyl=int(bool(intracyl)), parts=int(parts),
-                                   zmin=float(zmin), scale_dec=int(bool(scale_dec)), ntime=nt).items():
-                f.attrs[key] = value
-            if red is not None:
-                line = float(skysim.LINE_21CM_MHZ if conf["line_mhz"] is None else conf["line_mhz"]) / (1.0 + red)
-                sw = norm.mean(axis=(1, 2)) if conf["source_weight"] is None else conf["source_weight"]
-                st = skysim.stack_spectra(beam[:, :, 0], freq, line, 2 if conf["halfwidth"] is None else int(conf["halfwidth"]),
-                                          source_weight=sw, channel_weight=conf["channel_weight"])
-                f.create_dataset("redshift", data=red)
-                f.create_dataset("stack", data=st["stack"])
-                f.create_dataset("hits", data=st["hits"])
-                f.create_dataset("offsets", data=st["offsets"].astype(np.int64))
-                f.create_dataset("stack_weight", data=st["weight"])
-                f.create_dataset("channel", data=st["channel"])
+        tables = dict(beam=beam[:, :, 0], norm=norm, norm2=norm2, theta=theta, phi=phi, freq=freq, k0=win["k0"], half=win["half"],
+                      pol=groups["pol"])
+        if parts == 2:
+            tables["beam_imag"] = beam[:, :, 1]
+        if ew is not None:
+            tables["ew"] = np.atleast_1d(np.asarray(ew, dtype=np.float64))
+        if red is not None:
+            line = float(skysim.LINE_21CM_MHZ if conf["line_mhz"] is None else conf["line_mhz"]) / (1.0 + red)
+            sw = norm.mean(axis=(1, 2)) if conf["source_weight"] is None else conf["source_weight"]
+            st = skysim.stack_spectra(beam[:, :, 0], freq, line, 2 if conf["halfwidth"] is None else int(conf["halfwidth"]),
+                                      source_weight=sw, channel_weight=conf["channel_weight"])
+            tables.update(redshift=red, stack=st["stack"], hits=st["hits"], offsets=st["offsets"].astype(np.int64),
+                          stack_weight=st["weight"], channel=st["channel"])
+        _write_hdf5(root, tables, dict(ha_max=float(ha_max), envelope_fwhm=0.0 if envelope_fwhm is None else float(envelope_fwhm),
+                                       weighting=weighting, window=window or "none", intracyl=int(bool(intracyl)),
+                                       parts=int(parts), zmin=float(zmin), scale_dec=int(bool(scale_dec)), ntime=nt))
     parallel.barrier()
     return root
 
@@ -4253,47 +4224,28 @@ def delay_spectrum(m, indir, name="delayspectrum", nd=None, oversample=1.0, tau_
                                   norm=norm, ridge=ridge, min_valid=min_valid, tbin=tbin, blen_bins=blen_bins))
     _delay_one_rank("delay_spectrum")
     tel = m.beamtransfer.telescope
-    src = Timestream(indir, m)
-    src._refuse_unstacked()
-    freqs = list(range(tel.nfreq))
-    nf = len(freqs)
+    src, nrow, nt = _route_open("delay_spectrum", m, indir)
+    nf = int(tel.nfreq)
     tau, step, a0, dtau = delay_grid(tel, nd=p["nd"], oversample=p["oversample"], tau_max=p["tau_max"])
     nd = int(tau.size)
     tap = delay_taper(nf, p["taper"])
     need = 1 if p["min_valid"] is None else p["min_valid"]
     log = sim_log
     with _StepTimer(log, "read"):
-        xs, ws = [], []
-        for fi in freqs:
-            xs.append(np.asarray(src.timestream_f(fi), dtype=np.complex128))
-            ws.append(src.weight_f(fi))
-        nrow, nt = (int(v) for v in xs[0].shape)
-        if any(a.shape != (nrow, nt) for a in xs):
-            raise ValueError("delay_spectrum: the files of %s do not hold one shape" % src.directory)
-        if nrow != int(tel.npairs):
-            raise ValueError("delay_spectrum: %s holds %d rows, the telescope has %d baselines" % (src.directory, nrow, int(tel.npairs)))
-        weighted = any(wf is not None for wf in ws)
+        chunk = _route_read("delay_spectrum", src, range(nf), nrow, nt)
     from ._lib import delayspec_bins
 
     off = delayspec_bins(nt, p["tbin"])
     nbin = int(off.size) - 1
-    rows_per = int(chunk_gb * 2.0**30 // (24.0 * nf * nt + 40.0 * nbin * nd + 64.0))
-    if rows_per < 1:
-        raise ValueError("delay_spectrum: one row over all frequencies needs chunk_gb >= %.4g (given: %g)"
-                         % ((24.0 * nf * nt + 40.0 * nbin * nd + 64.0) / 2.0**30 * 1.001, chunk_gb))
+    ranges = _row_chunks("delay_spectrum", nrow, chunk_gb, 24.0 * nf * nt + 40.0 * nbin * nd + 64.0)
     ctx = get_context()
     out = dict(q=np.empty((nrow, nbin, nd)), window=np.empty((nrow, nbin, nd)), spectrum=np.empty((nrow, nbin, nd)),
                noise=np.empty((nrow, nbin, nd)), s1=np.empty((nrow, nbin)), s2=np.empty((nrow, nbin)),
                count=np.empty((nrow, nbin), dtype=np.int32), info=np.empty((nrow, nbin), dtype=np.int32))
     with _StepTimer(log, "delay_spectrum"):
         tap_d, step_d = ctx.to_device(tap), ctx.to_device(step)
-        for r0 in range(0, nrow, rows_per):
-            r1 = min(nrow, r0 + rows_per)
-            x_d = ctx.to_device(np.stack([a[r0:r1] for a in xs]))
-            w_d = None
-            if weighted:
-                w_d = ctx.to_device(np.stack([np.ones((r1 - r0, nt)) if wf is None else np.asarray(wf[r0:r1], dtype=np.float64)
-                                              for wf in ws]))
+        for r0, r1 in ranges:
+            x_d, w_d = _route_upload(ctx, chunk, r0, r1)
             q, h, s1, s2, cnt = ctx.delay_spectrum(x_d, w=w_d, taper=tap_d, step=step_d, nd=nd, a0=a0, weighting=p["weighting"],
                                                    min_valid=need, bins=off)
             sp, ns, info = delay_normalise(q, h, s1 if p["weighting"] == "weight" else s2, norm=p["norm"], ridge=p["ridge"])
@@ -4304,33 +4256,25 @@ def delay_spectrum(m, indir, name="delayspectrum", nd=None, oversample=1.0, tau_
     blen = np.sqrt((np.asarray(tel.baselines, dtype=np.float64).reshape(nrow, -1) ** 2).sum(axis=1))
     root = os.path.join(src.directory, "delayspectrum_%s.hdf5" % p["name"])
     with _StepTimer(log, "write"):
-        with storage.File(root, "w") as f:
-            f.create_dataset("tau", data=tau)
-            for key, value in out.items():
-                f.create_dataset(key, data=value)
-            for key, value in (("bin_off", off), ("step", step), ("taper", tap), ("blen", blen), ("horizon", blen / DELAY_C)):
-                f.create_dataset(key, data=value)
-            if p["blen_bins"] is not None:
-                edges = _delayspec_blen_edges(blen, p["blen_bins"])
-                which = np.clip(np.searchsorted(edges, blen, side="right") - 1, -1, edges.size - 2)
-                which[(blen < edges[0]) | (blen > edges[-1])] = -1
-                good = (out["info"] == 0) & (out["count"] > 0)
-                wgt = np.where(good, out["count"], 0).astype(np.float64)
-                wedge = np.full((edges.size - 1, nbin, nd), np.nan)
-                hits = np.zeros((edges.size - 1, nbin), dtype=np.int64)
-                for j in range(edges.size - 1):   # in row order: the bits do not depend on the chunk
-                    rows = np.nonzero(which == j)[0]
-                    num, den = np.zeros((nbin, nd)), np.zeros(nbin)
-                    for r in rows:
-                        num += wgt[r][:, None] * np.where(good[r][:, None], out["spectrum"][r], 0.0)
-                        den += wgt[r]
-                    wedge[j] = np.where(den[:, None] > 0, num / np.where(den > 0, den, 1.0)[:, None], np.nan)
-                    hits[j] = den.astype(np.int64)
-                f.create_dataset("blen_edges", data=edges)
-                f.create_dataset("wedge", data=wedge)
-                f.create_dataset("wedge_hits", data=hits)
-            for key, value in dict(nd=nd, a0=int(a0), dtau=float(dtau), oversample=p["oversample"], taper=p["taper"] or "none",
-                                   weighting=p["weighting"], norm=p["norm"], ridge=p["ridge"], min_valid=int(need),
-                                   tbin=-1 if p["tbin"] is None else p["tbin"], ntime=nt).items():
-                f.attrs[key] = value
+        tables = dict(out, tau=tau, bin_off=off, step=step, taper=tap, blen=blen, horizon=blen / DELAY_C)
+        if p["blen_bins"] is not None:
+            edges = _delayspec_blen_edges(blen, p["blen_bins"])
+            which = np.clip(np.searchsorted(edges, blen, side="right") - 1, -1, edges.size - 2)
+            which[(blen < edges[0]) | (blen > edges[-1])] = -1
+            good = (out["info"] == 0) & (out["count"] > 0)
+            wgt = np.where(good, out["count"], 0).astype(np.float64)
+            wedge = np.full((edges.size - 1, nbin, nd), np.nan)
+            hits = np.zeros((edges.size - 1, nbin), dtype=np.int64)
+            for j in range(edges.size - 1):   # in row order: the bits do not depend on the chunk
+                rows = np.nonzero(which == j)[0]
+                num, den = np.zeros((nbin, nd)), np.zeros(nbin)
+                for r in rows:
+                    num += wgt[r][:, None] * np.where(good[r][:, None], out["spectrum"][r], 0.0)
+                    den += wgt[r]
+                wedge[j] = np.where(den[:, None] > 0, num / np.where(den > 0, den, 1.0)[:, None], np.nan)
+                hits[j] = den.astype(np.int64)
+            tables.update(blen_edges=edges, wedge=wedge, wedge_hits=hits)
+        _write_hdf5(root, tables, dict(nd=nd, a0=int(a0), dtau=float(dtau), oversample=p["oversample"], taper=p["taper"] or "none",
+                                       weighting=p["weighting"], norm=p["norm"], ridge=p["ridge"], min_valid=int(need),
+                                       tbin=-1 if p["tbin"] is None else p["tbin"], ntime=nt))
     return root

@@ -212,6 +212,18 @@ def test_refusals_launch_nothing():
         ctx.rfi_flag(xd, w=wd[:, :2].contiguous())
     with pytest.raises(ValueError):
         ctx.rfi_flag(xd, out=(wd, wd, wd, wd))
+    # a tensor on the host is refused before anything is launched: the kernel would get its host address
+    torch = ctx.torch
+    xs, ws = ctx.to_device(np.ones((2, 3, 8), dtype=np.complex128)), ctx.to_device(np.ones((2, 3, 8)))
+    outs = [torch.empty(s, dtype=d, device=xs.device)
+            for s, d in (((2, 3, 8), torch.float64), ((2, 3, 1), torch.float64), ((2, 3), torch.int32), ((2, 8), torch.int32))]
+    with pytest.raises(ValueError, match="one GPU"):
+        ctx.rfi_flag(xs, w=ws.cpu())
+    for i in range(4):
+        with pytest.raises(ValueError, match="one GPU"):
+            ctx.rfi_flag(xs, w=ws, out=tuple(o.cpu() if j == i else o for j, o in enumerate(outs)))
+    with pytest.raises(ValueError, match="one GPU"):
+        ctx.rfi_flag(xs.cpu(), w=ws)
     # nothing to do is not refused
     empty = ctx.rfi_flag(xd[:, :0].contiguous())
     assert tuple(empty[0].shape) == (rc.NF, 0, nt)

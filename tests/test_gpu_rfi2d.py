@@ -220,6 +220,10 @@ def test_freq_refusals_launch_nothing():
         ctx.rfi_flag_freq(xd, w=wd[:, :2].contiguous())
     with pytest.raises(ValueError):
         ctx.rfi_flag_freq(xd, out=(wd, wd, wd, wd))
+    # a tensor on the host is refused before anything is launched
+    xs, ws = ctx.to_device(np.ones((2, 3, 8), dtype=np.complex128)), ctx.to_device(np.ones((2, 3, 8)))
+    with pytest.raises(ValueError, match="one GPU"):
+        ctx.rfi_flag_freq(xs, w=ws.cpu())
     empty = ctx.rfi_flag_freq(xd[:, :0].contiguous())
     assert tuple(empty[0].shape) == (nf, 0, nt) and tuple(empty[2].shape) == (0, nt)
 
@@ -345,6 +349,11 @@ def test_dilation_refusals_launch_nothing():
         ctx.rfi_dilate(wd, 0.2, ref=rd[:, :2].contiguous())
     with pytest.raises(ValueError):
         ctx.rfi_dilate(wd, 0.2, out=(wd, wd))
+    # a tensor on the host is refused before anything is launched
+    ws = ctx.to_device(np.ones((2, 3, 8)))
+    for axis in ("time", "freq"):
+        with pytest.raises(ValueError, match="one GPU"):
+            ctx.rfi_dilate(ws, 0.2, axis=axis, ref=ws.cpu())
     # the length limit is inclusive; nothing to do is not refused
     edge = ctx.rfi_dilate(long_t[:, :, :tmax].contiguous(), 0.2)
     assert not ctx.to_host(edge[1]).any()

@@ -240,6 +240,10 @@ def test_refusals_leave_the_outputs_alone():
                 lambda: ctx.sidereal_regrid(x, p, d, ntime, acc=(acc[0], acc[1], acc[2], acc[2]))):
         with pytest.raises(ValueError):
             bad()
+    # a tensor on the host is refused before anything is launched
+    xs, ws = ctx.to_device(np.ones((2, 3, 8), dtype=np.complex128)), ctx.to_device(np.ones((2, 3, 8)))
+    with pytest.raises(ValueError, match="one GPU"):
+        ctx.sidereal_regrid(xs, p, d, ntime, w=ws.cpu())
     # zero sizes with accumulate != 0 touch nothing
     assert rc(nf=0, accumulate=1) == 0 and rc(nrow_=0, accumulate=1) == 0 and rc(nt_in=0, accumulate=1) == 0
     ctx.sync()
