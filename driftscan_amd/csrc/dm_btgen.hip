@@ -1199,6 +1199,16 @@ static bool bt_ring_plan_make(int nside, int P, int cnt, int ncol, bt_ring_plan&
 
 }  // namespace
 
+// argument checks of the pixel-stage entry points: the message names the entry point, and every check stands before the
+// first upload (an upload is a copy in the stream), so a refused call launches nothing
+#define BT_ARG(ctx, cond)                                                              \
+  do {                                                                                 \
+    if (!(cond)) {                                                                     \
+      (ctx)->err = std::string(__func__) + ": bad argument: " + #cond;                 \
+      return DM_EARG;                                                                  \
+    }                                                                                  \
+  } while (0)
+
 extern "C" {
 
 // Cylinder field pattern on the pixel centres of a HEALPix map.
@@ -1211,7 +1221,7 @@ int dm_bt_beam_cyl(dm_ctx* ctx, int nside, const double* ring_cth_host, const do
                    const double* frame_host, int kind, const double* tab_x_host, const double* tab_y_host,
                    const double* tab_y2_host, int ntab, double fwhm_ns, double* out_dev) {
   if (!ctx) return DM_EARG;
-  DM_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && kind >= 0 && kind <= 2 && tab_x_host &&
+  BT_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && kind >= 0 && kind <= 2 && tab_x_host &&
                   tab_y_host && tab_y2_host && ntab >= 2 && out_dev);
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
   const size_t mark = ws_scope__.mark;
@@ -1241,17 +1251,19 @@ int dm_bt_beams_cyl(dm_ctx* ctx, int nside, const double* ring_cth_host, const d
                     const double* tab_y_host, const double* tab_y2_host, const int* tab_off_host,
                     const double* fwhm_ns_host, double* out_dev, size_t out_stride) {
   if (!ctx) return DM_EARG;
-  DM_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && nbeam >= 0 && kind_host && tab_x_host &&
+  BT_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && nbeam >= 0 && kind_host && tab_x_host &&
                   tab_y_host && tab_y2_host && tab_off_host && fwhm_ns_host && out_dev);
   if (nbeam == 0) return DM_OK;
+  const size_t npix = 12 * (size_t)nside * (size_t)nside;
+  BT_ARG(ctx, tab_off_host[0] >= 0);
+  for (int b = 0; b < nbeam; ++b) {
+    BT_ARG(ctx, kind_host[b] >= 0 && kind_host[b] <= 2 && tab_off_host[b + 1] - tab_off_host[b] >= 2);
+    BT_ARG(ctx, out_stride >= npix * (kind_host[b] == 0 ? 1 : 2));
+  }
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
   geo_host gh;
   DM_TRY(upload_geo(ctx, nside, ring_cth_host, ring_sth_host, gh));
   const int ntot = tab_off_host[nbeam];
-  for (int b = 0; b < nbeam; ++b) {
-    DM_ARG(ctx, kind_host[b] >= 0 && kind_host[b] <= 2 && tab_off_host[b + 1] - tab_off_host[b] >= 2);
-    DM_ARG(ctx, out_stride >= (size_t)gh.g.npix * (kind_host[b] == 0 ? 1 : 2));
-  }
   std::vector<double> tabs(3 * (size_t)ntot);
   std::memcpy(tabs.data(), tab_x_host, sizeof(double) * ntot);
   std::memcpy(tabs.data() + ntot, tab_y_host, sizeof(double) * ntot);
@@ -1281,9 +1293,11 @@ int dm_bt_maps(dm_ctx* ctx, int nside, const double* ring_cth_host, const double
                const double* frame_host, int polarised, int nbeam, const double* beams_dev, int ncol,
                const double* uv_host, const int* bi_host, const int* bj_host, void* maps_dev) {
   if (!ctx) return DM_EARG;
-  DM_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && nbeam > 0 && beams_dev && ncol >= 0 &&
+  BT_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && nbeam > 0 && beams_dev && ncol >= 0 &&
                   uv_host && bi_host && bj_host && maps_dev);
   if (ncol == 0) return DM_OK;
+  for (int c = 0; c < ncol; ++c)
+    BT_ARG(ctx, bi_host[c] >= 0 && bi_host[c] < nbeam && bj_host[c] >= 0 && bj_host[c] < nbeam);
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
   const size_t mark = ws_scope__.mark;
   geo_host gh;
@@ -1294,7 +1308,6 @@ int dm_bt_maps(dm_ctx* ctx, int nside, const double* ring_cth_host, const double
   double* omega = dm_ws_alloc_t<double>(ctx, nbeam);
   std::vector<double> uv(uv_host, uv_host + 2 * (size_t)ncol);
   std::vector<int> bi(bi_host, bi_host + ncol), bj(bj_host, bj_host + ncol);
-  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, bi[c] >= 0 && bi[c] < nbeam && bj[c] >= 0 && bj[c] < nbeam);
   double* duv = dm_ws_upload(ctx, uv);
   int* dbi = dm_ws_upload(ctx, bi);
   int* dbj = dm_ws_upload(ctx, bj);
@@ -1313,9 +1326,11 @@ int dm_bt_maps_c(dm_ctx* ctx, int nside, const double* ring_cth_host, const doub
                  const double* frame_host, int polarised, int nbeam, const void* beams_dev, int ncol,
                  const double* uv_host, const int* bi_host, const int* bj_host, void* maps_dev) {
   if (!ctx) return DM_EARG;
-  DM_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && nbeam > 0 && beams_dev && ncol >= 0 &&
+  BT_ARG(ctx, nside > 0 && ring_cth_host && ring_sth_host && frame_host && nbeam > 0 && beams_dev && ncol >= 0 &&
                   uv_host && bi_host && bj_host && maps_dev);
   if (ncol == 0) return DM_OK;
+  for (int c = 0; c < ncol; ++c)
+    BT_ARG(ctx, bi_host[c] >= 0 && bi_host[c] < nbeam && bj_host[c] >= 0 && bj_host[c] < nbeam);
   dm_ws_scope ws_scope__(ctx);  // releases on every return path
   geo_host gh;
   DM_TRY(upload_geo(ctx, nside, ring_cth_host, ring_sth_host, gh));
@@ -1325,7 +1340,6 @@ int dm_bt_maps_c(dm_ctx* ctx, int nside, const double* ring_cth_host, const doub
   double* omega = dm_ws_alloc_t<double>(ctx, nbeam);
   std::vector<double> uv(uv_host, uv_host + 2 * (size_t)ncol);
   std::vector<int> bi(bi_host, bi_host + ncol), bj(bj_host, bj_host + ncol);
-  for (int c = 0; c < ncol; ++c) DM_ARG(ctx, bi[c] >= 0 && bi[c] < nbeam && bj[c] >= 0 && bj[c] < nbeam);
   double* duv = dm_ws_upload(ctx, uv);
   int* dbi = dm_ws_upload(ctx, bi);
   int* dbj = dm_ws_upload(ctx, bj);
