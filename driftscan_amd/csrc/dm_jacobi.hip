@@ -37,7 +37,8 @@ namespace {
 constexpr int JB = 32;       // rows per block
 constexpr int JP = 64;       // rows per pair
 constexpr int GP = 65;       // LDS pitch (complex elements) of the 64x64 inner matrices
-constexpr int JNT = 1024;    // threads of jac_inner: 2 waves/SIMD hide the LDS latency of the rotation updates (1 WG/CU fits)
+constexpr int JNT = 512;     // threads of jac_inner: G alone is in LDS (Q rides in registers), so two workgroups share a CU
+constexpr int JNW = 4;       // waves per SIMD that jac_inner is compiled for: two workgroups of JNT threads -> 128 VGPRs each
 constexpr int QP = 80;       // LDS pitch (doubles) of the Q^H planes in jac_apply
 constexpr int XP = 17;       // LDS pitch (doubles) of the gram staging planes
 
@@ -221,8 +222,40 @@ __global__ __launch_bounds__(256) void jac_gram_kernel(const jac_item* __restric
 // offmax[prob] receives (atomicMax on the bit pattern of a non-negative double)
 // the largest relative off-diagonal |g_ij| / sqrt(g_ii g_jj) seen *before* the
 // solve: the sweep-level convergence measure.
+//
+// Storage.  G (64 x 65 complex, 66 560 B) is the only matrix in LDS.  Q never mixes rows: in the update Q <- Q J the
+// 32 lanes of a half-wave own one row of Q for the whole solve, lane t holding the two columns (p_t, q_t) of its pair.
+// With the pairing used here (t = 0: (63, step); t >= 1: p = (step + t) % 63, q = (step + 63 - t) % 63) the columns a
+// lane needs move by one lane per step,
+//     newP[t] = oldP[t + 1] (1 <= t <= 30)   newP[31] = oldQ[31]   newP[0] = oldP[0]  (column 63 stays)
+//     newQ[t] = oldQ[t - 1] (t >= 1)         newQ[0]  = oldP[1]
+// a ring of 63 values that is back where it started after the 63 steps of a sweep.  So Q lives in registers (four rows
+// per thread), is rotated with the (c, s phase) of the lane's own pair and handed on by a lane shift that every lane
+// executes on every step.  Two workgroups then fit a CU (LDS 2 x 67 664 B of 160 KB, 128 VGPRs at four waves per SIMD), and one
+// fills the barrier waits of the other.
+
+// value of the next / previous lane of the wave (DPP wave shift by one; the lane past the end reads 0)
+__device__ __forceinline__ double lane_next(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, true);  // wave_shl:1
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double lane_prev(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);  // wave_shr:1
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
+// rotation of one pair as phase A leaves it in LDS: one address per pair for its three readers
+struct jac_rot {
+  cplx sp;   // sin * phase
+  double c;  // cos
+  int act;   // pair rotates in this step
+  int pad;
+};
+
 template <bool HERM>
-__global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restrict__ items,
+__global__ __launch_bounds__(JNT, JNW) void jac_inner_kernel(const jac_item* __restrict__ items,
                                                         const int* __restrict__ active,
                                                         const double* __restrict__ absfloor_p,
                                                         const cplx* __restrict__ Gbuf, cplx* __restrict__ Qbuf,
@@ -232,18 +265,16 @@ __global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restri
                                                         int* __restrict__ blk_ok) {
   extern __shared__ __align__(16) unsigned char smem[];
   cplx* G = reinterpret_cast<cplx*>(smem);
-  cplx* Q = G + JP * GP;
-  double* rc = reinterpret_cast<double*>(Q + JP * GP);  // [32] cos
-  cplx* rs = reinterpret_cast<cplx*>(rc + 32);           // [32] sin * phase
-  int* ctl = reinterpret_cast<int*>(rs + 32);            // [0] rotations this sweep, [1..32] pair active
-  double* red = reinterpret_cast<double*>(ctl + 40);     // [4] reduction scratch
+  jac_rot* rot = reinterpret_cast<jac_rot*>(G + JP * GP);  // [32] the rotations of the step
+  double* red = reinterpret_cast<double*>(rot + 32);       // [JNT / 64] reduction scratch
+  int* ctl = reinterpret_cast<int*>(red + JNT / 64);       // [0] rotations this sweep, [1] another sweep needed
 
   const jac_item it = items[blockIdx.x];
   if (!active[it.prob]) return;
   const int tid = threadIdx.x;
   const double absfloor = absfloor_p ? absfloor_p[it.prob] : 0.0;
 
-  // ---- load G (Hermitian by construction), Q = I
+  // ---- load G (Hermitian by construction)
   for (int idx = tid; idx < JP * JP; idx += JNT) {
     int r = idx >> 6, c = idx & 63;
     cplx v;
@@ -255,7 +286,6 @@ __global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restri
       v = Gbuf[(size_t)it.q * JP * JP + idx];
     }
     G[r * GP + c] = v;
-    Q[r * GP + c] = make_double2(r == c ? 1.0 : 0.0, 0.0);
   }
   __syncthreads();
   if (HERM) {
@@ -303,9 +333,25 @@ __global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restri
   }
   if (mo <= tol_outer || measure_only) return;  // uniform across the block
 
+  // ---- Q = I in the assignment of step 0: lane 0 holds columns (63, 0), lane t holds (t, 63 - t); thread `tid` owns
+  //      the rows (tid >> 5) + 16 i
+  const int qt = tid & 31, qr = tid >> 5;
+  const int qc0 = qt == 0 ? 63 : qt, qc1 = qt == 0 ? 0 : 63 - qt;
+  cplx qp[4], qq[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    qp[i] = make_double2(qr + 16 * i == qc0 ? 1.0 : 0.0, 0.0);
+    qq[i] = make_double2(qr + 16 * i == qc1 ? 1.0 : 0.0, 0.0);
+  }
+  // the 496 block pairs ta < tb of the G update, dense over the first 496 threads: rows k and 30 - k of the strict upper
+  // triangle (31 - k and k + 1 entries) share the 32 threads of half-wave k
+  const int gk = tid >> 5;
+  const int gta = qt < 31 - gk ? gk : 30 - gk;
+  const int gtb = qt < 31 - gk ? gk + 1 + qt : qt;
+
   // ---- cyclic Jacobi, 63 parallel steps of 32 disjoint rotations per sweep
   for (int sweep = 0; sweep < 24; ++sweep) {
-    if (tid == 0) { ctl[0] = 0; ctl[33] = 0; }
+    if (tid == 0) { ctl[0] = 0; ctl[1] = 0; }
     __syncthreads();
     for (int step = 0; step < 63; ++step) {
       // phase A: rotation parameters
@@ -329,9 +375,9 @@ __global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restri
           sp = make_double2(s * g.x / ag, s * g.y / ag);  // s * phase
           act = 1;
         }
-        rc[tid] = c;
-        rs[tid] = sp;
-        ctl[1 + tid] = act;
+        rot[tid].sp = sp;
+        rot[tid].c = c;
+        rot[tid].act = act;
         if (act) ctl[0] = 1;  // benign race: all writers store 1
       }
       __syncthreads();
@@ -344,36 +390,33 @@ __global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restri
         if (t == 0) { pp = 63; qq = step; }
         else { pp = (step + t) % 63; qq = (step + 63 - t) % 63; }
       };
-#pragma unroll 2
-      for (int i = 0; i < 1024 / JNT; ++i) {
-        const int u = tid + JNT * i;
-        const int ta = u >> 5, tb = u & 31;
-        if (ta > tb) continue;
-        const int aa = ctl[1 + ta], ab = ctl[1 + tb];
-        if (!aa && !ab) continue;
+      if (tid < 32 && rot[tid].act) {
+        // diagonal block of an active pair, on the lane that set the rotation up: it annihilates the off-diagonal element
+        int pa, qa;
+        pair_of(tid, pa, qa);
+        const double ca = rot[tid].c;
+        const cplx sa = rot[tid].sp;
+        const cplx gpp = G[pa * GP + pa], gqq = G[qa * GP + qa], gpq = G[pa * GP + qa];
+        // (J^H X J)_pp = c^2 gpp + |s|^2 gqq - 2 c Re(conj(sp) ... ) — formed through the two half steps
+        // X1 = X J (columns), X2 = J^H X1 (rows), keeping only the real diagonal
+        const cplx gqp = make_double2(gpq.x, -gpq.y);
+        const cplx x_pp = csub(cscale(gpp, ca), cmulc(gpq, sa));   // c gpp - conj(sp) gpq
+        const cplx x_pq = cadd(cmul(sa, gpp), cscale(gpq, ca));     // sp gpp + c gpq
+        const cplx x_qp = csub(cscale(gqp, ca), cmulc(gqq, sa));   // c gqp - conj(sp) gqq
+        const cplx x_qq = cadd(cmul(sa, gqp), cscale(gqq, ca));     // sp gqp + c gqq
+        const cplx n_pp = csub(cscale(x_pp, ca), cmul(sa, x_qp));   // c x_pp - sp x_qp
+        const cplx n_qq = cadd(cmulc(x_pq, sa), cscale(x_qq, ca));  // conj(sp) x_pq + c x_qq
+        G[pa * GP + pa] = make_double2(n_pp.x, 0.0);
+        G[qa * GP + qa] = make_double2(n_qq.x, 0.0);
+        G[pa * GP + qa] = make_double2(0.0, 0.0);
+        G[qa * GP + pa] = make_double2(0.0, 0.0);
+      }
+      if (tid < 496 && (rot[gta].act | rot[gtb].act)) {
         int pa, qa, pb, qb;
-        pair_of(ta, pa, qa);
-        pair_of(tb, pb, qb);
-        const double ca = rc[ta], cb = rc[tb];
-        const cplx sa = rs[ta], sb = rs[tb];
-        if (ta == tb) {
-          // diagonal block of an active pair: the rotation annihilates the off-diagonal element
-          const cplx gpp = G[pa * GP + pa], gqq = G[qa * GP + qa], gpq = G[pa * GP + qa];
-          // (J^H X J)_pp = c^2 gpp + |s|^2 gqq - 2 c Re(conj(sp) ... ) — formed through the two half steps
-          // X1 = X J (columns), X2 = J^H X1 (rows), keeping only the real diagonal
-          const cplx gqp = make_double2(gpq.x, -gpq.y);
-          const cplx x_pp = csub(cscale(gpp, ca), cmulc(gpq, sa));   // c gpp - conj(sp) gpq
-          const cplx x_pq = cadd(cmul(sa, gpp), cscale(gpq, ca));     // sp gpp + c gpq
-          const cplx x_qp = csub(cscale(gqp, ca), cmulc(gqq, sa));   // c gqp - conj(sp) gqq
-          const cplx x_qq = cadd(cmul(sa, gqp), cscale(gqq, ca));     // sp gqp + c gqq
-          const cplx n_pp = csub(cscale(x_pp, ca), cmul(sa, x_qp));   // c x_pp - sp x_qp
-          const cplx n_qq = cadd(cmulc(x_pq, sa), cscale(x_qq, ca));  // conj(sp) x_pq + c x_qq
-          G[pa * GP + pa] = make_double2(n_pp.x, 0.0);
-          G[qa * GP + qa] = make_double2(n_qq.x, 0.0);
-          G[pa * GP + qa] = make_double2(0.0, 0.0);
-          G[qa * GP + pa] = make_double2(0.0, 0.0);
-          continue;
-        }
+        pair_of(gta, pa, qa);
+        pair_of(gtb, pb, qb);
+        const double ca = rot[gta].c, cb = rot[gtb].c;
+        const cplx sa = rot[gta].sp, sb = rot[gtb].sp;
         const cplx g00 = G[pa * GP + pb], g01 = G[pa * GP + qb], g10 = G[qa * GP + pb], g11 = G[qa * GP + qb];
         // columns: [x0 x1] = [g0 g1] J_B
         const cplx x00 = csub(cscale(g00, cb), cmulc(g01, sb)), x01 = cadd(cmul(sb, g00), cscale(g01, cb));
@@ -387,18 +430,26 @@ __global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restri
         G[pb * GP + qa] = make_double2(n10.x, -n10.y);
         G[qb * GP + qa] = make_double2(n11.x, -n11.y);
       }
-#pragma unroll 2
-      for (int i = 0; i < 2048 / JNT; ++i) {
-        int u = tid + JNT * i;
-        int t = u & 31, r = u >> 5;
-        if (!ctl[1 + t]) continue;
-        int pp, qq;
-        pair_of(t, pp, qq);
-        double c = rc[t];
-        cplx sp = rs[t];
-        cplx qp = Q[r * GP + pp], qv = Q[r * GP + qq];
-        Q[r * GP + pp] = csub(cscale(qp, c), cmulc(qv, sp));
-        Q[r * GP + qq] = cadd(cmul(sp, qp), cscale(qv, c));
+      // Q <- Q J on the two columns this lane holds (an inactive pair leaves them as they are) ...
+      if (rot[qt].act) {
+        const double c = rot[qt].c;
+        const cplx sp = rot[qt].sp;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const cplx vp = qp[i], vq = qq[i];
+          qp[i] = csub(cscale(vp, c), cmulc(vq, sp));
+          qq[i] = cadd(cmul(sp, vp), cscale(vq, c));
+        }
+      }
+      // ... then the ring moves one lane: every lane, every step, outside any branch
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const cplx fromnext = make_double2(lane_next(qp[i].x), lane_next(qp[i].y));  // oldP[t + 1]
+        const cplx fromprev = make_double2(lane_prev(qq[i].x), lane_prev(qq[i].y));  // oldQ[t - 1]
+        const cplx np = qt == 0 ? qp[i] : (qt == 31 ? qq[i] : fromnext);
+        const cplx nq = qt == 0 ? fromnext : fromprev;
+        qp[i] = np;
+        qq[i] = nq;
       }
       __syncthreads();
     }
@@ -417,18 +468,20 @@ __global__ __launch_bounds__(JNT) void jac_inner_kernel(const jac_item* __restri
           if (ag > 0.0 && ag > absfloor && ag > tol_inner * sqrt(fabs(G[r * GP + r].x * G[c * GP + c].x))) need = true;
         }
       }
-      if (need) ctl[33] = 1;  // benign race: all writers store 1
+      if (need) ctl[1] = 1;  // benign race: all writers store 1
     }
     __syncthreads();
-    const int go = ctl[33];
+    const int go = ctl[1];
     __syncthreads();
     if (!go) break;
   }
 
   cplx* Qo = Qbuf + (size_t)it.q * JP * JP;
-  for (int idx = tid; idx < JP * JP; idx += JNT) {
-    int r = idx >> 6, c = idx & 63;
-    Qo[idx] = Q[r * GP + c];
+  // the ring is back in the assignment of step 0 (the loops above leave between sweeps only)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    Qo[(qr + 16 * i) * JP + qc0] = qp[i];
+    Qo[(qr + 16 * i) * JP + qc1] = qq[i];
   }
 }
 
@@ -719,8 +772,10 @@ void tournament(int nb, std::vector<std::vector<std::pair<int, int>>>& rounds) {
   }
 }
 
-constexpr size_t INNER_LDS = (size_t)2 * JP * GP * sizeof(cplx) + 32 * sizeof(double) + 32 * sizeof(cplx) +
-                             40 * sizeof(int) + 4 * sizeof(double) + 64 + 16 * sizeof(double);  // + room for JNT / 64 reduction slots
+// G, the 32 rotations, red, ctl: 67 664 B, two workgroups in the 160 KB of a CU
+constexpr size_t INNER_LDS = (size_t)JP * GP * sizeof(cplx) + 32 * sizeof(jac_rot) + (JNT / 64) * sizeof(double) +
+                             4 * sizeof(int);
+static_assert(INNER_LDS <= 80 * 1024, "two jac_inner workgroups must fit the LDS of a CU");
 constexpr size_t APPLY_LDS = (size_t)2 * JP * QP * sizeof(double);
 
 bool g_attr_set = false;
@@ -732,6 +787,14 @@ int set_attrs(dm_ctx* ctx) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)INNER_LDS));
   DM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(jac_apply_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)APPLY_LDS));
+  if (getenv("DM_DEBUG")) {
+    // the pair solver is built for two workgroups per CU: say once what the runtime grants
+    int occ_rows = 0, occ_herm = 0;
+    DM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_rows, jac_inner_kernel<false>, JNT, INNER_LDS));
+    DM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_herm, jac_inner_kernel<true>, JNT, INNER_LDS));
+    fprintf(stderr, "[dm_jacobi] jac_inner workgroups per CU: rows %d, herm %d (%d threads, %zu B LDS)\n", occ_rows,
+            occ_herm, JNT, INNER_LDS);
+  }
   g_attr_set = true;
   return DM_OK;
 }
